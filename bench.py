@@ -14,7 +14,10 @@ Launch: ``python bench.py --gpus N``.  With N > 1 and no WORLD_SIZE in the envir
 process only spawns ``python -m torch.distributed.run --nproc-per-node N ... bench.py`` (it never
 touches a GPU itself) and forwards the child's output; under torchrun it is one rank.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).  A plain run sets up, warms up, times the
+``--steps`` passes and prints the headline (``value``, ``ms_per_step``, ...); ``--full`` adds everything else the line can carry
+(shard / all-gather decomposition, selfcheck, secondary precisions, the 256-chunk shard, roofline legs, the Q-former and drop-in
+module legs, CPU baselines).  ``--dump-outputs DIR`` writes what the last timed pass returned as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -58,10 +61,19 @@ def parse():
     ap.add_argument("--no-encode-video", action="store_true", help="skip the secondary per-chunk Q-former leg")
     ap.add_argument("--no-selfcheck", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (split-bf16 V' projection, bf16 frame tokens)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline also run the selfcheck, the secondary lines, the shard / roofline / Q-former / "
+                         "drop-in module legs and the CPU baseline (the --no-* options above switch legs of --full off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (a seeded sample of the per-chunk outputs, "
+                         "the gathered memory) as DIR/<name>.npy, float32, rank 0")
     ap.add_argument("--stub-engine", action="store_true",
                     help="TEST HOOK (tests/test_sharding_cpu.py): run the rank body on the CPU over gloo with a stand-in engine "
                          "-- launch, sharding, collective, max-over-ranks clock and the one JSON line, no GPU, no numbers worth reading")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(n: int) -> int:
@@ -356,6 +368,29 @@ def module_forward_us(dev, k):
 
 
 # ----------------------------------------------------------------------------------------------------------
+DUMP_SEED, DUMP_CTX_CHUNKS, DUMP_MAX_BYTES = 0, 128, 64 << 20
+
+
+def dump_outputs(out_dir: str, ctx, mem) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files.  ctx [C, L, Q, dm] of the rank is
+    403 MB at the headline shape, so a fixed sample of its chunks is written (the first, the last and DUMP_CTX_CHUNKS drawn
+    with DUMP_SEED; their ids in ctx_chunks.npy); the gathered memory (every rank's B, bin masses, output sum, count) is
+    written whole."""
+    import numpy as np
+    c = int(ctx.shape[0])
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(np.concatenate([[0, c - 1], rng.choice(c, size=min(DUMP_CTX_CHUNKS, c), replace=False)]))
+    arrays = {"ctx_chunks": idx.astype(np.float32), "ctx": ctx[idx.tolist()],
+              "memory_B": mem.B, "memory_bin_mass": mem.bin_mass, "memory_ctx_sum": mem.ctx_sum, "memory_count": mem.count}
+    arrays = {name: (a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()).astype(np.float32) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def selfcheck(eng_cls, dev, k, q, projs, u, ctx_timed, trace, batch_chunks):
     """Compare the timed path (one consolidate call over the whole block) with the per-chunk forward chain.
     (1) first 24 chunks from scratch: forward() per chunk, its draw forced to the timed run's recorded bins so that a
@@ -519,16 +554,24 @@ def main():
         ctx, mem = one_step()
     fence()
     elapsed = time.perf_counter() - t0
-    # shard / all-gather split of a step: a separate short pass (its extra device-wide sync behind the collective is not part of
-    # the timed region above, so a multi-GPU run overlaps step i's all-gather with step i+1's consolidation as a caller would)
-    for _ in range(min(5, args.steps)):
-        one_step(tim)
-    fence()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, mem)
+    if args.full:
+        # shard / all-gather split of a step: a separate short pass (its extra device-wide sync behind the collective is not part
+        # of the timed region above, so a multi-GPU run overlaps step i's all-gather with step i+1's consolidation as a caller would)
+        for _ in range(min(5, args.steps)):
+            one_step(tim)
+        fence()
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     assert bool(torch.isfinite(ctx).all()), "non-finite consolidation output"
+
+    def emit(out):
+        real_stdout.write(json.dumps(out) + "\n")
+        real_stdout.flush()
+
     if stub:
         # the plumbing line of a --stub-engine run: same keys as the real one where they exist without a GPU
         if rank == 0:
@@ -536,10 +579,47 @@ def main():
                    "value": args.chunks * args.steps / elapsed, "unit": "frame-chunks/s", "n_gpus": world, "steps": args.steps,
                    "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong",
                    "config": {"chunks": args.chunks, "chunks_per_gpu": c_local},
-                   "gathered_counts": [float(x) for x in mem.count],
-                   "shard_ms": 1e3 * tim["shard_s"] / tim["calls"], "allgather_ms": 1e3 * tim["allgather_s"] / tim["calls"]}
-            real_stdout.write(json.dumps(out) + "\n")
-            real_stdout.flush()
+                   "gathered_counts": [float(x) for x in mem.count]}
+            if tim.get("calls"):
+                out["shard_ms"] = 1e3 * tim["shard_s"] / tim["calls"]
+                out["allgather_ms"] = 1e3 * tim["allgather_s"] / tim["calls"]
+            emit(out)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    def headline():
+        value = args.chunks * args.steps / elapsed
+        v_split = os.environ.get("INFV_VPROJ_SPLIT", "0") not in ("", "0")
+        return {
+            "metric": "frame-chunks/sec consolidated (max_int=256, num_basis=256, d=768)",
+            "value": value, "unit": "frame-chunks/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32 (V' projection bf16x3)" if v_split else "f32", "data": "synthetic",
+            # every value is carried at full f32 precision everywhere.  The new-row projection GEMM multiplies f32 operands as exact
+            # three-piece bf16 splits (8 + 8 + 8 significand bits) -- six partial products, each exact, accumulated in f32 on the
+            # bf16 MFMA pipe: error against f64 at or below the f32-MFMA GEMM's (tests/test_ltm_gpu.py), same goldens, same drawn
+            # bins.  INFV_PROJ_X6=0 runs that GEMM as f32 MFMAs instead: timed by --full as secondary_proj_f32_mfma.
+            "dtype_detail": {"tokens": "f32", "pooling": "f32", "state_and_scores": "f32", "draw": "f32 cdf vs f64 uniforms (torch CPU semantics)",
+                             "projection_gemm": ("f32 MFMA" if os.environ.get("INFV_PROJ_X6", "") == "0" else
+                                                 "bf16x3-split operands (exact 24-bit), 6 MFMA products, f32 accumulate"),
+                             "value_projection": "bf16x3 (3 products)" if v_split else "same GEMM as the scores"},
+            "dtype_note": ("projection GEMM: f32 MFMA (INFV_PROJ_X6=0)" if os.environ.get("INFV_PROJ_X6", "") == "0" else
+                           "projection GEMM: f32 operands as exact 3-piece bf16 splits, 6 MFMA products, f32 accumulation (f32-accurate)"),
+            "config": {"workload": f"{args.chunks}-chunk synthetic video, max_int=256 frames x 32 tokens x 768, "
+                                   "num_basis=256, tau=0.75, sticky, 2 video-Q-former LTM layers, "
+                                   "Q=32 queries, LLM/Q-former stubbed (BASELINE configs[1]/[2])",
+                       "chunks": args.chunks, "chunks_per_gpu": c_local, "layer_steps_per_s": value * L,
+                       "parallelism": f"chunk-block sharding x{world} + 1 all-gather of consolidated memory"},
+            # every knob of the library / runtime that was set for this run (an empty list = the shipped defaults)
+            "env_overrides": sorted(f"{k_}={v_}" for k_, v_ in os.environ.items()
+                                    if k_.startswith("INFV_") or k_ in ("GPU_MAX_HW_QUEUES", "HIP_VISIBLE_DEVICES")),
+        }
+
+    if not args.full:
+        if rank == 0:
+            emit(headline())
         if world > 1:
             dist.destroy_process_group()
         return
@@ -799,34 +879,9 @@ def main():
         module_forward = module_forward_us(dev, k)
 
     if rank == 0:
-        value = args.chunks * args.steps / elapsed
-        v_split = os.environ.get("INFV_VPROJ_SPLIT", "0") not in ("", "0")
-        out = {
-            "metric": "frame-chunks/sec consolidated (max_int=256, num_basis=256, d=768)",
-            "value": value, "unit": "frame-chunks/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32 (V' projection bf16x3)" if v_split else "f32", "data": "synthetic",
-            # every value is carried at full f32 precision everywhere.  The new-row projection GEMM multiplies f32 operands as exact
-            # three-piece bf16 splits (8 + 8 + 8 significand bits) -- six partial products, each exact, accumulated in f32 on the
-            # bf16 MFMA pipe: error against f64 at or below the f32-MFMA GEMM's (tests/test_ltm_gpu.py), same goldens, same drawn
-            # bins.  INFV_PROJ_X6=0 runs that GEMM as f32 MFMAs instead: timed below as secondary_proj_f32_mfma.
-            "dtype_detail": {"tokens": "f32", "pooling": "f32", "state_and_scores": "f32", "draw": "f32 cdf vs f64 uniforms (torch CPU semantics)",
-                             "projection_gemm": ("f32 MFMA" if os.environ.get("INFV_PROJ_X6", "") == "0" else
-                                                 "bf16x3-split operands (exact 24-bit), 6 MFMA products, f32 accumulate"),
-                             "value_projection": "bf16x3 (3 products)" if v_split else "same GEMM as the scores"},
-            "dtype_note": ("projection GEMM: f32 MFMA (INFV_PROJ_X6=0)" if os.environ.get("INFV_PROJ_X6", "") == "0" else
-                           "projection GEMM: f32 operands as exact 3-piece bf16 splits, 6 MFMA products, f32 accumulation (f32-accurate)"),
-            "config": {"workload": f"{args.chunks}-chunk synthetic video, max_int=256 frames x 32 tokens x 768, "
-                                   "num_basis=256, tau=0.75, sticky, 2 video-Q-former LTM layers, "
-                                   "Q=32 queries, LLM/Q-former stubbed (BASELINE configs[1]/[2])",
-                       "chunks": args.chunks, "chunks_per_gpu": c_local, "layer_steps_per_s": value * L,
-                       "parallelism": f"chunk-block sharding x{world} + 1 all-gather of consolidated memory"},
-            "roofline": roofline,
-        }
-        # every knob of the library / runtime that was set for this run (an empty list = the shipped defaults)
-        out["env_overrides"] = sorted(f"{k_}={v_}" for k_, v_ in os.environ.items()
-                                      if k_.startswith("INFV_") or k_ in ("GPU_MAX_HW_QUEUES", "HIP_VISIBLE_DEVICES"))
+        out = headline()
+        value = out["value"]
+        out["roofline"] = roofline
         if check is not None:
             out["selfcheck"] = check
             out["selfcheck_max_abs_err"] = check["max_abs_err"]
@@ -871,8 +926,7 @@ def main():
             out["cpu_baseline"], out["cpu_closed_form"] = cpu_baselines(args.cpu_seconds)
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
             out["speedup_vs_cpu_closed_form"] = value / out["cpu_closed_form"]["value"]
-        real_stdout.write(json.dumps(out) + "\n")
-        real_stdout.flush()
+        emit(out)
     if world > 1:
         dist.destroy_process_group()
     if check is not None and not check["ok"]:

@@ -235,13 +235,14 @@ def test_bench_rank_body_end_to_end_with_a_stub_engine():
     """``python bench.py --gpus 2 --stub-engine``: the parent spawns two ranks through torch.distributed.run (127.0.0.1
     rendezvous), each shards the video, runs warm-up + timed steps through consolidate_video (gloo all-gather), the clock is the
     max over ranks and EXACTLY ONE JSON line appears on stdout, printed by rank 0, carrying the shard / all-gather decomposition
-    a SCALE line needs.  The engine is a stand-in (no GPU here); everything around it is the code the 8-GPU run executes."""
+    a SCALE line needs (``--full``: a plain run leaves the decomposition out).  The engine is a stand-in (no GPU here); everything
+    around it is the code the 8-GPU run executes."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--stub-engine", "--chunks", "6",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -250,3 +251,33 @@ def test_bench_rank_body_end_to_end_with_a_stub_engine():
     assert d["config"]["chunks"] == 6 and d["config"]["chunks_per_gpu"] == 3
     assert d["gathered_counts"] == [3.0, 3.0]                      # every rank's block arrived in the all-gather
     assert d["value"] > 0 and d["ms_per_step"] > 0 and d["shard_ms"] > 0 and d["allgather_ms"] >= 0
+
+
+def test_plain_bench_run_prints_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """``python bench.py --stub-engine --dump-outputs DIR`` without ``--full``: one JSON line with the headline keys and none of
+    the --full legs, and the last timed step's outputs as float32 .npy files (at most 64 MB) that are identical from run to run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--stub-engine", "--chunks", "5", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["higher_is_better"] is True
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "frame-chunks/s"
+        assert "shard_ms" not in line and "selfcheck" not in line and "cpu_baseline" not in line
+        files = {f.name: np.load(f) for f in sorted(d.glob("*.npy"))}
+        assert {"ctx.npy", "ctx_chunks.npy", "memory_B.npy", "memory_count.npy"} <= set(files)
+        assert all(a.dtype == np.float32 for a in files.values())
+        assert sum(f.stat().st_size for f in d.glob("*.npy")) <= 64 << 20
+        assert files["ctx.npy"].shape == (5, L, Q, DM) and files["ctx_chunks.npy"].tolist() == [0, 1, 2, 3, 4]
+        assert files["memory_count.npy"].tolist() == [5.0]
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        np.testing.assert_array_equal(a, dumps[1][name], err_msg=name)

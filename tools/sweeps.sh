@@ -187,7 +187,7 @@ r03o)
 # sub-batch size with the round-3 structure (fewer role-S launches per video vs longer pipeline fill)
 for bc in 42 56 63 84 42 28; do
   echo -n "batch-chunks $bc: "
-  python bench.py --steps 8 --warmup 2 --batch-chunks $bc --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
+  python bench.py --full --steps 8 --warmup 2 --batch-chunks $bc --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms_per_pass']
 print(round(d['value']), 'chunks/s wall', round(d['ms_per_step'],2), 'pool', k['pool'], 'project', k['project'], 'chain', k['chain'], 'uc', k['uc'])"
@@ -352,7 +352,7 @@ r04j)
 # longer sub-batches (fewer role-S launches) with and without long-lived pooling workgroups
 run() {  # $1 = batch chunks, rest = env
   bc=$1; shift
-  out=$(env "$@" python bench.py --steps 6 --warmup 2 --batch-chunks $bc --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
+  out=$(env "$@" python bench.py --full --steps 6 --warmup 2 --batch-chunks $bc --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms_per_pass']
 print(round(d['value']), 'chunks/s wall', round(d['ms_per_step'],2), 'pool', k['pool'], 'project', k['project'], 'chain', k['chain'], 'uc', k['uc'])")
@@ -391,7 +391,7 @@ r04l)
 for rep in 1 2; do
 tools/env_sweep.sh "INFV_PR_U=8" "INFV_PR_U=4" "INFV_PR_U=8 INFV_POOL_PRIO=1" "INFV_PR_U=4 INFV_POOL_PRIO=1" "INFV_PR_U=4 INFV_POOL_PRIO=1 INFV_UC_PRIO=2 INFV_ALPHA_PRIO=2" "INFV_PR_U=8 INFV_POOL_PRIO=1 INFV_UC_PRIO=2 INFV_ALPHA_PRIO=2" "INFV_PR_U=8 INFV_GEMM_SLICES=2" "INFV_POOL_ROWS=0"
 done 2>&1 | tee gpurun_out/sweep_r04l.txt
-INFV_LTM_LIBRARY= python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
+INFV_LTM_LIBRARY= python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('shipped library', round(d['value']), 'chunks/s', d['roofline']['kernel_ms_per_pass'])" | tee -a gpurun_out/sweep_r04l.txt
 python - <<'PY' | tee -a gpurun_out/sweep_r04l.txt
@@ -590,7 +590,7 @@ r05f)
 # more pooling seats (padding 44 / 56 KB, 40-register instantiation) with fewer role-S launches (84- / 126-chunk sub-batches)
 run() {  # $1 = batch chunks, rest = env
   bc=$1; shift
-  out=$(env "$@" python bench.py --steps 6 --warmup 2 --batch-chunks $bc --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
+  out=$(env "$@" python bench.py --full --steps 6 --warmup 2 --batch-chunks $bc --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms_per_pass']
 print(round(d['value']), 'chunks/s wall', round(d['ms_per_step'],2), 'pool', k['pool'], 'project', k['project'], 'chain', k['chain'], 'uc', k['uc'])")
@@ -627,7 +627,7 @@ done 2>&1 | tee gpurun_out/sweep_r05h.txt
 r05i)
 # sub-batch size of long calls, shipped library, same box alternating
 run() {
-  out=$(python bench.py --steps 8 --warmup 2 --batch-chunks $1 --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
+  out=$(python bench.py --full --steps 8 --warmup 2 --batch-chunks $1 --no-cpu-baseline --no-encode-video --no-selfcheck --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms_per_pass']
 print(round(d['value']), 'chunks/s wall', round(d['ms_per_step'],2), 'pool', k['pool'], 'project', k['project'], 'chain', k['chain'], 'uc', k['uc'])")
