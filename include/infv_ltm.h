@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define INFV_LTM_ABI_VERSION 5
+#define INFV_LTM_ABI_VERSION 6
 #define INFV_LTM_MAX_LAYERS 8
 
 typedef enum {
@@ -233,6 +233,28 @@ int infv_ltm_consolidate(infv_ltm_handle h, const void* k, int32_t n_chunks, int
 int infv_ltm_consolidate_pooled(infv_ltm_handle h, const float* kbar, int32_t n_chunks, int32_t T,
                                 const float* q, int32_t Q, const infv_ltm_proj* proj, const double* u,
                                 int32_t new_doc, float* ctx, void* stream);
+
+/* Several independent videos stepped together (ABI 6).  hs[V]: distinct handles with identical configuration (N, H, dh, d,
+ * P, L, S, sticky, token dtype) and the SAME plan for T (identical tables in infv_ltm_set_plan: same tau and num_basis).  Chunks are PACKED: video v owns chunks [cu[v], cu[v+1]) of
+ *   k   [cu[V], T*P, d]   (device, the handles' token dtype)
+ *   u   [cu[V], L, S]     float64 (device; may be NULL when not sticky)
+ *   ctx [cu[V], L, Q, dm] (device, output)
+ * q [L,Q,dm] and proj[L] are shared by every video and chunk (infv_ltm_consolidate's contract).  cu is a HOST array [V+1].
+ * new_doc = 1 resets every handle first; new_doc = 0 continues each handle's memory (every handle must hold one).  With
+ * new_doc = 0, cu[v+1] == cu[v] leaves video v untouched.  Afterwards each handle is in the state that infv_ltm_consolidate on
+ * its own chunks would have left it in, so export_state, get_draw, forward, ... keep working per video, and a handle with an
+ * armed trace (infv_ltm_set_trace) records its chunks' draws.
+ * The videos advance in lockstep, one chunk each per step: one launch per stage and step for all of them, a video index in every
+ * grid, nothing reduced across videos -- a video's results do not depend on the rest of the batch.  Per video the arithmetic is
+ * the per-call step's (infv_ltm_forward) except the new-row projection, which runs without split-K.  Shapes the lockstep kernels
+ * do not take (dense or psi plans, N above 256 or not a multiple of 16, S above 1024) run each handle's infv_ltm_consolidate in
+ * turn.  Everything is enqueued on `stream` (the video table travels in kernel arguments: no host buffer, capture-safe); no
+ * host synchronisation except workspace growth of the first handle, which owns the workspaces (one step of up to 256 videos:
+ * pooled frames, projected rows; more videos run in groups of 256).
+ * Refusals (INFV_ERR_INVALID: bad cu, duplicate handle, mismatched configuration or plan, missing u; INFV_ERR_NO_PLAN; INFV_ERR_STATE:
+ * new_doc = 0 on a handle without memory) leave every handle as it was. */
+int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const void* k, int32_t T, const float* q,
+                                int32_t Q, const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream);
 
 /* Consolidated memory of one layer: B_past [N,d] (long_term_attention_gibbs.py:220) and the
  * unnormalised sticky bin masses p[n_bins-1] derived from the last scores (:200-202).

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <new>
@@ -81,6 +82,7 @@ struct Plan {
     float w_out = 0.f;
     int n_bins = 0;
     bool points_ok = false;            // the histogram edges are the bins' left edges (what chain_batch3_kernel assumes)
+    uint64_t digest = 0;               // FNV-1a of every table infv_ltm_set_plan received (infv_ltm_consolidate_videos: same plan on every handle)
     StickyView sticky() const {
         StickyView s;
         s.points_ok = points_ok ? 1 : 0;
@@ -196,6 +198,7 @@ struct infv_ltm_s {
     DeviceBuf call_stats;              // call-long role S: [0] ticks (100 MHz) workgroup 0 waited for projections, [1] how many sub-batches it waited for
     hipEvent_t ev_chain = nullptr;     // the call-long role-S launch has finished (recorded on its stream)
     std::mutex* issue_mu = nullptr;    // the device's consolidate-issue lock (SharedStreams::issue)
+    DeviceBuf vid_tab, vid_kbar, vid_P;   // infv_ltm_consolidate_videos with this handle first: video table, pooled frames and projected rows of one step
     DeviceBuf mbox;                    // chain_batch3_kernel: mailboxes of role S's exchange + placement handshake (chain_mailbox_bytes)
     int mbox_G = 0;                    // workgroups per layer the mailboxes are laid out for
     int sc = 0;
@@ -577,6 +580,24 @@ int infv_ltm_set_plan(infv_ltm_handle h, const infv_ltm_plan* p) {
     for (int j = 0; j < p->n_bins; ++j) {
         if (p->bin_box[j] < 0) plan->points_ok = false;
         if (j > 0 && p->edge_box[j] != p->bin_box[j]) plan->points_ok = false;
+    }
+    {
+        uint64_t x = 1469598103934665603ull;
+        auto mix = [&x](const void* a, size_t bytes) {
+            const unsigned char* b = static_cast<const unsigned char*>(a);
+            for (size_t i = 0; i < bytes; ++i) { x ^= b[i]; x *= 1099511628211ull; }
+        };
+        const int32_t head[4] = {p->T, p->first_rows, p->inf_rows, p->n_bins};
+        mix(head, sizeof(head));
+        mix(p->first_row_box, p->first_rows * 4); mix(p->first_row_begin, p->first_rows * 4); mix(p->first_row_end, p->first_rows * 4);
+        mix(p->first_box_val, (size_t)h->N * 4);
+        mix(p->inf_row_box, p->inf_rows * 4); mix(p->inf_row_begin, p->inf_rows * 4); mix(p->inf_row_end, p->inf_rows * 4);
+        mix(p->inf_box_val, (size_t)h->N * 4);
+        mix(p->inf_old_ptr, (size_t)(h->N + 1) * 4); mix(p->inf_old_slot, (size_t)p->inf_old_ptr[h->N] * 4);
+        mix(p->readout_w, (size_t)h->N * 4); mix(&p->readout_w_out, 4);
+        mix(p->edge_box, (size_t)(p->n_bins + 1) * 4); mix(p->edge_dx, (size_t)p->n_bins * 4); mix(p->bin_box, (size_t)p->n_bins * 4);
+        mix(p->uniform_idx, (size_t)h->S * 4);
+        plan->digest = x;
     }
     hipError_t e = upload(plan->w, p->readout_w, h->N);
     if (e == hipSuccess) e = upload(plan->edge_box, p->edge_box, p->n_bins + 1);
@@ -1887,6 +1908,177 @@ int infv_ltm_consolidate_pooled(infv_ltm_handle h, const float* kbar, int32_t n_
                                 void* stream) {
     if (!kbar) return fail(INFV_ERR_INVALID, "consolidate_pooled: bad arguments");
     return consolidate_impl(h, nullptr, kbar, n_chunks, T, q, Q, proj, u, new_doc, ctx, stream);
+}
+
+}  // extern "C"
+
+// ---- several independent videos in lockstep ----------------------------------------------------------------------------
+// Step s advances every video that still has a chunk: ONE pooling, projection, draw, update and attend launch for all of them
+// (ltm_kernels.hip section 7), ordered by launch order on the caller's stream.  The state stays in the handles; the lead
+// handle (hs[0]) owns the call's workspaces: the video table and the pooled frames / projected rows of one step of at most
+// kVideoGroup videos.  Larger calls run their videos in groups of that size, one group after the other.
+namespace {
+constexpr int kVideoGroup = 256;
+
+bool same_config(infv_ltm_handle a, infv_ltm_handle b) {
+    return a->N == b->N && a->H == b->H && a->dh == b->dh && a->d == b->d && a->P == b->P && a->L == b->L && a->S == b->S &&
+           (a->cfg.sticky != 0) == (b->cfg.sticky != 0) && a->k_bf16 == b->k_bf16;
+}
+
+bool same_plan(const Plan& a, const Plan& b) {
+    return a.digest == b.digest && a.dense.on == b.dense.on && a.first.rows == b.first.rows && a.inf.rows == b.inf.rows &&
+           a.inf.tabw == b.inf.tabw && a.n_bins == b.n_bins && a.w_out == b.w_out;
+}
+}  // namespace
+
+extern "C" {
+
+int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const void* k_, int32_t T, const float* q,
+                                int32_t Q, const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream_) {
+    // ---- validation: nothing below changes a handle until every check has passed ----
+    if (!hs || !cu || V < 0) return fail(INFV_ERR_INVALID, "consolidate_videos: bad arguments");
+    if (V == 0) return INFV_OK;
+    if (cu[0] < 0) return fail(INFV_ERR_INVALID, "consolidate_videos: cu[0] = %d is negative", cu[0]);
+    for (int v = 0; v < V; ++v)
+        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "consolidate_videos: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)",
+                                            v, cu[v], v + 1, cu[v + 1]);
+    const int total = cu[V];
+    for (int v = 0; v < V; ++v) {
+        if (!hs[v]) return fail(INFV_ERR_INVALID, "consolidate_videos: handle %d is null", v);
+        for (int w = 0; w < v; ++w)
+            if (hs[w] == hs[v]) return fail(INFV_ERR_INVALID, "consolidate_videos: handle %d is also handle %d (a memory steps once per step)", v, w);
+        if (!same_config(hs[0], hs[v]))
+            return fail(INFV_ERR_INVALID, "consolidate_videos: handle %d's configuration (N, H, dh, d, P, L, S, sticky, token dtype) differs "
+                                          "from handle 0's", v);
+    }
+    if (total > 0 && (!k_ || !q || !proj || !ctx)) return fail(INFV_ERR_INVALID, "consolidate_videos: null argument");
+    infv_ltm_handle h0 = hs[0];
+    const bool sticky = h0->cfg.sticky != 0;
+    int max_len = 0;
+    for (int v = 0; v < V; ++v) max_len = cu[v + 1] - cu[v] > max_len ? cu[v + 1] - cu[v] : max_len;
+    if (sticky && !u && (new_doc ? max_len > 1 : total > 0))
+        return fail(INFV_ERR_INVALID, "consolidate_videos: sticky steps on an existing memory need the Gibbs uniforms u");
+    std::vector<Plan*> plans(V, nullptr);
+    for (int v = 0; v < V; ++v) {
+        infv_ltm_handle h = hs[v];
+        if (int rc = check_chain_error(h)) return rc;
+        if (int rc = check_q(h, Q)) return rc;
+        if (int rc = find_plan(h, T, &plans[v])) return rc;
+        if (!same_plan(*plans[0], *plans[v]))
+            return fail(INFV_ERR_INVALID, "consolidate_videos: handle %d's plan for T = %d differs from handle 0's (tau, num_basis or "
+                                          "the tables themselves): every video steps with one plan", v, T);
+        if (!new_doc && !h->has_memory)
+            return fail(INFV_ERR_STATE, "consolidate_videos: new_doc = 0 but handle %d holds no memory", v);
+        if (!new_doc && sticky && h->parts <= 0)
+            return fail(INFV_ERR_STATE, "consolidate_videos: handle %d has no sticky histogram (import_state or step first)", v);
+    }
+    if (new_doc)
+        for (int v = 0; v < V; ++v) infv_ltm_reset(hs[v]);
+    if (total == 0) return INFV_OK;
+    const char* k = static_cast<const char*>(k_);
+    const size_t chunk_k = (size_t)T * h0->P * h0->d * (h0->k_bf16 ? 2 : 4);
+    const size_t chunk_ctx = (size_t)h0->L * Q * h0->dm, chunk_u = (size_t)h0->L * h0->S;
+    bool batched = videos_supported(h0->N, h0->d, h0->dm, h0->L, h0->S);
+    batched = batched && !plans[0]->dense.on;
+    if (!batched) {
+        // shapes the lockstep kernels do not take (dense / psi plans, N above 256, ...): each video's own consolidate, in turn
+        for (int v = 0; v < V; ++v)
+            if (cu[v + 1] > cu[v])
+                if (int rc = infv_ltm_consolidate(hs[v], k + (size_t)cu[v] * chunk_k, cu[v + 1] - cu[v], T, q, Q, proj,
+                                                  u ? u + (size_t)cu[v] * chunk_u : nullptr, 0, ctx + (size_t)cu[v] * chunk_ctx,
+                                                  stream_)) return rc;
+        return INFV_OK;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const ProjPtrs pp = make_proj(proj, h0->L);
+    for (int v = 0; v < V; ++v)                    // the per-call step re-derives a stale K' half before stepping (infv_ltm_step)
+        if (cu[v + 1] > cu[v] && hs[v]->k_stale && hs[v]->has_memory)
+            if (int rc = infv_ltm_reproject(hs[v], proj, stream_)) return rc;
+    const Plan& plan = *plans[0];
+    const int N = h0->N, d = h0->d, dm = h0->dm, L = h0->L, S = h0->S;
+    const int rows_max = plan.first.rows > plan.inf.rows ? plan.first.rows : plan.inf.rows;
+    const int group = V < kVideoGroup ? V : kVideoGroup;
+    {   // workspaces of one step (grown, never shrunk; released with the lead handle)
+        const size_t need_t = (size_t)group * sizeof(VideoDesc);
+        const size_t need_k = (size_t)group * T * d * sizeof(float);
+        const size_t need_p = (size_t)group * (rows_max > 0 ? rows_max : 1) * L * 2 * dm * sizeof(float);
+        if (need_t > h0->vid_tab.bytes || need_k > h0->vid_kbar.bytes || need_p > h0->vid_P.bytes) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(h0->vid_tab.reserve(need_t));
+            HIP_TRY(h0->vid_kbar.reserve(need_k));
+            HIP_TRY(h0->vid_P.reserve(need_p));
+        }
+    }
+    const int mask_step = new_doc ? 1 : 0;
+    const int parts = attend_parts(Q, h0->H, N);
+    std::vector<VideoDesc> tab;
+    for (int g0 = 0; g0 < V; g0 += group) {
+        const int gn = V - g0 < group ? V - g0 : group;
+        // ranks by decreasing length: the videos still running at step s are ranks [0, n_s)
+        std::vector<int> order(gn);
+        for (int i = 0; i < gn; ++i) order[i] = g0 + i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cu[a + 1] - cu[a] > cu[b + 1] - cu[b]; });
+        tab.assign(gn, VideoDesc{});
+        int g_len = 0;
+        for (int j = 0; j < gn; ++j) {
+            infv_ltm_handle h = hs[order[j]];
+            VideoDesc& e = tab[j];
+            for (int i = 0; i < 2; ++i) { e.B[i] = h->B[i].as<float>(); e.KV[i] = h->KV[i].as<float>(); }
+            e.bin_part = h->bin_part[h->pc].as<float>();
+            e.probs = h->probs.as<float>(); e.bins = h->bins.as<int32_t>(); e.idx = h->idx.as<int32_t>(); e.scores = h->scores.as<float>();
+            e.probs_override = h->probs_override.as<float>(); e.bins_forced = h->bins_forced.as<int32_t>();
+            e.override_mask = h->override_mask; e.forced_mask = h->forced_mask;
+            e.trace_bins = h->trace_bins; e.trace_probs = h->trace_probs; e.trace_cap = h->trace_cap;
+            e.chunk0 = cu[order[j]];
+            e.cur0 = h->cur;
+            e.parts0 = new_doc ? parts : h->parts;
+            const int len = cu[order[j] + 1] - cu[order[j]];
+            g_len = len > g_len ? len : g_len;
+        }
+        // the table travels in kernel arguments (launch_video_table): no host buffer outlives the call, nothing waits on the host,
+        // and a captured graph holds its own copy; the group's launches and the next group's table write follow in stream order
+        HIP_TRY(launch_video_table(h0->vid_tab.as<VideoDesc>(), tab.data(), gn, stream));
+        int n = gn;
+        for (int s = 0; s < g_len; ++s) {
+            while (n > 0 && cu[order[n - 1] + 1] - cu[order[n - 1]] <= s) --n;
+            const bool inf = !(new_doc && s == 0);
+            const Operator& op = inf ? plan.inf : plan.first;
+            const VideoStep vs{h0->vid_tab.as<VideoDesc>(), s, n, mask_step};
+            {
+                Timed t_(h0->prof, INFV_KERNEL_POOL, stream);
+                HIP_TRY(launch_pool_videos(k, h0->k_bf16, vs, T, h0->P, d, h0->vid_kbar.as<float>(), stream));
+            }
+            {
+                Timed t_(h0->prof, INFV_KERNEL_PROJECT, stream);
+                HIP_TRY(launch_project_videos(h0->vid_kbar.as<float>(), n, T, d, dm, L, op.view(), pp, h0->vid_P.as<float>(), stream));
+            }
+            if (inf && sticky) {
+                Timed t_(h0->prof, INFV_KERNEL_DRAW, stream);
+                HIP_TRY(launch_draw_videos(vs, parts, plan.sticky(), u, S, L, stream));
+            }
+            {
+                Timed t_(h0->prof, INFV_KERNEL_UPDATE, stream);
+                HIP_TRY(launch_update_videos(vs, op.view(), N, T, d, dm, L, S, (inf && !sticky) ? plan.uniform_idx.as<int32_t>() : nullptr,
+                                             h0->vid_kbar.as<float>(), h0->vid_P.as<float>(), stream));
+            }
+            {
+                Timed t_(h0->prof, INFV_KERNEL_ATTEND, stream);
+                HIP_TRY(launch_attend_videos(vs, q, Q, N, h0->H, L, pp, plan.w.as<float>(), plan.w_out, plan.sticky(), ctx, stream));
+            }
+        }
+        for (int j = 0; j < gn; ++j) {             // the handles' host state after their chunks (chain_step's bookkeeping)
+            infv_ltm_handle h = hs[order[j]];
+            const int len = cu[order[j] + 1] - cu[order[j]];
+            if (len == 0) continue;
+            h->cur ^= len & 1;
+            h->has_memory = true;
+            h->parts = parts;
+            h->lastQ = Q;
+            h->last_fast = false;
+            if (sticky && len > mask_step) { h->override_mask = 0; h->forced_mask = 0; }
+        }
+    }
+    return INFV_OK;
 }
 
 }  // extern "C"

@@ -309,3 +309,45 @@ hipError_t launch_acc_to_part(const unsigned long long* acc, int n_layers, int p
 hipError_t launch_sum_parts(const float* bin_part_layer, int parts, int pitch, float* bin_mass, hipStream_t stream);
 
 }  // namespace infv
+
+namespace infv {
+// ---- several independent videos stepped in lockstep (infv_ltm_consolidate_videos) ----
+// One video of a multi-video call: its handle's state buffers and where its chunks sit in the packed k / u / ctx.
+struct VideoDesc {
+    float* B[2]; float* KV[2];        // the handle's ping-pong memory; slot cur0 holds it at the call's start
+    float* bin_part;                  // [L][parts][n_bins] sticky partials (read by the draw, rewritten by the attend)
+    float* probs; int32_t* bins; int32_t* idx; float* scores;   // diagnostics of the last step (infv_ltm_get_draw)
+    const float* probs_override; const int32_t* bins_forced;    // one-shot teacher forcing of the video's first draw
+    int32_t* trace_bins; float* trace_probs; long long trace_cap;   // draw trace (infv_ltm_set_trace) or nullptr
+    long long chunk0;                 // first chunk of the video in the packed arrays
+    int cur0;
+    unsigned override_mask, forced_mask;
+    int parts0;                       // partial rows per layer of bin_part at the video's first draw
+};
+// Step s of a multi-video call: the videos still running are ranks [0, n) of the table (sorted by decreasing length), and
+// video rank j's chunk of this step sits in slot j of the step's workspaces (pooled frames, projected rows).
+struct VideoStep {
+    const VideoDesc* vd;              // device table
+    int s, n;
+    int mask_step;                    // step of every video's first draw (where the one-shot masks apply)
+};
+// dst[0, n) = descs[0, n), written by kernels that carry kVideoTableChunk entries each in their arguments
+constexpr int kVideoTableChunk = 16;
+hipError_t launch_video_table(VideoDesc* dst, const VideoDesc* descs, int n, hipStream_t stream);
+// the shapes the multi-video kernels take: sparse plans of N <= 256 (multiple of 16), the 4-row attend tiles, S <= 1024
+bool videos_supported(int N, int d, int dm, int L, int S);
+// kbar[j][f][:] = mean over P tokens of frame f of video rank j's chunk of this step (k packed [chunks][T*P][d])
+hipError_t launch_pool_videos(const void* k, int k_bf16, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream);
+// Pnew[j * rows + r][l][kv][dm] = R(j, r) . W[l][kv]^T with the rows built from kbar[j] (no split-K: the summation order of an
+// element does not depend on how many videos share the launch)
+hipError_t launch_project_videos(const float* kbar, int n, int T, int d, int dm, int n_layers, const OperatorView& op,
+                                 const ProjPtrs& proj, float* Pnew, hipStream_t stream);
+hipError_t launch_draw_videos(const VideoStep& vs, int parts, const StickyView& sticky, const double* u, int S, int n_layers,
+                              hipStream_t stream);
+// idx_shared != nullptr: every video gathers through that table (non-sticky resampling); else through its own drawn idx
+hipError_t launch_update_videos(const VideoStep& vs, const OperatorView& op, int N, int T, int d, int dm, int n_layers, int S,
+                                const int32_t* idx_shared, const float* kbar, const float* Pnew, hipStream_t stream);
+hipError_t launch_attend_videos(const VideoStep& vs, const float* q, int Q, int N, int H, int n_layers, const ProjPtrs& proj,
+                                const float* readout_w, float readout_w_out, const StickyView& sticky, float* ctx,
+                                hipStream_t stream);
+}  // namespace infv

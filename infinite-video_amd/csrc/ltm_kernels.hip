@@ -431,6 +431,7 @@ constexpr int kLdsStride = kBK + 4;   // +1 access width (16 B) against ds_read_
 //   A[m][:] = sum_{f in [row_begin[m], row_end[m])} val_m * kbar[f][:]      (build_rows_kernel's fma chain, same bits)
 struct RowsA {
     const float* kbar; const int32_t* row_begin; const int32_t* row_end; const int32_t* row_box; const float* box_val;
+    int rpc; long cstride;      // GEMM row m is row m % rpc of the chunk whose frames start at kbar + (m / rpc) * cstride
 };
 
 template <int BM, int BN, bool ROWS>
@@ -457,8 +458,9 @@ __device__ inline void gemm_nt_tile(const float* __restrict__ A, const RowsA& ra
         const int m = m0 + row0 + 32 * i;
         fb[i] = fe[i] = 0; aval[i] = 0.f;
         if (ROWS) {
-            a_src[i] = ra.kbar + kbeg + c4 * 4;
-            if (m < M) { fb[i] = ra.row_begin[m]; fe[i] = ra.row_end[m]; aval[i] = ra.box_val[ra.row_box[m]]; }
+            const int mc = m / ra.rpc, mr = m - mc * ra.rpc;
+            a_src[i] = ra.kbar + mc * ra.cstride + kbeg + c4 * 4;
+            if (m < M) { fb[i] = ra.row_begin[mr]; fe[i] = ra.row_end[mr]; aval[i] = ra.box_val[ra.row_box[mr]]; }
         } else {
             a_src[i] = (m < M) ? A + (long)m * K + kbeg + c4 * 4 : nullptr;
         }
@@ -891,7 +893,7 @@ hipError_t launch_step_project(const float* kbar, int d, int dm, int n_layers, c
     *splitk = sk;
     if (M == 0 && draw.n_layers == 0) return hipSuccess;
     if (n_cols % 64 || (d / sk) % kBK) return hipErrorInvalidValue;
-    RowsA ra{kbar, op.row_begin, op.row_end, op.row_box, op.box_val};
+    RowsA ra{kbar, op.row_begin, op.row_end, op.row_box, op.box_val, M > 0 ? M : 1, 0};
     int gy = n_cols / 64;
     if (gy < draw.n_layers) gy = draw.n_layers;
     dim3 grid((M + 63) / 64 > 0 ? (M + 63) / 64 : 1, gy, sk + 1);
@@ -1014,16 +1016,16 @@ hipError_t launch_draw(const float* bin_part, int parts, const float* probs_over
 // 5. memory update: one workgroup per (box n, layer), three row families at once.
 //    next[n] = val_n * sum_{s in slots(n)} prev[idx[s]]  +  new row of box n
 // ======================================================================================
-__global__ __launch_bounds__(1024) void update_kernel(OperatorView op, int N, int d4, int dm4, int n_layers,
-                                                     int S, const int32_t* __restrict__ idx,
-                                                     int idx_layer_stride, const float* __restrict__ R,
-                                                     const float* __restrict__ Pnew, int splitk,
-                                                     long split_stride4,
-                                                     const float* __restrict__ B_prev,
-                                                     const float* __restrict__ KV_prev,
-                                                     float* __restrict__ B_next, float* __restrict__ KV_next,
-                                                     const float* __restrict__ kbar, const int32_t* __restrict__ tab) {
-    const int n = blockIdx.x, l = blockIdx.y;
+// (body shared with update_videos_kernel: workgroup (n, l) of one video's memory)
+__device__ __forceinline__ void update_body(int n, int l, const OperatorView& op, int N, int d4, int dm4, int n_layers,
+                                            const int32_t* __restrict__ idx,
+                                            int idx_layer_stride, const float* __restrict__ R,
+                                            const float* __restrict__ Pnew, int splitk,
+                                            long split_stride4,
+                                            const float* __restrict__ B_prev,
+                                            const float* __restrict__ KV_prev,
+                                            float* __restrict__ B_next, float* __restrict__ KV_next,
+                                            const float* __restrict__ kbar, const int32_t* __restrict__ tab) {
     const float val = op.box_val[n];
     const int row = op.box_row[n];
     int fb = 0, fe = 0;                                         // R == nullptr: the new row of B is built here from the pooled frames
@@ -1092,6 +1094,19 @@ __global__ __launch_bounds__(1024) void update_kernel(OperatorView op, int N, in
         }
         (isB ? Bn : KVn)[cc] = acc;
     }
+}
+
+__global__ __launch_bounds__(1024) void update_kernel(OperatorView op, int N, int d4, int dm4, int n_layers,
+                                                     int S, const int32_t* __restrict__ idx,
+                                                     int idx_layer_stride, const float* __restrict__ R,
+                                                     const float* __restrict__ Pnew, int splitk,
+                                                     long split_stride4,
+                                                     const float* __restrict__ B_prev,
+                                                     const float* __restrict__ KV_prev,
+                                                     float* __restrict__ B_next, float* __restrict__ KV_next,
+                                                     const float* __restrict__ kbar, const int32_t* __restrict__ tab) {
+    update_body(blockIdx.x, blockIdx.y, op, N, d4, dm4, n_layers, idx, idx_layer_stride, R, Pnew, splitk, split_stride4, B_prev,
+                KV_prev, B_next, KV_next, kbar, tab);
 }
 
 hipError_t launch_update(const OperatorView& op, int N, int d, int dm, int n_layers, int S, const int32_t* idx,
@@ -1239,12 +1254,13 @@ constexpr int kAtPitch = 80;                        // LDS pitch of the V' tile:
 // RT = query rows per workgroup: 16 (one MFMA row tile, four rows per wave in turn: 48 workgroups at the headline shape) or 4
 // (one row per wave: 192 workgroups, the row phase -- the longest part, a dependent chain of ~250 instructions per row -- runs
 // once instead of four times per wave; the score and read-out MFMAs then carry 12 idle rows, which costs nothing here).
+// (body shared with attend_videos_kernel: workgroup (h, qt, l) of one video's memory)
 template <int RT>
-__global__ __launch_bounds__(256) void attend_small_kernel(const float* __restrict__ q, int Q, int N, int H,
-                                                           const float* __restrict__ KV, ProjPtrs proj,
-                                                           const float* __restrict__ readout_w, float w_out,
-                                                           StickyView sticky, float* __restrict__ ctx,
-                                                           float* __restrict__ bin_part, float* __restrict__ scores) {
+__device__ __forceinline__ void attend_small_body(int h, int qt, int l, int QT, const float* __restrict__ q, int Q, int N, int H,
+                                                  const float* __restrict__ KV, const ProjPtrs& proj,
+                                                  const float* __restrict__ readout_w, float w_out,
+                                                  const StickyView& sticky, float* __restrict__ ctx,
+                                                  float* __restrict__ bin_part, float* __restrict__ scores) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int sstride = N + 2;
     float* Ssm = lds;                                   // [16][N+2]
@@ -1254,8 +1270,6 @@ __global__ __launch_bounds__(256) void attend_small_kernel(const float* __restri
     float* cq = Msm + kQTile * kMPitch;                 // [16]
     float* asum = cq + 16;                              // [16]
 
-    const int h = blockIdx.x, qt = blockIdx.y, l = blockIdx.z;
-    const int QT = gridDim.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int dm = H * kHeadSize;
     const int c = lane & 15, g = lane >> 4;
@@ -1375,6 +1389,16 @@ __global__ __launch_bounds__(256) void attend_small_kernel(const float* __restri
     }
 }
 
+template <int RT>
+__global__ __launch_bounds__(256) void attend_small_kernel(const float* __restrict__ q, int Q, int N, int H,
+                                                           const float* __restrict__ KV, ProjPtrs proj,
+                                                           const float* __restrict__ readout_w, float w_out,
+                                                           StickyView sticky, float* __restrict__ ctx,
+                                                           float* __restrict__ bin_part, float* __restrict__ scores) {
+    attend_small_body<RT>(blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, q, Q, N, H, KV, proj, readout_w, w_out, sticky, ctx,
+                          bin_part, scores);
+}
+
 size_t attend_small_lds_bytes(int N) {
     const int sstride = N + 2;
     size_t floats = ((kQTile * sstride + 3) & ~3) + (size_t)N * kAtPitch + kQTile * kDPitch + kQTile * kMPitch + 64;
@@ -1431,6 +1455,182 @@ hipError_t launch_attend(const float* q, int Q, int N, int H, int n_layers, cons
     }
     INFV_LAUNCH(attend_kernel, dim3(H, QT, n_layers), dim3(256), lds, stream, q, Q, N, H, KV, proj,
                        readout_w, readout_w_out, sticky, ctx, bin_part, scores);
+    return hipGetLastError();
+}
+
+// ======================================================================================
+// 7. Several independent videos in lockstep (infv_ltm_consolidate_videos): step s advances every video that still has a
+//    chunk by one chunk.  The per-video arithmetic is that of the per-call step (pool_frames_kernel's sum order, the row-built
+//    projection tile, draw_kernel, update_body, attend_small_body); the grids carry a video index (rank j of the call's
+//    table, VideoDesc) and nothing reduces across videos, so a video's bits do not depend on what else is in the batch.
+// ======================================================================================
+bool videos_supported(int N, int d, int dm, int L, int S) {
+    return N > 0 && N <= 256 && N % 16 == 0 && attend_tile_rows(N) == 4 && S > 0 && S <= 1024 && d % kBK == 0 &&
+           (L * 2 * dm) % 64 == 0 && L >= 1 && L <= kMaxLayers;
+}
+
+struct VideoTableChunk {
+    VideoDesc d[kVideoTableChunk];
+};
+static_assert(sizeof(VideoTableChunk) <= 3072, "kernel arguments of launch_video_table stay well inside the 4 KiB limit");
+__global__ __launch_bounds__(64) void video_table_kernel(VideoDesc* __restrict__ dst, VideoTableChunk c, int n) {
+    constexpr int words = sizeof(VideoDesc) / 8;
+    static_assert(sizeof(VideoDesc) % 8 == 0, "VideoDesc is copied in 8-byte words");
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(c.d);
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(dst);
+    for (int i = threadIdx.x; i < n * words; i += 64) out[i] = src[i];
+}
+
+hipError_t launch_video_table(VideoDesc* dst, const VideoDesc* descs, int n, hipStream_t stream) {
+    for (int i = 0; i < n; i += kVideoTableChunk) {
+        VideoTableChunk c;
+        const int m = n - i < kVideoTableChunk ? n - i : kVideoTableChunk;
+        memset(&c, 0, sizeof(c));
+        memcpy(c.d, descs + i, (size_t)m * sizeof(VideoDesc));
+        INFV_LAUNCH(video_table_kernel, dim3(1), dim3(64), 0, stream, dst + i, c, m);
+    }
+    return hipGetLastError();
+}
+
+// one wave per (slot j, frame f, 256-float column slice), as pool_frames_kernel: P loads in flight, summed in token order, / P
+template <class Tok>
+__global__ __launch_bounds__(256) void pool_videos_kernel(const void* __restrict__ k_, float* __restrict__ kbar, VideoStep vs,
+                                                          int T, int P, int d4, int slices) {
+    typedef typename Tok::vec tvec;
+    constexpr int UNROLL = 16;
+    const int lane = threadIdx.x & 63;
+    const long unit = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (unit >= (long)vs.n * T * slices) return;
+    const long fr = unit / slices;                      // j * T + f
+    const int c4 = (int)(unit - fr * slices) * 64 + lane;
+    if (c4 >= d4) return;
+    const int j = (int)(fr / T), f = (int)(fr - (long)j * T);
+    const long chunk = vs.vd[j].chunk0 + vs.s;
+    const tvec* src = reinterpret_cast<const tvec*>(k_) + (chunk * T + f) * (long)P * d4 + c4;
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+    int p = 0;
+    for (; p + UNROLL <= P; p += UNROLL) {
+        tvec v[UNROLL];
+#pragma unroll
+        for (int i = 0; i < UNROLL; ++i) v[i] = __builtin_nontemporal_load(src + (long)(p + i) * d4);
+#pragma unroll
+        for (int i = 0; i < UNROLL; ++i) acc += Tok::widen(v[i]);
+    }
+    for (; p < P; ++p) acc += Tok::widen(__builtin_nontemporal_load(src + (long)p * d4));
+    const float fp = (float)P;
+    acc.x /= fp; acc.y /= fp; acc.z /= fp; acc.w /= fp;
+    reinterpret_cast<floatx4*>(kbar)[fr * d4 + c4] = acc;
+}
+
+hipError_t launch_pool_videos(const void* k, int k_bf16, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream) {
+    const int d4 = d / 4, slices = (d4 + 63) / 64;
+    const long n_units = (long)vs.n * T * slices;
+    if (n_units == 0) return hipSuccess;
+    const dim3 grid((unsigned)((n_units + 3) / 4));
+    if (k_bf16) INFV_LAUNCH(pool_videos_kernel<TokBF16>, grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
+    else INFV_LAUNCH(pool_videos_kernel<TokF32>, grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
+    return hipGetLastError();
+}
+
+// the per-call step's projection tile over the new rows of n chunks at once; one K slab (k_per_split = K)
+__global__ __launch_bounds__(256) void project_videos_kernel(RowsA ra, int M, int K, WSegs segs, float* __restrict__ C, int ldc) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * 64 * kLdsStride];
+    gemm_nt_tile<64, 64, true>(nullptr, ra, M, K, segs, C, ldc, 0, K, 0, smem, smem + 64 * kLdsStride);
+}
+
+hipError_t launch_project_videos(const float* kbar, int n, int T, int d, int dm, int n_layers, const OperatorView& op,
+                                 const ProjPtrs& proj, float* Pnew, hipStream_t stream) {
+    const int M = n * op.rows, n_cols = n_layers * 2 * dm;
+    if (M == 0) return hipSuccess;
+    if (n_cols % 64 || d % kBK) return hipErrorInvalidValue;
+    RowsA ra{kbar, op.row_begin, op.row_end, op.row_box, op.box_val, op.rows, (long)T * d};
+    INFV_LAUNCH(project_videos_kernel, dim3((M + 63) / 64, n_cols / 64), dim3(256), 0, stream, ra, M, d,
+                kv_segs(proj, 0, n_layers, dm), Pnew, n_cols);
+    return hipGetLastError();
+}
+
+// workgroup (layer l, video rank j): draw_kernel on the video's own partials, uniforms, outputs and trace row
+__global__ __launch_bounds__(256) void draw_videos_kernel(VideoStep vs, int parts, StickyView sticky, const double* __restrict__ u,
+                                                          int S, int n_layers) {
+    __shared__ float cdf[kBins];
+    __shared__ double gsum[256];
+    __shared__ int32_t sidx[1024];
+    const int l = blockIdx.x, j = blockIdx.y;
+    const VideoDesc* v = vs.vd + j;
+    const bool first = vs.s == vs.mask_step;
+    const bool ovr = first && ((v->override_mask >> l) & 1u);
+    const bool frc = first && ((v->forced_mask >> l) & 1u);
+    const long chunk = v->chunk0 + vs.s;
+    float* probs_tr = nullptr;
+    int32_t* bins_tr = nullptr;
+    if (vs.s < v->trace_cap) {
+        if (v->trace_probs != nullptr) probs_tr = v->trace_probs + ((long)vs.s * n_layers + l) * kBins;
+        if (v->trace_bins != nullptr) bins_tr = v->trace_bins + ((long)vs.s * n_layers + l) * S;
+    }
+    if (first) parts = v->parts0;                 // (left by whatever stepped the memory last)
+    const DrawRegs<4> r = draw_load<256, 4>(v->bin_part + (long)l * parts * kBins, parts, nullptr, v->probs_override + l * kBins,
+                                            ovr, u + (chunk * n_layers + l) * S, S);
+    draw_finish<256, 4>(r, ovr, sticky.bin_box, S, cdf, sidx, gsum, v->probs + l * kBins, v->bins + (long)l * S,
+                        v->idx + (long)l * S, nullptr, frc ? v->bins_forced + (long)l * S : nullptr, probs_tr, bins_tr);
+}
+
+hipError_t launch_draw_videos(const VideoStep& vs, int parts, const StickyView& sticky, const double* u, int S, int n_layers,
+                              hipStream_t stream) {
+    if (S > 1024) return hipErrorInvalidValue;
+    if (vs.n == 0) return hipSuccess;
+    INFV_LAUNCH(draw_videos_kernel, dim3(n_layers, vs.n), dim3(256), 0, stream, vs, parts, sticky, u, S, n_layers);
+    return hipGetLastError();
+}
+
+// workgroup (box n, layer l, video rank j): update_body on the video's memory, B / KV slot cur -> cur ^ 1
+__global__ __launch_bounds__(1024) void update_videos_kernel(VideoStep vs, OperatorView op, int N, int d4, int dm4, int n_layers,
+                                                             int S, const int32_t* __restrict__ idx_shared,
+                                                             const float* __restrict__ kbar, long kbar_stride,
+                                                             const float* __restrict__ Pnew, long p_stride) {
+    const int j = blockIdx.z;
+    const VideoDesc* v = vs.vd + j;
+    const int cur = v->cur0 ^ (vs.s & 1);
+    const int32_t* idx = idx_shared != nullptr ? idx_shared : v->idx;
+    update_body(blockIdx.x, blockIdx.y, op, N, d4, dm4, n_layers, idx, idx_shared != nullptr ? 0 : S, nullptr, Pnew + j * p_stride, 1, 0,
+                v->B[cur], v->KV[cur], v->B[cur ^ 1], v->KV[cur ^ 1], kbar + j * kbar_stride, nullptr);
+}
+
+hipError_t launch_update_videos(const VideoStep& vs, const OperatorView& op, int N, int T, int d, int dm, int n_layers, int S,
+                                const int32_t* idx_shared, const float* kbar, const float* Pnew, hipStream_t stream) {
+    if (vs.n == 0) return hipSuccess;
+    const int total4 = d / 4 + 2 * (dm / 4);
+    const int nt = total4 >= 1024 ? 1024 : ((total4 + 63) / 64) * 64;
+    INFV_LAUNCH(update_videos_kernel, dim3(N, n_layers, vs.n), dim3(nt), 0, stream, vs, op, N, d / 4, dm / 4, n_layers, S,
+                idx_shared, kbar, (long)T * d, Pnew, (long)op.rows * n_layers * 2 * dm);
+    return hipGetLastError();
+}
+
+// workgroup (head h, 4-row query tile, layer l + L * video rank j): attend_small_body on the video's updated memory
+__global__ __launch_bounds__(256) void attend_videos_kernel(VideoStep vs, const float* __restrict__ q, int Q, int N, int H,
+                                                            int n_layers, ProjPtrs proj, const float* __restrict__ readout_w,
+                                                            float w_out, StickyView sticky, float* __restrict__ ctx) {
+    const int l = blockIdx.z % n_layers, j = blockIdx.z / n_layers;
+    const VideoDesc* v = vs.vd + j;
+    const int cur = v->cur0 ^ ((vs.s + 1) & 1);
+    const long chunk = v->chunk0 + vs.s;
+    attend_small_body<4>(blockIdx.x, blockIdx.y, l, gridDim.y, q, Q, N, H, v->KV[cur], proj, readout_w, w_out, sticky,
+                         ctx + chunk * n_layers * Q * H * kHeadSize, v->bin_part, v->scores);
+}
+
+hipError_t launch_attend_videos(const VideoStep& vs, const float* q, int Q, int N, int H, int n_layers, const ProjPtrs& proj,
+                                const float* readout_w, float readout_w_out, const StickyView& sticky, float* ctx,
+                                hipStream_t stream) {
+    if (vs.n == 0) return hipSuccess;
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attend_videos_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    const int QT = (Q + 3) / 4;
+    INFV_LAUNCH(attend_videos_kernel, dim3(H, QT, n_layers * vs.n), dim3(256), attend_small_lds_bytes(N), stream, vs, q, Q, N, H,
+                n_layers, proj, readout_w, readout_w_out, sticky, ctx);
     return hipGetLastError();
 }
 

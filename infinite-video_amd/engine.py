@@ -479,3 +479,71 @@ class LTMEngine:
             _lib.check(self.lib.infv_ltm_profile_read(self._h, i, C.byref(n), C.byref(ms)))
             out[name] = (n.value, ms.value)
         return out
+
+
+def _same_config(a: LTMEngine, b: LTMEngine) -> bool:
+    return ((a.N, a.Np, a.H, a.dh, a.d, a.P, a.L, a.S, a.sticky, a.tau, a.gaussian_sigmas, a.device) ==
+            (b.N, b.Np, b.H, b.dh, b.d, b.P, b.L, b.S, b.sticky, b.tau, b.gaussian_sigmas, b.device))
+
+
+def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.Tensor, projs: Sequence[ProjTensors],
+                       u=None, new_doc: bool = True) -> torch.Tensor:
+    """Step V independent videos together (infv_ltm_consolidate_videos): engine v holds video v's memory.
+
+    ``k`` is PACKED, [sum C_v, T*P, d] (fp32 or bf16) with video v's chunks at rows [cu[v], cu[v+1]) where cu is the running
+    sum of ``chunk_counts`` (a list or 1-D tensor), and ``u`` likewise [sum C_v, L, S] float64 (None when not sticky).
+    ``k`` (and ``u``) may also be lists of per-video [C_v, T*P, d] ([C_v, L, S]) tensors: they are then packed, which COPIES
+    every video's tokens once.  ``q`` [L, Q, dm] and ``projs`` are shared by all videos.  new_doc=True starts every memory
+    afresh; new_doc=False continues each engine's memory.  Returns ctx [sum C_v, L, Q, dm], packed the same way.
+    Afterwards each engine is in the state its own ``consolidate`` on its chunks would have left it in."""
+    engines = list(engines)
+    V = len(engines)
+    if V == 0:
+        raise ValueError("consolidate_videos needs at least one engine")
+    if isinstance(k, (list, tuple)):
+        if chunk_counts is None:
+            chunk_counts = [int(x.shape[0]) for x in k]
+        k = torch.cat(list(k)) if len(k) else k
+    if isinstance(u, (list, tuple)):
+        u = torch.cat(list(u))
+    if isinstance(chunk_counts, torch.Tensor):
+        if chunk_counts.dim() != 1:
+            raise ValueError("chunk_counts must be a list or a 1-D tensor")
+        chunk_counts = chunk_counts.tolist()
+    counts = [int(c) for c in chunk_counts]
+    if len(counts) != V:
+        raise ValueError(f"chunk_counts has {len(counts)} entries for {V} engines")
+    if any(c < 0 for c in counts):
+        raise ValueError(f"chunk_counts must be non-negative, got {counts}")
+    e0 = engines[0]
+    seen = set()
+    for i, e in enumerate(engines):
+        if not isinstance(e, LTMEngine):
+            raise TypeError(f"engines[{i}] is not an LTMEngine")
+        if id(e) in seen:
+            raise ValueError(f"engines[{i}] appears twice: every video needs its own engine")
+        seen.add(id(e))
+        if not _same_config(e0, e):
+            raise ValueError(f"engines[{i}] is configured differently from engines[0]")
+    cu = np.zeros(V + 1, np.int32)
+    cu[1:] = np.cumsum(counts)
+    total = int(cu[-1])
+    if k.dtype not in TOKEN_DTYPES:
+        raise TypeError(f"frame tokens must be float32 or bfloat16, got {k.dtype}")
+    _check_dev(k, e0.device, "k", k.dtype)
+    if k.dim() != 3 or k.shape[0] != total or k.shape[2] != e0.d or k.shape[1] % e0.P:
+        raise ValueError(f"k must be [{total}, T*{e0.P}, {e0.d}], got {tuple(k.shape)}")
+    T = int(k.shape[1]) // e0.P
+    Q = e0._check_q(q)
+    e0._check_u(u, (total,))
+    for e in engines:
+        e._tokens(k)
+        e.ensure_plan(T)
+        e._check_q(q)
+    proj_arr = e0._proj_array(projs)
+    out = torch.empty(total, e0.L, Q, e0.dm, device=e0.device, dtype=torch.float32)
+    hs = (C.c_void_p * V)(*[e._h.value for e in engines])
+    with torch.cuda.device(e0.device):
+        _lib.check(e0.lib.infv_ltm_consolidate_videos(C.cast(hs, C.c_void_p), V, C.c_void_p(cu.ctypes.data), _ptr(k), T, _ptr(q), Q, proj_arr,
+                                                      _ptr(u), int(new_doc), _ptr(out), _stream(e0.device)))
+    return out

@@ -152,3 +152,16 @@ def videochat2_qformer_weights(n_layers: int = 12, hidden: int = 768, inter: int
             lnorm(p + ffn + ".LayerNorm", hidden)
     linear("mistral_proj", proj_out, hidden)
     return out
+
+
+def video_batch(chunk_counts, T: int, P: int, d: int, n_layers: int, first_video: int = 0, nb_samples: int = NB_SAMPLES):
+    """Inputs of several independent videos (infv_ltm_consolidate_videos): video v (numbered from ``first_video``) has its own
+    tokens, keyed (SEED_K + 1000 (v + 1), chunk), and its own Gibbs uniforms (seed SEED_U + v + 1).  Returns the lists
+    ``ks[v]`` [C_v, T*P, d] fp32 and ``us[v]`` [C_v, L, S] float64."""
+    ks, us = [], []
+    for i, c in enumerate(chunk_counts):
+        v = first_video + i
+        ks.append(np.stack([frame_tokens(j, T, P, d, seed=SEED_K + 1000 * (v + 1)) for j in range(int(c))]) if c
+                  else np.zeros((0, T * P, d), np.float32))
+        us.append(gibbs_uniforms(int(c), n_layers, seed=SEED_U + v + 1, nb_samples=nb_samples))
+    return ks, us
