@@ -256,6 +256,25 @@ int infv_ltm_consolidate_pooled(infv_ltm_handle h, const float* kbar, int32_t n_
 int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const void* k, int32_t T, const float* q,
                                 int32_t Q, const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream);
 
+/* infv_ltm_consolidate_videos from frame means the caller already holds, with an optional query per chunk (additive in ABI 6;
+ * the video Q-former's layers after the first query the memory with chunk-dependent hidden states, Qformer.py:211).
+ *   kbar [cu[V], T, d]  fp32 (device, 16-byte aligned: read as float4): frame means (infv_ltm_pool of the tokens); the
+ *                       handles' token dtype does not enter
+ *   q    q_per_chunk = 0: [L, Q, dm] shared by every chunk;  q_per_chunk = 1: [cu[V], L, Q, dm], one per chunk (infv_ltm_steps)
+ * Everything else -- handles, packed cu, u, ctx, new_doc, refusals, groups of 256 videos, the caller's stream only -- is
+ * infv_ltm_consolidate_videos's contract.  The lockstep step copies each running video's kbar rows of the step into the call's
+ * workspace (plain copies) where consolidate_videos pools tokens, and reads chunk c's query at q + c * L*Q*dm when q_per_chunk.
+ * Bits:
+ *   (a) q_per_chunk = 0 and kbar = infv_ltm_pool(k): ctx, B, bin masses and draws equal infv_ltm_consolidate_videos(k, q)'s;
+ *   (b) a video's bits do not depend on the rest of the batch (which videos, their order, their lengths);
+ *   (c) per video, the results agree with infv_ltm_consolidate_q on that handle to fp32 rounding (its projection may take
+ *       split-K; this one never does), the draws apart from uniforms within rounding of a cdf edge.
+ * Shapes the lockstep kernels do not take (dense or psi plans, N above 256 or not a multiple of 16) run each handle's
+ * infv_ltm_steps (q_per_chunk = 1) or infv_ltm_consolidate_pooled (q_per_chunk = 0) in turn, after the reset when new_doc. */
+int infv_ltm_steps_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const float* kbar, int32_t T,
+                          const float* q, int32_t q_per_chunk, int32_t Q, const infv_ltm_proj* proj,
+                          const double* u, int32_t new_doc, float* ctx, void* stream);
+
 /* Consolidated memory of one layer: B_past [N,d] (long_term_attention_gibbs.py:220) and the
  * unnormalised sticky bin masses p[n_bins-1] derived from the last scores (:200-202).
  * Export copies device -> caller's DEVICE buffers (async on stream). */

@@ -108,6 +108,28 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
                           int32_t T, const infv_vqf_weights* w, const double* u, int32_t new_video,
                           float* hidden_out, float* llama_out, float* llama_mean, void* stream);
 
+/* infv_vqf_encode_video over V videos in one call (evaluation harnesses over many short videos).  Chunks are PACKED, video v
+ * owning chunks [cu[v], cu[v+1]) (cu: HOST array [V+1], cu[0] = 0, non-decreasing; a video may have no chunk):
+ *   frames     [cu[V]][T*P][enc_width]   u [cu[V]][n_layers][S] float64 (may be NULL when not sticky, or when every video is
+ *                                        new and has one chunk)
+ *   hidden_out [cu[V]][Q][hidden], llama_out [cu[V]][Q][proj_out] (either may be NULL)
+ *   llama_mean [V][Q][proj_out]: video v's mean over its chunks, bitwise infv_vqf_mean over its own llama rows (NULL: none)
+ *   ltm        [V][n_layers] one-layer handles, video-major (NULL when alpha == 1); all distinct
+ * new_video = 1 starts every memory afresh; 0 continues each video's memories.  The schedule is infv_vqf_encode_video's over
+ * all packed chunks: layer 0's chunk-independent prefix once, one token pass (split operands + frame means), layer 0's memories
+ * through infv_ltm_steps_videos with the shared query, short-term attention over all chunks; for later layers the query-token
+ * blocks batched over all chunks and their memories through infv_ltm_steps_videos with per-chunk queries on the side stream
+ * while the caller's stream runs the short-term attention; then merge, FFN, llama_proj and the per-video means.
+ * BATCH INVARIANCE: a video's hidden states, llama rows, mean and memories (B, bin masses, draws) do not depend on what else is
+ * in the call.  The GEMMs over row blocks of chunks take 128 x 128 tiles without split-K; the short-term contractions take
+ * their kernel shape and split-K counts from the chunk's shape and a constant (split-K partials are summed in a fixed order;
+ * no float atomics); sub-batch sizes still vary for occupancy, which changes no summation order.  So the
+ * values agree with infv_vqf_encode_video to fp32 rounding, not bit for bit; a Gibbs uniform within rounding of a cdf edge can
+ * flip a draw.  Refusals (INFV_ERR_INVALID: bad cu, null or repeated handle) happen before any device work. */
+int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu,
+                           const float* frames, int32_t T, const infv_vqf_weights* w, const double* u,
+                           int32_t new_video, float* hidden_out, float* llama_out, float* llama_mean, void* stream);
+
 /* out[i] = mean over n of in[n][i]  (the eval loop's mean over chunk embeddings,
  * run_inference_inf_video_llama_nextqa.py:194) */
 int infv_vqf_mean(const float* in, int32_t n, int64_t elems, float* out, void* stream);

@@ -1920,44 +1920,48 @@ int infv_ltm_consolidate_pooled(infv_ltm_handle h, const float* kbar, int32_t n_
 namespace {
 constexpr int kVideoGroup = 256;
 
-bool same_config(infv_ltm_handle a, infv_ltm_handle b) {
+// tokens: the handles also agree on their token dtype (infv_ltm_consolidate_videos pools tokens; infv_ltm_steps_videos reads
+// frame means, so the dtype does not enter)
+bool same_config(infv_ltm_handle a, infv_ltm_handle b, bool tokens) {
     return a->N == b->N && a->H == b->H && a->dh == b->dh && a->d == b->d && a->P == b->P && a->L == b->L && a->S == b->S &&
-           (a->cfg.sticky != 0) == (b->cfg.sticky != 0) && a->k_bf16 == b->k_bf16;
+           (a->cfg.sticky != 0) == (b->cfg.sticky != 0) && (!tokens || a->k_bf16 == b->k_bf16);
 }
 
 bool same_plan(const Plan& a, const Plan& b) {
     return a.digest == b.digest && a.dense.on == b.dense.on && a.first.rows == b.first.rows && a.inf.rows == b.inf.rows &&
            a.inf.tabw == b.inf.tabw && a.n_bins == b.n_bins && a.w_out == b.w_out;
 }
-}  // namespace
 
-extern "C" {
-
-int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const void* k_, int32_t T, const float* q,
-                                int32_t Q, const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream_) {
+// The lockstep step loop of infv_ltm_consolidate_videos (tokens k, pooled per step) and infv_ltm_steps_videos (frame means kbar,
+// gathered per step).  Chunk c of the packed arrays reads its query at q + c * q_stride: q_stride 0 shares one [L,Q,dm]
+// query, L*Q*dm gives every chunk its own.  `name` prefixes the refusals.
+int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const int32_t* cu, bool tokens, const void* k_,
+                const float* kbar, int32_t T, const float* q, bool q_per_chunk, int32_t Q, const infv_ltm_proj* proj,
+                const double* u, int32_t new_doc, float* ctx, void* stream_) {
     // ---- validation: nothing below changes a handle until every check has passed ----
-    if (!hs || !cu || V < 0) return fail(INFV_ERR_INVALID, "consolidate_videos: bad arguments");
+    if (!hs || !cu || V < 0) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
     if (V == 0) return INFV_OK;
-    if (cu[0] < 0) return fail(INFV_ERR_INVALID, "consolidate_videos: cu[0] = %d is negative", cu[0]);
+    if (cu[0] < 0) return fail(INFV_ERR_INVALID, "%s: cu[0] = %d is negative", name, cu[0]);
     for (int v = 0; v < V; ++v)
-        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "consolidate_videos: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)",
-                                            v, cu[v], v + 1, cu[v + 1]);
+        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "%s: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)",
+                                            name, v, cu[v], v + 1, cu[v + 1]);
     const int total = cu[V];
-    for (int v = 0; v < V; ++v) {
-        if (!hs[v]) return fail(INFV_ERR_INVALID, "consolidate_videos: handle %d is null", v);
+    for (int v = 0; v < V; ++v) {                  // (before any handle is read)
+        if (!hs[v]) return fail(INFV_ERR_INVALID, "%s: handle %d is null", name, v);
         for (int w = 0; w < v; ++w)
-            if (hs[w] == hs[v]) return fail(INFV_ERR_INVALID, "consolidate_videos: handle %d is also handle %d (a memory steps once per step)", v, w);
-        if (!same_config(hs[0], hs[v]))
-            return fail(INFV_ERR_INVALID, "consolidate_videos: handle %d's configuration (N, H, dh, d, P, L, S, sticky, token dtype) differs "
-                                          "from handle 0's", v);
+            if (hs[w] == hs[v]) return fail(INFV_ERR_INVALID, "%s: handle %d is also handle %d (a memory steps once per step)", name, v, w);
     }
-    if (total > 0 && (!k_ || !q || !proj || !ctx)) return fail(INFV_ERR_INVALID, "consolidate_videos: null argument");
+    if (total > 0 && ((tokens ? !k_ : !kbar) || !q || !proj || !ctx)) return fail(INFV_ERR_INVALID, "%s: null argument", name);
+    for (int v = 1; v < V; ++v)
+        if (!same_config(hs[0], hs[v], tokens))
+            return fail(INFV_ERR_INVALID, "%s: handle %d's configuration (N, H, dh, d, P, L, S, sticky%s) differs from handle 0's",
+                        name, v, tokens ? ", token dtype" : "");
     infv_ltm_handle h0 = hs[0];
     const bool sticky = h0->cfg.sticky != 0;
     int max_len = 0;
     for (int v = 0; v < V; ++v) max_len = cu[v + 1] - cu[v] > max_len ? cu[v + 1] - cu[v] : max_len;
     if (sticky && !u && (new_doc ? max_len > 1 : total > 0))
-        return fail(INFV_ERR_INVALID, "consolidate_videos: sticky steps on an existing memory need the Gibbs uniforms u");
+        return fail(INFV_ERR_INVALID, "%s: sticky steps on an existing memory need the Gibbs uniforms u", name);
     std::vector<Plan*> plans(V, nullptr);
     for (int v = 0; v < V; ++v) {
         infv_ltm_handle h = hs[v];
@@ -1965,28 +1969,39 @@ int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int3
         if (int rc = check_q(h, Q)) return rc;
         if (int rc = find_plan(h, T, &plans[v])) return rc;
         if (!same_plan(*plans[0], *plans[v]))
-            return fail(INFV_ERR_INVALID, "consolidate_videos: handle %d's plan for T = %d differs from handle 0's (tau, num_basis or "
-                                          "the tables themselves): every video steps with one plan", v, T);
+            return fail(INFV_ERR_INVALID, "%s: handle %d's plan for T = %d differs from handle 0's (tau, num_basis or "
+                                          "the tables themselves): every video steps with one plan", name, v, T);
         if (!new_doc && !h->has_memory)
-            return fail(INFV_ERR_STATE, "consolidate_videos: new_doc = 0 but handle %d holds no memory", v);
+            return fail(INFV_ERR_STATE, "%s: new_doc = 0 but handle %d holds no memory", name, v);
         if (!new_doc && sticky && h->parts <= 0)
-            return fail(INFV_ERR_STATE, "consolidate_videos: handle %d has no sticky histogram (import_state or step first)", v);
+            return fail(INFV_ERR_STATE, "%s: handle %d has no sticky histogram (import_state or step first)", name, v);
     }
     if (new_doc)
         for (int v = 0; v < V; ++v) infv_ltm_reset(hs[v]);
     if (total == 0) return INFV_OK;
     const char* k = static_cast<const char*>(k_);
-    const size_t chunk_k = (size_t)T * h0->P * h0->d * (h0->k_bf16 ? 2 : 4);
+    const size_t chunk_k = (size_t)T * h0->P * h0->d * (h0->k_bf16 ? 2 : 4), chunk_kbar = (size_t)T * h0->d;
     const size_t chunk_ctx = (size_t)h0->L * Q * h0->dm, chunk_u = (size_t)h0->L * h0->S;
     bool batched = videos_supported(h0->N, h0->d, h0->dm, h0->L, h0->S);
     batched = batched && !plans[0]->dense.on;
     if (!batched) {
-        // shapes the lockstep kernels do not take (dense / psi plans, N above 256, ...): each video's own consolidate, in turn
-        for (int v = 0; v < V; ++v)
-            if (cu[v + 1] > cu[v])
-                if (int rc = infv_ltm_consolidate(hs[v], k + (size_t)cu[v] * chunk_k, cu[v + 1] - cu[v], T, q, Q, proj,
-                                                  u ? u + (size_t)cu[v] * chunk_u : nullptr, 0, ctx + (size_t)cu[v] * chunk_ctx,
-                                                  stream_)) return rc;
+        // shapes the lockstep kernels do not take (dense / psi plans, N above 256, ...): each video's own per-call path, in turn
+        // (the handles were reset above when new_doc is set)
+        for (int v = 0; v < V; ++v) {
+            const int n = cu[v + 1] - cu[v];
+            if (n == 0) continue;
+            const double* uv = u ? u + (size_t)cu[v] * chunk_u : nullptr;
+            float* cv = ctx + (size_t)cu[v] * chunk_ctx;
+            int rc;
+            if (tokens)
+                rc = infv_ltm_consolidate(hs[v], k + (size_t)cu[v] * chunk_k, n, T, q, Q, proj, uv, 0, cv, stream_);
+            else if (q_per_chunk)
+                rc = infv_ltm_steps(hs[v], kbar + (size_t)cu[v] * chunk_kbar, n, T, q + (size_t)cu[v] * chunk_ctx, Q, proj, uv, cv,
+                                    stream_);
+            else
+                rc = infv_ltm_consolidate_pooled(hs[v], kbar + (size_t)cu[v] * chunk_kbar, n, T, q, Q, proj, uv, 0, cv, stream_);
+            if (rc) return rc;
+        }
         return INFV_OK;
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -1996,6 +2011,7 @@ int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int3
             if (int rc = infv_ltm_reproject(hs[v], proj, stream_)) return rc;
     const Plan& plan = *plans[0];
     const int N = h0->N, d = h0->d, dm = h0->dm, L = h0->L, S = h0->S;
+    const long q_stride = q_per_chunk ? (long)chunk_ctx : 0;
     const int rows_max = plan.first.rows > plan.inf.rows ? plan.first.rows : plan.inf.rows;
     const int group = V < kVideoGroup ? V : kVideoGroup;
     {   // workspaces of one step (grown, never shrunk; released with the lead handle)
@@ -2046,7 +2062,8 @@ int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int3
             const VideoStep vs{h0->vid_tab.as<VideoDesc>(), s, n, mask_step};
             {
                 Timed t_(h0->prof, INFV_KERNEL_POOL, stream);
-                HIP_TRY(launch_pool_videos(k, h0->k_bf16, vs, T, h0->P, d, h0->vid_kbar.as<float>(), stream));
+                if (tokens) HIP_TRY(launch_pool_videos(k, h0->k_bf16, vs, T, h0->P, d, h0->vid_kbar.as<float>(), stream));
+                else HIP_TRY(launch_gather_videos(kbar, vs, T, d, h0->vid_kbar.as<float>(), stream));
             }
             {
                 Timed t_(h0->prof, INFV_KERNEL_PROJECT, stream);
@@ -2063,7 +2080,8 @@ int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int3
             }
             {
                 Timed t_(h0->prof, INFV_KERNEL_ATTEND, stream);
-                HIP_TRY(launch_attend_videos(vs, q, Q, N, h0->H, L, pp, plan.w.as<float>(), plan.w_out, plan.sticky(), ctx, stream));
+                HIP_TRY(launch_attend_videos(vs, q, q_stride, Q, N, h0->H, L, pp, plan.w.as<float>(), plan.w_out, plan.sticky(), ctx,
+                                             stream));
             }
         }
         for (int j = 0; j < gn; ++j) {             // the handles' host state after their chunks (chain_step's bookkeeping)
@@ -2079,6 +2097,21 @@ int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int3
         }
     }
     return INFV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const void* k, int32_t T, const float* q,
+                                int32_t Q, const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream) {
+    return videos_impl("consolidate_videos", hs, V, cu, true, k, nullptr, T, q, false, Q, proj, u, new_doc, ctx, stream);
+}
+
+int infv_ltm_steps_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const float* kbar, int32_t T, const float* q,
+                          int32_t q_per_chunk, int32_t Q, const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx,
+                          void* stream) {
+    if (q_per_chunk != 0 && q_per_chunk != 1) return fail(INFV_ERR_INVALID, "steps_videos: q_per_chunk must be 0 or 1");
+    return videos_impl("steps_videos", hs, V, cu, false, nullptr, kbar, T, q, q_per_chunk != 0, Q, proj, u, new_doc, ctx, stream);
 }
 
 }  // extern "C"

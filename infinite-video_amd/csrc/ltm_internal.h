@@ -338,6 +338,8 @@ hipError_t launch_video_table(VideoDesc* dst, const VideoDesc* descs, int n, hip
 bool videos_supported(int N, int d, int dm, int L, int S);
 // kbar[j][f][:] = mean over P tokens of frame f of video rank j's chunk of this step (k packed [chunks][T*P][d])
 hipError_t launch_pool_videos(const void* k, int k_bf16, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream);
+// out[j][f][:] = kbar[chunk of video rank j at this step][f][:] (kbar packed [chunks][T][d] fp32): bitwise copies
+hipError_t launch_gather_videos(const float* kbar, const VideoStep& vs, int T, int d, float* out, hipStream_t stream);
 // Pnew[j * rows + r][l][kv][dm] = R(j, r) . W[l][kv]^T with the rows built from kbar[j] (no split-K: the summation order of an
 // element does not depend on how many videos share the launch)
 hipError_t launch_project_videos(const float* kbar, int n, int T, int d, int dm, int n_layers, const OperatorView& op,
@@ -347,7 +349,8 @@ hipError_t launch_draw_videos(const VideoStep& vs, int parts, const StickyView& 
 // idx_shared != nullptr: every video gathers through that table (non-sticky resampling); else through its own drawn idx
 hipError_t launch_update_videos(const VideoStep& vs, const OperatorView& op, int N, int T, int d, int dm, int n_layers, int S,
                                 const int32_t* idx_shared, const float* kbar, const float* Pnew, hipStream_t stream);
-hipError_t launch_attend_videos(const VideoStep& vs, const float* q, int Q, int N, int H, int n_layers, const ProjPtrs& proj,
-                                const float* readout_w, float readout_w_out, const StickyView& sticky, float* ctx,
-                                hipStream_t stream);
+// video rank j's chunk c reads its query at q + c * q_stride: 0 for one query [L,Q,dm] shared by every chunk, L*Q*dm for one per chunk
+hipError_t launch_attend_videos(const VideoStep& vs, const float* q, long q_stride, int Q, int N, int H, int n_layers,
+                                const ProjPtrs& proj, const float* readout_w, float readout_w_out, const StickyView& sticky,
+                                float* ctx, hipStream_t stream);
 }  // namespace infv

@@ -1459,7 +1459,7 @@ hipError_t launch_attend(const float* q, int Q, int N, int H, int n_layers, cons
 }
 
 // ======================================================================================
-// 7. Several independent videos in lockstep (infv_ltm_consolidate_videos): step s advances every video that still has a
+// 7. Several independent videos in lockstep (infv_ltm_consolidate_videos, infv_ltm_steps_videos): step s advances every video that still has a
 //    chunk by one chunk.  The per-video arithmetic is that of the per-call step (pool_frames_kernel's sum order, the row-built
 //    projection tile, draw_kernel, update_body, attend_small_body); the grids carry a video index (rank j of the call's
 //    table, VideoDesc) and nothing reduces across videos, so a video's bits do not depend on what else is in the batch.
@@ -1529,6 +1529,24 @@ hipError_t launch_pool_videos(const void* k, int k_bf16, const VideoStep& vs, in
     const dim3 grid((unsigned)((n_units + 3) / 4));
     if (k_bf16) INFV_LAUNCH(pool_videos_kernel<TokBF16>, grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
     else INFV_LAUNCH(pool_videos_kernel<TokF32>, grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
+    return hipGetLastError();
+}
+
+// one thread per float4 of video rank j's chunk of this step (infv_ltm_steps_videos: frame means the caller pooled): plain copies
+__global__ __launch_bounds__(256) void gather_videos_kernel(const float* __restrict__ kbar, float* __restrict__ out, VideoStep vs,
+                                                            long chunk4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= chunk4) return;
+    const int j = blockIdx.y;
+    const long chunk = vs.vd[j].chunk0 + vs.s;
+    reinterpret_cast<floatx4*>(out)[j * chunk4 + i] = reinterpret_cast<const floatx4*>(kbar)[chunk * chunk4 + i];
+}
+
+hipError_t launch_gather_videos(const float* kbar, const VideoStep& vs, int T, int d, float* out, hipStream_t stream) {
+    if (d % 4) return hipErrorInvalidValue;
+    const long chunk4 = (long)T * d / 4;
+    if (vs.n == 0 || chunk4 == 0) return hipSuccess;
+    INFV_LAUNCH(gather_videos_kernel, dim3((unsigned)((chunk4 + 255) / 256), vs.n), dim3(256), 0, stream, kbar, out, vs, chunk4);
     return hipGetLastError();
 }
 
@@ -1605,21 +1623,22 @@ hipError_t launch_update_videos(const VideoStep& vs, const OperatorView& op, int
     return hipGetLastError();
 }
 
-// workgroup (head h, 4-row query tile, layer l + L * video rank j): attend_small_body on the video's updated memory
-__global__ __launch_bounds__(256) void attend_videos_kernel(VideoStep vs, const float* __restrict__ q, int Q, int N, int H,
-                                                            int n_layers, ProjPtrs proj, const float* __restrict__ readout_w,
+// workgroup (head h, 4-row query tile, layer l + L * video rank j): attend_small_body on the video's updated memory, under the
+// chunk's query q + chunk * q_stride (q_stride 0: one query shared by every chunk)
+__global__ __launch_bounds__(256) void attend_videos_kernel(VideoStep vs, const float* __restrict__ q, long q_stride, int Q, int N,
+                                                            int H, int n_layers, ProjPtrs proj, const float* __restrict__ readout_w,
                                                             float w_out, StickyView sticky, float* __restrict__ ctx) {
     const int l = blockIdx.z % n_layers, j = blockIdx.z / n_layers;
     const VideoDesc* v = vs.vd + j;
     const int cur = v->cur0 ^ ((vs.s + 1) & 1);
     const long chunk = v->chunk0 + vs.s;
-    attend_small_body<4>(blockIdx.x, blockIdx.y, l, gridDim.y, q, Q, N, H, v->KV[cur], proj, readout_w, w_out, sticky,
-                         ctx + chunk * n_layers * Q * H * kHeadSize, v->bin_part, v->scores);
+    attend_small_body<4>(blockIdx.x, blockIdx.y, l, gridDim.y, q + chunk * q_stride, Q, N, H, v->KV[cur], proj, readout_w, w_out,
+                         sticky, ctx + chunk * n_layers * Q * H * kHeadSize, v->bin_part, v->scores);
 }
 
-hipError_t launch_attend_videos(const VideoStep& vs, const float* q, int Q, int N, int H, int n_layers, const ProjPtrs& proj,
-                                const float* readout_w, float readout_w_out, const StickyView& sticky, float* ctx,
-                                hipStream_t stream) {
+hipError_t launch_attend_videos(const VideoStep& vs, const float* q, long q_stride, int Q, int N, int H, int n_layers,
+                                const ProjPtrs& proj, const float* readout_w, float readout_w_out, const StickyView& sticky,
+                                float* ctx, hipStream_t stream) {
     if (vs.n == 0) return hipSuccess;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1629,8 +1648,8 @@ hipError_t launch_attend_videos(const VideoStep& vs, const float* q, int Q, int 
         attr_set = true;
     }
     const int QT = (Q + 3) / 4;
-    INFV_LAUNCH(attend_videos_kernel, dim3(H, QT, n_layers * vs.n), dim3(256), attend_small_lds_bytes(N), stream, vs, q, Q, N, H,
-                n_layers, proj, readout_w, readout_w_out, sticky, ctx);
+    INFV_LAUNCH(attend_videos_kernel, dim3(H, QT, n_layers * vs.n), dim3(256), attend_small_lds_bytes(N), stream, vs, q, q_stride, Q,
+                N, H, n_layers, proj, readout_w, readout_w_out, sticky, ctx);
     return hipGetLastError();
 }
 

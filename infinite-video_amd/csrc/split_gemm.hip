@@ -319,6 +319,7 @@ bool split_gemm_wide_applies(const SplitGemm& g) {
     static const int mode = [] { const char* e = exp_env("INFV_SPLIT_GEMM_WIDE"); return e ? atoi(e) : 1; }();
     if (!mode) return false;
     if (g.M % kWRowsA || g.N % kWRowsB) return false;               // whole tiles only (unconditional loads and stores)
+    if (g.wide) return true;
     const long mt = g.M / kWRowsA;
     const long wgs = mt * ((g.N + kWRowsB - 1) / kWRowsB) * g.nbatch * g.splitk;
     return mode > 1 || wgs >= 192;

@@ -2,6 +2,7 @@
 #include "../../include/infv_vqf.h"
 #include "capi_common.h"
 #include <algorithm>
+#include <vector>
 #include "vqf_internal.h"
 
 #include <cstdlib>
@@ -64,11 +65,12 @@ struct LinearCall {
     const float* residual = nullptr; int res_rows = 1;
     const infv_layernorm* ln = nullptr;
     float* y;
+    bool inv = false;      // batch invariant (infv_vqf_encode_videos): 128 x 128 tiles, no split-K, whatever M is
 };
 
 int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
     const int width = c.n_lin * c.n_out;
-    const int sk = qf_pick_splitk(c.M, width, c.K, 1);
+    const int sk = c.inv ? 1 : qf_pick_splitk(c.M, width, c.K, 1);
     const size_t need = (size_t)sk * c.M * width * sizeof(float);
     if (need > h->part.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->part.reserve(need)); }
     QfGemm g{};
@@ -76,7 +78,7 @@ int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
     for (int i = 0; i < c.n_lin; ++i) g.B[i] = c.lin[i]->w;
     g.ldb = c.K; g.strideB = 0; g.seg_rows = c.n_out;
     g.C = h->part.as<float>(); g.ldc = width; g.strideC = 0; g.split_stride = (long)c.M * width;
-    g.M = c.M; g.N = width; g.k_per_split = c.K / sk; g.splitk = sk; g.nbatch = 1;
+    g.M = c.M; g.N = width; g.k_per_split = c.K / sk; g.splitk = sk; g.nbatch = 1; g.tile = c.inv ? 128 : 0;
     HIP_TRY(launch_qf_gemm(g, false, stream));
     QfEpilogue e{};
     e.parts = h->part.as<float>(); e.nsplit = sk; e.split_stride = g.split_stride; e.ld_in = width;
@@ -94,6 +96,9 @@ int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
 //   -> merged [nb*Q][hidden] = alpha * short-term context + (1 - alpha) * along   (along == nullptr: short-term only)
 // Split-bf16 copies of frame tokens produced ahead of the attention (prepare_split): [.][n_tokens][d] and [.][d][n_tokens]
 struct SplitRef { const __bf16 *Fh, *Fl, *Th, *Tl; };
+// infv_vqf_encode_videos takes the short-term attention's split-K counts as for this many chunks per sub-batch, whatever the
+// sub-batch holds: a chunk's summation order then does not depend on the rest of the batch
+constexpr int kInvariantNb = 16;
 
 static bool split_path(const infv_vqf_s* h, int n_tokens) {
     static const bool want_fp32 = [] { const char* e = getenv("INFV_VQF_FP32"); return e && atoi(e) != 0; }();
@@ -129,13 +134,15 @@ static int prepare_split(infv_vqf_s* h, const float* frames, int nb, int n_token
 int short_attention(infv_vqf_s* h, const float* frames, int nb, int n_tokens, const float* xq, bool shared_q,
                     const infv_linear* key, const infv_linear* value, const float* along, float* merged,
                     hipStream_t stream, bool use_cache = false, const SplitRef* pre = nullptr,
-                    hipEvent_t along_ready = nullptr /* `along` is produced on another stream: wait here, before the merge */) {
+                    hipEvent_t along_ready = nullptr /* `along` is produced on another stream: wait here, before the merge */,
+                    int inv_nb = 0 /* > 0: batch invariant -- split-K counts and kernel shapes as for inv_nb chunks, whatever nb is */) {
     const infv_vqf_config& c = h->cfg;
     const int Q = c.n_query, H = c.n_heads, d = c.enc_width, rows = H * Q;
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
+    const int nb_pick = inv_nb > 0 ? inv_nb : nb;
     int kps = n_tokens;
-    int sk = qf_pick_splitk_fill(rows, d, n_tokens, nb, &kps);
-    if (split_path(h, n_tokens)) sk = split_gemm_pick_splitk(rows, d, n_tokens, nb, &kps);   // (64-deep k-tiles, its own tile shapes)
+    int sk = qf_pick_splitk_fill(rows, d, n_tokens, nb_pick, &kps);
+    if (split_path(h, n_tokens)) sk = split_gemm_pick_splitk(rows, d, n_tokens, nb_pick, &kps);   // (64-deep k-tiles, its own tile shapes)
     const int nq = shared_q ? 1 : nb;
     // leading dimension of the score matrix: padded by 256 B so that its rows (the A operand of the second
     // contraction, one 128-B line per row per k-tile) do not all map to the same memory channel
@@ -186,14 +193,14 @@ int short_attention(infv_vqf_s* h, const float* frames, int nb, int n_tokens, co
         g.A_hi = static_cast<const __bf16*>(qh); g.A_lo = static_cast<const __bf16*>(ql); g.lda = d; g.strideA = shared_q ? 0 : (long)rows * d;
         g.B_hi = sr.Fh; g.B_lo = sr.Fl; g.ldb = d; g.strideB = (long)n_tokens * d;
         g.C = h->S.as<float>(); g.ldc = ldS; g.strideC = (long)rows * ldS; g.split_stride = 0;
-        g.M = rows; g.N = n_tokens; g.K = d; g.k_per_split = d; g.splitk = 1; g.nbatch = nb;
+        g.M = rows; g.N = n_tokens; g.K = d; g.k_per_split = d; g.splitk = 1; g.nbatch = nb; g.wide = inv_nb > 0;
         HIP_TRY(launch_split_gemm(g, stream));
         HIP_TRY(launch_softmax_rows_split(h->S.as<float>(), (long)nb * rows, n_tokens, ldS, h->sPh.p, h->sPl.p, n_tokens, stream));
         SplitGemm p{};                                        // O[b] = P[b] . frames[b]
         p.A_hi = h->sPh.as<__bf16>(); p.A_lo = h->sPl.as<__bf16>(); p.lda = n_tokens; p.strideA = (long)rows * n_tokens;
         p.B_hi = sr.Th; p.B_lo = sr.Tl; p.ldb = n_tokens; p.strideB = (long)d * n_tokens;
         p.C = h->O.as<float>(); p.ldc = d; p.strideC = (long)rows * d; p.split_stride = (long)nb * rows * d;
-        p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb;
+        p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.wide = inv_nb > 0;
         HIP_TRY(launch_split_gemm(p, stream));
     } else {
     QfGemm g{};                                             // S[b] = qt[b] . frames[b]^T
@@ -216,7 +223,7 @@ int short_attention(infv_vqf_s* h, const float* frames, int nb, int n_tokens, co
     HIP_TRY(launch_qf_sum_slabs(h->O.as<float>(), sk, o_split_stride, (long)nb * rows * d, stream));
     const int M2 = nb * Q, hidden = c.hidden;
     int sk2 = 8;
-    while (sk2 > 1 && (d % (32 * sk2) || nb * H * sk2 > 4096)) sk2 >>= 1;
+    while (sk2 > 1 && (d % (32 * sk2) || nb_pick * H * sk2 > 4096)) sk2 >>= 1;
     const size_t needP = (size_t)sk2 * M2 * hidden * sizeof(float);
     if (needP > h->part.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->part.reserve(needP)); }
     QfGemm v{};
@@ -419,10 +426,12 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
     return INFV_OK;
 }
 
-int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const float* frames, int32_t n_chunks,
-                          int32_t T, const infv_vqf_weights* w, const double* u, int32_t new_video,
-                          float* hidden_out, float* llama_out, float* llama_mean, void* stream_) {
-    if (!h || !frames || !w || n_chunks < 1) return fail(INFV_ERR_INVALID, "bad argument");
+// The layer-major body of infv_vqf_encode_video (multi = false: one video, ltm [n_layers]) and infv_vqf_encode_videos (multi:
+// V videos packed by the host array cu, ltm [V][n_layers]; every choice that shapes a GEMM or contraction is taken from
+// per-chunk quantities or constants, and each layer's memories step through infv_ltm_steps_videos).
+static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const float* frames, int32_t n_chunks, int32_t T,
+                       const infv_vqf_weights* w, const double* u, int32_t new_video, float* hidden_out, float* llama_out,
+                       float* llama_mean, void* stream_, int32_t V, const int32_t* cu, bool multi) {
     const infv_vqf_config& c = h->cfg;
     if (int rc = check_layer_cfg(c)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -436,7 +445,8 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
     const long chunk_k = (long)n_tokens * c.enc_width;
     const long M = (long)C * Q;                               // rows of the whole-video activations
     // ---- workspaces: whole-video activations + per-block scratch ----
-    const int RB = C < 64 ? C : 64;                           // chunks per row block of the query-token GEMMs
+    const int rb_max = multi ? 128 : 64;                      // (batch invariant: the row count does not shape the GEMMs)
+    const int RB = C < rb_max ? C : rb_max;                   // chunks per row block of the query-token GEMMs
     // chunks per sub-batch of the short-term attention: the second contraction has few, long tiles per chunk
     // (rows/128 x d/128 = 18 at the headline shape, K = T*P), so pick the count whose tile total fills whole rounds
     // of the 256 CUs (16 chunks = 288 tiles ran at 56 % of 14 chunks' rate per tile)
@@ -503,6 +513,12 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
         *r = SplitRef{wref.Fh + o, wref.Fl + o, wref.Th + o, wref.Tl + o};
         return r;
     };
+    if (multi && use_ltm && !have_kbar) {                    // the frame means every layer's memories step from
+        if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;
+        if (int rc = infv_ltm_pool(ltm[0], frames, (int64_t)C * T, h->vkbar.as<float>(), stream_)) return rc;
+    }
+    std::vector<infv_ltm_handle> hs_l(multi ? V : 0);         // layer l's handles of every video
+    auto layer_handles = [&](int l) { for (int v = 0; v < V; ++v) hs_l[v] = ltm[(size_t)v * c.n_layers + l]; };
     float* vA = h->vA.as<float>(); float* v1 = h->v1.as<float>(); float* v2 = h->v2.as<float>();
     float* vxq = h->vxq.as<float>(); float* valong = h->valong.as<float>();
     float* vshort = h->vshort.as<float>(); float* vmerged = h->vmerged.as<float>();
@@ -531,18 +547,26 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
         if (shared) {
             // ---- self-attention block + cross query once ----
             LinearCall qkv{h->h_a.as<float>(), Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
+            qkv.inv = multi;
             qkv.y = h->qkv.as<float>();
             if (int rc = run_linear(h, qkv, stream)) return rc;
             HIP_TRY(launch_qf_self_attention(h->qkv.as<float>(), 1, Q, c.n_heads, h->sa.as<float>(), stream));
             LinearCall so{h->sa.as<float>(), Q, Hd, {&L.self_o}, 1, Hd};
+            so.inv = multi;
             so.residual = h->h_a.as<float>(); so.res_rows = Q; so.ln = &L.self_ln; so.y = h->v_h1s.as<float>();
             if (int rc = run_linear(h, so, stream)) return rc;
             LinearCall xq{h->v_h1s.as<float>(), Q, Hd, {&L.x_q}, 1, Hd};
+            xq.inv = multi;
             xq.y = h->v_xqs.as<float>();
             if (int rc = run_linear(h, xq, stream)) return rc;
             res1 = h->v_h1s.as<float>(); res1_rows = Q;
             // ---- long-term memory of every chunk with the constant query: the whole-video fast path ----
-            if (use_ltm) {
+            if (use_ltm && multi) {                           // every video's memory with the shared query, in lockstep
+                if (int rc = ltm_u(l)) return rc;
+                layer_handles(l);
+                if (int rc = infv_ltm_steps_videos(hs_l.data(), V, cu, h->vkbar.as<float>(), T, h->v_xqs.as<float>(), 0, Q, &pr,
+                                                   u ? h->vu.as<double>() : nullptr, new_video, valong, stream_)) return rc;
+            } else if (use_ltm) {
                 if (int rc = ltm_u(l)) return rc;
                 if (have_kbar) {
                     if (int rc = infv_ltm_consolidate_pooled(ltm[l], h->vkbar.as<float>(), C, T, h->v_xqs.as<float>(), Q, &pr,
@@ -558,7 +582,7 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
                 SplitRef sr;
                 if (int rc = short_attention(h, frames + c0 * chunk_k, nb, n_tokens, h->v_xqs.as<float>(), true, &L.x_k, &L.x_v,
                                              use_ltm ? valong + (long)c0 * Q * Hd : nullptr, vmerged + (long)c0 * Q * Hd, stream,
-                                             false, pre_at(c0, &sr))) return rc;
+                                             false, pre_at(c0, &sr), nullptr, multi ? kInvariantNb : 0)) return rc;
             }
         } else {
             // ---- self-attention block + cross query of every chunk (row blocks) ----
@@ -566,13 +590,16 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
                 const int nb = C - c0 < RB ? C - c0 : RB;
                 const long r0 = (long)c0 * Q * Hd;
                 LinearCall qkv{vA + r0, nb * Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
+                qkv.inv = multi;
                 qkv.y = h->vqkv.as<float>();
                 if (int rc = run_linear(h, qkv, stream)) return rc;
                 HIP_TRY(launch_qf_self_attention(h->vqkv.as<float>(), nb, Q, c.n_heads, h->vsa.as<float>(), stream));
                 LinearCall so{h->vsa.as<float>(), nb * Q, Hd, {&L.self_o}, 1, Hd};
+                so.inv = multi;
                 so.residual = vA + r0; so.res_rows = nb * Q; so.ln = &L.self_ln; so.y = v1 + r0;
                 if (int rc = run_linear(h, so, stream)) return rc;
                 LinearCall xq{v1 + r0, nb * Q, Hd, {&L.x_q}, 1, Hd};
+                xq.inv = multi;
                 xq.y = vxq + r0;
                 if (int rc = run_linear(h, xq, stream)) return rc;
             }
@@ -583,6 +610,11 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
                 if (int rc = ltm_u(l)) return rc;
                 HIP_TRY(hipEventRecord(h->ev_main, stream));
                 HIP_TRY(hipStreamWaitEvent(h->side, h->ev_main, 0));
+                if (multi) {                                  // every video's memory with its chunks' queries, in lockstep
+                    layer_handles(l);
+                    if (int rc = infv_ltm_steps_videos(hs_l.data(), V, cu, h->vkbar.as<float>(), T, vxq, 1, Q, &pr,
+                                                       u ? h->vu.as<double>() : nullptr, new_video, valong, h->side)) return rc;
+                } else {
                 if (new_video)
                     if (int rc = infv_ltm_reset(ltm[l])) return rc;
                 if (!have_kbar) {
@@ -592,6 +624,7 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
                 // per-chunk queries: new-row projections of all chunks in one GEMM, then the chain chunk by chunk
                 if (int rc = infv_ltm_steps(ltm[l], h->vkbar.as<float>(), C, T, vxq, Q, &pr, u ? h->vu.as<double>() : nullptr,
                                             valong, h->side)) return rc;
+                }
                 HIP_TRY(hipEventRecord(h->ev_side, h->side));
             }
             for (int c0 = 0; c0 < C; c0 += NB) {
@@ -599,7 +632,7 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
                 SplitRef sr;
                 if (int rc = short_attention(h, frames + c0 * chunk_k, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
                                              nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
-                                             pre_at(c0, &sr))) return rc;
+                                             pre_at(c0, &sr), nullptr, multi ? kInvariantNb : 0)) return rc;
             }
             if (use_ltm) {
                 HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
@@ -618,12 +651,15 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
             const int nb = C - c0 < RB ? C - c0 : RB;
             const long r0 = (long)c0 * Q * Hd;
             LinearCall xo{vmerged + r0, nb * Q, Hd, {&L.x_o}, 1, Hd};
+            xo.inv = multi;
             xo.residual = shared ? res1 : res1 + r0; xo.res_rows = shared ? res1_rows : nb * Q; xo.ln = &L.x_ln; xo.y = v2 + r0;
             if (int rc = run_linear(h, xo, stream)) return rc;
             LinearCall fi{v2 + r0, nb * Q, Hd, {&L.ffn_in}, 1, c.inter};
+            fi.inv = multi;
             fi.act = QF_ACT_GELU; fi.y = h->vinter.as<float>();
             if (int rc = run_linear(h, fi, stream)) return rc;
             LinearCall fo{h->vinter.as<float>(), nb * Q, c.inter, {&L.ffn_out}, 1, Hd};
+            fo.inv = multi;
             fo.residual = v2 + r0; fo.res_rows = nb * Q; fo.ln = &L.ffn_ln; fo.y = vA + r0;
             if (int rc = run_linear(h, fo, stream)) return rc;
         }
@@ -640,12 +676,51 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
         for (int c0 = 0; c0 < C; c0 += RB) {
             const int nb = C - c0 < RB ? C - c0 : RB;
             LinearCall pj{vA + (long)c0 * Q * Hd, nb * Q, Hd, {&w->llama_proj}, 1, c.proj_out};
+            pj.inv = multi;
             pj.y = lo + (long)c0 * Q * c.proj_out;
             if (int rc = run_linear(h, pj, stream)) return rc;
         }
-        if (llama_mean) HIP_TRY(launch_qf_mean(lo, C, (long)Q * c.proj_out, llama_mean, stream));
+        if (llama_mean && multi) HIP_TRY(launch_qf_mean_segments(lo, cu, V, (long)Q * c.proj_out, llama_mean, stream));
+        else if (llama_mean) HIP_TRY(launch_qf_mean(lo, C, (long)Q * c.proj_out, llama_mean, stream));
     }
     return INFV_OK;
+}
+
+int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const float* frames, int32_t n_chunks,
+                          int32_t T, const infv_vqf_weights* w, const double* u, int32_t new_video,
+                          float* hidden_out, float* llama_out, float* llama_mean, void* stream_) {
+    if (!h || !frames || !w || n_chunks < 1) return fail(INFV_ERR_INVALID, "bad argument");
+    return encode_impl(h, ltm, frames, n_chunks, T, w, u, new_video, hidden_out, llama_out, llama_mean, stream_, 1, nullptr, false);
+}
+
+int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+                           int32_t T, const infv_vqf_weights* w, const double* u, int32_t new_video, float* hidden_out,
+                           float* llama_out, float* llama_mean, void* stream_) {
+    // ---- validation before any device work or memory change ----
+    if (!h || !cu || !w || V < 0) return fail(INFV_ERR_INVALID, "encode_videos: bad arguments");
+    if (V == 0) return INFV_OK;
+    if (cu[0] != 0) return fail(INFV_ERR_INVALID, "encode_videos: cu[0] = %d, not 0", cu[0]);
+    for (int v = 0; v < V; ++v)
+        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "encode_videos: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)",
+                                            v, cu[v], v + 1, cu[v + 1]);
+    const bool use_ltm = h->cfg.alpha != 1.0f;
+    const int n_h = use_ltm ? V * h->cfg.n_layers : 0;
+    if (use_ltm) {
+        if (!ltm) return fail(INFV_ERR_INVALID, "encode_videos: alpha != 1 needs the per-layer LTM handles of every video");
+        std::vector<infv_ltm_handle> all(ltm, ltm + n_h);
+        for (int i = 0; i < n_h; ++i)
+            if (!all[i]) return fail(INFV_ERR_INVALID, "encode_videos: LTM handle %d is null", i);
+        std::sort(all.begin(), all.end());
+        if (std::adjacent_find(all.begin(), all.end()) != all.end())
+            return fail(INFV_ERR_INVALID, "encode_videos: an LTM handle appears twice (every video and layer needs its own memory)");
+    }
+    if (cu[V] == 0) {                                         // no chunk: new_video still starts every memory afresh
+        if (use_ltm && new_video)
+            for (int i = 0; i < n_h; ++i) infv_ltm_reset(ltm[i]);
+        return INFV_OK;
+    }
+    if (!frames) return fail(INFV_ERR_INVALID, "encode_videos: null frames");
+    return encode_impl(h, ltm, frames, cu[V], T, w, u, new_video, hidden_out, llama_out, llama_mean, stream_, V, cu, true);
 }
 
 int infv_vqf_mean(const float* in, int32_t n, int64_t elems, float* out, void* stream) {

@@ -19,6 +19,7 @@ struct QfGemm {
     int M, N, k_per_split, splitk, nbatch;
     int K;                                           // total depth; 0 = splitk * k_per_split (the last split may be shorter)
     int inner;  long strideA2, strideB2, strideC2;   // optional second batch level (zero-initialised = unused)
+    int tile;                                        // 0: 128 x 128 tiles where M and N reach 128, else 64 x 64; 64 / 128: that tile
 };
 hipError_t launch_qf_gemm(const QfGemm& g, bool nn, hipStream_t stream);
 int qf_pick_splitk(int M, int N, int K, int nbatch);
@@ -59,6 +60,7 @@ struct SplitGemm {
     float* C; long ldc, strideC, split_stride;
     int M, N, K, k_per_split, splitk, nbatch;
     long long* wg_stamps;            // residency / loop-cycle experiment (wg_stamps.h), or nullptr
+    int wide;                        // 0: the 384 x 256 kernel where whole tiles fill the chip; 1: wherever whole tiles apply
 };
 hipError_t launch_split_gemm(const SplitGemm& g, hipStream_t stream, int lds_pad = 0);
 // fp32-accurate contraction from three bf16 planes per operand (six partial products, fp32 accumulation): C = A . B^T
@@ -108,5 +110,7 @@ hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long 
 
 // out[m][:] = mean over nb of in[b][m][:]
 hipError_t launch_qf_mean(const float* in, int nb, long n, float* out, hipStream_t stream);
+// out[v][:] = mean over b in [cu[v], cu[v+1]) of in[b][:] for v < V, summed in b order as qf_mean_kernel (cu: host array [V+1])
+hipError_t launch_qf_mean_segments(const float* in, const int32_t* cu, int V, long n, float* out, hipStream_t stream);
 
 }  // namespace infv

@@ -201,7 +201,7 @@ hipError_t launch_qf_gemm(const QfGemm& g, bool nn, hipStream_t stream) {
     if (g.M <= 0 || g.N <= 0 || g.nbatch <= 0) return hipSuccess;
     if (g.k_per_split % kBK != 0 || g.k_per_split <= 0) return hipErrorInvalidValue;
     if (nn && (g.N % 4 != 0)) return hipErrorInvalidValue;
-    const bool big = qf_big_tiles(g.M, g.N);
+    const bool big = g.tile ? g.tile == 128 : qf_big_tiles(g.M, g.N);
     const int bm = big ? 128 : 64;
     dim3 grid((g.M + bm - 1) / bm, (g.N + bm - 1) / bm, g.nbatch * g.splitk);
     if (big) {
@@ -568,6 +568,28 @@ __global__ __launch_bounds__(256) void qf_mean_kernel(const float* __restrict__ 
 
 hipError_t launch_qf_mean(const float* in, int nb, long n, float* out, hipStream_t stream) {
     INFV_LAUNCH(qf_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, nb, n, out);
+    return hipGetLastError();
+}
+
+// one video per grid row: its chunks' rows summed in chunk order, / count (qf_mean_kernel's arithmetic on the video's rows)
+constexpr int kMeanSegs = 256;
+struct MeanSegs { int32_t cu[kMeanSegs + 1]; };
+__global__ __launch_bounds__(256) void qf_mean_segments_kernel(const float* __restrict__ in, MeanSegs sg, long n, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int v = blockIdx.y, b0 = sg.cu[v], b1 = sg.cu[v + 1];
+    float a = 0.f;
+    for (int b = b0; b < b1; ++b) a += in[(long)b * n + i];
+    out[(long)v * n + i] = a / (float)(b1 - b0);
+}
+
+hipError_t launch_qf_mean_segments(const float* in, const int32_t* cu, int V, long n, float* out, hipStream_t stream) {
+    for (int v0 = 0; v0 < V; v0 += kMeanSegs) {              // the table travels in kernel arguments, 256 videos per launch
+        const int nv = V - v0 < kMeanSegs ? V - v0 : kMeanSegs;
+        MeanSegs sg;
+        for (int j = 0; j <= nv; ++j) sg.cu[j] = cu[v0 + j];
+        INFV_LAUNCH(qf_mean_segments_kernel, dim3((unsigned)((n + 255) / 256), nv), dim3(256), 0, stream, in, sg, n, out + (long)v0 * n);
+    }
     return hipGetLastError();
 }
 

@@ -486,26 +486,12 @@ def _same_config(a: LTMEngine, b: LTMEngine) -> bool:
             (b.N, b.Np, b.H, b.dh, b.d, b.P, b.L, b.S, b.sticky, b.tau, b.gaussian_sigmas, b.device))
 
 
-def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.Tensor, projs: Sequence[ProjTensors],
-                       u=None, new_doc: bool = True) -> torch.Tensor:
-    """Step V independent videos together (infv_ltm_consolidate_videos): engine v holds video v's memory.
-
-    ``k`` is PACKED, [sum C_v, T*P, d] (fp32 or bf16) with video v's chunks at rows [cu[v], cu[v+1]) where cu is the running
-    sum of ``chunk_counts`` (a list or 1-D tensor), and ``u`` likewise [sum C_v, L, S] float64 (None when not sticky).
-    ``k`` (and ``u``) may also be lists of per-video [C_v, T*P, d] ([C_v, L, S]) tensors: they are then packed, which COPIES
-    every video's tokens once.  ``q`` [L, Q, dm] and ``projs`` are shared by all videos.  new_doc=True starts every memory
-    afresh; new_doc=False continues each engine's memory.  Returns ctx [sum C_v, L, Q, dm], packed the same way.
-    Afterwards each engine is in the state its own ``consolidate`` on its chunks would have left it in."""
+def _video_engines(engines: Sequence[LTMEngine], chunk_counts, what: str):
+    """The argument checks shared by the multi-video calls: (engines, cu) with cu the host int32 running sum of chunk_counts."""
     engines = list(engines)
     V = len(engines)
     if V == 0:
-        raise ValueError("consolidate_videos needs at least one engine")
-    if isinstance(k, (list, tuple)):
-        if chunk_counts is None:
-            chunk_counts = [int(x.shape[0]) for x in k]
-        k = torch.cat(list(k)) if len(k) else k
-    if isinstance(u, (list, tuple)):
-        u = torch.cat(list(u))
+        raise ValueError(f"{what} needs at least one engine")
     if isinstance(chunk_counts, torch.Tensor):
         if chunk_counts.dim() != 1:
             raise ValueError("chunk_counts must be a list or a 1-D tensor")
@@ -527,6 +513,27 @@ def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.T
             raise ValueError(f"engines[{i}] is configured differently from engines[0]")
     cu = np.zeros(V + 1, np.int32)
     cu[1:] = np.cumsum(counts)
+    return engines, cu
+
+
+def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.Tensor, projs: Sequence[ProjTensors],
+                       u=None, new_doc: bool = True) -> torch.Tensor:
+    """Step V independent videos together (infv_ltm_consolidate_videos): engine v holds video v's memory.
+
+    ``k`` is PACKED, [sum C_v, T*P, d] (fp32 or bf16) with video v's chunks at rows [cu[v], cu[v+1]) where cu is the running
+    sum of ``chunk_counts`` (a list or 1-D tensor), and ``u`` likewise [sum C_v, L, S] float64 (None when not sticky).
+    ``k`` (and ``u``) may also be lists of per-video [C_v, T*P, d] ([C_v, L, S]) tensors: they are then packed, which COPIES
+    every video's tokens once.  ``q`` [L, Q, dm] and ``projs`` are shared by all videos.  new_doc=True starts every memory
+    afresh; new_doc=False continues each engine's memory.  Returns ctx [sum C_v, L, Q, dm], packed the same way.
+    Afterwards each engine is in the state its own ``consolidate`` on its chunks would have left it in."""
+    if isinstance(k, (list, tuple)) and chunk_counts is None:
+        chunk_counts = [int(x.shape[0]) for x in k]
+    engines, cu = _video_engines(engines, chunk_counts, "consolidate_videos")
+    if isinstance(k, (list, tuple)):
+        k = torch.cat(list(k)) if len(k) else k
+    if isinstance(u, (list, tuple)):
+        u = torch.cat(list(u))
+    V, e0 = len(engines), engines[0]
     total = int(cu[-1])
     if k.dtype not in TOKEN_DTYPES:
         raise TypeError(f"frame tokens must be float32 or bfloat16, got {k.dtype}")
@@ -546,4 +553,47 @@ def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.T
     with torch.cuda.device(e0.device):
         _lib.check(e0.lib.infv_ltm_consolidate_videos(C.cast(hs, C.c_void_p), V, C.c_void_p(cu.ctypes.data), _ptr(k), T, _ptr(q), Q, proj_arr,
                                                       _ptr(u), int(new_doc), _ptr(out), _stream(e0.device)))
+    return out
+
+
+def steps_videos(engines: Sequence[LTMEngine], kbar, chunk_counts, q: torch.Tensor, projs: Sequence[ProjTensors],
+                 u=None, new_doc: bool = True) -> torch.Tensor:
+    """``consolidate_videos`` from frame means, with an optional query per chunk (infv_ltm_steps_videos).
+
+    ``kbar`` is PACKED [sum C_v, T, d] fp32 (``pool()`` of the tokens), or a list of per-video [C_v, T, d] tensors (packed with
+    one copy).  ``q`` is either [L, Q, dm], shared by every chunk, or [sum C_v, L, Q, dm], one query per chunk (a cross-attention
+    layer after the first, as ``steps`` takes it); ``q.dim()`` decides.  ``u``, ``chunk_counts``, ``new_doc`` and the result
+    ctx [sum C_v, L, Q, dm] are ``consolidate_videos``'s.  With a shared query and kbar = pool(k) the bits equal
+    ``consolidate_videos(k, q)``'s; each video's bits do not depend on the rest of the batch."""
+    if isinstance(kbar, (list, tuple)) and chunk_counts is None:
+        chunk_counts = [int(x.shape[0]) for x in kbar]
+    engines, cu = _video_engines(engines, chunk_counts, "steps_videos")
+    if isinstance(kbar, (list, tuple)):
+        kbar = torch.cat(list(kbar)) if len(kbar) else kbar
+    if isinstance(u, (list, tuple)):
+        u = torch.cat(list(u))
+    V, e0 = len(engines), engines[0]
+    total = int(cu[-1])
+    _check_dev(kbar, e0.device, "kbar")
+    if kbar.dim() != 3 or kbar.shape[0] != total or kbar.shape[2] != e0.d:
+        raise ValueError(f"kbar must be fp32 [{total}, T, {e0.d}], got {tuple(kbar.shape)}")
+    if kbar.data_ptr() % 16:
+        raise ValueError("kbar must start at a 16-byte boundary (the chunks are copied as float4)")
+    T = int(kbar.shape[1])
+    if q.dim() == 4:
+        _check_dev(q, e0.device, "q")
+        if q.shape[0] != total or q.shape[1] != e0.L or q.shape[3] != e0.dm or q.shape[2] > e0.max_q:
+            raise ValueError(f"q must be [{e0.L}, Q, {e0.dm}] or [{total}, {e0.L}, Q <= {e0.max_q}, {e0.dm}], got {tuple(q.shape)}")
+        Q, per_chunk = int(q.shape[2]), 1
+    else:
+        Q, per_chunk = e0._check_q(q), 0
+    e0._check_u(u, (total,))
+    for e in engines:
+        e.ensure_plan(T)
+    proj_arr = e0._proj_array(projs)
+    out = torch.empty(total, e0.L, Q, e0.dm, device=e0.device, dtype=torch.float32)
+    hs = (C.c_void_p * V)(*[e._h.value for e in engines])
+    with torch.cuda.device(e0.device):
+        _lib.check(e0.lib.infv_ltm_steps_videos(C.cast(hs, C.c_void_p), V, C.c_void_p(cu.ctypes.data), _ptr(kbar), T, _ptr(q),
+                                                per_chunk, Q, proj_arr, _ptr(u), int(new_doc), _ptr(out), _stream(e0.device)))
     return out

@@ -203,6 +203,95 @@ def _dev_f32(t: torch.Tensor, device: torch.device) -> torch.Tensor:
     return t
 
 
+class VideoMemory:
+    """One video's long-term memories for :meth:`InfVideoEncoder.encode_videos`: one one-layer ``LTMEngine`` per
+    cross-attention layer, created as ``LongTermAttention._get_engine`` creates the model's own.  ``export_state(l)`` and
+    ``last_draw(l)`` read layer l's memory."""
+
+    def __init__(self, model: "InfVideoEncoder", device: torch.device):
+        from .engine import LTMEngine
+        Q = model.num_video_query_token
+        self.device = device
+        self.engines = [LTMEngine(m.attn_num_basis, m.n_head, m.head_size, m.encoder_width, m.tokens_per_frame, tau=m.tau,
+                                  sticky=bool(m.sticky_memories), n_layers=1, max_q=max(Q, 32), device=device,
+                                  nb_samples=m.nb_samples)
+                        for m in model.video_Qformer.ltm_modules]
+
+    @property
+    def has_memory(self) -> bool:
+        return any(e.has_memory for e in self.engines)
+
+    def export_state(self, layer: int):
+        """(B [N, d], bin masses) of layer ``layer``'s memory (device tensors)."""
+        return self.engines[layer].export_state(0)
+
+    def last_draw(self, layer: int):
+        """(bins, idx, probs) of layer ``layer``'s last sticky step (host numpy)."""
+        return self.engines[layer].last_draw(0)
+
+    def _check(self, model: "InfVideoEncoder", device: torch.device):
+        if len(self.engines) != len(model.video_Qformer.ltm_modules):
+            raise ValueError("memory has another number of layers than the model")
+        if self.device != device:
+            raise ValueError(f"memory is on {self.device}, frames are on {device}")
+
+
+def _video_counts(chunk_counts) -> List[int]:
+    if isinstance(chunk_counts, torch.Tensor):
+        if chunk_counts.dim() != 1:
+            raise ValueError("chunk_counts must be a list or a 1-D tensor")
+        chunk_counts = chunk_counts.tolist()
+    counts = [int(c) for c in chunk_counts]
+    if not counts:
+        raise ValueError("encode_videos needs at least one video")
+    if any(c < 0 for c in counts):
+        raise ValueError(f"chunk_counts must be non-negative, got {counts}")
+    return counts
+
+
+def _cumsum(counts: Sequence[int]) -> List[int]:
+    out, acc = [], 0
+    for c in counts:
+        acc += c
+        out.append(acc)
+    return out
+
+
+def _check_memories(model: "InfVideoEncoder", memories, V: int, device: torch.device) -> List["VideoMemory"]:
+    """Every video its own VideoMemory, all configured alike; refused before any device work."""
+    from .engine import _same_config
+    memories = list(memories)
+    if len(memories) != V:
+        raise ValueError(f"{len(memories)} memories for {V} videos")
+    seen = set()
+    for i, mem in enumerate(memories):
+        if not isinstance(mem, VideoMemory):
+            raise TypeError(f"memories[{i}] is not a VideoMemory")
+        if id(mem) in seen:
+            raise ValueError(f"memories[{i}] appears twice: every video needs its own memory")
+        seen.add(id(mem))
+        mem._check(model, device)
+        for l, eng in enumerate(mem.engines):
+            if not _same_config(memories[0].engines[l], eng):
+                raise ValueError(f"memories[{i}] layer {l} is configured differently from memories[0]")
+    return memories
+
+
+def draw_video_uniforms(counts: Sequence[int], continuing: Sequence[bool], n_layers: int) -> torch.Tensor:
+    """Gibbs uniforms [sum C_v, n_layers, 512] float64 from torch's global CPU generator, video by video, in the order a loop
+    of ``encode_frames_batch`` over the videos draws them: every chunk that resamples takes 512 and discards 512 (the in-bin
+    draw of LTM.py:206) per layer; chunk 0 of a video that is not ``continuing`` draws nothing (its rows stay 0)."""
+    u = torch.zeros(sum(counts), n_layers, NB_SAMPLES, dtype=torch.float64)
+    row = 0
+    for c_v, cont in zip(counts, continuing):
+        for c in range(0 if cont else 1, c_v):
+            for l in range(n_layers):
+                u[row + c, l] = torch.rand(NB_SAMPLES, dtype=torch.float64)
+                torch.rand(NB_SAMPLES, dtype=torch.float64)
+        row += c_v
+    return u
+
+
 class InfVideoEncoder(nn.Module):
     """The in-scope slice of the reference model ``InfinityQA``: the members ``encode_video`` touches
     (infinityqa.py:195-209,217-236) and ``encode_video`` itself.  The ViT / image Q-former producer
@@ -229,6 +318,7 @@ class InfVideoEncoder(nn.Module):
         self._vqf_dev = None
         self.exact_fp32 = False        # True: exact-fp32 MFMA for the short-term attention instead of split-bf16
         self.last_hidden: Optional[torch.Tensor] = None
+        self._video_memories: List[VideoMemory] = []      # encode_videos' reused pool (memories=None)
 
     # ------------------------------------------------------------------ weights
     def load_reference_state_dict(self, sd: dict, strict: bool = True):
@@ -357,10 +447,12 @@ class InfVideoEncoder(nn.Module):
 
     # ------------------------------------------------------------------ one chunk
     def encode_frames(self, frame_hidden_state: torch.Tensor, new_video: bool,
-                      u: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                      u: Optional[torch.Tensor] = None, memory: Optional["VideoMemory"] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """frame_hidden_state [1, T*P, d] (device) -> (last_hidden_state [1, Q, hidden], inputs_llama [1, Q, llama]).
         ``u`` [n_layers, 512] float64: the Gibbs uniforms; by default drawn from torch's global CPU generator in
-        the order the reference's CPU path consumes them (512 + 512 discarded per LTM call that resamples)."""
+        the order the reference's CPU path consumes them (512 + 512 discarded per LTM call that resamples).
+        ``memory``: continue that video's memories (a :class:`VideoMemory` of :meth:`encode_videos`, e.g. with its ragged
+        tail chunk of another T) instead of the model's own; the model's state is then left untouched."""
         if not frame_hidden_state.is_cuda:
             raise RuntimeError("the video Q-former path runs on the HIP device only (no CPU fallback)")
         if frame_hidden_state.dim() != 3 or frame_hidden_state.size(0) != 1:
@@ -378,13 +470,18 @@ class InfVideoEncoder(nn.Module):
         handles = (C.c_void_p * cfg.num_hidden_layers)()
         if use_ltm:
             need_u = False
+            if memory is not None:
+                memory._check(self, device)
             for l, m in enumerate(self.video_Qformer.ltm_modules):
-                m.length = m.target_len = frame_hidden_state.size(1)             # Qformer.py:218-219
-                eng = m._get_engine(device, Q)
+                if memory is None:
+                    m.length = m.target_len = frame_hidden_state.size(1)         # Qformer.py:218-219
+                    eng = m._get_engine(device, Q)
+                    m.count += 1
+                else:
+                    eng = memory.engines[l]
                 eng.ensure_plan(T)
                 handles[l] = eng._h
                 need_u = need_u or (eng.has_memory and not new_video and bool(m.sticky_memories))
-                m.count += 1
             if u is None and need_u:
                 draws = []
                 for _ in range(cfg.num_hidden_layers):
@@ -408,7 +505,8 @@ class InfVideoEncoder(nn.Module):
                                                  int(bool(new_video)), C.c_void_p(hidden.data_ptr()),
                                                  C.c_void_p(llama.data_ptr()), stream))
         del keep
-        self.last_hidden = hidden
+        if memory is None:
+            self.last_hidden = hidden
         return hidden, llama
 
     # ------------------------------------------------------------------ a whole video, layer-major
@@ -465,6 +563,73 @@ class InfVideoEncoder(nn.Module):
                                                  int(bool(new_video)),
                                                  C.c_void_p(0 if hidden is None else hidden.data_ptr()),
                                                  C.c_void_p(llama.data_ptr()), C.c_void_p(mean.data_ptr()), stream))
+        del keep
+        return llama, mean, hidden
+
+    # ------------------------------------------------------------------ many videos, layer-major, one call
+    def encode_videos(self, frames, chunk_counts=None, new_video: bool = True, u: Optional[torch.Tensor] = None,
+                      want_hidden: bool = False, memories: Optional[Sequence["VideoMemory"]] = None):
+        """Many videos through the video Q-former in ONE C call (``infv_vqf_encode_videos``): ``encode_frames_batch``'s
+        layer-major schedule over the chunks of every video, each video's long-term memories in its own
+        :class:`VideoMemory` (``memories[v]``; by default a reused pool of the encoder, the model's own memory untouched).
+
+        ``frames``: packed [sum C_v, T*P, d] with ``chunk_counts``, or a list of [C_v, T*P, d] (packed with one copy).
+        Returns (inputs_llama [sum C_v, Q, llama], per-video means [V, Q, llama], last_hidden_state [sum C_v, Q, hidden]
+        or None).  A video's outputs and memories do not depend on the rest of the batch (bit for bit); they agree with
+        ``encode_frames_batch`` on that video to fp32 rounding.  ``u`` [sum C_v, n_layers, 512] float64; by default drawn
+        from torch's global CPU generator video by video, in the order looping ``encode_frames_batch`` over the videos
+        would draw it (chunk 0 of a new video draws nothing)."""
+        if isinstance(frames, (list, tuple)):
+            if chunk_counts is None:
+                chunk_counts = [int(f.size(0)) for f in frames]
+            frames = torch.cat(list(frames)) if len(frames) else None
+        if chunk_counts is None:
+            raise ValueError("packed frames need chunk_counts")
+        counts = _video_counts(chunk_counts)
+        V, total = len(counts), sum(counts)
+        cfg = self.video_Qformer.config
+        P, Q, Ln = self.tokens_per_frame, self.num_video_query_token, cfg.num_hidden_layers
+        if frames is None or not frames.is_cuda:
+            raise RuntimeError("the video Q-former path runs on the HIP device only (no CPU fallback)")
+        if frames.dim() != 3 or frames.size(0) != total or frames.size(2) != cfg.encoder_width or frames.size(1) % P:
+            raise ValueError(f"frames must be [{total}, T*{P}, {cfg.encoder_width}], got {tuple(frames.shape)}")
+        device = frames.device
+        T = frames.size(1) // P
+        k = _dev_f32(frames, device)
+        h = self._handle(device)
+        lib = _lib.load()
+        use_ltm = cfg.alpha != 1.0
+        handles = None
+        if not use_ltm:
+            u = None                                          # (no memory: nothing is drawn)
+        else:
+            if memories is None:
+                while len(self._video_memories) < V:
+                    self._video_memories.append(VideoMemory(self, device))
+                memories = self._video_memories[:V]
+            memories = _check_memories(self, memories, V, device)
+            handles = (C.c_void_p * (V * Ln))()
+            for v, mem in enumerate(memories):
+                for l, eng in enumerate(mem.engines):
+                    eng.ensure_plan(T)
+                    handles[v * Ln + l] = eng._h
+            if u is None and bool(self.video_Qformer.ltm_modules[0].sticky_memories):
+                u = draw_video_uniforms(counts, [not new_video and mem.has_memory for mem in memories], Ln)
+            if u is not None:
+                u = u.to(device=device, dtype=torch.float64).contiguous()
+                if tuple(u.shape) != (total, Ln, NB_SAMPLES):
+                    raise ValueError(f"u must be [{total}, {Ln}, {NB_SAMPLES}]")
+        w, keep = self._weights(device)
+        hidden = torch.empty(total, Q, cfg.hidden_size, device=device, dtype=torch.float32) if want_hidden else None
+        llama = torch.empty(total, Q, self.llama_proj.out_features, device=device, dtype=torch.float32)
+        mean = torch.empty(V, Q, self.llama_proj.out_features, device=device, dtype=torch.float32)
+        cu = (C.c_int32 * (V + 1))(0, *[int(x) for x in _cumsum(counts)])
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        with torch.cuda.device(device):
+            _lib.check(lib.infv_vqf_encode_videos(h, handles, V, C.cast(cu, C.c_void_p), C.c_void_p(k.data_ptr()), T,
+                                                  C.byref(w), C.c_void_p(0 if u is None else u.data_ptr()), int(bool(new_video)),
+                                                  C.c_void_p(0 if hidden is None else hidden.data_ptr()),
+                                                  C.c_void_p(llama.data_ptr()), C.c_void_p(mean.data_ptr()), stream))
         del keep
         return llama, mean, hidden
 
@@ -532,6 +697,76 @@ def encode_long_video(model: InfVideoEncoder, frame_tokens: torch.Tensor, max_in
         _lib.check(lib.infv_vqf_mean(C.c_void_p(stacked.data_ptr()), len(embs), embs[0].numel(),
                                      C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return out, embs
+
+
+def split_long_videos(frame_counts: Sequence[int], max_int: int) -> List[Tuple[int, int]]:
+    """Per video (full chunks, frames of the ragged tail chunk or 0): ``encode_long_video``'s split into ``max_int`` frames."""
+    if max_int < 1:
+        raise ValueError("max_int must be >= 1")
+    return [(int(f) // max_int, int(f) % max_int) for f in frame_counts]
+
+
+def encode_long_videos(model: InfVideoEncoder, videos: Sequence[torch.Tensor], max_int: int,
+                       u_of_chunk=None) -> List[Tuple[torch.Tensor, List[torch.Tensor]]]:
+    """``encode_long_video`` over many videos (``videos[v]``: [F_v, P, d] frame-token blocks): the full-length chunks of ALL
+    videos go through one :meth:`InfVideoEncoder.encode_videos` call, then each ragged tail through the per-chunk path on its
+    video's memory.  Returns per video ``encode_long_video``'s (mean [1, Q, llama], per-chunk list).
+    ``u_of_chunk(v, i)`` gives chunk i of video v its uniforms [n_layers, 512]; with None they come from torch's global CPU
+    generator, drawn video-major first, so that the generator is consumed exactly as
+    ``for v: encode_long_video(model, videos[v], max_int, batched=True)`` consumes it."""
+    videos = list(videos)
+    if not videos:
+        raise ValueError("encode_long_videos needs at least one video")
+    cfg = model.video_Qformer.config
+    Ln = cfg.num_hidden_layers
+    sticky = cfg.alpha != 1.0 and bool(model.video_Qformer.ltm_modules[0].sticky_memories)
+    split = split_long_videos([x.size(0) for x in videos], max_int)
+    n_full = [f for f, _ in split]
+    u_full, u_tail = None, [None] * len(videos)
+    if u_of_chunk is not None:
+        rows = [torch.as_tensor(u_of_chunk(v, i), dtype=torch.float64) for v, n in enumerate(n_full) for i in range(n)]
+        u_full = torch.stack(rows) if rows else None
+        u_tail = [torch.as_tensor(u_of_chunk(v, n_full[v]), dtype=torch.float64) if t else None for v, (_, t) in enumerate(split)]
+    elif sticky:
+        parts = []
+        for v, (n, t) in enumerate(split):
+            parts.append(draw_video_uniforms([n], [False], Ln))
+            if t and n > 0:                                   # the tail continues the memory: it resamples
+                u_tail[v] = draw_video_uniforms([2], [False], Ln)[1]
+        u_full = torch.cat(parts)
+    results: List[Tuple[torch.Tensor, List[torch.Tensor]]] = []
+    llama = means = None
+    if sum(n_full):
+        frames = torch.cat([x[:n * max_int].reshape(n, max_int * x.size(1), x.size(-1)) for x, n in zip(videos, n_full)])
+        llama, means, _ = model.encode_videos(frames, n_full, new_video=True, u=u_full)
+    lib = _lib.load()
+    row = 0
+    for v, (x, (n, t)) in enumerate(zip(videos, split)):
+        embs = [llama[row + i:row + i + 1] for i in range(n)]
+        row += n
+        if t:
+            blk = x[n * max_int:]
+            mem = _pool_memory(model, v, x.device) if cfg.alpha != 1.0 else None      # (what encode_videos just stepped)
+            _, emb = model.encode_frames(blk.reshape(1, -1, blk.size(-1)), new_video=(n == 0), u=u_tail[v], memory=mem)
+            embs.append(emb)
+        if not t:
+            results.append((means[v:v + 1], embs))
+            continue
+        stacked = torch.stack(embs).contiguous()
+        out = torch.empty_like(embs[0])
+        dev = stacked.device
+        with torch.cuda.device(dev):
+            _lib.check(lib.infv_vqf_mean(C.c_void_p(stacked.data_ptr()), len(embs), embs[0].numel(),
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        results.append((out, embs))
+    return results
+
+
+def _pool_memory(model: InfVideoEncoder, v: int, device: torch.device) -> "VideoMemory":
+    """Video v's memory of the encoder's pool (encode_videos with memories=None), grown when needed."""
+    while len(model._video_memories) <= v:
+        model._video_memories.append(VideoMemory(model, device))
+    return model._video_memories[v]
 
 
 # ---------------------------------------------------------------------------------------------- multi-GPU (chunk blocks)
