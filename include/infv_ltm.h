@@ -62,7 +62,10 @@ typedef struct {
     int32_t d_in;              /* d, encoder width of the frame tokens                 */
     int32_t tokens_per_frame;  /* P                                                    */
     int32_t n_layers;          /* LTM instances stepped together by this handle (>=1)  */
-    int32_t nb_samples;        /* S = 512 (long_term_attention_gibbs.py:55)            */
+    int32_t nb_samples;        /* S, 1..1024; the reference hard-codes 512 (long_term_attention_gibbs.py:55).  More than
+                                  1024: INFV_ERR_UNSUPPORTED at create (the draw kernels hold the S slots in LDS).  Every
+                                  entry point takes any S in range; infv_ltm_consolidate's fused chain takes S <= 512 and
+                                  runs the per-chunk step above it (same results to fp32 rounding)       */
     int32_t sticky;            /* sticky_memories                                      */
     int32_t max_q;             /* largest query length that will be passed             */
     int32_t max_batch_chunks;  /* chunks pooled/projected per sub-batch by consolidate */
@@ -111,7 +114,12 @@ typedef struct {
 int         infv_ltm_abi_version(void);
 const char* infv_ltm_last_error(void);
 
-/* LongTermAttention.__init__ (long_term_attention_gibbs.py:26-65). */
+/* LongTermAttention.__init__ (long_term_attention_gibbs.py:26-65).  Refused HERE, before any device work (INFV_ERR_UNSUPPORTED /
+ * INFV_ERR_INVALID, message in infv_ltm_last_error): head_size other than 64, num_basis that is no positive multiple of 16 (the
+ * Python wrapper pads any other value), d_in that is no positive multiple of 32, n_heads < 1, tokens_per_frame < 1, nb_samples
+ * outside 1..1024, n_layers outside 1..INFV_LTM_MAX_LAYERS, max_q < 1.  num_basis and max_q have no upper bound here; what the
+ * suite has run is num_basis up to 512 and query lengths up to 384 (tests/golden/sweep_cases.py lists every swept shape).
+ * infv_ltm_consolidate runs queries longer than 256 rows through the per-chunk step. */
 int infv_ltm_create(const infv_ltm_config* cfg, infv_ltm_handle* out);
 int infv_ltm_destroy(infv_ltm_handle h);
 
@@ -205,7 +213,10 @@ int infv_ltm_consolidate_q(infv_ltm_handle h, const void* k, int32_t n_chunks, i
                            void* stream);
 
 /* LongTermAttention.forward (long_term_attention_gibbs.py:288-346) for all layers of the
- * handle on one chunk: reset if new_doc, pool, step.  k [T*P, d]. */
+ * handle on one chunk: reset if new_doc, pool, step.  k [T*P, d].  What the step would refuse (a null argument, Q outside (0, max_q],
+ * no plan for T, a sticky step on a memory without u -- any chunk after the first of infv_ltm_consolidate_q --, no sticky
+ * histogram, a partial forced draw on a dense plan, a latched device error) is refused BEFORE the reset and the pooling launch --
+ * here, in infv_ltm_forward_into and in infv_ltm_consolidate_q: such a call launches no kernel and leaves the memory as it was. */
 int infv_ltm_forward(infv_ltm_handle h, const void* k, int32_t T, const float* q, int32_t Q,
                      const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx,
                      void* stream);

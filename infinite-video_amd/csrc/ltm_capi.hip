@@ -455,6 +455,27 @@ int check_q(infv_ltm_handle h, int Q) {
     return INFV_OK;
 }
 
+// What infv_ltm_step would refuse over the `n_chunks` chunks of a call, for the entry points that reset the memory or pool the
+// tokens in front of it (forward, forward_into, consolidate_q): checked first, so that a refused call launches nothing and
+// leaves the handle as it was.  `keeps_memory`: the first step runs on the handle's present memory (no reset in front of it).
+int precheck_step(infv_ltm_handle h, const void* q, const void* proj, const void* ctx, int T, int Q, const void* u, bool keeps_memory,
+                  int n_chunks = 1) {
+    if (!q || !proj || !ctx) return fail(INFV_ERR_INVALID, "step: null argument");
+    if (int rc = check_chain_error(h)) return rc;
+    if (int rc = check_q(h, Q)) return rc;
+    Plan* plan = nullptr;
+    if (int rc = find_plan(h, T, &plan)) return rc;
+    const bool on_memory = keeps_memory && h->has_memory;          // the call's first step resamples an existing memory
+    if (h->cfg.sticky && !u && (on_memory || n_chunks > 1))         // (every step after the call's first one does)
+        return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
+    if (h->cfg.sticky && on_memory) {
+        if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
+        if (plan->dense.on && h->forced_mask && h->forced_mask != (1u << h->L) - 1u)
+            return fail(INFV_ERR_UNSUPPORTED, "dense plans: infv_ltm_set_bins must force every layer of the handle or none");
+    }
+    return INFV_OK;
+}
+
 // project the new rows of `n_chunks` pooled chunks into workspace set `set`
 int project_chunks(infv_ltm_handle h, const Plan& plan, bool inf, const float* kbar, int n_chunks, int T,
                    const ProjPtrs& pp, int set, int* splitk, long* split_stride, hipStream_t stream, int gemm_pad = 0) {
@@ -498,6 +519,8 @@ int infv_ltm_create(const infv_ltm_config* cfg, infv_ltm_handle* out) {
     if (cfg->d_in <= 0 || cfg->d_in % 32) return fail(INFV_ERR_UNSUPPORTED, "d_in=%d must be a positive multiple of 32", cfg->d_in);
     if (cfg->n_heads <= 0 || (cfg->n_heads * cfg->head_size) % 64) return fail(INFV_ERR_UNSUPPORTED, "n_heads*head_size must be a multiple of 64");
     if (cfg->tokens_per_frame <= 0 || cfg->nb_samples <= 0 || cfg->max_q <= 0) return fail(INFV_ERR_INVALID, "tokens_per_frame, nb_samples, max_q must be positive");
+    // the draw kernels hold the S resampled slots of a layer in LDS (draw_kernel, step_project_kernel, draw_videos_kernel: 1024)
+    if (cfg->nb_samples > kMaxSamples) return fail(INFV_ERR_UNSUPPORTED, "nb_samples=%d (the draw kernels hold at most %d samples)", cfg->nb_samples, kMaxSamples);
     infv_ltm_s* h = new (std::nothrow) infv_ltm_s();
     if (!h) return fail(INFV_ERR_NOMEM, "out of host memory");
     h->cfg = *cfg;
@@ -812,6 +835,8 @@ int infv_ltm_consolidate_q(infv_ltm_handle h, const void* k, int32_t n_chunks, i
                            void* stream) {
     if (int rc = check_handle(h)) return rc;
     if (!k || n_chunks < 0) return fail(INFV_ERR_INVALID, "consolidate_q: bad arguments");
+    if (n_chunks > 0)
+        if (int rc = precheck_step(h, q, proj, ctx, T, Q, u, !new_doc, n_chunks)) return rc;
     if (new_doc) infv_ltm_reset(h);
     if (n_chunks == 0) return INFV_OK;
     const size_t need = (size_t)n_chunks * T * h->d * sizeof(float);
@@ -824,6 +849,7 @@ int infv_ltm_forward(infv_ltm_handle h, const void* k, int32_t T, const float* q
                      const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream) {
     if (int rc = check_handle(h)) return rc;
     if (!k) return fail(INFV_ERR_INVALID, "forward: null k");
+    if (int rc = precheck_step(h, q, proj, ctx, T, Q, u, !new_doc)) return rc;
     if (new_doc) infv_ltm_reset(h);
     HIP_TRY(h->kbar_ws.reserve((size_t)T * h->d * sizeof(float)));
     if (int rc = infv_ltm_pool(h, k, T, h->kbar_ws.as<float>(), stream)) return rc;
@@ -832,8 +858,11 @@ int infv_ltm_forward(infv_ltm_handle h, const void* k, int32_t T, const float* q
 
 int infv_ltm_forward_into(infv_ltm_handle h, const void* k, int32_t token_dtype, int32_t T, float* kbar, const float* q, int32_t Q,
                           const infv_ltm_proj* proj, const double* u, float* ctx, void* stream) {
+    if (int rc = check_handle(h)) return rc;
+    if (token_dtype != INFV_TOKENS_F32 && token_dtype != INFV_TOKENS_BF16) return fail(INFV_ERR_INVALID, "forward_into: unknown token dtype %d", token_dtype);
+    if (T <= 0 || !k || !kbar) return fail(INFV_ERR_INVALID, "forward_into: T must be positive, k and kbar non-null");
+    if (int rc = precheck_step(h, q, proj, ctx, T, Q, u, true)) return rc;
     if (int rc = infv_ltm_set_token_dtype(h, token_dtype)) return rc;
-    if (T <= 0) return fail(INFV_ERR_INVALID, "forward_into: T must be positive");
     if (int rc = infv_ltm_pool(h, k, T, kbar, stream)) return rc;
     return infv_ltm_step(h, kbar, T, q, Q, proj, u, ctx, stream);
 }
@@ -1285,8 +1314,8 @@ static int consolidate_impl(infv_ltm_handle h, const void* k_, const float* kbar
     if (n_chunks == 0) return INFV_OK;
     const int rows_max = plan->first.rows > plan->inf.rows ? plan->first.rows : plan->inf.rows;
     if (plan->dense.on || !chain_supported(h->N, h->S, rows_max, plan->inf.tabw) || (h->L * h->H * Q) % 128 != 0 || (h->L * h->dm) % 128 != 0 ||
-        !uc_supported(h->N, h->d, h->dm, plan->inf.tabw, rows_max)) {
-        // shapes the fused chain kernel cannot hold in LDS: per-chunk stage kernels
+        !uc_supported(h->N, h->d, h->dm, plan->inf.tabw, rows_max) || !qtilde_supported(Q)) {
+        // shapes the fused chain kernel cannot hold in LDS (or whose query block qtilde_kernel does not take): per-chunk stage kernels
         for (int c = 0; c < n_chunks; ++c) {
             if (kbar_pre) {
                 if (int rc = infv_ltm_step(h, kbar_pre + (size_t)c * T * h->d, T, q, Q, proj, u ? u + c * chunk_u : nullptr,

@@ -9,6 +9,7 @@ namespace infv {
 
 constexpr int kMaxLayers = 8;
 constexpr int kHeadSize = 64;      // dh the attend kernel is written for
+constexpr int kMaxSamples = 1024;  // nb_samples the draw kernels hold in LDS (infv_ltm_create refuses more)
 constexpr int kQTile = 16;         // query rows per attend workgroup (one MFMA row tile)
 // Layout of the fixed-point sticky bin-mass accumulators (u64 words, 128 per layer): bin j lives at word acc_word(j), which
 // interleaves the two halves of the histogram -- words (2 i, 2 i + 1) = bins (i, i + 64) -- so that ONE 16-byte load per
@@ -99,6 +100,7 @@ hipError_t launch_project_scores(int M, int d, int n_out, const float* qt, const
                                  hipStream_t stream, int lds_pad = 0);
 hipError_t launch_project_values(int M, int d, int dm, int n_layers, const ProjPtrs& proj, const float* R, float* C,
                                  int ldc, hipStream_t stream, int lds_pad = 0);
+bool qtilde_supported(int Q);          // the pre-multiplied queries of the fused chain: Q <= 256
 hipError_t launch_qtilde(const float* q, int Q, int H, int d, int n_layers, const ProjPtrs& proj, float* qt, float* cq,
                          hipStream_t stream);
 

@@ -942,6 +942,7 @@ hipError_t launch_project_values(int M, int d, int dm, int n_layers, const ProjP
 
 // qt[(l*H + h)*Q + q][:] = sum_e (q[l][q][h*64+e] / sqrt(dh)) * Wk[l][h*64+e][:]   and   cq[(l*H+h)*Q + q] = q_h . bk_h / sqrt(dh)
 // so that  S'new = (q/sqrt(dh)) . (R Wk^T)_h^T = R . qt^T  without projecting the K half of the new rows.
+constexpr int kQtildeMaxQ = 256;      // qtilde_kernel: 256 threads (one per row of cq), [Q][64] floats = 64 KB of LDS
 __global__ __launch_bounds__(256) void qtilde_kernel(const float* __restrict__ q, int Q, int H, int d, ProjPtrs proj,
                                                      float* __restrict__ qt, float* __restrict__ cq) {
     extern __shared__ float qs[];                      // [Q][64] scaled query slice of this head
@@ -975,8 +976,12 @@ __global__ __launch_bounds__(256) void qtilde_kernel(const float* __restrict__ q
     }
 }
 
+// one thread per query row writes the bias term cq, the scaled query slice [Q][64] lives in (default-limit) dynamic LDS
+bool qtilde_supported(int Q) { return Q >= 1 && Q <= kQtildeMaxQ; }
+
 hipError_t launch_qtilde(const float* q, int Q, int H, int d, int n_layers, const ProjPtrs& proj, float* qt, float* cq,
                          hipStream_t stream) {
+    if (!qtilde_supported(Q)) return hipErrorInvalidValue;      // (infv_ltm_consolidate sends longer queries to the per-chunk step)
     INFV_LAUNCH(qtilde_kernel, dim3(H, n_layers, (d + 255) / 256), dim3(256), (size_t)Q * kHeadSize * sizeof(float), stream, q, Q, H,
                        d, proj, qt, cq);
     return hipGetLastError();
@@ -994,7 +999,7 @@ __global__ __launch_bounds__(256) void draw_kernel(const float* __restrict__ bin
                                                    const int32_t* __restrict__ bins_forced, unsigned forced_mask) {
     __shared__ float cdf[kBins];
     __shared__ double gsum[256];
-    __shared__ int32_t sidx[1024];
+    __shared__ int32_t sidx[kMaxSamples];
     const int l = blockIdx.x;
     const bool ovr = (override_mask >> l) & 1u;
     const DrawRegs<4> r = draw_load<256, 4>(bin_part + (long)l * parts * kBins, parts, nullptr, probs_override + l * kBins,
@@ -1006,7 +1011,7 @@ __global__ __launch_bounds__(256) void draw_kernel(const float* __restrict__ bin
 hipError_t launch_draw(const float* bin_part, int parts, const float* probs_override, unsigned override_mask,
                        const StickyView& sticky, const double* u, int S, int n_layers, float* probs,
                        int32_t* bins, int32_t* idx, hipStream_t stream, const int32_t* bins_forced, unsigned forced_mask) {
-    if (S > 1024) return hipErrorInvalidValue;
+    if (S > kMaxSamples) return hipErrorInvalidValue;          // (infv_ltm_create refuses such a handle)
     INFV_LAUNCH(draw_kernel, dim3(n_layers), dim3(256), 0, stream, bin_part, parts, probs_override,
                        override_mask, sticky, u, S, probs, bins, idx, bins_forced, forced_mask);
     return hipGetLastError();
@@ -1572,7 +1577,7 @@ __global__ __launch_bounds__(256) void draw_videos_kernel(VideoStep vs, int part
                                                           int S, int n_layers) {
     __shared__ float cdf[kBins];
     __shared__ double gsum[256];
-    __shared__ int32_t sidx[1024];
+    __shared__ int32_t sidx[kMaxSamples];
     const int l = blockIdx.x, j = blockIdx.y;
     const VideoDesc* v = vs.vd + j;
     const bool first = vs.s == vs.mask_step;
@@ -1594,7 +1599,7 @@ __global__ __launch_bounds__(256) void draw_videos_kernel(VideoStep vs, int part
 
 hipError_t launch_draw_videos(const VideoStep& vs, int parts, const StickyView& sticky, const double* u, int S, int n_layers,
                               hipStream_t stream) {
-    if (S > 1024) return hipErrorInvalidValue;
+    if (S > kMaxSamples) return hipErrorInvalidValue;          // (infv_ltm_create refuses such a handle)
     if (vs.n == 0) return hipSuccess;
     INFV_LAUNCH(draw_videos_kernel, dim3(n_layers, vs.n), dim3(256), 0, stream, vs, parts, sticky, u, S, n_layers);
     return hipGetLastError();
