@@ -7,6 +7,9 @@
 // exp_env(), which only looks at the environment in the experiments build (-DINFV_EXPERIMENTS:
 // libinfv_ltm_exp.so, what tools/ and the variant / fault-injection tests load through INFV_LTM_LIBRARY=exp).  In the
 // shipped library exp_env() is a constant nullptr: no hidden work-skipping or tuning switch can change what it runs.
+// A variant that was measured and rejected is deleted, selector and code together, rather than kept behind a knob: its
+// measurements stay in profiles/ and docs/NOTEBOOK.md (so went round 5's call-long role S, resident GEMM and mailbox exchange,
+// round 6's LDS-DMA loader of role S, the CU-mask experiment and the sub-batch schedule sweeps).
 #pragma once
 #include <cstdlib>
 

@@ -167,7 +167,6 @@ struct infv_ltm_s {
     DeviceBuf crit_ring, tabb_ring;              // chain_batch3_kernel -> alpha_rows2_kernel: point scores, drawn-bin tables
     int ring = 0;
     hipStream_t ucs = nullptr;          // stream of the UC kernels (state update + read-out of a sub-batch)
-    hipStream_t chain_s = nullptr;      // role S's own stream (highest priority: a hardware queue it shares with no worker stream), where the call-long launch lives
     hipEvent_t ev_s[kPSets] = {}, ev_uc[kPSets] = {};
     DeviceBuf sync_words;              // [0..7] arrival counters per layer
     // error word of the persistent chain kernel: pinned host memory mapped into the device, so a time-out is
@@ -190,17 +189,9 @@ struct infv_ltm_s {
     DeviceBuf uf_all;                  // a consolidate call's Gibbs uniforms as fp32 round-ups [n_chunks][L][S] (chain_batch3_kernel's search)
     DeviceBuf step_tab;                // per-call path: resolved gather table of the step [L][N][tabw] (written by the draw plane of step_project)
     DeviceBuf psi_Y, psi_E, psi_Eg, psi_alpha;   // general-psi step: resampled rows, edge scores, grid scores / probabilities, read-out weights
-    DeviceBuf R_all, planes_all[3];    // call-long pooling launch: every new row of the call (fp32, and as three bf16 planes per sub-batch for the projection GEMM)
+    DeviceBuf R_all, planes_all[3];    // one pooling launch per call: every new row of the call (fp32, and as three bf16 planes per sub-batch for the projection GEMM)
     DeviceBuf pool_done;               // ... and its per-sub-batch completion counts
-    DeviceBuf gemm_flags;              // call-long projection GEMM: [0] tile queue head, [64] sub-batches whose UC kernel is done, [128 + b] S' tiles, [128 + cap + b] V' tiles of sub-batch b; the descriptor behind them
-    long gemm_flags_cap = 0;
-    DeviceBuf call_flags;              // call-long role S: [0] sub-batches projected (GEMM stream -> role S), [64] workgroup x sub-batch completions (role S -> UC stream); words 256 B apart
-    DeviceBuf call_stats;              // call-long role S: [0] ticks (100 MHz) workgroup 0 waited for projections, [1] how many sub-batches it waited for
-    hipEvent_t ev_chain = nullptr;     // the call-long role-S launch has finished (recorded on its stream)
-    std::mutex* issue_mu = nullptr;    // the device's consolidate-issue lock (SharedStreams::issue)
     DeviceBuf vid_tab, vid_kbar, vid_P;   // infv_ltm_consolidate_videos with this handle first: video table, pooled frames and projected rows of one step
-    DeviceBuf mbox;                    // chain_batch3_kernel: mailboxes of role S's exchange + placement handshake (chain_mailbox_bytes)
-    int mbox_G = 0;                    // workgroups per layer the mailboxes are laid out for
     int sc = 0;
     int n_bins = 128;
     Profiler prof;
@@ -210,14 +201,12 @@ struct infv_ltm_s {
         if (side) (void)hipStreamSynchronize(side);
         if (ucs) (void)hipStreamSynchronize(ucs);
         if (pools) (void)hipStreamSynchronize(pools);
-        if (chain_s) (void)hipStreamSynchronize(chain_s);
         for (int i = 0; i < kPSets; ++i) if (ev_pool[i]) (void)hipEventDestroy(ev_pool[i]);
         for (int i = 0; i < kRSets; ++i) if (ev_r[i]) (void)hipEventDestroy(ev_r[i]);
         for (int i = 0; i < kPSets; ++i) { if (ev_s[i]) (void)hipEventDestroy(ev_s[i]); if (ev_uc[i]) (void)hipEventDestroy(ev_uc[i]); }
         if (ev_in) (void)hipEventDestroy(ev_in);
         if (ev_start) (void)hipEventDestroy(ev_start);
         if (ev_q) (void)hipEventDestroy(ev_q);
-        if (ev_chain) (void)hipEventDestroy(ev_chain);
         for (int i = 0; i < kPSets; ++i) { if (ev_p[i]) (void)hipEventDestroy(ev_p[i]); }
         if (err_host) (void)hipHostFree(err_host);
     }
@@ -952,35 +941,11 @@ struct FastPipe {
         return INFV_OK;
     }
 
-    // role S of the WHOLE call in one launch: `n` steps in `n_batches` sub-batches of `sub` (the last may be shorter) whose S'new
-    // rows arrive in workspace set (sub-batch % n_sets)
-    struct CallLong { int sub, n_batches; const float* const* sets; int n_sets; int sk_last; long ss_last;
-                      const unsigned int* tiles_s; int n_tiled, tiles_full, tiles_last; };
-    int launch_s_call(int n, int sub, int n_batches, const float* const* sets, int n_sets, int sk_main, long ss_main, int sk_last, long ss_last,
-                      const double* u, const float* uf, const unsigned int* tiles_s = nullptr, int n_tiled = 0, int tiles_full = 0, int tiles_last = 0) {
-        const CallLong cl{sub, n_batches, sets, n_sets, sk_last, ss_last, tiles_s, n_tiled, tiles_full, tiles_last};
-        return launch_s_batch(n, sets[0], sk_main, ss_main, u, uf, &cl);
-    }
-
     // role S of `n` consecutive infinite-memory chunks in one persistent launch
-    int launch_s_batch(int n, const float* Snew, int sk, long ss, const double* u, const float* uf, const CallLong* cl = nullptr) {
+    int launch_s_batch(int n, const float* Snew, int sk, long ss, const double* u, const float* uf) {
         static int prev_n = 0;                     // (experiments: steps of the previous launch, for the stamps' average)
         ChainBatchArgs b;
         memset(&b, 0, sizeof(b));
-        if (cl != nullptr) {
-            // the sub-batch description travels through device memory (a small kernel in front of the launch writes it)
-            ChainCallDesc cd;
-            memset(&cd, 0, sizeof(cd));
-            cd.ready = h->call_flags.as<unsigned int>(); cd.done = h->call_flags.as<unsigned int>() + 64;
-            cd.tiles_s = cl->tiles_s; cd.n_tiled = cl->n_tiled; cd.tiles_full = cl->tiles_full; cd.tiles_last = cl->tiles_last;
-            cd.sub = cl->sub; cd.n_batches = cl->n_batches; cd.n_sets = cl->n_sets;
-            for (int i = 0; i < cl->n_sets && i < kCallSets; ++i) cd.snew_set[i] = cl->sets[i];
-            cd.sk_last = cl->sk_last; cd.ss_last = cl->ss_last;
-            cd.stats = h->call_stats.as<long long>();
-            ChainCallDesc* dst = reinterpret_cast<ChainCallDesc*>(h->call_flags.as<char>() + 512);
-            HIP_TRY(launch_chain_call_desc(dst, cd, stream));
-            b.call = dst; b.call_sub = cl->sub;
-        }
         const int QS = chain_s_tiles(Q);
         b.N = h->N; b.H = h->H; b.Q = Q; b.QS = QS; b.L = h->L; b.S = h->S;
         b.st = plan.sticky();
@@ -992,19 +957,6 @@ struct FastPipe {
         }
         b.n_steps = n; b.step0 = counter; b.ring = h->ring;
         b.first_from_parts = (counter == 0) ? 1 : 0;
-        b.first_from_acc = (counter > 0 && batch_launches == 0) ? 1 : 0;   // the step before ran in a per-chunk launch (first chunk of a document)
-        b.mbox = h->mbox.as<unsigned long long>();
-        { static int* rep = [] { int* p = nullptr; if (exp_env("INFV_XCC_REPORT")) { (void)hipMalloc(&p, 1024 * sizeof(int)); (void)hipMemset(p, 0xff, 1024 * sizeof(int)); } return p; }();
-          b.xcc_report = rep;
-          static int rep_calls = 0;
-          if (rep && (++rep_calls % 16) == 0) {
-              int hb[1024];
-              (void)hipStreamSynchronize(stream);
-              (void)hipMemcpy(hb, rep, sizeof(hb), hipMemcpyDeviceToHost);
-              fprintf(stderr, "[batch-S placement] (plain<<8 | xcc) per workgroup:");
-              for (int i = 0; i < 1024 && hb[i] != -1; ++i) fprintf(stderr, " %x", hb[i]);
-              fprintf(stderr, "\n");
-          } }
         b.part_prev = h->bin_part[h->pc].as<float>(); b.parts = h->parts;
         for (int i = 0; i < 3; ++i) b.acc[i] = h->mass_acc[i].as<unsigned long long>();
         b.arrive = h->sync_words.as<unsigned int>(); b.error = h->err_dev;
@@ -1200,12 +1152,13 @@ int batch_scores(infv_ltm_handle h, const Operator& op, int n_chunks, const floa
 // hardware queues (4 by default, GPU_MAX_HW_QUEUES): a second handle with four more streams of its own shared queues with
 // the first one's and its pipeline ran 12 % slower (107 k against 120 k chunks/s for the second engine of bench.py).
 // Handles are not re-entrant and their calls are issued from one host thread at a time, so FIFO order within a shared
-// stream is the order the host issued the work in; cross-stream dependencies are events, as before.
-struct SharedStreams { hipStream_t side = nullptr, pools = nullptr, ucs = nullptr, chain = nullptr; std::mutex issue; };   // issue: one consolidate call enqueues at a time
-// experiment INFV_CU_MASK=K: the first K CUs (in the runtime's CU-mask bit order) belong to role S alone -- its launches go to a
-// stream masked to them, the three worker streams are masked to the rest.  0 = no masks (default).
+// stream is the order the host issued the work in; cross-stream dependencies are events, as before.  No lock orders the calls
+// of different handles: the one kernel that spins, flag_wait_kernel on the `side` stream, waits only for a pooling launch
+// submitted before it (on `pools`, behind the call's own ev_start), and that pooling launch depends on nothing submitted later,
+// so whatever interleaving two handles' calls take, every wait is for work already ahead of it and ends.  (A second handle's
+// flag_wait_kernel can still hold the shared `side` stream for the other handle's whole pooling launch: a delay, not a deadlock.)
+struct SharedStreams { hipStream_t side = nullptr, pools = nullptr, ucs = nullptr; };
 bool host_serial() { static const bool v = exp_env("INFV_SERIAL") != nullptr; return v; }   // timing experiments: the host synchronises the streams (no overlap)
-int cu_mask_k() { static const int k = [] { const char* e = exp_env("INFV_CU_MASK"); return e ? atoi(e) : 0; }(); return k; }
 int shared_streams(int dev, SharedStreams** out) {
     static std::mutex mu;
     static SharedStreams pool[64];
@@ -1218,25 +1171,6 @@ int shared_streams(int dev, SharedStreams** out) {
         // INFV_PRIO_UCS / _POOL / _SIDE (experiments): -1 most urgent, 0 normal, 1 least urgent
         auto prio = [&](const char* name, int dflt) { const char* e = exp_env(name); int v = e ? atoi(e) : dflt; return v < hi ? hi : (v > lo ? lo : v); };
         const int prio_ucs = prio("INFV_PRIO_UCS", 0), prio_pool = prio("INFV_PRIO_POOL", lo), prio_side = prio("INFV_PRIO_SIDE", lo);
-        const int K = cu_mask_k();
-        if (K > 0) {
-            int cus = 0;
-            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            const int words = (cus + 31) / 32;
-            std::vector<uint32_t> ms(words, 0u), mo(words, 0u);
-            for (int i = 0; i < cus; ++i) ((i < K) ? ms : mo)[i / 32] |= 1u << (i % 32);
-            HIP_TRY(hipExtStreamCreateWithCUMask(&p.chain, words, ms.data()));
-            HIP_TRY(hipExtStreamCreateWithCUMask(&p.ucs, words, mo.data()));
-            HIP_TRY(hipExtStreamCreateWithCUMask(&p.pools, words, mo.data()));
-            HIP_TRY(hipExtStreamCreateWithCUMask(&p.side, words, mo.data()));
-            *out = &p;
-            return INFV_OK;
-        }
-        // Role S's stream: the call-long launch spin-waits on work of the three worker streams, so it must not sit in front of them
-        // in a hardware queue.  The runtime keeps separate queues per priority level: highest priority for role S alone, normal
-        // for the UC stream, lowest for pooling and GEMM.
-        static const bool own_chain_stream = [] { const char* e = exp_env("INFV_CHAIN_STREAM"); return e && atoi(e) != 0; }();
-        if (own_chain_stream) HIP_TRY(hipStreamCreateWithPriority(&p.chain, hipStreamNonBlocking, hi));
         HIP_TRY(hipStreamCreateWithPriority(&p.ucs, hipStreamNonBlocking, prio_ucs));
         HIP_TRY(hipStreamCreateWithPriority(&p.pools, hipStreamNonBlocking, prio_pool));
         HIP_TRY(hipStreamCreateWithPriority(&p.side, hipStreamNonBlocking, prio_side));   // last: marks the set complete
@@ -1267,7 +1201,7 @@ int ensure_side_stream(infv_ltm_handle h) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));                              // (the caller's current device: where the handle was created)
     if (int rc = shared_streams(dev, &sh)) return rc;
-    h->ucs = sh->ucs; h->pools = sh->pools; h->chain_s = sh->chain;
+    h->ucs = sh->ucs; h->pools = sh->pools;
     for (int i = 0; i < kPSets; ++i) {
         HIP_TRY(hipEventCreateWithFlags(&h->ev_s[i], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&h->ev_uc[i], hipEventDisableTiming));
@@ -1278,14 +1212,503 @@ int ensure_side_stream(infv_ltm_handle h) {
     HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_start, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&h->ev_chain, hipEventDisableTiming));
-    if (chain_call_long()) {                                   // (experiments build: hand-off words of the call-long launches)
-        HIP_TRY(h->call_flags.reserve(1024));                  // [0, 512): the two counters, [512, 1024): ChainCallDesc of the current call
-        HIP_TRY(h->call_stats.reserve(64));
-        HIP_TRY(hipMemset(h->call_stats.p, 0, 64));
-    }
-    h->issue_mu = &sh->issue;
     h->side = sh->side;                                       // last: h->side != nullptr means "streams and events exist"
+    return INFV_OK;
+}
+
+// ---- infv_ltm_consolidate: the stages of one call, in the order it runs them ----
+// The call's inputs and the decisions its stages take, one stage after the other.
+struct ConsolidateCall {
+    const Plan* plan; const char* k; const float* kbar_pre;   // k: frame tokens (byte addressing), or kbar_pre: the caller's frame means
+    int n_chunks, T, Q; const float* q; const infv_ltm_proj* proj; const ProjPtrs* pp; const double* u; float* ctx;
+    hipStream_t stream; void* stream_;
+    size_t chunk_k, chunk_ctx, chunk_u;            // bytes of one chunk's tokens; floats of one chunk's ctx / uniforms
+    // set-up
+    bool pool_call_wanted = false;                 // ONE pooling launch for the call, if the schedule allows it
+    const float* uf = nullptr;                     // the call's uniforms as fp32 round-ups (chain_batch3_kernel), or nullptr
+    // schedule: sub-batch b holds chunks [c0(b), c0(b) + nb(b))
+    bool persistent = false;                       // role S in one persistent launch per sub-batch (else one launch per chunk)
+    int first_c = 0, sub = 0, n_batches = 0;
+    size_t rows = 0;                               // new rows per chunk
+    bool split_pool = false; hipStream_t pools = nullptr;   // the pooling stream (the side stream when not split)
+    bool use_pr2 = false;                          // pool + rows in one kernel (pool_rows2_kernel)
+    int pr_u = 8, pr_pad = 0, pr_wgs = 0;          // its load width, LDS pad, grid cap
+    bool use_pool_call = false;                    // one pooling launch for the call ...
+    bool planes_call = false;                      // ... that also writes the bf16 planes of the projection GEMM
+    bool planes_in_pool = false;                   // the per-sub-batch pooling launches write those planes
+    bool uc_pending[kPSets] = {};                  // ev_uc[set] has been recorded in this call
+    int c0(int b) const { return first_c + b * sub; }
+    int nb(int b) const { return n_chunks - c0(b) < sub ? n_chunks - c0(b) : sub; }
+};
+
+// Shapes the fused chain kernel cannot hold in LDS (or whose query block qtilde_kernel does not take) run chunk by chunk
+// through the per-call stage kernels.
+bool fused_chain_holds(infv_ltm_handle h, const Plan& plan, int Q) {
+    const int rows_max = plan.first.rows > plan.inf.rows ? plan.first.rows : plan.inf.rows;
+    return !plan.dense.on && chain_supported(h->N, h->S, rows_max, plan.inf.tabw) && (h->L * h->H * Q) % 128 == 0 &&
+           (h->L * h->dm) % 128 == 0 && uc_supported(h->N, h->d, h->dm, plan.inf.tabw, rows_max) && qtilde_supported(Q);
+}
+
+int consolidate_per_chunk(infv_ltm_handle h, const ConsolidateCall& cc) {
+    for (int c = 0; c < cc.n_chunks; ++c) {
+        const double* uc = cc.u ? cc.u + c * cc.chunk_u : nullptr;
+        if (cc.kbar_pre) {
+            if (int rc = infv_ltm_step(h, cc.kbar_pre + (size_t)c * cc.T * h->d, cc.T, cc.q, cc.Q, cc.proj, uc, cc.ctx + c * cc.chunk_ctx,
+                                       cc.stream_)) return rc;
+        } else if (int rc = infv_ltm_forward(h, cc.k + c * cc.chunk_k, cc.T, cc.q, cc.Q, cc.proj, uc, 0, cc.ctx + c * cc.chunk_ctx,
+                                             cc.stream_)) return rc;
+    }
+    return INFV_OK;
+}
+
+// Per-call set-up on the caller's stream: the pooling launch's counters, the rings of role S's outputs, the pre-multiplied
+// queries, the weight planes of the projection GEMM and the fp32 uniforms.
+int consolidate_setup(infv_ltm_handle h, ConsolidateCall& cc, const FastPipe& pipe) {
+    const Plan& plan = *cc.plan;
+    hipStream_t stream = cc.stream;
+    const ProjPtrs& pp = *cc.pp;
+    h->wv_split_valid = false;                                // the caller's value weights may have changed since the last call
+    // ONE pooling launch per call (round 6, shipped for calls of 768 chunks and more): the pooling stream is what bounds a long call,
+    // and between its per-sub-batch launches sat an event record, a wait for the R set's last reader and the ramp of 2688 fresh
+    // workgroups (13 us per boundary by the residency stamps).  The launch walks every (chunk, row) of the call in order, writes rows
+    // and bf16 planes write-through and counts them into one word per sub-batch; the GEMM stream holds on that word with a one-wave
+    // flag_wait_kernel (bounded, latches the handle's error word) instead of an event.  Role S, the GEMM, alpha and UC keep their
+    // per-sub-batch launches: 13.3 against 13.7 ms per video on one box, four rounds (profiles/r06_matrix.txt, block 12), same bits.
+    // Rows + planes of the whole call live in HBM (0.49 MB per chunk: 1 GB at 2048 chunks); above kPoolCallBudget the call keeps its
+    // per-sub-batch pooling launches.  INFV_POOL_CALL (experiments build): 0 never, 2 always.
+    static const int pool_call_env = [] { const char* e = exp_env("INFV_POOL_CALL"); return e ? atoi(e) : -1; }();
+    constexpr size_t kPoolCallBudget = (size_t)16 << 30;
+    const size_t pool_call_bytes = (size_t)cc.n_chunks * (size_t)plan.inf.rows * h->d * (sizeof(float) + 3 * sizeof(__bf16));
+    cc.pool_call_wanted = pool_call_env >= 0 ? pool_call_env == 2 : (cc.n_chunks >= 768 && pool_call_bytes <= kPoolCallBudget);
+    if (cc.pool_call_wanted) {   // its completion counts restart with the call (before ev_start: the pooling stream starts behind it)
+        const size_t need_pd = ((size_t)cc.n_chunks + 1) * sizeof(unsigned int);
+        if (need_pd > h->pool_done.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->pool_done.reserve(need_pd < 32768 ? 32768 : need_pd)); }
+        HIP_TRY(hipMemsetAsync(h->pool_done.p, 0, need_pd, stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev_start, stream));
+    HIP_TRY(hipMemsetAsync(h->mass_acc[0].p, 0, h->mass_acc[0].bytes, stream));   // slot of the call's first step
+    {   // rings of role S's per-chunk outputs (sized for this call's Q)
+        const size_t need_a = (size_t)h->ring * pipe.alpha_slot() * sizeof(float);
+        if (need_a > h->alpha_ring.bytes) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(h->alpha_ring.reserve(need_a));
+            HIP_TRY(h->asum_ring.reserve((size_t)h->ring * pipe.asum_slot() * sizeof(float)));
+            HIP_TRY(h->tab_ring.reserve((size_t)h->ring * pipe.tab_slot() * sizeof(int32_t)));
+            HIP_TRY(h->tabb_ring.reserve((size_t)h->ring * pipe.tab_slot() * sizeof(int32_t)));
+            HIP_TRY(h->crit_ring.reserve((size_t)h->ring * pipe.crit_slot() * sizeof(float)));
+        }
+    }
+    // pre-multiplied queries qt = (q/sqrt(dh)) . Wk_h and the bias term cq = q_h . bk_h / sqrt(dh), once per call
+    HIP_TRY(launch_qtilde(cc.q, cc.Q, h->H, h->d, h->L, pp, h->qt_buf.as<float>(), h->cqbuf.as<float>(), stream));
+    h->w3_valid = false;
+    const long n_rows = (long)h->L * h->dm + (long)h->L * h->H * cc.Q;
+    if (h->proj_x6 && h->d % 32 == 0 && n_rows % 8 == 0) {
+        // bf16 planes of the projection GEMM's weight rows [Wv_0 ; ... ; Wv_{L-1} ; q~] (the caller's weights may change between calls)
+        const size_t szW = (size_t)n_rows * h->d * sizeof(__bf16);
+        if (szW > h->w3[0].bytes) {
+            HIP_TRY(hipDeviceSynchronize());
+            for (int i = 0; i < 3; ++i) HIP_TRY(h->w3[i].reserve(szW));
+        }
+        for (int l = 0; l < h->L; ++l)
+            HIP_TRY(launch_split3_rows(pp.wv[l], h->d, h->dm, h->d, h->w3[0].p, h->w3[1].p, h->w3[2].p, (long)l * h->dm, n_rows, stream));
+        HIP_TRY(launch_split3_rows(h->qt_buf.as<float>(), h->d, (long)h->L * h->H * cc.Q, h->d, h->w3[0].p, h->w3[1].p, h->w3[2].p,
+                                   (long)h->L * h->dm, n_rows, stream));
+        h->w3_valid = true;
+    }
+    HIP_TRY(hipEventRecord(h->ev_q, stream));                 // the side stream's projections need no more than this
+    // the persistent role S searches in fp32 against the round-ups of the f64 uniforms (equivalent to the f64 compare):
+    // converted once per call, off the chain
+    if (cc.u && h->cfg.sticky && chain_batch3_shape_ok(1, plan.sticky().points_ok, plan.inf.rows, h->S, cc.Q)) {
+        const size_t need_u = (size_t)cc.n_chunks * cc.chunk_u * sizeof(float);
+        if (need_u > h->uf_all.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->uf_all.reserve(need_u)); }
+        HIP_TRY(launch_round_up_uniforms(cc.u, h->uf_all.as<float>(), (long)cc.n_chunks * (long)cc.chunk_u, stream));
+        cc.uf = h->uf_all.as<float>();
+    }
+    return INFV_OK;
+}
+
+// The schedule (host decisions only): role S's form, the sub-batches, the pooling form.
+void consolidate_schedule(infv_ltm_handle h, ConsolidateCall& cc) {
+    const Plan& plan = *cc.plan;
+    const int mode = h->cfg.sticky ? 1 : 2;
+    // INFV_PERSISTENT=0 falls back to one role-S launch per chunk
+    static const bool want_persistent = [] { const char* e = exp_env("INFV_PERSISTENT"); return !e || atoi(e) != 0; }();
+    cc.persistent = want_persistent &&
+        chain_batch_supported(h->N, h->S, plan.inf.rows, plan.inf.tabw, h->H * chain_s_tiles(cc.Q) * h->L) &&
+        chain_batch_resident(h->N, h->S, plan.inf.rows, plan.inf.tabw,
+                             chain_batch_blocks(h->H, cc.Q, h->L, mode, plan.sticky().points_ok, plan.inf.rows, h->S),
+                             mode, plan.sticky().points_ok, cc.Q);
+    cc.first_c = h->has_memory ? 0 : 1;                      // the first chunk of a document runs on its own (consolidate_first_chunk)
+    // sub-batch size: long calls amortise the per-launch gap of role S over more chunks (42 x 64 new rows = 21 row tiles:
+    // 126 score tiles, 252 V' tiles); short ones (e.g. a 256-chunk shard of a multi-GPU run) keep 32 so that the
+    // pipeline fills and drains quickly.  INFV_SUB_BATCH overrides.  Every sub-batch but the last has `sub` chunks.
+    static const int sub_env = [] { const char* e = exp_env("INFV_SUB_BATCH"); return e ? atoi(e) : 0; }();
+    cc.sub = h->maxC;
+    if (sub_env > 0) cc.sub = sub_env < h->maxC ? sub_env : h->maxC;
+    else if (cc.n_chunks < 768 && cc.sub > 32) cc.sub = 32;  // (28 while the V' GEMM ran on the UC stream; 2.84 -> 2.68 ms per 256 chunks)
+    cc.n_batches = (cc.n_chunks - cc.first_c + cc.sub - 1) / cc.sub;
+    cc.rows = plan.inf.rows;
+    // The pooling has its own stream so that the HBM-bound pooling of batch b+2 overlaps the MFMA-bound projection of
+    // batch b+1 (pooled frames are triple-buffered either way); INFV_SPLIT_POOL=0 puts it back on the side stream.
+    // (Round 1 measured this worse, 87 k vs 95 k chunks/s, because role S was then sensitive to every concurrent
+    // kernel; with chain_batch2_kernel and no padding LDS on the GEMMs it is better: 112 k vs 102 k.)
+    static const bool split_pool_env = [] { const char* e = exp_env("INFV_SPLIT_POOL"); return !e || atoi(e) != 0; }();
+    cc.split_pool = split_pool_env && !cc.kbar_pre;           // (frame means handed in: there is no pooling stage)
+    cc.pools = cc.split_pool ? h->pools : h->side;
+    // Pool + rows in one kernel: the pooling stream writes the sub-batch's new rows R straight from the tokens -- in this path
+    // the frame means are consumed by the rows kernel only; same bits either way.  Default: pool_rows2_kernel (one short-lived
+    // workgroup per (chunk, row), a wave per frame and slice): no kbar round trip through HBM, no rows kernel on the side
+    // stream, and the pooling stream runs up to kRSets sub-batches ahead instead of three.  Measured in situ (round 3,
+    // tools/sweep_r03s.sh, alternating on one box): 132.5 k against 130.5 k chunks/s, pooling stream 14.65 against 15.05 ms.
+    // The experiments build keeps INFV_POOL_ROWS=0 (pool_frames_kernel + build_rows_kernel, the round-2 form, still used when
+    // frame means are handed in or the width has no pool_rows2 shape).  (Round 3's long-lived grid-stride form, pool_rows_kernel,
+    // streamed faster alone -- 218-270 us per launch against 304 -- but cost the chain launches their CUs, 116-121 k: deleted.)
+    static const int pr_env = [] { const char* e = exp_env("INFV_POOL_ROWS"); return e ? atoi(e) : 2; }();
+    static const int pr_u = [] { const char* e = exp_env("INFV_PR_U"); return e ? atoi(e) : 8; }();
+    static const int pr_pad = [] { const char* e = exp_env("INFV_PR_PAD"); return e ? atoi(e) : 84 * 1024; }();
+    static const int pr_wgs = [] { const char* e = exp_env("INFV_PR_WGS"); return e ? atoi(e) : 0; }();
+    cc.use_pr2 = pr_env == 2 && !cc.kbar_pre && pool_rows2_supported(h->d);
+    cc.pr_u = pr_u; cc.pr_pad = pr_pad; cc.pr_wgs = pr_wgs;
+    // the one pooling launch (see consolidate_setup): rows and their bf16 planes for the whole call in HBM (402 + 604 MB at 2048
+    // chunks), the GEMM stream follows it through per-sub-batch completion counts
+    cc.use_pool_call = cc.pool_call_wanted && cc.persistent && cc.n_batches > 0 && !host_serial() && cc.use_pr2 && cc.pr_wgs == 0 &&
+                       !(skip_mask() & 1);
+    cc.planes_call = cc.use_pool_call && h->proj_x6 && h->d % 32 == 0 && !h->vproj_on_uc(cc.n_chunks);
+    // per-sub-batch pooling launches: the kernel writes the bf16 planes of its rows too (no split3_rows_kernel, no re-read of R).
+    // Long calls only (round 6, same-box A/B, `profiles/r06_matrix.txt` block 10): a call of 768 chunks and more is bound by the role-S
+    // stream and the planes cost the pooling nothing (150.4 against 149.0 k chunks/s, four rounds); a short call -- the 256-chunk
+    // shard of the 8-GPU split -- is bound by its pooling launches, which the extra stores lengthen: 2.14-2.17 ms with
+    // split3_rows_kernel on the side stream against 2.20-2.24 with the planes written by the pooling kernel.  Same bits either way.
+    // (INFV_POOL_PLANES, experiments build: 0 = never, 2 = always.)
+    static const int planes_env = [] { const char* e = exp_env("INFV_POOL_PLANES"); return e ? atoi(e) : 1; }();
+    cc.planes_in_pool = (planes_env == 2 || (planes_env == 1 && cc.n_chunks >= 768)) && cc.use_pr2 && !cc.use_pool_call && h->proj_x6 &&
+                        h->w3_valid && h->d % 32 == 0 && !h->vproj_on_uc(cc.n_chunks) && cc.n_batches > 0;
+}
+
+// The first chunk of a document (first-chunk operator, workspace set 2) -- or, continuing a memory, the scores of its K' rows
+// under this call's query.
+int consolidate_first_chunk(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pipe) {
+    const Plan& plan = *cc.plan;
+    hipStream_t stream = cc.stream, ucs = h->ucs;
+    if (!h->has_memory) {
+        const float* kb0 = cc.kbar_pre;
+        if (!kb0) {
+            if ((size_t)cc.T * h->d * sizeof(float) > h->kbar_ws.bytes) HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(h->kbar_ws.reserve((size_t)cc.T * h->d * sizeof(float)));
+            if (int rc = infv_ltm_pool(h, cc.k, cc.T, h->kbar_ws.as<float>(), cc.stream_)) return rc;
+            kb0 = h->kbar_ws.as<float>();
+        }
+        int sk = 1; long ss = 0;
+        if (int rc = project_chunks_fast(h, plan, false, kb0, 1, cc.T, cc.Q, *cc.pp, 2, &sk, &ss, stream, 0, false, kRSets)) return rc;
+        const long v_cols = (long)h->L * h->dm;             // a GEMM output row is [ V' (L*dm) | scores (L*H*Q) ]
+        const StepS st{&plan.first, false, h->P_ws[2].as<float>() + v_cols, nullptr, sk, ss};
+        if (int rc = pipe.launch_s(st)) return rc;
+        HIP_TRY(hipEventRecord(h->ev_s[2], stream));
+        HIP_TRY(hipStreamWaitEvent(ucs, h->ev_s[2], 0));
+        if (int rc = pipe.launch_uc(plan.first, false, 1, 0, h->R_ws[kRSets].as<float>(), h->P_ws[2].as<float>(), sk, ss, cc.ctx, ucs)) return rc;
+        HIP_TRY(hipEventRecord(h->ev_uc[2], ucs));
+        cc.uc_pending[2] = true;
+    } else if (h->carry_scores && h->last_fast && h->lastQ == cc.Q) {
+        // ... handed over by infv_ltm_import_chain_state: the scores under this query and the projected memory are the
+        // exporting handle's own; nothing is re-derived, the chain goes on bit for bit
+    } else {
+        // ... bias-free scores of the current K' rows under this query
+        if (h->k_stale)
+            if (int rc = infv_ltm_reproject(h, cc.proj, cc.stream_)) return rc;
+        Timed t_(h->prof, INFV_KERNEL_SCORES, stream);
+        HIP_TRY(launch_new_scores(cc.q, cc.Q, h->H, h->L, 1, h->N, h->KV[h->cur].as<float>(), 0, 2L * h->dm,
+                                  (long)h->N * 2 * h->dm, 1, 0, *cc.pp, h->Sp[h->sc].as<float>(), h->cqbuf.as<float>(), stream));
+    }
+    h->carry_scores = false;
+    return INFV_OK;
+}
+
+// The workspaces of the sub-batches, sized ahead of their first launch (a growth synchronises the device).
+int consolidate_workspaces(infv_ltm_handle h, const ConsolidateCall& cc) {
+    const int n_chunks = cc.n_chunks, T = cc.T, Q = cc.Q, first_c = cc.first_c, sub = cc.sub, n_batches = cc.n_batches;
+    const size_t rows = cc.rows;
+    if (!cc.kbar_pre && !cc.use_pr2) {
+        const size_t need = (size_t)h->maxC * T * h->d * sizeof(float);
+        if (need > h->kbar_side[0].bytes) {
+            HIP_TRY(hipDeviceSynchronize());
+            for (int i = 0; i < kPSets; ++i) HIP_TRY(h->kbar_side[i].reserve(need));
+        }
+    }
+    if (n_batches > 0) {                                      // the rotating R sets are written off the side stream: size them here
+        const size_t needR = (size_t)sub * rows * h->d * sizeof(float);
+        bool grow = false;
+        for (int i = 0; i < kRSets; ++i) grow = grow || needR > h->R_ws[i].bytes;
+        if (grow) {
+            HIP_TRY(hipDeviceSynchronize());
+            for (int i = 0; i < kRSets; ++i) HIP_TRY(h->R_ws[i].reserve(needR));
+        }
+    }
+    if (cc.use_pool_call) {
+        // every workspace the loop would grow (a growth synchronises the device: fatal beside a kernel that waits for the loop's work)
+        const long ld = (long)h->L * h->dm + (long)h->L * h->H * Q;
+        size_t needP = 0;
+        for (int b = 0; b < n_batches; ++b) {
+            const size_t M = (size_t)cc.nb(b) * rows;
+            const size_t np = M * ld * sizeof(float) * (M < 1024 ? 8 : 1);
+            if (np > needP) needP = np;
+        }
+        const size_t need3 = (size_t)(h->maxC > sub ? h->maxC : sub) * rows * h->d * sizeof(__bf16);
+        const size_t szW = (size_t)h->L * h->dm * h->d * 2, szR = (size_t)(h->maxC > sub ? h->maxC : sub) * rows * h->d * 2;
+        const size_t needRall = (size_t)(n_chunks - first_c) * rows * h->d * sizeof(float);
+        const size_t needPl = cc.planes_call ? needRall / 2 : 0;
+        bool grow = needRall > h->R_all.bytes || needPl > h->planes_all[0].bytes;
+        for (int i = 0; i < kPSets; ++i) grow = grow || needP > h->P_ws[i].bytes;
+        if (h->proj_x6) for (int i = 0; i < 3; ++i) grow = grow || need3 > h->r3[i].bytes;
+        if (h->v_split) grow = grow || szW > h->wv_hi.bytes || szR > h->R_hi.bytes;
+        if (grow) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(h->R_all.reserve(needRall));
+            for (int i = 0; i < 3; ++i) HIP_TRY(h->planes_all[i].reserve(needPl));
+            for (int i = 0; i < kPSets; ++i) HIP_TRY(h->P_ws[i].reserve(needP));
+            if (h->proj_x6) for (int i = 0; i < 3; ++i) HIP_TRY(h->r3[i].reserve(need3));
+            if (h->v_split) {
+                HIP_TRY(h->wv_hi.reserve(szW)); HIP_TRY(h->wv_lo.reserve(szW));
+                HIP_TRY(h->R_hi.reserve(szR)); HIP_TRY(h->R_lo.reserve(szR));
+                h->wv_split_valid = false;
+            }
+        }
+    }
+    if (cc.planes_in_pool) {
+        const size_t need3r = (size_t)sub * rows * h->d * sizeof(__bf16);
+        bool grow3 = false;
+        for (int i = 0; i < kRSets; ++i) grow3 = grow3 || need3r > h->r3_ring[i][0].bytes;
+        if (grow3) {
+            HIP_TRY(hipDeviceSynchronize());
+            for (int i = 0; i < kRSets; ++i) for (int j = 0; j < 3; ++j) HIP_TRY(h->r3_ring[i][j].reserve(need3r));
+        }
+    }
+    return INFV_OK;
+}
+
+// The V' half of sub-batch projection `set` (nb chunks, new rows r_rows) as its own GEMM on the UC stream `vs`
+// (INFV_VPROJ_ON_UC=1, or implied by the split-bf16 V' projection).
+int project_values_on_uc(infv_ltm_handle h, const ConsolidateCall& cc, int set, int nb, const float* r_rows, hipStream_t vs, int gemm_pad) {
+    const Plan& plan = *cc.plan;
+    const ProjPtrs& pp = *cc.pp;
+    const int Q = cc.Q;
+    // V' half of this sub-batch's projection: needs the new rows (ev_p), feeds only the UC kernel below
+    HIP_TRY(hipStreamWaitEvent(vs, h->ev_p[set], 0));
+    Timed t_(h->prof, INFV_KERNEL_PROJECT, vs);
+    const long Mv = (long)nb * plan.inf.rows;
+    const int v_cols = h->L * h->dm, p_ld = h->L * h->dm + h->L * h->H * Q;
+    // exact fp32 MFMA by default.  INFV_VPROJ_SPLIT=1: V' only feeds the read-out (1e-3 budget), so it may run as a
+    // split-bf16 contraction (three bf16 MFMA products, ~1e-5 relative); bench.py then labels its dtype accordingly
+    if (h->v_split && h->d % 64 == 0 && v_cols % 128 == 0) {
+        const size_t szW = (size_t)v_cols * h->d * 2, szR = (size_t)h->maxC * plan.inf.rows * h->d * 2;
+        if (szW > h->wv_hi.bytes || szR > h->R_hi.bytes) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(h->wv_hi.reserve(szW)); HIP_TRY(h->wv_lo.reserve(szW));
+            HIP_TRY(h->R_hi.reserve(szR)); HIP_TRY(h->R_lo.reserve(szR));
+            h->wv_split_valid = false;
+        }
+        if (!h->wv_split_valid) {
+            for (int l = 0; l < h->L; ++l)
+                HIP_TRY(launch_split_rows(pp.wv[l], h->d, h->dm, h->d, h->wv_hi.as<__bf16>() + (size_t)l * h->dm * h->d,
+                                          h->wv_lo.as<__bf16>() + (size_t)l * h->dm * h->d, h->d, vs));
+            h->wv_split_valid = true;
+        }
+        HIP_TRY(launch_split_rows(r_rows, h->d, Mv, h->d, h->R_hi.p, h->R_lo.p, h->d, vs));
+        SplitGemm g{};
+        g.A_hi = h->R_hi.as<__bf16>(); g.A_lo = h->R_lo.as<__bf16>(); g.lda = h->d; g.strideA = 0;
+        g.B_hi = h->wv_hi.as<__bf16>(); g.B_lo = h->wv_lo.as<__bf16>(); g.ldb = h->d; g.strideB = 0;
+        g.C = h->P_ws[set].as<float>(); g.ldc = p_ld; g.strideC = 0; g.split_stride = 0;
+        g.M = (int)Mv; g.N = v_cols; g.K = h->d; g.k_per_split = h->d; g.splitk = 1; g.nbatch = 1;
+        HIP_TRY(launch_split_gemm(g, vs, gemm_pad));
+    } else {
+        HIP_TRY(launch_project_values((int)Mv, h->d, h->dm, h->L, pp, r_rows,
+                                      h->P_ws[set].as<float>(), p_ld, vs, gemm_pad));
+    }
+    return INFV_OK;
+}
+
+// The sub-batches.  Streams: `pools` = pooling of batch b+2, `side` = projection GEMM of batch b+1, caller's stream = role S of
+// batch b, `ucs` = softmax weights, memory update + read-out of batch b-1.
+int consolidate_sub_batches(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pipe) {
+    const Plan& plan = *cc.plan;
+    const ProjPtrs& pp = *cc.pp;
+    hipStream_t stream = cc.stream, side = h->side, ucs = h->ucs, pools = cc.pools;
+    const char* k = cc.k;
+    const float* kbar_pre = cc.kbar_pre;
+    const int n_chunks = cc.n_chunks, T = cc.T, Q = cc.Q, first_c = cc.first_c, sub = cc.sub, n_batches = cc.n_batches;
+    const size_t rows = cc.rows;
+    bool* uc_pending = cc.uc_pending;
+    // Padding LDS caps the pooling kernel's occupancy at ONE 512-thread workgroup (84 KB: two do not fit, one leaves room for
+    // a 74 KB workgroup of the loader-wave GEMM) per CU, so a role-S workgroup
+    // always finds LDS and wave slots and the pool's bytes in flight stay bounded.  The GEMMs carry no padding any more
+    // (INFV_GEMM_PAD): their workgroups (36 KB, one wave per SIMD) co-reside with a pooling workgroup -- MFMA work beside
+    // memory work -- instead of taking the CU away from it.
+    static const int kPoolPad = [] { const char* e = exp_env("INFV_POOL_PAD"); return e ? atoi(e) : 84 * 1024; }();
+    static const int kGemmPad = [] { const char* e = exp_env("INFV_GEMM_PAD"); return e ? atoi(e) : 0; }();
+    std::vector<int> sks(n_batches > 0 ? n_batches : 1, 1);
+    std::vector<long> sss(n_batches > 0 ? n_batches : 1, 0);
+    std::vector<char> planes_by_pool(n_batches > 0 ? n_batches : 1, 0);
+    bool p_pending[kPSets] = {};                              // ev_p[set] has been recorded in this call
+    bool r_pending[kRSets] = {};                              // ev_r[rset] has been recorded in this call
+    auto stage_pool = [&](int b) -> int {                      // frame means (or directly the new rows) of batch b, on `pools`
+        if (kbar_pre || cc.use_pool_call) return INFV_OK;
+        const int c0 = cc.c0(b), nb = cc.nb(b);
+        const int set = b % kPSets, rset = b % kRSets;
+        if (cc.use_pr2) {
+            // R set rset was last read by the UC kernel (and the projections) of batch b - kRSets
+            if (r_pending[rset]) HIP_TRY(hipStreamWaitEvent(pools, h->ev_r[rset], 0));
+            planes_by_pool[b] = false;
+            if (!(skip_mask() & 1)) {
+                // the pooling kernel also writes the rows' bf16 planes when the six-product GEMM will read them (>= 1024 rows)
+                void* pl[3] = {h->r3_ring[rset][0].p, h->r3_ring[rset][1].p, h->r3_ring[rset][2].p};
+                const bool want_planes = cc.planes_in_pool && (long)nb * (long)rows >= 1024;
+                bool done = false;
+                Timed t_(h->prof, INFV_KERNEL_POOL, pools);
+                HIP_TRY(launch_pool_rows2(k + c0 * cc.chunk_k, h->k_bf16, nb, T, h->P, h->d, plan.inf.view(), h->R_ws[rset].as<float>(),
+                                          pools, cc.pr_u, cc.pr_pad, cc.pr_wgs, want_planes ? pl : nullptr, &done));
+                planes_by_pool[b] = done;
+            }
+            if (cc.split_pool) HIP_TRY(hipEventRecord(h->ev_pool[set], pools));
+            return INFV_OK;
+        }
+        // the rows kernel that read this set's pooled frames (batch b-3) is done once its projection is
+        if (cc.split_pool && p_pending[set]) HIP_TRY(hipStreamWaitEvent(pools, h->ev_p[set], 0));
+        if (!(skip_mask() & 1)) {
+            Timed t_(h->prof, INFV_KERNEL_POOL, pools);
+            HIP_TRY(launch_pool(k + c0 * cc.chunk_k, h->k_bf16, h->kbar_side[set].as<float>(), (int64_t)nb * T, h->P, h->d, pools, kPoolPad));
+        }
+        if (cc.split_pool) HIP_TRY(hipEventRecord(h->ev_pool[set], pools));
+        return INFV_OK;
+    };
+    auto stage_project = [&](int b) -> int {                   // rows -> [V'new | S'new] GEMM of batch b, on `side`
+        const int c0 = cc.c0(b), nb = cc.nb(b);
+        const int set = b % kPSets, rset = b % kRSets;
+        if (uc_pending[set]) HIP_TRY(hipStreamWaitEvent(side, h->ev_uc[set], 0));   // the UC kernel that read this set is done
+        if (r_pending[rset] && !cc.use_pr2) HIP_TRY(hipStreamWaitEvent(side, h->ev_r[rset], 0));   // (the rows kernel writes R here)
+        if (cc.split_pool && !cc.use_pool_call) HIP_TRY(hipStreamWaitEvent(side, h->ev_pool[set], 0));
+        const float* kb = kbar_pre ? kbar_pre + (size_t)c0 * T * h->d : h->kbar_side[set].as<float>();
+        const float* r_ext = nullptr;
+        void* pl_ext[3] = {nullptr, nullptr, nullptr};
+        if (!cc.use_pool_call && planes_by_pool[b]) for (int i = 0; i < 3; ++i) pl_ext[i] = h->r3_ring[rset][i].p;
+        if (cc.use_pool_call) {
+            // the rows of sub-batch b are complete once every (chunk, row) workgroup of the pooling launch has counted itself in
+            HIP_TRY(launch_flag_wait(h->pool_done.as<unsigned int>() + b, (unsigned int)((size_t)nb * rows), h->spin_limit, h->err_dev, side));
+            const size_t off = (size_t)(c0 - first_c) * rows * h->d;
+            r_ext = h->R_all.as<float>() + off;
+            if (cc.planes_call) for (int i = 0; i < 3; ++i) pl_ext[i] = h->planes_all[i].as<__bf16>() + off;
+        }
+        // (experiments) INFV_SMALL_TILES=<mask>: bit 0 / 1 / 2 = the call's first / second / last sub-batch runs the projection as
+        // 128 x 128 tiles (hundreds of short workgroups: faster while the chip is still -- or again -- empty)
+        // Shipped (bit 3, round 6): the LAST sub-batch of a long call -- behind the pooling launch the call's tail is serial (GEMM -> role S ->
+        // alpha -> UC of the last sub-batch) and the chip is emptying: 288 short workgroups finish sooner than 54 of 120 us.  13.45
+        // against 13.63 ms per video over five alternating rounds on one box; the two tilings give the same bits (test-enforced).
+        static const int small_mask = [] { const char* e = exp_env("INFV_SMALL_TILES"); return e ? atoi(e) : 8; }();
+        static const int small_below = [] { const char* e = exp_env("INFV_SMALL_BELOW"); return e ? atoi(e) : 0; }();   // sub-batches of fewer chunks than this
+        const bool small = (n_chunks < 768 && (((small_mask & 1) && b == 0) || ((small_mask & 2) && b == 1) || ((small_mask & 4) && b == n_batches - 1) || nb < small_below)) ||
+                           ((small_mask & 8) && n_chunks >= 768 && b == n_batches - 1);      // bit 3: the LAST sub-batch of a long call (the chip is emptying: the serial tail)
+        if (int rc = project_chunks_fast(h, plan, true, kb, nb, T, Q, pp, set, &sks[b], &sss[b], side, kGemmPad,
+                                         h->vproj_on_uc(n_chunks), rset, cc.use_pr2, r_ext, (cc.planes_call || planes_by_pool[b]) ? pl_ext : nullptr, small)) return rc;
+        HIP_TRY(hipEventRecord(h->ev_p[set], side));
+        p_pending[set] = true;
+        return INFV_OK;
+    };
+    auto stage_parallel = [&](int b) -> int {                  // issued while batch b-1's chain is about to start
+        if (b + 1 < n_batches)
+            if (int rc = stage_pool(b + 1)) return rc;
+        return stage_project(b);
+    };
+    if (n_batches > 0) {
+        HIP_TRY(hipEventRecord(h->ev_in, stream));            // inputs, cq and the first chunk's set are ordered before
+        HIP_TRY(hipStreamWaitEvent(side, h->ev_q, 0));
+        if (cc.split_pool) HIP_TRY(hipStreamWaitEvent(pools, h->ev_start, 0));
+        if (cc.use_pool_call) {
+            PoolCallDesc pc;
+            memset(&pc, 0, sizeof(pc));
+            pc.sub = sub; pc.n_chunks = n_chunks - first_c;
+            pc.R_all = h->R_all.as<float>();
+            if (cc.planes_call) for (int i = 0; i < 3; ++i) pc.plane[i] = h->planes_all[i].p;
+            pc.done = h->pool_done.as<unsigned int>();
+            Timed t_(h->prof, INFV_KERNEL_POOL, pools);
+            HIP_TRY(launch_pool_rows2_call(k + first_c * cc.chunk_k, h->k_bf16, T, h->P, h->d, plan.inf.view(), pc, pools, cc.pr_u, cc.pr_pad));
+        }
+        if (int rc = stage_pool(0)) return rc;
+        if (n_batches > 1)
+            if (int rc = stage_pool(1)) return rc;
+        if (int rc = stage_project(0)) return rc;
+    }
+    static const bool host_trace = exp_env("INFV_HOST_TRACE") != nullptr;   // host time of every loop iteration (is the host ahead of the device?)
+    std::vector<double> host_us;
+    const auto host_t0 = std::chrono::steady_clock::now();
+    for (int b = 0; b < n_batches; ++b) {
+        if (host_trace) host_us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - host_t0).count());
+        const int c0 = cc.c0(b), nb = cc.nb(b);
+        const int set = b % kPSets, rset = b % kRSets;
+        // (experiments) INFV_DROP_WAITS=<mask>: what the packets between two role-S launches cost.  1: no wait for the UC kernel of
+        // sub-batch b - 5 on the caller's stream (redundant: the GEMM of sub-batch b waited for it, and this stream waits for that GEMM);
+        // 2: no event record behind role S / no wait of the UC stream for it (WRONG results: timing only); 4: no wait for the GEMM (WRONG)
+        static const int drop_waits = [] { const char* e = exp_env("INFV_DROP_WAITS"); return e ? atoi(e) : 1; }();   // (round 6: bit 0 is the default -- 13.62 against 13.72 ms, tighter)
+        if (!(drop_waits & 4)) HIP_TRY(hipStreamWaitEvent(stream, h->ev_p[set], 0));
+        // the ring slots this batch writes were last read by the UC kernel three batches ago (same set)
+        if (uc_pending[set] && !(drop_waits & 1)) HIP_TRY(hipStreamWaitEvent(stream, h->ev_uc[set], 0));
+        const long slot0 = pipe.counter;
+        const float* r_rows = cc.use_pool_call ? h->R_all.as<float>() + (size_t)(c0 - first_c) * rows * h->d : h->R_ws[rset].as<float>();   // the sub-batch's new rows
+        const bool serial = host_serial();                              // timing experiments: no overlap between the streams
+        if (serial) { HIP_TRY(hipStreamSynchronize(pools)); HIP_TRY(hipStreamSynchronize(side)); HIP_TRY(hipStreamSynchronize(ucs)); }
+        if (cc.persistent) {
+            // the chunk-parallel stage of the next batch goes out first so it overlaps this batch's chain
+            if (b + 1 < n_batches)
+                if (int rc = stage_parallel(b + 1)) return rc;
+            if (serial) { HIP_TRY(hipStreamSynchronize(pools)); HIP_TRY(hipStreamSynchronize(side)); }
+            if (int rc = pipe.launch_s_batch(nb, h->P_ws[set].as<float>() + (size_t)h->L * h->dm, sks[b], sss[b],
+                                             cc.u ? cc.u + (size_t)c0 * cc.chunk_u : nullptr, cc.uf ? cc.uf + (size_t)c0 * cc.chunk_u : nullptr)) return rc;
+            if (serial) HIP_TRY(hipStreamSynchronize(stream));
+        } else {
+            for (int i = 0; i < nb; ++i) {
+                const size_t ld = (size_t)h->L * h->dm + (size_t)h->L * h->H * Q;
+                const StepS st{&plan.inf, true, h->P_ws[set].as<float>() + (size_t)i * rows * ld + (size_t)h->L * h->dm,
+                               cc.u ? cc.u + (size_t)(c0 + i) * cc.chunk_u : nullptr, sks[b], sss[b]};
+                if (int rc = pipe.launch_s(st)) return rc;
+                if (i == 0 && b + 1 < n_batches)
+                    if (int rc = stage_parallel(b + 1)) return rc;
+            }
+        }
+        // What the UC kernel needs besides role S's tables -- the softmax weights, and the V' half of the projection when it
+        // is not part of the side stream's GEMM -- runs on the UC stream itself (a stream of its own for it was measured much
+        // worse in rounds 1 and 2: every extra concurrent kernel slows role S and the GEMMs more than the shorter stream gains).
+        hipStream_t vs = ucs;
+        if (h->vproj_on_uc(n_chunks) && (long)nb * plan.inf.rows >= 1024 && !(skip_mask() & 2))
+            if (int rc = project_values_on_uc(h, cc, set, nb, r_rows, vs, kGemmPad)) return rc;
+        if (!(drop_waits & 2)) {
+            HIP_TRY(hipEventRecord(h->ev_s[set], stream));
+            HIP_TRY(hipStreamWaitEvent(ucs, h->ev_s[set], 0));
+        }
+        if (cc.persistent)
+            if (int rc = pipe.launch_alpha(nb, slot0, vs, b == n_batches - 1)) return rc;
+        if (int rc = pipe.launch_uc(plan.inf, true, nb, slot0, r_rows, h->P_ws[set].as<float>(),
+                                    sks[b], sss[b], cc.ctx + (size_t)c0 * cc.chunk_ctx, ucs)) return rc;
+        HIP_TRY(hipEventRecord(h->ev_uc[set], ucs));
+        uc_pending[set] = true;
+        HIP_TRY(hipEventRecord(h->ev_r[rset], ucs));
+        r_pending[rset] = true;
+    }
+    if (host_trace && !host_us.empty()) {
+        fprintf(stderr, "[host trace] %d iterations, issue time us:", n_batches);
+        for (size_t i = 0; i < host_us.size(); i += 4) fprintf(stderr, " %.0f", host_us[i]);
+        fprintf(stderr, " | end %.0f\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - host_t0).count());
+    }
+    return INFV_OK;
+}
+
+// The join: the memory and every ctx are complete once the last UC kernel is; then hand the sticky histogram back as one
+// float partial row and bring the K' half of the projected memory up to date.
+int consolidate_join(infv_ltm_handle h, const ConsolidateCall& cc, const FastPipe& pipe) {
+    for (int i = 0; i < kPSets; ++i)
+        if (cc.uc_pending[i]) HIP_TRY(hipStreamWaitEvent(cc.stream, h->ev_uc[i], 0));
+    if (pipe.counter > 0) {
+        HIP_TRY(launch_acc_to_part(h->mass_acc[(pipe.counter + 2) % 3].as<unsigned long long>(), h->L, 1,
+                                   h->bin_part[h->pc].as<float>(), cc.stream));
+        h->parts = 1;
+    }
+    h->k_stale = true;                                        // K' is re-projected from B on demand (per-call path, continuation)
     return INFV_OK;
 }
 
@@ -1307,622 +1730,23 @@ static int consolidate_impl(infv_ltm_handle h, const void* k_, const float* kbar
     if (int rc = find_plan(h, T, &plan)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const ProjPtrs pp = make_proj(proj, h->L);
-    const size_t chunk_k = (size_t)T * h->P * h->d * (h->k_bf16 ? 2 : 4);   // bytes of one chunk's tokens
-    const size_t chunk_ctx = (size_t)h->L * Q * h->dm;
-    const size_t chunk_u = (size_t)h->L * h->S;
+    ConsolidateCall cc{};
+    cc.plan = plan; cc.k = k; cc.kbar_pre = kbar_pre; cc.n_chunks = n_chunks; cc.T = T; cc.Q = Q; cc.q = q; cc.proj = proj; cc.pp = &pp;
+    cc.u = u; cc.ctx = ctx; cc.stream = stream; cc.stream_ = stream_;
+    cc.chunk_k = (size_t)T * h->P * h->d * (h->k_bf16 ? 2 : 4);
+    cc.chunk_ctx = (size_t)h->L * Q * h->dm;
+    cc.chunk_u = (size_t)h->L * h->S;
     if (new_doc) infv_ltm_reset(h);
     if (n_chunks == 0) return INFV_OK;
-    const int rows_max = plan->first.rows > plan->inf.rows ? plan->first.rows : plan->inf.rows;
-    if (plan->dense.on || !chain_supported(h->N, h->S, rows_max, plan->inf.tabw) || (h->L * h->H * Q) % 128 != 0 || (h->L * h->dm) % 128 != 0 ||
-        !uc_supported(h->N, h->d, h->dm, plan->inf.tabw, rows_max) || !qtilde_supported(Q)) {
-        // shapes the fused chain kernel cannot hold in LDS (or whose query block qtilde_kernel does not take): per-chunk stage kernels
-        for (int c = 0; c < n_chunks; ++c) {
-            if (kbar_pre) {
-                if (int rc = infv_ltm_step(h, kbar_pre + (size_t)c * T * h->d, T, q, Q, proj, u ? u + c * chunk_u : nullptr,
-                                           ctx + c * chunk_ctx, stream_)) return rc;
-            } else if (int rc = infv_ltm_forward(h, k + c * chunk_k, T, q, Q, proj, u ? u + c * chunk_u : nullptr, 0,
-                                                 ctx + c * chunk_ctx, stream_)) return rc;
-        }
-        return INFV_OK;
-    }
+    if (!fused_chain_holds(h, *plan, Q)) return consolidate_per_chunk(h, cc);
     if (int rc = ensure_side_stream(h)) return rc;
-    // One call enqueues at a time per device: the worker streams are shared by every handle, and a call-long role-S launch
-    // spin-waits on work that must not end up behind another call's hand-off kernels in a shared stream.
-    // (The per-sub-batch launches of the shipped pipeline only order themselves through events: no lock, as in rounds 1-4.)
-    std::unique_lock<std::mutex> issue_lock(*h->issue_mu, std::defer_lock);
-    if (chain_call_long()) issue_lock.lock();
-    // Padding LDS caps the pooling kernel's occupancy at ONE 512-thread workgroup (84 KB: two do not fit, one leaves room for
-    // a 74 KB workgroup of the loader-wave GEMM) per CU, so a role-S workgroup
-    // always finds LDS and wave slots and the pool's bytes in flight stay bounded.  The GEMMs carry no padding any more
-    // (INFV_GEMM_PAD): their workgroups (36 KB, one wave per SIMD) co-reside with a pooling workgroup -- MFMA work beside
-    // memory work -- instead of taking the CU away from it.
-    static const int kPoolPad = [] { const char* e = exp_env("INFV_POOL_PAD"); return e ? atoi(e) : 84 * 1024; }();
-    static const int kGemmPad = [] { const char* e = exp_env("INFV_GEMM_PAD"); return e ? atoi(e) : 0; }();
     FastPipe pipe{h, *plan, Q, pp, stream};
-    h->wv_split_valid = false;                                // the caller's value weights may have changed since the last call
-    // the pooling of the first sub-batches depends on the caller's tokens only: it starts here, beside the first chunk
-    // ONE pooling launch per call (round 6, shipped for calls of 768 chunks and more): the pooling stream is what bounds a long call,
-    // and between its per-sub-batch launches sat an event record, a wait for the R set's last reader and the ramp of 2688 fresh
-    // workgroups (13 us per boundary by the residency stamps).  The launch walks every (chunk, row) of the call in order, writes rows
-    // and bf16 planes write-through and counts them into one word per sub-batch; the GEMM stream holds on that word with a one-wave
-    // flag_wait_kernel (bounded, latches the handle's error word) instead of an event.  Role S, the GEMM, alpha and UC keep their
-    // per-sub-batch launches -- round 5 measured this pooling launch only beside a RESIDENT role S, which cost more seats than the
-    // boundaries: alone it is 13.3 against 13.7 ms per video on one box, four rounds (profiles/r06_matrix.txt, block 12), same bits.
-    // Rows + planes of the whole call live in HBM (0.49 MB per chunk: 1 GB at 2048 chunks); above kPoolCallBudget the call keeps its
-    // per-sub-batch pooling launches.  INFV_POOL_CALL (experiments build): 0 never, 1 with the call-long role S, 2 always.
-    static const int pool_call_env_mode = [] { const char* e = exp_env("INFV_POOL_CALL"); return e ? atoi(e) : -1; }();
-    constexpr size_t kPoolCallBudget = (size_t)16 << 30;
-    const size_t pool_call_bytes = (size_t)n_chunks * (size_t)plan->inf.rows * h->d * (sizeof(float) + 3 * sizeof(__bf16));
-    const int pool_call_mode = pool_call_env_mode >= 0 ? pool_call_env_mode : ((n_chunks >= 768 && pool_call_bytes <= kPoolCallBudget) ? 2 : 0);
-    if (chain_call_long() || pool_call_mode == 2) {   // hand-off counters of the call-long launches restart with the call (before ev_start: the pooling stream starts behind it)
-        const size_t need_pd = ((size_t)n_chunks + 1) * sizeof(unsigned int);
-        if (need_pd > h->pool_done.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->pool_done.reserve(need_pd < 32768 ? 32768 : need_pd)); }
-        HIP_TRY(hipMemsetAsync(h->pool_done.p, 0, need_pd, stream));
-        const long cap = ((long)n_chunks + 64) & ~63l;
-        if (chain_call_long() && cap > h->gemm_flags_cap) {
-            HIP_TRY(hipDeviceSynchronize());
-            const long ncap = cap < 8192 ? 8192 : cap;
-            HIP_TRY(h->gemm_flags.reserve((size_t)(128 + 2 * ncap) * sizeof(unsigned int) + 1024));
-            h->gemm_flags_cap = ncap;
-        }
-        if (chain_call_long()) {
-            HIP_TRY(hipMemsetAsync(h->gemm_flags.p, 0, (size_t)(128 + 2 * h->gemm_flags_cap) * sizeof(unsigned int), stream));
-            HIP_TRY(hipMemsetAsync(h->call_flags.p, 0, 512, stream));
-        }
-    }
-    HIP_TRY(hipEventRecord(h->ev_start, stream));
-    HIP_TRY(hipMemsetAsync(h->mass_acc[0].p, 0, h->mass_acc[0].bytes, stream));   // slot of the call's first step
-    {   // rings of role S's per-chunk outputs (sized for this call's Q)
-        const size_t need_a = (size_t)h->ring * pipe.alpha_slot() * sizeof(float);
-        if (need_a > h->alpha_ring.bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h->alpha_ring.reserve(need_a));
-            HIP_TRY(h->asum_ring.reserve((size_t)h->ring * pipe.asum_slot() * sizeof(float)));
-            HIP_TRY(h->tab_ring.reserve((size_t)h->ring * pipe.tab_slot() * sizeof(int32_t)));
-            HIP_TRY(h->tabb_ring.reserve((size_t)h->ring * pipe.tab_slot() * sizeof(int32_t)));
-            HIP_TRY(h->crit_ring.reserve((size_t)h->ring * pipe.crit_slot() * sizeof(float)));
-        }
-    }
-    hipStream_t side = h->side, ucs = h->ucs;
-    // pre-multiplied queries qt = (q/sqrt(dh)) . Wk_h and the bias term cq = q_h . bk_h / sqrt(dh), once per call
-    HIP_TRY(launch_qtilde(q, Q, h->H, h->d, h->L, pp, h->qt_buf.as<float>(), h->cqbuf.as<float>(), stream));
-    h->w3_valid = false;
-    if (h->proj_x6 && h->d % 32 == 0 && ((long)h->L * h->dm + (long)h->L * h->H * Q) % 8 == 0) {
-        // bf16 planes of the projection GEMM's weight rows [Wv_0 ; ... ; Wv_{L-1} ; q~] (the caller's weights may change between calls)
-        const long n_rows = (long)h->L * h->dm + (long)h->L * h->H * Q;
-        const size_t szW = (size_t)n_rows * h->d * sizeof(__bf16);
-        if (szW > h->w3[0].bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            for (int i = 0; i < 3; ++i) HIP_TRY(h->w3[i].reserve(szW));
-        }
-        for (int l = 0; l < h->L; ++l)
-            HIP_TRY(launch_split3_rows(pp.wv[l], h->d, h->dm, h->d, h->w3[0].p, h->w3[1].p, h->w3[2].p, (long)l * h->dm, n_rows, stream));
-        HIP_TRY(launch_split3_rows(h->qt_buf.as<float>(), h->d, (long)h->L * h->H * Q, h->d, h->w3[0].p, h->w3[1].p, h->w3[2].p,
-                                   (long)h->L * h->dm, n_rows, stream));
-        h->w3_valid = true;
-    }
-    HIP_TRY(hipEventRecord(h->ev_q, stream));                 // the side stream's projections need no more than this
-    // the persistent role S searches in fp32 against the round-ups of the f64 uniforms (equivalent to the f64 compare):
-    // converted once per call, off the chain
-    const float* uf = nullptr;
-    if (u && h->cfg.sticky && chain_batch3_shape_ok(1, plan->sticky().points_ok, plan->inf.rows, h->S, Q)) {
-        const size_t need_u = (size_t)n_chunks * chunk_u * sizeof(float);
-        if (need_u > h->uf_all.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->uf_all.reserve(need_u)); }
-        HIP_TRY(launch_round_up_uniforms(u, h->uf_all.as<float>(), (long)n_chunks * (long)chunk_u, stream));
-        uf = h->uf_all.as<float>();
-        if (chain_batch3_mailboxes()) {
-            // (experiments) mailboxes of role S's exchange: zeroed per call (step tags restart with the call's chunk counter)
-            const int G = chain_batch_blocks(h->H, Q, h->L, 1, plan->sticky().points_ok, plan->inf.rows, h->S) / h->L;
-            const size_t need_m = chain_mailbox_bytes(h->L, G);
-            if (need_m > h->mbox.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->mbox.reserve(need_m)); }
-            h->mbox_G = G;
-            HIP_TRY(hipMemsetAsync(h->mbox.p, 0, need_m, stream));
-        }
-    }
-    int c = 0;
-    bool uc_pending[kPSets] = {};               // ev_uc[set] has been recorded in this call
-    if (!h->has_memory) {                                     // first chunk of a document: first-chunk operator, set 1
-        const float* kb0 = kbar_pre;
-        if (!kb0) {
-            if ((size_t)T * h->d * sizeof(float) > h->kbar_ws.bytes) HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h->kbar_ws.reserve((size_t)T * h->d * sizeof(float)));
-            if (int rc = infv_ltm_pool(h, k, T, h->kbar_ws.as<float>(), stream_)) return rc;
-            kb0 = h->kbar_ws.as<float>();
-        }
-        int sk = 1; long ss = 0;
-        if (int rc = project_chunks_fast(h, *plan, false, kb0, 1, T, Q, pp, 2, &sk, &ss, stream, 0, false, kRSets)) return rc;
-        const long v_cols = (long)h->L * h->dm;             // a GEMM output row is [ V' (L*dm) | scores (L*H*Q) ]
-        const StepS st{&plan->first, false, h->P_ws[2].as<float>() + v_cols, nullptr, sk, ss};
-        if (int rc = pipe.launch_s(st)) return rc;
-        HIP_TRY(hipEventRecord(h->ev_s[2], stream));
-        HIP_TRY(hipStreamWaitEvent(ucs, h->ev_s[2], 0));
-        if (int rc = pipe.launch_uc(plan->first, false, 1, 0, h->R_ws[kRSets].as<float>(), h->P_ws[2].as<float>(), sk, ss, ctx, ucs)) return rc;
-        HIP_TRY(hipEventRecord(h->ev_uc[2], ucs));
-        uc_pending[2] = true;
-        c = 1;
-    } else {
-        // continue an existing memory
-        if (h->carry_scores && h->last_fast && h->lastQ == Q) {
-            // ... handed over by infv_ltm_import_chain_state: the scores under this query and the projected memory are the
-            // exporting handle's own; nothing is re-derived, the chain goes on bit for bit
-        } else {
-            // ... bias-free scores of the current K' rows under this query
-            if (h->k_stale)
-                if (int rc = infv_ltm_reproject(h, proj, stream_)) return rc;
-            Timed t_(h->prof, INFV_KERNEL_SCORES, stream);
-            HIP_TRY(launch_new_scores(q, Q, h->H, h->L, 1, h->N, h->KV[h->cur].as<float>(), 0, 2L * h->dm,
-                                      (long)h->N * 2 * h->dm, 1, 0, pp, h->Sp[h->sc].as<float>(), h->cqbuf.as<float>(),
-                                      stream));
-        }
-    }
-    h->carry_scores = false;
-    // ---- sub-batches.  Streams: `side` = chunk-parallel stage of batch b+1, caller's stream = role S of
-    //      batch b (one launch per chunk), `ucs` = memory update + read-out of batch b-1 ----
-    // INFV_PERSISTENT=0 falls back to one role-S launch per chunk
-    static const bool want_persistent = [] { const char* e = exp_env("INFV_PERSISTENT"); return !e || atoi(e) != 0; }();
-    const bool persistent = want_persistent &&
-        chain_batch_supported(h->N, h->S, plan->inf.rows, plan->inf.tabw, h->H * chain_s_tiles(Q) * h->L) &&
-        chain_batch_resident(h->N, h->S, plan->inf.rows, plan->inf.tabw,
-                             chain_batch_blocks(h->H, Q, h->L, h->cfg.sticky ? 1 : 2, plan->sticky().points_ok, plan->inf.rows, h->S),
-                             h->cfg.sticky ? 1 : 2, plan->sticky().points_ok, Q);
-    const int first_c = c;
-    // sub-batch size: long calls amortise the per-launch gap of role S over more chunks (42 x 64 new rows = 21 row tiles:
-    // 126 score tiles, 252 V' tiles); short ones (e.g. a 256-chunk shard of a multi-GPU run) keep 32 so that the
-    // pipeline fills and drains quickly.  INFV_SUB_BATCH overrides.
-    static const int sub_env = [] { const char* e = exp_env("INFV_SUB_BATCH"); return e ? atoi(e) : 0; }();
-    // (experiments) INFV_SUB_RAMP=<n>: short calls run their first sub-batch with 32 chunks (fast fill) and the following ones
-    // with n (fewer role-S launches); needs max_batch_chunks >= n
-    static const int ramp_env = [] { const char* e = exp_env("INFV_SUB_RAMP"); return e ? atoi(e) : 0; }();
-    int sub = h->maxC;
-    if (sub_env > 0) sub = sub_env < h->maxC ? sub_env : h->maxC;
-    else if (n_chunks < 768 && sub > 32) sub = 32;             // (28 while the V' GEMM ran on the UC stream; 2.84 -> 2.68 ms per 256 chunks)
-    // first chunk of every sub-batch (+ the end of the call)
-    std::vector<int> bstart;
-    {
-        int later = sub;
-        if (sub_env <= 0 && n_chunks < 768 && ramp_env > sub) later = ramp_env < h->maxC ? ramp_env : h->maxC;
-        // (experiments) tapered schedule of a short call: INFV_TAPER="first,mid,last" -- a small first sub-batch (role S starts early), a
-        // small last one (the serial tail behind the last pooling launch: GEMM -> role S -> alpha -> UC of the last sub-batch), the rest
-        // in equal pieces of at most `mid` chunks
-        static const char* taper_env = exp_env("INFV_TAPER");
-        int tf = 0, tm = 0, tl = 0;
-        const int n_rest = n_chunks - first_c;
-        if (sub_env <= 0 && n_chunks < 768 && taper_env && sscanf(taper_env, "%d,%d,%d", &tf, &tm, &tl) == 3 && tf > 0 && tm > 0 && tl > 0 &&
-            tf <= h->maxC && tm <= h->maxC && tl <= h->maxC && n_rest > tf + tl) {
-            const int middle = n_rest - tf - tl, pieces = (middle + tm - 1) / tm;
-            bstart.push_back(first_c);
-            int c0 = first_c + tf;
-            for (int i = 0; i < pieces; ++i) { bstart.push_back(c0); c0 += middle / pieces + (i < middle % pieces ? 1 : 0); }
-            bstart.push_back(c0);                                // the last sub-batch
-            bstart.push_back(n_chunks);
-            sub = tf > tm ? tf : tm; if (tl > sub) sub = tl;
-        } else if (const char* sched = (sub_env <= 0 && n_chunks < 768) ? exp_env("INFV_SCHED") : nullptr) {
-            // (experiments) INFV_SCHED="a,b,c,...": explicit sub-batch sizes; used when they add up to the call's chunks
-            std::vector<int> sz; int tot = 0, mx = 0;
-            for (const char* p_ = sched; *p_;) { const int v = atoi(p_); sz.push_back(v); tot += v; if (v > mx) mx = v; while (*p_ && *p_ != ',') ++p_; if (*p_ == ',') ++p_; }
-            bool ok_ = tot == n_rest && mx <= h->maxC;
-            for (int v : sz) ok_ = ok_ && v > 0;
-            if (ok_) { int c0 = first_c; for (int v : sz) { bstart.push_back(c0); c0 += v; } bstart.push_back(n_chunks); sub = mx; }
-            else { for (int c0 = first_c; c0 < n_chunks; c0 += sub) bstart.push_back(c0); bstart.push_back(n_chunks); }
-        } else {
-        for (int c0 = first_c, i = 0; c0 < n_chunks; ++i) { bstart.push_back(c0); c0 += (i == 0) ? sub : later; }
-        bstart.push_back(n_chunks);
-        if (later > sub) sub = later;                           // (workspaces below are sized for the largest sub-batch)
-        }
-    }
-    const int n_batches = (int)bstart.size() - 1;
-    const size_t rows = plan->inf.rows;
-    std::vector<int> sks(n_batches > 0 ? n_batches : 1, 1);
-    std::vector<long> sss(n_batches > 0 ? n_batches : 1, 0);
-    auto batch_range = [&](int b, int* c0, int* nb) {
-        *c0 = bstart[b];
-        *nb = bstart[b + 1] - bstart[b];
-    };
-    // The pooling has its own stream so that the HBM-bound pooling of batch b+2 overlaps the MFMA-bound projection of
-    // batch b+1 (pooled frames are triple-buffered either way); INFV_SPLIT_POOL=0 puts it back on the side stream.
-    // (Round 1 measured this worse, 87 k vs 95 k chunks/s, because role S was then sensitive to every concurrent
-    // kernel; with chain_batch2_kernel and no padding LDS on the GEMMs it is better: 112 k vs 102 k.)
-    static const bool split_pool_env = [] { const char* e = exp_env("INFV_SPLIT_POOL"); return !e || atoi(e) != 0; }();
-    const bool split_pool = split_pool_env && !kbar_pre;      // (frame means handed in: there is no pooling stage)
-    hipStream_t pools = split_pool ? h->pools : side;
-    bool p_pending[kPSets] = {};                // ev_p[set] has been recorded in this call
-    bool r_pending[kRSets] = {};                              // ev_r[rset] has been recorded in this call
-    // Pool + rows in one kernel: the pooling stream writes the sub-batch's new rows R straight from the tokens -- in this path
-    // the frame means are consumed by the rows kernel only; same bits either way.  Default: pool_rows2_kernel (one short-lived
-    // workgroup per (chunk, row), a wave per frame and slice): no kbar round trip through HBM, no rows kernel on the side
-    // stream, and the pooling stream runs up to kRSets sub-batches ahead instead of three.  Measured in situ (round 3,
-    // tools/sweep_r03s.sh, alternating on one box): 132.5 k against 130.5 k chunks/s, pooling stream 14.65 against 15.05 ms.
-    // The experiments build keeps INFV_POOL_ROWS=0 (pool_frames_kernel + build_rows_kernel, the round-2 form, still used when
-    // frame means are handed in or the width has no pool_rows2 shape).  (Round 3's long-lived grid-stride form, pool_rows_kernel,
-    // streamed faster alone -- 218-270 us per launch against 304 -- but cost the chain launches their CUs, 116-121 k: deleted.)
-    static const int pr_env = [] { const char* e = exp_env("INFV_POOL_ROWS"); return e ? atoi(e) : 2; }();
-    const bool use_pr2 = pr_env == 2 && !kbar_pre && pool_rows2_supported(h->d);
-    const bool use_pr = use_pr2;
-    static const int pr_u = [] { const char* e = exp_env("INFV_PR_U"); return e ? atoi(e) : 8; }();
-    static const int pr_pad = [] { const char* e = exp_env("INFV_PR_PAD"); return e ? atoi(e) : 84 * 1024; }();
-    static const int pr_wgs = [] { const char* e = exp_env("INFV_PR_WGS"); return e ? atoi(e) : 0; }();
-    if (!kbar_pre && !use_pr) {
-        const size_t need = (size_t)h->maxC * T * h->d * sizeof(float);
-        if (need > h->kbar_side[0].bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            for (int i = 0; i < kPSets; ++i) HIP_TRY(h->kbar_side[i].reserve(need));
-        }
-    }
-    if (n_batches > 0) {                                      // the rotating R sets are written off the side stream: size them here
-        const size_t needR = (size_t)sub * rows * h->d * sizeof(float);
-        bool grow = false;
-        for (int i = 0; i < kRSets; ++i) grow = grow || needR > h->R_ws[i].bytes;
-        if (grow) {
-            HIP_TRY(hipDeviceSynchronize());
-            for (int i = 0; i < kRSets; ++i) HIP_TRY(h->R_ws[i].reserve(needR));
-        }
-    }
-    // ---- ONE role-S launch for the whole call (round 5).  It goes out FIRST -- before any pooling, GEMM or UC launch of the call,
-    // while its CUs are free: 24 workgroups per layer on one XCD each, where the step's exchange stays in that XCD's L2 -- and
-    // stays resident to the call's last step.  Sub-batches reach it through `ready` (raised behind each projection GEMM), it
-    // hands them on through `done` (flag_wait_kernel holds the UC stream).  Its ring slots and workspace sets need no wait of
-    // their own: the GEMM of sub-batch b is itself ordered behind the UC kernel of sub-batch b - kPSets.
-    const long call_slot0 = pipe.counter;                     // ring slot of the call-long launch's first step
-    const int call_wgs = chain_batch_blocks(h->H, Q, h->L, 1, plan->sticky().points_ok, plan->inf.rows, h->S);   // role-S workgroups that count a sub-batch in
-    hipStream_t call_stream = h->chain_s != nullptr ? h->chain_s : stream;      // where the call-long launch lives
-    const bool use_call = persistent && uf != nullptr && chain_call_long() && n_batches > 0 && cu_mask_k() == 0 &&
-                          !(sub_env <= 0 && n_chunks < 768 && ramp_env > 0) && kPSets <= kCallSets && !host_serial() && !(skip_mask() & 8);
-    // ... and ONE pooling launch for the whole call: no launch boundaries on the HBM stream (with role S resident nothing but the
-    // projection GEMM still needs an empty CU), rows and their bf16 planes for the whole call in HBM (402 + 604 MB at 2048 chunks),
-    // the GEMM stream follows it through per-sub-batch completion counts
-    // (mode 2: the one pooling launch WITHOUT the call-long role S, see above)
-    // (the pooling kernel maps a chunk to its sub-batch as chunk / sub: every sub-batch but the last must have `sub` chunks -- the tapered
-    //  schedules of the experiments build, short calls only, do not qualify)
-    bool uniform_batches = true;
-    for (int b = 0; b + 1 < n_batches; ++b) uniform_batches = uniform_batches && bstart[b + 1] - bstart[b] == sub;
-    const bool pool_call_alone = pool_call_mode == 2 && persistent && n_batches > 0 && !host_serial() && uniform_batches;
-    const bool use_pool_call = ((use_call && pool_call_mode != 0 && uniform_batches) || pool_call_alone) && use_pr2 && pr_wgs == 0 && !(skip_mask() & 1);
-    const bool planes_call = use_pool_call && h->proj_x6 && h->d % 32 == 0 && !h->vproj_on_uc(n_chunks);
-    // ... and ONE projection-GEMM launch: a few resident workgroups per XCD on a tile queue (gemm_x6_call_kernel).  Sub-batches it
-    // covers: every one of >= 1024 rows (all but, possibly, a short last one: that one keeps its own launch behind the resident kernel)
-    static const bool gemm_call_env = [] { const char* e = exp_env("INFV_GEMM_CALL"); return e && atoi(e) != 0; }();
-    static const int gemm_wgs = [] { const char* e = exp_env("INFV_GEMM_WGS"); const int v = e ? atoi(e) : 32; return v > 0 ? v : 32; }();
-    int n_tiled = 0;
-    if (planes_call && gemm_call_env && h->w3_valid && !(skip_mask() & 2) && (sub * rows) % 32 == 0 && (long)sub * rows >= 1024 &&
-        ((long)h->L * h->dm + (long)h->L * h->H * Q) % 256 == 0 && ((long)h->L * h->dm) % 256 == 0) {
-        int c0l, nbl; batch_range(n_batches - 1, &c0l, &nbl);
-        n_tiled = ((long)nbl * rows >= 1024 && ((long)nbl * rows) % 32 == 0) ? n_batches : n_batches - 1;
-    }
-    const bool use_gemm_call = n_tiled > 0;
-    const int v_cols_all = h->L * h->dm;
-    auto predict_split = [&](int nb, int* sk, long* ss) {       // the split-K form project_chunks_fast will choose for a sub-batch of nb chunks
-        const long M = (long)nb * plan->inf.rows;
-        const long ld = (long)h->L * h->dm + (long)h->L * h->H * Q;
-        const bool defer = h->vproj_on_uc(n_chunks);
-        if (skip_mask() & 2) *sk = project_splitk((int)M, h->d);
-        else if (defer && M >= 1024) *sk = 1;
-        else if (h->proj_x6 && h->w3_valid && M >= 1024 && h->d % 32 == 0 && !defer) *sk = 1;
-        else *sk = project_splitk((int)M, h->d);
-        *ss = M * ld;
-    };
-    if (use_call || use_pool_call) {
-        // every workspace the loop would grow (a growth synchronises the device: fatal beside a kernel that waits for the loop's work)
-        const long ld = (long)h->L * h->dm + (long)h->L * h->H * Q;
-        size_t needP = 0;
-        for (int b = 0; b < n_batches; ++b) {
-            int c0, nb; batch_range(b, &c0, &nb);
-            const size_t M = (size_t)nb * rows;
-            const size_t np = M * ld * sizeof(float) * (M < 1024 ? 8 : 1);
-            if (np > needP) needP = np;
-        }
-        const size_t need3 = (size_t)(h->maxC > sub ? h->maxC : sub) * rows * h->d * sizeof(__bf16);
-        const size_t szW = (size_t)v_cols_all * h->d * 2, szR = (size_t)(h->maxC > sub ? h->maxC : sub) * rows * h->d * 2;
-        bool grow = false;
-        const size_t needRall = use_pool_call ? (size_t)(n_chunks - first_c) * rows * h->d * sizeof(float) : 0;
-        const size_t needPl = planes_call ? needRall / 2 : 0;
-        grow = grow || needRall > h->R_all.bytes || needPl > h->planes_all[0].bytes;
-        for (int i = 0; i < kPSets; ++i) grow = grow || needP > h->P_ws[i].bytes;
-        if (h->proj_x6) for (int i = 0; i < 3; ++i) grow = grow || need3 > h->r3[i].bytes;
-        if (h->v_split) grow = grow || szW > h->wv_hi.bytes || szR > h->R_hi.bytes;
-        if (grow) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h->R_all.reserve(needRall));
-            for (int i = 0; i < 3; ++i) HIP_TRY(h->planes_all[i].reserve(needPl));
-            for (int i = 0; i < kPSets; ++i) HIP_TRY(h->P_ws[i].reserve(needP));
-            if (h->proj_x6) for (int i = 0; i < 3; ++i) HIP_TRY(h->r3[i].reserve(need3));
-            if (h->v_split) {
-                HIP_TRY(h->wv_hi.reserve(szW)); HIP_TRY(h->wv_lo.reserve(szW));
-                HIP_TRY(h->R_hi.reserve(szR)); HIP_TRY(h->R_lo.reserve(szR));
-                h->wv_split_valid = false;
-            }
-        }
-    }
-    // per-sub-batch pooling launches: the kernel writes the bf16 planes of its rows too (no split3_rows_kernel, no re-read of R).
-    // Long calls only (round 6, same-box A/B, `profiles/r06_matrix.txt` block 10): a call of 768 chunks and more is bound by the role-S
-    // stream and the planes cost the pooling nothing (150.4 against 149.0 k chunks/s, four rounds); a short call -- the 256-chunk
-    // shard of the 8-GPU split -- is bound by its pooling launches, which the extra stores lengthen: 2.14-2.17 ms with
-    // split3_rows_kernel on the side stream against 2.20-2.24 with the planes written by the pooling kernel.  Same bits either way.
-    // (INFV_POOL_PLANES, experiments build: 0 = never, 2 = always.)
-    static const int planes_env = [] { const char* e = exp_env("INFV_POOL_PLANES"); return e ? atoi(e) : 1; }();
-    const bool planes_in_pool = (planes_env == 2 || (planes_env == 1 && n_chunks >= 768)) && use_pr2 && !use_pool_call && h->proj_x6 && h->w3_valid && h->d % 32 == 0 && !h->vproj_on_uc(n_chunks) && n_batches > 0;
-    std::vector<char> planes_by_pool(n_batches > 0 ? n_batches : 1, 0);
-    if (planes_in_pool) {
-        const size_t need3r = (size_t)sub * rows * h->d * sizeof(__bf16);
-        bool grow3 = false;
-        for (int i = 0; i < kRSets; ++i) grow3 = grow3 || need3r > h->r3_ring[i][0].bytes;
-        if (grow3) {
-            HIP_TRY(hipDeviceSynchronize());
-            for (int i = 0; i < kRSets; ++i) for (int j = 0; j < 3; ++j) HIP_TRY(h->r3_ring[i][j].reserve(need3r));
-        }
-    }
-    auto stage_pool = [&](int b) -> int {                      // frame means (or directly the new rows) of batch b, on `pools`
-        if (kbar_pre || use_pool_call) return INFV_OK;
-        int c0, nb; batch_range(b, &c0, &nb);
-        const int set = b % kPSets, rset = b % kRSets;
-        if (use_pr) {
-            // R set rset was last read by the UC kernel (and the projections) of batch b - kRSets
-            if (r_pending[rset]) HIP_TRY(hipStreamWaitEvent(pools, h->ev_r[rset], 0));
-            planes_by_pool[b] = false;
-            if (!(skip_mask() & 1)) {
-                // the pooling kernel also writes the rows' bf16 planes when the six-product GEMM will read them (>= 1024 rows)
-                void* pl[3] = {h->r3_ring[rset][0].p, h->r3_ring[rset][1].p, h->r3_ring[rset][2].p};
-                const bool want_planes = planes_in_pool && (long)nb * (long)rows >= 1024;
-                bool done = false;
-                Timed t_(h->prof, INFV_KERNEL_POOL, pools);
-                HIP_TRY(launch_pool_rows2(k + c0 * chunk_k, h->k_bf16, nb, T, h->P, h->d, plan->inf.view(), h->R_ws[rset].as<float>(),
-                                          pools, pr_u, pr_pad, pr_wgs, want_planes ? pl : nullptr, &done));
-                planes_by_pool[b] = done;
-            }
-            if (split_pool) HIP_TRY(hipEventRecord(h->ev_pool[set], pools));
-            return INFV_OK;
-        }
-        // the rows kernel that read this set's pooled frames (batch b-3) is done once its projection is
-        if (split_pool && p_pending[set]) HIP_TRY(hipStreamWaitEvent(pools, h->ev_p[set], 0));
-        if (!(skip_mask() & 1)) {
-            Timed t_(h->prof, INFV_KERNEL_POOL, pools);
-            HIP_TRY(launch_pool(k + c0 * chunk_k, h->k_bf16, h->kbar_side[set].as<float>(), (int64_t)nb * T, h->P, h->d, pools, kPoolPad));
-        }
-        if (split_pool) HIP_TRY(hipEventRecord(h->ev_pool[set], pools));
-        return INFV_OK;
-    };
-    auto stage_project = [&](int b) -> int {                   // rows -> [V'new | S'new] GEMM of batch b, on `side`
-        int c0, nb; batch_range(b, &c0, &nb);
-        const int set = b % kPSets, rset = b % kRSets;
-        if (b < n_tiled) {                                     // the resident GEMM kernel has this sub-batch on its tile queue
-            sks[b] = 1; sss[b] = (long)nb * (long)rows * ((long)h->L * h->dm + (long)h->L * h->H * Q);
-            return INFV_OK;
-        }
-        if (uc_pending[set]) HIP_TRY(hipStreamWaitEvent(side, h->ev_uc[set], 0));   // the UC kernel that read this set is done
-        if (r_pending[rset] && !use_pr) HIP_TRY(hipStreamWaitEvent(side, h->ev_r[rset], 0));   // (the rows kernel writes R here)
-        if (split_pool && !use_pool_call) HIP_TRY(hipStreamWaitEvent(side, h->ev_pool[set], 0));
-        const float* kb = kbar_pre ? kbar_pre + (size_t)c0 * T * h->d : h->kbar_side[set].as<float>();
-        const float* r_ext = nullptr;
-        void* pl_ext[3] = {nullptr, nullptr, nullptr};
-        if (!use_pool_call && planes_by_pool[b]) for (int i = 0; i < 3; ++i) pl_ext[i] = h->r3_ring[rset][i].p;
-        if (use_pool_call) {
-            // the rows of sub-batch b are complete once every (chunk, row) workgroup of the pooling launch has counted itself in
-            HIP_TRY(launch_flag_wait(h->pool_done.as<unsigned int>() + b, (unsigned int)((size_t)nb * rows), h->spin_limit, h->err_dev, side));
-            const size_t off = (size_t)(c0 - first_c) * rows * h->d;
-            r_ext = h->R_all.as<float>() + off;
-            if (planes_call) for (int i = 0; i < 3; ++i) pl_ext[i] = h->planes_all[i].as<__bf16>() + off;
-        }
-        // (experiments) INFV_SMALL_TILES=<mask>: bit 0 / 1 / 2 = the call's first / second / last sub-batch runs the projection as
-        // 128 x 128 tiles (hundreds of short workgroups: faster while the chip is still -- or again -- empty)
-        // Shipped (bit 3, round 6): the LAST sub-batch of a long call -- behind the pooling launch the call's tail is serial (GEMM -> role S ->
-        // alpha -> UC of the last sub-batch) and the chip is emptying: 288 short workgroups finish sooner than 54 of 120 us.  13.45
-        // against 13.63 ms per video over five alternating rounds on one box; the two tilings give the same bits (test-enforced).
-        static const int small_mask = [] { const char* e = exp_env("INFV_SMALL_TILES"); return e ? atoi(e) : 8; }();
-        static const int small_below = [] { const char* e = exp_env("INFV_SMALL_BELOW"); return e ? atoi(e) : 0; }();   // sub-batches of fewer chunks than this
-        const bool small = (n_chunks < 768 && (((small_mask & 1) && b == 0) || ((small_mask & 2) && b == 1) || ((small_mask & 4) && b == n_batches - 1) || nb < small_below)) ||
-                           ((small_mask & 8) && n_chunks >= 768 && b == n_batches - 1);      // bit 3: the LAST sub-batch of a long call (the chip is emptying: the serial tail)
-        if (int rc = project_chunks_fast(h, *plan, true, kb, nb, T, Q, pp, set, &sks[b], &sss[b], side, kGemmPad,
-                                         h->vproj_on_uc(n_chunks), rset, use_pr, r_ext, (planes_call || planes_by_pool[b]) ? pl_ext : nullptr, small)) return rc;
-        HIP_TRY(hipEventRecord(h->ev_p[set], side));
-        p_pending[set] = true;
-        if (use_call) {
-            int sk = 1; long ss = 0;
-            predict_split(nb, &sk, &ss);
-            if (sk != sks[b] || ss != sss[b]) return fail(INFV_ERR_STATE, "consolidate: sub-batch %d was projected in a split-K form the resident chain kernel was not told about", b);
-            HIP_TRY(launch_flag_set(h->call_flags.as<unsigned int>(), (unsigned int)(b + 1), side));
-        }
-        return INFV_OK;
-    };
-    if (n_batches > 0) {
-        HIP_TRY(hipEventRecord(h->ev_in, stream));            // inputs, cq and the first chunk's set are ordered before
-        if (use_call) {
-            int sk_main = 1, sk_last = 1; long ss_main = 0, ss_last = 0;
-            int c0l, nbl; batch_range(n_batches - 1, &c0l, &nbl);
-            predict_split(sub, &sk_main, &ss_main);
-            predict_split(nbl, &sk_last, &ss_last);
-            if (n_batches == 1) { sk_main = sk_last; ss_main = ss_last; }
-            if (call_stream != stream) HIP_TRY(hipStreamWaitEvent(call_stream, h->ev_in, 0));
-            pipe.stream = call_stream;
-            const float* sets[kCallSets] = {};
-            for (int i = 0; i < kPSets; ++i) sets[i] = h->P_ws[i].as<float>() + (size_t)v_cols_all;
-            const int s_ct = (h->L * h->H * Q) / 256;                                   // S' column tiles of the projection
-            const int rt_full = (int)(((long)sub * (long)rows + 383) / 384), rt_last = (int)(((long)nbl * (long)rows + 383) / 384);
-            if (int rc = pipe.launch_s_call(n_chunks - first_c, sub, n_batches, sets, kPSets, sk_main, ss_main, sk_last, ss_last,
-                                            u + (size_t)first_c * chunk_u, uf + (size_t)first_c * chunk_u,
-                                            use_gemm_call ? h->gemm_flags.as<unsigned int>() + 128 : nullptr, n_tiled, s_ct * rt_full,
-                                            s_ct * (n_tiled == n_batches ? rt_last : rt_full))) return rc;
-            if (call_stream != stream) HIP_TRY(hipEventRecord(h->ev_chain, call_stream));
-            pipe.stream = stream;
-        }
-        HIP_TRY(hipStreamWaitEvent(side, h->ev_q, 0));
-        if (use_gemm_call) {
-            GemmCallDesc gd;
-            memset(&gd, 0, sizeof(gd));
-            unsigned int* gf = h->gemm_flags.as<unsigned int>();
-            for (int i = 0; i < 3; ++i) { gd.A_all[i] = h->planes_all[i].as<__bf16>(); gd.B[i] = h->w3[i].as<__bf16>(); }
-            for (int i = 0; i < kPSets; ++i) gd.C_set[i] = h->P_ws[i].as<float>();
-            gd.n_sets = kPSets;
-            gd.ldc = (long)h->L * h->dm + (long)h->L * h->H * Q; gd.N = (int)gd.ldc; gd.K = h->d;
-            gd.sub_rows = (int)(sub * rows);
-            gd.total_rows = (n_tiled == n_batches) ? (long)(n_chunks - first_c) * (long)rows : (long)n_tiled * sub * (long)rows;
-            gd.n_batches = n_tiled;
-            gd.s_col_tile0 = (h->L * h->dm) / 256;
-            gd.pool_done = h->pool_done.as<unsigned int>();
-            gd.tile_ctr = gf; gd.uc_done = gf + 64; gd.done_s = gf + 128; gd.done_v = gf + 128 + h->gemm_flags_cap;
-            gd.error = h->err_dev; gd.spin_limit = h->spin_limit;
-            GemmCallDesc* gd_dev = reinterpret_cast<GemmCallDesc*>(gf + 128 + 2 * h->gemm_flags_cap);
-            Timed t_(h->prof, INFV_KERNEL_PROJECT, side);
-            HIP_TRY(launch_gemm_x6_call(gd, gd_dev, gemm_wgs, side));
-        }
-        if (split_pool) HIP_TRY(hipStreamWaitEvent(pools, h->ev_start, 0));
-        if (use_pool_call) {
-            PoolCallDesc pc;
-            memset(&pc, 0, sizeof(pc));
-            pc.sub = sub; pc.n_chunks = n_chunks - first_c;
-            pc.R_all = h->R_all.as<float>();
-            if (planes_call) for (int i = 0; i < 3; ++i) pc.plane[i] = h->planes_all[i].p;
-            pc.done = h->pool_done.as<unsigned int>();
-            Timed t_(h->prof, INFV_KERNEL_POOL, pools);
-            HIP_TRY(launch_pool_rows2_call(k + first_c * chunk_k, h->k_bf16, T, h->P, h->d, plan->inf.view(), pc, pools, pr_u, pr_pad));
-        }
-        if (int rc = stage_pool(0)) return rc;
-        if (n_batches > 1)
-            if (int rc = stage_pool(1)) return rc;
-        if (int rc = stage_project(0)) return rc;
-    }
-    auto stage_parallel = [&](int b) -> int {                  // issued while batch b-1's chain is about to start
-        if (b + 1 < n_batches)
-            if (int rc = stage_pool(b + 1)) return rc;
-        return stage_project(b);
-    };
-    static const bool host_trace = exp_env("INFV_HOST_TRACE") != nullptr;   // host time of every loop iteration (is the host ahead of the device?)
-    std::vector<double> host_us;
-    const auto host_t0 = std::chrono::steady_clock::now();
-    // (CU-mask experiment: role S's launches go to the stream that owns the reserved CUs; it starts behind everything the caller's
-    //  stream has done so far and the caller's stream picks up behind it at the join)
-    hipStream_t ls = stream;
-    if (h->chain_s != nullptr && cu_mask_k() > 0 && persistent && n_batches > 0) {
-        ls = h->chain_s;
-        HIP_TRY(hipStreamWaitEvent(ls, h->ev_in, 0));
-        pipe.stream = ls;
-    }
-    for (int b = 0; b < n_batches; ++b) {
-        if (host_trace) host_us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - host_t0).count());
-        int c0, nb; batch_range(b, &c0, &nb);
-        const int set = b % kPSets, rset = b % kRSets;
-        // (experiments) INFV_DROP_WAITS=<mask>: what the packets between two role-S launches cost.  1: no wait for the UC kernel of
-        // sub-batch b - 5 on the caller's stream (redundant: the GEMM of sub-batch b waited for it, and this stream waits for that GEMM);
-        // 2: no event record behind role S / no wait of the UC stream for it (WRONG results: timing only); 4: no wait for the GEMM (WRONG)
-        static const int drop_waits = [] { const char* e = exp_env("INFV_DROP_WAITS"); return e ? atoi(e) : 1; }();   // (round 6: bit 0 is the default -- 13.62 against 13.72 ms, tighter)
-        if (!use_call) {
-            if (!(drop_waits & 4)) HIP_TRY(hipStreamWaitEvent(ls, h->ev_p[set], 0));
-            // the ring slots this batch writes were last read by the UC kernel three batches ago (same set)
-            if (uc_pending[set] && !(drop_waits & 1)) HIP_TRY(hipStreamWaitEvent(ls, h->ev_uc[set], 0));
-        }
-        const long slot0 = use_call ? call_slot0 + (long)(c0 - first_c) : pipe.counter;
-        const float* r_rows = use_pool_call ? h->R_all.as<float>() + (size_t)(c0 - first_c) * rows * h->d : h->R_ws[rset].as<float>();   // the sub-batch's new rows
-        const bool serial = host_serial();                              // timing experiments: no overlap between the streams
-        if (serial) { HIP_TRY(hipStreamSynchronize(pools)); HIP_TRY(hipStreamSynchronize(side)); HIP_TRY(hipStreamSynchronize(ucs)); }
-        if (use_call) {
-            // role S is resident: only the chunk-parallel stage of the next sub-batch goes out here
-            if (b + 1 < n_batches)
-                if (int rc = stage_parallel(b + 1)) return rc;
-        } else if (persistent) {
-            // the chunk-parallel stage of the next batch goes out first so it overlaps this batch's chain
-            if (b + 1 < n_batches)
-                if (int rc = stage_parallel(b + 1)) return rc;
-            if (serial) { HIP_TRY(hipStreamSynchronize(pools)); HIP_TRY(hipStreamSynchronize(side)); }
-            if (int rc = pipe.launch_s_batch(nb, h->P_ws[set].as<float>() + (size_t)h->L * h->dm, sks[b], sss[b],
-                                             u ? u + (size_t)c0 * chunk_u : nullptr, uf ? uf + (size_t)c0 * chunk_u : nullptr)) return rc;
-            if (serial) HIP_TRY(hipStreamSynchronize(ls));
-        } else {
-            for (int i = 0; i < nb; ++i) {
-                const size_t ld = (size_t)h->L * h->dm + (size_t)h->L * h->H * Q;
-                const StepS st{&plan->inf, true, h->P_ws[set].as<float>() + (size_t)i * rows * ld + (size_t)h->L * h->dm,
-                               u ? u + (size_t)(c0 + i) * chunk_u : nullptr, sks[b], sss[b]};
-                if (int rc = pipe.launch_s(st)) return rc;
-                if (i == 0 && b + 1 < n_batches)
-                    if (int rc = stage_parallel(b + 1)) return rc;
-            }
-        }
-        // What the UC kernel needs besides role S's tables -- the softmax weights, and the V' half of the projection when it
-        // is not part of the side stream's GEMM -- runs on the UC stream itself (a stream of its own for it was measured much
-        // worse in rounds 1 and 2: every extra concurrent kernel slows role S and the GEMMs more than the shorter stream gains).
-        hipStream_t vs = ucs;
-        if (h->vproj_on_uc(n_chunks) && (long)nb * plan->inf.rows >= 1024 && !(skip_mask() & 2)) {
-            // V' half of this sub-batch's projection: needs the new rows (ev_p), feeds only the UC kernel below
-            HIP_TRY(hipStreamWaitEvent(vs, h->ev_p[set], 0));
-            Timed t_(h->prof, INFV_KERNEL_PROJECT, vs);
-            const long Mv = (long)nb * plan->inf.rows;
-            const int v_cols = h->L * h->dm, p_ld = h->L * h->dm + h->L * h->H * Q;
-            // exact fp32 MFMA by default.  INFV_VPROJ_SPLIT=1: V' only feeds the read-out (1e-3 budget), so it may run as a
-            // split-bf16 contraction (three bf16 MFMA products, ~1e-5 relative); bench.py then labels its dtype accordingly
-            if (h->v_split && h->d % 64 == 0 && v_cols % 128 == 0) {
-                const size_t szW = (size_t)v_cols * h->d * 2, szR = (size_t)h->maxC * plan->inf.rows * h->d * 2;
-                if (szW > h->wv_hi.bytes || szR > h->R_hi.bytes) {
-                    HIP_TRY(hipDeviceSynchronize());
-                    HIP_TRY(h->wv_hi.reserve(szW)); HIP_TRY(h->wv_lo.reserve(szW));
-                    HIP_TRY(h->R_hi.reserve(szR)); HIP_TRY(h->R_lo.reserve(szR));
-                    h->wv_split_valid = false;
-                }
-                if (!h->wv_split_valid) {
-                    for (int l = 0; l < h->L; ++l)
-                        HIP_TRY(launch_split_rows(pp.wv[l], h->d, h->dm, h->d, h->wv_hi.as<__bf16>() + (size_t)l * h->dm * h->d,
-                                                  h->wv_lo.as<__bf16>() + (size_t)l * h->dm * h->d, h->d, vs));
-                    h->wv_split_valid = true;
-                }
-                HIP_TRY(launch_split_rows(r_rows, h->d, Mv, h->d, h->R_hi.p, h->R_lo.p, h->d, vs));
-                SplitGemm g{};
-                g.A_hi = h->R_hi.as<__bf16>(); g.A_lo = h->R_lo.as<__bf16>(); g.lda = h->d; g.strideA = 0;
-                g.B_hi = h->wv_hi.as<__bf16>(); g.B_lo = h->wv_lo.as<__bf16>(); g.ldb = h->d; g.strideB = 0;
-                g.C = h->P_ws[set].as<float>(); g.ldc = p_ld; g.strideC = 0; g.split_stride = 0;
-                g.M = (int)Mv; g.N = v_cols; g.K = h->d; g.k_per_split = h->d; g.splitk = 1; g.nbatch = 1;
-                HIP_TRY(launch_split_gemm(g, vs, kGemmPad));
-            } else {
-                HIP_TRY(launch_project_values((int)Mv, h->d, h->dm, h->L, pp, r_rows,
-                                              h->P_ws[set].as<float>(), p_ld, vs, kGemmPad));
-            }
-        }
-        if (use_call) {
-            // the UC stream holds until every role-S workgroup has written sub-batch b's steps back (the counter was zeroed on the
-            // caller's stream: the first wait of a call is ordered behind that)
-            if (b == 0) HIP_TRY(hipStreamWaitEvent(ucs, h->ev_in, 0));
-            HIP_TRY(launch_flag_wait(h->call_flags.as<unsigned int>() + 64, (unsigned int)(b + 1) * (unsigned int)call_wgs, h->spin_limit, h->err_dev, ucs));
-            if (b < n_tiled) {
-                const int rt_b = (int)(((long)nb * (long)rows + 383) / 384);
-                HIP_TRY(launch_flag_wait(h->gemm_flags.as<unsigned int>() + 128 + h->gemm_flags_cap + b, (unsigned int)(rt_b * (v_cols_all / 256)),
-                                         h->spin_limit, h->err_dev, ucs));
-            }
-            pipe.last_snew = h->P_ws[set].as<float>() + (size_t)v_cols_all; pipe.last_sk = sks[b]; pipe.last_ss = sss[b];
-        } else if (!(drop_waits & 2)) {
-            HIP_TRY(hipEventRecord(h->ev_s[set], ls));
-            HIP_TRY(hipStreamWaitEvent(ucs, h->ev_s[set], 0));
-        }
-        if (persistent)
-            if (int rc = pipe.launch_alpha(nb, slot0, vs, b == n_batches - 1)) return rc;
-        if (int rc = pipe.launch_uc(plan->inf, true, nb, slot0, r_rows, h->P_ws[set].as<float>(),
-                                    sks[b], sss[b], ctx + (size_t)c0 * chunk_ctx, ucs)) return rc;
-        if (use_gemm_call) HIP_TRY(launch_flag_set(h->gemm_flags.as<unsigned int>() + 64, (unsigned int)(b + 1), ucs));   // the output set of sub-batch b is free again
-        HIP_TRY(hipEventRecord(h->ev_uc[set], ucs));
-        uc_pending[set] = true;
-        HIP_TRY(hipEventRecord(h->ev_r[rset], ucs));
-        r_pending[rset] = true;
-    }
-    if (host_trace && !host_us.empty()) {
-        fprintf(stderr, "[host trace] %d iterations, issue time us:", n_batches);
-        for (size_t i = 0; i < host_us.size(); i += 4) fprintf(stderr, " %.0f", host_us[i]);
-        fprintf(stderr, " | end %.0f\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - host_t0).count());
-    }
-    // join: the memory and every ctx are complete once the last UC kernel is; then hand the sticky histogram
-    // back as one float partial row and bring the K' half of the projected memory up to date
-    if (ls != stream) {
-        HIP_TRY(hipEventRecord(h->ev_in, ls));
-        HIP_TRY(hipStreamWaitEvent(stream, h->ev_in, 0));
-        pipe.stream = stream;
-    }
-    if (use_call && call_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, h->ev_chain, 0));
-    for (int i = 0; i < kPSets; ++i)
-        if (uc_pending[i]) HIP_TRY(hipStreamWaitEvent(stream, h->ev_uc[i], 0));
-    if (pipe.counter > 0) {
-        if (pipe.last_v2 && pipe.batch_launches > 0 && chain_batch3_mailboxes())   // (experiments) the last step's totals are in the mailboxes
-            HIP_TRY(launch_mailbox_to_part(h->mbox.as<unsigned long long>(), h->L, h->mbox_G, (int)((pipe.counter - 1) & 1), 1,
-                                           h->bin_part[h->pc].as<float>(), stream));
-        else
-            HIP_TRY(launch_acc_to_part(h->mass_acc[(pipe.counter + 2) % 3].as<unsigned long long>(), h->L, 1,
-                                       h->bin_part[h->pc].as<float>(), stream));
-        h->parts = 1;
-    }
-    h->k_stale = true;                                        // K' is re-projected from B on demand (per-call path, continuation)
-    return INFV_OK;
+    if (int rc = consolidate_setup(h, cc, pipe)) return rc;
+    consolidate_schedule(h, cc);
+    if (int rc = consolidate_first_chunk(h, cc, pipe)) return rc;
+    if (int rc = consolidate_workspaces(h, cc)) return rc;
+    if (int rc = consolidate_sub_batches(h, cc, pipe)) return rc;
+    return consolidate_join(h, cc, pipe);
 }
 
 int infv_ltm_consolidate(infv_ltm_handle h, const void* k, int32_t n_chunks, int32_t T, const float* q,

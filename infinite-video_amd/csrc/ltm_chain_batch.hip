@@ -317,17 +317,11 @@ __device__ inline float wave_shl1(float v, float fill) {
 }
 
 // Round 4 -- what shortened the step (measured with tools/ubench/exchange.hip and the in-kernel stamps):
-//  (1) The exchange stays inside ONE XCD's L2.  Every cross-XCD form of the 127-value all-reduce over a layer's 24 workgroups
-//      costs 1.8-1.9 us per step on an idle chip -- fixed-point atomics (one word or 2-8 replicas per bin), or mailboxes
-//      written and read with sc1 -- because each hop is a trip to the memory side.  A layer's workgroups are now launched
-//      with block ids that are equal mod 8 (round-robin placement puts them on one XCD; blocks of the other residues exit
-//      at once) and exchange through MAILBOXES: every workgroup stores its 127 row sums as 8-byte {mass, step tag} granules
-//      into its own 1-KB slot with PLAIN stores (write-through L1, the line stays in that XCD's L2), every workgroup reads
-//      all slots with sc1 loads (past its L1, served by that same L2), re-reads a slot until its tags match, and adds the
-//      slots in a fixed order: 0.85 us per step in the micro-benchmark.  Placement is never assumed: at launch the
-//      workgroups of a layer publish their HW_REG_XCC_ID through sc1 granules (valid at any placement) and only if all are
-//      equal use plain stores; otherwise the same mailboxes are written with sc1 stores (cross-XCD coherent, 1.8 us).  The
-//      totals are the same fp32 sums in the same order either way, on every workgroup: placement changes speed only.
+//  (1) The exchange: every cross-XCD form of the 127-value all-reduce over a layer's 24 workgroups costs 1.8-1.9 us per step on
+//      an idle chip -- fixed-point atomics (one word or 2-8 replicas per bin), or mailboxes written and read with sc1.  Mailboxes
+//      inside ONE XCD's L2 took 0.85 us in the micro-benchmark, but a layer then needs 24 free CUs on one XCD at every launch,
+//      which in the shared pipeline cost far more than it saved (33 against 13.5 ms per video, round 5): the atomics stayed,
+//      and the mailbox form has been deleted.
 //  (2) The uniforms arrive as fp32 round-ups (round_up_uniforms_kernel, once per call, off the chain): the loader holds
 //      24 instead of 32 registers per set and parks with two b128 stores instead of 8 conversions; it parks BEHIND
 //      barrier 3 (in the shadow of the exchange), so the search window holds nothing but the search (0.84 -> 0.52 us).
@@ -338,30 +332,25 @@ __device__ inline float wave_shl1(float v, float fill) {
 //  Not kept: the cdf as one lane's register chain through LDS (a dependent v_add_f32 costs 9.3 clocks, not 4: 127 of them
 //  plus the LDS round trips took 1970 clocks against 1670 for the systolic DPP scan, whose floor is those 9.3 + a hazard nop).
 // ======================================================================================================
-struct Batch3Smem { int cdf, coarse, part, pos, tabb, box_val, box_row, pb, sc, Snew, uf, Msm, total; };
+struct Batch3Smem { int cdf, coarse, pos, tabb, box_val, box_row, pb, sc, Snew, uf, Msm, total; };
 constexpr int kZeroPoint = kBins;          // word 128 of every score row holds 0.0f (rows have kScPitch = 132 words)
-constexpr int kPollWaves = 6;              // waves 0..5 read the mailboxes (wave 7's long-latency input requests must not sit in
-                                           // front of a poll in its vmcnt queue; wave 6 carries the writer's extra stores)
-constexpr int kPollRound = 4;              // slots per wave and round: 24 workgroups per layer = one round
-
-constexpr int kDmaPar = 4;                // DMA loader: LDS buffers of the S'new tile / the uniforms (steps i .. i+3)
-constexpr int kDmaSnew = 64 * kB2Ld * 4;  // floats of one S'new buffer: kB2Ld load instructions of 1 KiB
-constexpr int kDmaUf = 64 * 2 * 4;        // floats of one uniforms buffer: two load instructions
-__host__ __device__ inline Batch3Smem batch3_smem(int N, int S, int rows, int tabw, int rpw, bool dma = false) {
+constexpr int kReservedWords = 6 * kBins;  // unused since the mailbox exchange was deleted: kept so that the launch's LDS, which
+                                           // decides what shares a CU with role S, stays what the stream layout was tuned for
+__host__ __device__ inline Batch3Smem batch3_smem(int N, int S, int rows, int tabw, int rpw) {
     Batch3Smem m;
     int o = 0;
     auto take = [&](int n) { int r = o; o += (n + 3) & ~3; return r; };
     m.cdf = take(kBins);
     m.coarse = take(16);
-    m.part = take(kPollWaves * kBins);
+    (void)take(kReservedWords);
     m.pos = take(S);
     m.tabb = take(N * tabw);
     m.box_val = take(N);
     m.box_row = take(N);
     m.pb = take(kBins);
     m.sc = take(rpw * kBRows * kScPitch);
-    m.Snew = dma ? take(kDmaPar * kDmaSnew) : take(2 * rpw * kBRows * (rows + 1));
-    m.uf = dma ? take(kDmaPar * kDmaUf) : take(2 * S);
+    m.Snew = take(2 * rpw * kBRows * (rows + 1));
+    m.uf = take(2 * S);
     m.Msm = take(rpw * kBRows * kMPitch);
     m.total = o;
     return m;
@@ -383,92 +372,31 @@ hipError_t launch_round_up_uniforms(const double* u, float* uf, long n, hipStrea
     return hipGetLastError();
 }
 
-// ---- mailboxes of the exchange (ChainBatchArgs.mbox): [2 parities][L][G slots][128 granules of {float mass, uint tag}], then the
-// placement handshake [L][G] 16-byte granules {xcc, tag, xcc, tag}.  Granule acc_word(j) of a slot holds bin j, so lane i's
-// 16-byte load at byte 16 i returns bins (i, i + 64).  The total of a bin is DEFINED as
-//     sum over w = 0..kPollWaves-1 (in order) of [ sum over slots g = w, w + kPollWaves, ... (in order) of mass[g] ]     (fp32)
-// -- the order the kernel's waves add in; mailbox_total() restates it for the hand-over kernels.
-__host__ __device__ inline long mbox_slot_granules(int L, int G, int parity, int l, int g) { return (((long)parity * L + l) * G + g) * kBins; }
-__host__ __device__ inline long mbox_handshake_granules(int L, int G) { return 2L * L * G * kBins; }     // 16-byte units follow at this 8-byte offset
-size_t chain_mailbox_bytes(int L, int G) { return (size_t)mbox_handshake_granules(L, G) * 8 + (size_t)L * G * 16; }
-
-__device__ inline float mailbox_total(const unsigned long long* mbox, int L, int G, int parity, int l, int j) {
-    float t = 0.f;
-    for (int w = 0; w < kPollWaves; ++w) {
-        float s = 0.f;
-        for (int g = w; g < G; g += kPollWaves) s += __uint_as_float((unsigned int)(mbox[mbox_slot_granules(L, G, parity, l, g) + acc_word(j)] & 0xffffffffull));
-        t += s;
-    }
-    return t;
-}
-
-#ifdef INFV_EXPERIMENTS
-// part[l][0][j] = total of bin j of the step whose mailboxes have parity `parity` (fast path -> per-call path hand-over)
-__global__ void mailbox_to_part_kernel(const unsigned long long* __restrict__ mbox, int L, int G, int parity, int parts_pitch, float* __restrict__ part) {
-    const int l = blockIdx.x, j = threadIdx.x;
-    if (j >= kBins) return;
-    part[((long)l * parts_pitch) * kBins + j] = (j < kBins - 1) ? mailbox_total(mbox, L, G, parity, l, j) : 0.f;
-}
-hipError_t launch_mailbox_to_part(const unsigned long long* mbox, int n_layers, int G, int parity, int parts_pitch, float* part, hipStream_t stream) {
-    INFV_LAUNCH(mailbox_to_part_kernel, dim3(n_layers), dim3(128), 0, stream, mbox, n_layers, G, parity, parts_pitch, part);
-    return hipGetLastError();
-}
-#else
-hipError_t launch_mailbox_to_part(const unsigned long long*, int, int, int, int, float*, hipStream_t) { return hipErrorNotSupported; }
-#endif
-
-__device__ inline int xcc_id() { int v; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v)); return v & 15; }
-
-// MBOX = false: the exchange of rounds 1-3 (fixed-point u64 atomics at the memory side, arrival count in the word, one
-//                poller), valid at any placement, linear grid: what the per-sub-batch launches of consolidate() use;
-// MBOX = true:  mailboxes inside one XCD's L2 (XCD-aware grid + placement handshake): 0.6 us per step less and no slower
-//                beside the other kernels -- but a layer then needs 24 FREE CUs on one XCD at every launch, which in the shared
-//                pipeline takes longer than the launch saves (21.5 against 14.7 ms per video): experiments build only
-//                (INFV_CHAIN_XCD=1), for a future call-long launch on dedicated CUs.
-// DMA = true (round 6): the loader wave moves the S'new tile and the uniforms global -> LDS with `buffer_load_dwordx4 ... lds`
-//   (no register sets: the two sets of the register loader and their address arithmetic were 86 of the kernel's 214 registers),
-//   four LDS buffers deep (requested three steps ahead).  The kernel then fits 128 registers: two of these workgroups -- or one
-//   and a pooling workgroup -- share a CU.  Needs splitk == 1 (a DMA cannot add slabs), per-sub-batch launches, atomics exchange.
-#ifndef INFV_CHAIN_WPE
-#define INFV_CHAIN_WPE 4
-#endif
-// (one kernel template, DMA a parameter: the waves-per-SIMD attribute takes a template-dependent argument -- as an inlined body
-//  function behind two kernels the register-loader form carried 20 bytes of unused private segment)
-template <int RPW, bool MBOX, bool DMA>
-__global__ __launch_bounds__(kBNT) __attribute__((amdgpu_waves_per_eu(DMA ? INFV_CHAIN_WPE : 2, DMA ? INFV_CHAIN_WPE : 2)))
+// The exchange: fixed-point u64 atomics at the memory side, arrival count in the word, one poller; valid at any placement,
+// linear grid, one launch per sub-batch.  (Rounds 4-6 also built a mailbox exchange inside one XCD's L2, a call-long launch and
+// an LDS-DMA loader of this kernel; all three measured slower in the shared pipeline and were deleted -- docs/NOTEBOOK.md.)
+template <int RPW>
+__global__ __launch_bounds__(kBNT) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void chain_batch3_kernel(ChainBatchArgs a) {
     constexpr int TR = kBRows * RPW;                                   // rows of the tile
     constexpr int PPR = TR / 4;                                        // float4 pieces per new row of the S'new tile
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int N = a.N, H = a.H, Q = a.Q, QS = a.QS;
     const int blocks_per_layer = H * QS;
-    // ---- block -> (layer, workgroup of the layer).  XCD-aware launches (a.xcd_grid): grid = 8 * blocks_per_layer, block b sits
-    // in placement class b % 8 (blocks of one class share an XCD under round-robin placement); layer l is served by class
-    // (8 l) / L, the other classes have nothing to do.
-    int l, blk;
-    if (MBOX && a.xcd_grid) {
-        const int cls = blockIdx.x & 7;
-        l = -1;
-        for (int ll = 0; ll < a.L; ++ll) if ((8 * ll) / a.L == cls) l = ll;
-        if (l < 0) return;
-        blk = blockIdx.x >> 3;
-    } else {
-        l = blockIdx.x / blocks_per_layer;
-        blk = blockIdx.x - l * blocks_per_layer;
-    }
+    // ---- block -> (layer, workgroup of the layer)
+    const int l = blockIdx.x / blocks_per_layer;
+    const int blk = blockIdx.x - l * blocks_per_layer;
     if (!(a.exp_flags & 1)) __builtin_amdgcn_s_setprio(3);
     wg_stamp_begin(a.wg_stamps);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (a.dbg != nullptr && l == 0 && blk == 0 && tid == 0) a.dbg[18] = wall_clock64();      // (stamps: kernel entry of workgroup 0)
     const int rows = a.op.rows, tabw = a.op.tabw;
-    const Batch3Smem m = batch3_smem(N, a.S, rows, tabw, RPW, DMA);
+    const Batch3Smem m = batch3_smem(N, a.S, rows, tabw, RPW);
     const int h = blk % H, qs = blk / H;
     const int b = l * blocks_per_layer + blk;                          // (stamps: workgroup 0 = layer 0, head 0, tile 0)
-    const int G = blocks_per_layer;
     const int sn = rows + 1, sn_tile = TR * sn;
     float* cdf = lds + m.cdf;
     float* coarse = lds + m.coarse;
-    float* part = lds + m.part;
     int32_t* tabb = reinterpret_cast<int32_t*>(lds + m.tabb);          // byte offset (into a score row) of the k-th resampled slot of box n
     int32_t* pb = reinterpret_cast<int32_t*>(lds + m.pb);
     const float* box_val = lds + m.box_val;
@@ -478,18 +406,6 @@ void chain_batch3_kernel(ChainBatchArgs a) {
     const int valid = min(TR, Q - qs * TR);
     const bool writer = (h == 0 && qs == 0);
     const bool loader = wave == kBRows - 1;
-    const bool poller = wave < kPollWaves;
-    const long tile_snew = (long)rows * a.snew_ld;
-
-    // ---- placement handshake, first half: publish this workgroup's XCD (sc1: visible at any placement) ----
-    const unsigned int launch_tag = (unsigned int)(a.step0 + 1);
-    uintx4_t* hs = MBOX ? reinterpret_cast<uintx4_t*>(a.mbox + mbox_handshake_granules(a.L, G)) + (long)l * G : nullptr;
-    if (MBOX && wave == 0 && lane == 0) {
-        const unsigned int x = (unsigned int)xcc_id();
-        const uintx4_t v = {x, launch_tag, x, launch_tag};
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(hs, 0, G * 16, 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, blk * 16, 0, 16 /* sc1 */);
-    }
 
     // ---- one-time set-up ----
     {
@@ -500,8 +416,7 @@ void chain_batch3_kernel(ChainBatchArgs a) {
         }
         if (tid < kBins) pb[tid] = a.st.bin_box[tid];
         if (tid < a.S) pos[tid] = -1;
-        for (int e = tid; e < (DMA ? kDmaPar * kDmaSnew : 2 * sn_tile); e += kBNT) (lds + m.Snew)[e] = 0.f;     // incl. the zero column (index rows) of every row
-        if (DMA) for (int e = tid; e < kDmaPar * kDmaUf; e += kBNT) (lds + m.uf)[e] = 2.f;                       // (a uniform nobody draws with)
+        for (int e = tid; e < 2 * sn_tile; e += kBNT) (lds + m.Snew)[e] = 0.f;     // incl. the zero column (index rows) of every row
         for (int e = tid; e < TR * kScPitch; e += kBNT) (lds + m.sc)[e] = 0.f;     // incl. the zero point of every row
         __syncthreads();
         for (int e = tid; e < N * tabw; e += kBNT) {
@@ -520,9 +435,6 @@ void chain_batch3_kernel(ChainBatchArgs a) {
     const int n0 = pb[lane], n1 = pb[lane + 64];
     const float val0 = box_val[n0], val1 = box_val[n1];
     const int br0 = box_row[n0] >= 0 ? box_row[n0] : rows, br1 = box_row[n1] >= 0 ? box_row[n1] : rows;   // `rows` = the zero column
-    // DMA layout of the S'new tile: float4 slot (hf, nr) = hf * rows + nr holds tile rows 4 hf .. 4 hf + 3 of new row nr
-    const bool has_r0 = br0 < rows, has_r1 = br1 < rows;
-    const int sna0 = has_r0 ? 4 * br0 : 0, sna1 = has_r1 ? 4 * br1 : 0;
     const bool e0ok = a.st.edge_box[lane] >= 0, e1ok = a.st.edge_box[lane + 64] >= 0;     // edge 0 lies left of every box
     const float dx0 = a.st.edge_dx[lane], dx1 = a.st.edge_dx[lane + 64];
     const float dxa = a.st.edge_dx[lane + 1], dxb = (lane + 65 < kBins) ? a.st.edge_dx[lane + 65] : 0.f;
@@ -547,81 +459,14 @@ void chain_batch3_kernel(ChainBatchArgs a) {
     // ---- loader (wave 7): the S'new tile and the rounded-up uniforms of a step in registers, two sets (steps i+1, i+2 in
     // flight).  Wide loads only.  S'new tile: new row nr holds this tile's TR scores contiguously -> float4 e4 = lane + 64 k:
     // row e4 / PPR, piece e4 % PPR;   uniforms: S floats -> two float4 per lane
-    struct LdSet { floatx4 sn[DMA ? 1 : kB2Ld]; floatx4 u[DMA ? 1 : 2]; };
+    struct LdSet { floatx4 sn[kB2Ld]; floatx4 u[2]; };
     LdSet ldA, ldB;
-    // ---- DMA loader: per-lane global byte offsets of this lane's float4 of each load instruction (an offset beyond the buffer's
-    // range reads as zero), the same for every step; the step selects the buffer through the scalar offset
-    typedef int v4i_t __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
-    int dvo[kB2Ld] = {-1, -1, -1, -1}, dvu[2] = {-1, -1};
-    v4i_t drs_sn = {0, 0, 0, 0}, drs_uf = {0, 0, 0, 0};
-    unsigned dl_sn = 0, dl_uf = 0;
-    if constexpr (DMA) {
-#pragma unroll
-        for (int k = 0; k < kB2Ld; ++k) {
-            const int e4 = lane + 64 * k;
-            const int hf = e4 / rows, nr = e4 - hf * rows;
-            dvo[k] = (hf < PPR && 4 * hf < valid) ? (nr * a.snew_ld + 4 * hf) * 4 : -1;
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) { const int s4 = lane + 64 * k; dvu[k] = (4 * s4 < a.S) ? 16 * s4 : -1; }
-        const unsigned long ps = reinterpret_cast<unsigned long>(a.Snew + tile), pu = reinterpret_cast<unsigned long>(a.uf + (long)l * a.S);
-        drs_sn = v4i_t{(int)(unsigned)ps, (int)(unsigned)((ps >> 32) & 0xffffu), 0x7fffffff, 0x00020000};
-        drs_uf = v4i_t{(int)(unsigned)pu, (int)(unsigned)((pu >> 32) & 0xffffu), 0x7fffffff, 0x00020000};
-        dl_sn = (unsigned)(unsigned long)(lds_ptr_t)(lds + m.Snew);
-        dl_uf = (unsigned)(unsigned long)(lds_ptr_t)(lds + m.uf);
-    }
-    auto dma16 = [](const v4i_t& rsrc, unsigned lds_addr, int voff, int soff) {
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                     :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(soff)) : "memory");
-    };
-    // request step i into buffer i % kDmaPar: six load instructions, no registers
-    auto dma_request = [&](int i) {
-        const int buf = i & (kDmaPar - 1);
-        const int so_sn = (int)((long)i * tile_snew * 4), so_uf = (int)((long)i * a.L * a.S * 4);     // (below 2^31: launcher)
-#pragma unroll
-        for (int k = 0; k < kB2Ld; ++k) dma16(drs_sn, dl_sn + (buf * kDmaSnew + k * 256) * 4, dvo[k], so_sn);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) dma16(drs_uf, dl_uf + (buf * kDmaUf + k * 256) * 4, dvu[k], so_uf);
-    };
-    // Call-long launch: step i belongs to sub-batch i / call_sub, whose S'new rows sit in workspace set (sub-batch % call_sets) once
-    // the GEMM stream has raised `ready` past it.  The rows were written by ANOTHER kernel while this one was running, possibly
-    // over lines this XCD's L2 still holds from the set's previous use: every load of them is an sc1 load (served by the
-    // memory side; the producer's end-of-kernel release has written them back before its flag kernel ran).
-    const bool call_long = a.call != nullptr;
-    unsigned int ready_seen = 0;                                              // (loader wave) sub-batches known to be projected
     auto ld_request = [&](int i, LdSet& r) {
-        const float* sb;
-        int splitk = a.snew_splitk;
-        long split_stride = a.snew_split_stride;
-        if (call_long) {
-            const ChainCallDesc* cd = a.call;                                 // (uniform address: scalar loads)
-            const int cb = i / a.call_sub, li = i - cb * a.call_sub;
-            if ((unsigned int)cb >= ready_seen) {
-                // sub-batch cb is projected: its S' tiles are counted in (call-long GEMM), or the per-sub-batch GEMM's flag has passed it
-                const bool tiled = cd->tiles_s != nullptr && cb < cd->n_tiled;
-                const unsigned int* ready = tiled ? cd->tiles_s + cb : cd->ready;
-                const unsigned int need = tiled ? (unsigned int)(cb == cd->n_tiled - 1 ? cd->tiles_last : cd->tiles_full) : (unsigned int)cb + 1u;
-                long long* stats = (b == 0) ? cd->stats : nullptr;
-                long long t0 = 0;
-                int spins = 0;
-                for (;;) {
-                    const unsigned int v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    if (v >= need) { ready_seen = tiled ? (unsigned int)cb + 1u : v; break; }
-                    if (spins == 0 && stats != nullptr) t0 = wall_clock64();
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > a.spin_limit) { __hip_atomic_store(a.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); ready_seen = 0xffffffffu; break; }   // (failed: no further waits)
-                }
-                if (spins > 0 && stats != nullptr && lane == 0) { stats[0] += wall_clock64() - t0; stats[1] += 1; }
-            }
-            sb = cd->snew_set[cb % cd->n_sets] + (long)li * tile_snew + tile;
-            if (cb == cd->n_batches - 1) { splitk = cd->sk_last; split_stride = cd->ss_last; }
-        } else {
-            sb = a.Snew + (long)i * tile_snew + tile;
-        }
+        // (the step's stride stays inline: as a hoisted variable the kernel carried an unused 20-byte private segment, kernel_regs.py)
+        const float* sb = a.Snew + (long)i * ((long)rows * a.snew_ld) + tile;
         // one buffer resource per split-K slab, its 64-bit base at the slab (a 32-bit slab offset overflowed for short sub-batches of
         // large models: the hardware then returns zeros, silently); the offset inside a slab, rows * snew_ld * 4 bytes, is bounded by
-        // the launcher.  sc1 only on the call-long launch, whose rows another kernel writes while this one is resident.
+        // the launcher.
         // (slab 0 on its own: its loads stay in flight behind the request; the further slabs of a short sub-batch are added behind them)
         {
             __amdgpu_buffer_rsrc_t rsn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sb), 0, 0x7fffffff, 0x00020000);
@@ -632,22 +477,20 @@ void chain_batch3_kernel(ChainBatchArgs a) {
                 floatx4 v = {0.f, 0.f, 0.f, 0.f};
                 if (nr < rows && 4 * hf < valid) {
                     const int off = (nr * a.snew_ld + 4 * hf) * 4;
-                    v = call_long ? as_floatx4(__builtin_amdgcn_raw_buffer_load_b128(rsn, off, 0, 16 /* sc1 */))
-                                  : as_floatx4(__builtin_amdgcn_raw_buffer_load_b128(rsn, off, 0, 0));
+                    v = as_floatx4(__builtin_amdgcn_raw_buffer_load_b128(rsn, off, 0, 0));
                 }
                 r.sn[k] = v;
             }
         }
-        for (int x = 1; x < splitk; ++x) {
-            __amdgpu_buffer_rsrc_t rsn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sb + (long)x * split_stride), 0, 0x7fffffff, 0x00020000);
+        for (int x = 1; x < a.snew_splitk; ++x) {
+            __amdgpu_buffer_rsrc_t rsn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sb + (long)x * a.snew_split_stride), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
             for (int k = 0; k < kB2Ld; ++k) {
                 const int e4 = lane + 64 * k;
                 const int nr = e4 / PPR, hf = e4 % PPR;
                 if (nr < rows && 4 * hf < valid) {
                     const int off = (nr * a.snew_ld + 4 * hf) * 4;
-                    r.sn[k] += call_long ? as_floatx4(__builtin_amdgcn_raw_buffer_load_b128(rsn, off, 0, 16 /* sc1 */))
-                                         : as_floatx4(__builtin_amdgcn_raw_buffer_load_b128(rsn, off, 0, 0));
+                    r.sn[k] += as_floatx4(__builtin_amdgcn_raw_buffer_load_b128(rsn, off, 0, 0));
                 }
             }
         }
@@ -678,88 +521,11 @@ void chain_batch3_kernel(ChainBatchArgs a) {
         }
     };
     if (loader) {
-        if constexpr (DMA) {
-            // steps 0, 1, 2 in flight; step 0 has landed before the barrier below hands it to the other waves
-            dma_request(0);
-            if (a.n_steps > 1) dma_request(1);
-            if (a.n_steps > 2) dma_request(2);
-            if (a.n_steps > 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-            else if (a.n_steps > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
         ld_request(0, ldA);
         ld_park(0, ldA);
         if (a.n_steps > 1) ld_request(1, ldB);                         // odd steps live in set B, even steps in set A
         if (a.n_steps > 2) ld_request(2, ldA);
-        }
     }
-
-    // ---- placement handshake, second half: one XCD for the whole layer?  (bounded wait; needs every workgroup resident, as
-    // the chain itself does) ----
-    bool plain = false;                                                       // plain mailbox stores: the layer's L2 is one
-    if constexpr (MBOX) {
-    if (wave == 0) {
-        bool same = false;
-        if (G <= 64 && a.xcd_grid && !(a.exp_flags & 32)) {
-            __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(hs, 0, G * 16, 0x00020000);
-            uintx4_t v = {0u, 0u, 0u, 0u};
-            int spins = 0;
-            for (;;) {
-                if (lane < G) v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, 0, 16 /* sc1 */);
-                if (!__any(lane < G && (v.y != launch_tag || v.w != launch_tag))) break;
-                __builtin_amdgcn_s_sleep(8);
-                if (++spins > a.spin_limit) { __hip_atomic_store(a.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-            }
-            const unsigned int mine = __builtin_amdgcn_readfirstlane(v.x);
-            same = !__any(lane < G && (v.x != mine || v.z != mine));
-        }
-        if (lane == 0) reinterpret_cast<int32_t*>(coarse)[0] = same ? 1 : 0;
-    }
-    __syncthreads();
-    plain = reinterpret_cast<const int32_t*>(coarse)[0] != 0;
-    __syncthreads();                                                          // (coarse is rewritten by wave 0 in step 0)
-    if (a.xcc_report != nullptr && tid == 0) a.xcc_report[b] = (plain ? 0x100 : 0) | xcc_id();
-    }
-
-    const unsigned long long* mbox = a.mbox;
-    // poll registers of waves 0..5: this wave's slots of the first round (slot g = wave + kPollWaves k)
-    uintx4_t pv[kPollRound];
-#pragma unroll
-    for (int k = 0; k < kPollRound; ++k) pv[k] = uintx4_t{0u, 0u, 0u, 0u};
-    auto poll_issue = [&](int parity, int round) {
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(mbox + mbox_slot_granules(a.L, G, parity, l, 0)), 0,
-                                                                      G * kBins * 8, 0x00020000);
-#pragma unroll
-        for (int k = 0; k < kPollRound; ++k) {
-            const int g = wave + kPollWaves * (kPollRound * round + k);
-            if (g < G) pv[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, g * kBins * 8, 16 /* sc1 */);
-        }
-    };
-    // wait for this wave's slots to carry `tag`, add them in slot order, park the partial sums for wave 0
-    auto poll_collect = [&](int parity, unsigned int tag, bool wait) {
-        float s0 = 0.f, s1 = 0.f;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(mbox + mbox_slot_granules(a.L, G, parity, l, 0)), 0,
-                                                                      G * kBins * 8, 0x00020000);
-        for (int round = 0; wave + kPollWaves * kPollRound * round < G; ++round) {
-            if (round > 0) poll_issue(parity, round);
-#pragma unroll
-            for (int k = 0; k < kPollRound; ++k) {
-                const int g = wave + kPollWaves * (kPollRound * round + k);
-                if (g < G) {
-                    int spins = 0;
-                    while (wait && __any(pv[k].y != tag || pv[k].w != tag)) {
-                        if (a.exp_flags & 2) __builtin_amdgcn_s_sleep(16); else __builtin_amdgcn_s_sleep(1);
-                        if (++spins > a.spin_limit) { __hip_atomic_store(a.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-                        pv[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, g * kBins * 8, 16 /* sc1 */);
-                    }
-                    s0 += __uint_as_float(pv[k].x);
-                    s1 += __uint_as_float(pv[k].z);
-                }
-            }
-        }
-        part[wave * kBins + lane] = s0;
-        part[wave * kBins + lane + 64] = s1;
-    };
 
     // ---- publish step `pi` (ring slot `pslot`) for alpha_rows2_kernel / the UC kernel: waves 1-6, stores only.  Runs in the shadow
     // of wave 0's scan of the NEXT step (behind its barrier 0), or after the loop for the last step.  pa0 / pa1: the publishing
@@ -789,10 +555,6 @@ void chain_batch3_kernel(ChainBatchArgs a) {
 #pragma unroll
         for (int j = 0; j < RPW; ++j) {
             const int row = wave + kBRows * j;
-            if constexpr (DMA) {
-                // (own rows from LDS as well: they hold the step's scores until barrier 2 of the next step; no registers live across the step)
-                if (row_ok[j]) { cr[row * kBins + lane] = scw[j * kBRows * kScPitch + lane]; cr[row * kBins + lane + 64] = scw[j * kBRows * kScPitch + lane + 64]; }
-            } else
             if (row_ok[j] && !(a.exp_flags & 4)) { cr[row * kBins + lane] = pa0[j]; cr[row * kBins + lane + 64] = pa1[j]; }
             const int extra = (wave == 1) ? kBRows * j : ((wave == 6) ? kBRows * j + kBRows - 1 : -1);
             if (extra >= 0 && extra < valid) {
@@ -809,11 +571,8 @@ void chain_batch3_kernel(ChainBatchArgs a) {
 
     int slot_run = (int)(a.step0 % a.ring);
     const int ring_n = (int)a.ring;
-    int cb_next = call_long ? a.call_sub : 0;                              // first step of the next sub-batch (call-long launch)
-    bool sig_pending = false;                                              // (wave 6) an L2 write-back of a finished sub-batch is in flight
     const bool ovr0 = ((a.override_mask >> l) & 1u) != 0;
-    // step 0 takes its totals from elsewhere than the exchange (mailboxes: also when the step before ran in a per-chunk launch)
-    const bool special0 = ovr0 || a.first_from_parts || (MBOX && a.first_from_acc);
+    const bool special0 = ovr0 || a.first_from_parts;                     // step 0 takes its totals from elsewhere than the exchange
     // atomics exchange: ring of three accumulator slots (read g-1 / add g / clear g+1), wave 0 polls one 16-byte word pair per lane
     int g3 = (int)(a.step0 % 3);
     const long layer_words = (long)kAccShards * kBins;
@@ -825,11 +584,7 @@ void chain_batch3_kernel(ChainBatchArgs a) {
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(layer_words_p), 0, kBins * 8, 0x00020000);
         pw = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, 0, 16 /* sc1 */);
     };
-    if constexpr (MBOX) {
-        if (poller && !special0) poll_issue((int)((a.step0 + 1) & 1), 0);   // the mailboxes of global step step0 - 1
-    } else {
-        if (wave == 0 && !special0) poll_pair(a.acc[g3 == 0 ? 2 : g3 - 1] + l * layer_words);
-    }
+    if (wave == 0 && !special0) poll_pair(a.acc[g3 == 0 ? 2 : g3 - 1] + l * layer_words);
     __syncthreads();
 
 #define B3STAMP(k) do { if (a.dbg != nullptr && b == 0 && tid == 0 && i == 5) { a.dbg[k] = wall_clock64(); a.dbg[8 + k] = clock64(); } } while (0)
@@ -838,43 +593,20 @@ void chain_batch3_kernel(ChainBatchArgs a) {
         B3STAMP(0);
         // (stamps 16 / 17: top of step 1 and of the last step -- the launch's average step without the per-phase stamps' own cost)
         if (a.dbg != nullptr && b == 0 && tid == 0 && (i == 1 || i == a.n_steps - 1)) a.dbg[i == 1 ? 16 : 17] = wall_clock64();
-        const long gstep = a.step0 + i;                                         // global index of this step in the call
         const long slot = slot_run;
         if (++slot_run == ring_n) slot_run = 0;
         const bool last = (i == a.n_steps - 1);
-        const float* Snew = lds + m.Snew + (DMA ? (i & (kDmaPar - 1)) * kDmaSnew : (i & 1) * sn_tile);
+        const float* Snew = lds + m.Snew + (i & 1) * sn_tile;
         unsigned long long* acc_prev = a.acc[g3 == 0 ? 2 : g3 - 1] + l * layer_words;
         unsigned long long* acc_cur = a.acc[g3] + l * layer_words;
         unsigned long long* acc_clr = a.acc[g3 == 2 ? 0 : g3 + 1] + l * layer_words;
         if (++g3 == 3) g3 = 0;
-        const bool from_box = MBOX && !(i == 0 && special0);
-        // ---- waves 0..5: the previous step's mailboxes (polled one step ahead) -> partial sums; fault injection: a slot nobody fills
-        if (from_box) {
-            if (poller) poll_collect((int)((gstep + 1) & 1), (unsigned int)gstep, i > 0 && !(a.exp_flags & 16));
-            if (a.expect_extra > 0 && i > 0 && wave == 0) {
-                for (int spins = 0; spins <= a.spin_limit; ++spins) __builtin_amdgcn_s_sleep(1);
-                __hip_atomic_store(a.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            __syncthreads();                                                     // barrier 0
-        }
-        // call-long launch: step i opens a new sub-batch -> the steps of the one before are all published once step i-1 is
-        const bool batch_open = call_long && i > 0 && i == cb_next;
-        if (batch_open) cb_next += a.call_sub;
         if (i > 0) {
             // in the shadow of wave 0's scan: the previous step goes out, the loader asks for the inputs of step i+2
             if (loader) {
-                if constexpr (DMA) { if (i + 2 < a.n_steps) dma_request(i + 2); }      // (buffer of step i - 2: its last readers ran before barrier 3 of that step)
-                else if (i + 2 < a.n_steps && !(a.exp_flags & 8)) { if ((i + 2) & 1) ld_request(i + 2, ldB); else ld_request(i + 2, ldA); }
+                if (i + 2 < a.n_steps && !(a.exp_flags & 8)) { if ((i + 2) & 1) ld_request(i + 2, ldB); else ld_request(i + 2, ldA); }
             } else if (wave != 0) {
                 publish_step(i - 1, prev_slot, acc0, acc1);
-                // hand a finished sub-batch to the UC stream.  Every publishing wave drains its stores (they are then in this XCD's
-                // L2); behind barrier 1 wave 6 starts the L2 write-back and, a step later, waits for it and counts this workgroup in.
-                if (wave == 6 && sig_pending) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the write-back issued one step ago has completed
-                    if (lane == 0) __hip_atomic_fetch_add(a.call->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    sig_pending = false;
-                }
-                if (batch_open) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
         }
         prev_slot = slot;
@@ -895,11 +627,7 @@ void chain_batch3_kernel(ChainBatchArgs a) {
                         if (j1 < nb) a1 += (double)a.part_prev[((long)l * a.parts + p) * kBins + j1];
                     }
                     raw0 = (float)a0; raw1 = (float)a1;
-                } else if (MBOX && i == 0 && a.first_from_acc) {
-                    // the previous step ran in a per-chunk launch: its fixed-point totals (complete: kernel boundary)
-                    raw0 = (float)mass_of(acc_prev[acc_word(lane)]);
-                    raw1 = (j1 < nb) ? (float)mass_of(acc_prev[acc_word(j1)]) : 0.f;
-                } else if (!MBOX) {
+                } else {
                     // the poll was issued one step ago; step 0 reads totals completed by an earlier launch (no count)
                     const unsigned long long need = (i > 0 && !(a.exp_flags & 16)) ? need_full : 0ull;
                     int spins = 0;
@@ -914,11 +642,6 @@ void chain_batch3_kernel(ChainBatchArgs a) {
                     }
                     raw0 = (float)mass_of(w0);
                     raw1 = (j1 < nb) ? (float)mass_of(w1) : 0.f;
-                } else {
-                    float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-                    for (int w = 0; w < kPollWaves; ++w) { t0 += part[w * kBins + lane]; t1 += part[w * kBins + j1]; }
-                    raw0 = t0; raw1 = t1;
                 }
                 if (j1 >= nb) raw1 = 0.f;
                 const float tot1 = (float)wave_sum_f64((double)raw0 + (double)raw1);
@@ -953,17 +676,14 @@ void chain_batch3_kernel(ChainBatchArgs a) {
         }
         __syncthreads();                                                         // barrier 1
         B3STAMP(2);
-        if (batch_open && wave == 6) { asm volatile("buffer_wbl2 sc1" ::: "memory"); sig_pending = true; }
-        if constexpr (!MBOX) {
-            // Clear the accumulator slot of step i+1 (it held the totals of step i-2).  Wave 0 has just seen every arrival of
-            // step i-1, and a workgroup arrives only after its own poll of step i-2's totals, so nobody reads the slot any more;
-            // nobody adds to it before having seen all arrivals of step i, this workgroup's included -- and that arrival (behind
-            // barrier 3) is held back until the clear has been acknowledged: the clearing waves drain vmcnt before barrier 3.
-            if (writer && tid >= 128 && tid < 128 + kBins) atomicExch(acc_clr + (tid - 128), 0ull);
-        }
+        // Clear the accumulator slot of step i+1 (it held the totals of step i-2).  Wave 0 has just seen every arrival of
+        // step i-1, and a workgroup arrives only after its own poll of step i-2's totals, so nobody reads the slot any more;
+        // nobody adds to it before having seen all arrivals of step i, this workgroup's included -- and that arrival (behind
+        // barrier 3) is held back until the clear has been acknowledged: the clearing waves drain vmcnt before barrier 3.
+        if (writer && tid >= 128 && tid < 128 + kBins) atomicExch(acc_clr + (tid - 128), 0ull);
         if (tid < a.S) {
             // ---- lower bound of this thread's uniform in the cdf == number of entries below it ----
-            const float my_uf = (lds + m.uf + (DMA ? (i & (kDmaPar - 1)) * kDmaUf : (i & 1) * a.S))[tid];
+            const float my_uf = (lds + m.uf + (i & 1) * a.S)[tid];
             const floatx4* c4 = reinterpret_cast<const floatx4*>(coarse);
             int grp = 0;
 #pragma unroll
@@ -1015,15 +735,8 @@ void chain_batch3_kernel(ChainBatchArgs a) {
 #pragma unroll
             for (int j = 0; j < RPW; ++j) {
                 const int row = wave + kBRows * j;
-                if constexpr (DMA) {
-                    const float* sr = Snew + (row >> 2) * rows * 4 + (row & 3);
-                    const float x0 = sr[sna0], x1 = sr[sna1];
-                    acc0[j] += has_r0 ? x0 : 0.f;
-                    acc1[j] += has_r1 ? x1 : 0.f;
-                } else {
                 acc0[j] += Snew[row * sn + br0];
                 acc1[j] += Snew[row * sn + br1];
-                }
                 // in place: every gather of this wave is issued before these stores (the lanes read each other's old values),
                 // and LDS runs a wave's operations in order
                 if (j == 0) wave_lds_handover();
@@ -1065,82 +778,38 @@ void chain_batch3_kernel(ChainBatchArgs a) {
                 *reinterpret_cast<float2*>(&Msm[row * kMPitch + 2 * lane]) = mm;
             }
         }
-        if (!MBOX && writer && (wave == 2 || wave == 3)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clear above is complete
+        if (writer && (wave == 2 || wave == 3)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clear above is complete
         __syncthreads();                                                         // barrier 3
         B3STAMP(4);
-        if constexpr (!MBOX) {
-            if (tid < kBins - 1) {
-                float mr[TR];
+        if (tid < kBins - 1) {
+            float mr[TR];
 #pragma unroll
-                for (int r = 0; r < TR; ++r) mr[r] = Msm[r * kMPitch + acc_word(tid)];
+            for (int r = 0; r < TR; ++r) mr[r] = Msm[r * kMPitch + acc_word(tid)];
 #pragma unroll
-                for (int w = TR / 2; w >= 1; w >>= 1)                   // pairwise: log2(TR) dependent adds instead of TR
+            for (int w = TR / 2; w >= 1; w >>= 1)                       // pairwise: log2(TR) dependent adds instead of TR
 #pragma unroll
-                    for (int r = 0; r < w; ++r) mr[r] += mr[r + w];
-                const float t = mr[0];
-                if (!(a.exp_flags & 16))
-                    atomicAdd(&acc_cur[acc_word(tid)], (unsigned long long)((double)t * kMassScale + 0.5) + (1ull << kArriveShift));
-            }
-            // re-arm the poll behind the deposit and go round: this wave issues nothing else until it has read it.  A poll that
-            // reaches the memory side before the slowest workgroup's adds returns an incomplete count and costs a second round
-            // trip, so the first poll is held back by poll_delay x 64 clocks (tuned in situ: chain_ab.sh)
-            if (wave == 0 && !last && !(a.exp_flags & 16)) {
-                for (int dly = 0; dly < a.poll_delay; ++dly) __builtin_amdgcn_s_sleep(1);
-                poll_pair(acc_cur);
-            }
-        } else if (wave == 0) {
-            // ---- this workgroup's row sums of the step -> its mailbox: one 16-byte store per lane = two {mass, tag} granules
-            float t0 = 0.f, t1 = 0.f;
-#pragma unroll
-            for (int r = 0; r < TR; ++r) {
-                const float2 mm = *reinterpret_cast<const float2*>(&Msm[r * kMPitch + 2 * lane]);
-                t0 += mm.x; t1 += mm.y;
-            }
-            if (!(a.exp_flags & 16)) {
-                const unsigned int tag = (unsigned int)(gstep + 1);
-                const uintx4_t v = {__float_as_uint(t0), tag, __float_as_uint(t1), tag};
-                unsigned long long* dst = a.mbox + mbox_slot_granules(a.L, G, (int)(gstep & 1), l, blk);
-                if (plain) {
-                    reinterpret_cast<uintx4_t*>(dst)[lane] = v;                 // stays in this XCD's L2, where the whole layer reads it
-                } else {
-                    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, kBins * 8, 0x00020000);
-                    __builtin_amdgcn_raw_buffer_store_b128(v, rs, lane * 16, 0, 16 /* sc1: write-through, valid at any placement */);
-                }
-            }
+                for (int r = 0; r < w; ++r) mr[r] += mr[r + w];
+            const float t = mr[0];
+            if (!(a.exp_flags & 16))
+                atomicAdd(&acc_cur[acc_word(tid)], (unsigned long long)((double)t * kMassScale + 0.5) + (1ull << kArriveShift));
         }
-        // re-arm the polls right behind the deposit.  Nothing else touches memory between here and barrier 0 of the next step:
-        // the publishing stores and the loader's requests wait for the window behind that barrier (wave 0's scan), so neither a
-        // poll nor a re-poll queues behind them in this CU's memory pipe
-        if (MBOX && poller && !last) poll_issue((int)(gstep & 1), 0);
-        if constexpr (DMA) {
-            // step i+1's tile and uniforms have landed (the barriers of step i+1 hand them to the other waves); step i+2 may still fly
-            if (loader && !last) {
-                if (i + 2 < a.n_steps) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        } else
+        // re-arm the poll behind the deposit and go round: this wave issues nothing else until it has read it.  A poll that
+        // reaches the memory side before the slowest workgroup's adds returns an incomplete count and costs a second round
+        // trip, so the first poll is held back by poll_delay x 64 clocks (tuned in situ: chain_ab.sh)
+        if (wave == 0 && !last && !(a.exp_flags & 16)) {
+            for (int dly = 0; dly < a.poll_delay; ++dly) __builtin_amdgcn_s_sleep(1);
+            poll_pair(acc_cur);
+        }
         if (loader && !last) { if ((i + 1) & 1) ld_park(i + 1, ldB); else ld_park(i + 1, ldA); }   // LDS only (requested two steps ago)
         if (wave == 0) B3STAMP(5);
         B3STAMP(6);
         B3STAMP(7);
-        // LDS reuse: `part` is rewritten by the polling waves at the top of step i+1, its reader (wave 0) is past barrier 1 of
-        // step i by then... and every polling wave passes barriers 1-3 of step i in between; cdf / coarse are rewritten by wave 0
-        // after barrier 0 of step i+1, i.e. after every search of this step; the S'new / uniform tiles of parity i+1 are rewritten
-        // by wave 7 behind barrier 3 (their readers ran before barrier 3 of step i-1); tabb and the bins parked in `pos` behind
-        // barrier 1 (their readers, the publishing waves, reach barrier 0 after their loads); Msm behind barrier 2; the score rows
-        // read by waves 1 and 6 behind barrier 2 of step i+1.
+        // LDS reuse: cdf / coarse are rewritten by wave 0 at the top of step i+1, i.e. after every search of this step; the S'new /
+        // uniform tiles of parity i+1 are rewritten by wave 7 behind barrier 3 (their readers ran before barrier 3 of step i-1);
+        // tabb and the bins parked in `pos` behind barrier 1 (their readers, the publishing waves, reach it after their loads);
+        // Msm behind barrier 2; the score rows read by waves 1 and 6 behind barrier 2 of step i+1.
     }
     if (a.n_steps > 0 && wave != 0 && !loader) publish_step(a.n_steps - 1, prev_slot, acc0, acc1);
-    if (call_long) {
-        // the last sub-batch (and a write-back still in flight): drain, write back, count this workgroup in
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (wave == 6 && sig_pending && lane == 0) __hip_atomic_fetch_add(a.call->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (wave == 6) {
-            asm volatile("buffer_wbl2 sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) __hip_atomic_fetch_add(a.call->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
     // ---- hand the point scores to the next launch (its set-up reads them back through pb) ----
 #pragma unroll
     for (int j = 0; j < RPW; ++j) {
@@ -1150,19 +819,9 @@ void chain_batch3_kernel(ChainBatchArgs a) {
             a.Sp_out[(tile + row) * N + n1] = scw[j * kBRows * kScPitch + lane + 64];
         }
     }
-    // (the last step's totals stay in the mailboxes: the next launch's step 0 reads them there; whoever continues without
-    // mailboxes -- the next call, a per-chunk launch -- gets them from launch_mailbox_to_part)
     if (a.dbg != nullptr && b == 0 && tid == 0) { a.dbg[21] = a.dbg[20]; a.dbg[20] = wall_clock64(); }   // (stamps: this / the previous launch's end)
     wg_stamp_end(a.wg_stamps);
 }
-
-// the DMA-loader form (atomics exchange, 16-row tiles): 128 registers, four of its waves per SIMD -- two workgroups, or one and
-// a pooling workgroup (168 registers x 3 waves per SIMD), fit a CU.  Bit-identical to the register loader and 2 % faster alone
-// (10.45 against 10.7 ms of chain per 2048-chunk video) -- and measured in situ (round 6, docs/NOTEBOOK.md): sharing its CUs with
-// pooling workgroups gives the pooling 48 more seats (12.5 -> 11.6 ms, 0.56 of the HBM peak), the GEMM and UC kernels 8-15 %,
-// and costs role S 3 us per step (chain 12.5 -> 14.9 ms, call 13.4 -> 16.3 ms; shorter pooling bursts do not help); padded to
-// 77 KB (two of these per CU, no pooling workgroup) the chain is 13.0-13.6 ms; padded to 84 KB (a CU each) it is the shipped
-// pipeline to the noise.  Role S stays a CU's only tenant: experiments build only (INFV_CHAIN_DMA=1).
 
 // ------------------------------------------------------------------------------------------------------
 // alpha_rows2_kernel: the chunk-parallel other half of chain_batch2_kernel.  For every step of a sub-batch and every
@@ -1538,46 +1197,24 @@ bool chain_batch_supported(int N, int S, int rows, int tabw, int n_blocks) {
 }
 
 // Variants of the persistent role S.  The shipped library launches ONE: 16-row tiles, atomics exchange, one launch per sub-batch.
-// The experiments build can select 8-row tiles (INFV_CHAIN_RPW=1), the mailbox exchange (INFV_CHAIN_XCD=1: inside one XCD's L2
-// with the XCD-aware grid, sc1 mailboxes with INFV_CHAIN_LINEAR=1) and ONE launch per call (INFV_CHAIN_CALL=1) for A/B runs.
+// The experiments build can select 8-row tiles (INFV_CHAIN_RPW=1) for A/B runs.
 // Round 5 built the call-long forms of role S, of the pooling and of the projection GEMM and measured them on one box against
 // this form (docs/NOTEBOOK.md, round 5): a resident role S is 12 % faster alone (9.4 against 10.65 ms of chain per video) and
 // 10.2 ms without the pooling stream -- but whatever is resident holds its CUs for the whole call, the pooling stream's speed is
 // the number of CUs that can host one of its workgroups, and every all-resident combination ended 3-5 % SLOWER end to end than
 // launches that give their CUs back (14.0-14.2 against 13.4-13.6 ms); a layer's 24 workgroups on ONE XCD (the mailbox exchange
 // in one L2) made it 33 ms: every other launch deals its workgroups round-robin over the XCDs and is paced by the fullest one.
+// Those forms, and the LDS-DMA loader of round 6 (role S 3 us per step slower beside a pooling workgroup), have been deleted; their
+// measurements are in profiles/ and docs/NOTEBOOK.md.
 constexpr int kDefRpw = 2;
 typedef void (*Chain3Fn)(ChainBatchArgs);
-bool chain_batch3_mailboxes() {
-    static const bool want = [] { const char* e = exp_env("INFV_CHAIN_XCD"); return e && atoi(e) != 0; }();
-    return want;
-}
-bool chain_call_long() {
-    static const bool want = [] { const char* e = exp_env("INFV_CHAIN_CALL"); return e && atoi(e) != 0; }();
-    return want;
-}
 static Chain3Fn chain3_fn(int rpw) {
 #ifdef INFV_EXPERIMENTS
-    if (chain_batch3_mailboxes()) return rpw == 1 ? chain_batch3_kernel<1, true, false> : chain_batch3_kernel<2, true, false>;
-    return rpw == 1 ? chain_batch3_kernel<1, false, false> : chain_batch3_kernel<2, false, false>;
+    return rpw == 1 ? chain_batch3_kernel<1> : chain_batch3_kernel<2>;
 #else
     (void)rpw;
-    return chain_batch3_kernel<2, false, false>;
+    return chain_batch3_kernel<2>;
 #endif
-}
-
-// Round 6 (experiments build, INFV_CHAIN_DMA=1): the DMA-loader form of the default role S (chain_batch3_kernel<2, false, true>, 128 registers).
-// It applies to every launch whose new-row scores are one slab (the sub-batches of 16 chunks and more), on the atomics exchange
-// with per-sub-batch launches.
-static bool chain_dma_wanted() {
-    static const bool want = [] { const char* e = exp_env("INFV_CHAIN_DMA"); return e && atoi(e) != 0; }();
-    return want;
-}
-static bool chain_dma_applies(const ChainBatchArgs& a, int rpw) {
-    return chain_dma_wanted() && rpw == 2 && !chain_batch3_mailboxes() && a.call == nullptr && a.snew_splitk == 1 && a.exp_flags == 0 &&
-           a.snew_ld % 4 == 0 && a.Q % 4 == 0 && (reinterpret_cast<unsigned long>(a.Snew) & 15) == 0 && (reinterpret_cast<unsigned long>(a.uf) & 15) == 0 &&
-           a.S % 4 == 0 && a.S <= 512 && 4 * a.op.rows <= 64 * kB2Ld &&
-           (long)a.n_steps * a.op.rows * a.snew_ld * 4 < (1l << 31) && (long)a.n_steps * a.L * a.S * 4 < (1l << 31);
 }
 
 static hipError_t chain_batch_attr() {
@@ -1587,9 +1224,6 @@ static hipError_t chain_batch_attr() {
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         for (int rpw = 1; rpw <= 2 && e == hipSuccess; ++rpw)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain3_fn(rpw)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#ifdef INFV_EXPERIMENTS
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(chain_batch3_kernel<2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#endif
         if (e != hipSuccess) return e;
         attr_set = true;
     }
@@ -1621,8 +1255,7 @@ static int chain_batch3_rpw(int rows, int Q) {
 }
 
 bool chain_batch2_applies(const ChainBatchArgs& a) {
-    return chain_batch3_shape_ok(a.draw_mode, a.st.points_ok, a.op.rows, a.S, a.Q) && a.crit_ring != nullptr && a.uf != nullptr &&
-           (a.mbox != nullptr || !chain_batch3_mailboxes());
+    return chain_batch3_shape_ok(a.draw_mode, a.st.points_ok, a.op.rows, a.S, a.Q) && a.crit_ring != nullptr && a.uf != nullptr;
 }
 
 // Workgroups of the persistent role-S launch for this shape (the kernel launch_chain_batch will choose).
@@ -1631,10 +1264,10 @@ int chain_batch_blocks(int H, int Q, int L, int draw_mode, int points_ok, int ro
     return H * ((Q + kBRows * rpw - 1) / (kBRows * rpw)) * L;
 }
 
-static size_t chain_batch3_launch_lds(int N, int S, int rows, int tabw, int rpw, bool dma = false) {
+static size_t chain_batch3_launch_lds(int N, int S, int rows, int tabw, int rpw) {
     // padding LDS keeps the workgroup's CU footprint what the stream layout of consolidate() was tuned for
     static const int pad = [] { const char* e = exp_env("INFV_S_LDS"); return e ? atoi(e) : 0; }();
-    size_t lds = (size_t)batch3_smem(N, S, rows, tabw, rpw, dma).total * sizeof(float);
+    size_t lds = (size_t)batch3_smem(N, S, rows, tabw, rpw).total * sizeof(float);
     if ((size_t)pad > lds) lds = pad;
     return lds;
 }
@@ -1673,30 +1306,6 @@ hipError_t launch_flag_wait(const unsigned int* counter, unsigned int target, in
     INFV_LAUNCH(flag_wait_kernel, dim3(1), dim3(64), 0, stream, counter, target, spin_limit, error);
     return hipGetLastError();
 }
-bool launch_flag_wait_available() { return true; }
-
-#ifdef INFV_EXPERIMENTS
-// ---- hand-offs of a call-long role-S launch.  GEMM stream -> role S: flag_set_kernel runs behind a sub-batch's projection GEMM (whose
-// end-of-kernel release has written its output back) and raises the count role S's loaders poll.  Role S -> UC stream:
-// flag_wait_kernel holds the UC stream until every role-S workgroup has counted the sub-batch in (ChainBatchArgs.done); the
-// kernels behind it start with the usual launch-time acquire.  One wave each; the wait is bounded and latches the error word.
-__global__ void chain_call_desc_kernel(ChainCallDesc* dst, ChainCallDesc v) { if (threadIdx.x == 0) *dst = v; }
-hipError_t launch_chain_call_desc(ChainCallDesc* dst, const ChainCallDesc& v, hipStream_t stream) {
-    INFV_LAUNCH(chain_call_desc_kernel, dim3(1), dim3(64), 0, stream, dst, v);
-    return hipGetLastError();
-}
-__global__ void flag_set_kernel(unsigned int* flag, unsigned int value) {
-    if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-hipError_t launch_flag_set(unsigned int* flag, unsigned int value, hipStream_t stream) {
-    INFV_LAUNCH(flag_set_kernel, dim3(1), dim3(64), 0, stream, flag, value);
-    return hipGetLastError();
-}
-
-#else
-hipError_t launch_chain_call_desc(ChainCallDesc*, const ChainCallDesc&, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_flag_set(unsigned int*, unsigned int, hipStream_t) { return hipErrorNotSupported; }
-#endif
 
 hipError_t launch_chain_batch(const ChainBatchArgs& a_in, hipStream_t stream) {
     if (hipError_t e = chain_batch_attr()) return e;
@@ -1707,19 +1316,9 @@ hipError_t launch_chain_batch(const ChainBatchArgs& a_in, hipStream_t stream) {
         if ((long)a.op.rows * a.snew_ld * 4 >= (1l << 31)) return hipErrorInvalidValue;   // (32-bit byte offsets inside one step's rows of S'new)
         const int rpw = chain_batch3_rpw(a.op.rows, a.Q);
         a.QS = (a.Q + kBRows * rpw - 1) / (kBRows * rpw);             // tiles of 8 * rpw query rows
-        const int G = a.H * a.QS;                                      // workgroups of a layer
-        // XCD-aware launch: a layer's workgroups get block ids that are equal mod 8 (one XCD under round-robin placement, where
-        // the exchange then stays in that XCD's L2); needs a layer to fit one XCD's CUs and a placement class per layer.  The
-        // kernel verifies the placement itself (handshake) and is correct without it.
-        static const bool linear = [] { const char* e = exp_env("INFV_CHAIN_LINEAR"); return e && atoi(e) != 0; }();   // experiments: linear grid (the layer spread over all XCDs)
-        a.xcd_grid = (chain_batch3_mailboxes() && !linear && G <= 32 && a.L <= 8) ? 1 : 0;
-        const int blocks = a.xcd_grid ? 8 * G : G * a.L;
-        const bool dma = chain_dma_applies(a, rpw);
-        const size_t lds = chain_batch3_launch_lds(a.N, a.S, a.op.rows, a.op.tabw, rpw, dma);
+        const int blocks = a.H * a.QS * a.L;
+        const size_t lds = chain_batch3_launch_lds(a.N, a.S, a.op.rows, a.op.tabw, rpw);
         a.wg_stamps = exp_stamps_reserve(WG_CHAIN, blocks);
-#ifdef INFV_EXPERIMENTS
-        if (dma) { INFV_LAUNCH((chain_batch3_kernel<2, false, true>), dim3(blocks), dim3(kBNT), lds, stream, a); return hipGetLastError(); }
-#endif
         INFV_LAUNCH(chain3_fn(rpw), dim3(blocks), dim3(kBNT), lds, stream, a);
         return hipGetLastError();
     }

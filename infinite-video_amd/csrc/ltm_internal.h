@@ -19,11 +19,8 @@ __host__ __device__ inline int acc_word(int j) { return j < 64 ? 2 * j : 2 * (j 
 // (integer) sum over the replicas, whoever clears a slot clears all of them.  Round 4 measured 2-8 replicas for the
 // persistent role S (adds to one word serialise at the memory side): 1.77-1.95 us per exchange against 1.90 with one --
 // every cross-XCD exchange costs that much, replicas buy nothing -- so the ring is back to one replica.  Who uses it: the
-// per-chunk kernels, and chain_batch3_kernel<., false> (one launch per sub-batch, atomics exchange).  The call-long launch
-// (chain_batch3_kernel<., true>, round 5) exchanges through mailboxes inside one XCD's L2 instead and only reads the
-// accumulators when the step before it ran in a per-chunk launch.
+// per-chunk kernels and chain_batch3_kernel (one launch per sub-batch, atomics exchange).
 constexpr int kAccShards = 1;
-constexpr int kCallSets = 8;               // most rotating projection workspace sets a call-long role-S launch can address (kPSets <= this)
 
 // Device-side view of one ridge operator (first-chunk or infinite-memory) of a plan.
 struct OperatorView {
@@ -165,20 +162,6 @@ bool chain_supported(int N, int S, int rows_max, int tabw);
 int chain_s_tiles(int Q);            // 8-row query tiles of role S (= sticky partial rows per head)
 hipError_t launch_chain(const ChainArgs& a, hipStream_t stream);
 // ---- role S of a whole sub-batch in one persistent launch (ltm_chain_batch.hip) ----
-// description of a call-long launch's sub-batches
-struct ChainCallDesc {
-    const unsigned int* tiles_s;    // [b] S' tiles of sub-batch b the call-long projection GEMM has completed, for b < n_tiled; or nullptr
-    int n_tiled, tiles_full, tiles_last;   // sub-batches covered by it; S' tiles of a full sub-batch / of sub-batch n_tiled - 1
-    const unsigned int* ready;      // (the other sub-batches) sub-batches whose projection GEMM is complete (flag_set_kernel on the GEMM's stream)
-    unsigned int* done;             // every workgroup adds 1 per sub-batch once the steps it published are written back (flag_wait_kernel on the UC stream polls it)
-    int sub;                        // steps per sub-batch (the last one may be shorter)
-    int n_batches;                  // sub-batches of the launch
-    const float* snew_set[kCallSets];   // S'new origin of workspace set s; sub-batch b reads set b % n_sets
-    int n_sets;
-    int sk_last; long ss_last;      // split-K form of the LAST sub-batch's projection (all others: snew_splitk / snew_split_stride)
-    long long* stats;               // [0]: 100 MHz ticks workgroup 0 spent waiting for `ready`; [1]: sub-batches it had to wait for; or nullptr
-};
-hipError_t launch_chain_call_desc(ChainCallDesc* dst, const ChainCallDesc& v, hipStream_t stream);
 struct ChainBatchArgs {
     int N, H, Q, QS, L, S;
     StickyView st;
@@ -187,10 +170,6 @@ struct ChainBatchArgs {
     int n_steps;
     long step0; int ring;           // step i has global index step0+i: histogram slot (step0+i)%3, output slot (step0+i)%ring
     int first_from_parts;           // step 0 reads the float partials of the per-call path instead of the ring
-    int first_from_acc;             // chain_batch3_kernel: step 0 reads the fixed-point totals of a per-chunk launch (acc[(step0+2)%3]) instead of the mailboxes
-    unsigned long long* mbox;       // chain_batch3_kernel: mailboxes of the exchange + placement handshake (chain_mailbox_bytes), zeroed at the start of a call
-    int xcd_grid;                   // chain_batch3_kernel: launched as 8 * (H*QS) blocks, layer l served by placement class (8 l) / L (set by launch_chain_batch)
-    int* xcc_report;                // experiments / tests: per workgroup (plain-store mode << 8) | XCC id, or nullptr
     const float* part_prev; int parts;
     unsigned long long* acc[3];     // fixed-point sticky histograms [L][kAccShards][128], ring of 3
     unsigned int* arrive;           // [L] arrival counters, zero at launch
@@ -215,24 +194,13 @@ struct ChainBatchArgs {
     const float* cq; const float* w; float w_out;
     long long* dbg;                 // timing experiments: phase stamps of workgroup 0 at step 5, or nullptr
     long long* wg_stamps;           // residency experiment (wg_stamps.h), or nullptr
-    // ---- call-long launch of chain_batch3_kernel: ONE launch per infv_ltm_consolidate, resident from the call's first sub-batch to its
-    // last (ready == nullptr: one launch per sub-batch, Snew / snew_splitk / snew_split_stride describe that sub-batch) ----
-    const ChainCallDesc* call;      // device memory (written by chain_call_desc_kernel ahead of the launch: the kernel's argument registers are full), or nullptr
-    int call_sub;                   // = call->sub (the one field every wave needs every step)
 };
-// role S -> UC stream / GEMM stream -> role S hand-offs of a call-long launch (ltm_chain_batch.hip)
-hipError_t launch_flag_set(unsigned int* flag, unsigned int value, hipStream_t stream);
+// holds `stream` until *counter >= target (the one pooling launch of a call -> the GEMM stream); bounded, latches `error`
 hipError_t launch_flag_wait(const unsigned int* counter, unsigned int target, int spin_limit, unsigned int* error, hipStream_t stream);
-bool launch_flag_wait_available();       // the flag kernels are compiled in (experiments build)
 bool chain_batch_supported(int N, int S, int rows, int tabw, int n_blocks);
 bool chain_batch2_applies(const ChainBatchArgs& a);        // the launch will run chain_batch3_kernel (scores rebuilt by alpha_rows2)
 bool chain_batch3_shape_ok(int draw_mode, int points_ok, int rows, int S, int Q);   // the shape runs chain_batch3_kernel (needs ChainBatchArgs.uf)
 hipError_t launch_round_up_uniforms(const double* u, float* uf, long n, hipStream_t stream);   // uf[i] = smallest float >= u[i]
-bool chain_batch3_mailboxes();                               // role S exchanges through mailboxes in one XCD's L2 (experiments build, INFV_CHAIN_XCD=0: memory-side atomics)
-bool chain_call_long();                                      // role S is ONE launch per consolidate call (experiments build, INFV_CHAIN_CALL=0: one per sub-batch)
-size_t chain_mailbox_bytes(int L, int G);                    // G = workgroups of a layer (chain_batch_blocks / L)
-// part[l][0][j] = total of bin j held by the mailboxes of parity `parity` (the last step of a chain_batch3 launch), same sum order as the kernel
-hipError_t launch_mailbox_to_part(const unsigned long long* mbox, int n_layers, int G, int parity, int parts_pitch, float* part, hipStream_t stream);
 int chain_batch_blocks(int H, int Q, int L, int draw_mode, int points_ok, int rows, int S);   // workgroups of the launch for this shape
 // the chunk-parallel half of chain_batch3_kernel: full score rows from the published point scores + drawn bins, then alpha
 struct AlphaRows2Args {

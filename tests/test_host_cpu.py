@@ -106,6 +106,10 @@ def test_shipped_library_reads_only_the_documented_environment_options():
     assert shipped == documented, sorted(shipped - documented)
     exp = knobs(os.path.join(os.path.dirname(_lib.LIB_PATH), "libinfv_ltm_exp.so"))
     assert documented < exp and {"INFV_SKIP", "INFV_CHAIN_FAULT", "INFV_POOL_ROWS"} <= exp
+    # the selectors of the variants that were measured, rejected and deleted are in neither build
+    deleted = {"INFV_CHAIN_CALL", "INFV_GEMM_CALL", "INFV_GEMM_WGS", "INFV_CHAIN_XCD", "INFV_CHAIN_LINEAR", "INFV_CHAIN_DMA",
+               "INFV_CU_MASK", "INFV_CHAIN_STREAM", "INFV_TAPER", "INFV_SCHED", "INFV_SUB_RAMP"}
+    assert not deleted & shipped and not deleted & exp, sorted(deleted & (shipped | exp))
 
 
 def test_experiments_build_keeps_the_register_footprint_of_the_shipped_kernels(tmp_path):
@@ -166,23 +170,22 @@ def _kernel_names(lib, tmp_path):
 
 def test_shipped_library_holds_only_the_kernels_it_can_launch(tmp_path):
     """A/B variants live in the experiments build only: the shipped code object has ONE persistent role-S kernel (16-row tiles,
-    atomics exchange), ONE instantiation per pooling form and token type it can select, no LDS-DMA / mailbox / 8-row-tile
-    variants, of round 5's call-long machinery only the one pooling launch per call and the flag_wait kernel that follows it (no
-    resident role S, no resident GEMM tile queue, no flag_set / descriptor kernels), none of the kernels deleted
-    in round 4 (grid-stride fused pooling, rolling double-buffered pooling, round 2-3's chain_batch2)."""
+    atomics exchange), ONE instantiation per pooling form and token type it can select, no 8-row-tile variant, of round 5's
+    call-long machinery only the one pooling launch per call and the flag_wait kernel that follows it.  Neither build has the
+    kernels of the forms measured and deleted: round 4's grid-stride fused pooling, rolling double-buffered pooling and round 2-3's
+    chain_batch2; round 5's resident role S, resident GEMM tile queue, mailbox exchange and their flag_set / descriptor kernels;
+    round 6's LDS-DMA loader of role S."""
     shipped, exp = _kernel_names("libinfv_ltm.so", tmp_path), _kernel_names("libinfv_ltm_exp.so", tmp_path)
     def having(names, frag):
         return sorted(n for n in names if frag in n)
-    assert len(having(shipped, "chain_batch3_kernel")) == 1 and "Lb0" in having(shipped, "chain_batch3_kernel")[0]
-    assert "Lb0ELb0E" in having(shipped, "chain_batch3_kernel")[0]      # atomics exchange, register loader
-    assert len(having(exp, "chain_batch3_kernel")) == 5              # + 8-row tiles, mailbox exchange, and round 6's LDS-DMA loader (128 registers: measured, not shipped)
-    for gone in ("chain_batch2_kernel", "pool_rows_kernel", "pool_frames_db_kernel"):
+    assert len(having(shipped, "chain_batch3_kernel")) == 1
+    assert "chain_batch3_kernelILi2EEEv" in having(shipped, "chain_batch3_kernel")[0]      # 16-row tiles: the kernel's one template parameter
+    assert len(having(exp, "chain_batch3_kernel")) == 2              # + 8-row tiles
+    for gone in ("chain_batch2_kernel", "pool_rows_kernel", "pool_frames_db_kernel", "mailbox_to_part_kernel", "gemm_x6_call_kernel",
+                 "flag_set_kernel", "chain_call_desc_kernel", "gemm_call_desc_kernel"):
         assert not having(shipped, gone) and not having(exp, gone), gone
     assert not having(shipped, "pool_rows2_dma_kernel") and not having(exp, "pool_rows2_dma_kernel")     # (racy LDS-DMA variant: deleted in round 5)
     assert having(shipped, "flag_wait_kernel")      # round 6: the GEMM stream holds on the call-long pooling launch's completion counts
-    for exp_only in ("mailbox_to_part_kernel", "gemm_x6_call_kernel", "flag_set_kernel",
-                     "chain_call_desc_kernel", "gemm_call_desc_kernel"):
-        assert not having(shipped, exp_only) and having(exp, exp_only), exp_only
     assert len(having(shipped, "pool_frames_kernel")) == 4          # {padded 512-thread, plain 256-thread} x {fp32, bf16 tokens}
     assert len(having(shipped, "pool_rows2_kernel")) == 8           # {8, 4 loads per burst} x {fp32, bf16 tokens} x {rows only, rows + bf16 planes}
     # the general-psi step (Gaussian family) and the dense step are product paths

@@ -251,9 +251,9 @@ def test_chain_timeout_is_reported_not_swallowed(dev):
     unaffected.  Runs in a child process: a process loads one build of the library."""
     r = _run_child(_FAULT_CHILD, {"INFV_LTM_LIBRARY": "exp"})
     assert "FAULT_CHILD_OK" in r.stdout, r.stdout + r.stderr
-    # the same with round 5's call-long launches (role S, pooling and projection GEMM resident for the whole call, handed off through
-    # device-side counters): every bounded wait -- exchange, readiness poll, flag_wait_kernel -- must give up, latch and report
-    r = _run_child(_FAULT_CHILD, {"INFV_LTM_LIBRARY": "exp", "INFV_CHAIN_CALL": "1", "INFV_POOL_CALL": "1", "INFV_GEMM_CALL": "1"})
+    # the same with the one pooling launch per call (what calls of 768+ chunks ship), whose GEMM stream waits on device-side
+    # completion counts: every bounded wait -- the exchange, flag_wait_kernel -- must give up, latch and report
+    r = _run_child(_FAULT_CHILD, {"INFV_LTM_LIBRARY": "exp", "INFV_POOL_CALL": "2"})
     assert "FAULT_CHILD_OK" in r.stdout, r.stdout + r.stderr
 
 
@@ -298,20 +298,14 @@ np.savez(sys.argv[1], a=a.cpu().numpy(), b=b.cpu().numpy(), B0=B[0], B1=B[1], bi
 '''
 
 # non-default variants kept in the sources (A/B material, experiments build only): each must reproduce the shipped default
-_CALL = {"INFV_CHAIN_CALL": "1"}                                # role S as ONE launch per call (round 5), atomics exchange
 _VARIANTS = [
     {},                                                        # the experiments build with no knob set
     {"INFV_POOL_ROWS": "0"},                                   # pool_frames_kernel + build_rows_kernel (the round-2 form)
     {"INFV_POOL_ROWS": "2", "INFV_PR_U": "4", "INFV_PR_WGS": "500"},   # default kernel, 4-load bursts, grid-stride (rows only: split3_rows_kernel makes the planes)
     {"INFV_POOL_PLANES": "0"},                                 # the pooling kernel writes rows only, split3_rows_kernel makes the GEMM's bf16 planes (round 4; what calls under 768 chunks ship since round 6)
     {"INFV_POOL_PLANES": "2"},                                 # the pooling kernel writes the planes too (what calls of 768+ chunks ship), here on a short call
-    _CALL,                                                     # call-long role S; pooling and GEMM launched per sub-batch
-    dict(_CALL, INFV_POOL_CALL="1"),                           # ... + ONE pooling launch per call (completion counts instead of launch boundaries)
-    dict(_CALL, INFV_POOL_CALL="1", INFV_GEMM_CALL="1"),       # ... + the projection GEMM as a resident tile-queue kernel (32 workgroups)
-    dict(_CALL, INFV_POOL_CALL="1", INFV_GEMM_CALL="1", INFV_GEMM_WGS="7"),   # ... with 7 workgroups: a sub-batch's tiles over several rounds
     {"INFV_CHAIN_RPW": "1"},                                   # 8-row chain tiles (96 workgroups) as in round 2
     {"INFV_PROJ_X6": "0", "INFV_VPROJ_ON_UC": "1"},            # (fp32-MFMA GEMM) V' half of the projection as its own GEMM on the UC stream
-    dict(_CALL, INFV_PROJ_X6="0", INFV_POOL_CALL="1"),         # (fp32-MFMA GEMM) call-long role S and pooling launch (rows only)
     {"INFV_PERSISTENT": "0"},                                  # one role-S launch per chunk
     {"INFV_PROJ_X6": "0", "INFV_GEMM_LW": "0"},                # (fp32-MFMA GEMM) without loader waves
     {"INFV_POOL_TID": "1"},                                    # pooling kernel with lane-id addressed loads (no vector address operand)
@@ -321,16 +315,14 @@ _VARIANTS = [
     {"INFV_POOL_CALL": "2"},                                   # ONE pooling launch for the call beside per-sub-batch role-S / GEMM launches: what calls of 768+ chunks ship since round 6, here forced on a short one
     {"INFV_POOL_CALL": "2", "INFV_DROP_WAITS": "0"},           # ... with the (redundant) wait of the caller's stream for the UC kernel of five sub-batches ago, as up to round 5
     {"INFV_SMALL_TILES": "5"},                                 # the projection of the first and the last sub-batch as 128 x 128 tiles (what the last sub-batch of a 768+-chunk call ships, round 6)
-    {"INFV_CHAIN_DMA": "1"},                                   # role S with the LDS-DMA loader (128 registers, round 6); the short last sub-batch keeps the register loader
 ]
 
 
 def test_kept_variants_reproduce_the_default_bit_for_bit(dev, tmp_path):
     """A 70-chunk call (two 32-chunk sub-batches + a short one: split-K slabs) and a 5-chunk continuation, once with the
     shipped library and once per variant with the experiments build: contexts, memory and draws identical bit for bit (variants of
-    the fp32-MFMA projection GEMM against the shipped library with INFV_PROJ_X6=0).  Includes round 5's call-long launches of
-    role S, of the pooling and of the projection GEMM: same arithmetic, other hand-offs (device-side flags instead of launch
-    boundaries)."""
+    the fp32-MFMA projection GEMM against the shipped library with INFV_PROJ_X6=0).  Includes the one pooling launch per call:
+    same arithmetic, another hand-off (device-side completion counts instead of launch boundaries)."""
     def run(env_add, name):
         path = str(tmp_path / name)
         _run_child(_VARIANT_CHILD, env_add, path)
@@ -346,31 +338,6 @@ def test_kept_variants_reproduce_the_default_bit_for_bit(dev, tmp_path):
                 np.testing.assert_allclose(want[key], got[key], rtol=0, atol=2e-7, err_msg=f"{v}: {key}")
             else:
                 np.testing.assert_array_equal(want[key], got[key], err_msg=f"{v}: {key}")
-
-
-def test_mailbox_exchange_variants(dev, tmp_path):
-    """INFV_CHAIN_XCD=1 (experiments build): role S exchanges its bin masses through mailboxes (inside one XCD's L2 with the
-    XCD-aware grid + placement handshake, csrc/ltm_chain_batch.hip).  The totals are fp32 sums of per-workgroup row sums in a fixed
-    order instead of the exact fixed-point totals of the atomics exchange: same draws (but for a flip within rounding of a cdf
-    edge), contexts and memory equal to fp32 rounding; the result must not depend on the placement (sc1 mailboxes when the
-    handshake finds the layer on several XCDs: forced with INFV_S_FLAGS=32, or a linear grid: INFV_CHAIN_LINEAR=1) nor on whether
-    role S is launched per sub-batch or once per call -- bit for bit."""
-    def run(env_add, name):
-        path = str(tmp_path / name)
-        _run_child(_VARIANT_CHILD, env_add, path)
-        return {k_: v for k_, v in np.load(path).items()}
-    base = run({}, "base.npz")
-    xcd = run({"INFV_LTM_LIBRARY": "exp", "INFV_CHAIN_XCD": "1"}, "xcd.npz")
-    for name, env in (("far", {"INFV_S_FLAGS": "32"}), ("linear", {"INFV_CHAIN_LINEAR": "1"}), ("call", {"INFV_CHAIN_CALL": "1"}),
-                      ("call_linear", {"INFV_CHAIN_CALL": "1", "INFV_CHAIN_LINEAR": "1", "INFV_POOL_CALL": "1", "INFV_GEMM_CALL": "1"})):
-        other = run(dict(env, INFV_LTM_LIBRARY="exp", INFV_CHAIN_XCD="1"), name + ".npz")
-        for key in base:
-            np.testing.assert_array_equal(xcd[key], other[key], err_msg=f"{name} changed {key}")
-    assert int((base["bins"] != xcd["bins"]).sum()) <= 1
-    for key in ("a", "b"):
-        assert float(np.abs(base[key] - xcd[key]).max()) <= 1e-5, key
-    for key in ("B0", "B1"):
-        assert float(np.abs(base[key] - xcd[key]).max()) <= 2e-6, key
 
 
 @pytest.mark.parametrize("n_chunks,max_batch,split", [(33, 42, 0), (45, 7, 0), (70, 28, 37), (129, 42, 1), (97, 13, 50),

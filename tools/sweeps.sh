@@ -421,32 +421,11 @@ tools/env_sweep.sh "INFV_NONE=0" "INFV_PR_PAD=57344" "INFV_PR_PAD=57344 INFV_POO
 done 2>&1 | tee gpurun_out/sweep_r04o.txt
 INFV_PR_PAD=57344 INFV_POOL_PRIO=1 INFV_UC_PRIO=2 INFV_ALPHA_PRIO=2 INFV_WG_STAMPS=1 python tools/residency.py pad56prio 2>&1 | grep -v amdgpu.ids | tail -18 | tee -a gpurun_out/sweep_r04o.txt
 ;;
-r04p)
-# CU masks: the first K CUs reserved for role S (its own masked stream), the worker streams masked to the rest
-{
-INFV_CU_MASK=56 INFV_WG_STAMPS=1 timeout 300 python tools/residency.py mask56 2>&1 | grep -v amdgpu.ids | tail -18
-python - <<'PY'
-import numpy as np
-st=np.load("gpurun_out/wg_stamps_mask56.npy"); st=st[(st[:,1]>0)&(st[:,0]>0)]
-hw=st[:,2]&0xffffffff; xcc=st[:,2]>>32; cu=(xcc<<8)|(((hw>>13)&7)<<5)|((hw>>8)&15); k=st[:,3]
-rs=set(cu[k==4]); others=set(cu[(k!=4)])
-print("CUs used by role S:", len(rs), " by the other kernels:", len(others), " shared:", len(rs&others))
-PY
-tools/env_sweep.sh "INFV_NONE=0" "INFV_CU_MASK=48" "INFV_CU_MASK=56" "INFV_CU_MASK=56 INFV_PR_PAD=57344" "INFV_CU_MASK=56 INFV_PR_PAD=40960" "INFV_CU_MASK=64 INFV_PR_PAD=57344" "INFV_NONE=1"
-} 2>&1 | tee gpurun_out/sweep_r04p.txt
-;;
 r04q)
-# five rotating workspace sets (projection GEMM up to five sub-batches ahead of the UC kernel) with and without CU masks
+# five rotating workspace sets (projection GEMM up to five sub-batches ahead of the UC kernel)
 {
 python -m pytest tests/test_timed_path_gpu.py -x -q -k "odd_call or oracle or equals" 2>&1 | tail -2
-tools/env_sweep.sh "INFV_NONE=0" "INFV_CU_MASK=64" "INFV_CU_MASK=64 INFV_PR_PAD=57344" "INFV_CU_MASK=64 INFV_PR_PAD=40960" "INFV_CU_MASK=60 INFV_PR_PAD=57344" "INFV_CU_MASK=72 INFV_PR_PAD=57344" "INFV_PR_PAD=57344" "INFV_NONE=1"
 } 2>&1 | tee gpurun_out/sweep_r04q.txt
-;;
-r04r)
-{
-INFV_CU_MASK=64 INFV_PR_PAD=57344 INFV_WG_STAMPS=1 python tools/residency.py mask64 2>&1 | grep -v amdgpu.ids | tail -18
-python tools/launch_table.py gpurun_out/wg_stamps_mask64.npy 20 8
-} 2>&1 | tee gpurun_out/sweep_r04r.txt
 ;;
 r04s)
 # three against five rotating workspace sets (compile-time INFV_PSETS), same box, alternating
@@ -635,6 +614,6 @@ print(round(d['value']), 'chunks/s wall', round(d['ms_per_step'],2), 'pool', k['
 }
 for rep in 1 2 3; do run 42; run 64; run 84; done 2>&1 | tee gpurun_out/sweep_r05i.txt
 ;;
-list) echo r03a r03b r03c r03d r03e r03f r03g r03h r03i r03k r03l r03m r03n r03o r03p r03q r03r r03s r03t r03u r03v r03w r03x r03y r03z r04a r04b r04c r04d r04e r04f r04g r04h r04i r04j r04k r04l r04n r04o r04p r04q r04r r04s r04t r04u r04v r04x r04y r04z r05a r05b r05c r05d r05e r05f r05g r05h r05i ;;
+list) echo r03a r03b r03c r03d r03e r03f r03g r03h r03i r03k r03l r03m r03n r03o r03p r03q r03r r03s r03t r03u r03v r03w r03x r03y r03z r04a r04b r04c r04d r04e r04f r04g r04h r04i r04j r04k r04l r04n r04o r04q r04s r04t r04u r04v r04x r04y r04z r05a r05b r05c r05d r05e r05f r05g r05h r05i ;;
 *) echo "usage: tools/sweeps.sh <name>   (tools/sweeps.sh list)"; exit 2 ;;
 esac
