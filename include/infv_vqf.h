@@ -3,7 +3,8 @@
  * The reference has no FFI for this path either: the boundary is Python (`video_Qformer.bert(...)` called by
  * `encode_video`, infty-Video-LLaMA/InfVideoLLaMA/models/infinityqa.py:280-344).  These entry points are what the
  * Python mirror (infinite_video_amd/video_qformer.py) binds with ctypes.  Plain pointers and sizes only; all
- * pointers are DEVICE pointers (fp32, row-major) unless stated; every call is asynchronous on `stream`.
+ * pointers are DEVICE pointers (fp32, row-major) unless stated; every call is asynchronous on `stream`.  Only the frame tokens
+ * (`frames`) may be bf16 instead (infv_vqf_set_token_dtype).
  * Errors: int status as in infv_ltm.h, message via infv_ltm_last_error().
  *
  * Scope: the query-token-only, eval-mode, all-ones-mask case the video Q-former is run in
@@ -63,6 +64,15 @@ int infv_vqf_destroy(infv_vqf_handle h);
  *   1            exact fp32 MFMA (bitwise an fp32 fma chain). */
 int infv_vqf_set_precision(infv_vqf_handle h, int32_t exact_fp32);
 
+/* Element type of every `frames` argument below: an infv_token_dtype (infv_ltm.h), default INFV_TOKENS_F32; anything else is
+ * refused with INFV_ERR_INVALID and the handle keeps its setting.  A bf16 `frames` pointer must be 16-byte aligned (refused
+ * otherwise, before any device work).  With bf16 tokens the split-bf16 contractions read the caller's buffer in place (a bf16
+ * token is its own hi plane and its lo plane is exactly zero): one pass writes the transposed copy and the frame means, and
+ * both contractions run two bf16 MFMA products instead of three.  Results are bit for bit those of the same values passed as
+ * fp32.  Where the split path does not apply (exact fp32, token counts that are no multiple of 64) the tokens are copied to
+ * fp32 in a workspace of the handle first.  Every shape accepted with fp32 tokens is accepted with bf16 tokens. */
+int infv_vqf_set_token_dtype(infv_vqf_handle h, int32_t dtype);
+
 /* Layer 0's hidden states entering the cross-attention come from the learned query tokens and the weights only, so
  * infv_vqf_encode_chunk can reuse them (embedding LayerNorm, self-attention block, cross query, pre-multiplied query)
  * from one chunk to the next.  The host vouches for the weights with an epoch: while the same non-zero epoch is set,
@@ -73,7 +83,7 @@ int infv_vqf_set_weights_epoch(infv_vqf_handle h, uint64_t epoch);
  *   merged = alpha * softmax((xq W-free restatement, see vqf_kernels.hip)) ... = Qformer.py:232-304 for a cross layer.
  * frames [n_tokens][enc_width], xq [n_query][hidden] (= self.query(hidden_states), bias applied),
  * a_long [n_query][hidden] or NULL (then merged = short-term context, the alpha == 1.0 / image-Q-former case). */
-int infv_vqf_short_attention(infv_vqf_handle h, const float* frames, int32_t n_tokens, const float* xq,
+int infv_vqf_short_attention(infv_vqf_handle h, const void* frames, int32_t n_tokens, const float* xq,
                              const infv_linear* key, const infv_linear* value, const float* a_long,
                              float* merged, void* stream);
 
@@ -86,7 +96,7 @@ int infv_vqf_short_attention(infv_vqf_handle h, const float* frames, int32_t n_t
  *   llama_out   [n_query][proj_out]  llama_proj(last_hidden)  (may be NULL)
  * The chunk's frame tokens are read ONCE: one pass yields the split-bf16 operands of every layer's short-term attention
  * (Qformer.py:278-291) and the frame means every layer's memory pools (long_term_attention_gibbs.py:304). */
-int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const float* frames, int32_t T,
+int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const void* frames, int32_t T,
                           const infv_vqf_weights* w, const double* u, int32_t new_video,
                           float* hidden_out, float* llama_out, void* stream);
 
@@ -97,14 +107,14 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
  *   - later layers have per-chunk queries: their LTM is the sequential per-call chain, issued on an internal side
  *     stream while the caller's stream runs the layer's short-term attention for all chunks;
  *   - every query-token block (linear / LayerNorm / GELU / self-attention) is batched over chunks;
- *   - the frame tokens of the whole video are read once: their split-bf16 copies (2 x the tokens' bytes) are kept for the
- *     call when they fit INFV_VQF_SPLIT_CACHE_GB (default 64), and layer 0's memory runs from the frame means of that pass
+ *   - the frame tokens of the whole video are read once: their split-bf16 copies (2 x the tokens' bytes; bf16 tokens: the
+ *     transposed copy only, 1 x) are kept for the call when they fit INFV_VQF_SPLIT_CACHE_GB (default 64), and layer 0's memory runs from the frame means of that pass
  *     (infv_ltm_consolidate_pooled).
  * Results equal n_chunks calls of infv_vqf_encode_chunk (new_video on the first only).
  *   frames [n_chunks][T * tokens_per_frame][enc_width], u [n_chunks][n_layers][nb_samples] or NULL,
  *   hidden_out [n_chunks][n_query][hidden] / llama_out [n_chunks][n_query][proj_out] / llama_mean [n_query][proj_out]
  *   (the eval loop's mean over chunks, run_inference_inf_video_llama_nextqa.py:194); each may be NULL. */
-int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const float* frames, int32_t n_chunks,
+int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const void* frames, int32_t n_chunks,
                           int32_t T, const infv_vqf_weights* w, const double* u, int32_t new_video,
                           float* hidden_out, float* llama_out, float* llama_mean, void* stream);
 
@@ -127,7 +137,7 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
  * values agree with infv_vqf_encode_video to fp32 rounding, not bit for bit; a Gibbs uniform within rounding of a cdf edge can
  * flip a draw.  Refusals (INFV_ERR_INVALID: bad cu, null or repeated handle) happen before any device work. */
 int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu,
-                           const float* frames, int32_t T, const infv_vqf_weights* w, const double* u,
+                           const void* frames, int32_t T, const infv_vqf_weights* w, const double* u,
                            int32_t new_video, float* hidden_out, float* llama_out, float* llama_mean, void* stream);
 
 /* out[i] = mean over n of in[n][i]  (the eval loop's mean over chunk embeddings,

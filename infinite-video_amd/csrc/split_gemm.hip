@@ -30,8 +30,13 @@ __device__ inline unsigned pack2(__bf16 a, __bf16 b) {
 // ------------------------------------------------------------------------------------------------------
 // C[z][m][o] = sum_k (A_hi + A_lo)[b][m][k] * (B_hi + B_lo)[b][o][k]   (three bf16 MFMA products, fp32 accumulate)
 // 128 x 128 x 64 tiles, 4 waves as 2 x 2, register prefetch of the next k-tile.
+// NPROD = 2: the B operand is bf16 as it stands (B_lo == nullptr, e.g. bf16 frame tokens read in place): no B_lo tile (three
+// array tiles in LDS) and no A_hi . B_lo product; the other two per accumulator and k-step in the same order, so the result has
+// the bits of the three-product form on a B whose lo plane is all zeros.
 // ------------------------------------------------------------------------------------------------------
+template <int NPROD>
 __global__ __launch_bounds__(256) void split_gemm_kernel(SplitGemm g) {
+    constexpr int NARR = NPROD == 3 ? 4 : 3;      // A_hi, A_lo, B_hi (, B_lo) tiles
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -63,11 +68,11 @@ __global__ __launch_bounds__(256) void split_gemm_kernel(SplitGemm g) {
     const long a_off = (long)b * g.strideA + (long)(m0 + row) * g.lda + kbeg + half * (kSBK / 2);
     const long b_off = (long)b * g.strideB + (long)(n0 + row) * g.ldb + kbeg + half * (kSBK / 2);
     const uint4* src[4] = {reinterpret_cast<const uint4*>(g.A_hi + a_off), reinterpret_cast<const uint4*>(g.A_lo + a_off),
-                           reinterpret_cast<const uint4*>(g.B_hi + b_off), reinterpret_cast<const uint4*>(g.B_lo + b_off)};
-    uint4 reg[4][kSVec];
+                           reinterpret_cast<const uint4*>(g.B_hi + b_off), reinterpret_cast<const uint4*>((NPROD == 3 ? g.B_lo : g.B_hi) + b_off)};
+    uint4 reg[NARR][kSVec];
     auto load_tile = [&](int t) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
+        for (int a = 0; a < NARR; ++a) {
             const bool ok = a < 2 ? a_ok : b_ok;
 #pragma unroll
             for (int v = 0; v < kSVec; ++v)
@@ -76,7 +81,7 @@ __global__ __launch_bounds__(256) void split_gemm_kernel(SplitGemm g) {
     };
     auto store_tile = [&]() {
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
+        for (int a = 0; a < NARR; ++a)
 #pragma unroll
             for (int v = 0; v < kSVec; ++v)
                 *reinterpret_cast<uint4*>(smem + a * kSArr + row * kSPitch + half * kSBK + v * 16) = reg[a][v];
@@ -109,14 +114,14 @@ __global__ __launch_bounds__(256) void split_gemm_kernel(SplitGemm g) {
             for (int j = 0; j < 2; ++j) {
                 const int off = (wn * 64 + j * 32 + li) * kSPitch + ks * 32 + kh * 16;
                 bh[j] = *reinterpret_cast<const bf16x8*>(smem + 2 * kSArr + off);
-                bl[j] = *reinterpret_cast<const bf16x8*>(smem + 3 * kSArr + off);
+                if (NPROD == 3) bl[j] = *reinterpret_cast<const bf16x8*>(smem + 3 * kSArr + off);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                    if (NPROD == 3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
                 }
         }
@@ -152,6 +157,9 @@ __global__ __launch_bounds__(256) void split_gemm_kernel(SplitGemm g) {
 //     cycles per tile; interleaved: + 400); here the SIMD's other wave also has MFMAs to issue meanwhile.
 // Round 2's form (384 x 128 x 64 tiles staged through registers, two barriers per tile) sat at 38 % MFMA-busy; the 384 x 128 x 32
 // LDS-DMA form of this round (four waves) at 49 % (profiles/r04_*qformer*).
+// NPROD = 2 (B_lo == nullptr: B is bf16 as it stands): the B stage holds one plane, 16 KB instead of 32 KB, so a stage is 64 KB and
+// the two stages 128 KB; a wave's k-tile is 6 + 2 = 8 pieces, one behind each of the loop's 8 issue slots; the A_hi . B_lo product is
+// gone, the other two per accumulator and k-step keep their order (the bits of the three-product form on a B with an all-zero lo plane).
 // ------------------------------------------------------------------------------------------------------
 namespace {
 constexpr int kWI = 3, kWJ = 4;                   // 32 x 32 accumulators per wave: kWI along M, kWJ along N
@@ -163,11 +171,14 @@ constexpr int kDArrA = kWRowsA * kDRow, kDArrB = kWRowsB * kDRow;
 constexpr int kDStageA = 2 * kDArrA, kDStageB = 2 * kDArrB;     // hi + lo planes of one k-tile: 48 KB of A, 32 KB of B
 constexpr int kDLds = 2 * (kDStageA + kDStageB);  // two stages: 163 840 B, all of a CU's LDS
 constexpr int kPiecesA = 6, kPiecesB = 4;         // 1-KiB load pieces per wave and k-tile
+constexpr int kDLds2 = 2 * (kDStageA + kDArrB);   // two-product form: 131 072 B
+constexpr int kPiecesB2 = 2;
 }  // namespace
 
 // (PROBE: experiments build only, INFV_WIDE_MODE -- 1 = no operand loads, 2 = loads only: timing probes with wrong results)
-template <int PROBE>
+template <int PROBE, int NPROD>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void split_gemm_wide_kernel(SplitGemm g) {
+    constexpr int kStageB = NPROD == 3 ? kDStageB : kDArrB, kPieces = kPiecesA + (NPROD == 3 ? kPiecesB : kPiecesB2);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -202,7 +213,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         return r;
     };
     const v4i rah = make_rsrc(g.A_hi + a0, a_bytes), ral = make_rsrc(g.A_lo + a0, a_bytes);
-    const v4i rbh = make_rsrc(g.B_hi + b0, b_bytes), rbl = make_rsrc(g.B_lo + b0, b_bytes);
+    const v4i rbh = make_rsrc(g.B_hi + b0, b_bytes), rbl = make_rsrc((NPROD == 3 ? g.B_lo : g.B_hi) + b0, b_bytes);
     auto dma16 = [](const v4i& rsrc, unsigned lds_addr, int voff, int soff) {
         // (readfirstlane: the "s" constraint alone does not move a value the compiler holds in a vector register)
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
@@ -213,15 +224,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int lrow = lane >> 2, lseg = (lane & 3) ^ ((lane >> 4) & 3);
     const int va = (lrow * (int)g.lda + lseg * 8) * 2, vb = (lrow * (int)g.ldb + lseg * 8) * 2;
     const int blk_a = 16 * (int)g.lda * 2, blk_b = 16 * (int)g.ldb * 2;        // bytes between 16-row blocks
-    // piece p of k-tile t: 48 of the 384 rows of A (3 blocks x 2 planes), then 32 of the 256 rows of B (2 blocks x 2 planes)
+    // piece p of k-tile t: 48 of the 384 rows of A (3 blocks x 2 planes), then 32 of the 256 rows of B (2 blocks x 2 planes; NPROD = 2:
+    // 2 blocks of the one plane)
     auto piece = [&](int t, int p) {                             // p is a constant after unrolling
         const int kt = t * kDRow;
         if (p < kPiecesA) {
             const int blk = wave * 3 + (p >> 1);
             dma16((p & 1) ? ral : rah, lds0 + (t & 1) * kDStageA + (p & 1) * kDArrA + blk * 1024, va, blk * blk_a + kt);
-        } else {
+        } else if (NPROD == 3) {
             const int blk = wave * 2 + ((p - kPiecesA) >> 1);
             dma16((p & 1) ? rbl : rbh, lds0 + 2 * kDStageA + (t & 1) * kDStageB + (p & 1) * kDArrB + blk * 1024, vb, blk * blk_b + kt);
+        } else {
+            const int blk = wave * 2 + (p - kPiecesA);
+            dma16(rbh, lds0 + 2 * kDStageA + (t & 1) * kStageB + blk * 1024, vb, blk * blk_b + kt);
         }
     };
 
@@ -239,7 +254,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int fa = wm * (32 * kWI) * kDRow, fb = wn * (32 * kWJ) * kDRow;
     if (PROBE != 1 && ntiles > 0) {
 #pragma unroll
-        for (int p = 0; p < kPiecesA + kPiecesB; ++p) piece(0, p);
+        for (int p = 0; p < kPieces; ++p) piece(0, p);
     }
 #ifdef INFV_EXPERIMENTS
     wg_stamp_begin(g.wg_stamps);
@@ -249,12 +264,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's part of tile t has landed ...
         __syncthreads();                                         // ... everybody's has, and nobody still reads the other stage
         const unsigned char* base = smem + (t & 1) * kDStageA + fa;
-        const unsigned char* base_b = smem + 2 * kDStageA + (t & 1) * kDStageB + fb;
+        const unsigned char* base_b = smem + 2 * kDStageA + (t & 1) * kStageB + fb;
         const bool ld = PROBE != 1 && t + 1 < ntiles;
         if (PROBE == 2) {
             if (ld) {
 #pragma unroll
-                for (int p = 0; p < kPiecesA + kPiecesB; ++p) piece(t + 1, p);
+                for (int p = 0; p < kPieces; ++p) piece(t + 1, p);
             }
             continue;
         }
@@ -268,21 +283,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 ah[i] = *reinterpret_cast<const bf16x8*>(base + i * 32 * kDRow + fo);
             }
             bh[0] = *reinterpret_cast<const bf16x8*>(base_b + fo);
-            bl[0] = *reinterpret_cast<const bf16x8*>(base_b + kDArrB + fo);
+            if (NPROD == 3) bl[0] = *reinterpret_cast<const bf16x8*>(base_b + kDArrB + fo);
 #pragma unroll
             for (int j = 0; j < kWJ; ++j) {
                 if (j + 1 < kWJ) {                               // the next 32-column block's fragments, one block ahead
                     bh[(j + 1) & 1] = *reinterpret_cast<const bf16x8*>(base_b + (j + 1) * 32 * kDRow + fo);
-                    bl[(j + 1) & 1] = *reinterpret_cast<const bf16x8*>(base_b + kDArrB + (j + 1) * 32 * kDRow + fo);
+                    if (NPROD == 3) bl[(j + 1) & 1] = *reinterpret_cast<const bf16x8*>(base_b + kDArrB + (j + 1) * 32 * kDRow + fo);
                 }
                 // the three products on three accumulators each; behind them one load piece of the next k-tile (8 slots, 10 pieces:
-                // the first two slots take two)
+                // the first two slots take two; NPROD = 2: two products, 8 pieces, one per slot)
                 const int slot = ks * kWJ + j;
 #pragma unroll
                 for (int i = 0; i < kWI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j & 1], acc[i][j], 0, 0, 0);
-                if (ld && slot < 2) piece(t + 1, 8 + slot);
+                if (NPROD == 3) {
+                    if (ld && slot < 2) piece(t + 1, 8 + slot);
 #pragma unroll
-                for (int i = 0; i < kWI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j & 1], acc[i][j], 0, 0, 0);
+                    for (int i = 0; i < kWI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j & 1], acc[i][j], 0, 0, 0);
+                }
 #pragma unroll
                 for (int i = 0; i < kWI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j & 1], acc[i][j], 0, 0, 0);
                 if (ld) piece(t + 1, slot);
@@ -380,25 +397,39 @@ hipError_t launch_split_gemm(const SplitGemm& g, hipStream_t stream, int lds_pad
         };
 #ifdef INFV_EXPERIMENTS
         static const int probe = [] { const char* e = exp_env("INFV_WIDE_MODE"); return e ? atoi(e) : 0; }();
-        if (probe == 1) return go(split_gemm_wide_kernel<1>);
-        if (probe == 2) return go(split_gemm_wide_kernel<2>);
+        if (probe == 1 && g.B_lo) return go(split_gemm_wide_kernel<1, 3>);
+        if (probe == 2 && g.B_lo) return go(split_gemm_wide_kernel<2, 3>);
 #endif
-        return go(split_gemm_wide_kernel<0>);
+        if (!g.B_lo) {                                     // B is bf16 as it stands: the two-product form, 128 KB of LDS
+            static bool attr_2 = false;
+            if (!attr_2) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(split_gemm_wide_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (e != hipSuccess) return e;
+                attr_2 = true;
+            }
+            INFV_LAUNCH((split_gemm_wide_kernel<0, 2>), grid, dim3(512), kDLds2, stream, gg);
+            return hipGetLastError();
+        }
+        return go(split_gemm_wide_kernel<0, 3>);
     }
     {                                                   // tiles live in dynamic LDS; `lds_pad` more (unused) bytes cap the kernel at one workgroup per CU
         static bool attr_set = false;
         if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(split_gemm_kernel),
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(split_gemm_kernel<3>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(split_gemm_kernel<2>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
             attr_set = true;
         }
     }
-    if (lds_pad > 160 * 1024 - kSLds) lds_pad = 160 * 1024 - kSLds;
+    const int lds = g.B_lo ? kSLds : 3 * kSArr;
+    if (lds_pad > 160 * 1024 - lds) lds_pad = 160 * 1024 - lds;
     if (g.K % kSBK || g.k_per_split % kSBK || g.k_per_split <= 0 || g.lda % 8 || g.ldb % 8 || g.strideA % 8 || g.strideB % 8)
         return hipErrorInvalidValue;
     dim3 grid((g.M + 127) / 128, (g.N + 127) / 128, g.nbatch * g.splitk);
-    INFV_LAUNCH(split_gemm_kernel, grid, dim3(256), kSLds + (lds_pad > 0 ? lds_pad : 0), stream, g);
+    if (g.B_lo) INFV_LAUNCH(split_gemm_kernel<3>, grid, dim3(256), lds + (lds_pad > 0 ? lds_pad : 0), stream, g);
+    else INFV_LAUNCH(split_gemm_kernel<2>, grid, dim3(256), lds + (lds_pad > 0 ? lds_pad : 0), stream, g);
     return hipGetLastError();
 }
 
@@ -755,14 +786,16 @@ hipError_t launch_split3_rows(const float* x, long ld_in, long rows, int cols, v
 }  // namespace infv
 // test hook (experiments build only, tests/test_ltm_gpu.py): C [M][N] = A [M][K] . B [N][K]^T through the bf16x6 path (which = 0) or
 // through the fp32-MFMA kernel the whole-video path used before (which = 1); which = 2: the bf16x6 path's 128 x 128 kernel even where
-// the 384 x 256 one applies; which = 3 / 4: the split-bf16 (three-product) contraction, wide tiles / 128 x 128 tiles; device pointers, synchronous
+// the 384 x 256 one applies; which = 3 / 4: the split-bf16 (three-product) contraction, wide tiles / 128 x 128 tiles; which = 5 / 6: its
+// two-product form (B rounded to bf16 here, no lo plane), wide tiles / 128 x 128 tiles; device pointers, synchronous
 extern "C" int infv_exp_gemm(int which, const float* A, const float* B, float* C, int M, int N, int K) {
     using namespace infv;
     if (which == 1) {
         if (launch_project_scores(M, K, N, B, A, C, N, nullptr, 0) != hipSuccess) return -1;
         return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
     }
-    if (which == 3 || which == 4) {
+    if (which >= 3 && which <= 6) {
+        const bool two = which >= 5, narrow = which == 4 || which == 6;
         // split-bf16 (hi/lo, three products) contraction of the video Q-former: 3 = whichever kernel the launcher picks (the
         // 384 x 256 one where whole tiles fit), 4 = the 128 x 128 kernel on the same operands
         __bf16* sp[4] = {};
@@ -772,10 +805,11 @@ extern "C" int infv_exp_gemm(int which, const float* A, const float* B, float* C
         if (launch_split_rows(A, K, M, K, sp[0], sp[1], K, nullptr) != hipSuccess) rc3 = -1;
         if (launch_split_rows(B, K, N, K, sp[2], sp[3], K, nullptr) != hipSuccess) rc3 = -1;
         SplitGemm sg{};
-        sg.A_hi = sp[0]; sg.A_lo = sp[1]; sg.lda = K; sg.strideA = 0; sg.B_hi = sp[2]; sg.B_lo = sp[3]; sg.ldb = K; sg.strideB = 0;
+        sg.A_hi = sp[0]; sg.A_lo = sp[1]; sg.lda = K; sg.strideA = 0; sg.B_hi = sp[2]; sg.B_lo = two ? nullptr : sp[3]; sg.ldb = K; sg.strideB = 0;
         sg.C = C; sg.ldc = N; sg.strideC = 0; sg.split_stride = 0; sg.M = M; sg.N = N; sg.K = K; sg.k_per_split = K; sg.splitk = 1; sg.nbatch = 1;
-        if (rc3 == 0 && which == 3 && !split_gemm_wide_applies(sg)) rc3 = -2;        // (the test wants to know that the wide kernel ran)
-        if (rc3 == 0 && launch_split_gemm(sg, nullptr, which == 4 ? 1 : 0) != hipSuccess) rc3 = -1;
+        sg.wide = !narrow;                               // (3 / 5: the 384 x 256 kernel wherever whole tiles apply, however few)
+        if (rc3 == 0 && !narrow && !split_gemm_wide_applies(sg)) rc3 = -2;           // (the test wants to know that the wide kernel ran)
+        if (rc3 == 0 && launch_split_gemm(sg, nullptr, narrow ? 1 : 0) != hipSuccess) rc3 = -1;
         if (hipDeviceSynchronize() != hipSuccess) rc3 = -1;
         for (int i = 0; i < 4; ++i) (void)hipFree(sp[i]);
         return rc3;
@@ -865,6 +899,85 @@ hipError_t launch_split_transpose(const float* F, int nb, int n, int d, void* Fh
     INFV_LAUNCH(split_transpose_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, F, n, d,
                        static_cast<__bf16*>(Fh), static_cast<__bf16*>(Fl), static_cast<__bf16*>(Th), static_cast<__bf16*>(Tl),
                        kbar, P);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The token pass for bf16 frame tokens: F [n][d] bf16 is the score contraction's B operand as it stands (hi = the token, lo = 0
+// exactly), so only FT_hi [d][n] is written -- and, with kbar != nullptr, the frame means, summed in token order and divided by P
+// as above (the same bits as the fp32 pass on the same values, and as pool_frames_kernel).  64 x 64 tiles, 16-byte loads and
+// stores of 8 bf16; grid (n / 64, d / 64, chunks).  LDS rows are 66 bf16 (33 words) apart: the transposed read of a wave (8 columns x
+// 8 row groups) touches 32 distinct banks.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void transpose_bf16_kernel(const __bf16* __restrict__ F, int n, int d, __bf16* __restrict__ Th,
+                                                             float* __restrict__ kbar, int P) {
+    __shared__ unsigned tile[64 * 33];               // [64 tokens][66 bf16]
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const long cb = (long)blockIdx.z * n * d;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int e = tid + 256 * p;                 // 512 vectors of 8 bf16
+        const int r = e >> 3, c8 = (e & 7) * 8;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (r0 + r < n) v = *reinterpret_cast<const uint4*>(F + cb + (long)(r0 + r) * d + c0 + c8);
+        unsigned* t = tile + r * 33 + (c8 >> 1);
+        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+    }
+    __syncthreads();
+    const unsigned short* th = reinterpret_cast<const unsigned short*>(tile);
+    // transposed: row = column c of the tile, 8 consecutive tokens per thread
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int e = tid + 256 * p;
+        const int c = e >> 3, r8 = (e & 7) * 8;
+        if (r0 + r8 < n) {                           // n % 8 == 0 (multiple of 32)
+            unsigned w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                w[k] = (unsigned)th[(r8 + 2 * k) * 66 + c] | ((unsigned)th[(r8 + 2 * k + 1) * 66 + c] << 16);
+            *reinterpret_cast<uint4*>(Th + cb + (long)(c0 + c) * n + r0 + r8) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+    if (kbar) {
+        const int fpt = 64 / P;                      // frames per tile
+        for (int e = tid; e < fpt * 64; e += 256) {
+            const int f = e >> 6, c = e & 63;
+            if (r0 + (f + 1) * P <= n) {
+                float acc = 0.f;
+                for (int p = 0; p < P; ++p) acc += __uint_as_float((unsigned)th[(f * P + p) * 66 + c] << 16);
+                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
+            }
+        }
+    }
+}
+
+hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, hipStream_t stream, float* kbar, int P) {
+    if (n % 32 || d % 64) return hipErrorInvalidValue;
+    if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
+    INFV_LAUNCH(transpose_bf16_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const __bf16*>(F), n, d,
+                static_cast<__bf16*>(Th), kbar, P);
+    return hipGetLastError();
+}
+
+// x [n] bf16 -> y [n] fp32 (n % 8 == 0): bf16 tokens where the split path does not apply run the fp32 kernels from this copy
+__global__ __launch_bounds__(256) void upcast_bf16_kernel(const __bf16* __restrict__ x, float* __restrict__ y, long n8) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    const uint4 v = reinterpret_cast<const uint4*>(x)[i];
+    floatx4 a = {__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u)};
+    floatx4 b = {__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xffff0000u)};
+    reinterpret_cast<floatx4*>(y)[2 * i] = a;
+    reinterpret_cast<floatx4*>(y)[2 * i + 1] = b;
+}
+
+hipError_t launch_upcast_bf16(const void* x, float* y, long n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (n % 8) return hipErrorInvalidValue;
+    for (long o = 0; o < n; o += (1l << 33)) {          // (grid.x limit)
+        const long m = n - o < (1l << 33) ? n - o : (1l << 33);
+        INFV_LAUNCH(upcast_bf16_kernel, dim3((unsigned)((m / 8 + 255) / 256)), dim3(256), 0, stream, static_cast<const __bf16*>(x) + o, y + o, m / 8);
+    }
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@ struct infv_vqf_s {
     infv_vqf_config cfg;
     int dev = 0;
     bool exact_fp32 = false;
+    bool tok_bf16 = false;                              // the `frames` arguments point to bf16 tokens (infv_vqf_set_token_dtype)
     // chunk-independent prefix of layer 0 (embedding LayerNorm, self-attention block, cross query, pre-multiplied query):
     // reused across encode_chunk calls while the host keeps the weights epoch unchanged (0 = never reuse)
     unsigned long long epoch = 0, c_epoch = 0;
@@ -23,6 +24,7 @@ struct infv_vqf_s {
     DeviceBuf part, h_a, h_b, h1, h2, qkv, sa, xq, along, qt, S, O, merged, inter, kbar;
     DeviceBuf sFh, sFl, sTh, sTl, sPh, sPl, sQh, sQl;   // split-bf16 operands of the short-term attention
     DeviceBuf wFh, wFl, wTh, wTl;                       // the same split of a WHOLE video's frame tokens (layer-major path)
+    DeviceBuf up;                                       // fp32 copy of bf16 tokens where the split path does not apply
     bool fuse = true;                                   // one pass over the frame tokens: split + transpose + frame means
     double split_cache_gb = 64.0;                       // budget for a whole video's split tokens (INFV_VQF_SPLIT_CACHE_GB at create)
     // whole-video (layer-major) path
@@ -95,6 +97,7 @@ int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
 // chunk (shared_q = true: layer 0 of the video Q-former, whose query does not depend on the chunk)
 //   -> merged [nb*Q][hidden] = alpha * short-term context + (1 - alpha) * along   (along == nullptr: short-term only)
 // Split-bf16 copies of frame tokens produced ahead of the attention (prepare_split): [.][n_tokens][d] and [.][d][n_tokens]
+// (bf16 tokens: Fh is the caller's buffer itself, Fl and Tl are nullptr -- the contractions then run their two-product form)
 struct SplitRef { const __bf16 *Fh, *Fl, *Th, *Tl; };
 // infv_vqf_encode_videos takes the short-term attention's split-K counts as for this many chunks per sub-batch, whatever the
 // sub-batch holds: a chunk's summation order then does not depend on the rest of the batch
@@ -109,12 +112,41 @@ static bool split_path(const infv_vqf_s* h, int n_tokens) {
 // means the long-term memories consume.  The tokens do not depend on the layer, so every layer's short-term attention
 // and every layer's memory share this pass (the reference reads them once per layer and once more for the pooling:
 // Qformer.py:236, 278-291).  `whole` selects the video-sized buffers of the layer-major path.
-static int prepare_split(infv_vqf_s* h, const float* frames, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
+// element `elems` of a token buffer of either dtype
+static const void* tok_at(const void* frames, bool bf16, long elems) {
+    return static_cast<const char*>(frames) + elems * (bf16 ? 2 : 4);
+}
+
+// bf16 tokens where the split path does not apply: an fp32 copy in the handle's workspace for today's fp32 kernels
+static int upcast_tokens(infv_vqf_s* h, const void* frames, size_t elems, const float** out, hipStream_t stream) {
+    if (elems * sizeof(float) > h->up.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->up.reserve(elems * sizeof(float))); }
+    HIP_TRY(launch_upcast_bf16(frames, h->up.as<float>(), (long)elems, stream));
+    *out = h->up.as<float>();
+    return INFV_OK;
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+static int prepare_split(infv_vqf_s* h, const void* frames_, bool bf16, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
                          hipStream_t stream) {
     const int d = h->cfg.enc_width;
     const size_t szF = (size_t)nb * n_tokens * d * 2;
     DeviceBuf& Fh = whole ? h->wFh : h->sFh; DeviceBuf& Fl = whole ? h->wFl : h->sFl;
     DeviceBuf& Th = whole ? h->wTh : h->sTh; DeviceBuf& Tl = whole ? h->wTl : h->sTl;
+    if (bf16) {                                              // read in place: only the transposed copy is written
+        if (szF > Th.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(Th.reserve(szF)); }
+        const __bf16* fb = static_cast<const __bf16*>(frames_);
+        for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
+            const int n = nb - c0 < 32768 ? nb - c0 : 32768;
+            const size_t o = (size_t)c0 * n_tokens * d;
+            HIP_TRY(launch_transpose_bf16(fb + o, n, n_tokens, d, Th.as<__bf16>() + o, stream,
+                                          kbar ? kbar + (size_t)c0 * (n_tokens / h->cfg.tokens_per_frame) * d : nullptr,
+                                          h->cfg.tokens_per_frame));
+        }
+        *ref = SplitRef{fb, nullptr, Th.as<__bf16>(), nullptr};
+        return INFV_OK;
+    }
+    const float* frames = static_cast<const float*>(frames_);
     if (szF > Fh.bytes || szF > Fl.bytes || szF > Th.bytes || szF > Tl.bytes) {
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(Fh.reserve(szF)); HIP_TRY(Fl.reserve(szF)); HIP_TRY(Th.reserve(szF)); HIP_TRY(Tl.reserve(szF));
@@ -131,7 +163,7 @@ static int prepare_split(infv_vqf_s* h, const float* frames, int nb, int n_token
     return INFV_OK;
 }
 
-int short_attention(infv_vqf_s* h, const float* frames, int nb, int n_tokens, const float* xq, bool shared_q,
+int short_attention(infv_vqf_s* h, const void* frames_, bool bf16 /* only where split_path() holds */, int nb, int n_tokens, const float* xq, bool shared_q,
                     const infv_linear* key, const infv_linear* value, const float* along, float* merged,
                     hipStream_t stream, bool use_cache = false, const SplitRef* pre = nullptr,
                     hipEvent_t along_ready = nullptr /* `along` is produced on another stream: wait here, before the merge */,
@@ -179,7 +211,7 @@ int short_attention(infv_vqf_s* h, const float* frames, int nb, int n_tokens, co
         }
         SplitRef sr;
         if (pre) sr = *pre;                                   // the caller split these tokens already (shared by the layers)
-        else if (int rc = prepare_split(h, frames, nb, n_tokens, nullptr, false, &sr, stream)) return rc;
+        else if (int rc = prepare_split(h, frames_, bf16, nb, n_tokens, nullptr, false, &sr, stream)) return rc;
         if (use_cache) {                                      // (the buffers may just have been (re)allocated above)
             qh = h->c_qh.p; ql = h->c_ql.p;
         } else {
@@ -203,6 +235,8 @@ int short_attention(infv_vqf_s* h, const float* frames, int nb, int n_tokens, co
         p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.wide = inv_nb > 0;
         HIP_TRY(launch_split_gemm(p, stream));
     } else {
+    if (bf16) return fail(INFV_ERR_INVALID, "bf16 tokens reached the fp32 contractions");      // (callers upcast first)
+    const float* frames = static_cast<const float*>(frames_);
     QfGemm g{};                                             // S[b] = qt[b] . frames[b]^T
     g.A = qt; g.lda = d; g.strideA = shared_q ? 0 : (long)rows * d;
     g.B[0] = frames; g.ldb = d; g.strideB = (long)n_tokens * d; g.seg_rows = n_tokens;
@@ -296,21 +330,36 @@ int infv_vqf_set_precision(infv_vqf_handle h, int32_t exact_fp32) {
     return INFV_OK;
 }
 
+int infv_vqf_set_token_dtype(infv_vqf_handle h, int32_t dtype) {
+    if (!h) return fail(INFV_ERR_INVALID, "null handle");
+    if (dtype != INFV_TOKENS_F32 && dtype != INFV_TOKENS_BF16) return fail(INFV_ERR_INVALID, "set_token_dtype: unknown token dtype %d", dtype);
+    h->tok_bf16 = dtype == INFV_TOKENS_BF16;
+    return INFV_OK;
+}
+
 int infv_vqf_set_weights_epoch(infv_vqf_handle h, uint64_t epoch) {
     if (!h) return fail(INFV_ERR_INVALID, "null handle");
     h->epoch = epoch;
     return INFV_OK;
 }
 
-int infv_vqf_short_attention(infv_vqf_handle h, const float* frames, int32_t n_tokens, const float* xq,
+int infv_vqf_short_attention(infv_vqf_handle h, const void* frames, int32_t n_tokens, const float* xq,
                              const infv_linear* key, const infv_linear* value, const float* a_long,
                              float* merged, void* stream) {
     if (!h || !frames || !xq || !key || !value || !merged || !key->w || !value->w || !value->b)
         return fail(INFV_ERR_INVALID, "null argument");
-    return short_attention(h, frames, 1, n_tokens, xq, false, key, value, a_long, merged, static_cast<hipStream_t>(stream));
+    bool bf16 = h->tok_bf16;
+    if (bf16 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "bf16 frames must be 16-byte aligned");
+    if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
+    if (bf16 && !split_path(h, n_tokens)) {
+        const float* f32 = nullptr;
+        if (int rc = upcast_tokens(h, frames, (size_t)n_tokens * h->cfg.enc_width, &f32, static_cast<hipStream_t>(stream))) return rc;
+        frames = f32; bf16 = false;
+    }
+    return short_attention(h, frames, bf16, 1, n_tokens, xq, false, key, value, a_long, merged, static_cast<hipStream_t>(stream));
 }
 
-int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const float* frames, int32_t T,
+int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const void* frames, int32_t T,
                           const infv_vqf_weights* w, const double* u, int32_t new_video,
                           float* hidden_out, float* llama_out, void* stream_) {
     if (!h || !frames || !w) return fail(INFV_ERR_INVALID, "null argument");
@@ -322,8 +371,15 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
     if (T < 1) return fail(INFV_ERR_INVALID, "T must be >= 1");
     if (llama_out && (c.proj_out <= 0 || !w->llama_proj.w)) return fail(INFV_ERR_INVALID, "llama_out without llama_proj");
     const int Q = c.n_query, Hd = c.hidden, n_tokens = T * c.tokens_per_frame;
+    bool bf16 = h->tok_bf16;
+    if (bf16 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "bf16 frames must be 16-byte aligned");
     if (use_ltm)
         if (int rc = ensure_streams(h)) return rc;
+    if (bf16 && !split_path(h, n_tokens)) {                    // today's fp32 kernels from an fp32 copy
+        const float* f32 = nullptr;
+        if (int rc = upcast_tokens(h, frames, (size_t)n_tokens * c.enc_width, &f32, stream)) return rc;
+        frames = f32; bf16 = false;
+    }
 
     // The prefix of layer 0 (embedding LayerNorm -> self-attention block -> cross query) depends on the weights only,
     // not on the chunk: with a non-zero weights epoch it is computed once and reused until the epoch changes.
@@ -356,12 +412,12 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
     SplitRef sref; const SplitRef* pre = nullptr;
     const bool fused_pool = h->fuse && split_path(h, n_tokens) && 64 % c.tokens_per_frame == 0;
     if (h->fuse && split_path(h, n_tokens)) {
-        if (int rc = prepare_split(h, frames, 1, n_tokens, use_ltm && fused_pool ? h->kbar.as<float>() : nullptr, false, &sref, stream)) return rc;
+        if (int rc = prepare_split(h, frames, bf16, 1, n_tokens, use_ltm && fused_pool ? h->kbar.as<float>() : nullptr, false, &sref, stream)) return rc;
         pre = &sref;
     }
     if (use_ltm && !fused_pool) {
-        // (the frames of this entry point are fp32: the handle's token dtype is sticky state an earlier bf16 caller may have set)
-        if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;
+        // (the LTM handle's token dtype is sticky state an earlier caller may have set)
+        if (int rc = infv_ltm_set_token_dtype(ltm[0], bf16 ? INFV_TOKENS_BF16 : INFV_TOKENS_F32)) return rc;
         if (int rc = infv_ltm_pool(ltm[0], frames, T, h->kbar.as<float>(), stream_)) return rc;   // shared by all layers
     }
 
@@ -402,7 +458,7 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
             along = h->along.as<float>();
             along_ready = h->ev_side;
         }
-        if (int rc = short_attention(h, frames, 1, n_tokens, xqb, false, &L.x_k, &L.x_v, along,
+        if (int rc = short_attention(h, frames, bf16, 1, n_tokens, xqb, false, &L.x_k, &L.x_v, along,
                                      h->merged.as<float>(), stream, l0c, pre, along_ready)) return rc;
         LinearCall xo{h->merged.as<float>(), Q, Hd, {&L.x_o}, 1, Hd};
         xo.residual = h1; xo.res_rows = Q; xo.ln = &L.x_ln; xo.y = h->h2.as<float>();
@@ -429,7 +485,7 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const f
 // The layer-major body of infv_vqf_encode_video (multi = false: one video, ltm [n_layers]) and infv_vqf_encode_videos (multi:
 // V videos packed by the host array cu, ltm [V][n_layers]; every choice that shapes a GEMM or contraction is taken from
 // per-chunk quantities or constants, and each layer's memories step through infv_ltm_steps_videos).
-static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const float* frames, int32_t n_chunks, int32_t T,
+static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void* frames, int32_t n_chunks, int32_t T,
                        const infv_vqf_weights* w, const double* u, int32_t new_video, float* hidden_out, float* llama_out,
                        float* llama_mean, void* stream_, int32_t V, const int32_t* cu, bool multi) {
     const infv_vqf_config& c = h->cfg;
@@ -439,10 +495,17 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const floa
     if (use_ltm && !ltm) return fail(INFV_ERR_INVALID, "alpha != 1 needs the per-layer LTM handles");
     if (T < 1) return fail(INFV_ERR_INVALID, "T must be >= 1");
     if ((llama_out || llama_mean) && (c.proj_out <= 0 || !w->llama_proj.w)) return fail(INFV_ERR_INVALID, "llama output without llama_proj");
+    bool bf16 = h->tok_bf16;
+    if (bf16 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "bf16 frames must be 16-byte aligned");
     if (int rc = ensure_streams(h)) return rc;
     const int Q = c.n_query, Hd = c.hidden, C = n_chunks, S = c.nb_samples;
     const int n_tokens = T * c.tokens_per_frame;
     const long chunk_k = (long)n_tokens * c.enc_width;
+    if (bf16 && !split_path(h, n_tokens)) {                    // today's fp32 kernels from an fp32 copy
+        const float* f32 = nullptr;
+        if (int rc = upcast_tokens(h, frames, (size_t)C * chunk_k, &f32, stream)) return rc;
+        frames = f32; bf16 = false;
+    }
     const long M = (long)C * Q;                               // rows of the whole-video activations
     // ---- workspaces: whole-video activations + per-block scratch ----
     const int rb_max = multi ? 128 : 64;                      // (batch invariant: the row count does not shape the GEMMs)
@@ -500,21 +563,22 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const floa
     SplitRef wref{}; bool have_w = false, have_kbar = false;
     {
         const double budget_gb = h->split_cache_gb;
-        const double need_gb = 4.0 * (double)C * (double)chunk_k * 2.0 / 1e9;
+        const double need_gb = (bf16 ? 1.0 : 4.0) * (double)C * (double)chunk_k * 2.0 / 1e9;   // (bf16 tokens: only FT_hi is written)
         if (h->fuse && split_path(h, n_tokens) && need_gb <= budget_gb) {
             have_kbar = use_ltm && 64 % c.tokens_per_frame == 0;
-            if (int rc = prepare_split(h, frames, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
+            if (int rc = prepare_split(h, frames, bf16, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
             have_w = true;
         }
     }
     auto pre_at = [&](int c0, SplitRef* r) -> const SplitRef* {  // the cached split of chunks c0.. (nullptr: split per sub-batch)
         if (!have_w) return nullptr;
         const long o = (long)c0 * chunk_k;
-        *r = SplitRef{wref.Fh + o, wref.Fl + o, wref.Th + o, wref.Tl + o};
+        *r = SplitRef{wref.Fh + o, wref.Fl ? wref.Fl + o : nullptr, wref.Th + o, wref.Tl ? wref.Tl + o : nullptr};
         return r;
     };
+    const int ltm_dtype = bf16 ? INFV_TOKENS_BF16 : INFV_TOKENS_F32;   // (what the fallbacks below hand the memories)
     if (multi && use_ltm && !have_kbar) {                    // the frame means every layer's memories step from
-        if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;
+        if (int rc = infv_ltm_set_token_dtype(ltm[0], ltm_dtype)) return rc;
         if (int rc = infv_ltm_pool(ltm[0], frames, (int64_t)C * T, h->vkbar.as<float>(), stream_)) return rc;
     }
     std::vector<infv_ltm_handle> hs_l(multi ? V : 0);         // layer l's handles of every video
@@ -571,7 +635,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const floa
                 if (have_kbar) {
                     if (int rc = infv_ltm_consolidate_pooled(ltm[l], h->vkbar.as<float>(), C, T, h->v_xqs.as<float>(), Q, &pr,
                                                              u ? h->vu.as<double>() : nullptr, new_video, valong, stream_)) return rc;
-                } else if (int rc = infv_ltm_set_token_dtype(ltm[l], INFV_TOKENS_F32)) {
+                } else if (int rc = infv_ltm_set_token_dtype(ltm[l], ltm_dtype)) {
                     return rc;
                 } else if (int rc = infv_ltm_consolidate(ltm[l], frames, C, T, h->v_xqs.as<float>(), Q, &pr,
                                                          u ? h->vu.as<double>() : nullptr, new_video, valong, stream_)) return rc;
@@ -580,7 +644,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const floa
             for (int c0 = 0; c0 < C; c0 += NB) {
                 const int nb = C - c0 < NB ? C - c0 : NB;
                 SplitRef sr;
-                if (int rc = short_attention(h, frames + c0 * chunk_k, nb, n_tokens, h->v_xqs.as<float>(), true, &L.x_k, &L.x_v,
+                if (int rc = short_attention(h, tok_at(frames, bf16, c0 * chunk_k), bf16, nb, n_tokens, h->v_xqs.as<float>(), true, &L.x_k, &L.x_v,
                                              use_ltm ? valong + (long)c0 * Q * Hd : nullptr, vmerged + (long)c0 * Q * Hd, stream,
                                              false, pre_at(c0, &sr), nullptr, multi ? kInvariantNb : 0)) return rc;
             }
@@ -618,7 +682,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const floa
                 if (new_video)
                     if (int rc = infv_ltm_reset(ltm[l])) return rc;
                 if (!have_kbar) {
-                    if (int rc = infv_ltm_set_token_dtype(ltm[l], INFV_TOKENS_F32)) return rc;
+                    if (int rc = infv_ltm_set_token_dtype(ltm[l], ltm_dtype)) return rc;
                     if (int rc = infv_ltm_pool(ltm[l], frames, (int64_t)C * T, h->vkbar.as<float>(), h->side)) return rc;
                 }
                 // per-chunk queries: new-row projections of all chunks in one GEMM, then the chain chunk by chunk
@@ -630,7 +694,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const floa
             for (int c0 = 0; c0 < C; c0 += NB) {
                 const int nb = C - c0 < NB ? C - c0 : NB;
                 SplitRef sr;
-                if (int rc = short_attention(h, frames + c0 * chunk_k, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
+                if (int rc = short_attention(h, tok_at(frames, bf16, c0 * chunk_k), bf16, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
                                              nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
                                              pre_at(c0, &sr), nullptr, multi ? kInvariantNb : 0)) return rc;
             }
@@ -686,14 +750,14 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const floa
     return INFV_OK;
 }
 
-int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const float* frames, int32_t n_chunks,
+int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const void* frames, int32_t n_chunks,
                           int32_t T, const infv_vqf_weights* w, const double* u, int32_t new_video,
                           float* hidden_out, float* llama_out, float* llama_mean, void* stream_) {
     if (!h || !frames || !w || n_chunks < 1) return fail(INFV_ERR_INVALID, "bad argument");
     return encode_impl(h, ltm, frames, n_chunks, T, w, u, new_video, hidden_out, llama_out, llama_mean, stream_, 1, nullptr, false);
 }
 
-int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
                            int32_t T, const infv_vqf_weights* w, const double* u, int32_t new_video, float* hidden_out,
                            float* llama_out, float* llama_mean, void* stream_) {
     // ---- validation before any device work or memory change ----

@@ -56,7 +56,7 @@ hipError_t launch_qf_sum_slabs(float* parts, int nsplit, long stride, long n, hi
 // C[z][m][o] = sum_k (A_hi + A_lo)[b][m][k] * (B_hi + B_lo)[b][o][k], z = b * splitk + s; all operands K-contiguous bf16
 struct SplitGemm {
     const __bf16* A_hi; const __bf16* A_lo; long lda, strideA;
-    const __bf16* B_hi; const __bf16* B_lo; long ldb, strideB;
+    const __bf16* B_hi; const __bf16* B_lo; long ldb, strideB;       // B_lo == nullptr: B is bf16 as it stands (two products)
     float* C; long ldc, strideC, split_stride;
     int M, N, K, k_per_split, splitk, nbatch;
     long long* wg_stamps;            // residency / loop-cycle experiment (wg_stamps.h), or nullptr
@@ -85,6 +85,10 @@ hipError_t launch_split_rows(const float* x, long ld_in, long rows, int cols, vo
 // F [nb][n][d] fp32 -> Fh/Fl [nb][n][d] and Th/Tl [nb][d][n] (bf16 hi/lo)
 hipError_t launch_split_transpose(const float* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl, hipStream_t stream,
                                   float* kbar = nullptr, int P = 0);   // kbar: also the frame means [nb][n / P][d]
+// F [nb][n][d] bf16 -> Th [nb][d][n] bf16 (the untransposed operand is F itself) and, with kbar, the frame means [nb][n / P][d]
+hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, hipStream_t stream, float* kbar = nullptr, int P = 0);
+// x [n] bf16 -> y [n] fp32, n % 8 == 0
+hipError_t launch_upcast_bf16(const void* x, float* y, long n, hipStream_t stream);
 // softmax of fp32 score rows, written as bf16 hi/lo
 hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long ld, void* Ph, void* Pl, long ld_out, hipStream_t stream);
 

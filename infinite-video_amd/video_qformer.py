@@ -156,8 +156,10 @@ class ShortMemoryBuffer:
       only the newest ``n_position**2`` frames survive; it returns them as ``[1, T*P, d]`` without copying.
 
     ``dtype=torch.bfloat16`` stores the tokens at half the bytes: ``infv_ltm_pool`` / ``infv_ltm_consolidate`` read them
-    directly (``infv_ltm_set_token_dtype``); the result then differs from the fp32-token run by the rounding of the
-    tokens (off by default, never used for the headline number)."""
+    directly (``infv_ltm_set_token_dtype``), and so does the video Q-former (``encode_video`` -> ``encode_frames``,
+    ``infv_vqf_set_token_dtype``): no fp32 copy is made, the short-term contractions read the buffer in place.  The result
+    then differs from the fp32-token run by the rounding of the tokens only -- it is bit for bit the run on the rounded
+    values (off by default, never used for the headline number)."""
 
     def __init__(self, tokens_per_frame: int, width: int, capacity_frames: int = 2049, dtype=torch.float32,
                  device=None):
@@ -201,6 +203,17 @@ def _dev_f32(t: torch.Tensor, device: torch.device) -> torch.Tensor:
     if t.dtype != torch.float32 or not t.is_contiguous() or t.device != device:
         t = t.to(device=device, dtype=torch.float32).contiguous()
     return t
+
+
+def _dev_tokens(t: torch.Tensor, device: torch.device):
+    """Frame tokens for the C ABI: (tensor, infv_token_dtype).  Contiguous bf16 tokens on the device pass through untouched
+    (16-byte aligned, as the ABI asks; a misaligned view is copied, still bf16); everything else becomes fp32 as before."""
+    t = t.detach()
+    if t.dtype == torch.bfloat16 and t.device == device:
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            t = t.clone(memory_format=torch.contiguous_format)
+        return t, 1
+    return _dev_f32(t, device), 0
 
 
 class VideoMemory:
@@ -409,11 +422,12 @@ class InfVideoEncoder(nn.Module):
             sig.append((m.bias.data_ptr(), m.bias._version))
         return (hash(tuple(sig)) & 0x7FFFFFFFFFFFFFFF) | 1
 
-    def _handle(self, device: torch.device):
+    def _handle(self, device: torch.device, token_dtype: int = 0):
         h = self._handle_raw(device)
         if getattr(self, "_vqf_exact", None) != bool(self.exact_fp32):
             _lib.check(_lib.load().infv_vqf_set_precision(h, int(bool(self.exact_fp32))))
             self._vqf_exact = bool(self.exact_fp32)
+        _lib.check(_lib.load().infv_vqf_set_token_dtype(h, token_dtype))      # per call: 0 fp32, 1 bf16 (infv_token_dtype)
         return h
 
     def _handle_raw(self, device: torch.device):
@@ -463,8 +477,8 @@ class InfVideoEncoder(nn.Module):
         if frame_hidden_state.size(2) != cfg.encoder_width or frame_hidden_state.size(1) % P:
             raise ValueError(f"frame_hidden_state must be [1, T*{P}, {cfg.encoder_width}]")
         T = frame_hidden_state.size(1) // P
-        k = _dev_f32(frame_hidden_state[0], device)
-        h = self._handle(device)
+        k, tok = _dev_tokens(frame_hidden_state[0], device)
+        h = self._handle(device, tok)
         lib = _lib.load()
         use_ltm = cfg.alpha != 1.0
         handles = (C.c_void_p * cfg.num_hidden_layers)()
@@ -526,8 +540,8 @@ class InfVideoEncoder(nn.Module):
             raise ValueError(f"frames must be [C, T*{P}, {cfg.encoder_width}]")
         device = frames.device
         Cn, T = frames.size(0), frames.size(1) // P
-        k = _dev_f32(frames, device)
-        h = self._handle(device)
+        k, tok = _dev_tokens(frames, device)
+        h = self._handle(device, tok)
         lib = _lib.load()
         use_ltm = cfg.alpha != 1.0
         handles = (C.c_void_p * Ln)()
@@ -595,8 +609,8 @@ class InfVideoEncoder(nn.Module):
             raise ValueError(f"frames must be [{total}, T*{P}, {cfg.encoder_width}], got {tuple(frames.shape)}")
         device = frames.device
         T = frames.size(1) // P
-        k = _dev_f32(frames, device)
-        h = self._handle(device)
+        k, tok = _dev_tokens(frames, device)
+        h = self._handle(device, tok)
         lib = _lib.load()
         use_ltm = cfg.alpha != 1.0
         handles = None
