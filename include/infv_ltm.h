@@ -358,6 +358,40 @@ int infv_ltm_profile_read(infv_ltm_handle h, int32_t kernel, int64_t* launches, 
  * benchmark reads it before and after a call to state "launches per chunk".  Host-side counter, no device work. */
 int64_t infv_ltm_launch_count(void);
 
+/* ---- Device rng for the Gibbs uniforms (additive in ABI 6) ----
+ * The reference samples the sticky memory with torch.rand(nb_samples) on the memory's device
+ * (long_term_attention_gibbs.py:204-206); on its CUDA deployment that is torch's Philox device generator.  With the rng on, every
+ * entry point that takes `u` accepts u == NULL on an existing sticky memory and the kernels generate the uniforms themselves,
+ * in registers, with a counter-based Philox4x32-10 (csrc/philox.h) -- no more launches than with explicit u.  (The reference's
+ * second nb_samples uniforms, :206, place the sample inside the drawn bin; they are degenerate and not generated.)
+ *   key = (seed & 0xffffffff, seed >> 32)
+ *   ctr = (s >> 1, layer, pos, stream_id)      s: sample slot in [0, S); layer: index inside the handle
+ *   one block (w0, w1, w2, w3) serves two slots: u[s even] = u53(w0, w1), u[s odd] = u53(w2, w3)
+ *   u53(a, b) = ((a >> 5) * 2^26 + (b >> 6)) * 2^-53, a double in [0, 1)
+ * pos is the number of steps the handle has taken since its last reset: the index of the chunk within the document.  The first
+ * chunk of a document has pos = 0 and draws nothing.  pos advances on EVERY step of every entry point, explicit-u steps included;
+ * infv_ltm_reset and new_doc set it to 0.  A video's draws therefore depend only on (seed, stream_id) and its own content, not
+ * on what the handle or the process did before.  infv_ltm_import_state / infv_ltm_import_chain_state leave pos alone: a caller
+ * who continues a document on another handle sets it with infv_ltm_set_rng_position.  The chain-state blob does not carry it.
+ * Precedence: a non-NULL u is always used as given (same bits as with the rng off); NULL u with the rng on is generated; NULL u
+ * with the rng off is refused as before.  The multi-handle calls (infv_ltm_consolidate_videos, infv_ltm_steps_videos) need the
+ * rng on for EVERY handle when u is NULL (INFV_ERR_INVALID before any handle changes); each handle draws from its own
+ * (seed, stream_id) at its own position.  One-layer handles that stand for the layers of one model (infv_vqf_*) are told apart
+ * by their stream_id, since `layer` is 0 for each.
+ * pos travels in the launch arguments, so a captured graph replays the position it was captured with.
+ * on = 0 restores the default (the seed and stream are kept but unused).  set_rng touches neither the memory nor pos. */
+int infv_ltm_set_rng(infv_ltm_handle h, int32_t on, uint64_t seed, uint32_t stream_id);
+int infv_ltm_get_rng_position(infv_ltm_handle h, uint32_t* pos);
+int infv_ltm_set_rng_position(infv_ltm_handle h, uint32_t pos);
+/* The uniforms the kernels would generate for steps pos0 .. pos0 + n_steps - 1 (pos wraps at 2^32) of a handle of n_layers layers
+ * and S samples: u [n_steps][n_layers][S] float64, written to a DEVICE buffer by one launch on `stream` ... */
+int infv_ltm_rng_fill(uint64_t seed, uint32_t stream_id, uint32_t pos0, int32_t n_steps, int32_t n_layers, int32_t S,
+                      double* u_device, void* stream);
+/* ... or to a HOST buffer by the CPU, from the same header, with no device work: feeding them back as explicit u (or to a CPU
+ * reference) replays a device-rng run draw for draw. */
+int infv_ltm_rng_fill_host(uint64_t seed, uint32_t stream_id, uint32_t pos0, int32_t n_steps, int32_t n_layers, int32_t S,
+                           double* u_host);
+
 #ifdef __cplusplus
 }
 #endif

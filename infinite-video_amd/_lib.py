@@ -148,6 +148,11 @@ _SIGNATURES = {
     "infv_ltm_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "infv_ltm_profile_read": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "infv_ltm_launch_count": (C.c_int64, []),
+    "infv_ltm_set_rng": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32]),
+    "infv_ltm_get_rng_position": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "infv_ltm_set_rng_position": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "infv_ltm_rng_fill": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "infv_ltm_rng_fill_host": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     # include/infv_vqf.h
     "infv_vqf_create": (C.c_int, [C.POINTER(VqfConfig), C.POINTER(C.c_void_p)]),
     "infv_vqf_destroy": (C.c_int, [C.c_void_p]),

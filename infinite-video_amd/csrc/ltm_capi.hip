@@ -194,6 +194,10 @@ struct infv_ltm_s {
     DeviceBuf vid_tab, vid_kbar, vid_P;   // infv_ltm_consolidate_videos with this handle first: video table, pooled frames and projected rows of one step
     int sc = 0;
     int n_bins = 128;
+    // device rng (infv_ltm_set_rng): with it on, a NULL u is generated by the kernels (philox.h).  pos = steps since the last reset.
+    bool rng_on = false; uint64_t rng_seed = 0; uint32_t rng_stream = 0; uint32_t pos = 0;
+    bool gen(const void* u) const { return !u && rng_on; }                       // this call's uniforms are generated
+    RngView rng_view(uint32_t at) const { RngView g = make_rng_view(rng_seed, rng_stream, at); g.on = rng_on ? 1u : 0u; return g; }
     Profiler prof;
     ~infv_ltm_s() {
         for (auto& kv : plans) delete kv.second;
@@ -238,7 +242,7 @@ int check_chain_error(infv_ltm_handle h) {
     if (h->err_host && *reinterpret_cast<volatile unsigned int*>(h->err_host)) {
         const unsigned int code = *reinterpret_cast<volatile unsigned int*>(h->err_host);
         *reinterpret_cast<volatile unsigned int*>(h->err_host) = 0;
-        h->has_memory = false; h->parts = 0; h->k_stale = false;
+        h->has_memory = false; h->parts = 0; h->k_stale = false; h->pos = 0;
         if (code == kErrBlobMismatch)
             return fail(INFV_ERR_STATE, "the blob handed to an earlier infv_ltm_import_chain_state was not exported by a handle of "
                                         "this shape (magic / version / L, N, d, dm, H, Q, n_bins in its header); the memory has been reset");
@@ -309,13 +313,13 @@ int chain_step(infv_ltm_handle h, const Plan& plan, const float* R, const float*
     if (inf) {
         if (h->cfg.sticky) {
             if (!draw_done) {
-                if (!u) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
+                if (!u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
                 if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
                 Timed t_(h->prof, INFV_KERNEL_DRAW, stream);
                 HIP_TRY(launch_draw(h->bin_part[h->pc].as<float>(), h->parts, h->probs_override.as<float>(),
                                     h->override_mask, plan.sticky(), u, h->S, h->L,
                                     h->probs.as<float>(), h->bins.as<int32_t>(), h->idx.as<int32_t>(), stream,
-                                    h->bins_forced.as<int32_t>(), h->forced_mask));
+                                    h->bins_forced.as<int32_t>(), h->forced_mask, h->rng_view(h->pos)));
             }
             h->override_mask = 0;
             h->forced_mask = 0;
@@ -344,6 +348,7 @@ int chain_step(infv_ltm_handle h, const Plan& plan, const float* R, const float*
     h->parts = parts;
     h->lastQ = Q;
     h->last_fast = false;
+    ++h->pos;
     return INFV_OK;
 }
 
@@ -357,7 +362,7 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
     int bins_stride = 0;
     const int32_t* pos_box2 = dp.uniform_box2.as<int32_t>();
     if (inf && h->cfg.sticky) {
-        if (!u) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
+        if (!u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
         if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
         // (checked BEFORE the draw consumes the one-shot masks: an unsupported request leaves the handle as it was)
         if (h->forced_mask && h->forced_mask != (1u << h->L) - 1u)
@@ -365,7 +370,7 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
         Timed t_(h->prof, INFV_KERNEL_DRAW, stream);
         HIP_TRY(launch_draw(h->bin_part[h->pc].as<float>(), h->parts, h->probs_override.as<float>(), h->override_mask,
                             plan.sticky(), u, h->S, h->L, h->probs.as<float>(), h->bins.as<int32_t>(), h->idx.as<int32_t>(),
-                            stream, h->bins_forced.as<int32_t>(), h->forced_mask));
+                            stream, h->bins_forced.as<int32_t>(), h->forced_mask, h->rng_view(h->pos)));
         h->override_mask = 0;
         // a forced draw replaces the resampled bins (infv_ltm_set_bins); get_draw still returns the step's own
         bins = h->forced_mask ? h->bins_forced.as<int32_t>() : h->bins.as<int32_t>();
@@ -429,6 +434,7 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
     h->parts = h->H;
     h->lastQ = Q;
     h->last_fast = false;
+    ++h->pos;
     return INFV_OK;
 }
 
@@ -455,7 +461,7 @@ int precheck_step(infv_ltm_handle h, const void* q, const void* proj, const void
     Plan* plan = nullptr;
     if (int rc = find_plan(h, T, &plan)) return rc;
     const bool on_memory = keeps_memory && h->has_memory;          // the call's first step resamples an existing memory
-    if (h->cfg.sticky && !u && (on_memory || n_chunks > 1))         // (every step after the call's first one does)
+    if (h->cfg.sticky && !u && !h->rng_on && (on_memory || n_chunks > 1))   // (every step after the call's first one does)
         return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
     if (h->cfg.sticky && on_memory) {
         if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
@@ -677,6 +683,7 @@ int infv_ltm_reset(infv_ltm_handle h) {
     h->has_memory = false;
     h->parts = 0;
     h->k_stale = false;
+    h->pos = 0;
     return INFV_OK;
 }
 
@@ -754,8 +761,9 @@ int infv_ltm_step(infv_ltm_handle h, const float* kbar, int32_t T, const float* 
     StepDraw dr;
     memset(&dr, 0, sizeof(dr));
     if (inf && h->cfg.sticky) {
-        if (!u) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
+        if (!u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
         if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
+        dr.rng = h->rng_view(h->pos);
         dr.n_layers = h->L; dr.bin_part = h->bin_part[h->pc].as<float>(); dr.parts = h->parts;
         dr.probs_override = h->probs_override.as<float>(); dr.override_mask = h->override_mask; dr.sticky = plan->sticky();
         dr.u = u; dr.S = h->S; dr.probs_out = h->probs.as<float>(); dr.bins_out = h->bins.as<int32_t>(); dr.idx_out = h->idx.as<int32_t>();
@@ -892,7 +900,7 @@ struct FastPipe {
         s.op = st.op->view();
         s.draw_mode = st.inf ? (h->cfg.sticky ? 1 : 2) : 0;
         if (s.draw_mode == 1) {
-            if (!st.u) return fail(INFV_ERR_INVALID, "sticky consolidation needs the Gibbs uniforms u");
+            if (!st.u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky consolidation needs the Gibbs uniforms u");
             if (counter == 0 && h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available");
         }
         const long slot = counter % h->ring;
@@ -903,7 +911,7 @@ struct FastPipe {
         s.acc_next = h->mass_acc[counter % 3].as<unsigned long long>();
         s.acc_clear = h->mass_acc[(counter + 1) % 3].as<unsigned long long>();
         s.probs_override = h->probs_override.as<float>(); s.override_mask = h->override_mask;
-        s.u = st.u; s.uniform_idx = plan.uniform_idx.as<int32_t>();
+        s.u = st.u; s.rng = h->rng_view(h->pos); s.uniform_idx = plan.uniform_idx.as<int32_t>();
         s.probs_out = h->probs.as<float>(); s.bins_out = h->bins.as<int32_t>(); s.idx_out = h->idx.as<int32_t>();
         if (h->trace_cap > counter) {
             s.probs_tr = h->trace_probs ? h->trace_probs + (size_t)counter * h->L * h->n_bins : nullptr;
@@ -938,6 +946,7 @@ struct FastPipe {
         h->lastQ = Q;
         h->last_fast = true;
         ++counter;
+        ++h->pos;
         return INFV_OK;
     }
 
@@ -952,7 +961,7 @@ struct FastPipe {
         b.op = plan.inf.view();
         b.draw_mode = h->cfg.sticky ? 1 : 2;
         if (b.draw_mode == 1) {
-            if (!u) return fail(INFV_ERR_INVALID, "sticky consolidation needs the Gibbs uniforms u");
+            if (!u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky consolidation needs the Gibbs uniforms u");
             if (counter == 0 && h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available");
         }
         b.n_steps = n; b.step0 = counter; b.ring = h->ring;
@@ -969,7 +978,7 @@ struct FastPipe {
             b.bins_tr = h->trace_bins ? h->trace_bins + (size_t)counter * h->L * h->S : nullptr;
         }
         b.probs_override = h->probs_override.as<float>(); b.override_mask = h->override_mask;
-        b.u = u; b.uf = uf; b.uniform_idx = plan.uniform_idx.as<int32_t>();
+        b.u = u; b.rng = h->rng_view(h->pos); b.uf = uf; b.uniform_idx = plan.uniform_idx.as<int32_t>();
         b.probs_out = h->probs.as<float>(); b.bins_out = h->bins.as<int32_t>(); b.idx_out = h->idx.as<int32_t>();
         b.tab_ring = h->tab_ring.as<int32_t>(); b.tab_slot = (long)tab_slot();
         b.tabb_ring = h->tabb_ring.as<int32_t>();
@@ -1013,6 +1022,7 @@ struct FastPipe {
         h->lastQ = Q;
         h->last_fast = true;
         counter += n;
+        h->pos += (uint32_t)n;
         return INFV_OK;
     }
 
@@ -1318,10 +1328,15 @@ int consolidate_setup(infv_ltm_handle h, ConsolidateCall& cc, const FastPipe& pi
     HIP_TRY(hipEventRecord(h->ev_q, stream));                 // the side stream's projections need no more than this
     // the persistent role S searches in fp32 against the round-ups of the f64 uniforms (equivalent to the f64 compare):
     // converted once per call, off the chain
-    if (cc.u && h->cfg.sticky && chain_batch3_shape_ok(1, plan.sticky().points_ok, plan.inf.rows, h->S, cc.Q)) {
+    // With the handle's device rng on and no u, this pass IS the generator: chunk c of the call sits at position pos + c, and
+    // the round-up is the same function of the double (philox.h, round_up_f32), so the launch count does not change and the
+    // search sees the floats an explicit run of the same uniforms would.  The kernels that read doubles (the per-chunk role S,
+    // chain_batch_kernel) generate their own.
+    if ((cc.u || h->rng_on) && h->cfg.sticky && chain_batch3_shape_ok(1, plan.sticky().points_ok, plan.inf.rows, h->S, cc.Q)) {
         const size_t need_u = (size_t)cc.n_chunks * cc.chunk_u * sizeof(float);
         if (need_u > h->uf_all.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->uf_all.reserve(need_u)); }
-        HIP_TRY(launch_round_up_uniforms(cc.u, h->uf_all.as<float>(), (long)cc.n_chunks * (long)cc.chunk_u, stream));
+        if (cc.u) HIP_TRY(launch_round_up_uniforms(cc.u, h->uf_all.as<float>(), (long)cc.n_chunks * (long)cc.chunk_u, stream));
+        else HIP_TRY(launch_rng_fill(h->rng_view(h->pos), cc.n_chunks, h->L, h->S, nullptr, h->uf_all.as<float>(), stream));
         cc.uf = h->uf_all.as<float>();
     }
     return INFV_OK;
@@ -1813,8 +1828,12 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
     const bool sticky = h0->cfg.sticky != 0;
     int max_len = 0;
     for (int v = 0; v < V; ++v) max_len = cu[v + 1] - cu[v] > max_len ? cu[v + 1] - cu[v] : max_len;
-    if (sticky && !u && (new_doc ? max_len > 1 : total > 0))
-        return fail(INFV_ERR_INVALID, "%s: sticky steps on an existing memory need the Gibbs uniforms u", name);
+    if (sticky && !u && (new_doc ? max_len > 1 : total > 0)) {
+        // generated uniforms: every handle draws from its own stream, so every handle needs its device rng on
+        bool all_on = true;
+        for (int v = 0; v < V; ++v) all_on = all_on && hs[v]->rng_on;
+        if (!all_on) return fail(INFV_ERR_INVALID, "%s: sticky steps on an existing memory need the Gibbs uniforms u", name);
+    }
     std::vector<Plan*> plans(V, nullptr);
     for (int v = 0; v < V; ++v) {
         infv_ltm_handle h = hs[v];
@@ -1901,6 +1920,7 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
             e.chunk0 = cu[order[j]];
             e.cur0 = h->cur;
             e.parts0 = new_doc ? parts : h->parts;
+            e.rng = h->rng_view(h->pos);          // (reset above when new_doc: step s of the call draws at position pos + s)
             const int len = cu[order[j] + 1] - cu[order[j]];
             g_len = len > g_len ? len : g_len;
         }
@@ -1942,6 +1962,7 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
             const int len = cu[order[j] + 1] - cu[order[j]];
             if (len == 0) continue;
             h->cur ^= len & 1;
+            h->pos += (uint32_t)len;
             h->has_memory = true;
             h->parts = parts;
             h->lastQ = Q;
@@ -1970,6 +1991,59 @@ int infv_ltm_steps_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* c
 }  // extern "C"
 
 extern "C" {
+
+// ---- device rng (philox.h) ----
+int infv_ltm_set_rng(infv_ltm_handle h, int32_t on, uint64_t seed, uint32_t stream_id) {
+    if (int rc = check_handle(h)) return rc;
+    h->rng_on = on != 0;
+    h->rng_seed = seed;
+    h->rng_stream = stream_id;
+    return INFV_OK;
+}
+
+int infv_ltm_get_rng_position(infv_ltm_handle h, uint32_t* pos) {
+    if (int rc = check_handle(h)) return rc;
+    if (!pos) return fail(INFV_ERR_INVALID, "get_rng_position: null pos");
+    *pos = h->pos;
+    return INFV_OK;
+}
+
+int infv_ltm_set_rng_position(infv_ltm_handle h, uint32_t pos) {
+    if (int rc = check_handle(h)) return rc;
+    h->pos = pos;
+    return INFV_OK;
+}
+
+static int rng_fill_check(const char* name, int32_t n_steps, int32_t n_layers, int32_t S, const void* out) {
+    if (n_steps < 0 || n_layers < 1 || S < 1) return fail(INFV_ERR_INVALID, "%s: n_steps must not be negative, n_layers and S positive", name);
+    if (n_steps > 0 && !out) return fail(INFV_ERR_INVALID, "%s: null output", name);
+    if ((uint64_t)n_steps * (uint64_t)n_layers * (uint64_t)S > ((uint64_t)1 << 40)) return fail(INFV_ERR_INVALID, "%s: too many uniforms", name);
+    return INFV_OK;
+}
+
+int infv_ltm_rng_fill(uint64_t seed, uint32_t stream_id, uint32_t pos0, int32_t n_steps, int32_t n_layers, int32_t S,
+                      double* u_device, void* stream) {
+    if (int rc = rng_fill_check("rng_fill", n_steps, n_layers, S, u_device)) return rc;
+    HIP_TRY(launch_rng_fill(make_rng_view(seed, stream_id, pos0), n_steps, n_layers, S, u_device, nullptr,
+                            static_cast<hipStream_t>(stream)));
+    return INFV_OK;
+}
+
+int infv_ltm_rng_fill_host(uint64_t seed, uint32_t stream_id, uint32_t pos0, int32_t n_steps, int32_t n_layers, int32_t S,
+                           double* u_host) {
+    if (int rc = rng_fill_check("rng_fill_host", n_steps, n_layers, S, u_host)) return rc;
+    const RngView g = make_rng_view(seed, stream_id, pos0);
+    for (int32_t i = 0; i < n_steps; ++i)
+        for (int l = 0; l < n_layers; ++l) {
+            double* row = u_host + ((size_t)i * n_layers + l) * S;
+            for (int s = 0; s < S; s += 2) {
+                const Philox4 b = gibbs_block(g, (uint32_t)l, pos0 + (uint32_t)i, (uint32_t)(s >> 1));
+                row[s] = philox_u53(b.w[0], b.w[1]);
+                if (s + 1 < S) row[s + 1] = philox_u53(b.w[2], b.w[3]);
+            }
+        }
+    return INFV_OK;
+}
 
 int infv_ltm_export_state(infv_ltm_handle h, int32_t layer, float* B, float* bin_mass, void* stream_) {
     if (int rc = check_handle(h)) return rc;

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(kNT) void chain_kernel(ChainArgs a) {
         if (rs.draw_mode == 1)
             dr = draw_load<kNT, 1>(rs.part_prev + (long)l * rs.parts * kBins, rs.parts,
                                    rs.acc_prev ? rs.acc_prev + (long)l * kAccShards * kBins : nullptr, rs.probs_override + l * kBins,
-                                   (rs.override_mask >> l) & 1u, rs.u + (long)l * a.S, a.S);
+                                   (rs.override_mask >> l) & 1u, rs.u ? rs.u + (long)l * a.S : nullptr, a.S, rs.rng, (uint32_t)l);
         if (writer)                                                                  // ring slot of the NEXT launch: idle now
             for (int e = tid; e < kAccShards * kBins; e += kNT) rs.acc_clear[(long)l * kAccShards * kBins + e] = 0ull;
         int uni = -1;

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kBNT) void chain_batch_kernel(ChainBatchArgs a) {
         sn_off[k] = (e < kBRows * rows && qr < valid) ? (int)((long)nr * a.snew_ld + tile + qr) : -1;
         sn_lds[k] = (e < kBRows * rows) ? qr * sn + nr : -1;
     }
-    const double* u_base = a.u + (long)l * a.S + tid;
+    const double* u_base = a.u ? a.u + (long)l * a.S + tid : nullptr;   // nullptr: generated (the handle's device rng)
     const long u_step = (long)a.L * a.S;
     const bool has_u = a.draw_mode == 1 && tid < a.S;
     auto prefetch = [&](int i) {
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kBNT) void chain_batch_kernel(ChainBatchArgs a) {
             }
             sn_reg[k] = v;
         }
-        if (has_u) u_reg = u_base[i * u_step];
+        if (has_u) u_reg = u_base ? u_base[i * u_step] : gibbs_uniform(a.rng, (uint32_t)l, a.rng.pos + (uint32_t)i, (uint32_t)tid);
     };
     prefetch(0);
     __syncthreads();
@@ -360,10 +360,33 @@ __host__ __device__ inline Batch3Smem batch3_smem(int N, int S, int rows, int ta
 __global__ void round_up_uniforms_kernel(const double* __restrict__ u, float* __restrict__ uf, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double x = u[i];
-    float f = (float)x;
-    if ((double)f < x) f = __int_as_float(__float_as_int(f) + 1);
-    uf[i] = f;
+    uf[i] = round_up_f32(u[i]);
+}
+
+// One thread per Philox block: the two uniforms of slots (2 p, 2 p + 1) of (step, layer), as doubles and / or as the fp32
+// round-ups round_up_uniforms_kernel makes of explicit uniforms (the same function of the double: generated and explicit
+// runs search against the same floats).
+__global__ void rng_fill_kernel(RngView rng, int L, int S, long n_pairs, double* __restrict__ u_out, float* __restrict__ uf_out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pairs) return;
+    const int pairs = (S + 1) / 2;
+    const long sl = i / pairs;                                  // step * L + layer
+    const int p = (int)(i - sl * pairs);
+    const long step = sl / L;
+    const int l = (int)(sl - step * L);
+    const Philox4 b = gibbs_block(rng, (uint32_t)l, rng.pos + (uint32_t)step, (uint32_t)p);
+    const double x0 = philox_u53(b.w[0], b.w[1]), x1 = philox_u53(b.w[2], b.w[3]);
+    const long o = sl * S + 2 * p;
+    const bool two = 2 * p + 1 < S;
+    if (u_out != nullptr) { u_out[o] = x0; if (two) u_out[o + 1] = x1; }
+    if (uf_out != nullptr) { uf_out[o] = round_up_f32(x0); if (two) uf_out[o + 1] = round_up_f32(x1); }
+}
+
+hipError_t launch_rng_fill(const RngView& rng, int n_steps, int L, int S, double* u_out, float* uf_out, hipStream_t stream) {
+    const long n_pairs = (long)n_steps * L * ((S + 1) / 2);
+    if (n_pairs <= 0) return hipSuccess;
+    INFV_LAUNCH(rng_fill_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, rng, L, S, n_pairs, u_out, uf_out);
+    return hipGetLastError();
 }
 
 hipError_t launch_round_up_uniforms(const double* u, float* uf, long n, hipStream_t stream) {

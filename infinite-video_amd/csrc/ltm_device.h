@@ -2,6 +2,7 @@
 // whole-video chain kernel (ltm_chain.hip).  All assume 256-thread workgroups (4 waves of 64).
 #pragma once
 #include "ltm_internal.h"
+#include "philox.h"
 #include "wg_stamps.h"
 
 namespace infv {
@@ -102,19 +103,52 @@ struct DrawRegs {
     float ovr[2];        // wave 0: teacher-forced probabilities of those bins (if overriding)
 };
 
+// The uniforms of slots tid + i * NT generated in registers (u == nullptr with the handle's device rng on: philox.h).
+// Threads 2m and 2m + 1 hold the two slots of one Philox block for every i, so with an even SPT the pair shares the work:
+// the even thread computes the blocks of even i, the odd thread those of odd i, and each hands the other its half through
+// one lane exchange -- every block is computed once.  Called by all NT threads (the exchange needs both lanes of a pair).
+template <int NT, int SPT>
+__device__ inline void draw_generate(double (&us)[SPT], int S, const RngView& rng, uint32_t layer) {
+    const int tid = threadIdx.x;
+    if constexpr (SPT % 2 == 0) {
+        static_assert(NT % 2 == 0, "the two slots of a block sit in neighbouring threads");
+        const int odd = tid & 1;
+#pragma unroll
+        for (int i = 0; i < SPT; i += 2) {
+            const int mine = i + odd;                                        // the block this thread computes
+            const Philox4 b = gibbs_block(rng, layer, rng.pos, (uint32_t)((tid + mine * NT) >> 1));
+            const double even_half = philox_u53(b.w[0], b.w[1]), odd_half = philox_u53(b.w[2], b.w[3]);
+            const double keep = odd ? odd_half : even_half;                  // slot tid + mine * NT
+            const double got = __shfl_xor(odd ? even_half : odd_half, 1);    // the partner's block, this thread's half
+            us[i] = odd ? got : keep;
+            us[i + 1] = odd ? keep : got;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < SPT; ++i) us[i] = gibbs_uniform(rng, layer, rng.pos, (uint32_t)(tid + i * NT));
+    }
+#pragma unroll
+    for (int i = 0; i < SPT; ++i)
+        if (tid + i * NT >= S) us[i] = 2.0;
+}
+
 // Phase 1: issue every global read of the draw (uniforms, partial masses) -- no LDS, no barrier.
 // `mass_acc` (fixed-point totals accumulated with integer atomics, exact and order-independent) replaces
-// the per-workgroup float partials when non-null.
+// the per-workgroup float partials when non-null.  u == nullptr: the uniforms are generated (draw_generate).
 template <int NT, int SPT>
 __device__ inline DrawRegs<SPT> draw_load(const float* __restrict__ part, int parts,
                                           const unsigned long long* __restrict__ mass_acc,
                                           const float* __restrict__ probs_override, bool use_override,
-                                          const double* __restrict__ u, int S) {
+                                          const double* __restrict__ u, int S, const RngView& rng, uint32_t layer) {
     constexpr int nb = kBins - 1;
     const int tid = threadIdx.x;
     DrawRegs<SPT> r;
+    if (u != nullptr) {
 #pragma unroll
-    for (int i = 0; i < SPT; ++i) r.us[i] = (tid + i * NT < S) ? u[tid + i * NT] : 2.0;
+        for (int i = 0; i < SPT; ++i) r.us[i] = (tid + i * NT < S) ? u[tid + i * NT] : 2.0;
+    } else {
+        draw_generate<NT, SPT>(r.us, S, rng, layer);
+    }
     r.acc = 0.0;
     r.ovr[0] = r.ovr[1] = 0.f;
     if (use_override) {

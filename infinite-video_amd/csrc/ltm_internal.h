@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "knobs.h"
+#include "philox.h"
 
 namespace infv {
 
@@ -109,6 +110,7 @@ struct StepDraw {
     int n_layers;                   // 0: no draw (first chunk of a document / uniform resampling)
     const float* bin_part; int parts; const float* probs_override; unsigned override_mask; StickyView sticky;
     const double* u; int S; float* probs_out; int32_t* bins_out; int32_t* idx_out; const int32_t* bins_forced; unsigned forced_mask;
+    RngView rng;                    // u == nullptr: the uniforms are generated (philox.h)
     // optional: the resolved gather table of the step, tab_out[l][e] = source box of entry e of slot_tab (-1: none), so that the
     // update kernel reads ONE table row per box instead of chasing old_ptr -> old_slot -> idx
     const int32_t* slot_tab; int tab_entries; int32_t* tab_out;
@@ -116,7 +118,7 @@ struct StepDraw {
 hipError_t launch_draw(const float* bin_part, int parts, const float* probs_override, unsigned override_mask,
                        const StickyView& sticky, const double* u, int S, int n_layers, float* probs,
                        int32_t* bins, int32_t* idx, hipStream_t stream, const int32_t* bins_forced = nullptr,
-                       unsigned forced_mask = 0);
+                       unsigned forced_mask = 0, const RngView& rng = RngView{} /* u == nullptr: generated */);
 
 // next[l][n] = val_n * sum_{slots s of box n} prev[l][idx[l][s]] + new row of box n, for B and [K'|V'].
 hipError_t launch_update(const OperatorView& op, int N, int d, int dm, int n_layers, int S, const int32_t* idx,
@@ -144,6 +146,7 @@ struct ChainRoleS {
     const unsigned long long* acc_prev;           // ... or its fixed-point totals [L][kAccShards][128] (fast path steady state)
     unsigned long long* acc_next; unsigned long long* acc_clear;   // this step's totals; the ring slot to zero for the next
     const float* probs_override; unsigned override_mask; const double* u; const int32_t* uniform_idx;
+    RngView rng;                    // u == nullptr: the uniforms are generated (philox.h)
     float* probs_out; int32_t* bins_out; int32_t* idx_out;     // [L][128], [L][S], [L][S]  (diagnostics)
     float* probs_tr; int32_t* bins_tr;                         // draw trace rows of this chunk ([L][128], [L][S]) or nullptr
     int32_t* tab_out;               // [L][N*tabw] resolved source box of every (box, slot) for role U
@@ -180,6 +183,7 @@ struct ChainBatchArgs {
     int expect_extra;               // fault injection (tests): arrivals expected beyond the launch's workgroups
     const float* probs_override; unsigned override_mask;     // teacher forcing of step 0
     const double* u;                // [n_steps][L][S]
+    RngView rng;                    // u == nullptr: chain_batch_kernel generates them, step i at position rng.pos + i
     const float* uf;                // chain_batch3_kernel: the same uniforms as fp32 round-ups (launch_round_up_uniforms), or nullptr
     const int32_t* uniform_idx;
     float* probs_out; int32_t* bins_out; int32_t* idx_out;    // diagnostics of the last step
@@ -201,6 +205,9 @@ bool chain_batch_supported(int N, int S, int rows, int tabw, int n_blocks);
 bool chain_batch2_applies(const ChainBatchArgs& a);        // the launch will run chain_batch3_kernel (scores rebuilt by alpha_rows2)
 bool chain_batch3_shape_ok(int draw_mode, int points_ok, int rows, int S, int Q);   // the shape runs chain_batch3_kernel (needs ChainBatchArgs.uf)
 hipError_t launch_round_up_uniforms(const double* u, float* uf, long n, hipStream_t stream);   // uf[i] = smallest float >= u[i]
+// The generator as a pass of its own: u[n_steps][L][S] of steps rng.pos .. rng.pos + n_steps - 1 (wrapping), as doubles (u_out)
+// and / or as the same fp32 round-ups launch_round_up_uniforms makes of them (uf_out); either may be null.
+hipError_t launch_rng_fill(const RngView& rng, int n_steps, int L, int S, double* u_out, float* uf_out, hipStream_t stream);
 int chain_batch_blocks(int H, int Q, int L, int draw_mode, int points_ok, int rows, int S);   // workgroups of the launch for this shape
 // the chunk-parallel half of chain_batch3_kernel: full score rows from the published point scores + drawn bins, then alpha
 struct AlphaRows2Args {
@@ -293,6 +300,7 @@ struct VideoDesc {
     int cur0;
     unsigned override_mask, forced_mask;
     int parts0;                       // partial rows per layer of bin_part at the video's first draw
+    RngView rng;                      // the handle's device rng (u == nullptr); rng.pos = the handle's position at the call's start
 };
 // Step s of a multi-video call: the videos still running are ranks [0, n) of the table (sorted by decreasing length), and
 // video rank j's chunk of this step sits in slot j of the step's workspaces (pooled frames, projected rows).

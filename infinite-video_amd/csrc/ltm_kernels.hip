@@ -606,7 +606,8 @@ __global__ __launch_bounds__(256) void step_project_kernel(RowsA ra, int M, int 
         float* cdf = smem + 512 + 1024;                                  // [kBins]
         const bool ovr = (dr.override_mask >> l) & 1u;
         const DrawRegs<4> r = draw_load<256, 4>(dr.bin_part + (long)l * dr.parts * kBins, dr.parts, nullptr,
-                                                dr.probs_override + l * kBins, ovr, dr.u + (long)l * dr.S, dr.S);
+                                                dr.probs_override + l * kBins, ovr, dr.u ? dr.u + (long)l * dr.S : nullptr, dr.S,
+                                                dr.rng, (uint32_t)l);
         draw_finish<256, 4>(r, ovr, dr.sticky.bin_box, dr.S, cdf, sidx, gsum, dr.probs_out + l * kBins, dr.bins_out + (long)l * dr.S,
                             dr.idx_out + (long)l * dr.S, nullptr, ((dr.forced_mask >> l) & 1u) ? dr.bins_forced + (long)l * dr.S : nullptr);
         // resolved gather table for the update kernel (draw_finish ends with a barrier: sidx holds every slot's source box)
@@ -996,24 +997,25 @@ __global__ __launch_bounds__(256) void draw_kernel(const float* __restrict__ bin
                                                    const double* __restrict__ u, int S,
                                                    float* __restrict__ probs_out, int32_t* __restrict__ bins_out,
                                                    int32_t* __restrict__ idx_out,
-                                                   const int32_t* __restrict__ bins_forced, unsigned forced_mask) {
+                                                   const int32_t* __restrict__ bins_forced, unsigned forced_mask, RngView rng) {
     __shared__ float cdf[kBins];
     __shared__ double gsum[256];
     __shared__ int32_t sidx[kMaxSamples];
     const int l = blockIdx.x;
     const bool ovr = (override_mask >> l) & 1u;
     const DrawRegs<4> r = draw_load<256, 4>(bin_part + (long)l * parts * kBins, parts, nullptr, probs_override + l * kBins,
-                                            ovr, u + (long)l * S, S);
+                                            ovr, u ? u + (long)l * S : nullptr, S, rng, (uint32_t)l);
     draw_finish<256, 4>(r, ovr, sticky.bin_box, S, cdf, sidx, gsum, probs_out + l * kBins, bins_out + (long)l * S,
                         idx_out + (long)l * S, nullptr, ((forced_mask >> l) & 1u) ? bins_forced + (long)l * S : nullptr);
 }
 
 hipError_t launch_draw(const float* bin_part, int parts, const float* probs_override, unsigned override_mask,
                        const StickyView& sticky, const double* u, int S, int n_layers, float* probs,
-                       int32_t* bins, int32_t* idx, hipStream_t stream, const int32_t* bins_forced, unsigned forced_mask) {
+                       int32_t* bins, int32_t* idx, hipStream_t stream, const int32_t* bins_forced, unsigned forced_mask,
+                       const RngView& rng) {
     if (S > kMaxSamples) return hipErrorInvalidValue;          // (infv_ltm_create refuses such a handle)
     INFV_LAUNCH(draw_kernel, dim3(n_layers), dim3(256), 0, stream, bin_part, parts, probs_override,
-                       override_mask, sticky, u, S, probs, bins, idx, bins_forced, forced_mask);
+                       override_mask, sticky, u, S, probs, bins, idx, bins_forced, forced_mask, rng);
     return hipGetLastError();
 }
 
@@ -1591,8 +1593,10 @@ __global__ __launch_bounds__(256) void draw_videos_kernel(VideoStep vs, int part
         if (v->trace_bins != nullptr) bins_tr = v->trace_bins + ((long)vs.s * n_layers + l) * S;
     }
     if (first) parts = v->parts0;                 // (left by whatever stepped the memory last)
+    RngView rng = v->rng;                         // the video's own stream, at its own position
+    rng.pos += (uint32_t)vs.s;
     const DrawRegs<4> r = draw_load<256, 4>(v->bin_part + (long)l * parts * kBins, parts, nullptr, v->probs_override + l * kBins,
-                                            ovr, u + (chunk * n_layers + l) * S, S);
+                                            ovr, u ? u + (chunk * n_layers + l) * S : nullptr, S, rng, (uint32_t)l);
     draw_finish<256, 4>(r, ovr, sticky.bin_box, S, cdf, sidx, gsum, v->probs + l * kBins, v->bins + (long)l * S,
                         v->idx + (long)l * S, nullptr, frc ? v->bins_forced + (long)l * S : nullptr, probs_tr, bins_tr);
 }

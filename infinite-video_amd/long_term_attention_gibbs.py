@@ -99,17 +99,36 @@ class LongTermAttention(nn.Module):
         eng = self._engine
         if eng is None or eng.device != device or eng.max_q < Q:
             carried = None
+            pos = 0
             if eng is not None and eng.has_memory:
                 if eng.device != device:
                     raise RuntimeError("LongTermAttention moved device mid-document")
                 carried = eng.export_state(0)             # a longer query mid-document: carry the memory into a larger engine
+                pos = eng.rng_position
             self._engine = eng = LTMEngine(
                 self.attn_num_basis, self.n_head, self.head_size, self.encoder_width, self.tokens_per_frame,
                 tau=self.tau, sticky=bool(self.sticky_memories), n_layers=1, max_q=max(Q, 32), device=device,
                 nb_samples=self.nb_samples)
             if carried is not None:
                 eng.import_state(0, carried[0].contiguous(), carried[1].contiguous(), self._proj(device))
+                eng.rng_position = pos                    # (import_state leaves the position alone: the document goes on)
+            rng = getattr(self, "_device_rng", None)
+            if rng is not None:
+                eng.set_device_rng(*rng)
         return eng
+
+    def use_device_rng(self, seed: Optional[int], stream: int = 0):
+        """Draw the Gibbs uniforms on the device (``LTMEngine.set_device_rng``) instead of from torch's global CPU generator:
+        ``forward`` then hands the step no uniforms, consumes nothing from the global generator and never builds the pinned
+        ring.  The draws of a document depend on ``(seed, stream)`` and its content only (:204-206 on a CUDA device draws
+        from torch's Philox device generator in the same spirit).  ``seed=None`` turns it off again.  Off by default: the
+        CPU-generator order is what reproduces a reference CPU run draw for draw."""
+        self._device_rng = None if seed is None else (int(seed), int(stream))
+        if self._engine is not None:
+            if seed is None:
+                self._engine.clear_device_rng()
+            else:
+                self._engine.set_device_rng(int(seed), int(stream))
 
     def _proj(self, device):
         # the borrowed key/value Linear layers rarely change between calls: reuse the fp32 views while the parameters are the
@@ -270,8 +289,8 @@ class LongTermAttention(nn.Module):
         stream = C.c_void_p(_raw_stream(dev_index))
         other_device = _cur_device() != dev_index
         # torch.multinomial on the CPU path draws its uniforms from the global CPU generator
-        sticky_step = eng.has_memory and self.sticky_memories
-        u_addr = self._draw_uniforms(k.device) if sticky_step else 0
+        sticky_step = eng.has_memory and self.sticky_memories and getattr(self, "_device_rng", None) is None
+        u_addr = self._draw_uniforms(k.device) if sticky_step else 0    # (device rng: no uniforms, the kernels generate them)
         qf = q.detach()
         if qf.dtype != torch.float32 or not qf.is_contiguous():
             qf = qf.float().contiguous()

@@ -219,16 +219,31 @@ def _dev_tokens(t: torch.Tensor, device: torch.device):
 class VideoMemory:
     """One video's long-term memories for :meth:`InfVideoEncoder.encode_videos`: one one-layer ``LTMEngine`` per
     cross-attention layer, created as ``LongTermAttention._get_engine`` creates the model's own.  ``export_state(l)`` and
-    ``last_draw(l)`` read layer l's memory."""
+    ``last_draw(l)`` read layer l's memory.  ``video_id`` names the video's device-rng streams
+    (:meth:`InfVideoEncoder.use_device_rng`): layer l draws from stream ``(video_id + 1) * n_layers + l``."""
 
-    def __init__(self, model: "InfVideoEncoder", device: torch.device):
+    def __init__(self, model: "InfVideoEncoder", device: torch.device, video_id: int = 0):
         from .engine import LTMEngine
         Q = model.num_video_query_token
         self.device = device
+        self.video_id = int(video_id)
         self.engines = [LTMEngine(m.attn_num_basis, m.n_head, m.head_size, m.encoder_width, m.tokens_per_frame, tau=m.tau,
                                   sticky=bool(m.sticky_memories), n_layers=1, max_q=max(Q, 32), device=device,
                                   nb_samples=m.nb_samples)
                         for m in model.video_Qformer.ltm_modules]
+        self.set_device_rng(getattr(model, "_device_rng_seed", None))
+
+    def set_device_rng(self, seed: Optional[int], video_id: Optional[int] = None):
+        """Device rng of this video's memories: seed (None = off) and, optionally, a new ``video_id``."""
+        if video_id is not None:
+            self.video_id = int(video_id)
+        n = len(self.engines)
+        for l, eng in enumerate(self.engines):
+            if seed is None:
+                if eng.rng_seed is not None:
+                    eng.clear_device_rng()
+            elif (eng.rng_seed, eng.rng_stream) != (int(seed), (self.video_id + 1) * n + l):
+                eng.set_device_rng(seed, (self.video_id + 1) * n + l)
 
     @property
     def has_memory(self) -> bool:
@@ -332,6 +347,20 @@ class InfVideoEncoder(nn.Module):
         self.exact_fp32 = False        # True: exact-fp32 MFMA for the short-term attention instead of split-bf16
         self.last_hidden: Optional[torch.Tensor] = None
         self._video_memories: List[VideoMemory] = []      # encode_videos' reused pool (memories=None)
+        self._device_rng_seed: Optional[int] = None
+
+    def use_device_rng(self, seed: Optional[int]):
+        """Draw every Gibbs uniform of the encoder on the device (``LTMEngine.set_device_rng``): with ``u=None`` no uniforms are
+        drawn or copied on the host in ``encode_frames``, ``encode_frames_batch``, ``encode_videos`` and
+        ``encode_long_videos``, and torch's global generator is left alone.  The model's own memories draw from streams
+        ``l`` (layer index); a :class:`VideoMemory` of video id ``v`` from ``(v + 1) * n_layers + l``, so a video's result
+        depends on ``(seed, video id)`` and its frames only -- not on its place in a batch or on what was encoded before.
+        An explicit ``u`` still wins.  ``seed=None`` restores the CPU-generator default."""
+        self._device_rng_seed = None if seed is None else int(seed)
+        for l, m in enumerate(self.video_Qformer.ltm_modules):
+            m.use_device_rng(self._device_rng_seed, l)
+        for mem in self._video_memories:
+            mem.set_device_rng(self._device_rng_seed)
 
     # ------------------------------------------------------------------ weights
     def load_reference_state_dict(self, sd: dict, strict: bool = True):
@@ -496,7 +525,9 @@ class InfVideoEncoder(nn.Module):
                 eng.ensure_plan(T)
                 handles[l] = eng._h
                 need_u = need_u or (eng.has_memory and not new_video and bool(m.sticky_memories))
-            if u is None and need_u:
+            if memory is not None:
+                memory.set_device_rng(self._device_rng_seed)
+            if u is None and need_u and self._device_rng_seed is None:
                 draws = []
                 for _ in range(cfg.num_hidden_layers):
                     draws.append(torch.rand(NB_SAMPLES, dtype=torch.float64))
@@ -555,7 +586,7 @@ class InfVideoEncoder(nn.Module):
                 had_memory = had_memory or eng.has_memory
                 m.count += Cn
             sticky = bool(self.video_Qformer.ltm_modules[0].sticky_memories)
-            if u is None and sticky:
+            if u is None and sticky and self._device_rng_seed is None:
                 first_draws = 0 if (had_memory and not new_video) else 1      # chunk 0 of a new video resamples nothing
                 u = torch.zeros(Cn, Ln, NB_SAMPLES, dtype=torch.float64)
                 for c in range(first_draws, Cn):
@@ -582,7 +613,8 @@ class InfVideoEncoder(nn.Module):
 
     # ------------------------------------------------------------------ many videos, layer-major, one call
     def encode_videos(self, frames, chunk_counts=None, new_video: bool = True, u: Optional[torch.Tensor] = None,
-                      want_hidden: bool = False, memories: Optional[Sequence["VideoMemory"]] = None):
+                      want_hidden: bool = False, memories: Optional[Sequence["VideoMemory"]] = None,
+                      video_ids: Optional[Sequence[int]] = None):
         """Many videos through the video Q-former in ONE C call (``infv_vqf_encode_videos``): ``encode_frames_batch``'s
         layer-major schedule over the chunks of every video, each video's long-term memories in its own
         :class:`VideoMemory` (``memories[v]``; by default a reused pool of the encoder, the model's own memory untouched).
@@ -592,7 +624,9 @@ class InfVideoEncoder(nn.Module):
         or None).  A video's outputs and memories do not depend on the rest of the batch (bit for bit); they agree with
         ``encode_frames_batch`` on that video to fp32 rounding.  ``u`` [sum C_v, n_layers, 512] float64; by default drawn
         from torch's global CPU generator video by video, in the order looping ``encode_frames_batch`` over the videos
-        would draw it (chunk 0 of a new video draws nothing)."""
+        would draw it (chunk 0 of a new video draws nothing).  With :meth:`use_device_rng` and ``u=None`` nothing is drawn on the
+        host: video v's memories draw from the streams of ``video_ids[v]`` (default: v, its index in the call) -- pass stable
+        ids to make a video's result independent of its place in the batch."""
         if isinstance(frames, (list, tuple)):
             if chunk_counts is None:
                 chunk_counts = [int(f.size(0)) for f in frames]
@@ -627,7 +661,12 @@ class InfVideoEncoder(nn.Module):
                 for l, eng in enumerate(mem.engines):
                     eng.ensure_plan(T)
                     handles[v * Ln + l] = eng._h
-            if u is None and bool(self.video_Qformer.ltm_modules[0].sticky_memories):
+            if video_ids is not None and len(video_ids) != V:
+                raise ValueError(f"{len(video_ids)} video_ids for {V} videos")
+            for v, mem in enumerate(memories):
+                mem.set_device_rng(self._device_rng_seed, (video_ids[v] if video_ids is not None else v)
+                                   if self._device_rng_seed is not None else None)
+            if u is None and self._device_rng_seed is None and bool(self.video_Qformer.ltm_modules[0].sticky_memories):
                 u = draw_video_uniforms(counts, [not new_video and mem.has_memory for mem in memories], Ln)
             if u is not None:
                 u = u.to(device=device, dtype=torch.float64).contiguous()
@@ -721,16 +760,21 @@ def split_long_videos(frame_counts: Sequence[int], max_int: int) -> List[Tuple[i
 
 
 def encode_long_videos(model: InfVideoEncoder, videos: Sequence[torch.Tensor], max_int: int,
-                       u_of_chunk=None) -> List[Tuple[torch.Tensor, List[torch.Tensor]]]:
+                       u_of_chunk=None, video_ids: Optional[Sequence[int]] = None) -> List[Tuple[torch.Tensor, List[torch.Tensor]]]:
     """``encode_long_video`` over many videos (``videos[v]``: [F_v, P, d] frame-token blocks): the full-length chunks of ALL
     videos go through one :meth:`InfVideoEncoder.encode_videos` call, then each ragged tail through the per-chunk path on its
     video's memory.  Returns per video ``encode_long_video``'s (mean [1, Q, llama], per-chunk list).
     ``u_of_chunk(v, i)`` gives chunk i of video v its uniforms [n_layers, 512]; with None they come from torch's global CPU
     generator, drawn video-major first, so that the generator is consumed exactly as
-    ``for v: encode_long_video(model, videos[v], max_int, batched=True)`` consumes it."""
+    ``for v: encode_long_video(model, videos[v], max_int, batched=True)`` consumes it.  With ``model.use_device_rng`` and no
+    ``u_of_chunk`` nothing is drawn on the host: video v draws from the streams of ``video_ids[v]`` (default v), the ragged
+    tail from the same streams at the position its full chunks left."""
     videos = list(videos)
     if not videos:
         raise ValueError("encode_long_videos needs at least one video")
+    if video_ids is not None and len(video_ids) != len(videos):
+        raise ValueError(f"{len(video_ids)} video_ids for {len(videos)} videos")
+    device_rng = model._device_rng_seed is not None
     cfg = model.video_Qformer.config
     Ln = cfg.num_hidden_layers
     sticky = cfg.alpha != 1.0 and bool(model.video_Qformer.ltm_modules[0].sticky_memories)
@@ -741,18 +785,20 @@ def encode_long_videos(model: InfVideoEncoder, videos: Sequence[torch.Tensor], m
         rows = [torch.as_tensor(u_of_chunk(v, i), dtype=torch.float64) for v, n in enumerate(n_full) for i in range(n)]
         u_full = torch.stack(rows) if rows else None
         u_tail = [torch.as_tensor(u_of_chunk(v, n_full[v]), dtype=torch.float64) if t else None for v, (_, t) in enumerate(split)]
-    elif sticky:
+    elif sticky and not device_rng:
         parts = []
         for v, (n, t) in enumerate(split):
             parts.append(draw_video_uniforms([n], [False], Ln))
             if t and n > 0:                                   # the tail continues the memory: it resamples
                 u_tail[v] = draw_video_uniforms([2], [False], Ln)[1]
         u_full = torch.cat(parts)
+    # (only videos with a full chunk enter encode_videos: their ids travel with them)
+    ids_full = [(video_ids[v] if video_ids is not None else v) for v, n in enumerate(n_full)]
     results: List[Tuple[torch.Tensor, List[torch.Tensor]]] = []
     llama = means = None
     if sum(n_full):
         frames = torch.cat([x[:n * max_int].reshape(n, max_int * x.size(1), x.size(-1)) for x, n in zip(videos, n_full)])
-        llama, means, _ = model.encode_videos(frames, n_full, new_video=True, u=u_full)
+        llama, means, _ = model.encode_videos(frames, n_full, new_video=True, u=u_full, video_ids=ids_full)
     lib = _lib.load()
     row = 0
     for v, (x, (n, t)) in enumerate(zip(videos, split)):
@@ -761,6 +807,8 @@ def encode_long_videos(model: InfVideoEncoder, videos: Sequence[torch.Tensor], m
         if t:
             blk = x[n * max_int:]
             mem = _pool_memory(model, v, x.device) if cfg.alpha != 1.0 else None      # (what encode_videos just stepped)
+            if mem is not None and device_rng:
+                mem.set_device_rng(model._device_rng_seed, ids_full[v])
             _, emb = model.encode_frames(blk.reshape(1, -1, blk.size(-1)), new_video=(n == 0), u=u_tail[v], memory=mem)
             embs.append(emb)
         if not t:

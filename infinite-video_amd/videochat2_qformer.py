@@ -184,6 +184,12 @@ class VideoChat2Encoder(nn.Module):
         self._vqf = None
         self._vqf_dev = None
 
+    def use_device_rng(self, seed: Optional[int]):
+        """Draw the Gibbs uniforms of every cross-attention's memory on the device (``LongTermAttention.use_device_rng``): the
+        i-th LTM instance draws from stream ``i``; torch's global generator is left alone.  ``seed=None`` turns it off."""
+        for i, m in enumerate(self.qformer.ltm_modules):
+            m.use_device_rng(seed, i)
+
     # ------------------------------------------------------------------ weights
     def load_reference_state_dict(self, sd: dict, strict: bool = True):
         """``sd`` under the reference's names: ``bert.encoder.layer.*``, ``query_tokens`` (query + extra query tokens
