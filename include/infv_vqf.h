@@ -140,6 +140,77 @@ int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_
                            const void* frames, int32_t T, const infv_vqf_weights* w, const double* u,
                            int32_t new_video, float* hidden_out, float* llama_out, float* llama_mean, void* stream);
 
+/* ---- VideoChat2 Q-former (infty-VideoChat2/models/blip2/Qformer.py): query tokens + instruction text tokens ---- */
+
+#define INFV_VQF_VC_MAX_LAYERS 24
+#define INFV_VQF_VC_MAX_TOKENS 608   /* 96 query tokens + max_txt_len = 512 instruction tokens */
+
+/* Self-attention over the query + text tokens of nb chunks (Qformer.py:232-300 with all-ones masks, eval mode), the building
+ * block beside infv_vqf_short_attention:  ctx = softmax(q k^T / sqrt(64)) v  per head of the handle's n_heads.
+ *   qkv     [nb][n_max][3 * hidden]  query | key | value of every token, bias applied (device)
+ *   n_valid HOST int32[nb], each in 1..n_max: chunk b attends over its first n_valid[b] tokens; NULL = n_max everywhere
+ *   ctx     [nb][n_max][hidden]      rows at or beyond n_valid[b] are written as zeros
+ * n_max <= INFV_VQF_VC_MAX_TOKENS (INFV_ERR_UNSUPPORTED above).  Keys at or beyond n_valid[b] are never read.  Arithmetic is
+ * fp32 FMA; the summation order of an output element depends on its chunk's n_valid alone, so a chunk's result is the same
+ * bits whatever else is in the call.  Row tiles of 32 go across workgroups (grid: head x chunk x row tile). */
+int infv_vqf_self_attention(infv_vqf_handle h, const float* qkv, int32_t nb, int32_t n_max, const int32_t* n_valid,
+                            float* ctx, void* stream);
+
+/* One BertLayer of the VideoChat2 Q-former (Qformer.py:419-505): self-attention over query + text tokens (:195-310, :320-324),
+ * cross-attention of the query part in every cross_attention_freq-th layer (:463-481), the query FFN and the text FFN
+ * (:483-496).  The x_* members are read only when has_cross is set. */
+typedef struct {
+    infv_linear self_q, self_k, self_v, self_o;   infv_layernorm self_ln;    /* layer.attention                      */
+    int32_t has_cross;                                                        /* layer.has_cross_attention            */
+    int32_t reserved;                                                         /* 0                                    */
+    infv_linear x_q, x_k, x_v, x_o;               infv_layernorm x_ln;       /* layer.crossattention                 */
+    infv_linear q_ffn_in, q_ffn_out;              infv_layernorm q_ffn_ln;   /* intermediate_query / output_query    */
+    infv_linear t_ffn_in, t_ffn_out;              infv_layernorm t_ffn_ln;   /* intermediate / output (text rows)    */
+} infv_vqf_vc_layer;
+
+typedef struct {
+    int32_t n_layers;                    /* 1..INFV_VQF_VC_MAX_LAYERS (Qformer.py:544-640: the encoder loop; 12) */
+    int32_t reserved;                    /* 0 */
+    const infv_vqf_vc_layer* layers;     /* HOST array [n_layers] */
+    infv_linear mistral_proj;            /* videochat2_it_mistral.py:252; w == NULL: absent (proj_out / proj_mean must be NULL) */
+} infv_vqf_vc_weights;
+
+/* The VideoChat2 Q-former over the packed chunks of V >= 1 videos, layer-major (the device side of encode_img after the
+ * vision encoder, videochat2_it_mistral.py:199-252, inside the eval loop of eval_code/run_nextqa_mistral.py:141-152; one video
+ * is V = 1).  The handle's config gives n_heads, hidden, inter, enc_width, tokens_per_frame, n_query, proj_out, nb_samples,
+ * alpha and ln_eps; its n_layers is not read (the weights carry the layer count).  n_cross = number of layers with has_cross.
+ *   ltm        [V][n_cross] one-layer LTM handles, video-major, all distinct (NULL when alpha == 1)
+ *   cu         HOST [V+1], cu[0] = 0, non-decreasing: video v owns chunks [cu[v], cu[v+1])
+ *   frames     [cu[V]][T * tokens_per_frame][enc_width] fp32
+ *   hidden_in  the encoder input rows of every video, packed: video v's [n_query + text_len[v]][hidden] (query rows first)
+ *              start at row  sum_{w<v} (n_query + text_len[w]);  every chunk of a video starts from the same rows
+ *   text_len   HOST [V], each >= 0 with n_query + text_len[v] <= INFV_VQF_VC_MAX_TOKENS
+ *   u          [cu[V]][n_cross][nb_samples] float64, or NULL under infv_vqf_encode_videos's rules (not sticky; every video new
+ *              with one chunk; the device rng of every memory on)
+ *   new_video  1 starts every memory afresh, 0 continues each video's memories
+ *   hidden_out last hidden states, packed per CHUNK: chunk c of video v holds n_query + text_len[v] rows (query rows first)
+ *              starting at row  sum over earlier chunks of their row counts        (may be NULL)
+ *   proj_out   [cu[V]][n_query][proj_out] mistral_proj of the query rows           (may be NULL)
+ *   proj_mean  [V][n_query][proj_out] per-video mean over its chunks (run_nextqa_mistral.py:150), undefined for a video
+ *              without chunks                                                        (may be NULL)
+ * Schedule: every chunk's frames are pooled once (all cross layers step from that one copy) and split once into the bf16
+ * operands of the short-term attention when they fit INFV_VQF_SPLIT_CACHE_GB; per layer, over all packed chunks, the QKV
+ * projection, infv_vqf_self_attention's kernel, output dense + LayerNorm; on cross layers the cross query, that layer's V
+ * memories through infv_ltm_steps_videos with per-chunk queries on the shared worker stream while the caller's stream runs the
+ * short-term attention, the merge and its output block; then the query FFN on the query rows and the text FFN on the text
+ * rows (text rows are kept packed: no padding enters any kernel); last mistral_proj and the per-video means.
+ * BATCH INVARIANCE as in infv_vqf_encode_videos: a video's hidden rows, projected rows, mean and memories (B, bin masses,
+ * draws, probabilities) are the same bits whatever else is in the call, at whatever position, whatever the neighbours' text
+ * lengths, and whether its chunks come in one call or in two (new_video = 0 on the second).  Values agree with the per-chunk
+ * binding to fp32 rounding.  Token counts that are a multiple of 32 but not of 64 take the exact-fp32 contractions.
+ * Refused before any device work or memory change: bad cu, a null or repeated LTM handle, negative text_len (INFV_ERR_INVALID);
+ * n_query + text_len[v] > 608, n_layers > 24, T * tokens_per_frame not a multiple of 32, bf16 tokens set on the handle
+ * (INFV_ERR_UNSUPPORTED). */
+int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+                              int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len,
+                              const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
+                              void* stream);
+
 /* out[i] = mean over n of in[n][i]  (the eval loop's mean over chunk embeddings,
  * run_inference_inf_video_llama_nextqa.py:194) */
 int infv_vqf_mean(const float* in, int32_t n, int64_t elems, float* out, void* stream);

@@ -95,6 +95,23 @@ class VqfWeights(C.Structure):
                 ("llama_proj", Linear)]
 
 
+class VqfVcLayer(C.Structure):
+    """infv_vqf_vc_layer: one BertLayer of the VideoChat2 Q-former (query + text tokens, optional cross-attention)."""
+    _fields_ = [("self_q", Linear), ("self_k", Linear), ("self_v", Linear), ("self_o", Linear), ("self_ln", LayerNorm),
+                ("has_cross", C.c_int32), ("reserved", C.c_int32),
+                ("x_q", Linear), ("x_k", Linear), ("x_v", Linear), ("x_o", Linear), ("x_ln", LayerNorm),
+                ("q_ffn_in", Linear), ("q_ffn_out", Linear), ("q_ffn_ln", LayerNorm),
+                ("t_ffn_in", Linear), ("t_ffn_out", Linear), ("t_ffn_ln", LayerNorm)]
+
+
+class VqfVcWeights(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("reserved", C.c_int32), ("layers", C.POINTER(VqfVcLayer)), ("mistral_proj", Linear)]
+
+
+VC_MAX_LAYERS = 24
+VC_MAX_TOKENS = 608
+
+
 class LTMError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"infv_ltm error {code}: {msg}")
@@ -170,6 +187,10 @@ _SIGNATURES = {
     "infv_vqf_encode_videos": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                          C.POINTER(VqfWeights), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "infv_vqf_self_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infv_vqf_vc_encode_videos": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.POINTER(VqfVcWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "infv_vqf_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 KERNELS = ("pool", "rows", "project", "draw", "update", "attend", "scores", "chain", "uc")

@@ -29,6 +29,7 @@ struct infv_vqf_s {
     double split_cache_gb = 64.0;                       // budget for a whole video's split tokens (INFV_VQF_SPLIT_CACHE_GB at create)
     // whole-video (layer-major) path
     DeviceBuf vA, v1, v2, vxq, valong, vshort, vmerged, vqkv, vsa, vinter, vu, vkbar, v_h1s, v_xqs;
+    DeviceBuf tA, t1, tqkv, tsa, tinter;                // packed text rows of the VideoChat2 path (infv_vqf_vc_encode_videos)
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
     ~infv_vqf_s() {
@@ -482,6 +483,38 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
     return INFV_OK;
 }
 
+// chunks per sub-batch of the short-term attention of a layer-major call over C chunks
+static int pick_short_nb(const infv_vqf_s* h, int C, int n_tokens) {
+    const infv_vqf_config& c = h->cfg;
+    const int Q = c.n_query;
+    int NB = C;
+    if (C > 8) {
+        auto fill = [](long wgs) { return (double)wgs / (double)(((wgs + 255) / 256) * 256); };
+        // with the 384 x 256 kernel (split path, whole tiles): workgroups of the scores contraction, and of the read-out with the
+        // split-K count that fills best -- both should come out as whole rounds (headline: 32 chunks = 1024 and 96 x 8)
+        const long ts = split_path(h, n_tokens) ? split_gemm_wide_tile_count(c.n_heads * Q, n_tokens) : 0;
+        const long tr = split_path(h, n_tokens) ? split_gemm_wide_tile_count(c.n_heads * Q, c.enc_width) : 0;
+        const int tiles = ((c.n_heads * Q + 127) / 128) * ((c.enc_width + 127) / 128);
+        double best = -1.0;
+        for (int nb = 8; nb <= 32 && nb <= C; ++nb) {
+            double eff;
+            if (ts > 0 && tr > 0) {
+                double er = 0.0;
+                for (int sk = 1; sk <= 16; ++sk) er = std::max(er, fill(tr * nb * sk) - 0.004 * sk);
+                eff = 0.5 * (fill(ts * nb) + er);
+            } else {
+                eff = fill((long)tiles * nb);
+            }
+            if (eff >= best - 1e-9) { best = eff; NB = nb; }
+        }
+    }
+    {
+        static const int nb_env = [] { const char* e = exp_env("INFV_VQF_NB"); return e ? atoi(e) : 0; }();   // (sweeps)
+        if (nb_env > 0) NB = nb_env < C ? nb_env : C;
+    }
+    return NB;
+}
+
 // The layer-major body of infv_vqf_encode_video (multi = false: one video, ltm [n_layers]) and infv_vqf_encode_videos (multi:
 // V videos packed by the host array cu, ltm [V][n_layers]; every choice that shapes a GEMM or contraction is taken from
 // per-chunk quantities or constants, and each layer's memories step through infv_ltm_steps_videos).
@@ -513,31 +546,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     // chunks per sub-batch of the short-term attention: the second contraction has few, long tiles per chunk
     // (rows/128 x d/128 = 18 at the headline shape, K = T*P), so pick the count whose tile total fills whole rounds
     // of the 256 CUs (16 chunks = 288 tiles ran at 56 % of 14 chunks' rate per tile)
-    int NB = C;
-    if (C > 8) {
-        auto fill = [](long wgs) { return (double)wgs / (double)(((wgs + 255) / 256) * 256); };
-        // with the 384 x 256 kernel (split path, whole tiles): workgroups of the scores contraction, and of the read-out with the
-        // split-K count that fills best -- both should come out as whole rounds (headline: 32 chunks = 1024 and 96 x 8)
-        const long ts = split_path(h, n_tokens) ? split_gemm_wide_tile_count(c.n_heads * Q, n_tokens) : 0;
-        const long tr = split_path(h, n_tokens) ? split_gemm_wide_tile_count(c.n_heads * Q, c.enc_width) : 0;
-        const int tiles = ((c.n_heads * Q + 127) / 128) * ((c.enc_width + 127) / 128);
-        double best = -1.0;
-        for (int nb = 8; nb <= 32 && nb <= C; ++nb) {
-            double eff;
-            if (ts > 0 && tr > 0) {
-                double er = 0.0;
-                for (int sk = 1; sk <= 16; ++sk) er = std::max(er, fill(tr * nb * sk) - 0.004 * sk);
-                eff = 0.5 * (fill(ts * nb) + er);
-            } else {
-                eff = fill((long)tiles * nb);
-            }
-            if (eff >= best - 1e-9) { best = eff; NB = nb; }
-        }
-    }
-    {
-        static const int nb_env = [] { const char* e = exp_env("INFV_VQF_NB"); return e ? atoi(e) : 0; }();   // (sweeps)
-        if (nb_env > 0) NB = nb_env < C ? nb_env : C;
-    }
+    const int NB = pick_short_nb(h, C, n_tokens);
     {
         const size_t act = (size_t)M * Hd * sizeof(float);
         bool grow = act > h->vA.bytes || (size_t)RB * Q * 3 * Hd * sizeof(float) > h->vqkv.bytes ||
@@ -785,6 +794,282 @@ int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_
     }
     if (!frames) return fail(INFV_ERR_INVALID, "encode_videos: null frames");
     return encode_impl(h, ltm, frames, cu[V], T, w, u, new_video, hidden_out, llama_out, llama_mean, stream_, V, cu, true);
+}
+
+int infv_vqf_self_attention(infv_vqf_handle h, const float* qkv, int32_t nb, int32_t n_max, const int32_t* n_valid,
+                            float* ctx, void* stream) {
+    if (!h || !qkv || !ctx || nb < 0 || n_max < 1) return fail(INFV_ERR_INVALID, "self_attention: bad arguments");
+    if (n_max > INFV_VQF_VC_MAX_TOKENS)
+        return fail(INFV_ERR_UNSUPPORTED, "self_attention: %d tokens, at most %d are supported", n_max, INFV_VQF_VC_MAX_TOKENS);
+    if (nb == 0) return INFV_OK;
+    std::vector<int32_t> nv(nb, n_max);
+    if (n_valid)
+        for (int b = 0; b < nb; ++b) {
+            if (n_valid[b] < 1 || n_valid[b] > n_max)
+                return fail(INFV_ERR_INVALID, "self_attention: n_valid[%d] = %d outside 1..n_max = %d", b, n_valid[b], n_max);
+            nv[b] = n_valid[b];
+        }
+    VcAttn a{};
+    a.qkv0 = qkv; a.rows0 = n_max; a.nsplit = n_max; a.qkv1 = qkv; a.ctx0 = ctx; a.ctx1 = ctx; a.H = h->cfg.n_heads; a.n_alloc = n_max;
+    HIP_TRY(launch_qf_vc_self_attention(a, nb, nv.data(), nullptr, static_cast<hipStream_t>(stream)));
+    return INFV_OK;
+}
+
+int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+                              int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len,
+                              const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
+                              void* stream_) {
+    // ---- validation before any device work or memory change ----
+    if (!h || !cu || !w || !text_len || V < 0) return fail(INFV_ERR_INVALID, "vc_encode_videos: bad arguments");
+    if (V == 0) return INFV_OK;
+    const infv_vqf_config& c = h->cfg;
+    if (cu[0] != 0) return fail(INFV_ERR_INVALID, "vc_encode_videos: cu[0] = %d, not 0", cu[0]);
+    for (int v = 0; v < V; ++v)
+        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "vc_encode_videos: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)",
+                                            v, cu[v], v + 1, cu[v + 1]);
+    if (w->n_layers < 1 || !w->layers) return fail(INFV_ERR_INVALID, "vc_encode_videos: no layers");
+    if (w->n_layers > INFV_VQF_VC_MAX_LAYERS)
+        return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: %d layers, at most %d are supported", w->n_layers, INFV_VQF_VC_MAX_LAYERS);
+    const int Q = c.n_query, Hd = c.hidden, S = c.nb_samples, Ln = w->n_layers;
+    for (int v = 0; v < V; ++v) {
+        if (text_len[v] < 0) return fail(INFV_ERR_INVALID, "vc_encode_videos: text_len[%d] = %d is negative", v, text_len[v]);
+        if (Q + text_len[v] > INFV_VQF_VC_MAX_TOKENS)
+            return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: video %d attends over %d + %d tokens, at most %d are supported",
+                        v, Q, text_len[v], INFV_VQF_VC_MAX_TOKENS);
+    }
+    if (T < 1) return fail(INFV_ERR_INVALID, "vc_encode_videos: T must be >= 1");
+    const int n_tokens = T * c.tokens_per_frame;
+    if (n_tokens % 32) return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: T * tokens_per_frame = %d is no multiple of 32", n_tokens);
+    if (h->tok_bf16) return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: bf16 frame tokens are not supported on this path");
+    int n_cross = 0;
+    for (int l = 0; l < Ln; ++l) n_cross += w->layers[l].has_cross != 0;
+    const bool use_ltm = c.alpha != 1.0f && n_cross > 0;
+    const int n_h = use_ltm ? V * n_cross : 0;
+    if (use_ltm) {
+        if (!ltm) return fail(INFV_ERR_INVALID, "vc_encode_videos: alpha != 1 needs the LTM handles of every video and cross layer");
+        std::vector<infv_ltm_handle> all(ltm, ltm + n_h);
+        for (int i = 0; i < n_h; ++i)
+            if (!all[i]) return fail(INFV_ERR_INVALID, "vc_encode_videos: LTM handle %d is null", i);
+        std::sort(all.begin(), all.end());
+        if (std::adjacent_find(all.begin(), all.end()) != all.end())
+            return fail(INFV_ERR_INVALID, "vc_encode_videos: an LTM handle appears twice (every video and cross layer needs its own memory)");
+    }
+    if ((proj_out || proj_mean) && (c.proj_out <= 0 || !w->mistral_proj.w))
+        return fail(INFV_ERR_INVALID, "vc_encode_videos: projected output without mistral_proj");
+    const int C = cu[V];
+    if (C == 0) {                                             // no chunk: new_video still starts every memory afresh
+        if (use_ltm && new_video)
+            for (int i = 0; i < n_h; ++i) infv_ltm_reset(ltm[i]);
+        return INFV_OK;
+    }
+    if (!frames || !hidden_in) return fail(INFV_ERR_INVALID, "vc_encode_videos: null frames or hidden_in");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (use_ltm)
+        if (int rc = ensure_streams(h)) return rc;
+
+    // ---- host tables: per chunk its video's text length, the offset of its packed text rows, its rows in hidden_in / hidden_out
+    std::vector<int32_t> n_valid(C), toff(C + 1, 0), q_dst(C), q_src(C), t_src(C), tl(C), o_q(C), o_t(C), q_n(C, Q);
+    {
+        int32_t in_row = 0, c_i = 0;
+        for (int v = 0; v < V; ++v) {
+            for (int cc = cu[v]; cc < cu[v + 1]; ++cc, ++c_i) {
+                tl[cc] = text_len[v]; n_valid[cc] = Q + text_len[v]; toff[cc + 1] = toff[cc] + text_len[v];
+                q_dst[cc] = cc * Q; q_src[cc] = in_row; t_src[cc] = in_row + Q;
+                o_q[cc] = cc * Q + toff[cc]; o_t[cc] = o_q[cc] + Q;
+            }
+            in_row += Q + text_len[v];
+        }
+    }
+    const long M = (long)C * Q, Tt = toff[C];
+    const long chunk_k = (long)n_tokens * c.enc_width;
+    const int RB = C < 128 ? C : 128;                          // chunks per row block of the token GEMMs (batch invariant: any size)
+    const long TB = Tt < 16384 ? Tt : 16384;                   // text rows per block of the text FFN
+    long tb_max = 0;                                           // text rows of the largest row block
+    for (int c0 = 0; c0 < C; c0 += RB) { const int c1 = c0 + RB < C ? c0 + RB : C; tb_max = std::max<long>(tb_max, toff[c1] - toff[c0]); }
+    const int NB = pick_short_nb(h, C, n_tokens);
+    {
+        const size_t act = (size_t)M * Hd * sizeof(float), tact = (size_t)Tt * Hd * sizeof(float);
+        const bool grow = act > h->vA.bytes || act > h->v1.bytes || act > h->v2.bytes || act > h->vxq.bytes || act > h->vshort.bytes ||
+                          act > h->vmerged.bytes || (use_ltm && act > h->valong.bytes) ||
+                          (size_t)RB * Q * 3 * Hd * sizeof(float) > h->vqkv.bytes || (size_t)RB * Q * Hd * sizeof(float) > h->vsa.bytes ||
+                          (size_t)RB * Q * c.inter * sizeof(float) > h->vinter.bytes || tact > h->tA.bytes || tact > h->t1.bytes ||
+                          (size_t)tb_max * 3 * Hd * sizeof(float) > h->tqkv.bytes || (size_t)tb_max * Hd * sizeof(float) > h->tsa.bytes ||
+                          (size_t)TB * c.inter * sizeof(float) > h->tinter.bytes ||
+                          (use_ltm && ((size_t)C * S * sizeof(double) > h->vu.bytes || (size_t)C * T * c.enc_width * sizeof(float) > h->vkbar.bytes));
+        if (grow) HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(h->vA.reserve(act)); HIP_TRY(h->v1.reserve(act)); HIP_TRY(h->v2.reserve(act)); HIP_TRY(h->vxq.reserve(act));
+        HIP_TRY(h->vshort.reserve(act)); HIP_TRY(h->vmerged.reserve(act));
+        if (use_ltm) {
+            HIP_TRY(h->valong.reserve(act));
+            HIP_TRY(h->vu.reserve((size_t)C * S * sizeof(double)));
+            HIP_TRY(h->vkbar.reserve((size_t)C * T * c.enc_width * sizeof(float)));
+        }
+        HIP_TRY(h->vqkv.reserve((size_t)RB * Q * 3 * Hd * sizeof(float)));
+        HIP_TRY(h->vsa.reserve((size_t)RB * Q * Hd * sizeof(float)));
+        HIP_TRY(h->vinter.reserve((size_t)RB * Q * c.inter * sizeof(float)));
+        if (Tt > 0) {
+            HIP_TRY(h->tA.reserve(tact)); HIP_TRY(h->t1.reserve(tact));
+            HIP_TRY(h->tqkv.reserve((size_t)tb_max * 3 * Hd * sizeof(float)));
+            HIP_TRY(h->tsa.reserve((size_t)tb_max * Hd * sizeof(float)));
+            HIP_TRY(h->tinter.reserve((size_t)TB * c.inter * sizeof(float)));
+        }
+    }
+    float* vA = h->vA.as<float>(); float* v1 = h->v1.as<float>(); float* v2 = h->v2.as<float>();
+    float* vxq = h->vxq.as<float>(); float* valong = h->valong.as<float>();
+    float* vshort = h->vshort.as<float>(); float* vmerged = h->vmerged.as<float>();
+    float* tA = h->tA.as<float>(); float* t1 = h->t1.as<float>();
+
+    // ---- every chunk starts from its video's encoder input rows
+    HIP_TRY(launch_qf_copy_rows(hidden_in, vA, q_dst.data(), q_src.data(), q_n.data(), C, Hd, stream));
+    if (Tt > 0) HIP_TRY(launch_qf_copy_rows(hidden_in, tA, toff.data(), t_src.data(), tl.data(), C, Hd, stream));
+
+    // ---- ONE pass over the frame tokens: split-bf16 operands of every cross layer's short-term attention (kept for the call
+    //      when they fit INFV_VQF_SPLIT_CACHE_GB) and the frame means every cross layer's memories step from
+    SplitRef wref{}; bool have_w = false, have_kbar = false;
+    if (n_cross > 0) {
+        const double need_gb = 4.0 * (double)C * (double)chunk_k * 2.0 / 1e9;
+        if (h->fuse && split_path(h, n_tokens) && need_gb <= h->split_cache_gb) {
+            have_kbar = use_ltm && 64 % c.tokens_per_frame == 0;
+            if (int rc = prepare_split(h, frames, false, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
+            have_w = true;
+        }
+        if (use_ltm && !have_kbar) {
+            if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;
+            if (int rc = infv_ltm_pool(ltm[0], frames, (int64_t)C * T, h->vkbar.as<float>(), stream_)) return rc;
+        }
+    }
+    auto pre_at = [&](int c0, SplitRef* r) -> const SplitRef* {
+        if (!have_w) return nullptr;
+        const long o = (long)c0 * chunk_k;
+        *r = SplitRef{wref.Fh + o, wref.Fl + o, wref.Th + o, wref.Tl + o};
+        return r;
+    };
+    std::vector<infv_ltm_handle> hs_l(use_ltm ? V : 0);
+    std::vector<int32_t> off1(RB);
+
+    int j_cross = 0;
+    for (int l = 0; l < Ln; ++l) {
+        const infv_vqf_vc_layer& L = w->layers[l];
+        const bool cross = L.has_cross != 0;
+        const bool last = l == Ln - 1;
+        const bool text_out = Tt > 0 && (!last || hidden_out);   // the last layer's text rows feed nothing but hidden_out
+        // ---- self-attention over query + text tokens, output dense + LayerNorm, cross query (row blocks of chunks) ----
+        for (int c0 = 0; c0 < C; c0 += RB) {
+            const int nb = C - c0 < RB ? C - c0 : RB;
+            const long r0 = (long)c0 * Q * Hd, t0 = toff[c0], tn = toff[c0 + nb] - t0;
+            LinearCall qkv{vA + r0, nb * Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
+            qkv.inv = true; qkv.y = h->vqkv.as<float>();
+            if (int rc = run_linear(h, qkv, stream)) return rc;
+            if (tn > 0) {
+                LinearCall qkt{tA + t0 * Hd, (int)tn, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
+                qkt.inv = true; qkt.y = h->tqkv.as<float>();
+                if (int rc = run_linear(h, qkt, stream)) return rc;
+            }
+            for (int b = 0; b < nb; ++b) off1[b] = toff[c0 + b] - (int32_t)t0;
+            VcAttn a{};
+            a.qkv0 = h->vqkv.as<float>(); a.rows0 = Q; a.nsplit = Q; a.qkv1 = h->tqkv.as<float>();
+            a.ctx0 = h->vsa.as<float>(); a.ctx1 = h->tsa.as<float>(); a.H = c.n_heads; a.n_alloc = 0;
+            HIP_TRY(launch_qf_vc_self_attention(a, nb, n_valid.data() + c0, off1.data(), stream));
+            LinearCall so{h->vsa.as<float>(), nb * Q, Hd, {&L.self_o}, 1, Hd};
+            so.inv = true; so.residual = vA + r0; so.res_rows = nb * Q; so.ln = &L.self_ln; so.y = v1 + r0;
+            if (int rc = run_linear(h, so, stream)) return rc;
+            if (tn > 0 && text_out) {
+                LinearCall st{h->tsa.as<float>(), (int)tn, Hd, {&L.self_o}, 1, Hd};
+                st.inv = true; st.residual = tA + t0 * Hd; st.res_rows = (int)tn; st.ln = &L.self_ln; st.y = t1 + t0 * Hd;
+                if (int rc = run_linear(h, st, stream)) return rc;
+            }
+            if (cross) {
+                LinearCall xq{v1 + r0, nb * Q, Hd, {&L.x_q}, 1, Hd};
+                xq.inv = true; xq.y = vxq + r0;
+                if (int rc = run_linear(h, xq, stream)) return rc;
+            }
+        }
+        const float* qin = v1;                                 // the query rows entering the query FFN
+        if (cross) {
+            // ---- this layer's V memories with per-chunk queries on the worker stream, beside the short-term attention ----
+            if (use_ltm) {
+                infv_ltm_proj pr{};
+                pr.wk = L.x_k.w; pr.bk = L.x_k.b; pr.wv = L.x_v.w; pr.bv = L.x_v.b;
+                if (u)                                         // u[:, j, :] -> contiguous [C][S] for the one-layer handles
+                    HIP_TRY(hipMemcpy2DAsync(h->vu.p, (size_t)S * sizeof(double), u + (size_t)j_cross * S, (size_t)n_cross * S * sizeof(double),
+                                             (size_t)S * sizeof(double), (size_t)C, hipMemcpyDeviceToDevice, stream));
+                HIP_TRY(hipEventRecord(h->ev_main, stream));
+                HIP_TRY(hipStreamWaitEvent(h->side, h->ev_main, 0));
+                for (int v = 0; v < V; ++v) hs_l[v] = ltm[(size_t)v * n_cross + j_cross];
+                if (int rc = infv_ltm_steps_videos(hs_l.data(), V, cu, h->vkbar.as<float>(), T, vxq, 1, Q, &pr,
+                                                   u ? h->vu.as<double>() : nullptr, new_video, valong, h->side)) return rc;
+                HIP_TRY(hipEventRecord(h->ev_side, h->side));
+            }
+            for (int c0 = 0; c0 < C; c0 += NB) {
+                const int nb = C - c0 < NB ? C - c0 : NB;
+                SplitRef sr;
+                if (int rc = short_attention(h, frames + (long)c0 * chunk_k, false, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
+                                             nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
+                                             pre_at(c0, &sr), nullptr, kInvariantNb)) return rc;
+            }
+            if (use_ltm) {
+                HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
+                for (long m0 = 0; m0 < M; m0 += 32768) {       // merged = alpha * short + (1 - alpha) * long
+                    QfEpilogue em{};
+                    em.parts = vshort + m0 * Hd; em.nsplit = 1; em.ld_in = Hd; em.seg_cols = Hd;
+                    em.scale = c.alpha; em.res_scale = (float)(1.0 - (double)c.alpha);
+                    em.residual = valong + m0 * Hd; em.ld_res = Hd; em.res_rows = (int)(M - m0 < 32768 ? M - m0 : 32768);
+                    em.out = vmerged + m0 * Hd; em.ld_out = Hd; em.M = em.res_rows; em.width = Hd; em.eps = c.ln_eps;
+                    HIP_TRY(launch_qf_epilogue(em, stream));
+                }
+            }
+            for (int c0 = 0; c0 < C; c0 += RB) {
+                const int nb = C - c0 < RB ? C - c0 : RB;
+                const long r0 = (long)c0 * Q * Hd;
+                LinearCall xo{vmerged + r0, nb * Q, Hd, {&L.x_o}, 1, Hd};
+                xo.inv = true; xo.residual = v1 + r0; xo.res_rows = nb * Q; xo.ln = &L.x_ln; xo.y = v2 + r0;
+                if (int rc = run_linear(h, xo, stream)) return rc;
+            }
+            qin = v2;
+            ++j_cross;
+        }
+        // ---- query FFN on the query rows, text FFN on the text rows (Qformer.py:483-496) ----
+        for (int c0 = 0; c0 < C; c0 += RB) {
+            const int nb = C - c0 < RB ? C - c0 : RB;
+            const long r0 = (long)c0 * Q * Hd;
+            LinearCall fi{qin + r0, nb * Q, Hd, {&L.q_ffn_in}, 1, c.inter};
+            fi.inv = true; fi.act = QF_ACT_GELU; fi.y = h->vinter.as<float>();
+            if (int rc = run_linear(h, fi, stream)) return rc;
+            LinearCall fo{h->vinter.as<float>(), nb * Q, c.inter, {&L.q_ffn_out}, 1, Hd};
+            fo.inv = true; fo.residual = qin + r0; fo.res_rows = nb * Q; fo.ln = &L.q_ffn_ln; fo.y = vA + r0;
+            if (int rc = run_linear(h, fo, stream)) return rc;
+        }
+        if (text_out)
+            for (long m0 = 0; m0 < Tt; m0 += TB) {
+                const int m = (int)(Tt - m0 < TB ? Tt - m0 : TB);
+                LinearCall fi{t1 + m0 * Hd, m, Hd, {&L.t_ffn_in}, 1, c.inter};
+                fi.inv = true; fi.act = QF_ACT_GELU; fi.y = h->tinter.as<float>();
+                if (int rc = run_linear(h, fi, stream)) return rc;
+                LinearCall fo{h->tinter.as<float>(), m, c.inter, {&L.t_ffn_out}, 1, Hd};
+                fo.inv = true; fo.residual = t1 + m0 * Hd; fo.res_rows = m; fo.ln = &L.t_ffn_ln; fo.y = tA + m0 * Hd;
+                if (int rc = run_linear(h, fo, stream)) return rc;
+            }
+    }
+    if (hidden_out) {
+        HIP_TRY(launch_qf_copy_rows(vA, hidden_out, o_q.data(), q_dst.data(), q_n.data(), C, Hd, stream));
+        if (Tt > 0) HIP_TRY(launch_qf_copy_rows(tA, hidden_out, o_t.data(), toff.data(), tl.data(), C, Hd, stream));
+    }
+    if (proj_out || proj_mean) {
+        float* lo = proj_out;
+        if (!lo) {                                             // only the mean is wanted: project into scratch
+            const size_t need = (size_t)M * c.proj_out * sizeof(float);
+            if (need > h->S.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->S.reserve(need)); }
+            lo = h->S.as<float>();
+        }
+        for (int c0 = 0; c0 < C; c0 += RB) {
+            const int nb = C - c0 < RB ? C - c0 : RB;
+            LinearCall pj{vA + (long)c0 * Q * Hd, nb * Q, Hd, {&w->mistral_proj}, 1, c.proj_out};
+            pj.inv = true; pj.y = lo + (long)c0 * Q * c.proj_out;
+            if (int rc = run_linear(h, pj, stream)) return rc;
+        }
+        if (proj_mean) HIP_TRY(launch_qf_mean_segments(lo, cu, V, (long)Q * c.proj_out, proj_mean, stream));
+    }
+    return INFV_OK;
 }
 
 int infv_vqf_mean(const float* in, int32_t n, int64_t elems, float* out, void* stream) {

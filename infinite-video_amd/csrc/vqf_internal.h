@@ -43,6 +43,24 @@ hipError_t launch_qf_epilogue(const QfEpilogue& e, hipStream_t stream);
 // qkv [nb*Q][3*hidden] (bias applied) -> ctx [nb*Q][hidden]; softmax(q k^T / sqrt(dh)) v per head, Q <= 32, dh = 64
 hipError_t launch_qf_self_attention(const float* qkv, int nb, int Q, int H, float* ctx, hipStream_t stream);
 
+// Self-attention over the n_valid[b] <= kVcAttnMaxN query + text tokens of chunk b (VideoChat2), dh = 64.  Row r of chunk b
+// lives at row  b * rows0 + r  of qkv0 / ctx0 when r < nsplit, else at row  off1[b] + r - nsplit  of qkv1 / ctx1 (query rows
+// in a regular block, text rows packed behind an offset table; nsplit = rows0 = n_max and off1 = nullptr: one padded block).
+// qkv rows are [3*hidden] (bias applied), ctx rows [hidden].  Rows [n_valid[b], n_alloc) of the first block are written as
+// zeros; keys at or beyond n_valid[b] are never read.  n_valid / off1 are HOST arrays (they travel in kernel arguments).
+constexpr int kVcAttnMaxN = 608;
+constexpr int kVcAttnGroup = 256;
+struct VcAttn {
+    const float* qkv0; long rows0; int nsplit; const float* qkv1;
+    float* ctx0; float* ctx1;
+    int H; int n_alloc;
+};
+hipError_t launch_qf_vc_self_attention(const VcAttn& a, int nb, const int32_t* n_valid, const int32_t* off1, hipStream_t stream);
+// dst rows [dst_row[s], +n_rows[s]) = src rows [src_row[s], +n_rows[s]) for n_segs segments (HOST tables), rows of `width` floats
+constexpr int kRowSegs = 128;
+hipError_t launch_qf_copy_rows(const float* src, float* dst, const int32_t* dst_row, const int32_t* src_row, const int32_t* n_rows,
+                               int n_segs, int width, hipStream_t stream);
+
 // qt[b][h*Q + q][j] = sum_e xq[b][q][h*64 + e] / sqrt(64) * Wk[h*64 + e][j]
 hipError_t launch_qf_qtilde(const float* xq, int nb, int Q, int H, int d, const float* wk, float* qt, hipStream_t stream);
 

@@ -439,6 +439,170 @@ hipError_t launch_qf_self_attention(const float* qkv, int nb, int Q, int H, floa
 }
 
 // ------------------------------------------------------------------------------------------------------
+// Self-attention over the query + text tokens of one chunk (VideoChat2: 96 query tokens + up to 512 instruction tokens,
+// infty-VideoChat2/models/blip2/Qformer.py:232-300 with all-ones masks), one workgroup per (head, chunk, 32-row tile).
+// The tile's scores stay in LDS ([32][ldS] fp32, up to 81 KB: dynamic LDS), K and V stream through one [32][65] tile; the
+// softmax is the exact two-pass form.  Every loop bound is the chunk's own length n: keys at or beyond n are neither
+// loaded nor summed, so an output element's summation order depends on n alone -- not on the batch, the grid or ldS.
+// LDS layout: ldS = 8 (mod 64), so the 8 rows x 8 column phases one wave reads in the softmax pass fall into 64 distinct
+// banks; the K/V tile has the odd row stride 65 of qf_self_attention_kernel.
+// ------------------------------------------------------------------------------------------------------
+struct VcAttnTab { int32_t n_valid[kVcAttnGroup]; int32_t off1[kVcAttnGroup]; };
+
+__device__ __forceinline__ long vc_row(const VcAttn& a, int off1, int b, int r) {
+    return r < a.nsplit ? (long)b * a.rows0 + r : (long)off1 + (r - a.nsplit);
+}
+
+__global__ __launch_bounds__(256) void qf_vc_self_attention_kernel(VcAttn a, VcAttnTab tab, int ldS) {
+    extern __shared__ __attribute__((aligned(16))) float vc_lds[];
+    float* qs = vc_lds;                 // [32][65] query rows of the tile, pre-scaled by 1/8
+    float* kv = qs + 32 * 65;           // [32][65] the current K (then V) tile
+    float* S = kv + 32 * 65;            // [32][ldS] scores, then exp(score - max)
+    const int h = blockIdx.x, b = blockIdx.y, r0 = blockIdx.z * 32, tid = threadIdx.x;
+    const int n = tab.n_valid[b], off1 = tab.off1[b];
+    const int hidden = a.H * 64;
+    const long ld = 3L * hidden;
+    const int r = tid >> 3, g8 = tid & 7;
+    const int row = r0 + r;
+    if (r0 >= n) {                      // a tile of padding only: keep its rows finite (uniform exit, before any barrier)
+        if (row < a.n_alloc && row < a.nsplit) {
+            float* out = a.ctx0 + ((long)b * a.rows0 + row) * hidden + h * 64 + g8 * 8;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) out[e] = 0.f;
+        }
+        return;
+    }
+    const bool in0 = row < a.nsplit;
+    for (int e = tid; e < 32 * 64; e += 256) {
+        const int rr = e >> 6, c = e & 63;
+        const int gr = r0 + rr;
+        const float* src = (gr < a.nsplit ? a.qkv0 : a.qkv1) + vc_row(a, off1, b, gr) * ld + h * 64 + c;
+        qs[rr * 65 + c] = gr < n ? src[0] * 0.125f : 0.f;
+    }
+    const int ntile = (n + 31) >> 5;
+    // ---- scores of the tile's rows against every valid key
+    for (int kt = 0; kt < ntile; ++kt) {
+        __syncthreads();
+        for (int e = tid; e < 32 * 64; e += 256) {
+            const int rr = e >> 6, c = e & 63;
+            const int gr = kt * 32 + rr;
+            const float* src = (gr < a.nsplit ? a.qkv0 : a.qkv1) + vc_row(a, off1, b, gr) * ld + hidden + h * 64 + c;
+            kv[rr * 65 + c] = gr < n ? src[0] : 0.f;
+        }
+        __syncthreads();
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        const float* q = qs + r * 65;
+        const float* k0 = kv + (g8 * 4) * 65;
+#pragma unroll 8
+        for (int c = 0; c < 64; ++c) {
+            const float qv = q[c];
+            s0 = fmaf(qv, k0[c], s0); s1 = fmaf(qv, k0[65 + c], s1); s2 = fmaf(qv, k0[130 + c], s2); s3 = fmaf(qv, k0[195 + c], s3);
+        }
+        const int kc = kt * 32 + g8 * 4;
+        float* srow = S + (long)r * ldS;
+        if (kc < n) srow[kc] = s0;
+        if (kc + 1 < n) srow[kc + 1] = s1;
+        if (kc + 2 < n) srow[kc + 2] = s2;
+        if (kc + 3 < n) srow[kc + 3] = s3;
+    }
+    __syncthreads();
+    // ---- exact two-pass softmax: 8 lanes per row, columns g8, g8 + 8, ...; the normalisation is applied to the output
+    float* srow = S + (long)r * ldS;
+    float mx = -INFINITY;
+    for (int j = g8; j < n; j += 8) mx = fmaxf(mx, srow[j]);
+    for (int off = 1; off < 8; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    float sum = 0.f;
+    for (int j = g8; j < n; j += 8) { const float p = expf(srow[j] - mx); srow[j] = p; sum += p; }
+    for (int off = 1; off < 8; off <<= 1) sum += __shfl_xor(sum, off);
+    // ---- read-out: V streamed in tiles of 32 keys, keys in ascending order
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    for (int kt = 0; kt < ntile; ++kt) {
+        __syncthreads();
+        for (int e = tid; e < 32 * 64; e += 256) {
+            const int rr = e >> 6, c = e & 63;
+            const int gr = kt * 32 + rr;
+            const float* src = (gr < a.nsplit ? a.qkv0 : a.qkv1) + vc_row(a, off1, b, gr) * ld + 2 * hidden + h * 64 + c;
+            kv[rr * 65 + c] = gr < n ? src[0] : 0.f;
+        }
+        __syncthreads();
+        const int jn = n - kt * 32 < 32 ? n - kt * 32 : 32;
+        const float* p = srow + kt * 32;
+#pragma unroll 4
+        for (int j = 0; j < jn; ++j) {
+            const float pj = p[j];
+            const float* v = kv + j * 65 + g8 * 8;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, v[e], acc[e]);
+        }
+    }
+    if (row < n) {
+        float* out = (in0 ? a.ctx0 : a.ctx1) + vc_row(a, off1, b, row) * hidden + h * 64 + g8 * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[e] = acc[e] / sum;
+    } else if (row < a.n_alloc && in0) {
+        float* out = a.ctx0 + ((long)b * a.rows0 + row) * hidden + h * 64 + g8 * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[e] = 0.f;
+    }
+}
+
+hipError_t launch_qf_vc_self_attention(const VcAttn& a, int nb, const int32_t* n_valid, const int32_t* off1, hipStream_t stream) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qf_vc_self_attention_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    for (int b0 = 0; b0 < nb; b0 += kVcAttnGroup) {          // the length table travels in kernel arguments
+        const int gn = nb - b0 < kVcAttnGroup ? nb - b0 : kVcAttnGroup;
+        VcAttnTab tab;
+        int n_hi = 0;
+        for (int j = 0; j < gn; ++j) {
+            const int n = n_valid[b0 + j];
+            if (n < 1 || n > kVcAttnMaxN) return hipErrorInvalidValue;
+            tab.n_valid[j] = n; tab.off1[j] = off1 ? off1[b0 + j] : 0;
+            n_hi = n > n_hi ? n : n_hi;
+        }
+        for (int j = gn; j < kVcAttnGroup; ++j) { tab.n_valid[j] = 0; tab.off1[j] = 0; }
+        const int rows_hi = a.n_alloc > n_hi ? a.n_alloc : n_hi;   // (padding rows are zeroed by tiles past the chunk's length)
+        const int ldS = ((n_hi + 63) / 64) * 64 + 8;
+        const size_t lds = (size_t)(2 * 32 * 65 + 32 * ldS) * sizeof(float);
+        VcAttn g = a;
+        g.qkv0 = a.qkv0 + (long)b0 * a.rows0 * 3 * a.H * 64;
+        g.ctx0 = a.ctx0 + (long)b0 * a.rows0 * a.H * 64;
+        INFV_LAUNCH(qf_vc_self_attention_kernel, dim3(a.H, gn, (rows_hi + 31) / 32), dim3(256), lds, stream, g, tab, ldS);
+    }
+    return hipGetLastError();
+}
+
+// dst rows [dst[s], dst[s] + n[s]) = src rows [src[s], src[s] + n[s]) for every segment s (rows of `width` floats, width % 4 == 0)
+struct RowSegs { int32_t dst[kRowSegs], src[kRowSegs], n[kRowSegs]; };
+__global__ __launch_bounds__(256) void qf_copy_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, RowSegs sg, int width4) {
+    const int s = blockIdx.x;
+    const long total = (long)sg.n[s] * width4;
+    const float4* in = reinterpret_cast<const float4*>(src) + (long)sg.src[s] * width4;
+    float4* out = reinterpret_cast<float4*>(dst) + (long)sg.dst[s] * width4;
+    for (long i = (long)blockIdx.y * 256 + threadIdx.x; i < total; i += 256L * gridDim.y) out[i] = in[i];
+}
+
+hipError_t launch_qf_copy_rows(const float* src, float* dst, const int32_t* dst_row, const int32_t* src_row, const int32_t* n_rows,
+                               int n_segs, int width, hipStream_t stream) {
+    if (width % 4) return hipErrorInvalidValue;
+    for (int s0 = 0; s0 < n_segs; s0 += kRowSegs) {
+        const int gn = n_segs - s0 < kRowSegs ? n_segs - s0 : kRowSegs;
+        RowSegs sg;
+        for (int j = 0; j < kRowSegs; ++j) {
+            sg.dst[j] = j < gn ? dst_row[s0 + j] : 0; sg.src[j] = j < gn ? src_row[s0 + j] : 0; sg.n[j] = j < gn ? n_rows[s0 + j] : 0;
+        }
+        INFV_LAUNCH(qf_copy_rows_kernel, dim3(gn, 8), dim3(256), 0, stream, src, dst, sg, width / 4);
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Pre-multiplied cross-attention queries: qt[b][h*Q+q][j] = sum_e xq[b][q][h*64+e]/8 * Wk[h*64+e][j]
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void qf_qtilde_kernel(const float* __restrict__ xq, int Q, int H, int d,

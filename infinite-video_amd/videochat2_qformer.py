@@ -20,12 +20,16 @@ stock PyTorch-ROCm"):
 ``VideoChat2Encoder.encode_tokens`` is the counterpart of ``encode_img`` after the vision encoder
 (videochat2_it_mistral.py:196-252), ``encode_long_video_vc`` that of the eval loop ``infer_*_inf``
 (eval_code/run_nextqa_mistral.py:141-152).  Parameters live under the reference's state-dict names.
+
+``VideoChat2Encoder.encode_videos`` / ``encode_long_videos_vc`` are the batched counterparts for harnesses that walk many
+short videos: ONE C call (``infv_vqf_vc_encode_videos``) runs the whole encoder -- BERT scaffolding included -- layer-major
+over the packed chunks of every video, each video's six memories in its own :class:`VideoChat2Memory`.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -34,6 +38,9 @@ import torch.nn.functional as F
 from . import _lib
 from .basis_maps import NB_SAMPLES
 from .qformer_hook import LongTermMemoryHook
+from .video_qformer import VideoMemory, _cumsum, _dev_f32, draw_video_uniforms
+
+MAX_TXT_LEN = 512              # max_txt_len of the instruction (configs/config_mistral.json)
 
 
 class _Cfg:
@@ -156,15 +163,64 @@ class VideoChat2Qformer(nn.Module):
 
 
 def init_Qformer(num_query_token: int, vision_width: int, tau: float, alpha: float, sticky: bool, num_basis: int,
-                 num_hidden_layers: int = 12, cross_attention_freq: int = 2):
-    """Counterpart of ``Blip2Base.init_Qformer`` (blip2.py:47-77): (Q-former, query tokens)."""
+                 num_hidden_layers: int = 12, cross_attention_freq: int = 2, hidden_size: int = 768,
+                 intermediate_size: int = 3072, num_attention_heads: int = 12):
+    """Counterpart of ``Blip2Base.init_Qformer`` (blip2.py:47-77): (Q-former, query tokens).  The last three arguments
+    default to bert-base; tests build small shapes with them."""
     cfg = _Cfg(encoder_width=vision_width, sticky=sticky, num_basis=num_basis, tau=tau, alpha=alpha,
                cross_attention_freq=cross_attention_freq, query_length=num_query_token,
-               num_hidden_layers=num_hidden_layers)
+               num_hidden_layers=num_hidden_layers, hidden_size=hidden_size, intermediate_size=intermediate_size,
+               num_attention_heads=num_attention_heads)
     qformer = VideoChat2Qformer(cfg)
     query_tokens = nn.Parameter(torch.zeros(1, num_query_token, cfg.hidden_size))
     nn.init.normal_(query_tokens, mean=0.0, std=0.02)
     return qformer, query_tokens
+
+
+class VideoChat2Memory(VideoMemory):
+    """One video's long-term memories for :meth:`VideoChat2Encoder.encode_videos`: a one-layer ``LTMEngine`` per
+    cross-attention layer (six in the model), created as ``LongTermAttentionVC._get_engine`` creates the model's own.
+    ``export_state(i)`` / ``last_draw(i)`` read cross layer i's memory.  ``video_id`` names the video's device-rng streams:
+    cross layer i draws from stream ``(video_id + 1) * n_cross + i`` (the model's own modules keep stream i)."""
+
+    def __init__(self, model: "VideoChat2Encoder", device: torch.device, video_id: int = 0):
+        from .engine import LTMEngine
+        self.device = device
+        self.video_id = int(video_id)
+        self.engines = [LTMEngine(m.attn_num_basis, m.n_head, m.head_size, m.encoder_width, m.tokens_per_frame, tau=m.tau,
+                                  sticky=bool(m.sticky_memories), n_layers=1, max_q=max(model.n_query, 32), device=device,
+                                  nb_samples=m.nb_samples)
+                        for m in model.qformer.ltm_modules]
+        self.set_device_rng(getattr(model, "_device_rng_seed", None))
+
+    def _check(self, model: "VideoChat2Encoder", device: torch.device):
+        if len(self.engines) != len(model.qformer.ltm_modules):
+            raise ValueError("memory has another number of cross layers than the model")
+        if self.device != device:
+            raise ValueError(f"memory is on {self.device}, frames are on {device}")
+
+
+def _check_vc_memories(model: "VideoChat2Encoder", memories, V: int) -> list:
+    """Every video its own VideoChat2Memory; refused before any library call."""
+    memories = list(memories)
+    if len(memories) != V:
+        raise ValueError(f"{len(memories)} memories for {V} videos")
+    seen = set()
+    for i, mem in enumerate(memories):
+        if id(mem) in seen:
+            raise ValueError(f"memories[{i}] appears twice: every video needs its own memory")
+        seen.add(id(mem))
+    for i, mem in enumerate(memories):
+        if not isinstance(mem, VideoChat2Memory):
+            raise TypeError(f"memories[{i}] is not a VideoChat2Memory")
+    return memories
+
+
+def draw_vc_uniforms(counts: Sequence[int], continuing: Sequence[bool], n_cross: int) -> torch.Tensor:
+    """Gibbs uniforms [sum C_v, n_cross, 512] float64 from torch's global CPU generator in the order the loop of
+    ``encode_tokens`` consumes it: video by video, chunk by chunk, per LTM instance 512 for the bin draw and 512 discarded
+    (the in-bin draw); the first chunk of a video that is not ``continuing`` draws nothing (its rows stay 0)."""
+    return draw_video_uniforms(counts, continuing, n_cross)
 
 
 class VideoChat2Encoder(nn.Module):
@@ -175,20 +231,30 @@ class VideoChat2Encoder(nn.Module):
 
     def __init__(self, num_query_token: int = 32, extra_num_query_token: int = 64, vision_width: int = 1024,
                  llm_hidden: int = 4096, num_basis: int = 256, sticky: bool = True, tau: float = 0.75,
-                 alpha: float = 0.75, num_hidden_layers: int = 12, cross_attention_freq: int = 2):
+                 alpha: float = 0.75, num_hidden_layers: int = 12, cross_attention_freq: int = 2, hidden_size: int = 768,
+                 intermediate_size: int = 3072, num_attention_heads: int = 12, tokens_per_frame: Optional[int] = None):
         super().__init__()
         self.n_query = num_query_token + extra_num_query_token
         self.qformer, self.query_tokens = init_Qformer(self.n_query, vision_width, tau, alpha, sticky, num_basis,
-                                                       num_hidden_layers, cross_attention_freq)
+                                                       num_hidden_layers, cross_attention_freq, hidden_size,
+                                                       intermediate_size, num_attention_heads)
         self.mistral_proj = nn.Linear(self.qformer.config.hidden_size, llm_hidden)
         self._vqf = None
         self._vqf_dev = None
+        self._vc = None                                   # handle of the batched path (encode_videos): (handle, device)
+        self._vc_memories: List["VideoChat2Memory"] = []  # default pool of encode_videos
+        self._device_rng_seed: Optional[int] = None
+        if tokens_per_frame is not None:                  # (small test shapes; the model has 14 x 14 patches per frame)
+            self.tokens_per_frame = int(tokens_per_frame)
+        for m in self.qformer.ltm_modules:                # the memories pool frames of this encoder's shape
+            m.tokens_per_frame, m.encoder_width = self.tokens_per_frame, vision_width
 
     def use_device_rng(self, seed: Optional[int]):
         """Draw the Gibbs uniforms of every cross-attention's memory on the device (``LongTermAttention.use_device_rng``): the
         i-th LTM instance draws from stream ``i``; torch's global generator is left alone.  ``seed=None`` turns it off."""
         for i, m in enumerate(self.qformer.ltm_modules):
             m.use_device_rng(seed, i)
+        self._device_rng_seed = None if seed is None else int(seed)
 
     # ------------------------------------------------------------------ weights
     def load_reference_state_dict(self, sd: dict, strict: bool = True):
@@ -227,6 +293,12 @@ class VideoChat2Encoder(nn.Module):
                 _lib.load().infv_vqf_destroy(h)
             except Exception:
                 pass
+        vc, self._vc = getattr(self, "_vc", None), None
+        if vc:
+            try:
+                _lib.load().infv_vqf_destroy(vc[0])
+            except Exception:
+                pass
 
     def __del__(self):
         self._release()
@@ -258,6 +330,182 @@ class VideoChat2Encoder(nn.Module):
                 C.byref(val), C.c_void_p(0 if along is None else along.data_ptr()), C.c_void_p(out.data_ptr()),
                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return out.unsqueeze(0)
+
+    # ------------------------------------------------------------------ many videos, layer-major, one call
+    def _vc_handle(self, device):
+        """Handle of the batched path: the short-term handle's shape plus ``mistral_proj``'s width."""
+        if self._vc is not None and self._vc[1] == device:
+            return self._vc[0]
+        if self._vc is not None:
+            _lib.load().infv_vqf_destroy(self._vc[0])
+            self._vc = None
+        cfg = self.qformer.config
+        c = _lib.VqfConfig(1, cfg.num_attention_heads, cfg.hidden_size, cfg.intermediate_size, cfg.encoder_width,
+                           self.tokens_per_frame, self.n_query, self.mistral_proj.out_features, NB_SAMPLES, float(cfg.alpha),
+                           float(cfg.layer_norm_eps))
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().infv_vqf_create(C.byref(c), C.byref(h)))
+        self._vc = (h, device)
+        return h
+
+    def _vc_weights(self, device):
+        """ctypes view of the parameters (``infv_vqf_vc_weights``), rebuilt only when a parameter moved or changed in place."""
+        layers = self.qformer.bert.encoder.layer
+        src = [p for p in self.parameters()]
+        sig = (str(device),) + tuple((p.data_ptr(), p._version, p.dtype) for p in src)
+        cached = getattr(self, "_vc_w_cache", None)
+        if cached is not None and cached[0] == sig:
+            return cached[1], cached[2]
+        keep = []
+
+        def t(x):
+            y = _dev_f32(x, device)
+            keep.append(y)
+            return y.data_ptr()
+
+        lin = lambda m: _lib.Linear(t(m.weight), t(m.bias))
+        ln = lambda m: _lib.LayerNorm(t(m.weight), t(m.bias))
+        none_l, none_n = _lib.Linear(None, None), _lib.LayerNorm(None, None)
+        arr = (_lib.VqfVcLayer * len(layers))()
+        for i, layer in enumerate(layers):
+            a = layer.attention
+            x = layer.crossattention if layer.has_cross_attention else None
+            arr[i] = _lib.VqfVcLayer(
+                lin(a.self.query), lin(a.self.key), lin(a.self.value), lin(a.output.dense), ln(a.output.LayerNorm),
+                int(x is not None), 0,
+                lin(x.self.query) if x else none_l, lin(x.self.key) if x else none_l, lin(x.self.value) if x else none_l,
+                lin(x.output.dense) if x else none_l, ln(x.output.LayerNorm) if x else none_n,
+                lin(layer.intermediate_query.dense), lin(layer.output_query.dense), ln(layer.output_query.LayerNorm),
+                lin(layer.intermediate.dense), lin(layer.output.dense), ln(layer.output.LayerNorm))
+        w = _lib.VqfVcWeights(len(layers), 0, arr, lin(self.mistral_proj))
+        keep.append(arr)
+        self._vc_w_cache = (sig, w, keep)
+        return w, keep
+
+    def _vc_inputs(self, V: int, text_embeds, hidden_in) -> List[torch.Tensor]:
+        """Per video the encoder input rows [n_query + n_text_v, hidden] (``encode_tokens``' rule, video by video)."""
+        cfg = self.qformer.config
+
+        def per_video(x, what):
+            if x is None or isinstance(x, torch.Tensor):
+                return [x] * V
+            x = list(x)
+            if len(x) != V:
+                raise ValueError(f"{len(x)} {what} for {V} videos")
+            return x
+
+        rows = []
+        for v, (te, hi) in enumerate(zip(per_video(text_embeds, "text_embeds"), per_video(hidden_in, "hidden_in"))):
+            if hi is not None:
+                r = hi.reshape(-1, hi.size(-1))
+                if r.size(0) < self.n_query:
+                    raise ValueError(f"hidden_in of video {v} has {r.size(0)} rows, fewer than the {self.n_query} query tokens")
+            else:
+                r = self.query_tokens[0]
+                if te is not None:
+                    r = torch.cat([r.to(torch.float32), te.reshape(-1, te.size(-1)).to(device=r.device, dtype=torch.float32)], 0)
+            if r.size(-1) != cfg.hidden_size:
+                raise ValueError(f"encoder input rows of video {v} must have width {cfg.hidden_size}")
+            if r.size(0) - self.n_query > MAX_TXT_LEN:
+                raise ValueError(f"video {v} has {r.size(0) - self.n_query} text tokens, at most {MAX_TXT_LEN} are supported")
+            rows.append(r)
+        return rows
+
+    def encode_videos(self, videos: Sequence[torch.Tensor], text_embeds=None, hidden_in=None, new_video: bool = True,
+                      u: Optional[torch.Tensor] = None, memories: Optional[Sequence["VideoChat2Memory"]] = None,
+                      video_ids: Optional[Sequence[int]] = None, want_hidden: bool = False):
+        """Many videos through the VideoChat2 Q-former in ONE C call (``infv_vqf_vc_encode_videos``): the whole encoder, layer-major
+        over the packed chunks of every video, on the HIP path.
+
+        ``videos``: a list of [C_v, T*P, width] frame-token tensors that all share one T (a video may have no chunk).
+        ``text_embeds`` / ``hidden_in``: as in :meth:`encode_tokens`, one tensor for every video or a list with one entry per
+        video (entries may be None); every chunk of a video starts from the same rows.  ``memories[v]``: video v's
+        :class:`VideoChat2Memory` (by default a reused pool of the encoder; the model's own modules are untouched).
+        Returns (inputs_mistral [sum C_v, n_query, llm_hidden], per-video means [V, n_query, llm_hidden], per-video last hidden
+        states -- a list of [C_v, n_query + n_text_v, hidden] -- or None).  A video's outputs and memories do not depend on the
+        rest of the batch (bit for bit); they agree with looping :meth:`encode_tokens` to fp32 rounding.
+        ``u`` [sum C_v, n_cross, 512] float64; by default drawn from torch's global CPU generator exactly as that loop consumes
+        it (video by video, chunk by chunk, 512 + 512 per LTM instance, nothing on a new video's first chunk).  With
+        :meth:`use_device_rng` and ``u=None`` nothing is drawn on the host: cross layer i of video id ``video_ids[v]`` (default:
+        v) draws from stream ``(id + 1) * n_cross + i``; the model's own modules keep stream i."""
+        videos = list(videos)
+        V = len(videos)
+        if V == 0:
+            raise ValueError("encode_videos needs at least one video")
+        cfg = self.qformer.config
+        P, Q = self.tokens_per_frame, self.n_query
+        n_cross = len(self.qformer.cross_layers)
+        for v, f in enumerate(videos):
+            if f.dim() != 3 or f.size(2) != cfg.encoder_width or f.size(1) % P or f.size(1) == 0:
+                raise ValueError(f"videos[{v}] must be [C, T*{P}, {cfg.encoder_width}], got {tuple(f.shape)}")
+            if f.size(1) != videos[0].size(1):
+                raise ValueError(f"videos[{v}] has T = {f.size(1) // P}, videos[0] has T = {videos[0].size(1) // P}: "
+                                 "one call takes one chunk length")
+        T = videos[0].size(1) // P
+        counts = [int(f.size(0)) for f in videos]
+        total = sum(counts)
+        rows = self._vc_inputs(V, text_embeds, hidden_in)
+        text_len = [int(r.size(0)) - Q for r in rows]
+        use_ltm = cfg.alpha != 1.0 and n_cross > 0
+        if use_ltm and memories is not None:
+            memories = _check_vc_memories(self, memories, V)
+        if video_ids is not None and len(video_ids) != V:
+            raise ValueError(f"{len(video_ids)} video_ids for {V} videos")
+        if not all(f.is_cuda for f in videos):
+            raise RuntimeError("the VideoChat2 binding runs on the HIP device only (no CPU fallback)")
+        device = videos[0].device
+        llm = self.mistral_proj.out_features
+        if total == 0 and not (use_ltm and new_video):
+            return (torch.empty(0, Q, llm, device=device), torch.full((V, Q, llm), float("nan"), device=device),
+                    [torch.empty(0, Q + n, cfg.hidden_size, device=device) for n in text_len] if want_hidden else None)
+        frames = _dev_f32(torch.cat(videos) if V > 1 else videos[0], device)
+        hin = torch.cat([_dev_f32(r, device) for r in rows]).contiguous()
+        handles = None
+        if not use_ltm:
+            u = None                                          # (no memory: nothing is drawn)
+        else:
+            if memories is None:
+                while len(self._vc_memories) < V:
+                    self._vc_memories.append(VideoChat2Memory(self, device))
+                memories = self._vc_memories[:V]
+            for mem in memories:
+                mem._check(self, device)
+            handles = (C.c_void_p * (V * n_cross))()
+            for v, mem in enumerate(memories):
+                for i, eng in enumerate(mem.engines):
+                    eng.ensure_plan(T)
+                    handles[v * n_cross + i] = eng._h
+                mem.set_device_rng(self._device_rng_seed, (video_ids[v] if video_ids is not None else v)
+                                   if self._device_rng_seed is not None else None)
+            if u is None and self._device_rng_seed is None and bool(cfg.sticky):
+                u = draw_vc_uniforms(counts, [not new_video and mem.has_memory for mem in memories], n_cross)
+            if u is not None:
+                u = u.to(device=device, dtype=torch.float64).contiguous()
+                if tuple(u.shape) != (total, n_cross, NB_SAMPLES):
+                    raise ValueError(f"u must be [{total}, {n_cross}, {NB_SAMPLES}]")
+        w, keep = self._vc_weights(device)
+        n_rows = sum(c * (Q + n) for c, n in zip(counts, text_len))
+        hidden = torch.empty(n_rows, cfg.hidden_size, device=device, dtype=torch.float32) if want_hidden else None
+        proj = torch.empty(total, Q, llm, device=device, dtype=torch.float32)
+        mean = torch.empty(V, Q, llm, device=device, dtype=torch.float32)
+        cu = (C.c_int32 * (V + 1))(0, *_cumsum(counts))
+        tl = (C.c_int32 * V)(*text_len)
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().infv_vqf_vc_encode_videos(
+                self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()), T, C.byref(w),
+                C.c_void_p(hin.data_ptr()), C.cast(tl, C.c_void_p), C.c_void_p(0 if u is None else u.data_ptr()),
+                int(bool(new_video)), C.c_void_p(0 if hidden is None else hidden.data_ptr()), C.c_void_p(proj.data_ptr()),
+                C.c_void_p(mean.data_ptr()), stream))
+        del keep
+        hid = None
+        if want_hidden:
+            hid, r0 = [], 0
+            for c, n in zip(counts, text_len):
+                hid.append(hidden[r0:r0 + c * (Q + n)].view(c, Q + n, cfg.hidden_size))
+                r0 += c * (Q + n)
+        return proj, mean, hid
 
     # ------------------------------------------------------------------ encode_img after the vision encoder
     def encode_tokens(self, image_embeds: torch.Tensor, text_embeds: Optional[torch.Tensor] = None,
@@ -316,3 +564,62 @@ def encode_long_video_vc(model: VideoChat2Encoder, frame_tokens: torch.Tensor, n
         embs.append(emb)
         new_video = False
     return torch.mean(torch.stack(embs), dim=0, keepdim=True).squeeze(0), embs
+
+
+def batched_chunks_vc(n_frames: int, num_samples: int, tokens_per_frame: int) -> Optional[int]:
+    """Frames per chunk if ``torch.chunk(video, num_samples)`` cuts ``n_frames`` frames into equal chunks whose token count
+    the HIP contractions tile (a multiple of 32); None if the video has to take the per-chunk loop."""
+    if n_frames <= 0 or num_samples <= 0:
+        return None
+    T = -(-n_frames // num_samples)                         # torch.chunk: ceil-sized chunks, the last one may be shorter
+    if n_frames % T or (T * tokens_per_frame) % 32:
+        return None
+    return T
+
+
+def encode_long_videos_vc(model: VideoChat2Encoder, frame_tokens_list: Sequence[torch.Tensor], num_samples: int,
+                          text_embeds=None, hidden_in=None, memories: Optional[Sequence[VideoChat2Memory]] = None,
+                          video_ids: Optional[Sequence[int]] = None):
+    """Batched counterpart of :func:`encode_long_video_vc` over many videos: ``frame_tokens_list[v]`` [F_v, 196, width] is cut
+    by ``torch.chunk(video, num_samples)`` as the eval loop cuts it; the videos whose chunks are equal and tile (see
+    :func:`batched_chunks_vc`) go through :meth:`VideoChat2Encoder.encode_videos`, one call per chunk length; the others take
+    the per-chunk loop on the model's own modules.  ``text_embeds`` / ``hidden_in``: one for all or one per video.
+    ``memories`` / ``video_ids``: one per video, used by the batched ones.  The global generator is consumed video by video
+    as the loop over :func:`encode_long_video_vc` consumes it (nothing with :meth:`VideoChat2Encoder.use_device_rng`).
+    Returns a list of (mean [1, n_query, llm_hidden], per-chunk list) per video."""
+    V = len(frame_tokens_list)
+    P = model.tokens_per_frame
+    cfg = model.qformer.config
+    n_cross = len(model.qformer.cross_layers)
+    per_video = lambda x: list(x) if isinstance(x, (list, tuple)) else [x] * V
+    tes, his = per_video(text_embeds), per_video(hidden_in)
+    if len(tes) != V or len(his) != V:
+        raise ValueError("text_embeds / hidden_in: one for all videos or one per video")
+    if memories is not None and len(memories) != V:
+        raise ValueError(f"{len(memories)} memories for {V} videos")
+    if video_ids is not None and len(video_ids) != V:
+        raise ValueError(f"{len(video_ids)} video_ids for {V} videos")
+    host_u = cfg.alpha != 1.0 and bool(cfg.sticky) and model._device_rng_seed is None and n_cross > 0
+    out: List = [None] * V
+    groups: dict = {}
+    for v, ft in enumerate(frame_tokens_list):                  # in video order: the generator is consumed as the loop does
+        T = batched_chunks_vc(int(ft.size(0)), num_samples, P)
+        if T is None:
+            out[v] = encode_long_video_vc(model, ft, num_samples, tes[v], his[v])
+            continue
+        n_c = int(ft.size(0)) // T
+        u_v = draw_vc_uniforms([n_c], [False], n_cross) if host_u else None
+        groups.setdefault(T, []).append((v, ft.reshape(n_c, T * P, ft.size(-1)), u_v))
+    for T, items in groups.items():
+        idx = [v for v, _, _ in items]
+        proj, mean, _ = model.encode_videos(
+            [f for _, f, _ in items], [tes[v] for v in idx], [his[v] for v in idx], True,
+            torch.cat([u_v for _, _, u_v in items]) if host_u else None,
+            None if memories is None else [memories[v] for v in idx],
+            None if video_ids is None else [video_ids[v] for v in idx])
+        r0 = 0
+        for j, (v, f, _) in enumerate(items):
+            n_c = int(f.size(0))
+            out[v] = (mean[j:j + 1], [proj[r0 + c:r0 + c + 1] for c in range(n_c)])
+            r0 += n_c
+    return out
