@@ -541,7 +541,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     }
     const long M = (long)C * Q;                               // rows of the whole-video activations
     // ---- workspaces: whole-video activations + per-block scratch ----
-    const int rb_max = multi ? 128 : 64;                      // (batch invariant: the row count does not shape the GEMMs)
+    const int rb_max = multi ? kRowBlockVideos : kRowBlockVideo;   // (batch invariant: the row count does not shape the GEMMs)
     const int RB = C < rb_max ? C : rb_max;                   // chunks per row block of the query-token GEMMs
     // chunks per sub-batch of the short-term attention: the second contraction has few, long tiles per chunk
     // (rows/128 x d/128 = 18 at the headline shape, K = T*P), so pick the count whose tile total fills whole rounds
@@ -709,11 +709,11 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
             }
             if (use_ltm) {
                 HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
-                for (long m0 = 0; m0 < M; m0 += 32768) {       // merged = alpha * short + (1 - alpha) * long
+                for (long m0 = 0; m0 < M; m0 += kMergeRows) {  // merged = alpha * short + (1 - alpha) * long
                     QfEpilogue em{};
                     em.parts = vshort + m0 * Hd; em.nsplit = 1; em.ld_in = Hd; em.seg_cols = Hd;
                     em.scale = c.alpha; em.res_scale = (float)(1.0 - (double)c.alpha);
-                    em.residual = valong + m0 * Hd; em.ld_res = Hd; em.res_rows = (int)(M - m0 < 32768 ? M - m0 : 32768);
+                    em.residual = valong + m0 * Hd; em.ld_res = Hd; em.res_rows = (int)(M - m0 < kMergeRows ? M - m0 : kMergeRows);
                     em.out = vmerged + m0 * Hd; em.ld_out = Hd; em.M = em.res_rows; em.width = Hd; em.eps = c.ln_eps;
                     HIP_TRY(launch_qf_epilogue(em, stream));
                 }
@@ -882,8 +882,8 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
     }
     const long M = (long)C * Q, Tt = toff[C];
     const long chunk_k = (long)n_tokens * c.enc_width;
-    const int RB = C < 128 ? C : 128;                          // chunks per row block of the token GEMMs (batch invariant: any size)
-    const long TB = Tt < 16384 ? Tt : 16384;                   // text rows per block of the text FFN
+    const int RB = C < kRowBlockVideos ? C : kRowBlockVideos;  // chunks per row block of the token GEMMs (batch invariant: any size)
+    const long TB = Tt < kTextFfnRows ? Tt : kTextFfnRows;     // text rows per block of the text FFN
     long tb_max = 0;                                           // text rows of the largest row block
     for (int c0 = 0; c0 < C; c0 += RB) { const int c1 = c0 + RB < C ? c0 + RB : C; tb_max = std::max<long>(tb_max, toff[c1] - toff[c0]); }
     const int NB = pick_short_nb(h, C, n_tokens);
@@ -1009,11 +1009,11 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
             }
             if (use_ltm) {
                 HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
-                for (long m0 = 0; m0 < M; m0 += 32768) {       // merged = alpha * short + (1 - alpha) * long
+                for (long m0 = 0; m0 < M; m0 += kMergeRows) {  // merged = alpha * short + (1 - alpha) * long
                     QfEpilogue em{};
                     em.parts = vshort + m0 * Hd; em.nsplit = 1; em.ld_in = Hd; em.seg_cols = Hd;
                     em.scale = c.alpha; em.res_scale = (float)(1.0 - (double)c.alpha);
-                    em.residual = valong + m0 * Hd; em.ld_res = Hd; em.res_rows = (int)(M - m0 < 32768 ? M - m0 : 32768);
+                    em.residual = valong + m0 * Hd; em.ld_res = Hd; em.res_rows = (int)(M - m0 < kMergeRows ? M - m0 : kMergeRows);
                     em.out = vmerged + m0 * Hd; em.ld_out = Hd; em.M = em.res_rows; em.width = Hd; em.eps = c.ln_eps;
                     HIP_TRY(launch_qf_epilogue(em, stream));
                 }

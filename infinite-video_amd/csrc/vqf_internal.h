@@ -8,6 +8,13 @@ namespace infv {
 
 constexpr int kQfMaxSeg = 4;
 
+// Host-side seams of the layer-major calls (vqf_capi.hip): a large call is cut into pieces of these sizes, each with its own
+// offset arithmetic.  tests/golden/seam_cases.py reads them from here.
+constexpr int kRowBlockVideo = 64;       // chunks per row block of the query-token GEMMs, infv_vqf_encode_video
+constexpr int kRowBlockVideos = 128;     // ... of the batch-invariant calls (infv_vqf_encode_videos, infv_vqf_vc_encode_videos)
+constexpr long kTextFfnRows = 16384;     // packed text rows per block of the VideoChat2 text FFN
+constexpr long kMergeRows = 32768;       // rows per launch of the alpha-merge epilogue
+
 // C[z][m][o] (+)= sum_k A[b][m][k] * Bop[b][k][o]   for z = b * splitk + s, k in split s.
 // The batch index b = bo * inner + bi addresses operands as  X + bi * strideX + bo * strideX2  (inner = 0: one level).
 //   NT: Bop[k][o] = B[o][k]  (B rows are output columns; up to kQfMaxSeg row segments of seg_rows rows each)
@@ -112,6 +119,7 @@ hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long 
 
 // out[m][:] = mean over nb of in[b][m][:]
 hipError_t launch_qf_mean(const float* in, int nb, long n, float* out, hipStream_t stream);
+constexpr int kMeanSegs = 256;           // videos per launch of launch_qf_mean_segments (the table travels in kernel arguments)
 // out[v][:] = mean over b in [cu[v], cu[v+1]) of in[b][:] for v < V, summed in b order as qf_mean_kernel (cu: host array [V+1])
 hipError_t launch_qf_mean_segments(const float* in, const int32_t* cu, int V, long n, float* out, hipStream_t stream);
 

@@ -736,7 +736,6 @@ hipError_t launch_qf_mean(const float* in, int nb, long n, float* out, hipStream
 }
 
 // one video per grid row: its chunks' rows summed in chunk order, / count (qf_mean_kernel's arithmetic on the video's rows)
-constexpr int kMeanSegs = 256;
 struct MeanSegs { int32_t cu[kMeanSegs + 1]; };
 __global__ __launch_bounds__(256) void qf_mean_segments_kernel(const float* __restrict__ in, MeanSegs sg, long n, float* __restrict__ out) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;

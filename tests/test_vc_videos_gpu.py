@@ -9,15 +9,16 @@ import pytest
 import torch
 
 from infinite_video_amd import synth
-from oracle.ltm_oracle import ClosedFormOracle, DenseOracle, categorical_probs, inverse_cdf_draw
+from oracle.ltm_oracle import DenseOracle, inverse_cdf_draw
 from oracle.videochat2_oracle import VideoChat2Oracle
 from tests.conftest import record_parity
+# the small shape, its synthetic videos and the margin-safe oracle runs are shared with the seam tests (one copy)
+from tests.golden.seam_cases import (BASE, MARGIN, S, OracleRun, draw_margins, n_cross_of, small_oracle, small_reference,
+                                     small_video)
 from tests.golden.vc_cases import VC_CASE, chunk_uniforms, load_vc_golden, vc_inputs
 
 pytestmark = pytest.mark.gpu
 ATOL = 2e-4              # test_vc_gpu.py's ATOL, DESIGN.md section 5
-MARGIN = 2e-5            # the project's bound on probabilities: draws with a wider margin must agree
-S = synth.NB_SAMPLES
 
 
 def dev0():
@@ -108,66 +109,6 @@ def test_self_attention_kernel_against_fp64(H):
 
 
 # ------------------------------------------------------------------------------------------------ oracle-side helpers
-def draw_margins(probs, u):
-    """Distance of every uniform to the nearest edge of the oracle's fp32 cdf (``inverse_cdf_draw``'s construction)."""
-    probs = np.asarray(probs, np.float32)
-    run, cdf = np.float32(0), np.empty(len(probs), np.float32)
-    for j in range(len(probs)):
-        run = np.float32(run + probs[j])
-        cdf[j] = run
-    cdf = (cdf / run).astype(np.float32)
-    cdf[-1] = np.float32(1)
-    edges = np.concatenate([[0.0], cdf.astype(np.float64)])
-    return np.abs(np.asarray(u, np.float64)[:, None] - edges[None, :]).min(1)
-
-
-class OracleRun:
-    """One video through ``VideoChat2Oracle`` chunk by chunk, keeping per chunk the outputs and per LTM step the oracle's own
-    bins and margins.  ``bins`` [C][n_cross][S] hands every LTM step those bins (``ClosedFormOracle.step``'s ``bins_override``);
-    ``safe_rng``: draw the uniforms here, step by step, re-drawing any that falls within MARGIN of an edge of the oracle's cdf."""
-
-    def __init__(self, orc, chunks, h0, u=None, bins=None, safe_rng=None):
-        self.hidden, self.proj, self.bins, self.margin, self.u = [], [], [], [], []
-        layers = sorted(orc.ltm)
-        state = {"c": 0}
-        rec_b, rec_m, rec_u = {}, {}, {}
-
-        def patched(j, o):
-            def step(k, q, new_doc, uu=None):
-                stepping = o.sticky and o.B_past is not None and not new_doc
-                if stepping and safe_rng is not None:
-                    probs = categorical_probs(torch.from_numpy(o.sticky_p_raw(o.S_prev))).numpy()
-                    uu = safe_rng.random(S)
-                    for _ in range(64):
-                        bad = draw_margins(probs, uu) < MARGIN
-                        if not bad.any():
-                            break
-                        uu[bad] = safe_rng.random(int(bad.sum()))
-                ov = None if bins is None or not stepping else bins[state["c"]][j]
-                out = ClosedFormOracle.step(o, k, q, new_doc, uu, bins_override=ov)
-                if stepping:
-                    rec_b[j], rec_m[j], rec_u[j] = o.last_bins.copy(), draw_margins(o.last_probs, uu), np.asarray(uu).copy()
-                return out
-            return step
-
-        for j, l in enumerate(layers):
-            orc.ltm[l].step = patched(j, orc.ltm[l])
-        try:
-            for c, k in enumerate(chunks):
-                state["c"] = c
-                rec_b.clear(), rec_m.clear(), rec_u.clear()
-                hid, pr = orc.encode_chunk(k, h0, c == 0, None if u is None else u[c])
-                self.hidden.append(hid)
-                self.proj.append(pr)
-                self.bins.append([rec_b.get(j) for j in range(len(layers))])
-                self.margin.append([rec_m.get(j) for j in range(len(layers))])
-                self.u.append([rec_u.get(j) for j in range(len(layers))])
-        finally:
-            for l in layers:
-                del orc.ltm[l].step
-        self.Bsum = [orc.ltm[l].B_past.astype(np.float64).sum(1) if orc.ltm[l].B_past is not None else None for l in layers]
-
-
 def armed(mem, n_chunks):
     return [e.set_trace(n_chunks) if n_chunks else None for e in mem.engines]
 
@@ -306,8 +247,6 @@ def test_golden_video_inside_a_batch():
 
 
 # ------------------------------------------------------------------------------------------------ 4. small shapes
-BASE = dict(hidden=128, heads=2, inter=256, enc_width=64, P=4, T=16, N=32, proj=64, n_layers=4, cross_freq=2, n_query=40,
-            texts=(5, 0, 17), counts=(2, 0, 3), alpha=0.75, sticky=True, tau=0.75)
 SMALL = {
     "base": {},
     "T8_exact_fp32": dict(T=8),
@@ -332,45 +271,6 @@ def small_setup(dev, **over):
                           tokens_per_frame=s["P"])
     m.load_reference_state_dict(w)
     return s, w, m.to(dev).eval()
-
-
-def small_video(s, v, n_chunks, n_text):
-    """(chunks [C, T*P, width], encoder input rows [n_query + n_text, hidden]) of synthetic video ``v``."""
-    k = np.stack([synth.frame_tokens(c, s["T"], s["P"], s["enc_width"], seed=synth.SEED_K + 1000 * (v + 1)) for c in range(n_chunks)]) \
-        if n_chunks else np.zeros((0, s["T"] * s["P"], s["enc_width"]), np.float32)
-    w = synth.videochat2_qformer_weights(s["n_layers"], s["hidden"], s["inter"], s["enc_width"], s["cross_freq"], s["n_query"],
-                                         s["proj"], seed=synth.SEED_VC + 31)
-    rows = [w["query_tokens"][0] * np.float32(50.0)]
-    if n_text:
-        rows.append(synth.layer_query(40 + v, n_text, s["hidden"]))
-    return k, np.concatenate(rows, 0).astype(np.float32)
-
-
-def small_oracle(s, w):
-    return VideoChat2Oracle(w, s["N"], s["tau"], s["alpha"], s["sticky"], s["n_layers"], s["cross_freq"], s["heads"], s["n_query"], s["P"])
-
-
-def n_cross_of(s):
-    return len(range(0, s["n_layers"], s["cross_freq"]))
-
-
-def small_reference(s, w, vids, seed):
-    """Oracle runs of the videos with uniforms drawn step by step so that every margin is at least MARGIN (asserted).  With
-    ~127 cdf edges a uniform falls within 2e-5 of one with probability ~0.5 %, so no seed of a plain generator clears the
-    thousands of draws of a run: the uniforms that would are re-drawn, deterministically from ``seed``."""
-    runs, us = [], []
-    nx = n_cross_of(s)
-    for v, (k, h0) in enumerate(vids):
-        orun = OracleRun(small_oracle(s, w), list(k), h0, safe_rng=np.random.default_rng(seed + v))
-        u = np.zeros((len(k), nx, S))
-        for c in range(len(k)):
-            for j in range(nx):
-                if orun.u[c][j] is not None:
-                    u[c, j] = orun.u[c][j]
-                    assert float(orun.margin[c][j].min()) >= MARGIN          # the precondition of exact draws
-        runs.append(orun)
-        us.append(u)
-    return runs, np.concatenate(us)
 
 
 @pytest.mark.parametrize("name", list(SMALL))
