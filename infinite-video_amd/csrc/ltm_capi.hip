@@ -2148,6 +2148,10 @@ int infv_ltm_import_state(infv_ltm_handle h, int32_t layer, const float* B, cons
     HIP_TRY(launch_reproject(h->B[h->cur].as<float>() + (size_t)layer * h->N * h->d, h->N, h->d, h->dm, 1, one,
                              h->KV[h->cur].as<float>() + (size_t)layer * h->N * 2 * h->dm, stream));
     h->has_memory = true;
+    // the fused chain's scores (Sp) describe the memory this one replaces: nothing may hand them on any more -- neither
+    // export_chain_state nor the one-shot carry of an import_chain_state that no call consumed
+    h->last_fast = false;
+    h->carry_scores = false;
     return INFV_OK;
 }
 
