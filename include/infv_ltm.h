@@ -26,7 +26,7 @@
  *     the ABI.  infv_ltm_last_error() returns a thread-local description;
  *   - a handle is not re-entrant (the reference module is mutable, single-threaded state);
  *   - all floating-point data is fp32, row-major, batch size 1 (reference
- *     long_term_attention_gibbs.py:208,346); only the frame tokens may be bf16 (infv_ltm_set_token_dtype).
+ *     long_term_attention_gibbs.py:208,346); only the frame tokens may be fp16 or bf16 (infv_ltm_set_token_dtype).
  */
 #ifndef INFV_LTM_H
 #define INFV_LTM_H
@@ -172,12 +172,19 @@ int infv_ltm_set_psi_plan(infv_ltm_handle h, const infv_ltm_psi_plan* plan);
 int infv_ltm_reset(infv_ltm_handle h);
 int infv_ltm_has_memory(infv_ltm_handle h);                    /* 1 / 0 */
 
-/* Element type of the frame tokens `k` handed to pool / forward / consolidate.  The reference's tokens are fp32
- * (infinityqa.py:317-322 concatenates the image Q-former's fp32 outputs).  A producer that stores them as bf16
- * halves the bytes of the only HBM-heavy stream of the path; the pooled frames and everything after stay fp32,
- * so results differ from the fp32-token run only by the rounding of the tokens themselves (2^-9 relative each,
- * averaged over P tokens).  Default fp32; set before the first call that takes `k`. */
-typedef enum { INFV_TOKENS_F32 = 0, INFV_TOKENS_BF16 = 1 } infv_token_dtype;
+/* Element type of the frame tokens `k` handed to pool / forward / consolidate.  The reference concatenates fp32
+ * tensors (infinityqa.py:317-322), but their values come out of an fp16 producer: the ViT is .half() and the image
+ * Q-former runs under fp16 autocast (blip2.py:37-43, infinityqa.py:256-259).  Three layouts are read in place:
+ *   INFV_TOKENS_F32   4 bytes per element.
+ *   INFV_TOKENS_F16   2 bytes per element and nothing lost: every fp16 value (subnormals included) is exact in fp32, it
+ *                     is widened by the hardware conversion, and the sum, the division by P and everything after run
+ *                     in fp32 in the same order -- every result has the bits of the fp32-token run on the same values.
+ *   INFV_TOKENS_BF16  2 bytes per element; results differ from the fp32-token run only by the rounding of the tokens
+ *                     themselves where the producer rounded them (2^-9 relative each, averaged over P tokens).
+ * Either half format halves the bytes of the only HBM-heavy stream of the path; the pooled frames and everything after
+ * stay fp32.  fp16 and bf16 tokens must be 16-byte aligned where the video Q-former reads them (infv_vqf.h).  Codes not
+ * listed here (2 among them) are refused.  Default fp32; set before the first call that takes `k`. */
+typedef enum { INFV_TOKENS_F32 = 0, INFV_TOKENS_BF16 = 1, INFV_TOKENS_F16 = 3 } infv_token_dtype;
 int infv_ltm_set_token_dtype(infv_ltm_handle h, int32_t dtype);
 
 /* Frame mean-pool, long_term_attention_gibbs.py:304:  k [n_frames, P, d] -> kbar [n_frames, d] (fp32). */

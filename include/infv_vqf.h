@@ -4,7 +4,7 @@
  * `encode_video`, infty-Video-LLaMA/InfVideoLLaMA/models/infinityqa.py:280-344).  These entry points are what the
  * Python mirror (infinite_video_amd/video_qformer.py) binds with ctypes.  Plain pointers and sizes only; all
  * pointers are DEVICE pointers (fp32, row-major) unless stated; every call is asynchronous on `stream`.  Only the frame tokens
- * (`frames`) may be bf16 instead (infv_vqf_set_token_dtype).
+ * (`frames`) may be fp16 or bf16 instead (infv_vqf_set_token_dtype).
  * Errors: int status as in infv_ltm.h, message via infv_ltm_last_error().
  *
  * Scope: the query-token-only, eval-mode, all-ones-mask case the video Q-former is run in
@@ -65,12 +65,16 @@ int infv_vqf_destroy(infv_vqf_handle h);
 int infv_vqf_set_precision(infv_vqf_handle h, int32_t exact_fp32);
 
 /* Element type of every `frames` argument below: an infv_token_dtype (infv_ltm.h), default INFV_TOKENS_F32; anything else is
- * refused with INFV_ERR_INVALID and the handle keeps its setting.  A bf16 `frames` pointer must be 16-byte aligned (refused
- * otherwise, before any device work).  With bf16 tokens the split-bf16 contractions read the caller's buffer in place (a bf16
+ * refused with INFV_ERR_INVALID and the handle keeps its setting.  An fp16 or bf16 `frames` pointer must be 16-byte aligned
+ * (refused otherwise, before any device work).  With fp16 tokens (INFV_TOKENS_F16, what the reference's fp16 producer holds)
+ * one pass reads the caller's buffer at 2 bytes per element and writes the hi / lo planes, their transposed copies and the
+ * frame means -- an fp16 value is exactly hi + lo (11 = 8 + 3 significand bits), so planes, means and every result are bit for
+ * bit those of the same values passed as fp32, and the contractions are the three-product ones.  With bf16 tokens the split-bf16 contractions read the caller's buffer in place (a bf16
  * token is its own hi plane and its lo plane is exactly zero): one pass writes the transposed copy and the frame means, and
  * both contractions run two bf16 MFMA products instead of three.  Results are bit for bit those of the same values passed as
  * fp32.  Where the split path does not apply (exact fp32, token counts that are no multiple of 64) the tokens are copied to
- * fp32 in a workspace of the handle first.  Every shape accepted with fp32 tokens is accepted with bf16 tokens. */
+ * fp32 in a workspace of the handle first (fp16 and bf16 alike).  Every shape accepted with fp32 tokens is accepted with
+ * fp16 and with bf16 tokens. */
 int infv_vqf_set_token_dtype(infv_vqf_handle h, int32_t dtype);
 
 /* Layer 0's hidden states entering the cross-attention come from the learned query tokens and the weights only, so
@@ -204,7 +208,7 @@ typedef struct {
  * lengths, and whether its chunks come in one call or in two (new_video = 0 on the second).  Values agree with the per-chunk
  * binding to fp32 rounding.  Token counts that are a multiple of 32 but not of 64 take the exact-fp32 contractions.
  * Refused before any device work or memory change: bad cu, a null or repeated LTM handle, negative text_len (INFV_ERR_INVALID);
- * n_query + text_len[v] > 608, n_layers > 24, T * tokens_per_frame not a multiple of 32, bf16 tokens set on the handle
+ * n_query + text_len[v] > 608, n_layers > 24, T * tokens_per_frame not a multiple of 32, fp16 or bf16 tokens set on the handle
  * (INFV_ERR_UNSUPPORTED). */
 int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
                               int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len,

@@ -18,6 +18,10 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
             return ::infv::fail(INFV_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
+// frame-token element types (infv_token_dtype): the codes the entry points accept, and bytes per element
+inline bool token_dtype_known(int dtype) { return dtype == INFV_TOKENS_F32 || dtype == INFV_TOKENS_BF16 || dtype == INFV_TOKENS_F16; }
+inline size_t token_bytes(infv_token_dtype tok) { return tok == INFV_TOKENS_F32 ? 4 : 2; }
+
 struct DeviceBuf {
     void* p = nullptr;
     size_t bytes = 0;

@@ -172,7 +172,7 @@ struct infv_ltm_s {
     // error word of the persistent chain kernel: pinned host memory mapped into the device, so a time-out is
     // visible to the host without any synchronisation or copy
     unsigned int* err_host = nullptr; unsigned int* err_dev = nullptr;
-    int k_bf16 = 0;                     // frame tokens arrive as bf16 (infv_ltm_set_token_dtype)
+    infv_token_dtype tok = INFV_TOKENS_F32;   // element type of the frame tokens `k` (infv_ltm_set_token_dtype)
     bool v_split = false;               // INFV_VPROJ_SPLIT=1 at create: V' half of the sub-batch projection as a split-bf16 contraction
     // Where the V' half of a sub-batch's projection runs.  Default (round 3): inside the side stream's one [V' | S'] GEMM.  The
     // UC stream (V' GEMM -> softmax weights -> update, serial per sub-batch) was the second-longest stream of the pipeline
@@ -694,8 +694,8 @@ int infv_ltm_has_memory(infv_ltm_handle h) {
 
 int infv_ltm_set_token_dtype(infv_ltm_handle h, int32_t dtype) {
     if (int rc = check_handle(h)) return rc;
-    if (dtype != INFV_TOKENS_F32 && dtype != INFV_TOKENS_BF16) return fail(INFV_ERR_INVALID, "set_token_dtype: unknown dtype %d", dtype);
-    h->k_bf16 = dtype == INFV_TOKENS_BF16;
+    if (!token_dtype_known(dtype)) return fail(INFV_ERR_INVALID, "set_token_dtype: unknown dtype %d", dtype);
+    h->tok = static_cast<infv_token_dtype>(dtype);
     return INFV_OK;
 }
 
@@ -703,7 +703,7 @@ int infv_ltm_pool(infv_ltm_handle h, const void* k, int64_t n_frames, float* kba
     if (int rc = check_handle(h)) return rc;
     if (!k || !kbar || n_frames < 0) return fail(INFV_ERR_INVALID, "pool: bad arguments");
     Timed t_(h->prof, INFV_KERNEL_POOL, static_cast<hipStream_t>(stream));
-    HIP_TRY(launch_pool(k, h->k_bf16, kbar, n_frames, h->P, h->d, static_cast<hipStream_t>(stream)));
+    HIP_TRY(launch_pool(k, h->tok, kbar, n_frames, h->P, h->d, static_cast<hipStream_t>(stream)));
     return INFV_OK;
 }
 
@@ -726,13 +726,13 @@ int infv_ltm_pool_rows(infv_ltm_handle h, const void* k, int32_t n_chunks, int32
     if (pool_rows2_supported(h->d)) {
         static const int wgs = [] { const char* e = exp_env("INFV_PR_WGS"); return e ? atoi(e) : 0; }();      // (tools/pool_cus.py)
         static const int pad = [] { const char* e = exp_env("INFV_PR_PAD"); return e ? atoi(e) : 84 * 1024; }();
-        HIP_TRY(launch_pool_rows2(k, h->k_bf16, n_chunks, T, h->P, h->d, plan->inf.view(), R, stream, 8, pad, wgs));
+        HIP_TRY(launch_pool_rows2(k, h->tok, n_chunks, T, h->P, h->d, plan->inf.view(), R, stream, 8, pad, wgs));
         return INFV_OK;
     }
     // widths without a pool_rows2 shape: the two kernels, one chunk group at a time through the pooled-frame workspace
     const size_t need = (size_t)n_chunks * T * h->d * sizeof(float);
     if (need > h->kbar_side[0].bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->kbar_side[0].reserve(need)); }
-    HIP_TRY(launch_pool(k, h->k_bf16, h->kbar_side[0].as<float>(), (int64_t)n_chunks * T, h->P, h->d, stream));
+    HIP_TRY(launch_pool(k, h->tok, h->kbar_side[0].as<float>(), (int64_t)n_chunks * T, h->P, h->d, stream));
     HIP_TRY(launch_rows(h->kbar_side[0].as<float>(), n_chunks, T, h->d, plan->inf.view(), R, stream));
     return INFV_OK;
 }
@@ -856,7 +856,7 @@ int infv_ltm_forward(infv_ltm_handle h, const void* k, int32_t T, const float* q
 int infv_ltm_forward_into(infv_ltm_handle h, const void* k, int32_t token_dtype, int32_t T, float* kbar, const float* q, int32_t Q,
                           const infv_ltm_proj* proj, const double* u, float* ctx, void* stream) {
     if (int rc = check_handle(h)) return rc;
-    if (token_dtype != INFV_TOKENS_F32 && token_dtype != INFV_TOKENS_BF16) return fail(INFV_ERR_INVALID, "forward_into: unknown token dtype %d", token_dtype);
+    if (!token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "forward_into: unknown token dtype %d", token_dtype);
     if (T <= 0 || !k || !kbar) return fail(INFV_ERR_INVALID, "forward_into: T must be positive, k and kbar non-null");
     if (int rc = precheck_step(h, q, proj, ctx, T, Q, u, true)) return rc;
     if (int rc = infv_ltm_set_token_dtype(h, token_dtype)) return rc;
@@ -1578,7 +1578,7 @@ int consolidate_sub_batches(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pi
                 const bool want_planes = cc.planes_in_pool && (long)nb * (long)rows >= 1024;
                 bool done = false;
                 Timed t_(h->prof, INFV_KERNEL_POOL, pools);
-                HIP_TRY(launch_pool_rows2(k + c0 * cc.chunk_k, h->k_bf16, nb, T, h->P, h->d, plan.inf.view(), h->R_ws[rset].as<float>(),
+                HIP_TRY(launch_pool_rows2(k + c0 * cc.chunk_k, h->tok, nb, T, h->P, h->d, plan.inf.view(), h->R_ws[rset].as<float>(),
                                           pools, cc.pr_u, cc.pr_pad, cc.pr_wgs, want_planes ? pl : nullptr, &done));
                 planes_by_pool[b] = done;
             }
@@ -1589,7 +1589,7 @@ int consolidate_sub_batches(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pi
         if (cc.split_pool && p_pending[set]) HIP_TRY(hipStreamWaitEvent(pools, h->ev_p[set], 0));
         if (!(skip_mask() & 1)) {
             Timed t_(h->prof, INFV_KERNEL_POOL, pools);
-            HIP_TRY(launch_pool(k + c0 * cc.chunk_k, h->k_bf16, h->kbar_side[set].as<float>(), (int64_t)nb * T, h->P, h->d, pools, kPoolPad));
+            HIP_TRY(launch_pool(k + c0 * cc.chunk_k, h->tok, h->kbar_side[set].as<float>(), (int64_t)nb * T, h->P, h->d, pools, kPoolPad));
         }
         if (cc.split_pool) HIP_TRY(hipEventRecord(h->ev_pool[set], pools));
         return INFV_OK;
@@ -1643,7 +1643,7 @@ int consolidate_sub_batches(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pi
             if (cc.planes_call) for (int i = 0; i < 3; ++i) pc.plane[i] = h->planes_all[i].p;
             pc.done = h->pool_done.as<unsigned int>();
             Timed t_(h->prof, INFV_KERNEL_POOL, pools);
-            HIP_TRY(launch_pool_rows2_call(k + first_c * cc.chunk_k, h->k_bf16, T, h->P, h->d, plan.inf.view(), pc, pools, cc.pr_u, cc.pr_pad));
+            HIP_TRY(launch_pool_rows2_call(k + first_c * cc.chunk_k, h->tok, T, h->P, h->d, plan.inf.view(), pc, pools, cc.pr_u, cc.pr_pad));
         }
         if (int rc = stage_pool(0)) return rc;
         if (n_batches > 1)
@@ -1748,7 +1748,7 @@ static int consolidate_impl(infv_ltm_handle h, const void* k_, const float* kbar
     ConsolidateCall cc{};
     cc.plan = plan; cc.k = k; cc.kbar_pre = kbar_pre; cc.n_chunks = n_chunks; cc.T = T; cc.Q = Q; cc.q = q; cc.proj = proj; cc.pp = &pp;
     cc.u = u; cc.ctx = ctx; cc.stream = stream; cc.stream_ = stream_;
-    cc.chunk_k = (size_t)T * h->P * h->d * (h->k_bf16 ? 2 : 4);
+    cc.chunk_k = (size_t)T * h->P * h->d * token_bytes(h->tok);
     cc.chunk_ctx = (size_t)h->L * Q * h->dm;
     cc.chunk_u = (size_t)h->L * h->S;
     if (new_doc) infv_ltm_reset(h);
@@ -1792,7 +1792,7 @@ constexpr int kVideoGroup = 256;
 // frame means, so the dtype does not enter)
 bool same_config(infv_ltm_handle a, infv_ltm_handle b, bool tokens) {
     return a->N == b->N && a->H == b->H && a->dh == b->dh && a->d == b->d && a->P == b->P && a->L == b->L && a->S == b->S &&
-           (a->cfg.sticky != 0) == (b->cfg.sticky != 0) && (!tokens || a->k_bf16 == b->k_bf16);
+           (a->cfg.sticky != 0) == (b->cfg.sticky != 0) && (!tokens || a->tok == b->tok);
 }
 
 bool same_plan(const Plan& a, const Plan& b) {
@@ -1852,7 +1852,7 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
         for (int v = 0; v < V; ++v) infv_ltm_reset(hs[v]);
     if (total == 0) return INFV_OK;
     const char* k = static_cast<const char*>(k_);
-    const size_t chunk_k = (size_t)T * h0->P * h0->d * (h0->k_bf16 ? 2 : 4), chunk_kbar = (size_t)T * h0->d;
+    const size_t chunk_k = (size_t)T * h0->P * h0->d * token_bytes(h0->tok), chunk_kbar = (size_t)T * h0->d;
     const size_t chunk_ctx = (size_t)h0->L * Q * h0->dm, chunk_u = (size_t)h0->L * h0->S;
     bool batched = videos_supported(h0->N, h0->d, h0->dm, h0->L, h0->S);
     batched = batched && !plans[0]->dense.on;
@@ -1935,7 +1935,7 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
             const VideoStep vs{h0->vid_tab.as<VideoDesc>(), s, n, mask_step};
             {
                 Timed t_(h0->prof, INFV_KERNEL_POOL, stream);
-                if (tokens) HIP_TRY(launch_pool_videos(k, h0->k_bf16, vs, T, h0->P, d, h0->vid_kbar.as<float>(), stream));
+                if (tokens) HIP_TRY(launch_pool_videos(k, h0->tok, vs, T, h0->P, d, h0->vid_kbar.as<float>(), stream));
                 else HIP_TRY(launch_gather_videos(kbar, vs, T, d, h0->vid_kbar.as<float>(), stream));
             }
             {

@@ -27,8 +27,8 @@ namespace infv {
 //    1 KiB contiguous; P loads per lane are independent, so the whole 32 KiB of a unit is in
 //    flight at once.  This is the only HBM-heavy stage of the path (25.2 MB per chunk).
 // ======================================================================================
-// Tokens as the producer stores them: fp32 (the reference's layout) or bf16 (half the HBM bytes of the only heavy
-// stream of the path; every bf16 value is exact in fp32, the sum runs in fp32 in the same order).
+// Tokens as the producer stores them: fp32 (the reference's layout), or fp16 / bf16 (half the HBM bytes of the only heavy
+// stream of the path; every fp16 and every bf16 value is exact in fp32, the sum runs in fp32 in the same order).
 typedef unsigned int uintx4_t __attribute__((ext_vector_type(4)));
 struct TokF32 {
     typedef floatx4 vec;                               // 4 columns per lane
@@ -55,10 +55,36 @@ struct TokBF16 {
     }
 };
 
-template <int UNROLL, int NT, class Tok = TokF32>
-__global__ __launch_bounds__(NT) void pool_frames_kernel(const void* __restrict__ k_,
-                                                          float* __restrict__ kbar,
-                                                          long n_units, int P, int d4, int slices) {
+// fp16 as the reference's producer holds it (.half() ViT, fp16 autocast): widened by the hardware conversion (v_cvt_f32_f16 is
+// exact for every fp16 value, subnormals included -- they are normal numbers in fp32), so everything behind widen() sees the
+// values an fp32 copy of the tokens would hold.
+typedef _Float16 halfx4 __attribute__((ext_vector_type(4)));
+struct TokF16 {
+    typedef uintx2 vec;                                // 4 fp16 columns per lane (8 bytes)
+    // (the whole 8 bytes are reinterpreted at once: __builtin_bit_cast of ONE component of the vector, `v.y`, reads the vector's
+    //  first dword with this compiler -- caught by tests/test_f16_tokens_ltm_gpu.py)
+    static __device__ inline floatx4 widen(uintx2 v) { return __builtin_convertvector(__builtin_bit_cast(halfx4, v), floatx4); }
+    static __device__ inline uintx2 load_nt(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+        return __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 2 /* nt */);
+    }
+};
+
+// tok -> the token type: `f` is a generic callable taking a value of TokF32 / TokBF16 / TokF16
+template <class F>
+static hipError_t with_token_type(infv_token_dtype tok, F f) {
+    switch (tok) {
+        case INFV_TOKENS_F32: return f(TokF32{});
+        case INFV_TOKENS_BF16: return f(TokBF16{});
+        case INFV_TOKENS_F16: return f(TokF16{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// (the kernels' bodies are __device__ templates: the fp32 / bf16 kernels are instantiations over the token type, the fp16 ones are
+//  kernels of their own name over the same body -- the shipped library's kernel census counts the former by name)
+template <int UNROLL, int NT, class Tok>
+__device__ __forceinline__ void pool_frames_body(const void* __restrict__ k_, float* __restrict__ kbar,
+                                                 long n_units, int P, int d4, int slices) {
     typedef typename Tok::vec tvec;
     const int lane = threadIdx.x & 63;
     // grid-stride over units: with a full grid every wave takes exactly one unit; a smaller grid throttles the kernel
@@ -84,14 +110,27 @@ __global__ __launch_bounds__(NT) void pool_frames_kernel(const void* __restrict_
     }
 }
 
+template <int UNROLL, int NT, class Tok = TokF32>
+__global__ __launch_bounds__(NT) void pool_frames_kernel(const void* __restrict__ k_,
+                                                          float* __restrict__ kbar,
+                                                          long n_units, int P, int d4, int slices) {
+    pool_frames_body<UNROLL, NT, Tok>(k_, kbar, n_units, P, d4, slices);
+}
+template <int UNROLL, int NT>
+__global__ __launch_bounds__(NT) void pool_frames_f16_kernel(const void* __restrict__ k_, float* __restrict__ kbar,
+                                                              long n_units, int P, int d4, int slices) {
+    pool_frames_body<UNROLL, NT, TokF16>(k_, kbar, n_units, P, d4, slices);
+}
+template <int UNROLL, int NT, class Tok> struct PoolFramesFn { static auto get() { return pool_frames_kernel<UNROLL, NT, Tok>; } };
+template <int UNROLL, int NT> struct PoolFramesFn<UNROLL, NT, TokF16> { static auto get() { return pool_frames_f16_kernel<UNROLL, NT>; } };
+
 // `lds_pad` bytes of (unused) dynamic LDS per workgroup cap how many of them a CU hosts, so that a
 // latency-critical kernel on another stream always finds wave slots and LDS (see consolidate()).
 template <class Tok>
 static hipError_t launch_pool_t(const void* k, float* kbar, int64_t n_frames, int P, int d, hipStream_t stream, int lds_pad);
 
-hipError_t launch_pool(const void* k, int k_bf16, float* kbar, int64_t n_frames, int P, int d, hipStream_t stream, int lds_pad) {
-    return k_bf16 ? launch_pool_t<TokBF16>(k, kbar, n_frames, P, d, stream, lds_pad)
-                  : launch_pool_t<TokF32>(k, kbar, n_frames, P, d, stream, lds_pad);
+hipError_t launch_pool(const void* k, infv_token_dtype tok, float* kbar, int64_t n_frames, int P, int d, hipStream_t stream, int lds_pad) {
+    return with_token_type(tok, [&](auto t) { return launch_pool_t<decltype(t)>(k, kbar, n_frames, P, d, stream, lds_pad); });
 }
 
 template <class Tok>
@@ -110,15 +149,15 @@ static hipError_t launch_pool_t(const void* k, float* kbar, int64_t n_frames, in
         // the pipeline -- DESIGN notebook; those instantiations are gone.)
         static bool attr_set = false;
         if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pool_frames_kernel<4, 512, Tok>),
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(PoolFramesFn<4, 512, Tok>::get()),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
             attr_set = true;
         }
         const unsigned grid = (unsigned)((n_units + 7) / 8);
-        INFV_LAUNCH((pool_frames_kernel<4, 512, Tok>), dim3(grid), dim3(512), lds_pad, stream, k, kbar, n_units, P, d4, slices);
+        INFV_LAUNCH((PoolFramesFn<4, 512, Tok>::get()), dim3(grid), dim3(512), lds_pad, stream, k, kbar, n_units, P, d4, slices);
     } else {
-        INFV_LAUNCH((pool_frames_kernel<16, 256, Tok>), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, stream, k, kbar,
+        INFV_LAUNCH((PoolFramesFn<16, 256, Tok>::get()), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, stream, k, kbar,
                            n_units, P, d4, slices);
     }
     return hipGetLastError();
@@ -164,9 +203,9 @@ __device__ inline unsigned pool_pack2(__bf16 a, __bf16 b) {
 }
 
 template <int U, class Tok, bool CALL>
-__global__ __launch_bounds__(1024) void pool_rows2_kernel(const void* __restrict__ k_, long chunk_stride, int P, int d4, int slices,
-                                                          OperatorView op, long n_rows_total, float* __restrict__ R,
-                                                          long long* __restrict__ stamps, int prio, int tid_addr, PoolCallDesc pc) {
+__device__ __forceinline__ void pool_rows2_body(const void* __restrict__ k_, long chunk_stride, int P, int d4, int slices,
+                                                const OperatorView& op, long n_rows_total, float* __restrict__ R,
+                                                long long* __restrict__ stamps, int prio, int tid_addr, const PoolCallDesc& pc) {
     typedef typename Tok::vec tvec;
     extern __shared__ __attribute__((aligned(16))) float pr2_lds[];          // [4 frames][d4] float4
     floatx4* park = reinterpret_cast<floatx4*>(pr2_lds);
@@ -301,6 +340,21 @@ __global__ __launch_bounds__(1024) void pool_rows2_kernel(const void* __restrict
 #endif
 }
 
+template <int U, class Tok, bool CALL>
+__global__ __launch_bounds__(1024) void pool_rows2_kernel(const void* __restrict__ k_, long chunk_stride, int P, int d4, int slices,
+                                                          OperatorView op, long n_rows_total, float* __restrict__ R,
+                                                          long long* __restrict__ stamps, int prio, int tid_addr, PoolCallDesc pc) {
+    pool_rows2_body<U, Tok, CALL>(k_, chunk_stride, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
+}
+template <int U, bool CALL>
+__global__ __launch_bounds__(1024) void pool_rows2_f16_kernel(const void* __restrict__ k_, long chunk_stride, int P, int d4, int slices,
+                                                              OperatorView op, long n_rows_total, float* __restrict__ R,
+                                                              long long* __restrict__ stamps, int prio, int tid_addr, PoolCallDesc pc) {
+    pool_rows2_body<U, TokF16, CALL>(k_, chunk_stride, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
+}
+template <int U, class Tok, bool CALL> struct PoolRows2Fn { static auto get() { return pool_rows2_kernel<U, Tok, CALL>; } };
+template <int U, bool CALL> struct PoolRows2Fn<U, TokF16, CALL> { static auto get() { return pool_rows2_f16_kernel<U, CALL>; } };
+
 #ifdef INFV_EXPERIMENTS
 static long long* g_stamps = nullptr;            // [kStampCap][4], launches appended
 static long g_stamp_fill = 0;
@@ -358,13 +412,13 @@ static hipError_t launch_pool_rows2_t(const void* k, int n_chunks, int T, int P,
     if ((size_t)lds_pad > lds) lds = lds_pad;
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pool_rows2_kernel<4, Tok, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(pool_rows2_kernel<8, Tok, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(pool_rows2_kernel<4, Tok, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(pool_rows2_kernel<8, Tok, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(PoolRows2Fn<4, Tok, false>::get()), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(PoolRows2Fn<8, Tok, false>::get()), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(PoolRows2Fn<4, Tok, true>::get()), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(PoolRows2Fn<8, Tok, true>::get()), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #ifdef INFV_EXPERIMENTS
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(pool_rows2_kernel<16, Tok, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(pool_rows2_kernel<32, Tok, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(PoolRows2Fn<16, Tok, false>::get()), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(PoolRows2Fn<32, Tok, false>::get()), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #endif
         if (e != hipSuccess) return e;
         attr_set = true;
@@ -386,34 +440,36 @@ static hipError_t launch_pool_rows2_t(const void* k, int n_chunks, int T, int P,
     static const int want_tid = [] { const char* e = exp_env("INFV_POOL_TID"); return e ? atoi(e) : kPoolTidAddr; }();
     const int tid_addr = (want_tid && d4 % 64 == 0) ? 1 : 0;               // every lane of every slice holds a column
 #ifdef INFV_EXPERIMENTS
-    if (call == nullptr && u >= 32 && P % 32 == 0) { INFV_LAUNCH((pool_rows2_kernel<32, Tok, false>), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc); return hipGetLastError(); }
-    if (call == nullptr && u >= 16 && P % 16 == 0) { INFV_LAUNCH((pool_rows2_kernel<16, Tok, false>), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc); return hipGetLastError(); }
+    if (call == nullptr && u >= 32 && P % 32 == 0) { INFV_LAUNCH((PoolRows2Fn<32, Tok, false>::get()), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc); return hipGetLastError(); }
+    if (call == nullptr && u >= 16 && P % 16 == 0) { INFV_LAUNCH((PoolRows2Fn<16, Tok, false>::get()), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc); return hipGetLastError(); }
 #endif
     if (call != nullptr) {
-        if (u >= 8 && P % 8 == 0) INFV_LAUNCH((pool_rows2_kernel<8, Tok, true>), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
-        else INFV_LAUNCH((pool_rows2_kernel<4, Tok, true>), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
+        if (u >= 8 && P % 8 == 0) INFV_LAUNCH((PoolRows2Fn<8, Tok, true>::get()), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
+        else INFV_LAUNCH((PoolRows2Fn<4, Tok, true>::get()), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
         return hipGetLastError();
     }
-    if (u >= 8 && P % 8 == 0) INFV_LAUNCH((pool_rows2_kernel<8, Tok, false>), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
-    else INFV_LAUNCH((pool_rows2_kernel<4, Tok, false>), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
+    if (u >= 8 && P % 8 == 0) INFV_LAUNCH((PoolRows2Fn<8, Tok, false>::get()), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
+    else INFV_LAUNCH((PoolRows2Fn<4, Tok, false>::get()), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
     return hipGetLastError();
 }
 
-hipError_t launch_pool_rows2(const void* k, int k_bf16, int n_chunks, int T, int P, int d, const OperatorView& op, float* R,
+hipError_t launch_pool_rows2(const void* k, infv_token_dtype tok, int n_chunks, int T, int P, int d, const OperatorView& op, float* R,
                              hipStream_t stream, int u, int lds_pad, int max_wgs, void* const* planes, bool* planes_done) {
     if (planes_done != nullptr) *planes_done = false;
     if (op.rows == 0 || n_chunks == 0) return hipSuccess;
     if (planes != nullptr && d % 16 != 0) return hipErrorInvalidValue;
-    return k_bf16 ? launch_pool_rows2_t<TokBF16>(k, n_chunks, T, P, d, op, R, stream, u, lds_pad, max_wgs, nullptr, planes, planes_done)
-                  : launch_pool_rows2_t<TokF32>(k, n_chunks, T, P, d, op, R, stream, u, lds_pad, max_wgs, nullptr, planes, planes_done);
+    return with_token_type(tok, [&](auto t) {
+        return launch_pool_rows2_t<decltype(t)>(k, n_chunks, T, P, d, op, R, stream, u, lds_pad, max_wgs, nullptr, planes, planes_done);
+    });
 }
 
-hipError_t launch_pool_rows2_call(const void* k, int k_bf16, int T, int P, int d, const OperatorView& op, const PoolCallDesc& pc,
+hipError_t launch_pool_rows2_call(const void* k, infv_token_dtype tok, int T, int P, int d, const OperatorView& op, const PoolCallDesc& pc,
                                   hipStream_t stream, int u, int lds_pad) {
     if (op.rows == 0 || pc.n_chunks == 0) return hipSuccess;
     if (pc.R_all == nullptr || pc.sub <= 0) return hipErrorInvalidValue;
-    return k_bf16 ? launch_pool_rows2_t<TokBF16>(k, pc.n_chunks, T, P, d, op, nullptr, stream, u, lds_pad, 0, &pc)
-                  : launch_pool_rows2_t<TokF32>(k, pc.n_chunks, T, P, d, op, nullptr, stream, u, lds_pad, 0, &pc);
+    return with_token_type(tok, [&](auto t) {
+        return launch_pool_rows2_t<decltype(t)>(k, pc.n_chunks, T, P, d, op, nullptr, stream, u, lds_pad, 0, &pc);
+    });
 }
 
 bool pool_rows2_supported(int d) { return d % 4 == 0 && ((d / 4 + 63) / 64) * 4 * 64 <= 1024; }
@@ -1529,14 +1585,15 @@ __global__ __launch_bounds__(256) void pool_videos_kernel(const void* __restrict
     reinterpret_cast<floatx4*>(kbar)[fr * d4 + c4] = acc;
 }
 
-hipError_t launch_pool_videos(const void* k, int k_bf16, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream) {
+hipError_t launch_pool_videos(const void* k, infv_token_dtype tok, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream) {
     const int d4 = d / 4, slices = (d4 + 63) / 64;
     const long n_units = (long)vs.n * T * slices;
     if (n_units == 0) return hipSuccess;
     const dim3 grid((unsigned)((n_units + 3) / 4));
-    if (k_bf16) INFV_LAUNCH(pool_videos_kernel<TokBF16>, grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
-    else INFV_LAUNCH(pool_videos_kernel<TokF32>, grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
-    return hipGetLastError();
+    return with_token_type(tok, [&](auto t) {
+        INFV_LAUNCH(pool_videos_kernel<decltype(t)>, grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
+        return hipGetLastError();
+    });
 }
 
 // one thread per float4 of video rank j's chunk of this step (infv_ltm_steps_videos: frame means the caller pooled): plain copies

@@ -903,6 +903,78 @@ hipError_t launch_split_transpose(const float* F, int nb, int n, int d, void* Fh
 }
 
 // ------------------------------------------------------------------------------------------------------
+// The token pass for fp16 frame tokens (what the reference's fp16 producer holds): split_transpose_kernel with F [n][d] fp16, read
+// at 2 bytes per element in 16-byte vectors of 8.  An fp16 value is exact in fp32 and split2() is the function the fp32 pass applies,
+// so F_hi / F_lo, FT_hi / FT_lo and (kbar != nullptr) the frame means -- summed in token order from the same fp32 tile and divided
+// by P -- are the fp32 pass's bits on the same values (hi + lo is the token exactly: 11 significand bits = 8 + 3).
+// The tile is kept widened, 65 words a row, as the fp32 pass keeps it.  ds_write_b32 / ds_read_b32 are served per 32-lane half
+// over 32 banks: a half writes 4 rows x 8 column groups at banks (r + 8 j + k) % 32 and reads 4 columns x 8 row groups at
+// (8 i + k + c) % 32 -- 16 distinct banks, each twice: the 2-way pattern of the fp32 pass in both directions (not measured with
+// the conflict counter; the pass is bound by its global traffic).  Stores are 16 bytes of 8 bf16.
+// ------------------------------------------------------------------------------------------------------
+typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
+__global__ __launch_bounds__(256) void split_transpose_f16_kernel(const _Float16* __restrict__ F, int n, int d,
+                                                                  __bf16* __restrict__ Fh, __bf16* __restrict__ Fl,
+                                                                  __bf16* __restrict__ Th, __bf16* __restrict__ Tl,
+                                                                  float* __restrict__ kbar, int P) {
+    __shared__ float tile[64][65];
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const long cb = (long)blockIdx.z * n * d;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int e = tid + 256 * p;                 // 512 vectors of 8 fp16
+        const int r = e >> 3, c8 = (e & 7) * 8;
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        if (r0 + r < n) raw = *reinterpret_cast<const uint4*>(F + cb + (long)(r0 + r) * d + c0 + c8);
+        const halfx8 v = __builtin_bit_cast(halfx8, raw);
+        __bf16 h[8], l[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const float x = (float)v[k]; split2(x, h[k], l[k]); tile[r][c8 + k] = x; }
+        if (r0 + r < n) {
+            const long o = cb + (long)(r0 + r) * d + c0 + c8;
+            *reinterpret_cast<uint4*>(Fh + o) = make_uint4(pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7]));
+            *reinterpret_cast<uint4*>(Fl + o) = make_uint4(pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7]));
+        }
+    }
+    __syncthreads();
+    // transposed: row = column c of the tile, 8 consecutive tokens per thread
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int e = tid + 256 * p;
+        const int c = e >> 3, r8 = (e & 7) * 8;
+        if (r0 + r8 < n) {                           // n % 8 == 0 (multiple of 32)
+            __bf16 h[8], l[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) split2(tile[r8 + k][c], h[k], l[k]);
+            const long o = cb + (long)(c0 + c) * n + r0 + r8;
+            *reinterpret_cast<uint4*>(Th + o) = make_uint4(pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7]));
+            *reinterpret_cast<uint4*>(Tl + o) = make_uint4(pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7]));
+        }
+    }
+    if (kbar) {
+        const int fpt = 64 / P;                      // frames per tile
+        for (int e = tid; e < fpt * 64; e += 256) {
+            const int f = e >> 6, c = e & 63;
+            if (r0 + (f + 1) * P <= n) {
+                float acc = 0.f;
+                for (int p = 0; p < P; ++p) acc += tile[f * P + p][c];
+                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
+            }
+        }
+    }
+}
+
+hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
+                                      hipStream_t stream, float* kbar, int P) {
+    if (n % 32 || d % 64) return hipErrorInvalidValue;
+    if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
+    INFV_LAUNCH(split_transpose_f16_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const _Float16*>(F), n, d,
+                static_cast<__bf16*>(Fh), static_cast<__bf16*>(Fl), static_cast<__bf16*>(Th), static_cast<__bf16*>(Tl), kbar, P);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------
 // The token pass for bf16 frame tokens: F [n][d] bf16 is the score contraction's B operand as it stands (hi = the token, lo = 0
 // exactly), so only FT_hi [d][n] is written -- and, with kbar != nullptr, the frame means, summed in token order and divided by P
 // as above (the same bits as the fp32 pass on the same values, and as pool_frames_kernel).  64 x 64 tiles, 16-byte loads and
@@ -977,6 +1049,27 @@ hipError_t launch_upcast_bf16(const void* x, float* y, long n, hipStream_t strea
     for (long o = 0; o < n; o += (1l << 33)) {          // (grid.x limit)
         const long m = n - o < (1l << 33) ? n - o : (1l << 33);
         INFV_LAUNCH(upcast_bf16_kernel, dim3((unsigned)((m / 8 + 255) / 256)), dim3(256), 0, stream, static_cast<const __bf16*>(x) + o, y + o, m / 8);
+    }
+    return hipGetLastError();
+}
+
+// x [n] fp16 -> y [n] fp32 (n % 8 == 0), exact: fp16 tokens where the split path does not apply
+__global__ __launch_bounds__(256) void upcast_f16_kernel(const _Float16* __restrict__ x, float* __restrict__ y, long n8) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    const halfx8 v = __builtin_bit_cast(halfx8, reinterpret_cast<const uint4*>(x)[i]);
+    floatx4 a = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+    floatx4 b = {(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
+    reinterpret_cast<floatx4*>(y)[2 * i] = a;
+    reinterpret_cast<floatx4*>(y)[2 * i + 1] = b;
+}
+
+hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (n % 8) return hipErrorInvalidValue;
+    for (long o = 0; o < n; o += (1l << 33)) {          // (grid.x limit)
+        const long m = n - o < (1l << 33) ? n - o : (1l << 33);
+        INFV_LAUNCH(upcast_f16_kernel, dim3((unsigned)((m / 8 + 255) / 256)), dim3(256), 0, stream, static_cast<const _Float16*>(x) + o, y + o, m / 8);
     }
     return hipGetLastError();
 }

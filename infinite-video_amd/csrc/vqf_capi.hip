@@ -14,7 +14,7 @@ struct infv_vqf_s {
     infv_vqf_config cfg;
     int dev = 0;
     bool exact_fp32 = false;
-    bool tok_bf16 = false;                              // the `frames` arguments point to bf16 tokens (infv_vqf_set_token_dtype)
+    infv_token_dtype tok = INFV_TOKENS_F32;             // element type of the `frames` arguments (infv_vqf_set_token_dtype)
     // chunk-independent prefix of layer 0 (embedding LayerNorm, self-attention block, cross query, pre-multiplied query):
     // reused across encode_chunk calls while the host keeps the weights epoch unchanged (0 = never reuse)
     unsigned long long epoch = 0, c_epoch = 0;
@@ -24,7 +24,7 @@ struct infv_vqf_s {
     DeviceBuf part, h_a, h_b, h1, h2, qkv, sa, xq, along, qt, S, O, merged, inter, kbar;
     DeviceBuf sFh, sFl, sTh, sTl, sPh, sPl, sQh, sQl;   // split-bf16 operands of the short-term attention
     DeviceBuf wFh, wFl, wTh, wTl;                       // the same split of a WHOLE video's frame tokens (layer-major path)
-    DeviceBuf up;                                       // fp32 copy of bf16 tokens where the split path does not apply
+    DeviceBuf up;                                       // fp32 copy of fp16 / bf16 tokens where the split path does not apply
     bool fuse = true;                                   // one pass over the frame tokens: split + transpose + frame means
     double split_cache_gb = 64.0;                       // budget for a whole video's split tokens (INFV_VQF_SPLIT_CACHE_GB at create)
     // whole-video (layer-major) path
@@ -98,7 +98,8 @@ int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
 // chunk (shared_q = true: layer 0 of the video Q-former, whose query does not depend on the chunk)
 //   -> merged [nb*Q][hidden] = alpha * short-term context + (1 - alpha) * along   (along == nullptr: short-term only)
 // Split-bf16 copies of frame tokens produced ahead of the attention (prepare_split): [.][n_tokens][d] and [.][d][n_tokens]
-// (bf16 tokens: Fh is the caller's buffer itself, Fl and Tl are nullptr -- the contractions then run their two-product form)
+// (bf16 tokens: Fh is the caller's buffer itself, Fl and Tl are nullptr -- the contractions then run their two-product form;
+//  fp16 tokens: four planes as for fp32, written by a pass that reads 2 bytes per element)
 struct SplitRef { const __bf16 *Fh, *Fl, *Th, *Tl; };
 // infv_vqf_encode_videos takes the short-term attention's split-K counts as for this many chunks per sub-batch, whatever the
 // sub-batch holds: a chunk's summation order then does not depend on the rest of the batch
@@ -114,27 +115,28 @@ static bool split_path(const infv_vqf_s* h, int n_tokens) {
 // and every layer's memory share this pass (the reference reads them once per layer and once more for the pooling:
 // Qformer.py:236, 278-291).  `whole` selects the video-sized buffers of the layer-major path.
 // element `elems` of a token buffer of either dtype
-static const void* tok_at(const void* frames, bool bf16, long elems) {
-    return static_cast<const char*>(frames) + elems * (bf16 ? 2 : 4);
+static const void* tok_at(const void* frames, infv_token_dtype tok, long elems) {
+    return static_cast<const char*>(frames) + elems * (long)token_bytes(tok);
 }
 
-// bf16 tokens where the split path does not apply: an fp32 copy in the handle's workspace for today's fp32 kernels
-static int upcast_tokens(infv_vqf_s* h, const void* frames, size_t elems, const float** out, hipStream_t stream) {
+// fp16 / bf16 tokens where the split path does not apply: an fp32 copy in the handle's workspace for today's fp32 kernels
+static int upcast_tokens(infv_vqf_s* h, const void* frames, infv_token_dtype tok, size_t elems, const float** out, hipStream_t stream) {
     if (elems * sizeof(float) > h->up.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->up.reserve(elems * sizeof(float))); }
-    HIP_TRY(launch_upcast_bf16(frames, h->up.as<float>(), (long)elems, stream));
+    if (tok == INFV_TOKENS_F16) HIP_TRY(launch_upcast_f16(frames, h->up.as<float>(), (long)elems, stream));
+    else HIP_TRY(launch_upcast_bf16(frames, h->up.as<float>(), (long)elems, stream));
     *out = h->up.as<float>();
     return INFV_OK;
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-static int prepare_split(infv_vqf_s* h, const void* frames_, bool bf16, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
+static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype tok, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
                          hipStream_t stream) {
     const int d = h->cfg.enc_width;
     const size_t szF = (size_t)nb * n_tokens * d * 2;
     DeviceBuf& Fh = whole ? h->wFh : h->sFh; DeviceBuf& Fl = whole ? h->wFl : h->sFl;
     DeviceBuf& Th = whole ? h->wTh : h->sTh; DeviceBuf& Tl = whole ? h->wTl : h->sTl;
-    if (bf16) {                                              // read in place: only the transposed copy is written
+    if (tok == INFV_TOKENS_BF16) {                           // read in place: only the transposed copy is written
         if (szF > Th.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(Th.reserve(szF)); }
         const __bf16* fb = static_cast<const __bf16*>(frames_);
         for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
@@ -155,16 +157,19 @@ static int prepare_split(infv_vqf_s* h, const void* frames_, bool bf16, int nb, 
     for (int c0 = 0; c0 < nb; c0 += 32768) {                   // grid.z limit
         const int n = nb - c0 < 32768 ? nb - c0 : 32768;
         const size_t o = (size_t)c0 * n_tokens * d;
-        HIP_TRY(launch_split_transpose(frames + o, n, n_tokens, d, Fh.as<__bf16>() + o, Fl.as<__bf16>() + o, Th.as<__bf16>() + o,
-                                       Tl.as<__bf16>() + o, stream,
-                                       kbar ? kbar + (size_t)c0 * (n_tokens / h->cfg.tokens_per_frame) * d : nullptr,
-                                       h->cfg.tokens_per_frame));
+        float* kb = kbar ? kbar + (size_t)c0 * (n_tokens / h->cfg.tokens_per_frame) * d : nullptr;
+        if (tok == INFV_TOKENS_F16)
+            HIP_TRY(launch_split_transpose_f16(tok_at(frames_, tok, (long)o), n, n_tokens, d, Fh.as<__bf16>() + o, Fl.as<__bf16>() + o,
+                                               Th.as<__bf16>() + o, Tl.as<__bf16>() + o, stream, kb, h->cfg.tokens_per_frame));
+        else
+            HIP_TRY(launch_split_transpose(frames + o, n, n_tokens, d, Fh.as<__bf16>() + o, Fl.as<__bf16>() + o, Th.as<__bf16>() + o,
+                                           Tl.as<__bf16>() + o, stream, kb, h->cfg.tokens_per_frame));
     }
     *ref = SplitRef{Fh.as<__bf16>(), Fl.as<__bf16>(), Th.as<__bf16>(), Tl.as<__bf16>()};
     return INFV_OK;
 }
 
-int short_attention(infv_vqf_s* h, const void* frames_, bool bf16 /* only where split_path() holds */, int nb, int n_tokens, const float* xq, bool shared_q,
+int short_attention(infv_vqf_s* h, const void* frames_, infv_token_dtype tok /* fp16, bf16: only where split_path() holds */, int nb, int n_tokens, const float* xq, bool shared_q,
                     const infv_linear* key, const infv_linear* value, const float* along, float* merged,
                     hipStream_t stream, bool use_cache = false, const SplitRef* pre = nullptr,
                     hipEvent_t along_ready = nullptr /* `along` is produced on another stream: wait here, before the merge */,
@@ -212,7 +217,7 @@ int short_attention(infv_vqf_s* h, const void* frames_, bool bf16 /* only where 
         }
         SplitRef sr;
         if (pre) sr = *pre;                                   // the caller split these tokens already (shared by the layers)
-        else if (int rc = prepare_split(h, frames_, bf16, nb, n_tokens, nullptr, false, &sr, stream)) return rc;
+        else if (int rc = prepare_split(h, frames_, tok, nb, n_tokens, nullptr, false, &sr, stream)) return rc;
         if (use_cache) {                                      // (the buffers may just have been (re)allocated above)
             qh = h->c_qh.p; ql = h->c_ql.p;
         } else {
@@ -236,7 +241,7 @@ int short_attention(infv_vqf_s* h, const void* frames_, bool bf16 /* only where 
         p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.wide = inv_nb > 0;
         HIP_TRY(launch_split_gemm(p, stream));
     } else {
-    if (bf16) return fail(INFV_ERR_INVALID, "bf16 tokens reached the fp32 contractions");      // (callers upcast first)
+    if (tok != INFV_TOKENS_F32) return fail(INFV_ERR_INVALID, "fp16 / bf16 tokens reached the fp32 contractions");      // (callers upcast first)
     const float* frames = static_cast<const float*>(frames_);
     QfGemm g{};                                             // S[b] = qt[b] . frames[b]^T
     g.A = qt; g.lda = d; g.strideA = shared_q ? 0 : (long)rows * d;
@@ -333,8 +338,8 @@ int infv_vqf_set_precision(infv_vqf_handle h, int32_t exact_fp32) {
 
 int infv_vqf_set_token_dtype(infv_vqf_handle h, int32_t dtype) {
     if (!h) return fail(INFV_ERR_INVALID, "null handle");
-    if (dtype != INFV_TOKENS_F32 && dtype != INFV_TOKENS_BF16) return fail(INFV_ERR_INVALID, "set_token_dtype: unknown token dtype %d", dtype);
-    h->tok_bf16 = dtype == INFV_TOKENS_BF16;
+    if (!token_dtype_known(dtype)) return fail(INFV_ERR_INVALID, "set_token_dtype: unknown token dtype %d", dtype);
+    h->tok = static_cast<infv_token_dtype>(dtype);
     return INFV_OK;
 }
 
@@ -349,15 +354,15 @@ int infv_vqf_short_attention(infv_vqf_handle h, const void* frames, int32_t n_to
                              float* merged, void* stream) {
     if (!h || !frames || !xq || !key || !value || !merged || !key->w || !value->w || !value->b)
         return fail(INFV_ERR_INVALID, "null argument");
-    bool bf16 = h->tok_bf16;
-    if (bf16 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "bf16 frames must be 16-byte aligned");
+    infv_token_dtype tok = h->tok;
+    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 frames must be 16-byte aligned");
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
-    if (bf16 && !split_path(h, n_tokens)) {
+    if (tok != INFV_TOKENS_F32 && !split_path(h, n_tokens)) {
         const float* f32 = nullptr;
-        if (int rc = upcast_tokens(h, frames, (size_t)n_tokens * h->cfg.enc_width, &f32, static_cast<hipStream_t>(stream))) return rc;
-        frames = f32; bf16 = false;
+        if (int rc = upcast_tokens(h, frames, tok, (size_t)n_tokens * h->cfg.enc_width, &f32, static_cast<hipStream_t>(stream))) return rc;
+        frames = f32; tok = INFV_TOKENS_F32;
     }
-    return short_attention(h, frames, bf16, 1, n_tokens, xq, false, key, value, a_long, merged, static_cast<hipStream_t>(stream));
+    return short_attention(h, frames, tok, 1, n_tokens, xq, false, key, value, a_long, merged, static_cast<hipStream_t>(stream));
 }
 
 int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const void* frames, int32_t T,
@@ -372,14 +377,14 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
     if (T < 1) return fail(INFV_ERR_INVALID, "T must be >= 1");
     if (llama_out && (c.proj_out <= 0 || !w->llama_proj.w)) return fail(INFV_ERR_INVALID, "llama_out without llama_proj");
     const int Q = c.n_query, Hd = c.hidden, n_tokens = T * c.tokens_per_frame;
-    bool bf16 = h->tok_bf16;
-    if (bf16 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "bf16 frames must be 16-byte aligned");
+    infv_token_dtype tok = h->tok;
+    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 frames must be 16-byte aligned");
     if (use_ltm)
         if (int rc = ensure_streams(h)) return rc;
-    if (bf16 && !split_path(h, n_tokens)) {                    // today's fp32 kernels from an fp32 copy
+    if (tok != INFV_TOKENS_F32 && !split_path(h, n_tokens)) {  // today's fp32 kernels from an fp32 copy
         const float* f32 = nullptr;
-        if (int rc = upcast_tokens(h, frames, (size_t)n_tokens * c.enc_width, &f32, stream)) return rc;
-        frames = f32; bf16 = false;
+        if (int rc = upcast_tokens(h, frames, tok, (size_t)n_tokens * c.enc_width, &f32, stream)) return rc;
+        frames = f32; tok = INFV_TOKENS_F32;
     }
 
     // The prefix of layer 0 (embedding LayerNorm -> self-attention block -> cross query) depends on the weights only,
@@ -413,12 +418,12 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
     SplitRef sref; const SplitRef* pre = nullptr;
     const bool fused_pool = h->fuse && split_path(h, n_tokens) && 64 % c.tokens_per_frame == 0;
     if (h->fuse && split_path(h, n_tokens)) {
-        if (int rc = prepare_split(h, frames, bf16, 1, n_tokens, use_ltm && fused_pool ? h->kbar.as<float>() : nullptr, false, &sref, stream)) return rc;
+        if (int rc = prepare_split(h, frames, tok, 1, n_tokens, use_ltm && fused_pool ? h->kbar.as<float>() : nullptr, false, &sref, stream)) return rc;
         pre = &sref;
     }
     if (use_ltm && !fused_pool) {
         // (the LTM handle's token dtype is sticky state an earlier caller may have set)
-        if (int rc = infv_ltm_set_token_dtype(ltm[0], bf16 ? INFV_TOKENS_BF16 : INFV_TOKENS_F32)) return rc;
+        if (int rc = infv_ltm_set_token_dtype(ltm[0], tok)) return rc;
         if (int rc = infv_ltm_pool(ltm[0], frames, T, h->kbar.as<float>(), stream_)) return rc;   // shared by all layers
     }
 
@@ -459,7 +464,7 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
             along = h->along.as<float>();
             along_ready = h->ev_side;
         }
-        if (int rc = short_attention(h, frames, bf16, 1, n_tokens, xqb, false, &L.x_k, &L.x_v, along,
+        if (int rc = short_attention(h, frames, tok, 1, n_tokens, xqb, false, &L.x_k, &L.x_v, along,
                                      h->merged.as<float>(), stream, l0c, pre, along_ready)) return rc;
         LinearCall xo{h->merged.as<float>(), Q, Hd, {&L.x_o}, 1, Hd};
         xo.residual = h1; xo.res_rows = Q; xo.ln = &L.x_ln; xo.y = h->h2.as<float>();
@@ -528,16 +533,16 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     if (use_ltm && !ltm) return fail(INFV_ERR_INVALID, "alpha != 1 needs the per-layer LTM handles");
     if (T < 1) return fail(INFV_ERR_INVALID, "T must be >= 1");
     if ((llama_out || llama_mean) && (c.proj_out <= 0 || !w->llama_proj.w)) return fail(INFV_ERR_INVALID, "llama output without llama_proj");
-    bool bf16 = h->tok_bf16;
-    if (bf16 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "bf16 frames must be 16-byte aligned");
+    infv_token_dtype tok = h->tok;
+    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 frames must be 16-byte aligned");
     if (int rc = ensure_streams(h)) return rc;
     const int Q = c.n_query, Hd = c.hidden, C = n_chunks, S = c.nb_samples;
     const int n_tokens = T * c.tokens_per_frame;
     const long chunk_k = (long)n_tokens * c.enc_width;
-    if (bf16 && !split_path(h, n_tokens)) {                    // today's fp32 kernels from an fp32 copy
+    if (tok != INFV_TOKENS_F32 && !split_path(h, n_tokens)) {  // today's fp32 kernels from an fp32 copy
         const float* f32 = nullptr;
-        if (int rc = upcast_tokens(h, frames, (size_t)C * chunk_k, &f32, stream)) return rc;
-        frames = f32; bf16 = false;
+        if (int rc = upcast_tokens(h, frames, tok, (size_t)C * chunk_k, &f32, stream)) return rc;
+        frames = f32; tok = INFV_TOKENS_F32;
     }
     const long M = (long)C * Q;                               // rows of the whole-video activations
     // ---- workspaces: whole-video activations + per-block scratch ----
@@ -572,10 +577,10 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     SplitRef wref{}; bool have_w = false, have_kbar = false;
     {
         const double budget_gb = h->split_cache_gb;
-        const double need_gb = (bf16 ? 1.0 : 4.0) * (double)C * (double)chunk_k * 2.0 / 1e9;   // (bf16 tokens: only FT_hi is written)
+        const double need_gb = (tok == INFV_TOKENS_BF16 ? 1.0 : 4.0) * (double)C * (double)chunk_k * 2.0 / 1e9;   // (bf16 tokens: only FT_hi is written; fp16: four planes, as fp32)
         if (h->fuse && split_path(h, n_tokens) && need_gb <= budget_gb) {
             have_kbar = use_ltm && 64 % c.tokens_per_frame == 0;
-            if (int rc = prepare_split(h, frames, bf16, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
+            if (int rc = prepare_split(h, frames, tok, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
             have_w = true;
         }
     }
@@ -585,7 +590,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
         *r = SplitRef{wref.Fh + o, wref.Fl ? wref.Fl + o : nullptr, wref.Th + o, wref.Tl ? wref.Tl + o : nullptr};
         return r;
     };
-    const int ltm_dtype = bf16 ? INFV_TOKENS_BF16 : INFV_TOKENS_F32;   // (what the fallbacks below hand the memories)
+    const int ltm_dtype = tok;   // (what the fallbacks below hand the memories)
     if (multi && use_ltm && !have_kbar) {                    // the frame means every layer's memories step from
         if (int rc = infv_ltm_set_token_dtype(ltm[0], ltm_dtype)) return rc;
         if (int rc = infv_ltm_pool(ltm[0], frames, (int64_t)C * T, h->vkbar.as<float>(), stream_)) return rc;
@@ -653,7 +658,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
             for (int c0 = 0; c0 < C; c0 += NB) {
                 const int nb = C - c0 < NB ? C - c0 : NB;
                 SplitRef sr;
-                if (int rc = short_attention(h, tok_at(frames, bf16, c0 * chunk_k), bf16, nb, n_tokens, h->v_xqs.as<float>(), true, &L.x_k, &L.x_v,
+                if (int rc = short_attention(h, tok_at(frames, tok, c0 * chunk_k), tok, nb, n_tokens, h->v_xqs.as<float>(), true, &L.x_k, &L.x_v,
                                              use_ltm ? valong + (long)c0 * Q * Hd : nullptr, vmerged + (long)c0 * Q * Hd, stream,
                                              false, pre_at(c0, &sr), nullptr, multi ? kInvariantNb : 0)) return rc;
             }
@@ -703,7 +708,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
             for (int c0 = 0; c0 < C; c0 += NB) {
                 const int nb = C - c0 < NB ? C - c0 : NB;
                 SplitRef sr;
-                if (int rc = short_attention(h, tok_at(frames, bf16, c0 * chunk_k), bf16, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
+                if (int rc = short_attention(h, tok_at(frames, tok, c0 * chunk_k), tok, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
                                              nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
                                              pre_at(c0, &sr), nullptr, multi ? kInvariantNb : 0)) return rc;
             }
@@ -840,7 +845,7 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
     if (T < 1) return fail(INFV_ERR_INVALID, "vc_encode_videos: T must be >= 1");
     const int n_tokens = T * c.tokens_per_frame;
     if (n_tokens % 32) return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: T * tokens_per_frame = %d is no multiple of 32", n_tokens);
-    if (h->tok_bf16) return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: bf16 frame tokens are not supported on this path");
+    if (h->tok != INFV_TOKENS_F32) return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: fp16 / bf16 frame tokens are not supported on this path");
     int n_cross = 0;
     for (int l = 0; l < Ln; ++l) n_cross += w->layers[l].has_cross != 0;
     const bool use_ltm = c.alpha != 1.0f && n_cross > 0;
@@ -930,7 +935,7 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
         const double need_gb = 4.0 * (double)C * (double)chunk_k * 2.0 / 1e9;
         if (h->fuse && split_path(h, n_tokens) && need_gb <= h->split_cache_gb) {
             have_kbar = use_ltm && 64 % c.tokens_per_frame == 0;
-            if (int rc = prepare_split(h, frames, false, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
+            if (int rc = prepare_split(h, frames, INFV_TOKENS_F32, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
             have_w = true;
         }
         if (use_ltm && !have_kbar) {
@@ -1003,7 +1008,7 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
             for (int c0 = 0; c0 < C; c0 += NB) {
                 const int nb = C - c0 < NB ? C - c0 : NB;
                 SplitRef sr;
-                if (int rc = short_attention(h, frames + (long)c0 * chunk_k, false, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
+                if (int rc = short_attention(h, frames + (long)c0 * chunk_k, INFV_TOKENS_F32, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
                                              nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
                                              pre_at(c0, &sr), nullptr, kInvariantNb)) return rc;
             }

@@ -114,6 +114,11 @@ hipError_t launch_split_transpose(const float* F, int nb, int n, int d, void* Fh
 hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, hipStream_t stream, float* kbar = nullptr, int P = 0);
 // x [n] bf16 -> y [n] fp32, n % 8 == 0
 hipError_t launch_upcast_bf16(const void* x, float* y, long n, hipStream_t stream);
+// F [nb][n][d] fp16 -> Fh/Fl [nb][n][d] and Th/Tl [nb][d][n] (bf16 hi/lo: the fp32 pass's planes) and, with kbar, the frame means
+hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl, hipStream_t stream,
+                                      float* kbar = nullptr, int P = 0);
+// x [n] fp16 -> y [n] fp32 (exact), n % 8 == 0
+hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream);
 // softmax of fp32 score rows, written as bf16 hi/lo
 hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long ld, void* Ph, void* Pl, long ld_out, hipStream_t stream);
 

@@ -33,7 +33,7 @@ def _np_f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-TOKEN_DTYPES = {torch.float32: 0, torch.bfloat16: 1}      # infv_token_dtype
+TOKEN_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 3}      # infv_token_dtype (2 is not a code)
 
 
 def _check_dev(t: torch.Tensor, device: torch.device, name: str, dtype=torch.float32):
@@ -52,11 +52,16 @@ class LTMEngine:
                  tau: float, sticky: bool, n_layers: int = 1, max_q: int = 32,
                  device: Optional[torch.device] = None, nb_samples: int = NB_SAMPLES,
                  max_batch_chunks: int = 32, gaussian_sigmas: Optional[Sequence[float]] = None,
-                 rng_seed: Optional[int] = None, rng_stream: int = 0):
-        """``rng_seed``: turn the device rng on at creation (``set_device_rng``).  ``gaussian_sigmas``: use the reference's Gaussian basis family (``add_gaussian_basis_functions``,
+                 rng_seed: Optional[int] = None, rng_stream: int = 0, fp16_tokens: bool = False):
+        """``fp16_tokens``: the tensor methods (``pool``, ``pool_rows``, ``forward``, ``consolidate*``) also take ``torch.float16``
+        frame tokens and read them in place (INFV_TOKENS_F16: the bits of the run on ``k.float()``).  Off by default -- an engine
+        then refuses fp16 tensors with a ``TypeError`` as it always has; the attribute of the same name may be set later.  The raw
+        entry points (``forward_into_raw``, ``pool_into``) take the code from their caller and are not gated.
+        ``rng_seed``: turn the device rng on at creation (``set_device_rng``).  ``gaussian_sigmas``: use the reference's Gaussian basis family (``add_gaussian_basis_functions``,
         long_term_attention_gibbs.py:167-174: centres ``linspace(0, 1, num_basis // len(sigmas))`` x these widths) instead
         of the rectangular one the active reference module builds; every step then takes the dense per-call path."""
         self.lib = _lib.load()
+        self.fp16_tokens = bool(fp16_tokens)
         if not torch.cuda.is_available():
             raise RuntimeError("LTMEngine needs a HIP device (no CPU fallback exists)")
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -237,10 +242,10 @@ class LTMEngine:
         _lib.check(self.lib.infv_ltm_reset(self._h))
 
     def _tokens(self, k: torch.Tensor):
-        """Frame tokens may be fp32 (the reference's layout) or bf16 (a producer that halves the HBM stream): tell the
-        handle which one this call passes."""
-        if k.dtype not in TOKEN_DTYPES:
-            raise TypeError(f"frame tokens must be float32 or bfloat16, got {k.dtype}")
+        """Frame tokens may be fp32 (the reference's layout), fp16 (what its fp16 producer holds: read at half the bytes, same
+        bits as the fp32 run) or bf16 (a producer that rounds them): tell the handle which one this call passes."""
+        if k.dtype not in TOKEN_DTYPES or (k.dtype == torch.float16 and not self.fp16_tokens):
+            raise TypeError(f"frame tokens must be float32 or bfloat16 (float16 on an engine created with fp16_tokens=True), got {k.dtype}")
         _check_dev(k, self.device, "k", k.dtype)
         # always: the dtype is sticky state of the handle and other users of the handle (the video Q-former's C path) set it
         # too, so a Python-side cache of it could go stale
@@ -250,7 +255,7 @@ class LTMEngine:
 
     # ------------------------------------------------------------------ operators
     def pool(self, k: torch.Tensor) -> torch.Tensor:
-        """k [..., T*P, d] (fp32 or bf16) -> frame means [..., T, d] fp32   (reference :304)."""
+        """k [..., T*P, d] (fp32 or bf16; fp16 on an engine with fp16_tokens=True) -> frame means [..., T, d] fp32   (reference :304)."""
         self._tokens(k)
         if k.shape[-1] != self.d or k.shape[-2] % self.P:
             raise ValueError(f"k must be [..., T*{self.P}, {self.d}], got {tuple(k.shape)}")
@@ -261,7 +266,7 @@ class LTMEngine:
         return out
 
     def pool_rows(self, k: torch.Tensor) -> torch.Tensor:
-        """k [C, T*P, d] (fp32 or bf16) -> the memory's new rows R [C, rows, d] fp32: frame means (reference :304) summed
+        """k [C, T*P, d] (fp32 or bf16; fp16 with fp16_tokens=True) -> the memory's new rows R [C, rows, d] fp32: frame means (reference :304) summed
         per box row with the operator's weights (reference :216), one pass over the tokens.  Sparse plans only."""
         self._tokens(k)
         if k.dim() != 3 or k.shape[-1] != self.d or k.shape[-2] % self.P:
@@ -291,6 +296,7 @@ class LTMEngine:
     # -- lean entry points of the drop-in module's per-call path: the caller has validated shapes / dtypes / devices once for
     #    this call signature; nothing is re-checked here, no context manager is entered (the caller's device is current)
     def pool_into(self, k: torch.Tensor, kbar: torch.Tensor, n_frames: int, token_code: int, stream: C.c_void_p):
+        # (``token_code``: any infv_token_dtype -- 0 fp32, 1 bf16, 3 fp16; the caller vouches for it, ``fp16_tokens`` does not gate it)
         # the token dtype is sticky state of the C handle and other callers of the same handle change it (the video
         # Q-former's C path forces fp32): always set it, one cheap host call, never trust a Python-side cache
         _lib.check(self.lib.infv_ltm_set_token_dtype(self._h, token_code))
@@ -307,7 +313,7 @@ class LTMEngine:
 
     def forward_into_raw(self, k_ptr: int, token_code: int, T: int, kbar_ptr: int, q_ptr: int, Q: int, proj_arr, u_ptr: int,
                          ctx_ptr: int, stream: C.c_void_p):
-        """infv_ltm_forward_into on raw addresses: set the token dtype, pool k into the caller's kbar, step from it -- ONE C call
+        """infv_ltm_forward_into on raw addresses (``token_code``: 0 fp32, 1 bf16, 3 fp16; not gated by ``fp16_tokens``): set the token dtype, pool k into the caller's kbar, step from it -- ONE C call
         (the drop-in module's steady-state forward; ``pool_into`` + ``step_raw`` were three)."""
         rc = self.lib.infv_ltm_forward_into(self._h, C.c_void_p(k_ptr), token_code, T, C.c_void_p(kbar_ptr), C.c_void_p(q_ptr), Q,
                                             proj_arr, C.c_void_p(u_ptr) if u_ptr else None, C.c_void_p(ctx_ptr), stream)
@@ -333,7 +339,7 @@ class LTMEngine:
     def consolidate(self, k: torch.Tensor, q: torch.Tensor, projs: Sequence[ProjTensors],
                     u: Optional[torch.Tensor] = None, new_doc: bool = True,
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Whole-video loop: k [C, T*P, d] (fp32 or bf16), q [L, Q, dm], u [C, L, S] -> ctx [C, L, Q, dm]."""
+        """Whole-video loop: k [C, T*P, d] (fp32 or bf16; fp16 with fp16_tokens=True), q [L, Q, dm], u [C, L, S] -> ctx [C, L, Q, dm]."""
         self._tokens(k)
         if k.dim() != 3 or k.shape[2] != self.d or k.shape[1] % self.P:
             raise ValueError(f"k must be [C, T*{self.P}, {self.d}], got {tuple(k.shape)}")
@@ -553,7 +559,7 @@ def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.T
                        u=None, new_doc: bool = True) -> torch.Tensor:
     """Step V independent videos together (infv_ltm_consolidate_videos): engine v holds video v's memory.
 
-    ``k`` is PACKED, [sum C_v, T*P, d] (fp32 or bf16) with video v's chunks at rows [cu[v], cu[v+1]) where cu is the running
+    ``k`` is PACKED, [sum C_v, T*P, d] (fp32 or bf16; fp16 if every engine has fp16_tokens=True) with video v's chunks at rows [cu[v], cu[v+1]) where cu is the running
     sum of ``chunk_counts`` (a list or 1-D tensor), and ``u`` likewise [sum C_v, L, S] float64 (None when not sticky).
     ``k`` (and ``u``) may also be lists of per-video [C_v, T*P, d] ([C_v, L, S]) tensors: they are then packed, which COPIES
     every video's tokens once.  ``q`` [L, Q, dm] and ``projs`` are shared by all videos.  new_doc=True starts every memory
@@ -569,7 +575,9 @@ def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.T
     V, e0 = len(engines), engines[0]
     total = int(cu[-1])
     if k.dtype not in TOKEN_DTYPES:
-        raise TypeError(f"frame tokens must be float32 or bfloat16, got {k.dtype}")
+        raise TypeError(f"frame tokens must be float32, float16 or bfloat16, got {k.dtype}")
+    if k.dtype == torch.float16 and not all(e.fp16_tokens for e in engines):   # (before any handle's dtype is touched)
+        raise TypeError("float16 frame tokens need engines created with fp16_tokens=True")
     _check_dev(k, e0.device, "k", k.dtype)
     if k.dim() != 3 or k.shape[0] != total or k.shape[2] != e0.d or k.shape[1] % e0.P:
         raise ValueError(f"k must be [{total}, T*{e0.P}, {e0.d}], got {tuple(k.shape)}")

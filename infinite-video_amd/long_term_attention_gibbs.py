@@ -307,7 +307,7 @@ class LongTermAttention(nn.Module):
                 eng.step_raw(kbar.data_ptr(), klen, qf.data_ptr(), qlen, proj_arr, u_addr, ctx.data_ptr(), stream)
         else:
             kf = k
-            if kf.dtype not in TOKEN_DTYPES:                      # bf16 tokens are pooled as they are
+            if kf.dtype not in TOKEN_DTYPES:                      # fp16 and bf16 tokens are pooled as they are
                 kf = kf.float()
             if not kf.is_contiguous():
                 kf = kf.contiguous()

@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from . import _lib
 from .basis_maps import NB_SAMPLES
+from .engine import TOKEN_DTYPES
 from .qformer_hook import build_long_term_attention
 
 
@@ -159,12 +160,16 @@ class ShortMemoryBuffer:
     directly (``infv_ltm_set_token_dtype``), and so does the video Q-former (``encode_video`` -> ``encode_frames``,
     ``infv_vqf_set_token_dtype``): no fp32 copy is made, the short-term contractions read the buffer in place.  The result
     then differs from the fp32-token run by the rounding of the tokens only -- it is bit for bit the run on the rounded
-    values (off by default, never used for the headline number)."""
+    values (off by default, never used for the headline number).
+
+    ``dtype=torch.float16`` is for a producer that holds fp16 (the reference's ViT and image Q-former run in fp16): the same
+    half-size buffer, read in place by the same entry points, and nothing is rounded -- every result is bit for bit the run on
+    ``tokens.float()``."""
 
     def __init__(self, tokens_per_frame: int, width: int, capacity_frames: int = 2049, dtype=torch.float32,
                  device=None):
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise TypeError("ShortMemoryBuffer holds float32 or bfloat16 tokens")
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError("ShortMemoryBuffer holds float32, float16 or bfloat16 tokens")
         self.P, self.d = int(tokens_per_frame), int(width)
         self.store = torch.empty(int(capacity_frames), self.P, self.d, dtype=dtype, device=device)
         self.n = 0
@@ -206,13 +211,14 @@ def _dev_f32(t: torch.Tensor, device: torch.device) -> torch.Tensor:
 
 
 def _dev_tokens(t: torch.Tensor, device: torch.device):
-    """Frame tokens for the C ABI: (tensor, infv_token_dtype).  Contiguous bf16 tokens on the device pass through untouched
-    (16-byte aligned, as the ABI asks; a misaligned view is copied, still bf16); everything else becomes fp32 as before."""
+    """Frame tokens for the C ABI: (tensor, infv_token_dtype).  Contiguous fp16 / bf16 tokens on the device pass through
+    untouched (16-byte aligned, as the ABI asks; a misaligned view is copied, in its own dtype); everything else becomes fp32
+    as before."""
     t = t.detach()
-    if t.dtype == torch.bfloat16 and t.device == device:
+    if t.dtype in (torch.bfloat16, torch.float16) and t.device == device:
         if not t.is_contiguous() or t.data_ptr() % 16:
             t = t.clone(memory_format=torch.contiguous_format)
-        return t, 1
+        return t, TOKEN_DTYPES[t.dtype]
     return _dev_f32(t, device), 0
 
 
@@ -456,7 +462,7 @@ class InfVideoEncoder(nn.Module):
         if getattr(self, "_vqf_exact", None) != bool(self.exact_fp32):
             _lib.check(_lib.load().infv_vqf_set_precision(h, int(bool(self.exact_fp32))))
             self._vqf_exact = bool(self.exact_fp32)
-        _lib.check(_lib.load().infv_vqf_set_token_dtype(h, token_dtype))      # per call: 0 fp32, 1 bf16 (infv_token_dtype)
+        _lib.check(_lib.load().infv_vqf_set_token_dtype(h, token_dtype))      # per call: 0 fp32, 1 bf16, 3 fp16 (infv_token_dtype)
         return h
 
     def _handle_raw(self, device: torch.device):

@@ -1,4 +1,4 @@
-"""bf16 frame tokens through the video Q-former against fp32 tokens, at the headline chunk shape (T 256, P 32, d 768, N 256,
+"""bf16 (or, with --dtype float16, fp16) frame tokens through the video Q-former against fp32 tokens, at the headline chunk shape (T 256, P 32, d 768, N 256,
 Q 32, 2 layers, alpha 0.9, sticky, llama 4096).  Three legs on the same values, ALTERNATED within the process (a b c a b c ...),
 device-event timing after a warm-up of every leg, median and min-max of each:
 
@@ -9,6 +9,10 @@ device-event timing after a warm-up of every leg, median and min-max of each:
 One configuration per process; one JSON line appended to profiles/vqf_bf16_tokens.jsonl (--out):
 
     timeout -k 10 600 python tools/bench_qformer_tokens.py --config video252
+
+--dtype float16 runs legs b and c on fp16 tokens: b reads them in place (INFV_TOKENS_F16: one token pass at 2 bytes per element,
+then the three-product contractions of leg a), c is "fp16 tokens cast to fp32 first", what a user of fp16 tokens did before.
+The counts from the shapes then are: token pass 2 + 8 bytes per element, contractions as for fp32 tokens.
 
 --legs a times leg (a) only and touches nothing of the bf16 interface (the same script then runs against a build of an earlier
 commit: the fp32 path before / after).  Bytes and bf16-MFMA FLOP per chunk are computed from the shapes, so that the
@@ -42,7 +46,8 @@ def counts_from_shapes():
            "mfma_flop": L * 2 * 3 * 2 * rows * n * D}
     bf16 = {"token_pass_bytes": elems * (2 + 2), "contraction_token_bytes": L * 2 * elems * 2,
             "mfma_flop": L * 2 * 2 * 2 * rows * n * D}
-    return {"fp32_tokens": f32, "bf16_tokens": bf16}
+    f16 = dict(f32, token_pass_bytes=elems * (2 + 8))
+    return {"fp32_tokens": f32, "bf16_tokens": bf16, "fp16_tokens": f16}
 
 
 def main():
@@ -50,6 +55,7 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), required=True)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--legs", default="abc", choices=["abc", "a", "b"])
+    ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float16"], help="the half format of legs b and c")
     ap.add_argument("--tag", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vqf_bf16_tokens.jsonl"))
     a = ap.parse_args()
@@ -64,9 +70,11 @@ def main():
     m.load_reference_state_dict(synth.video_qformer_weights())
     m = m.to(dev)
     gen = torch.Generator(device=dev).manual_seed(1)
-    x = torch.empty(total, T * P, D, device=dev, dtype=torch.bfloat16)
+    half = getattr(torch, a.dtype)
+    short = "bf16" if half == torch.bfloat16 else "fp16"
+    x = torch.empty(total, T * P, D, device=dev, dtype=half)
     for c0 in range(0, total, 32):                                 # (no fp32 tensor of the whole video beside the two below)
-        x[c0:c0 + 32] = torch.randn(min(32, total - c0), T * P, D, device=dev, generator=gen).bfloat16()
+        x[c0:c0 + 32] = torch.randn(min(32, total - c0), T * P, D, device=dev, generator=gen).to(half)
     x32 = x.float() if a.legs != "b" else None
     u = torch.rand(total, L, 512, dtype=torch.float64, generator=torch.Generator().manual_seed(2)).to(dev)
     mems = [VideoMemory(m, dev) for _ in range(V)] if entry == "encode_videos" else None
@@ -106,8 +114,8 @@ def main():
             ms[k].append(e0.elapsed_time(e1))
     line = {"config": a.config, "entry": entry, "videos": V, "chunks": total, "T": T, "N": 256, "Q": Q, "layers": L, "alpha": 0.9,
             "llama": 4096, "rounds": a.rounds, "legs": a.legs, "tag": a.tag, "library": os.path.basename(_lib.LIB_PATH),
-            "tokens_bytes_bf16": x.numel() * 2, "counts_per_chunk_from_shapes": counts_from_shapes()}
-    names = {"a": "fp32_tokens", "b": "bf16_tokens_native", "c": "bf16_tokens_upcast_in_window"}
+            "half_dtype": a.dtype, "tokens_bytes_bf16" if short == "bf16" else "tokens_bytes_fp16": x.numel() * 2, "counts_per_chunk_from_shapes": counts_from_shapes()}
+    names = {"a": "fp32_tokens", "b": f"{short}_tokens_native", "c": f"{short}_tokens_upcast_in_window"}
     for k in legs:
         med = statistics.median(ms[k])
         line[names[k]] = {"median_ms": round(med, 3), "min_ms": round(min(ms[k]), 3), "max_ms": round(max(ms[k]), 3),
@@ -118,8 +126,8 @@ def main():
         line["b_over_c"] = round(statistics.median(ms["b"]) / statistics.median(ms["c"]), 4)
         line["b_over_a"] = round(statistics.median(ms["b"]) / statistics.median(ms["a"]), 4)
         per_chunk_s = statistics.median(ms["b"]) / total * 1e-3
-        cnt = counts_from_shapes()["bf16_tokens"]
-        line["bf16_achieved"] = {"token_bytes_GBps": round((cnt["token_pass_bytes"] + cnt["contraction_token_bytes"]) / per_chunk_s / 1e9, 1),
+        cnt = counts_from_shapes()[f"{short}_tokens"]
+        line[f"{short}_achieved"] = {"token_bytes_GBps": round((cnt["token_pass_bytes"] + cnt["contraction_token_bytes"]) / per_chunk_s / 1e9, 1),
                                  "mfma_TFLOPs": round(cnt["mfma_flop"] / per_chunk_s / 1e12, 1)}
     print(json.dumps(line), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
