@@ -293,6 +293,21 @@ int infv_ltm_steps_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* c
                           const float* q, int32_t q_per_chunk, int32_t Q, const infv_ltm_proj* proj,
                           const double* u, int32_t new_doc, float* ctx, void* stream);
 
+/* infv_ltm_steps_videos with the frame means read through a per-video base (additive in ABI 6): several memories may step from
+ * ONE block of frame means, as when several instructions are asked of one video (the VideoChat2 Q-former's queries, and so its
+ * memories, depend on the instruction; the frames do not: videochat2_it_mistral.py:199-252).
+ *   kbar_chunk0 [V]  HOST int32: chunk i of video v reads its frame means at kbar + (kbar_chunk0[v] + i) * T * d instead of at
+ *                    chunk cu[v] + i.  Entries may repeat and come in any order; kbar must hold kbar_chunk0[v] + cu[v+1] - cu[v]
+ *                    chunks for every v.  NULL: cu[v], which is infv_ltm_steps_videos itself.
+ * u, q (q_per_chunk = 1) and ctx stay packed by cu.  A negative entry is refused (INFV_ERR_INVALID) before any handle changes;
+ * everything else is infv_ltm_steps_videos's contract.  The new-row projection of a step is computed per video even where videos
+ * share frame means.
+ * Bits: those of infv_ltm_steps_videos on a kbar in which video v's chunks are copies of chunks kbar_chunk0[v].. (the lockstep
+ * step gathers through the base; the per-handle fallback hands each handle the pointer at its base). */
+int infv_ltm_steps_videos_from(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const float* kbar,
+                               const int32_t* kbar_chunk0, int32_t T, const float* q, int32_t q_per_chunk, int32_t Q,
+                               const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream);
+
 /* Consolidated memory of one layer: B_past [N,d] (long_term_attention_gibbs.py:220) and the
  * unnormalised sticky bin masses p[n_bins-1] derived from the last scores (:200-202).
  * Export copies device -> caller's DEVICE buffers (async on stream). */

@@ -215,6 +215,36 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
                               const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
                               void* stream);
 
+/* infv_vqf_vc_encode_videos over V STREAMS that read their frame tokens from F distinct blocks (additive): several instructions
+ * asked of one video.  The Q-former takes the instruction as input (encode_img with qformer_text_input,
+ * videochat2_it_mistral.py:199-252, :204-223), so the queries, densities, draws and memories of a video depend on it -- the
+ * frame tokens do not.  Asking K questions of one video (run_nextqa_mistral.py:141-152 with a different `instruction` per
+ * stream) is K streams over ONE copy of its tokens.  A stream has its own instruction (hidden_in rows, text_len), its own
+ * n_cross memories, its own rows of u and of the outputs.
+ *   frames     [fcu[F]][T * tokens_per_frame][enc_width] fp32: the F blocks, packed
+ *   fcu        HOST [F+1], fcu[0] = 0, non-decreasing: block f owns chunks [fcu[f], fcu[f+1])
+ *   frame_src  HOST [V], each in [0, F), in any order (streams of one block need not be adjacent); stream v has as many chunks
+ *              as its block: cu[v+1] - cu[v] == fcu[s+1] - fcu[s], s = frame_src[v]
+ * Everything else -- ltm [V][n_cross], cu, hidden_in, text_len [V], u [cu[V]][n_cross][nb_samples], the outputs packed per stream
+ * and chunk, new_video -- is infv_vqf_vc_encode_videos's, with "video" read as "stream".
+ * Bits: every result (hidden rows, projected rows, per-stream means, each memory's B, bin masses, draws and probabilities) is
+ * bit for bit that of infv_vqf_vc_encode_videos on V videos where video v's frames are a copy of block frame_src[v].
+ * Schedule: the one token pass (split planes, their transposed copies, the frame means; else infv_ltm_pool) runs over the fcu[F]
+ * distinct chunks only, and the planes fit INFV_VQF_SPLIT_CACHE_GB by the distinct bytes.  The short-term contractions read
+ * stream-chunk c's B operand at chunk  fcu[frame_src[v]] + i  through a device map written from kernel arguments (no host buffer
+ * outlives the call, no host synchronisation beyond workspace growth); each cross layer's memories step through
+ * infv_ltm_steps_videos_from with kbar_chunk0[v] = fcu[frame_src[v]].  On the exact-fp32 path (token counts that are a multiple
+ * of 32 but not of 64) the map applies to the caller's `frames` directly.  Where the split path is in use and the planes of
+ * the distinct chunks do NOT fit the budget, every sub-batch splits each contiguous run of its source chunks into its own plane
+ * buffers and contracts with the identity map: correct, but the split work is not shared between streams in that case.
+ * Refused before any device work or memory change: bad cu or fcu, frame_src out of range, a chunk-count mismatch between a
+ * stream and its block, a null or repeated LTM handle, negative text_len (INFV_ERR_INVALID); the token-count, layer-count and
+ * token-dtype cases of infv_vqf_vc_encode_videos (INFV_ERR_UNSUPPORTED). */
+int infv_vqf_vc_encode_streams(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+                               int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w,
+                               const float* hidden_in, const int32_t* text_len, const double* u, int32_t new_video,
+                               float* hidden_out, float* proj_out, float* proj_mean, void* stream);
+
 /* out[i] = mean over n of in[n][i]  (the eval loop's mean over chunk embeddings,
  * run_inference_inf_video_llama_nextqa.py:194) */
 int infv_vqf_mean(const float* in, int32_t n, int64_t elems, float* out, void* stream);

@@ -151,6 +151,8 @@ _SIGNATURES = {
                                               C.POINTER(Proj), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "infv_ltm_steps_videos": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                         C.c_int32, C.POINTER(Proj), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "infv_ltm_steps_videos_from": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_int32, C.c_int32, C.POINTER(Proj), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "infv_ltm_export_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infv_ltm_import_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Proj), C.c_void_p]),
     "infv_ltm_chain_state_bytes": (C.c_int64, [C.c_void_p, C.c_int32]),
@@ -191,6 +193,9 @@ _SIGNATURES = {
     "infv_vqf_vc_encode_videos": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.POINTER(VqfVcWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infv_vqf_vc_encode_streams": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(VqfVcWeights), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infv_vqf_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 KERNELS = ("pool", "rows", "project", "draw", "update", "attend", "scores", "chain", "uc")

@@ -1804,8 +1804,8 @@ bool same_plan(const Plan& a, const Plan& b) {
 // gathered per step).  Chunk c of the packed arrays reads its query at q + c * q_stride: q_stride 0 shares one [L,Q,dm]
 // query, L*Q*dm gives every chunk its own.  `name` prefixes the refusals.
 int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const int32_t* cu, bool tokens, const void* k_,
-                const float* kbar, int32_t T, const float* q, bool q_per_chunk, int32_t Q, const infv_ltm_proj* proj,
-                const double* u, int32_t new_doc, float* ctx, void* stream_) {
+                const float* kbar, const int32_t* kbar_chunk0, int32_t T, const float* q, bool q_per_chunk, int32_t Q,
+                const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream_) {
     // ---- validation: nothing below changes a handle until every check has passed ----
     if (!hs || !cu || V < 0) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
     if (V == 0) return INFV_OK;
@@ -1814,6 +1814,10 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
         if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "%s: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)",
                                             name, v, cu[v], v + 1, cu[v + 1]);
     const int total = cu[V];
+    if (kbar_chunk0)
+        for (int v = 0; v < V; ++v)
+            if (kbar_chunk0[v] < 0) return fail(INFV_ERR_INVALID, "%s: kbar_chunk0[%d] = %d is negative", name, v, kbar_chunk0[v]);
+    auto kbar_base = [&](int v) -> size_t { return (size_t)(kbar_chunk0 ? kbar_chunk0[v] : cu[v]); };   // first chunk of video v's frame means
     for (int v = 0; v < V; ++v) {                  // (before any handle is read)
         if (!hs[v]) return fail(INFV_ERR_INVALID, "%s: handle %d is null", name, v);
         for (int w = 0; w < v; ++w)
@@ -1868,10 +1872,10 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
             if (tokens)
                 rc = infv_ltm_consolidate(hs[v], k + (size_t)cu[v] * chunk_k, n, T, q, Q, proj, uv, 0, cv, stream_);
             else if (q_per_chunk)
-                rc = infv_ltm_steps(hs[v], kbar + (size_t)cu[v] * chunk_kbar, n, T, q + (size_t)cu[v] * chunk_ctx, Q, proj, uv, cv,
+                rc = infv_ltm_steps(hs[v], kbar + kbar_base(v) * chunk_kbar, n, T, q + (size_t)cu[v] * chunk_ctx, Q, proj, uv, cv,
                                     stream_);
             else
-                rc = infv_ltm_consolidate_pooled(hs[v], kbar + (size_t)cu[v] * chunk_kbar, n, T, q, Q, proj, uv, 0, cv, stream_);
+                rc = infv_ltm_consolidate_pooled(hs[v], kbar + kbar_base(v) * chunk_kbar, n, T, q, Q, proj, uv, 0, cv, stream_);
             if (rc) return rc;
         }
         return INFV_OK;
@@ -1918,6 +1922,7 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
             e.override_mask = h->override_mask; e.forced_mask = h->forced_mask;
             e.trace_bins = h->trace_bins; e.trace_probs = h->trace_probs; e.trace_cap = h->trace_cap;
             e.chunk0 = cu[order[j]];
+            e.kbar0 = (long long)kbar_base(order[j]);
             e.cur0 = h->cur;
             e.parts0 = new_doc ? parts : h->parts;
             e.rng = h->rng_view(h->pos);          // (reset above when new_doc: step s of the call draws at position pos + s)
@@ -1978,14 +1983,22 @@ extern "C" {
 
 int infv_ltm_consolidate_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const void* k, int32_t T, const float* q,
                                 int32_t Q, const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream) {
-    return videos_impl("consolidate_videos", hs, V, cu, true, k, nullptr, T, q, false, Q, proj, u, new_doc, ctx, stream);
+    return videos_impl("consolidate_videos", hs, V, cu, true, k, nullptr, nullptr, T, q, false, Q, proj, u, new_doc, ctx, stream);
 }
 
 int infv_ltm_steps_videos(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const float* kbar, int32_t T, const float* q,
                           int32_t q_per_chunk, int32_t Q, const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx,
                           void* stream) {
     if (q_per_chunk != 0 && q_per_chunk != 1) return fail(INFV_ERR_INVALID, "steps_videos: q_per_chunk must be 0 or 1");
-    return videos_impl("steps_videos", hs, V, cu, false, nullptr, kbar, T, q, q_per_chunk != 0, Q, proj, u, new_doc, ctx, stream);
+    return videos_impl("steps_videos", hs, V, cu, false, nullptr, kbar, nullptr, T, q, q_per_chunk != 0, Q, proj, u, new_doc, ctx, stream);
+}
+
+int infv_ltm_steps_videos_from(const infv_ltm_handle* hs, int32_t V, const int32_t* cu, const float* kbar, const int32_t* kbar_chunk0,
+                               int32_t T, const float* q, int32_t q_per_chunk, int32_t Q, const infv_ltm_proj* proj, const double* u,
+                               int32_t new_doc, float* ctx, void* stream) {
+    if (q_per_chunk != 0 && q_per_chunk != 1) return fail(INFV_ERR_INVALID, "steps_videos_from: q_per_chunk must be 0 or 1");
+    return videos_impl("steps_videos_from", hs, V, cu, false, nullptr, kbar, kbar_chunk0, T, q, q_per_chunk != 0, Q, proj, u, new_doc, ctx,
+                       stream);
 }
 
 }  // extern "C"

@@ -298,6 +298,7 @@ struct VideoDesc {
     const float* probs_override; const int32_t* bins_forced;    // one-shot teacher forcing of the video's first draw
     int32_t* trace_bins; float* trace_probs; long long trace_cap;   // draw trace (infv_ltm_set_trace) or nullptr
     long long chunk0;                 // first chunk of the video in the packed arrays
+    long long kbar0;                  // first chunk of its frame means (infv_ltm_steps_videos_from; chunk0 for the other calls)
     int cur0;
     unsigned override_mask, forced_mask;
     int parts0;                       // partial rows per layer of bin_part at the video's first draw

@@ -1602,7 +1602,7 @@ __global__ __launch_bounds__(256) void gather_videos_kernel(const float* __restr
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= chunk4) return;
     const int j = blockIdx.y;
-    const long chunk = vs.vd[j].chunk0 + vs.s;
+    const long chunk = vs.vd[j].kbar0 + vs.s;             // (the frame means' own base: several videos may read one block)
     reinterpret_cast<floatx4*>(out)[j * chunk4 + i] = reinterpret_cast<const floatx4*>(kbar)[chunk * chunk4 + i];
 }
 

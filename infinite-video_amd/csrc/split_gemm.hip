@@ -66,7 +66,8 @@ __global__ __launch_bounds__(256) void split_gemm_kernel(SplitGemm g) {
     const int row = tid >> 1, half = tid & 1;
     const bool a_ok = m0 + row < g.M, b_ok = n0 + row < g.N;
     const long a_off = (long)b * g.strideA + (long)(m0 + row) * g.lda + kbeg + half * (kSBK / 2);
-    const long b_off = (long)b * g.strideB + (long)(n0 + row) * g.ldb + kbeg + half * (kSBK / 2);
+    const int bb = g.b_map ? g.b_map[b] : b;      // (uniform over the workgroup: one scalar read)
+    const long b_off = (long)bb * g.strideB + (long)(n0 + row) * g.ldb + kbeg + half * (kSBK / 2);
     const uint4* src[4] = {reinterpret_cast<const uint4*>(g.A_hi + a_off), reinterpret_cast<const uint4*>(g.A_lo + a_off),
                            reinterpret_cast<const uint4*>(g.B_hi + b_off), reinterpret_cast<const uint4*>((NPROD == 3 ? g.B_lo : g.B_hi) + b_off)};
     uint4 reg[NARR][kSVec];
@@ -201,7 +202,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float* C = g.C + (long)b * g.strideC + (long)s * g.split_stride;
 
     // (M % 384 == 0, N % 256 == 0, K % 32 == 0: checked by the launcher -- every load is a whole in-range 16 bytes)
-    const long a0 = (long)b * g.strideA + (long)m0 * g.lda + kbeg, b0 = (long)b * g.strideB + (long)n0 * g.ldb + kbeg;
+    const int bb = g.b_map ? g.b_map[b] : b;      // (uniform over the workgroup: one scalar read)
+    const long a0 = (long)b * g.strideA + (long)m0 * g.lda + kbeg, b0 = (long)bb * g.strideB + (long)n0 * g.ldb + kbeg;
     const int a_bytes = (int)((kWRowsA - 1) * g.lda + (kend - kbeg)) * 2, b_bytes = (int)((kWRowsB - 1) * g.ldb + (kend - kbeg)) * 2;
     // The LDS-DMA loads are written in assembly: through the builtin the compiler knows that they write LDS, cannot tell the
     // stage being filled from the stage being read, and drains vmcnt(0) in front of the first fragment read behind every load.

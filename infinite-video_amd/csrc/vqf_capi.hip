@@ -30,6 +30,7 @@ struct infv_vqf_s {
     // whole-video (layer-major) path
     DeviceBuf vA, v1, v2, vxq, valong, vshort, vmerged, vqkv, vsa, vinter, vu, vkbar, v_h1s, v_xqs;
     DeviceBuf tA, t1, tqkv, tsa, tinter;                // packed text rows of the VideoChat2 path (infv_vqf_vc_encode_videos)
+    DeviceBuf smap;                                     // infv_vqf_vc_encode_streams: source chunk of every stream-chunk (int32; grown, never shrunk)
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
     ~infv_vqf_s() {
@@ -130,10 +131,13 @@ static int upcast_tokens(infv_vqf_s* h, const void* frames, infv_token_dtype tok
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// dst0 / cap: the planes of these nb chunks go to chunks [dst0, dst0 + nb) of buffers reserved for cap chunks (0, 0: [0, nb) of nb);
+// *ref always addresses chunk 0 of the buffers
 static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype tok, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
-                         hipStream_t stream) {
+                         hipStream_t stream, int dst0 = 0, int cap = 0) {
     const int d = h->cfg.enc_width;
-    const size_t szF = (size_t)nb * n_tokens * d * 2;
+    const size_t szF = (size_t)(cap > dst0 + nb ? cap : dst0 + nb) * n_tokens * d * 2;
+    const size_t d0 = (size_t)dst0 * n_tokens * d;
     DeviceBuf& Fh = whole ? h->wFh : h->sFh; DeviceBuf& Fl = whole ? h->wFl : h->sFl;
     DeviceBuf& Th = whole ? h->wTh : h->sTh; DeviceBuf& Tl = whole ? h->wTl : h->sTl;
     if (tok == INFV_TOKENS_BF16) {                           // read in place: only the transposed copy is written
@@ -159,11 +163,11 @@ static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype to
         const size_t o = (size_t)c0 * n_tokens * d;
         float* kb = kbar ? kbar + (size_t)c0 * (n_tokens / h->cfg.tokens_per_frame) * d : nullptr;
         if (tok == INFV_TOKENS_F16)
-            HIP_TRY(launch_split_transpose_f16(tok_at(frames_, tok, (long)o), n, n_tokens, d, Fh.as<__bf16>() + o, Fl.as<__bf16>() + o,
-                                               Th.as<__bf16>() + o, Tl.as<__bf16>() + o, stream, kb, h->cfg.tokens_per_frame));
+            HIP_TRY(launch_split_transpose_f16(tok_at(frames_, tok, (long)o), n, n_tokens, d, Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o,
+                                               Th.as<__bf16>() + d0 + o, Tl.as<__bf16>() + d0 + o, stream, kb, h->cfg.tokens_per_frame));
         else
-            HIP_TRY(launch_split_transpose(frames + o, n, n_tokens, d, Fh.as<__bf16>() + o, Fl.as<__bf16>() + o, Th.as<__bf16>() + o,
-                                           Tl.as<__bf16>() + o, stream, kb, h->cfg.tokens_per_frame));
+            HIP_TRY(launch_split_transpose(frames + o, n, n_tokens, d, Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o, Th.as<__bf16>() + d0 + o,
+                                           Tl.as<__bf16>() + d0 + o, stream, kb, h->cfg.tokens_per_frame));
     }
     *ref = SplitRef{Fh.as<__bf16>(), Fl.as<__bf16>(), Th.as<__bf16>(), Tl.as<__bf16>()};
     return INFV_OK;
@@ -173,7 +177,8 @@ int short_attention(infv_vqf_s* h, const void* frames_, infv_token_dtype tok /* 
                     const infv_linear* key, const infv_linear* value, const float* along, float* merged,
                     hipStream_t stream, bool use_cache = false, const SplitRef* pre = nullptr,
                     hipEvent_t along_ready = nullptr /* `along` is produced on another stream: wait here, before the merge */,
-                    int inv_nb = 0 /* > 0: batch invariant -- split-K counts and kernel shapes as for inv_nb chunks, whatever nb is */) {
+                    int inv_nb = 0 /* > 0: batch invariant -- split-K counts and kernel shapes as for inv_nb chunks, whatever nb is */,
+                    const int32_t* b_map = nullptr /* device [nb]: chunk b reads chunk b_map[b] of frames_ / *pre (several streams over one block) */) {
     const infv_vqf_config& c = h->cfg;
     const int Q = c.n_query, H = c.n_heads, d = c.enc_width, rows = H * Q;
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
@@ -231,14 +236,14 @@ int short_attention(infv_vqf_s* h, const void* frames_, infv_token_dtype tok /* 
         g.A_hi = static_cast<const __bf16*>(qh); g.A_lo = static_cast<const __bf16*>(ql); g.lda = d; g.strideA = shared_q ? 0 : (long)rows * d;
         g.B_hi = sr.Fh; g.B_lo = sr.Fl; g.ldb = d; g.strideB = (long)n_tokens * d;
         g.C = h->S.as<float>(); g.ldc = ldS; g.strideC = (long)rows * ldS; g.split_stride = 0;
-        g.M = rows; g.N = n_tokens; g.K = d; g.k_per_split = d; g.splitk = 1; g.nbatch = nb; g.wide = inv_nb > 0;
+        g.M = rows; g.N = n_tokens; g.K = d; g.k_per_split = d; g.splitk = 1; g.nbatch = nb; g.wide = inv_nb > 0; g.b_map = b_map;
         HIP_TRY(launch_split_gemm(g, stream));
         HIP_TRY(launch_softmax_rows_split(h->S.as<float>(), (long)nb * rows, n_tokens, ldS, h->sPh.p, h->sPl.p, n_tokens, stream));
         SplitGemm p{};                                        // O[b] = P[b] . frames[b]
         p.A_hi = h->sPh.as<__bf16>(); p.A_lo = h->sPl.as<__bf16>(); p.lda = n_tokens; p.strideA = (long)rows * n_tokens;
         p.B_hi = sr.Th; p.B_lo = sr.Tl; p.ldb = n_tokens; p.strideB = (long)d * n_tokens;
         p.C = h->O.as<float>(); p.ldc = d; p.strideC = (long)rows * d; p.split_stride = (long)nb * rows * d;
-        p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.wide = inv_nb > 0;
+        p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.wide = inv_nb > 0; p.b_map = b_map;
         HIP_TRY(launch_split_gemm(p, stream));
     } else {
     if (tok != INFV_TOKENS_F32) return fail(INFV_ERR_INVALID, "fp16 / bf16 tokens reached the fp32 contractions");      // (callers upcast first)
@@ -247,14 +252,14 @@ int short_attention(infv_vqf_s* h, const void* frames_, infv_token_dtype tok /* 
     g.A = qt; g.lda = d; g.strideA = shared_q ? 0 : (long)rows * d;
     g.B[0] = frames; g.ldb = d; g.strideB = (long)n_tokens * d; g.seg_rows = n_tokens;
     g.C = h->S.as<float>(); g.ldc = ldS; g.strideC = (long)rows * ldS; g.split_stride = 0;
-    g.M = rows; g.N = n_tokens; g.k_per_split = d; g.splitk = 1; g.nbatch = nb;
+    g.M = rows; g.N = n_tokens; g.k_per_split = d; g.splitk = 1; g.nbatch = nb; g.b_map = b_map;
     HIP_TRY(launch_qf_gemm(g, false, stream));
     HIP_TRY(launch_qf_softmax_rows(h->S.as<float>(), (long)nb * rows, n_tokens, ldS, stream));
     QfGemm p{};                                             // O[b] = P[b] . frames[b]
     p.A = h->S.as<float>(); p.lda = ldS; p.strideA = (long)rows * ldS;
     p.B[0] = frames; p.ldb = d; p.strideB = (long)n_tokens * d; p.seg_rows = d;
     p.C = h->O.as<float>(); p.ldc = d; p.strideC = (long)rows * d; p.split_stride = (long)nb * rows * d;
-    p.M = rows; p.N = d; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.K = n_tokens;
+    p.M = rows; p.N = d; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.K = n_tokens; p.b_map = b_map;
     HIP_TRY(launch_qf_gemm(p, true, stream));
     }
     const long o_split_stride = (long)nb * rows * d;
@@ -820,54 +825,71 @@ int infv_vqf_self_attention(infv_vqf_handle h, const float* qkv, int32_t nb, int
     return INFV_OK;
 }
 
-int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
-                              int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len,
-                              const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
-                              void* stream_) {
+// The body of infv_vqf_vc_encode_videos (fcu == nullptr: stream v reads its own chunks [cu[v], cu[v+1]) of `frames`) and of
+// infv_vqf_vc_encode_streams (stream v reads block frame_src[v] of the F blocks packed by fcu).  `name` prefixes the refusals.
+static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+                   int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in,
+                   const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
+                   void* stream_) {
     // ---- validation before any device work or memory change ----
-    if (!h || !cu || !w || !text_len || V < 0) return fail(INFV_ERR_INVALID, "vc_encode_videos: bad arguments");
+    if (!h || !cu || !w || !text_len || V < 0) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
     if (V == 0) return INFV_OK;
     const infv_vqf_config& c = h->cfg;
-    if (cu[0] != 0) return fail(INFV_ERR_INVALID, "vc_encode_videos: cu[0] = %d, not 0", cu[0]);
+    if (cu[0] != 0) return fail(INFV_ERR_INVALID, "%s: cu[0] = %d, not 0", name, cu[0]);
     for (int v = 0; v < V; ++v)
-        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "vc_encode_videos: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)",
+        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "%s: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)", name,
                                             v, cu[v], v + 1, cu[v + 1]);
-    if (w->n_layers < 1 || !w->layers) return fail(INFV_ERR_INVALID, "vc_encode_videos: no layers");
+    const bool streams = fcu != nullptr;
+    if (streams) {
+        if (!frame_src || F < 1) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
+        if (fcu[0] != 0) return fail(INFV_ERR_INVALID, "%s: fcu[0] = %d, not 0", name, fcu[0]);
+        for (int f = 0; f < F; ++f)
+            if (fcu[f + 1] < fcu[f]) return fail(INFV_ERR_INVALID, "%s: fcu is not non-decreasing (fcu[%d] = %d > fcu[%d] = %d)",
+                                                name, f, fcu[f], f + 1, fcu[f + 1]);
+        for (int v = 0; v < V; ++v) {
+            const int s = frame_src[v];
+            if (s < 0 || s >= F) return fail(INFV_ERR_INVALID, "%s: frame_src[%d] = %d outside [0, %d)", name, v, s, F);
+            if (cu[v + 1] - cu[v] != fcu[s + 1] - fcu[s])
+                return fail(INFV_ERR_INVALID, "%s: stream %d has %d chunks, its block %d has %d", name, v, cu[v + 1] - cu[v], s,
+                            fcu[s + 1] - fcu[s]);
+        }
+    }
+    if (w->n_layers < 1 || !w->layers) return fail(INFV_ERR_INVALID, "%s: no layers", name);
     if (w->n_layers > INFV_VQF_VC_MAX_LAYERS)
-        return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: %d layers, at most %d are supported", w->n_layers, INFV_VQF_VC_MAX_LAYERS);
+        return fail(INFV_ERR_UNSUPPORTED, "%s: %d layers, at most %d are supported", name, w->n_layers, INFV_VQF_VC_MAX_LAYERS);
     const int Q = c.n_query, Hd = c.hidden, S = c.nb_samples, Ln = w->n_layers;
     for (int v = 0; v < V; ++v) {
-        if (text_len[v] < 0) return fail(INFV_ERR_INVALID, "vc_encode_videos: text_len[%d] = %d is negative", v, text_len[v]);
+        if (text_len[v] < 0) return fail(INFV_ERR_INVALID, "%s: text_len[%d] = %d is negative", name, v, text_len[v]);
         if (Q + text_len[v] > INFV_VQF_VC_MAX_TOKENS)
-            return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: video %d attends over %d + %d tokens, at most %d are supported",
+            return fail(INFV_ERR_UNSUPPORTED, "%s: video %d attends over %d + %d tokens, at most %d are supported", name,
                         v, Q, text_len[v], INFV_VQF_VC_MAX_TOKENS);
     }
-    if (T < 1) return fail(INFV_ERR_INVALID, "vc_encode_videos: T must be >= 1");
+    if (T < 1) return fail(INFV_ERR_INVALID, "%s: T must be >= 1", name);
     const int n_tokens = T * c.tokens_per_frame;
-    if (n_tokens % 32) return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: T * tokens_per_frame = %d is no multiple of 32", n_tokens);
-    if (h->tok != INFV_TOKENS_F32) return fail(INFV_ERR_UNSUPPORTED, "vc_encode_videos: fp16 / bf16 frame tokens are not supported on this path");
+    if (n_tokens % 32) return fail(INFV_ERR_UNSUPPORTED, "%s: T * tokens_per_frame = %d is no multiple of 32", name, n_tokens);
+    if (h->tok != INFV_TOKENS_F32) return fail(INFV_ERR_UNSUPPORTED, "%s: fp16 / bf16 frame tokens are not supported on this path", name);
     int n_cross = 0;
     for (int l = 0; l < Ln; ++l) n_cross += w->layers[l].has_cross != 0;
     const bool use_ltm = c.alpha != 1.0f && n_cross > 0;
     const int n_h = use_ltm ? V * n_cross : 0;
     if (use_ltm) {
-        if (!ltm) return fail(INFV_ERR_INVALID, "vc_encode_videos: alpha != 1 needs the LTM handles of every video and cross layer");
+        if (!ltm) return fail(INFV_ERR_INVALID, "%s: alpha != 1 needs the LTM handles of every video and cross layer", name);
         std::vector<infv_ltm_handle> all(ltm, ltm + n_h);
         for (int i = 0; i < n_h; ++i)
-            if (!all[i]) return fail(INFV_ERR_INVALID, "vc_encode_videos: LTM handle %d is null", i);
+            if (!all[i]) return fail(INFV_ERR_INVALID, "%s: LTM handle %d is null", name, i);
         std::sort(all.begin(), all.end());
         if (std::adjacent_find(all.begin(), all.end()) != all.end())
-            return fail(INFV_ERR_INVALID, "vc_encode_videos: an LTM handle appears twice (every video and cross layer needs its own memory)");
+            return fail(INFV_ERR_INVALID, "%s: an LTM handle appears twice (every video and cross layer needs its own memory)", name);
     }
     if ((proj_out || proj_mean) && (c.proj_out <= 0 || !w->mistral_proj.w))
-        return fail(INFV_ERR_INVALID, "vc_encode_videos: projected output without mistral_proj");
+        return fail(INFV_ERR_INVALID, "%s: projected output without mistral_proj", name);
     const int C = cu[V];
     if (C == 0) {                                             // no chunk: new_video still starts every memory afresh
         if (use_ltm && new_video)
             for (int i = 0; i < n_h; ++i) infv_ltm_reset(ltm[i]);
         return INFV_OK;
     }
-    if (!frames || !hidden_in) return fail(INFV_ERR_INVALID, "vc_encode_videos: null frames or hidden_in");
+    if (!frames || !hidden_in) return fail(INFV_ERR_INVALID, "%s: null frames or hidden_in", name);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (use_ltm)
         if (int rc = ensure_streams(h)) return rc;
@@ -887,6 +909,15 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
     }
     const long M = (long)C * Q, Tt = toff[C];
     const long chunk_k = (long)n_tokens * c.enc_width;
+    const int Cf = streams ? fcu[F] : C;                       // distinct chunks of frame tokens
+    std::vector<int32_t> src_chunk, kbar0;                     // streams: each stream-chunk's source chunk, each stream's first one
+    if (streams) {
+        src_chunk.resize(C); kbar0.resize(V);
+        for (int v = 0; v < V; ++v) {
+            kbar0[v] = fcu[frame_src[v]];
+            for (int i = 0; i < cu[v + 1] - cu[v]; ++i) src_chunk[cu[v] + i] = kbar0[v] + i;
+        }
+    }
     const int RB = C < kRowBlockVideos ? C : kRowBlockVideos;  // chunks per row block of the token GEMMs (batch invariant: any size)
     const long TB = Tt < kTextFfnRows ? Tt : kTextFfnRows;     // text rows per block of the text FFN
     long tb_max = 0;                                           // text rows of the largest row block
@@ -900,14 +931,16 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
                           (size_t)RB * Q * c.inter * sizeof(float) > h->vinter.bytes || tact > h->tA.bytes || tact > h->t1.bytes ||
                           (size_t)tb_max * 3 * Hd * sizeof(float) > h->tqkv.bytes || (size_t)tb_max * Hd * sizeof(float) > h->tsa.bytes ||
                           (size_t)TB * c.inter * sizeof(float) > h->tinter.bytes ||
-                          (use_ltm && ((size_t)C * S * sizeof(double) > h->vu.bytes || (size_t)C * T * c.enc_width * sizeof(float) > h->vkbar.bytes));
+                          (use_ltm && ((size_t)C * S * sizeof(double) > h->vu.bytes || (size_t)Cf * T * c.enc_width * sizeof(float) > h->vkbar.bytes)) ||
+                          (streams && (size_t)C * sizeof(int32_t) > h->smap.bytes);
         if (grow) HIP_TRY(hipDeviceSynchronize());
+        if (streams) HIP_TRY(h->smap.reserve((size_t)C * sizeof(int32_t)));
         HIP_TRY(h->vA.reserve(act)); HIP_TRY(h->v1.reserve(act)); HIP_TRY(h->v2.reserve(act)); HIP_TRY(h->vxq.reserve(act));
         HIP_TRY(h->vshort.reserve(act)); HIP_TRY(h->vmerged.reserve(act));
         if (use_ltm) {
             HIP_TRY(h->valong.reserve(act));
             HIP_TRY(h->vu.reserve((size_t)C * S * sizeof(double)));
-            HIP_TRY(h->vkbar.reserve((size_t)C * T * c.enc_width * sizeof(float)));
+            HIP_TRY(h->vkbar.reserve((size_t)Cf * T * c.enc_width * sizeof(float)));
         }
         HIP_TRY(h->vqkv.reserve((size_t)RB * Q * 3 * Hd * sizeof(float)));
         HIP_TRY(h->vsa.reserve((size_t)RB * Q * Hd * sizeof(float)));
@@ -932,22 +965,45 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
     //      when they fit INFV_VQF_SPLIT_CACHE_GB) and the frame means every cross layer's memories step from
     SplitRef wref{}; bool have_w = false, have_kbar = false;
     if (n_cross > 0) {
-        const double need_gb = 4.0 * (double)C * (double)chunk_k * 2.0 / 1e9;
+        const double need_gb = 4.0 * (double)Cf * (double)chunk_k * 2.0 / 1e9;   // (streams: the distinct chunks only)
         if (h->fuse && split_path(h, n_tokens) && need_gb <= h->split_cache_gb) {
             have_kbar = use_ltm && 64 % c.tokens_per_frame == 0;
-            if (int rc = prepare_split(h, frames, INFV_TOKENS_F32, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
+            if (int rc = prepare_split(h, frames, INFV_TOKENS_F32, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
             have_w = true;
         }
         if (use_ltm && !have_kbar) {
             if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;
-            if (int rc = infv_ltm_pool(ltm[0], frames, (int64_t)C * T, h->vkbar.as<float>(), stream_)) return rc;
+            if (int rc = infv_ltm_pool(ltm[0], frames, (int64_t)Cf * T, h->vkbar.as<float>(), stream_)) return rc;
         }
     }
-    auto pre_at = [&](int c0, SplitRef* r) -> const SplitRef* {
-        if (!have_w) return nullptr;
-        const long o = (long)c0 * chunk_k;
-        *r = SplitRef{wref.Fh + o, wref.Fl + o, wref.Th + o, wref.Tl + o};
-        return r;
+    // the chunk map reaches the device in kernel arguments, once per call: no host buffer outlives the call, nothing waits on the host
+    if (streams && n_cross > 0) HIP_TRY(launch_qf_write_map(h->smap.as<int32_t>(), src_chunk.data(), C, stream));
+    // The frame operand of the short-term attention of stream-chunks [c0, c0 + nb): *fr (fp32 path) or the planes *r, and the map
+    // the contractions read them through (nullptr: chunk b of the sub-batch is entry b).
+    //   videos:  today's -- the cached planes at c0, else the caller's tokens at c0 (split per sub-batch inside short_attention)
+    //   streams: the cached planes of the DISTINCT chunks, or the caller's tokens on the fp32 path, read through the map; where the
+    //            planes do not fit, each contiguous run of source chunks is split into the sub-batch's own planes (identity map)
+    auto operand_at = [&](int c0, int nb, SplitRef* r, const SplitRef** pre, const float** fr, const int32_t** map) -> int {
+        *pre = nullptr; *map = nullptr; *fr = frames + (long)c0 * chunk_k;
+        if (!streams) {
+            if (have_w) {
+                const long o = (long)c0 * chunk_k;
+                *r = SplitRef{wref.Fh + o, wref.Fl + o, wref.Th + o, wref.Tl + o};
+                *pre = r;
+            }
+            return INFV_OK;
+        }
+        if (have_w) { *r = wref; *pre = r; *map = h->smap.as<int32_t>() + c0; return INFV_OK; }
+        if (!split_path(h, n_tokens)) { *fr = frames; *map = h->smap.as<int32_t>() + c0; return INFV_OK; }
+        for (int b0 = 0; b0 < nb;) {
+            int b1 = b0 + 1;
+            while (b1 < nb && src_chunk[c0 + b1] == src_chunk[c0 + b1 - 1] + 1) ++b1;
+            if (int rc = prepare_split(h, frames + (long)src_chunk[c0 + b0] * chunk_k, INFV_TOKENS_F32, b1 - b0, n_tokens, nullptr, false, r,
+                                       stream, b0, nb)) return rc;
+            b0 = b1;
+        }
+        *pre = r;
+        return INFV_OK;
     };
     std::vector<infv_ltm_handle> hs_l(use_ltm ? V : 0);
     std::vector<int32_t> off1(RB);
@@ -1001,16 +1057,17 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
                 HIP_TRY(hipEventRecord(h->ev_main, stream));
                 HIP_TRY(hipStreamWaitEvent(h->side, h->ev_main, 0));
                 for (int v = 0; v < V; ++v) hs_l[v] = ltm[(size_t)v * n_cross + j_cross];
-                if (int rc = infv_ltm_steps_videos(hs_l.data(), V, cu, h->vkbar.as<float>(), T, vxq, 1, Q, &pr,
-                                                   u ? h->vu.as<double>() : nullptr, new_video, valong, h->side)) return rc;
+                if (int rc = infv_ltm_steps_videos_from(hs_l.data(), V, cu, h->vkbar.as<float>(), streams ? kbar0.data() : nullptr, T, vxq, 1,
+                                                        Q, &pr, u ? h->vu.as<double>() : nullptr, new_video, valong, h->side)) return rc;
                 HIP_TRY(hipEventRecord(h->ev_side, h->side));
             }
             for (int c0 = 0; c0 < C; c0 += NB) {
                 const int nb = C - c0 < NB ? C - c0 : NB;
-                SplitRef sr;
-                if (int rc = short_attention(h, frames + (long)c0 * chunk_k, INFV_TOKENS_F32, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
+                SplitRef sr; const SplitRef* pre; const float* fr; const int32_t* map;
+                if (int rc = operand_at(c0, nb, &sr, &pre, &fr, &map)) return rc;
+                if (int rc = short_attention(h, fr, INFV_TOKENS_F32, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
                                              nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
-                                             pre_at(c0, &sr), nullptr, kInvariantNb)) return rc;
+                                             pre, nullptr, kInvariantNb, map)) return rc;
             }
             if (use_ltm) {
                 HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
@@ -1075,6 +1132,23 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
         if (proj_mean) HIP_TRY(launch_qf_mean_segments(lo, cu, V, (long)Q * c.proj_out, proj_mean, stream));
     }
     return INFV_OK;
+}
+
+int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+                              int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len,
+                              const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
+                              void* stream_) {
+    return vc_impl("vc_encode_videos", h, ltm, V, cu, frames, 0, nullptr, nullptr, T, w, hidden_in, text_len, u, new_video, hidden_out,
+                   proj_out, proj_mean, stream_);
+}
+
+int infv_vqf_vc_encode_streams(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+                               int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w,
+                               const float* hidden_in, const int32_t* text_len, const double* u, int32_t new_video,
+                               float* hidden_out, float* proj_out, float* proj_mean, void* stream_) {
+    if (!fcu || !frame_src) return fail(INFV_ERR_INVALID, "vc_encode_streams: bad arguments");
+    return vc_impl("vc_encode_streams", h, ltm, V, cu, frames, F, fcu, frame_src, T, w, hidden_in, text_len, u, new_video, hidden_out,
+                   proj_out, proj_mean, stream_);
 }
 
 int infv_vqf_mean(const float* in, int32_t n, int64_t elems, float* out, void* stream) {

@@ -27,6 +27,7 @@ struct QfGemm {
     int K;                                           // total depth; 0 = splitk * k_per_split (the last split may be shorter)
     int inner;  long strideA2, strideB2, strideC2;   // optional second batch level (zero-initialised = unused)
     int tile;                                        // 0: 128 x 128 tiles where M and N reach 128, else 64 x 64; 64 / 128: that tile
+    const int32_t* b_map;                            // device [nbatch] or nullptr: batch entry b reads B at b_map[b] * strideB (one batch level)
 };
 hipError_t launch_qf_gemm(const QfGemm& g, bool nn, hipStream_t stream);
 int qf_pick_splitk(int M, int N, int K, int nbatch);
@@ -68,6 +69,10 @@ constexpr int kRowSegs = 128;
 hipError_t launch_qf_copy_rows(const float* src, float* dst, const int32_t* dst_row, const int32_t* src_row, const int32_t* n_rows,
                                int n_segs, int width, hipStream_t stream);
 
+// dst[0, n) = tab[0, n): a HOST int32 table written to device memory through kernel arguments (no host buffer outlives the call)
+constexpr int kMapChunk = 512;
+hipError_t launch_qf_write_map(int32_t* dst, const int32_t* tab, int n, hipStream_t stream);
+
 // qt[b][h*Q + q][j] = sum_e xq[b][q][h*64 + e] / sqrt(64) * Wk[h*64 + e][j]
 hipError_t launch_qf_qtilde(const float* xq, int nb, int Q, int H, int d, const float* wk, float* qt, hipStream_t stream);
 
@@ -86,6 +91,8 @@ struct SplitGemm {
     int M, N, K, k_per_split, splitk, nbatch;
     long long* wg_stamps;            // residency / loop-cycle experiment (wg_stamps.h), or nullptr
     int wide;                        // 0: the 384 x 256 kernel where whole tiles fill the chip; 1: wherever whole tiles apply
+    const int32_t* b_map;            // device [nbatch] or nullptr: batch entry b reads its B operand at b_map[b] * strideB (A, C and
+                                     // the split-K slabs keep indexing by b; nullptr = b itself)
 };
 hipError_t launch_split_gemm(const SplitGemm& g, hipStream_t stream, int lds_pad = 0);
 // fp32-accurate contraction from three bf16 planes per operand (six partial products, fp32 accumulation): C = A . B^T

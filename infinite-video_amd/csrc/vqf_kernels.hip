@@ -42,7 +42,8 @@ __global__ __launch_bounds__(256) void qf_gemm_kernel(QfGemm g) {
     const int bo = g.inner > 0 ? b / g.inner : 0, bi = g.inner > 0 ? b - bo * g.inner : b;
     const float* A = g.A + (long)bi * g.strideA + (long)bo * g.strideA2;
     float* C = g.C + (long)bi * g.strideC + (long)bo * g.strideC2 + (long)s * g.split_stride;
-    const long boff = (long)bi * g.strideB + (long)bo * g.strideB2;
+    const int bb = g.b_map ? g.b_map[bi] : bi;       // (uniform over the workgroup: one scalar read)
+    const long boff = (long)bb * g.strideB + (long)bo * g.strideB2;
 
     const int c4 = tid & 7, row0 = tid >> 3;
     const float* a_src[AR];
@@ -586,6 +587,22 @@ __global__ __launch_bounds__(256) void qf_copy_rows_kernel(const float* __restri
     const float4* in = reinterpret_cast<const float4*>(src) + (long)sg.src[s] * width4;
     float4* out = reinterpret_cast<float4*>(dst) + (long)sg.dst[s] * width4;
     for (long i = (long)blockIdx.y * 256 + threadIdx.x; i < total; i += 256L * gridDim.y) out[i] = in[i];
+}
+
+// dst[0, n) = tab[0, n) (HOST table), written by kernels that carry kMapChunk entries each in their arguments
+struct MapChunk { int32_t v[kMapChunk]; };
+__global__ __launch_bounds__(256) void qf_write_map_kernel(int32_t* __restrict__ dst, MapChunk c, int n) {
+    for (int i = threadIdx.x; i < n; i += 256) dst[i] = c.v[i];
+}
+
+hipError_t launch_qf_write_map(int32_t* dst, const int32_t* tab, int n, hipStream_t stream) {
+    for (int i = 0; i < n; i += kMapChunk) {
+        const int m = n - i < kMapChunk ? n - i : kMapChunk;
+        MapChunk c;
+        for (int j = 0; j < kMapChunk; ++j) c.v[j] = j < m ? tab[i + j] : 0;
+        INFV_LAUNCH(qf_write_map_kernel, dim3(1), dim3(256), 0, stream, dst + i, c, m);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_qf_copy_rows(const float* src, float* dst, const int32_t* dst_row, const int32_t* src_row, const int32_t* n_rows,

@@ -598,14 +598,19 @@ def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.T
 
 
 def steps_videos(engines: Sequence[LTMEngine], kbar, chunk_counts, q: torch.Tensor, projs: Sequence[ProjTensors],
-                 u=None, new_doc: bool = True) -> torch.Tensor:
+                 u=None, new_doc: bool = True, kbar_chunk0: Optional[Sequence[int]] = None) -> torch.Tensor:
     """``consolidate_videos`` from frame means, with an optional query per chunk (infv_ltm_steps_videos).
 
     ``kbar`` is PACKED [sum C_v, T, d] fp32 (``pool()`` of the tokens), or a list of per-video [C_v, T, d] tensors (packed with
     one copy).  ``q`` is either [L, Q, dm], shared by every chunk, or [sum C_v, L, Q, dm], one query per chunk (a cross-attention
     layer after the first, as ``steps`` takes it); ``q.dim()`` decides.  ``u``, ``chunk_counts``, ``new_doc`` and the result
     ctx [sum C_v, L, Q, dm] are ``consolidate_videos``'s.  With a shared query and kbar = pool(k) the bits equal
-    ``consolidate_videos(k, q)``'s; each video's bits do not depend on the rest of the batch."""
+    ``consolidate_videos(k, q)``'s; each video's bits do not depend on the rest of the batch.
+
+    ``kbar_chunk0`` [V] (infv_ltm_steps_videos_from): chunk i of video v reads its frame means at ``kbar[kbar_chunk0[v] + i]``,
+    so several memories may step from one block of frame means; ``kbar`` is then PACKED [n, T, d] with every
+    ``kbar_chunk0[v] + C_v <= n`` and ``chunk_counts`` is required.  ``u``, ``q`` and the result stay packed by video.  The
+    bits are those of the call on a kbar that holds each video's own copy."""
     if isinstance(kbar, (list, tuple)) and chunk_counts is None:
         chunk_counts = [int(x.shape[0]) for x in kbar]
     engines, cu = _video_engines(engines, chunk_counts, "steps_videos")
@@ -616,7 +621,17 @@ def steps_videos(engines: Sequence[LTMEngine], kbar, chunk_counts, q: torch.Tens
     V, e0 = len(engines), engines[0]
     total = int(cu[-1])
     _check_dev(kbar, e0.device, "kbar")
-    if kbar.dim() != 3 or kbar.shape[0] != total or kbar.shape[2] != e0.d:
+    base = None
+    if kbar_chunk0 is not None:
+        base = np.ascontiguousarray(np.asarray(list(kbar_chunk0), dtype=np.int64))
+        if base.shape != (V,):
+            raise ValueError(f"{base.size} kbar_chunk0 entries for {V} videos")
+        if kbar.dim() != 3 or kbar.shape[2] != e0.d:
+            raise ValueError(f"kbar must be fp32 [n, T, {e0.d}], got {tuple(kbar.shape)}")
+        if np.any(base + np.diff(cu) > kbar.shape[0]) or np.any(np.abs(base) >= 2 ** 31):
+            raise ValueError(f"kbar_chunk0 + chunk_counts reaches beyond kbar's {kbar.shape[0]} chunks")
+        base = np.ascontiguousarray(base.astype(np.int32))          # (a negative entry is the library's refusal)
+    elif kbar.dim() != 3 or kbar.shape[0] != total or kbar.shape[2] != e0.d:
         raise ValueError(f"kbar must be fp32 [{total}, T, {e0.d}], got {tuple(kbar.shape)}")
     if kbar.data_ptr() % 16:
         raise ValueError("kbar must start at a 16-byte boundary (the chunks are copied as float4)")
@@ -635,6 +650,11 @@ def steps_videos(engines: Sequence[LTMEngine], kbar, chunk_counts, q: torch.Tens
     out = torch.empty(total, e0.L, Q, e0.dm, device=e0.device, dtype=torch.float32)
     hs = (C.c_void_p * V)(*[e._h.value for e in engines])
     with torch.cuda.device(e0.device):
-        _lib.check(e0.lib.infv_ltm_steps_videos(C.cast(hs, C.c_void_p), V, C.c_void_p(cu.ctypes.data), _ptr(kbar), T, _ptr(q),
-                                                per_chunk, Q, proj_arr, _ptr(u), int(new_doc), _ptr(out), _stream(e0.device)))
+        if base is not None:
+            _lib.check(e0.lib.infv_ltm_steps_videos_from(C.cast(hs, C.c_void_p), V, C.c_void_p(cu.ctypes.data), _ptr(kbar),
+                                                         C.c_void_p(base.ctypes.data), T, _ptr(q), per_chunk, Q, proj_arr, _ptr(u),
+                                                         int(new_doc), _ptr(out), _stream(e0.device)))
+        else:
+            _lib.check(e0.lib.infv_ltm_steps_videos(C.cast(hs, C.c_void_p), V, C.c_void_p(cu.ctypes.data), _ptr(kbar), T, _ptr(q),
+                                                    per_chunk, Q, proj_arr, _ptr(u), int(new_doc), _ptr(out), _stream(e0.device)))
     return out

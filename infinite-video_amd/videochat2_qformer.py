@@ -429,10 +429,41 @@ class VideoChat2Encoder(nn.Module):
         it (video by video, chunk by chunk, 512 + 512 per LTM instance, nothing on a new video's first chunk).  With
         :meth:`use_device_rng` and ``u=None`` nothing is drawn on the host: cross layer i of video id ``video_ids[v]`` (default:
         v) draws from stream ``(id + 1) * n_cross + i``; the model's own modules keep stream i."""
+        return self._vc_call("encode_videos", videos, None, text_embeds, hidden_in, new_video, u, memories, video_ids, want_hidden)
+
+    def encode_streams(self, videos: Sequence[torch.Tensor], frame_src: Sequence[int], text_embeds=None, hidden_in=None,
+                       new_video: bool = True, u: Optional[torch.Tensor] = None,
+                       memories: Optional[Sequence["VideoChat2Memory"]] = None, video_ids: Optional[Sequence[int]] = None,
+                       want_hidden: bool = False):
+        """Several instructions per video over ONE copy of its frame tokens (``infv_vqf_vc_encode_streams``).  The Q-former
+        takes the instruction as input (videochat2_it_mistral.py:204-223), so queries, draws and memories depend on it; the
+        frame tokens do not.
+
+        ``videos``: the F distinct [C_f, T*P, width] frame-token tensors.  ``frame_src[v]``: the block stream v reads, in any
+        order; several streams may name one block.  ``text_embeds`` / ``hidden_in`` (one for all or one per stream),
+        ``memories`` and ``video_ids`` are per STREAM; ``u`` is [sum over streams of C, n_cross, 512].  Returns
+        :meth:`encode_videos`'s triple, per stream, and its bits: those of ``encode_videos([videos[s] for s in frame_src], ...)``
+        -- without the copies, with one token pass over the distinct chunks.  The default host uniforms are drawn stream by
+        stream exactly as ``draw_vc_uniforms`` draws them for that many videos; with :meth:`use_device_rng` stream v draws from
+        the stream ids ``encode_videos`` gives video id ``video_ids[v]`` (default: v)."""
+        return self._vc_call("encode_streams", videos, frame_src, text_embeds, hidden_in, new_video, u, memories, video_ids, want_hidden)
+
+    def _vc_call(self, name, videos, frame_src, text_embeds, hidden_in, new_video, u, memories, video_ids, want_hidden):
+        """Body of :meth:`encode_videos` (``frame_src`` None: video v reads ``videos[v]``) and :meth:`encode_streams`.  Everything
+        a caller can get wrong on the host raises ValueError before any device call."""
         videos = list(videos)
-        V = len(videos)
-        if V == 0:
-            raise ValueError("encode_videos needs at least one video")
+        F = len(videos)
+        if F == 0:
+            raise ValueError(f"{name} needs at least one video")
+        streams = frame_src is not None
+        if streams:
+            frame_src = [int(s) for s in frame_src]
+            for v, s_ in enumerate(frame_src):
+                if not 0 <= s_ < F:
+                    raise ValueError(f"frame_src[{v}] = {s_} outside [0, {F})")
+            if not frame_src:
+                raise ValueError(f"{name} needs at least one stream")
+        V = len(frame_src) if streams else F
         cfg = self.qformer.config
         P, Q = self.tokens_per_frame, self.n_query
         n_cross = len(self.qformer.cross_layers)
@@ -443,7 +474,8 @@ class VideoChat2Encoder(nn.Module):
                 raise ValueError(f"videos[{v}] has T = {f.size(1) // P}, videos[0] has T = {videos[0].size(1) // P}: "
                                  "one call takes one chunk length")
         T = videos[0].size(1) // P
-        counts = [int(f.size(0)) for f in videos]
+        block_counts = [int(f.size(0)) for f in videos]
+        counts = [block_counts[s_] for s_ in frame_src] if streams else block_counts   # chunks per stream
         total = sum(counts)
         rows = self._vc_inputs(V, text_embeds, hidden_in)
         text_len = [int(r.size(0)) - Q for r in rows]
@@ -452,6 +484,8 @@ class VideoChat2Encoder(nn.Module):
             memories = _check_vc_memories(self, memories, V)
         if video_ids is not None and len(video_ids) != V:
             raise ValueError(f"{len(video_ids)} video_ids for {V} videos")
+        if u is not None and use_ltm and tuple(u.shape) != (total, n_cross, NB_SAMPLES):
+            raise ValueError(f"u must be [{total}, {n_cross}, {NB_SAMPLES}]")
         if not all(f.is_cuda for f in videos):
             raise RuntimeError("the VideoChat2 binding runs on the HIP device only (no CPU fallback)")
         device = videos[0].device
@@ -459,7 +493,7 @@ class VideoChat2Encoder(nn.Module):
         if total == 0 and not (use_ltm and new_video):
             return (torch.empty(0, Q, llm, device=device), torch.full((V, Q, llm), float("nan"), device=device),
                     [torch.empty(0, Q + n, cfg.hidden_size, device=device) for n in text_len] if want_hidden else None)
-        frames = _dev_f32(torch.cat(videos) if V > 1 else videos[0], device)
+        frames = _dev_f32(torch.cat(videos) if F > 1 else videos[0], device)
         hin = torch.cat([_dev_f32(r, device) for r in rows]).contiguous()
         handles = None
         if not use_ltm:
@@ -492,12 +526,19 @@ class VideoChat2Encoder(nn.Module):
         cu = (C.c_int32 * (V + 1))(0, *_cumsum(counts))
         tl = (C.c_int32 * V)(*text_len)
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        with torch.cuda.device(device):
-            _lib.check(_lib.load().infv_vqf_vc_encode_videos(
-                self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()), T, C.byref(w),
-                C.c_void_p(hin.data_ptr()), C.cast(tl, C.c_void_p), C.c_void_p(0 if u is None else u.data_ptr()),
+        tail = (T, C.byref(w), C.c_void_p(hin.data_ptr()), C.cast(tl, C.c_void_p), C.c_void_p(0 if u is None else u.data_ptr()),
                 int(bool(new_video)), C.c_void_p(0 if hidden is None else hidden.data_ptr()), C.c_void_p(proj.data_ptr()),
-                C.c_void_p(mean.data_ptr()), stream))
+                C.c_void_p(mean.data_ptr()), stream)
+        with torch.cuda.device(device):
+            if streams:
+                fcu = (C.c_int32 * (F + 1))(0, *_cumsum(block_counts))
+                src = (C.c_int32 * V)(*frame_src)
+                _lib.check(_lib.load().infv_vqf_vc_encode_streams(
+                    self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()), F,
+                    C.cast(fcu, C.c_void_p), C.cast(src, C.c_void_p), *tail))
+            else:
+                _lib.check(_lib.load().infv_vqf_vc_encode_videos(
+                    self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()), *tail))
         del keep
         hid = None
         if want_hidden:
@@ -623,3 +664,40 @@ def encode_long_videos_vc(model: VideoChat2Encoder, frame_tokens_list: Sequence[
             out[v] = (mean[j:j + 1], [proj[r0 + c:r0 + c + 1] for c in range(n_c)])
             r0 += n_c
     return out
+
+
+def encode_long_video_prompts_vc(model: VideoChat2Encoder, frame_tokens: torch.Tensor, num_samples: int,
+                                 text_embeds_list: Sequence[Optional[torch.Tensor]], hidden_in_list=None,
+                                 memories: Optional[Sequence[VideoChat2Memory]] = None,
+                                 video_ids: Optional[Sequence[int]] = None):
+    """K instructions asked of ONE video (the eval loop with the question passed to the Q-former,
+    eval_code/run_nextqa_mistral.py:141-152 with ``system_q``): ``frame_tokens`` [F, 196, width] is cut as
+    :func:`encode_long_video_vc` cuts it, and every instruction of ``text_embeds_list`` is a stream of
+    :meth:`VideoChat2Encoder.encode_streams` over the one copy of its chunks.  Where the cut does not batch (see
+    :func:`batched_chunks_vc`) it is the loop over :func:`encode_long_video_vc`, instruction by instruction; the global generator
+    is consumed in that loop's order either way (not at all with :meth:`VideoChat2Encoder.use_device_rng`).
+    ``hidden_in_list``: None or one entry per instruction; ``memories`` / ``video_ids``: one per instruction.
+    Returns a list of (mean [1, n_query, llm_hidden], per-chunk list) per instruction."""
+    tes = list(text_embeds_list)
+    K = len(tes)
+    if K == 0:
+        raise ValueError("encode_long_video_prompts_vc needs at least one instruction")
+    his = [None] * K if hidden_in_list is None else list(hidden_in_list)
+    if len(his) != K:
+        raise ValueError(f"{len(his)} hidden_in for {K} instructions")
+    if memories is not None and len(memories) != K:
+        raise ValueError(f"{len(memories)} memories for {K} instructions")
+    if video_ids is not None and len(video_ids) != K:
+        raise ValueError(f"{len(video_ids)} video_ids for {K} instructions")
+    P = model.tokens_per_frame
+    T = batched_chunks_vc(int(frame_tokens.size(0)), num_samples, P)
+    if T is None:
+        return [encode_long_video_vc(model, frame_tokens, num_samples, tes[k], his[k]) for k in range(K)]
+    cfg = model.qformer.config
+    n_cross = len(model.qformer.cross_layers)
+    n_c = int(frame_tokens.size(0)) // T
+    host_u = cfg.alpha != 1.0 and bool(cfg.sticky) and model._device_rng_seed is None and n_cross > 0
+    u = draw_vc_uniforms([n_c] * K, [False] * K, n_cross) if host_u else None
+    proj, mean, _ = model.encode_streams([frame_tokens.reshape(n_c, T * P, frame_tokens.size(-1))], [0] * K, tes, his, True, u,
+                                         memories, video_ids)
+    return [(mean[k:k + 1], [proj[k * n_c + c:k * n_c + c + 1] for c in range(n_c)]) for k in range(K)]
