@@ -209,7 +209,9 @@ typedef struct {
  * binding to fp32 rounding.  Token counts that are a multiple of 32 but not of 64 take the exact-fp32 contractions.
  * Refused before any device work or memory change: bad cu, a null or repeated LTM handle, negative text_len (INFV_ERR_INVALID);
  * n_query + text_len[v] > 608, n_layers > 24, T * tokens_per_frame not a multiple of 32, fp16 or bf16 tokens set on the handle
- * (INFV_ERR_UNSUPPORTED). */
+ * (INFV_ERR_UNSUPPORTED).
+ * This call and infv_vqf_vc_encode_streams read fp32 tokens only: fp16 / bf16 tokens go to infv_vqf_vc_encode_videos_tok /
+ * infv_vqf_vc_encode_streams_tok below, which take the element type as an argument and read the tokens in place. */
 int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
                               int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len,
                               const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
@@ -244,6 +246,39 @@ int infv_vqf_vc_encode_streams(infv_vqf_handle h, const infv_ltm_handle* ltm, in
                                int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w,
                                const float* hidden_in, const int32_t* text_len, const double* u, int32_t new_video,
                                float* hidden_out, float* proj_out, float* proj_mean, void* stream);
+
+/* infv_vqf_vc_encode_videos / infv_vqf_vc_encode_streams with the frame tokens' element type as an ARGUMENT of the call
+ * (additive): token_dtype is an infv_token_dtype code -- 0 fp32, 1 bf16, 3 fp16 -- and `frames` holds that type.  The handle's
+ * infv_vqf_set_token_dtype setting is neither read nor changed.  Code 0 is the call without the argument: its bits, its
+ * launches.  fp16 / bf16 tokens are read in place at 2 bytes per element (no fp32 copy) and give the bits of the fp32 call on
+ * the same values: an fp16 value is exactly its bf16 hi + lo planes, a bf16 value is its own hi plane (the contractions then take
+ * two products instead of three), and the frame means are summed in token order in fp32 either way.  Where T * tokens_per_frame
+ * is a multiple of 64 the token pass writes the planes, and the frame means too where a frame divides its 64-token tile; other
+ * frame sizes (tokens_per_frame = 196) pool through infv_ltm_pool at the token type, then split -- a one-launch form for them was
+ * measured slower than these two and is not shipped.  Token counts that are a multiple of 32 only, infv_vqf_set_precision(h, 1)
+ * and INFV_VQF_FP32 take the fp32 contractions from an fp32 copy of the distinct chunks in the handle's workspace.
+ * Refused before any device work or memory change, beside the refusals of the calls without the argument: an unknown code,
+ * fp16 / bf16 `frames` that are not 16-byte aligned (INFV_ERR_INVALID). */
+int infv_vqf_vc_encode_videos_tok(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
+                                  int32_t token_dtype, int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in,
+                                  const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out,
+                                  float* proj_mean, void* stream);
+
+int infv_vqf_vc_encode_streams_tok(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
+                                   int32_t token_dtype, int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T,
+                                   const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len, const double* u,
+                                   int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean, void* stream);
+
+/* The token pass alone (exported for tests and measurements, as infv_vqf_self_attention is): the launches the encoders issue for
+ * frames [nb][n_tokens][d] of element type token_dtype.
+ *   Fh, Fl [nb][n_tokens][d], Th, Tl [nb][d][n_tokens] bf16: the hi / lo planes and their transposed copies.  bf16 tokens are
+ *          their own hi plane: Fh, Fl and Tl must be NULL and only Th is written.
+ *   kbar   [nb][n_tokens / tokens_per_frame][d] fp32 frame means, the bits of infv_ltm_pool; NULL: planes only
+ * n_tokens a multiple of 32, d a multiple of 64, every pointer 16-byte aligned, tokens_per_frame dividing n_tokens where kbar is
+ * given (INFV_ERR_INVALID otherwise).  INFV_ERR_UNSUPPORTED, and no launch, where no one-pass form with the means exists:
+ * kbar given and tokens_per_frame not dividing 64. */
+int infv_vqf_token_pass(const void* frames, int32_t token_dtype, int32_t nb, int32_t n_tokens, int32_t d, int32_t tokens_per_frame,
+                        void* Fh, void* Fl, void* Th, void* Tl, float* kbar, void* stream);
 
 /* out[i] = mean over n of in[n][i]  (the eval loop's mean over chunk embeddings,
  * run_inference_inf_video_llama_nextqa.py:194) */

@@ -196,6 +196,14 @@ _SIGNATURES = {
     "infv_vqf_vc_encode_streams": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                              C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(VqfVcWeights), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infv_vqf_vc_encode_videos_tok": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                C.POINTER(VqfVcWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infv_vqf_vc_encode_streams_tok": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(VqfVcWeights), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infv_vqf_token_pass": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infv_vqf_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 KERNELS = ("pool", "rows", "project", "draw", "update", "attend", "scores", "chain", "uc")

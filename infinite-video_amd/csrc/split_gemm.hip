@@ -1034,6 +1034,23 @@ hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, 
     return hipGetLastError();
 }
 
+// The token pass of `nb` <= 32768 chunks (grid.z) for any token type: the launch prepare_split issues.  kbar != nullptr needs
+// token_pass_gives_means(P): a frame that divides the 64-token tile.  (A per-frame form for P = 196 -- one workgroup per frame,
+// slab and chunk, the column sums kept in registers across sub-tiles -- was measured at 128 eval-shape chunks and lost to pooling
+// + this pass for fp16 and bf16 tokens alike, profiles/vc_half_tokens.jsonl; it is gone.)  bf16: Fh / Fl / Tl are not written.
+bool token_pass_gives_means(int P) { return P >= 1 && 64 % P == 0; }
+
+hipError_t launch_token_pass(const void* F, infv_token_dtype tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
+                             hipStream_t stream, float* kbar, int P) {
+    if (kbar && !token_pass_gives_means(P)) return hipErrorInvalidValue;
+    switch (tok) {
+        case INFV_TOKENS_BF16: return launch_transpose_bf16(F, nb, n, d, Th, stream, kbar, P);
+        case INFV_TOKENS_F16: return launch_split_transpose_f16(F, nb, n, d, Fh, Fl, Th, Tl, stream, kbar, P);
+        case INFV_TOKENS_F32: return launch_split_transpose(static_cast<const float*>(F), nb, n, d, Fh, Fl, Th, Tl, stream, kbar, P);
+    }
+    return hipErrorInvalidValue;
+}
+
 // x [n] bf16 -> y [n] fp32 (n % 8 == 0): bf16 tokens where the split path does not apply run the fp32 kernels from this copy
 __global__ __launch_bounds__(256) void upcast_bf16_kernel(const __bf16* __restrict__ x, float* __restrict__ y, long n8) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;

@@ -140,20 +140,19 @@ static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype to
     const size_t d0 = (size_t)dst0 * n_tokens * d;
     DeviceBuf& Fh = whole ? h->wFh : h->sFh; DeviceBuf& Fl = whole ? h->wFl : h->sFl;
     DeviceBuf& Th = whole ? h->wTh : h->sTh; DeviceBuf& Tl = whole ? h->wTl : h->sTl;
+    const int P = h->cfg.tokens_per_frame;
     if (tok == INFV_TOKENS_BF16) {                           // read in place: only the transposed copy is written
         if (szF > Th.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(Th.reserve(szF)); }
         const __bf16* fb = static_cast<const __bf16*>(frames_);
         for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
             const int n = nb - c0 < 32768 ? nb - c0 : 32768;
             const size_t o = (size_t)c0 * n_tokens * d;
-            HIP_TRY(launch_transpose_bf16(fb + o, n, n_tokens, d, Th.as<__bf16>() + o, stream,
-                                          kbar ? kbar + (size_t)c0 * (n_tokens / h->cfg.tokens_per_frame) * d : nullptr,
-                                          h->cfg.tokens_per_frame));
+            HIP_TRY(launch_token_pass(fb + o, tok, n, n_tokens, d, nullptr, nullptr, Th.as<__bf16>() + d0 + o, nullptr, stream,
+                                      kbar ? kbar + (size_t)c0 * (n_tokens / P) * d : nullptr, P));
         }
-        *ref = SplitRef{fb, nullptr, Th.as<__bf16>(), nullptr};
+        *ref = SplitRef{fb, nullptr, Th.as<__bf16>(), nullptr};   // (Fh: THESE chunks, whatever dst0 is)
         return INFV_OK;
     }
-    const float* frames = static_cast<const float*>(frames_);
     if (szF > Fh.bytes || szF > Fl.bytes || szF > Th.bytes || szF > Tl.bytes) {
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(Fh.reserve(szF)); HIP_TRY(Fl.reserve(szF)); HIP_TRY(Th.reserve(szF)); HIP_TRY(Tl.reserve(szF));
@@ -161,13 +160,9 @@ static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype to
     for (int c0 = 0; c0 < nb; c0 += 32768) {                   // grid.z limit
         const int n = nb - c0 < 32768 ? nb - c0 : 32768;
         const size_t o = (size_t)c0 * n_tokens * d;
-        float* kb = kbar ? kbar + (size_t)c0 * (n_tokens / h->cfg.tokens_per_frame) * d : nullptr;
-        if (tok == INFV_TOKENS_F16)
-            HIP_TRY(launch_split_transpose_f16(tok_at(frames_, tok, (long)o), n, n_tokens, d, Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o,
-                                               Th.as<__bf16>() + d0 + o, Tl.as<__bf16>() + d0 + o, stream, kb, h->cfg.tokens_per_frame));
-        else
-            HIP_TRY(launch_split_transpose(frames + o, n, n_tokens, d, Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o, Th.as<__bf16>() + d0 + o,
-                                           Tl.as<__bf16>() + d0 + o, stream, kb, h->cfg.tokens_per_frame));
+        float* kb = kbar ? kbar + (size_t)c0 * (n_tokens / P) * d : nullptr;
+        HIP_TRY(launch_token_pass(tok_at(frames_, tok, (long)o), tok, n, n_tokens, d, Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o,
+                                  Th.as<__bf16>() + d0 + o, Tl.as<__bf16>() + d0 + o, stream, kb, P));
     }
     *ref = SplitRef{Fh.as<__bf16>(), Fl.as<__bf16>(), Th.as<__bf16>(), Tl.as<__bf16>()};
     return INFV_OK;
@@ -178,7 +173,8 @@ int short_attention(infv_vqf_s* h, const void* frames_, infv_token_dtype tok /* 
                     hipStream_t stream, bool use_cache = false, const SplitRef* pre = nullptr,
                     hipEvent_t along_ready = nullptr /* `along` is produced on another stream: wait here, before the merge */,
                     int inv_nb = 0 /* > 0: batch invariant -- split-K counts and kernel shapes as for inv_nb chunks, whatever nb is */,
-                    const int32_t* b_map = nullptr /* device [nb]: chunk b reads chunk b_map[b] of frames_ / *pre (several streams over one block) */) {
+                    const int32_t* b_map = nullptr /* device [nb]: chunk b reads chunk b_map[b] of frames_ / *pre (several streams over one block) */,
+                    bool t_identity = false /* the transposed plane of *pre holds the sub-batch's chunks in order: only the untransposed operand goes through b_map */) {
     const infv_vqf_config& c = h->cfg;
     const int Q = c.n_query, H = c.n_heads, d = c.enc_width, rows = H * Q;
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
@@ -243,7 +239,7 @@ int short_attention(infv_vqf_s* h, const void* frames_, infv_token_dtype tok /* 
         p.A_hi = h->sPh.as<__bf16>(); p.A_lo = h->sPl.as<__bf16>(); p.lda = n_tokens; p.strideA = (long)rows * n_tokens;
         p.B_hi = sr.Th; p.B_lo = sr.Tl; p.ldb = n_tokens; p.strideB = (long)d * n_tokens;
         p.C = h->O.as<float>(); p.ldc = d; p.strideC = (long)rows * d; p.split_stride = (long)nb * rows * d;
-        p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.wide = inv_nb > 0; p.b_map = b_map;
+        p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.wide = inv_nb > 0; p.b_map = t_identity ? nullptr : b_map;
         HIP_TRY(launch_split_gemm(p, stream));
     } else {
     if (tok != INFV_TOKENS_F32) return fail(INFV_ERR_INVALID, "fp16 / bf16 tokens reached the fp32 contractions");      // (callers upcast first)
@@ -827,12 +823,17 @@ int infv_vqf_self_attention(infv_vqf_handle h, const float* qkv, int32_t nb, int
 
 // The body of infv_vqf_vc_encode_videos (fcu == nullptr: stream v reads its own chunks [cu[v], cu[v+1]) of `frames`) and of
 // infv_vqf_vc_encode_streams (stream v reads block frame_src[v] of the F blocks packed by fcu).  `name` prefixes the refusals.
-static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
+static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
+                   int32_t token_dtype /* < 0: the entry points without the argument -- fp32, refused unless the handle's setting is fp32 too */,
                    int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in,
                    const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
                    void* stream_) {
     // ---- validation before any device work or memory change ----
     if (!h || !cu || !w || !text_len || V < 0) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
+    const bool tok_arg = token_dtype >= 0;                     // the dtype is an argument of the call: the handle's setting is not read
+    if (tok_arg && !token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "%s: unknown token dtype %d", name, token_dtype);
+    infv_token_dtype tok = tok_arg ? static_cast<infv_token_dtype>(token_dtype) : INFV_TOKENS_F32;
+    if (tok != INFV_TOKENS_F32 && frames && !aligned16(frames)) return fail(INFV_ERR_INVALID, "%s: fp16 / bf16 frames must be 16-byte aligned", name);
     if (V == 0) return INFV_OK;
     const infv_vqf_config& c = h->cfg;
     if (cu[0] != 0) return fail(INFV_ERR_INVALID, "%s: cu[0] = %d, not 0", name, cu[0]);
@@ -867,7 +868,8 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     if (T < 1) return fail(INFV_ERR_INVALID, "%s: T must be >= 1", name);
     const int n_tokens = T * c.tokens_per_frame;
     if (n_tokens % 32) return fail(INFV_ERR_UNSUPPORTED, "%s: T * tokens_per_frame = %d is no multiple of 32", name, n_tokens);
-    if (h->tok != INFV_TOKENS_F32) return fail(INFV_ERR_UNSUPPORTED, "%s: fp16 / bf16 frame tokens are not supported on this path", name);
+    if (!tok_arg && h->tok != INFV_TOKENS_F32)
+        return fail(INFV_ERR_UNSUPPORTED, "%s: fp16 / bf16 frame tokens are not supported on this path (the _tok entry point takes them)", name);
     int n_cross = 0;
     for (int l = 0; l < Ln; ++l) n_cross += w->layers[l].has_cross != 0;
     const bool use_ltm = c.alpha != 1.0f && n_cross > 0;
@@ -910,6 +912,11 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     const long M = (long)C * Q, Tt = toff[C];
     const long chunk_k = (long)n_tokens * c.enc_width;
     const int Cf = streams ? fcu[F] : C;                       // distinct chunks of frame tokens
+    if (tok != INFV_TOKENS_F32 && n_cross > 0 && !split_path(h, n_tokens)) {   // today's fp32 kernels from an fp32 copy of the distinct chunks
+        const float* f32 = nullptr;
+        if (int rc = upcast_tokens(h, frames, tok, (size_t)Cf * chunk_k, &f32, stream)) return rc;
+        frames = f32; tok = INFV_TOKENS_F32;
+    }
     std::vector<int32_t> src_chunk, kbar0;                     // streams: each stream-chunk's source chunk, each stream's first one
     if (streams) {
         src_chunk.resize(C); kbar0.resize(V);
@@ -965,15 +972,18 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     //      when they fit INFV_VQF_SPLIT_CACHE_GB) and the frame means every cross layer's memories step from
     SplitRef wref{}; bool have_w = false, have_kbar = false;
     if (n_cross > 0) {
-        const double need_gb = 4.0 * (double)Cf * (double)chunk_k * 2.0 / 1e9;   // (streams: the distinct chunks only)
+        // (streams: the distinct chunks only; bf16 tokens: only the transposed plane is written, as in infv_vqf_encode_video)
+        const double need_gb = (tok == INFV_TOKENS_BF16 ? 1.0 : 4.0) * (double)Cf * (double)chunk_k * 2.0 / 1e9;
         if (h->fuse && split_path(h, n_tokens) && need_gb <= h->split_cache_gb) {
-            have_kbar = use_ltm && 64 % c.tokens_per_frame == 0;
-            if (int rc = prepare_split(h, frames, INFV_TOKENS_F32, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
+            have_kbar = use_ltm && token_pass_gives_means(c.tokens_per_frame);   // (where a frame divides the 64-token tile)
+            if (int rc = prepare_split(h, frames, tok, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
             have_w = true;
         }
         if (use_ltm && !have_kbar) {
-            if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;
-            if (int rc = infv_ltm_pool(ltm[0], frames, (int64_t)Cf * T, h->vkbar.as<float>(), stream_)) return rc;
+            if (int rc = infv_ltm_set_token_dtype(ltm[0], tok)) return rc;
+            const int rc_pool = infv_ltm_pool(ltm[0], frames, (int64_t)Cf * T, h->vkbar.as<float>(), stream_);
+            if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;   // (left on fp32, as before)
+            if (rc_pool) return rc_pool;
         }
     }
     // the chunk map reaches the device in kernel arguments, once per call: no host buffer outlives the call, nothing waits on the host
@@ -983,12 +993,12 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     //   videos:  today's -- the cached planes at c0, else the caller's tokens at c0 (split per sub-batch inside short_attention)
     //   streams: the cached planes of the DISTINCT chunks, or the caller's tokens on the fp32 path, read through the map; where the
     //            planes do not fit, each contiguous run of source chunks is split into the sub-batch's own planes (identity map)
-    auto operand_at = [&](int c0, int nb, SplitRef* r, const SplitRef** pre, const float** fr, const int32_t** map) -> int {
-        *pre = nullptr; *map = nullptr; *fr = frames + (long)c0 * chunk_k;
+    auto operand_at = [&](int c0, int nb, SplitRef* r, const SplitRef** pre, const void** fr, const int32_t** map, bool* t_identity) -> int {
+        *pre = nullptr; *map = nullptr; *t_identity = false; *fr = tok_at(frames, tok, (long)c0 * chunk_k);
         if (!streams) {
             if (have_w) {
                 const long o = (long)c0 * chunk_k;
-                *r = SplitRef{wref.Fh + o, wref.Fl + o, wref.Th + o, wref.Tl + o};
+                *r = SplitRef{wref.Fh + o, wref.Fl ? wref.Fl + o : nullptr, wref.Th + o, wref.Tl ? wref.Tl + o : nullptr};
                 *pre = r;
             }
             return INFV_OK;
@@ -998,9 +1008,13 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
         for (int b0 = 0; b0 < nb;) {
             int b1 = b0 + 1;
             while (b1 < nb && src_chunk[c0 + b1] == src_chunk[c0 + b1 - 1] + 1) ++b1;
-            if (int rc = prepare_split(h, frames + (long)src_chunk[c0 + b0] * chunk_k, INFV_TOKENS_F32, b1 - b0, n_tokens, nullptr, false, r,
+            if (int rc = prepare_split(h, tok_at(frames, tok, (long)src_chunk[c0 + b0] * chunk_k), tok, b1 - b0, n_tokens, nullptr, false, r,
                                        stream, b0, nb)) return rc;
             b0 = b1;
+        }
+        if (tok == INFV_TOKENS_BF16) {                         // the untransposed operand is the caller's buffer: read through the map,
+            r->Fh = static_cast<const __bf16*>(frames);        // while the transposed plane just written holds the sub-batch in order
+            *map = h->smap.as<int32_t>() + c0; *t_identity = true;
         }
         *pre = r;
         return INFV_OK;
@@ -1063,11 +1077,11 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
             }
             for (int c0 = 0; c0 < C; c0 += NB) {
                 const int nb = C - c0 < NB ? C - c0 : NB;
-                SplitRef sr; const SplitRef* pre; const float* fr; const int32_t* map;
-                if (int rc = operand_at(c0, nb, &sr, &pre, &fr, &map)) return rc;
-                if (int rc = short_attention(h, fr, INFV_TOKENS_F32, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
+                SplitRef sr; const SplitRef* pre; const void* fr; const int32_t* map; bool t_identity;
+                if (int rc = operand_at(c0, nb, &sr, &pre, &fr, &map, &t_identity)) return rc;
+                if (int rc = short_attention(h, fr, tok, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
                                              nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
-                                             pre, nullptr, kInvariantNb, map)) return rc;
+                                             pre, nullptr, kInvariantNb, map, t_identity)) return rc;
             }
             if (use_ltm) {
                 HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
@@ -1138,7 +1152,7 @@ int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int
                               int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len,
                               const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
                               void* stream_) {
-    return vc_impl("vc_encode_videos", h, ltm, V, cu, frames, 0, nullptr, nullptr, T, w, hidden_in, text_len, u, new_video, hidden_out,
+    return vc_impl("vc_encode_videos", h, ltm, V, cu, frames, -1, 0, nullptr, nullptr, T, w, hidden_in, text_len, u, new_video, hidden_out,
                    proj_out, proj_mean, stream_);
 }
 
@@ -1147,8 +1161,55 @@ int infv_vqf_vc_encode_streams(infv_vqf_handle h, const infv_ltm_handle* ltm, in
                                const float* hidden_in, const int32_t* text_len, const double* u, int32_t new_video,
                                float* hidden_out, float* proj_out, float* proj_mean, void* stream_) {
     if (!fcu || !frame_src) return fail(INFV_ERR_INVALID, "vc_encode_streams: bad arguments");
-    return vc_impl("vc_encode_streams", h, ltm, V, cu, frames, F, fcu, frame_src, T, w, hidden_in, text_len, u, new_video, hidden_out,
+    return vc_impl("vc_encode_streams", h, ltm, V, cu, frames, -1, F, fcu, frame_src, T, w, hidden_in, text_len, u, new_video, hidden_out,
                    proj_out, proj_mean, stream_);
+}
+
+int infv_vqf_vc_encode_videos_tok(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
+                                  int32_t token_dtype, int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in,
+                                  const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out,
+                                  float* proj_mean, void* stream_) {
+    if (token_dtype < 0) return fail(INFV_ERR_INVALID, "vc_encode_videos_tok: unknown token dtype %d", token_dtype);
+    return vc_impl("vc_encode_videos_tok", h, ltm, V, cu, frames, token_dtype, 0, nullptr, nullptr, T, w, hidden_in, text_len, u, new_video,
+                   hidden_out, proj_out, proj_mean, stream_);
+}
+
+int infv_vqf_vc_encode_streams_tok(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
+                                   int32_t token_dtype, int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T,
+                                   const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len, const double* u,
+                                   int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean, void* stream_) {
+    if (!fcu || !frame_src) return fail(INFV_ERR_INVALID, "vc_encode_streams_tok: bad arguments");
+    if (token_dtype < 0) return fail(INFV_ERR_INVALID, "vc_encode_streams_tok: unknown token dtype %d", token_dtype);
+    return vc_impl("vc_encode_streams_tok", h, ltm, V, cu, frames, token_dtype, F, fcu, frame_src, T, w, hidden_in, text_len, u, new_video,
+                   hidden_out, proj_out, proj_mean, stream_);
+}
+
+int infv_vqf_token_pass(const void* frames, int32_t token_dtype, int32_t nb, int32_t n_tokens, int32_t d, int32_t tokens_per_frame,
+                        void* Fh, void* Fl, void* Th, void* Tl, float* kbar, void* stream) {
+    // ---- every refusal before any launch ----
+    if (!token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "token_pass: unknown token dtype %d", token_dtype);
+    const infv_token_dtype tok = static_cast<infv_token_dtype>(token_dtype);
+    if (!frames || !Th || nb < 0) return fail(INFV_ERR_INVALID, "token_pass: bad arguments");
+    if (tok == INFV_TOKENS_BF16 ? (Fh || Fl || Tl) : (!Fh || !Fl || !Tl))
+        return fail(INFV_ERR_INVALID, "token_pass: bf16 tokens take Th alone (Fh, Fl, Tl NULL), fp32 / fp16 tokens all four planes");
+    if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "token_pass: n_tokens must be a positive multiple of 32");
+    if (d < 64 || d % 64) return fail(INFV_ERR_INVALID, "token_pass: d must be a positive multiple of 64");
+    if (!aligned16(frames) || !aligned16(Fh) || !aligned16(Fl) || !aligned16(Th) || !aligned16(Tl))
+        return fail(INFV_ERR_INVALID, "token_pass: frames and planes must be 16-byte aligned");
+    if (kbar && (tokens_per_frame < 1 || n_tokens % tokens_per_frame))
+        return fail(INFV_ERR_INVALID, "token_pass: tokens_per_frame must divide n_tokens");
+    if (kbar && !token_pass_gives_means(tokens_per_frame))
+        return fail(INFV_ERR_UNSUPPORTED, "token_pass: no one-pass form with the frame means for tokens_per_frame = %d (it must divide 64)",
+                    tokens_per_frame);
+    const size_t chunk = (size_t)n_tokens * d;
+    for (int c0 = 0; c0 < nb; c0 += 32768) {                   // grid.z limit
+        const int n = nb - c0 < 32768 ? nb - c0 : 32768;
+        const size_t o = (size_t)c0 * chunk;
+        auto at = [&](void* p) -> void* { return p ? static_cast<__bf16*>(p) + o : nullptr; };
+        HIP_TRY(launch_token_pass(tok_at(frames, tok, (long)o), tok, n, n_tokens, d, at(Fh), at(Fl), at(Th), at(Tl), static_cast<hipStream_t>(stream),
+                                  kbar ? kbar + (size_t)c0 * (n_tokens / tokens_per_frame) * d : nullptr, tokens_per_frame));
+    }
+    return INFV_OK;
 }
 
 int infv_vqf_mean(const float* in, int32_t n, int64_t elems, float* out, void* stream) {

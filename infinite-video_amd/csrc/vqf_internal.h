@@ -1,6 +1,7 @@
 // Internal interface between the video Q-former C ABI (vqf_capi.hip) and its gfx950 kernels (vqf_kernels.hip).
 #pragma once
 #include "knobs.h"
+#include "../../include/infv_ltm.h"      // infv_token_dtype
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -126,6 +127,10 @@ hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void*
                                       float* kbar = nullptr, int P = 0);
 // x [n] fp16 -> y [n] fp32 (exact), n % 8 == 0
 hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream);
+// the token pass of nb <= 32768 chunks for any token type (bf16: only Th is written); kbar needs token_pass_gives_means(P)
+bool token_pass_gives_means(int P);
+hipError_t launch_token_pass(const void* F, infv_token_dtype tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
+                             hipStream_t stream, float* kbar, int P);
 // softmax of fp32 score rows, written as bf16 hi/lo
 hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long ld, void* Ph, void* Pl, long ld_out, hipStream_t stream);
 

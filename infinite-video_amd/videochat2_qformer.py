@@ -38,7 +38,7 @@ import torch.nn.functional as F
 from . import _lib
 from .basis_maps import NB_SAMPLES
 from .qformer_hook import LongTermMemoryHook
-from .video_qformer import VideoMemory, _cumsum, _dev_f32, draw_video_uniforms
+from .video_qformer import TOKEN_DTYPES, VideoMemory, _cumsum, _dev_f32, draw_video_uniforms
 
 MAX_TXT_LEN = 512              # max_txt_len of the instruction (configs/config_mistral.json)
 
@@ -418,7 +418,9 @@ class VideoChat2Encoder(nn.Module):
         """Many videos through the VideoChat2 Q-former in ONE C call (``infv_vqf_vc_encode_videos``): the whole encoder, layer-major
         over the packed chunks of every video, on the HIP path.
 
-        ``videos``: a list of [C_v, T*P, width] frame-token tensors that all share one T (a video may have no chunk).
+        ``videos``: a list of [C_v, T*P, width] frame-token tensors that all share one T (a video may have no chunk).  If every
+        tensor is fp16, or every one bf16, the tokens are read in place (``infv_vqf_vc_encode_videos_tok``) and the results are
+        the bits of the call on ``tokens.float()``; anything else goes in as fp32.
         ``text_embeds`` / ``hidden_in``: as in :meth:`encode_tokens`, one tensor for every video or a list with one entry per
         video (entries may be None); every chunk of a video starts from the same rows.  ``memories[v]``: video v's
         :class:`VideoChat2Memory` (by default a reused pool of the encoder; the model's own modules are untouched).
@@ -439,7 +441,7 @@ class VideoChat2Encoder(nn.Module):
         takes the instruction as input (videochat2_it_mistral.py:204-223), so queries, draws and memories depend on it; the
         frame tokens do not.
 
-        ``videos``: the F distinct [C_f, T*P, width] frame-token tensors.  ``frame_src[v]``: the block stream v reads, in any
+        ``videos``: the F distinct [C_f, T*P, width] frame-token tensors (fp16 / bf16 as in :meth:`encode_videos`).  ``frame_src[v]``: the block stream v reads, in any
         order; several streams may name one block.  ``text_embeds`` / ``hidden_in`` (one for all or one per stream),
         ``memories`` and ``video_ids`` are per STREAM; ``u`` is [sum over streams of C, n_cross, 512].  Returns
         :meth:`encode_videos`'s triple, per stream, and its bits: those of ``encode_videos([videos[s] for s in frame_src], ...)``
@@ -493,7 +495,18 @@ class VideoChat2Encoder(nn.Module):
         if total == 0 and not (use_ltm and new_video):
             return (torch.empty(0, Q, llm, device=device), torch.full((V, Q, llm), float("nan"), device=device),
                     [torch.empty(0, Q + n, cfg.hidden_size, device=device) for n in text_len] if want_hidden else None)
-        frames = _dev_f32(torch.cat(videos) if F > 1 else videos[0], device)
+        # fp16 / bf16 tokens (every block of one such type) are read in place by the _tok entry points: no fp32 copy, no cat of one
+        # block, a clone only where a view is not contiguous or not 16-byte aligned; anything else goes in as fp32, as before
+        half = videos[0].dtype if videos[0].dtype in (torch.float16, torch.bfloat16) and \
+            all(f.dtype == videos[0].dtype and f.device == device for f in videos) else None
+        if half is None:
+            frames = _dev_f32(torch.cat(videos) if F > 1 else videos[0], device)
+        else:
+            frames = torch.cat(videos) if F > 1 else videos[0].detach()
+            if not frames.is_contiguous() or frames.data_ptr() % 16:
+                frames = frames.clone(memory_format=torch.contiguous_format)
+        tok = () if half is None else (TOKEN_DTYPES[half],)      # the argument the _tok entry points take behind `frames`
+        lib = _lib.load()
         hin = torch.cat([_dev_f32(r, device) for r in rows]).contiguous()
         handles = None
         if not use_ltm:
@@ -533,12 +546,12 @@ class VideoChat2Encoder(nn.Module):
             if streams:
                 fcu = (C.c_int32 * (F + 1))(0, *_cumsum(block_counts))
                 src = (C.c_int32 * V)(*frame_src)
-                _lib.check(_lib.load().infv_vqf_vc_encode_streams(
-                    self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()), F,
+                _lib.check((lib.infv_vqf_vc_encode_streams_tok if tok else lib.infv_vqf_vc_encode_streams)(
+                    self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()), *tok, F,
                     C.cast(fcu, C.c_void_p), C.cast(src, C.c_void_p), *tail))
             else:
-                _lib.check(_lib.load().infv_vqf_vc_encode_videos(
-                    self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()), *tail))
+                _lib.check((lib.infv_vqf_vc_encode_videos_tok if tok else lib.infv_vqf_vc_encode_videos)(
+                    self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()), *tok, *tail))
         del keep
         hid = None
         if want_hidden:
