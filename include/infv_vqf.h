@@ -269,6 +269,72 @@ int infv_vqf_vc_encode_streams_tok(infv_vqf_handle h, const infv_ltm_handle* ltm
                                    const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len, const double* u,
                                    int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean, void* stream);
 
+/* ---- encode_img from what a pipeline holds: the vision encoder's output and the tokenizer's ids (additive) ----
+ * Two pieces of the reference's encode_img stand between the vision encoder and the calls above:
+ *   vision_layernorm (videochat2_it_mistral.py:195; nn.LayerNorm(width, eps = 1e-12), blip2.py:88) over the vision encoder's fp16
+ *     output -- under autocast it hands over an fp32 tensor, twice the bytes of what it read;
+ *   the embedding layer (Qformer.py:54-111, called from videochat2_it_mistral.py:204-223): word_embeddings(input_ids) +
+ *     position_embeddings behind the query tokens, ONE LayerNorm over query and text rows together.
+ * infv_vqf_vc_front carries both; either may be off. */
+typedef struct {
+    const float* gamma;                  /* device fp32 [enc_width]; NULL: no vision LayerNorm (beta is then not read) */
+    const float* beta;                   /* device fp32 [enc_width] */
+    float eps;                           /* 1e-12 in the reference */
+} infv_vqf_vision_ln;
+
+typedef struct {
+    const float* word;                   /* device fp32 [vocab][hidden]; NULL: no embedding layer (hidden_in is read as before) */
+    const float* pos;                    /* device fp32 [max_pos][hidden] */
+    infv_layernorm ln;                   /* bert.embeddings.LayerNorm, eps = the handle's ln_eps */
+    int32_t vocab, max_pos;
+    const float* query_tokens;           /* device fp32 [n_query][hidden]: the raw query tokens (query + extra, concatenated) */
+} infv_vqf_vc_emb;
+
+typedef struct {
+    infv_vqf_vision_ln vision_ln;
+    infv_vqf_vc_emb emb;
+    const int32_t* input_ids;            /* HOST, packed by text_len as cu packs chunks: video v's ids start at sum_{w<v} text_len[w] */
+    int32_t reserved;                    /* 0 */
+} infv_vqf_vc_front;
+
+/* infv_vqf_vc_encode_videos_tok (frame_src == NULL; F and fcu are not read) or infv_vqf_vc_encode_streams_tok (frame_src given)
+ * with `front` in front.  With front NULL, or both of its parts off, it IS that call: its bits, its launches.
+ *   vision LayerNorm on: `frames` is the vision encoder's output in its own type (fp32 / fp16 / bf16, 16-byte aligned), read in
+ *     place.  One launch writes (mean, 1 / sqrt(var + eps)) per distinct token row (8 bytes a token; two-pass, biased variance,
+ *     fixed-order wave reductions); the token pass and the pooling then normalise on load:  y = fma((x - mean) * rstd, gamma, beta)
+ *     with x widened exactly.  No fp32 copy of the tokens is made.  A normalised value is a general fp32 number, so every source
+ *     type writes all four planes and takes the three-product contractions (bf16 too; the planes count 4 x towards
+ *     INFV_VQF_SPLIT_CACHE_GB).  Where the split path does not apply (token counts that are a multiple of 32 only,
+ *     infv_vqf_set_precision(h, 1), INFV_VQF_FP32) the normalised tokens of the distinct chunks are written as fp32 into the
+ *     handle's workspace and the fp32 contractions run from there.
+ *     BITS: for any source type the call equals, bit for bit, the call without the LayerNorm on the fp32 tensor
+ *     infv_vqf_layernorm_tokens writes from the same `frames`.
+ *   embedding layer on: hidden_in must be NULL; video v's encoder input rows are LN(query_tokens[q]) for q < n_query and
+ *     LN(word[ids_v[t]] + pos[t]) for t < text_len[v] (positions start at 0 at the first text token; no padding, no mask).  A
+ *     video's rows do not depend on the batch.  The ids are checked on the host, then staged through a pinned buffer of the handle
+ *     whose reuse waits on an event recorded behind the copy.  BITS: those of the call with hidden_in = infv_vqf_vc_embed's rows.
+ * Refused before any launch or memory change, beside the refusals of the _tok calls (INFV_ERR_INVALID): reserved != 0, gamma
+ * without beta, frames not 16-byte aligned under the LayerNorm, the embedding layer together with a non-NULL hidden_in, a table or
+ * input_ids missing, text_len[v] > max_pos, an id outside [0, vocab) (the message names the video);  INFV_ERR_UNSUPPORTED: the
+ * LayerNorm with enc_width no multiple of 64 or above 4096. */
+int infv_vqf_vc_encode_img(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
+                           int32_t token_dtype, int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T,
+                           const infv_vqf_vc_weights* w, const infv_vqf_vc_front* front, const float* hidden_in,
+                           const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out,
+                           float* proj_mean, void* stream);
+
+/* The vision LayerNorm alone (exported for tests and measurements): out_f32 [n_rows][d] = LayerNorm(frames [n_rows][d]) with the
+ * kernels and the arithmetic of infv_vqf_vc_encode_img -- the reference form of its bits.  d a multiple of 64 up to 4096; frames,
+ * gamma, beta and out_f32 16-byte aligned.  The row statistics go through a process-wide device buffer. */
+int infv_vqf_layernorm_tokens(const void* frames, int32_t token_dtype, int64_t n_rows, int32_t d, const float* gamma,
+                              const float* beta, float eps, float* out_f32, void* stream);
+
+/* The embedding layer alone (exported for tests and measurements): out_rows = the packed encoder input rows of V videos, video v's
+ * n_query + text_len[v] rows of width hidden (query rows first), from front->emb and front->input_ids (front->vision_ln is not
+ * read).  The handle gives n_query, hidden and ln_eps and owns the pinned staging buffer.  Refusals as in infv_vqf_vc_encode_img. */
+int infv_vqf_vc_embed(infv_vqf_handle h, const infv_vqf_vc_front* front, int32_t V, const int32_t* text_len, float* out_rows,
+                      void* stream);
+
 /* The token pass alone (exported for tests and measurements, as infv_vqf_self_attention is): the launches the encoders issue for
  * frames [nb][n_tokens][d] of element type token_dtype.
  *   Fh, Fl [nb][n_tokens][d], Th, Tl [nb][d][n_tokens] bf16: the hi / lo planes and their transposed copies.  bf16 tokens are

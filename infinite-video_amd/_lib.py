@@ -108,6 +108,21 @@ class VqfVcWeights(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("reserved", C.c_int32), ("layers", C.POINTER(VqfVcLayer)), ("mistral_proj", Linear)]
 
 
+class VqfVisionLn(C.Structure):
+    """infv_vqf_vision_ln: the vision LayerNorm in front of the Q-former (gamma NULL: off)."""
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float)]
+
+
+class VqfVcEmb(C.Structure):
+    """infv_vqf_vc_emb: the embedding layer of the VideoChat2 Q-former (word NULL: off)."""
+    _fields_ = [("word", C.c_void_p), ("pos", C.c_void_p), ("ln", LayerNorm), ("vocab", C.c_int32), ("max_pos", C.c_int32),
+                ("query_tokens", C.c_void_p)]
+
+
+class VqfVcFront(C.Structure):
+    _fields_ = [("vision_ln", VqfVisionLn), ("emb", VqfVcEmb), ("input_ids", C.c_void_p), ("reserved", C.c_int32)]
+
+
 VC_MAX_LAYERS = 24
 VC_MAX_TOKENS = 608
 
@@ -202,6 +217,12 @@ _SIGNATURES = {
     "infv_vqf_vc_encode_streams_tok": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                  C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(VqfVcWeights), C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infv_vqf_vc_encode_img": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(VqfVcWeights), C.POINTER(VqfVcFront), C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infv_vqf_layernorm_tokens": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                            C.c_void_p]),
+    "infv_vqf_vc_embed": (C.c_int, [C.c_void_p, C.POINTER(VqfVcFront), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infv_vqf_token_pass": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infv_vqf_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -23,6 +23,62 @@ constexpr int kArriveShift = 54;                                   // masses < 2
 constexpr unsigned long long kMassMask = (1ull << kArriveShift) - 1;
 __device__ inline double mass_of(unsigned long long word) { return (double)(word & kMassMask) * (1.0 / kMassScale); }
 
+// Tokens as the producer stores them: fp32 (the reference's layout), or fp16 / bf16 (half the HBM bytes of the only heavy
+// stream of the path; every fp16 and every bf16 value is exact in fp32, the sum runs in fp32 in the same order).
+typedef unsigned int uintx4_t __attribute__((ext_vector_type(4)));
+struct TokF32 {
+    typedef floatx4 vec;                               // 4 columns per lane
+    static __device__ inline floatx4 widen(floatx4 v) { return v; }
+    // streaming (nt) buffer load: scalar resource + scalar row offset + one lane offset, no 64-bit address per load in flight
+    static __device__ inline floatx4 load_nt(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+        const uintx4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 2 /* nt */);
+        floatx4 r;
+        r.x = __uint_as_float(v.x); r.y = __uint_as_float(v.y); r.z = __uint_as_float(v.z); r.w = __uint_as_float(v.w);
+        return r;
+    }
+};
+typedef unsigned int uintx2 __attribute__((ext_vector_type(2)));
+struct TokBF16 {
+    typedef uintx2 vec;                                // 4 bf16 columns per lane (8 bytes)
+    static __device__ inline floatx4 widen(uintx2 v) {
+        floatx4 r;
+        r.x = __uint_as_float(v.x << 16); r.y = __uint_as_float(v.x & 0xffff0000u);
+        r.z = __uint_as_float(v.y << 16); r.w = __uint_as_float(v.y & 0xffff0000u);
+        return r;
+    }
+    static __device__ inline uintx2 load_nt(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+        return __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 2 /* nt */);
+    }
+};
+
+// fp16 as the reference's producer holds it (.half() ViT, fp16 autocast): widened by the hardware conversion (v_cvt_f32_f16 is
+// exact for every fp16 value, subnormals included -- they are normal numbers in fp32), so everything behind widen() sees the
+// values an fp32 copy of the tokens would hold.
+typedef _Float16 halfx4 __attribute__((ext_vector_type(4)));
+struct TokF16 {
+    typedef uintx2 vec;                                // 4 fp16 columns per lane (8 bytes)
+    // (the whole 8 bytes are reinterpreted at once: __builtin_bit_cast of ONE component of the vector, `v.y`, reads the vector's
+    //  first dword with this compiler -- caught by tests/test_f16_tokens_ltm_gpu.py)
+    static __device__ inline floatx4 widen(uintx2 v) { return __builtin_convertvector(__builtin_bit_cast(halfx4, v), floatx4); }
+    static __device__ inline uintx2 load_nt(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+        return __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 2 /* nt */);
+    }
+};
+
+// ---- vision LayerNorm of frame tokens (nn.LayerNorm(width, eps) in front of the Q-former, videochat2_it_mistral.py:195) ----
+// y = fma((x - mu) * r, gamma[c], beta[c]) of one token value: (mu, r) = the token row's mean and 1 / sqrt(var + eps), as
+// token_ln_stats_kernel writes them.  THE definition: ln_tokens_kernel (the fp32 copy), the tile pass and the pooling that apply the
+// LayerNorm on load all call it, with explicit roundings so that no consumer contracts it differently -- they agree bit for bit.
+__device__ __forceinline__ float token_ln(float x, float mu, float r, float g, float b) {
+    return __fmaf_rn(__fmul_rn(__fsub_rn(x, mu), r), g, b);
+}
+__device__ __forceinline__ floatx4 token_ln4(floatx4 x, float2 st, floatx4 g, floatx4 b) {
+    floatx4 y;
+    y.x = token_ln(x.x, st.x, st.y, g.x, b.x); y.y = token_ln(x.y, st.x, st.y, g.y, b.y);
+    y.z = token_ln(x.z, st.x, st.y, g.z, b.z); y.w = token_ln(x.w, st.x, st.y, g.w, b.w);
+    return y;
+}
+
 // Sum over the NT threads of the workgroup (NT/64 waves); every thread gets the result.
 template <int NT>
 __device__ inline double block_sum(double v, double* scratch /*LDS[NT/64]*/) {

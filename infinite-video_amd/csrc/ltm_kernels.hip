@@ -27,48 +27,7 @@ namespace infv {
 //    1 KiB contiguous; P loads per lane are independent, so the whole 32 KiB of a unit is in
 //    flight at once.  This is the only HBM-heavy stage of the path (25.2 MB per chunk).
 // ======================================================================================
-// Tokens as the producer stores them: fp32 (the reference's layout), or fp16 / bf16 (half the HBM bytes of the only heavy
-// stream of the path; every fp16 and every bf16 value is exact in fp32, the sum runs in fp32 in the same order).
-typedef unsigned int uintx4_t __attribute__((ext_vector_type(4)));
-struct TokF32 {
-    typedef floatx4 vec;                               // 4 columns per lane
-    static __device__ inline floatx4 widen(floatx4 v) { return v; }
-    // streaming (nt) buffer load: scalar resource + scalar row offset + one lane offset, no 64-bit address per load in flight
-    static __device__ inline floatx4 load_nt(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
-        const uintx4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 2 /* nt */);
-        floatx4 r;
-        r.x = __uint_as_float(v.x); r.y = __uint_as_float(v.y); r.z = __uint_as_float(v.z); r.w = __uint_as_float(v.w);
-        return r;
-    }
-};
-typedef unsigned int uintx2 __attribute__((ext_vector_type(2)));
-struct TokBF16 {
-    typedef uintx2 vec;                                // 4 bf16 columns per lane (8 bytes)
-    static __device__ inline floatx4 widen(uintx2 v) {
-        floatx4 r;
-        r.x = __uint_as_float(v.x << 16); r.y = __uint_as_float(v.x & 0xffff0000u);
-        r.z = __uint_as_float(v.y << 16); r.w = __uint_as_float(v.y & 0xffff0000u);
-        return r;
-    }
-    static __device__ inline uintx2 load_nt(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
-        return __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 2 /* nt */);
-    }
-};
-
-// fp16 as the reference's producer holds it (.half() ViT, fp16 autocast): widened by the hardware conversion (v_cvt_f32_f16 is
-// exact for every fp16 value, subnormals included -- they are normal numbers in fp32), so everything behind widen() sees the
-// values an fp32 copy of the tokens would hold.
-typedef _Float16 halfx4 __attribute__((ext_vector_type(4)));
-struct TokF16 {
-    typedef uintx2 vec;                                // 4 fp16 columns per lane (8 bytes)
-    // (the whole 8 bytes are reinterpreted at once: __builtin_bit_cast of ONE component of the vector, `v.y`, reads the vector's
-    //  first dword with this compiler -- caught by tests/test_f16_tokens_ltm_gpu.py)
-    static __device__ inline floatx4 widen(uintx2 v) { return __builtin_convertvector(__builtin_bit_cast(halfx4, v), floatx4); }
-    static __device__ inline uintx2 load_nt(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
-        return __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 2 /* nt */);
-    }
-};
-
+// (the token types TokF32 / TokBF16 / TokF16 -- how a kernel loads and widens frame tokens -- live in ltm_device.h)
 // tok -> the token type: `f` is a generic callable taking a value of TokF32 / TokBF16 / TokF16
 template <class F>
 static hipError_t with_token_type(infv_token_dtype tok, F f) {
@@ -159,6 +118,70 @@ static hipError_t launch_pool_t(const void* k, float* kbar, int64_t n_frames, in
     } else {
         INFV_LAUNCH((PoolFramesFn<16, 256, Tok>::get()), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, stream, k, kbar,
                            n_units, P, d4, slices);
+    }
+    return hipGetLastError();
+}
+
+// The frame means of LAYER-NORMED tokens without an fp32 copy of them: pool_frames_body with y = token_ln(x) applied on load
+// (ltm_device.h; stats [n_frames * P] = (mean, 1 / sqrt(var + eps)) per token row, gamma / beta [d]).  The P values of a column are
+// added in token order and divided by P as above, so the means are the bits of launch_pool on the fp32 tensor ln_tokens_kernel
+// writes.  One wave per (frame, 256-column slice), 8 token rows of loads in flight.
+template <class Tok>
+__device__ __forceinline__ void pool_frames_ln_body(const void* __restrict__ k_, const float2* __restrict__ stats,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    float* __restrict__ kbar, long n_units, int P, int d4, int slices) {
+    typedef typename Tok::vec tvec;
+    constexpr int UNROLL = 8;
+    const int lane = threadIdx.x & 63;
+    for (long unit = (long)blockIdx.x * 4 + (threadIdx.x >> 6); unit < n_units; unit += (long)gridDim.x * 4) {
+        const long frame = unit / slices;
+        const int c4 = (int)(unit - frame * slices) * 64 + lane;
+        if (c4 >= d4) continue;
+        const tvec* src = reinterpret_cast<const tvec*>(k_) + frame * (long)P * d4 + c4;
+        const float2* st = stats + frame * (long)P;
+        const floatx4 g = reinterpret_cast<const floatx4*>(gamma)[c4], b = reinterpret_cast<const floatx4*>(beta)[c4];
+        floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+        int p = 0;
+        for (; p + UNROLL <= P; p += UNROLL) {
+            tvec v[UNROLL]; float2 s[UNROLL];
+#pragma unroll
+            for (int i = 0; i < UNROLL; ++i) { v[i] = __builtin_nontemporal_load(src + (long)(p + i) * d4); s[i] = st[p + i]; }
+#pragma unroll
+            for (int i = 0; i < UNROLL; ++i) acc += token_ln4(Tok::widen(v[i]), s[i], g, b);
+        }
+        for (; p < P; ++p) acc += token_ln4(Tok::widen(__builtin_nontemporal_load(src + (long)p * d4)), st[p], g, b);
+        const float fp = (float)P;
+        acc.x /= fp; acc.y /= fp; acc.z /= fp; acc.w /= fp;
+        __builtin_nontemporal_store(acc, reinterpret_cast<floatx4*>(kbar) + frame * d4 + c4);
+    }
+}
+// (named so that neither contains a fragment the kernel census counts, as pool_frames_f16_kernel is)
+template <class Tok>
+__global__ __launch_bounds__(256) void pool_frames_ln_kernel(const void* __restrict__ k_, const float2* __restrict__ stats,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             float* __restrict__ kbar, long n_units, int P, int d4, int slices) {
+    pool_frames_ln_body<Tok>(k_, stats, gamma, beta, kbar, n_units, P, d4, slices);
+}
+__global__ __launch_bounds__(256) void pool_frames_ln_f16_kernel(const void* __restrict__ k_, const float2* __restrict__ stats,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 float* __restrict__ kbar, long n_units, int P, int d4, int slices) {
+    pool_frames_ln_body<TokF16>(k_, stats, gamma, beta, kbar, n_units, P, d4, slices);
+}
+
+hipError_t launch_pool_ln(const void* k, infv_token_dtype tok, const void* stats, const float* gamma, const float* beta, float* kbar,
+                          int64_t n_frames, int P, int d, hipStream_t stream) {
+    const int d4 = d / 4;
+    const int slices = (d4 + 63) / 64;
+    const long n_units = (long)n_frames * slices;
+    if (n_units == 0) return hipSuccess;
+    if (d % 4 || P < 1) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n_units + 3) / 4));
+    const float2* st = static_cast<const float2*>(stats);
+    switch (tok) {
+        case INFV_TOKENS_F32: INFV_LAUNCH(pool_frames_ln_kernel<TokF32>, grid, dim3(256), 0, stream, k, st, gamma, beta, kbar, n_units, P, d4, slices); break;
+        case INFV_TOKENS_BF16: INFV_LAUNCH(pool_frames_ln_kernel<TokBF16>, grid, dim3(256), 0, stream, k, st, gamma, beta, kbar, n_units, P, d4, slices); break;
+        case INFV_TOKENS_F16: INFV_LAUNCH(pool_frames_ln_f16_kernel, grid, dim3(256), 0, stream, k, st, gamma, beta, kbar, n_units, P, d4, slices); break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

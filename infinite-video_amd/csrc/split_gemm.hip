@@ -1094,6 +1094,184 @@ hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream
 }
 
 // ------------------------------------------------------------------------------------------------------
+// The vision LayerNorm of the frame tokens (videochat2_it_mistral.py:195: nn.LayerNorm(width, eps = 1e-12) between the vision
+// encoder's fp16 output and the Q-former), applied while the tokens are read at their own dtype -- no fp32 copy of them.
+//   token_ln_stats_kernel   (mean, 1 / sqrt(var + eps)) per token row, 8 bytes per token
+//   ln_tokens_kernel        y = token_ln(x) as an fp32 tensor: the reference form of the bits, and the fallback where the split path
+//                           does not apply (as upcast_f16_kernel / upcast_bf16_kernel are for plain tokens)
+//   split_transpose_ln_kernel   split_transpose_kernel's body over y computed on load (the pooling form is in ltm_kernels.hip)
+// Every consumer calls token_ln() of ltm_device.h on values widened exactly, so all of them see the bits ln_tokens_kernel writes.
+// ------------------------------------------------------------------------------------------------------
+// One wave per token row: the row is read once into registers (NV float4 per lane, lanes beyond the row idle), the mean is a
+// fixed-order reduction (per lane in column order, then an xor butterfly over the wave) divided by d, the variance a second
+// reduction of (x - mean)^2 from the registers (two-pass, biased, as nn.LayerNorm).  No atomics; the order does not depend on the grid.
+template <class Tok, int NV>
+__global__ __launch_bounds__(256) void token_ln_stats_kernel(const void* __restrict__ F, long n_rows, int d4, float eps,
+                                                             float2* __restrict__ stats) {
+    typedef typename Tok::vec tvec;
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const tvec* src = reinterpret_cast<const tvec*>(F) + row * d4;
+    floatx4 x[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        x[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+        if (lane + 64 * i < d4) x[i] = Tok::widen(src[lane + 64 * i]);
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) s += (x[i].x + x[i].y) + (x[i].z + x[i].w);      // (idle slots hold zeros)
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const float mu = s / (float)(4 * d4);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        if (lane + 64 * i < d4) {
+            const floatx4 dx = x[i] - mu;
+            q += (dx.x * dx.x + dx.y * dx.y) + (dx.z * dx.z + dx.w * dx.w);
+        }
+    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
+    const float var = q / (float)(4 * d4);
+    if (lane == 0) stats[row] = make_float2(mu, 1.0f / sqrtf(var + eps));
+}
+
+template <class Tok>
+static hipError_t launch_token_ln_stats_t(const void* F, long n_rows, int d, float eps, float2* stats, hipStream_t stream) {
+    const int d4 = d / 4;
+    const dim3 grid((unsigned)((n_rows + 3) / 4));
+    if (d4 <= 64) INFV_LAUNCH((token_ln_stats_kernel<Tok, 1>), grid, dim3(256), 0, stream, F, n_rows, d4, eps, stats);
+    else if (d4 <= 256) INFV_LAUNCH((token_ln_stats_kernel<Tok, 4>), grid, dim3(256), 0, stream, F, n_rows, d4, eps, stats);
+    else INFV_LAUNCH((token_ln_stats_kernel<Tok, 16>), grid, dim3(256), 0, stream, F, n_rows, d4, eps, stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_token_ln_stats(const void* F, infv_token_dtype tok, long n_rows, int d, float eps, void* stats, hipStream_t stream) {
+    if (n_rows <= 0) return hipSuccess;
+    if (d < 64 || d % 64 || d > kTokenLnMaxWidth || (n_rows + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
+    float2* st = static_cast<float2*>(stats);
+    switch (tok) {
+        case INFV_TOKENS_F32: return launch_token_ln_stats_t<TokF32>(F, n_rows, d, eps, st, stream);
+        case INFV_TOKENS_BF16: return launch_token_ln_stats_t<TokBF16>(F, n_rows, d, eps, st, stream);
+        case INFV_TOKENS_F16: return launch_token_ln_stats_t<TokF16>(F, n_rows, d, eps, st, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <class Tok>
+__global__ __launch_bounds__(256) void ln_tokens_kernel(const void* __restrict__ F, long n_vec, int d4, const float2* __restrict__ stats,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                        float* __restrict__ y) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_vec) return;
+    const long row = i / d4;
+    const int c4 = (int)(i - row * d4);
+    const floatx4 x = Tok::widen(reinterpret_cast<const typename Tok::vec*>(F)[i]);
+    reinterpret_cast<floatx4*>(y)[i] = token_ln4(x, stats[row], reinterpret_cast<const floatx4*>(gamma)[c4],
+                                                 reinterpret_cast<const floatx4*>(beta)[c4]);
+}
+
+hipError_t launch_ln_tokens(const void* F, infv_token_dtype tok, long n_rows, int d, const void* stats, const float* gamma, const float* beta,
+                            float* y, hipStream_t stream) {
+    if (n_rows <= 0) return hipSuccess;
+    if (d < 64 || d % 64) return hipErrorInvalidValue;
+    const int d4 = d / 4;
+    const long step = 0x7fffffffL * 256 / d4;           // rows per launch (grid.x limit)
+    const float2* st = static_cast<const float2*>(stats);
+    for (long r0 = 0; r0 < n_rows; r0 += step) {
+        const long m = n_rows - r0 < step ? n_rows - r0 : step;
+        const long n_vec = m * d4;
+        const dim3 grid((unsigned)((n_vec + 255) / 256));
+        const void* src = static_cast<const char*>(F) + r0 * d * (tok == INFV_TOKENS_F32 ? 4 : 2);
+        float* dst = y + r0 * d;
+        switch (tok) {
+            case INFV_TOKENS_F32: INFV_LAUNCH(ln_tokens_kernel<TokF32>, grid, dim3(256), 0, stream, src, n_vec, d4, st + r0, gamma, beta, dst); break;
+            case INFV_TOKENS_BF16: INFV_LAUNCH(ln_tokens_kernel<TokBF16>, grid, dim3(256), 0, stream, src, n_vec, d4, st + r0, gamma, beta, dst); break;
+            case INFV_TOKENS_F16: INFV_LAUNCH(ln_tokens_kernel<TokF16>, grid, dim3(256), 0, stream, src, n_vec, d4, st + r0, gamma, beta, dst); break;
+            default: return hipErrorInvalidValue;
+        }
+    }
+    return hipGetLastError();
+}
+
+// split_transpose_kernel over y = token_ln(F): F [n][d] of the token type is read once (4 columns per thread), normalised on load
+// into the 64 x 64 fp32 tile (65-word pitch) and from there everything is the fp32 pass's -- F_hi / F_lo, FT_hi / FT_lo and, with
+// kbar, the frame means in token order.  A normalised value is a general fp32 number, so every token type writes all four planes.
+// stats [chunks * n] addresses the launch's first chunk.
+template <class Tok>
+__global__ __launch_bounds__(256) void split_transpose_ln_kernel(const void* __restrict__ F, int n, int d, const float2* __restrict__ stats,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 __bf16* __restrict__ Fh, __bf16* __restrict__ Fl,
+                                                                 __bf16* __restrict__ Th, __bf16* __restrict__ Tl,
+                                                                 float* __restrict__ kbar, int P) {
+    __shared__ float tile[64][65];
+    typedef typename Tok::vec tvec;
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const long cb = (long)blockIdx.z * n * d;
+    const tvec* src = reinterpret_cast<const tvec*>(F);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int e = tid + 256 * p;                 // 1024 groups of 4 columns
+        const int r = e >> 4, c4 = (e & 15) * 4;
+        floatx4 v = {0.f, 0.f, 0.f, 0.f};
+        if (r0 + r < n)
+            v = token_ln4(Tok::widen(src[(cb + (long)(r0 + r) * d + c0 + c4) >> 2]), stats[(long)blockIdx.z * n + r0 + r],
+                          *reinterpret_cast<const floatx4*>(gamma + c0 + c4), *reinterpret_cast<const floatx4*>(beta + c0 + c4));
+        __bf16 h[4], l[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { split2(v[k], h[k], l[k]); tile[r][c4 + k] = v[k]; }
+        if (r0 + r < n) {
+            const long o = cb + (long)(r0 + r) * d + c0 + c4;
+            *reinterpret_cast<uint2*>(Fh + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
+            *reinterpret_cast<uint2*>(Fl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int e = tid + 256 * p;
+        const int c = e >> 4, r4 = (e & 15) * 4;
+        if (r0 + r4 < n) {                           // n % 4 == 0 (multiple of 32)
+            __bf16 h[4], l[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) split2(tile[r4 + k][c], h[k], l[k]);
+            const long o = cb + (long)(c0 + c) * n + r0 + r4;
+            *reinterpret_cast<uint2*>(Th + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
+            *reinterpret_cast<uint2*>(Tl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
+        }
+    }
+    if (kbar) {
+        const int fpt = 64 / P;                      // frames per tile
+        for (int e = tid; e < fpt * 64; e += 256) {
+            const int f = e >> 6, c = e & 63;
+            if (r0 + (f + 1) * P <= n) {
+                float acc = 0.f;
+                for (int p = 0; p < P; ++p) acc += tile[f * P + p][c];
+                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
+            }
+        }
+    }
+}
+
+hipError_t launch_token_pass_ln(const void* F, infv_token_dtype tok, int nb, int n, int d, const void* stats, const float* gamma,
+                                const float* beta, void* Fh_, void* Fl_, void* Th_, void* Tl_, hipStream_t stream, float* kbar, int P) {
+    if (nb <= 0) return hipSuccess;
+    if (n % 32 || d % 64 || nb > 32768) return hipErrorInvalidValue;
+    if (kbar && (!token_pass_gives_means(P) || n % P)) return hipErrorInvalidValue;
+    const dim3 grid((n + 63) / 64, d / 64, nb);
+    const float2* st = static_cast<const float2*>(stats);
+    __bf16 *Fh = static_cast<__bf16*>(Fh_), *Fl = static_cast<__bf16*>(Fl_), *Th = static_cast<__bf16*>(Th_), *Tl = static_cast<__bf16*>(Tl_);
+    switch (tok) {
+        case INFV_TOKENS_F32: INFV_LAUNCH(split_transpose_ln_kernel<TokF32>, grid, dim3(256), 0, stream, F, n, d, st, gamma, beta, Fh, Fl, Th, Tl, kbar, P); break;
+        case INFV_TOKENS_BF16: INFV_LAUNCH(split_transpose_ln_kernel<TokBF16>, grid, dim3(256), 0, stream, F, n, d, st, gamma, beta, Fh, Fl, Th, Tl, kbar, P); break;
+        case INFV_TOKENS_F16: INFV_LAUNCH(split_transpose_ln_kernel<TokF16>, grid, dim3(256), 0, stream, F, n, d, st, gamma, beta, Fh, Fl, Th, Tl, kbar, P); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Row softmax of fp32 scores [n_rows][len] (leading dimension ld), written as split bf16 P_hi / P_lo (ld_out)
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void softmax_rows_split_kernel(const float* __restrict__ S, int len, long ld,

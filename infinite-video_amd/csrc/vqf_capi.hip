@@ -2,6 +2,7 @@
 #include "../../include/infv_vqf.h"
 #include "capi_common.h"
 #include <algorithm>
+#include <mutex>
 #include <vector>
 #include "vqf_internal.h"
 
@@ -31,12 +32,21 @@ struct infv_vqf_s {
     DeviceBuf vA, v1, v2, vxq, valong, vshort, vmerged, vqkv, vsa, vinter, vu, vkbar, v_h1s, v_xqs;
     DeviceBuf tA, t1, tqkv, tsa, tinter;                // packed text rows of the VideoChat2 path (infv_vqf_vc_encode_videos)
     DeviceBuf smap;                                     // infv_vqf_vc_encode_streams: source chunk of every stream-chunk (int32; grown, never shrunk)
+    // infv_vqf_vc_encode_img: (mean, 1 / sqrt(var + eps)) of every distinct token row; the embedding layer's output rows; the row
+    // table of the embedding kernel on the device and its pinned staging buffer (reused once ev_ids, recorded behind the copy, has passed)
+    DeviceBuf lnstats, embrows, ids_dev;
+    int32_t* ids_pin = nullptr;
+    size_t ids_pin_n = 0;
+    hipEvent_t ev_ids = nullptr;
+    bool ids_in_flight = false;
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
     ~infv_vqf_s() {
         if (side) (void)hipStreamSynchronize(side);           // (a stream of the process-wide set: not destroyed here)
         if (ev_main) (void)hipEventDestroy(ev_main);
         if (ev_side) (void)hipEventDestroy(ev_side);
+        if (ev_ids) { (void)hipEventSynchronize(ev_ids); (void)hipEventDestroy(ev_ids); }
+        if (ids_pin) (void)hipHostFree(ids_pin);
     }
 };
 
@@ -131,17 +141,22 @@ static int upcast_tokens(infv_vqf_s* h, const void* frames, infv_token_dtype tok
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The vision LayerNorm applied while the tokens are read (infv_vqf_vc_encode_img): stats [rows][2] = (mean, 1 / sqrt(var + eps))
+// of the token rows of the buffer the call addresses (row 0 = its first token), gamma / beta [enc_width] on the device
+struct TokLn { const float* stats; const float* gamma; const float* beta; };
+
 // dst0 / cap: the planes of these nb chunks go to chunks [dst0, dst0 + nb) of buffers reserved for cap chunks (0, 0: [0, nb) of nb);
 // *ref always addresses chunk 0 of the buffers
 static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype tok, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
-                         hipStream_t stream, int dst0 = 0, int cap = 0) {
+                         hipStream_t stream, int dst0 = 0, int cap = 0,
+                         const TokLn* ln = nullptr /* the planes (and means) of token_ln(frames); ln->stats addresses frames_' first token */) {
     const int d = h->cfg.enc_width;
     const size_t szF = (size_t)(cap > dst0 + nb ? cap : dst0 + nb) * n_tokens * d * 2;
     const size_t d0 = (size_t)dst0 * n_tokens * d;
     DeviceBuf& Fh = whole ? h->wFh : h->sFh; DeviceBuf& Fl = whole ? h->wFl : h->sFl;
     DeviceBuf& Th = whole ? h->wTh : h->sTh; DeviceBuf& Tl = whole ? h->wTl : h->sTl;
     const int P = h->cfg.tokens_per_frame;
-    if (tok == INFV_TOKENS_BF16) {                           // read in place: only the transposed copy is written
+    if (tok == INFV_TOKENS_BF16 && !ln) {                    // read in place: only the transposed copy is written
         if (szF > Th.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(Th.reserve(szF)); }
         const __bf16* fb = static_cast<const __bf16*>(frames_);
         for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
@@ -161,6 +176,11 @@ static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype to
         const int n = nb - c0 < 32768 ? nb - c0 : 32768;
         const size_t o = (size_t)c0 * n_tokens * d;
         float* kb = kbar ? kbar + (size_t)c0 * (n_tokens / P) * d : nullptr;
+        if (ln) {                                              // a normalised value is a general fp32 number: four planes for every token type
+            HIP_TRY(launch_token_pass_ln(tok_at(frames_, tok, (long)o), tok, n, n_tokens, d, ln->stats + 2 * (size_t)c0 * n_tokens, ln->gamma, ln->beta,
+                                         Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o, Th.as<__bf16>() + d0 + o, Tl.as<__bf16>() + d0 + o, stream, kb, P));
+            continue;
+        }
         HIP_TRY(launch_token_pass(tok_at(frames_, tok, (long)o), tok, n, n_tokens, d, Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o,
                                   Th.as<__bf16>() + d0 + o, Tl.as<__bf16>() + d0 + o, stream, kb, P));
     }
@@ -293,6 +313,58 @@ int ensure_streams(infv_vqf_s* h) {
     if (int rc = shared_worker_stream(&h->side)) return rc;
     HIP_TRY(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_side, hipEventDisableTiming));
+    return INFV_OK;
+}
+
+// The embedding layer in front of the VideoChat2 encoder (infv_vqf_vc_front.emb): everything a caller can get wrong, checked on the
+// host before any launch or memory change -- no id can index outside its table on the device.
+int check_front_emb(const char* name, const infv_vqf_vc_front* f, int V, const int32_t* text_len) {
+    const auto& e = f->emb;
+    if (!e.pos || !e.ln.gamma || !e.ln.beta || !e.query_tokens || e.vocab < 1 || e.max_pos < 1)
+        return fail(INFV_ERR_INVALID, "%s: the embedding layer needs word, pos, ln, query_tokens, vocab >= 1 and max_pos >= 1", name);
+    long n_text = 0;
+    for (int v = 0; v < V; ++v) {
+        if (text_len[v] < 0) return fail(INFV_ERR_INVALID, "%s: text_len[%d] = %d is negative", name, v, text_len[v]);
+        if (text_len[v] > e.max_pos)
+            return fail(INFV_ERR_INVALID, "%s: video %d has %d text tokens, the position table has %d rows", name, v, text_len[v], e.max_pos);
+        n_text += text_len[v];
+    }
+    if (n_text > 0 && !f->input_ids) return fail(INFV_ERR_INVALID, "%s: text tokens without input_ids", name);
+    long i = 0;
+    for (int v = 0; v < V; ++v)
+        for (int t = 0; t < text_len[v]; ++t, ++i)
+            if (f->input_ids[i] < 0 || f->input_ids[i] >= e.vocab)
+                return fail(INFV_ERR_INVALID, "%s: video %d: input id %d at position %d is outside [0, %d)", name, v, f->input_ids[i], t, e.vocab);
+    return INFV_OK;
+}
+
+// Packed encoder input rows of V videos, video v's n_query + text_len[v] rows (query rows first), into out: the row table goes
+// through the handle's pinned buffer, whose reuse waits for the event recorded behind the previous call's copy.
+int run_embed(infv_vqf_s* h, const infv_vqf_vc_front* f, int V, const int32_t* text_len, float* out, hipStream_t stream) {
+    const int Q = h->cfg.n_query, Hd = h->cfg.hidden;
+    long n = 0;
+    for (int v = 0; v < V; ++v) n += Q + text_len[v];
+    if (n == 0) return INFV_OK;
+    if (n > 0x3fffffffL) return fail(INFV_ERR_UNSUPPORTED, "embedding layer: %ld rows in one call", n);
+    if (!h->ev_ids) HIP_TRY(hipEventCreateWithFlags(&h->ev_ids, hipEventDisableTiming));
+    if (h->ids_in_flight) { HIP_TRY(hipEventSynchronize(h->ev_ids)); h->ids_in_flight = false; }   // the last copy has read the buffer
+    if ((size_t)(2 * n) > h->ids_pin_n) {
+        if (h->ids_pin) { HIP_TRY(hipHostFree(h->ids_pin)); h->ids_pin = nullptr; h->ids_pin_n = 0; }
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->ids_pin), (size_t)(2 * n) * sizeof(int32_t), hipHostMallocDefault));
+        h->ids_pin_n = (size_t)(2 * n);
+    }
+    if ((size_t)(2 * n) * sizeof(int32_t) > h->ids_dev.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->ids_dev.reserve((size_t)(2 * n) * sizeof(int32_t))); }
+    int32_t* src = h->ids_pin; int32_t* pos = h->ids_pin + n;
+    long m = 0, i = 0;
+    for (int v = 0; v < V; ++v) {
+        for (int q = 0; q < Q; ++q, ++m) { src[m] = -(q + 1); pos[m] = 0; }
+        for (int t = 0; t < text_len[v]; ++t, ++m, ++i) { src[m] = f->input_ids[i]; pos[m] = t; }   // positions start at 0 at the first text token
+    }
+    HIP_TRY(hipMemcpyAsync(h->ids_dev.p, h->ids_pin, (size_t)(2 * n) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(h->ev_ids, stream));
+    h->ids_in_flight = true;
+    HIP_TRY(launch_qf_vc_embed(f->emb.word, f->emb.pos, f->emb.query_tokens, f->emb.ln.gamma, f->emb.ln.beta, h->cfg.ln_eps,
+                               h->ids_dev.as<int32_t>(), h->ids_dev.as<int32_t>() + n, (int)n, Hd, out, stream));
     return INFV_OK;
 }
 
@@ -827,13 +899,19 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
                    int32_t token_dtype /* < 0: the entry points without the argument -- fp32, refused unless the handle's setting is fp32 too */,
                    int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in,
                    const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
-                   void* stream_) {
+                   void* stream_, const infv_vqf_vc_front* front = nullptr /* infv_vqf_vc_encode_img: vision LayerNorm and / or embedding layer in front */) {
     // ---- validation before any device work or memory change ----
     if (!h || !cu || !w || !text_len || V < 0) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
+    if (front && front->reserved != 0) return fail(INFV_ERR_INVALID, "%s: front->reserved must be 0", name);
+    const bool vis_ln = front && front->vision_ln.gamma;       // the vision LayerNorm runs inside the token pass
+    const bool emb = front && front->emb.word;                 // the embedding layer writes the encoder input rows
+    if (vis_ln && !front->vision_ln.beta) return fail(INFV_ERR_INVALID, "%s: vision_ln.gamma without vision_ln.beta", name);
+    if (emb && hidden_in) return fail(INFV_ERR_INVALID, "%s: the embedding layer and hidden_in are both given (one of them writes the input rows)", name);
     const bool tok_arg = token_dtype >= 0;                     // the dtype is an argument of the call: the handle's setting is not read
     if (tok_arg && !token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "%s: unknown token dtype %d", name, token_dtype);
     infv_token_dtype tok = tok_arg ? static_cast<infv_token_dtype>(token_dtype) : INFV_TOKENS_F32;
     if (tok != INFV_TOKENS_F32 && frames && !aligned16(frames)) return fail(INFV_ERR_INVALID, "%s: fp16 / bf16 frames must be 16-byte aligned", name);
+    if (vis_ln && frames && !aligned16(frames)) return fail(INFV_ERR_INVALID, "%s: frames must be 16-byte aligned for the vision LayerNorm", name);
     if (V == 0) return INFV_OK;
     const infv_vqf_config& c = h->cfg;
     if (cu[0] != 0) return fail(INFV_ERR_INVALID, "%s: cu[0] = %d, not 0", name, cu[0]);
@@ -865,9 +943,14 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
             return fail(INFV_ERR_UNSUPPORTED, "%s: video %d attends over %d + %d tokens, at most %d are supported", name,
                         v, Q, text_len[v], INFV_VQF_VC_MAX_TOKENS);
     }
+    if (emb)
+        if (int rc = check_front_emb(name, front, V, text_len)) return rc;
     if (T < 1) return fail(INFV_ERR_INVALID, "%s: T must be >= 1", name);
     const int n_tokens = T * c.tokens_per_frame;
     if (n_tokens % 32) return fail(INFV_ERR_UNSUPPORTED, "%s: T * tokens_per_frame = %d is no multiple of 32", name, n_tokens);
+    if (vis_ln && (c.enc_width % 64 || c.enc_width > kTokenLnMaxWidth))
+        return fail(INFV_ERR_UNSUPPORTED, "%s: the vision LayerNorm needs enc_width = %d to be a multiple of 64, at most %d", name, c.enc_width,
+                    kTokenLnMaxWidth);
     if (!tok_arg && h->tok != INFV_TOKENS_F32)
         return fail(INFV_ERR_UNSUPPORTED, "%s: fp16 / bf16 frame tokens are not supported on this path (the _tok entry point takes them)", name);
     int n_cross = 0;
@@ -891,7 +974,7 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
             for (int i = 0; i < n_h; ++i) infv_ltm_reset(ltm[i]);
         return INFV_OK;
     }
-    if (!frames || !hidden_in) return fail(INFV_ERR_INVALID, "%s: null frames or hidden_in", name);
+    if (!frames || (!hidden_in && !emb)) return fail(INFV_ERR_INVALID, "%s: null frames or hidden_in", name);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (use_ltm)
         if (int rc = ensure_streams(h)) return rc;
@@ -912,6 +995,23 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     const long M = (long)C * Q, Tt = toff[C];
     const long chunk_k = (long)n_tokens * c.enc_width;
     const int Cf = streams ? fcu[F] : C;                       // distinct chunks of frame tokens
+    TokLn ln_{}; const TokLn* ln = nullptr;                    // the vision LayerNorm on load (split path), else nullptr
+    if (vis_ln && n_cross > 0) {
+        // (mean, 1 / sqrt(var + eps)) of every DISTINCT token row, once per call: 8 bytes per token
+        const size_t rows = (size_t)Cf * n_tokens;
+        if (rows * 2 * sizeof(float) > h->lnstats.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->lnstats.reserve(rows * 2 * sizeof(float))); }
+        HIP_TRY(launch_token_ln_stats(frames, tok, (long)rows, c.enc_width, front->vision_ln.eps, h->lnstats.p, stream));
+        if (split_path(h, n_tokens)) {
+            ln_ = TokLn{h->lnstats.as<float>(), front->vision_ln.gamma, front->vision_ln.beta};
+            ln = &ln_;
+        } else {                                               // the fp32 contractions from the normalised fp32 copy of the distinct chunks
+            const size_t elems = rows * c.enc_width;
+            if (elems * sizeof(float) > h->up.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->up.reserve(elems * sizeof(float))); }
+            HIP_TRY(launch_ln_tokens(frames, tok, (long)rows, c.enc_width, h->lnstats.p, front->vision_ln.gamma, front->vision_ln.beta,
+                                     h->up.as<float>(), stream));
+            frames = h->up.p; tok = INFV_TOKENS_F32;
+        }
+    }
     if (tok != INFV_TOKENS_F32 && n_cross > 0 && !split_path(h, n_tokens)) {   // today's fp32 kernels from an fp32 copy of the distinct chunks
         const float* f32 = nullptr;
         if (int rc = upcast_tokens(h, frames, tok, (size_t)Cf * chunk_k, &f32, stream)) return rc;
@@ -964,6 +1064,14 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     float* vshort = h->vshort.as<float>(); float* vmerged = h->vmerged.as<float>();
     float* tA = h->tA.as<float>(); float* t1 = h->t1.as<float>();
 
+    if (emb) {                                                 // the embedding layer writes the packed encoder input rows (Qformer.py:54-111)
+        long n_in = 0;
+        for (int v = 0; v < V; ++v) n_in += Q + text_len[v];
+        const size_t need = (size_t)n_in * Hd * sizeof(float);
+        if (need > h->embrows.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->embrows.reserve(need)); }
+        if (int rc = run_embed(h, front, V, text_len, h->embrows.as<float>(), stream)) return rc;
+        hidden_in = h->embrows.as<float>();
+    }
     // ---- every chunk starts from its video's encoder input rows
     HIP_TRY(launch_qf_copy_rows(hidden_in, vA, q_dst.data(), q_src.data(), q_n.data(), C, Hd, stream));
     if (Tt > 0) HIP_TRY(launch_qf_copy_rows(hidden_in, tA, toff.data(), t_src.data(), tl.data(), C, Hd, stream));
@@ -973,13 +1081,16 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     SplitRef wref{}; bool have_w = false, have_kbar = false;
     if (n_cross > 0) {
         // (streams: the distinct chunks only; bf16 tokens: only the transposed plane is written, as in infv_vqf_encode_video)
-        const double need_gb = (tok == INFV_TOKENS_BF16 ? 1.0 : 4.0) * (double)Cf * (double)chunk_k * 2.0 / 1e9;
+        const double need_gb = (tok == INFV_TOKENS_BF16 && !ln ? 1.0 : 4.0) * (double)Cf * (double)chunk_k * 2.0 / 1e9;   // (normalised tokens: four planes)
         if (h->fuse && split_path(h, n_tokens) && need_gb <= h->split_cache_gb) {
             have_kbar = use_ltm && token_pass_gives_means(c.tokens_per_frame);   // (where a frame divides the 64-token tile)
-            if (int rc = prepare_split(h, frames, tok, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
+            if (int rc = prepare_split(h, frames, tok, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream, 0, 0, ln)) return rc;
             have_w = true;
         }
-        if (use_ltm && !have_kbar) {
+        if (use_ltm && !have_kbar && ln) {                     // pooling with the LayerNorm on load: the means of the normalised tokens
+            HIP_TRY(launch_pool_ln(frames, tok, ln->stats, ln->gamma, ln->beta, h->vkbar.as<float>(), (int64_t)Cf * T, c.tokens_per_frame,
+                                   c.enc_width, stream));
+        } else if (use_ltm && !have_kbar) {
             if (int rc = infv_ltm_set_token_dtype(ltm[0], tok)) return rc;
             const int rc_pool = infv_ltm_pool(ltm[0], frames, (int64_t)Cf * T, h->vkbar.as<float>(), stream_);
             if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;   // (left on fp32, as before)
@@ -1000,6 +1111,10 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
                 const long o = (long)c0 * chunk_k;
                 *r = SplitRef{wref.Fh + o, wref.Fl ? wref.Fl + o : nullptr, wref.Th + o, wref.Tl ? wref.Tl + o : nullptr};
                 *pre = r;
+            } else if (ln) {                                   // the split per sub-batch short_attention would issue, with the LayerNorm on load
+                const TokLn lc{ln->stats + 2 * (size_t)c0 * n_tokens, ln->gamma, ln->beta};
+                if (int rc = prepare_split(h, *fr, tok, nb, n_tokens, nullptr, false, r, stream, 0, 0, &lc)) return rc;
+                *pre = r;
             }
             return INFV_OK;
         }
@@ -1008,11 +1123,13 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
         for (int b0 = 0; b0 < nb;) {
             int b1 = b0 + 1;
             while (b1 < nb && src_chunk[c0 + b1] == src_chunk[c0 + b1 - 1] + 1) ++b1;
+            TokLn lc{};
+            if (ln) lc = TokLn{ln->stats + 2 * (size_t)src_chunk[c0 + b0] * n_tokens, ln->gamma, ln->beta};
             if (int rc = prepare_split(h, tok_at(frames, tok, (long)src_chunk[c0 + b0] * chunk_k), tok, b1 - b0, n_tokens, nullptr, false, r,
-                                       stream, b0, nb)) return rc;
+                                       stream, b0, nb, ln ? &lc : nullptr)) return rc;
             b0 = b1;
         }
-        if (tok == INFV_TOKENS_BF16) {                         // the untransposed operand is the caller's buffer: read through the map,
+        if (tok == INFV_TOKENS_BF16 && !ln) {                         // the untransposed operand is the caller's buffer: read through the map,
             r->Fh = static_cast<const __bf16*>(frames);        // while the transposed plane just written holds the sub-batch in order
             *map = h->smap.as<int32_t>() + c0; *t_identity = true;
         }
@@ -1182,6 +1299,59 @@ int infv_vqf_vc_encode_streams_tok(infv_vqf_handle h, const infv_ltm_handle* ltm
     if (token_dtype < 0) return fail(INFV_ERR_INVALID, "vc_encode_streams_tok: unknown token dtype %d", token_dtype);
     return vc_impl("vc_encode_streams_tok", h, ltm, V, cu, frames, token_dtype, F, fcu, frame_src, T, w, hidden_in, text_len, u, new_video,
                    hidden_out, proj_out, proj_mean, stream_);
+}
+
+int infv_vqf_vc_encode_img(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames, int32_t token_dtype,
+                           int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w,
+                           const infv_vqf_vc_front* front, const float* hidden_in, const int32_t* text_len, const double* u, int32_t new_video,
+                           float* hidden_out, float* proj_out, float* proj_mean, void* stream_) {
+    if (token_dtype < 0) return fail(INFV_ERR_INVALID, "vc_encode_img: unknown token dtype %d", token_dtype);
+    if (frame_src && !fcu) return fail(INFV_ERR_INVALID, "vc_encode_img: bad arguments");
+    const bool streams = frame_src != nullptr;                 // NULL: videos (F and fcu are not read)
+    return vc_impl("vc_encode_img", h, ltm, V, cu, frames, token_dtype, streams ? F : 0, streams ? fcu : nullptr, frame_src, T, w, hidden_in,
+                   text_len, u, new_video, hidden_out, proj_out, proj_mean, stream_, front);
+}
+
+int infv_vqf_layernorm_tokens(const void* frames, int32_t token_dtype, int64_t n_rows, int32_t d, const float* gamma, const float* beta,
+                              float eps, float* out_f32, void* stream_) {
+    // ---- every refusal before any launch ----
+    if (!token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "layernorm_tokens: unknown token dtype %d", token_dtype);
+    if (!frames || !gamma || !beta || !out_f32 || n_rows < 0) return fail(INFV_ERR_INVALID, "layernorm_tokens: bad arguments");
+    if (d < 64 || d % 64) return fail(INFV_ERR_INVALID, "layernorm_tokens: d must be a positive multiple of 64");
+    if (d > kTokenLnMaxWidth) return fail(INFV_ERR_UNSUPPORTED, "layernorm_tokens: d = %d, at most %d is supported", d, kTokenLnMaxWidth);
+    if (!aligned16(frames) || !aligned16(out_f32) || !aligned16(gamma) || !aligned16(beta))
+        return fail(INFV_ERR_INVALID, "layernorm_tokens: frames, gamma, beta and out must be 16-byte aligned");
+    if (n_rows == 0) return INFV_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // the per-row statistics live in a process-wide buffer, grown on demand (the encoders keep theirs in the handle)
+    // (a call on another stream waits for the event recorded behind the last reader before it overwrites them)
+    static std::mutex mu;
+    static DeviceBuf* stats = new DeviceBuf();
+    static hipEvent_t last_read = nullptr;
+    std::lock_guard<std::mutex> lock(mu);
+    if ((size_t)n_rows * 2 * sizeof(float) > stats->bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(stats->reserve((size_t)n_rows * 2 * sizeof(float))); }
+    if (!last_read) HIP_TRY(hipEventCreateWithFlags(&last_read, hipEventDisableTiming));
+    else HIP_TRY(hipStreamWaitEvent(stream, last_read, 0));
+    const infv_token_dtype tok = static_cast<infv_token_dtype>(token_dtype);
+    HIP_TRY(launch_token_ln_stats(frames, tok, (long)n_rows, d, eps, stats->p, stream));
+    HIP_TRY(launch_ln_tokens(frames, tok, (long)n_rows, d, stats->p, gamma, beta, out_f32, stream));
+    HIP_TRY(hipEventRecord(last_read, stream));
+    return INFV_OK;
+}
+
+int infv_vqf_vc_embed(infv_vqf_handle h, const infv_vqf_vc_front* front, int32_t V, const int32_t* text_len, float* out_rows, void* stream_) {
+    // ---- every refusal before any launch or memory change ----
+    if (!h || !front || !text_len || V < 0) return fail(INFV_ERR_INVALID, "vc_embed: bad arguments");
+    if (front->reserved != 0) return fail(INFV_ERR_INVALID, "vc_embed: front->reserved must be 0");
+    if (!front->emb.word) return fail(INFV_ERR_INVALID, "vc_embed: no embedding tables (emb.word is NULL)");
+    if (int rc = check_front_emb("vc_embed", front, V, text_len)) return rc;
+    for (int v = 0; v < V; ++v)
+        if (h->cfg.n_query + text_len[v] > INFV_VQF_VC_MAX_TOKENS)
+            return fail(INFV_ERR_UNSUPPORTED, "vc_embed: video %d has %d + %d tokens, at most %d are supported", v, h->cfg.n_query, text_len[v],
+                        INFV_VQF_VC_MAX_TOKENS);
+    if (V == 0) return INFV_OK;
+    if (!out_rows) return fail(INFV_ERR_INVALID, "vc_embed: null out_rows");
+    return run_embed(h, front, V, text_len, out_rows, static_cast<hipStream_t>(stream_));
 }
 
 int infv_vqf_token_pass(const void* frames, int32_t token_dtype, int32_t nb, int32_t n_tokens, int32_t d, int32_t tokens_per_frame,

@@ -131,6 +131,24 @@ hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream
 bool token_pass_gives_means(int P);
 hipError_t launch_token_pass(const void* F, infv_token_dtype tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
                              hipStream_t stream, float* kbar, int P);
+// ---- vision LayerNorm of the frame tokens (videochat2_it_mistral.py:195), y = token_ln(x) of ltm_device.h ----
+constexpr int kTokenLnMaxWidth = 4096;   // a token row is held in one wave's registers: 16 float4 per lane
+// stats[row] = (mean, 1 / sqrt(var + eps)) of n_rows token rows of width d (d % 64 == 0, d <= kTokenLnMaxWidth); stats: float2
+hipError_t launch_token_ln_stats(const void* F, infv_token_dtype tok, long n_rows, int d, float eps, void* stats, hipStream_t stream);
+// y [n_rows][d] fp32 = token_ln(F): the reference form of the bits, and the operand of the fp32 contractions
+hipError_t launch_ln_tokens(const void* F, infv_token_dtype tok, long n_rows, int d, const void* stats, const float* gamma, const float* beta,
+                            float* y, hipStream_t stream);
+// launch_token_pass over y = token_ln(F) applied on load: all four planes for every token type, kbar as there
+hipError_t launch_token_pass_ln(const void* F, infv_token_dtype tok, int nb, int n, int d, const void* stats, const float* gamma,
+                                const float* beta, void* Fh, void* Fl, void* Th, void* Tl, hipStream_t stream, float* kbar, int P);
+// launch_pool (ltm_kernels.hip) over y = token_ln(k) applied on load: the bits of launch_pool on ln_tokens_kernel's tensor
+hipError_t launch_pool_ln(const void* k, infv_token_dtype tok, const void* stats, const float* gamma, const float* beta, float* kbar,
+                          int64_t n_frames, int P, int d, hipStream_t stream);
+// The VideoChat2 embedding layer (Qformer.py:54-111): out row m = LN(query_tokens[-src[m] - 1]) where src[m] < 0, else
+// LN(word[src[m]] + position[pos[m]]); src / pos: DEVICE int32 [n_rows], validated on the host; width <= 4096
+hipError_t launch_qf_vc_embed(const float* word, const float* position, const float* query_tokens, const float* gamma, const float* beta,
+                              float eps, const int32_t* src, const int32_t* pos, int n_rows, int width, float* out, hipStream_t stream);
+
 // softmax of fp32 score rows, written as bf16 hi/lo
 hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long ld, void* Ph, void* Pl, long ld_out, hipStream_t stream);
 

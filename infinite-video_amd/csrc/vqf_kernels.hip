@@ -386,6 +386,68 @@ hipError_t launch_qf_epilogue(const QfEpilogue& e, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------------------------------------------
+// The embedding layer of the VideoChat2 Q-former (Qformer.py:54-111): one workgroup per packed encoder input row.  Row m is
+// LN(query_tokens[q]) where src[m] = -(q + 1), else LN(word[src[m]] + position[pos[m]]) -- ONE LayerNorm over query and text rows
+// alike, with the row epilogue's arithmetic (qf_layernorm_row below is qf_epilogue_kernel's LayerNorm: fp64 block sums, two-pass
+// variance).  A row depends on its own table entries alone, so a video's rows are the same bits whatever else is in the call.
+// src / pos are validated on the host before they reach the device: no id indexes outside its table here.
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void qf_layernorm_row(float (&x)[kEpiMaxPerThread], const float (&gam)[kEpiMaxPerThread],
+                                                 const float (&bet)[kEpiMaxPerThread], int width, float eps, double* scratch) {
+    const int tid = threadIdx.x;
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < kEpiMaxPerThread; ++i) sum += (tid + 256 * i < width) ? (double)x[i] : 0.0;
+    const float mean = (float)(block_sum<256>(sum, scratch) / width);
+    double sq = 0.0;
+#pragma unroll
+    for (int i = 0; i < kEpiMaxPerThread; ++i) {
+        const float dlt = x[i] - mean;
+        sq += (tid + 256 * i < width) ? (double)dlt * dlt : 0.0;
+    }
+    const float var = (float)(block_sum<256>(sq, scratch) / width);
+    const float rstd = 1.0f / sqrtf(var + eps);
+#pragma unroll
+    for (int i = 0; i < kEpiMaxPerThread; ++i) x[i] = (x[i] - mean) * rstd * gam[i] + bet[i];
+}
+
+__global__ __launch_bounds__(256) void qf_vc_embed_kernel(const float* __restrict__ word, const float* __restrict__ position,
+                                                          const float* __restrict__ query_tokens, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, float eps, const int32_t* __restrict__ src,
+                                                          const int32_t* __restrict__ pos, int width, float* __restrict__ out) {
+    __shared__ double scratch[4];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const int s = src[m];
+    const float* a = s < 0 ? query_tokens + (long)(-s - 1) * width : word + (long)s * width;
+    const float* b = s < 0 ? nullptr : position + (long)pos[m] * width;
+    float x[kEpiMaxPerThread], gam[kEpiMaxPerThread], bet[kEpiMaxPerThread];
+#pragma unroll
+    for (int i = 0; i < kEpiMaxPerThread; ++i) {
+        const int c = tid + 256 * i;
+        x[i] = 0.f; gam[i] = 1.f; bet[i] = 0.f;
+        if (256 * i < width && c < width) {
+            x[i] = a[c];
+            if (b) x[i] += b[c];
+            gam[i] = gamma[c]; bet[i] = beta[c];
+        }
+    }
+    qf_layernorm_row(x, gam, bet, width, eps, scratch);
+#pragma unroll
+    for (int i = 0; i < kEpiMaxPerThread; ++i) {
+        const int c = tid + 256 * i;
+        if (c < width) out[(long)m * width + c] = x[i];
+    }
+}
+
+hipError_t launch_qf_vc_embed(const float* word, const float* position, const float* query_tokens, const float* gamma, const float* beta,
+                              float eps, const int32_t* src, const int32_t* pos, int n_rows, int width, float* out, hipStream_t stream) {
+    if (n_rows <= 0) return hipSuccess;
+    if (width < 1 || width > 256 * kEpiMaxPerThread) return hipErrorInvalidValue;
+    INFV_LAUNCH(qf_vc_embed_kernel, dim3(n_rows), dim3(256), 0, stream, word, position, query_tokens, gamma, beta, eps, src, pos, width, out);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Self-attention over the (<= 32) query tokens of one chunk, one workgroup per (head, chunk)   (Qformer.py:238-301)
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void qf_self_attention_kernel(const float* __restrict__ qkv, int Q, int H,

@@ -24,6 +24,11 @@ stock PyTorch-ROCm"):
 ``VideoChat2Encoder.encode_videos`` / ``encode_long_videos_vc`` are the batched counterparts for harnesses that walk many
 short videos: ONE C call (``infv_vqf_vc_encode_videos``) runs the whole encoder -- BERT scaffolding included -- layer-major
 over the packed chunks of every video, each video's six memories in its own :class:`VideoChat2Memory`.
+
+``VideoChat2Encoder.encode_img_videos`` starts two steps earlier in ``encode_img``: at the vision encoder's output before
+``vision_layernorm`` (videochat2_it_mistral.py:195), in its own dtype, and at the tokenizer's ids (:204-223, Qformer.py:54-111).
+``infv_vqf_vc_encode_img`` applies the LayerNorm while the tokens are read and runs the embedding layer on the device; the model
+carries ``vision_layernorm`` and ``qformer.bert.embeddings`` when built with ``vision_layernorm=True`` / ``vocab_size=...``.
 """
 from __future__ import annotations
 
@@ -138,10 +143,20 @@ class _Encoder(nn.Module):
         self.layer = nn.ModuleList([_Layer(cfg, i) for i in range(cfg.num_hidden_layers)])
 
 
+class _Embeddings(nn.Module):                          # Qformer.py:54-111 (parameters only: the forward is the HIP kernel)
+    def __init__(self, cfg):
+        super().__init__()
+        self.word_embeddings = nn.Embedding(cfg.vocab_size, cfg.hidden_size)
+        self.position_embeddings = nn.Embedding(cfg.max_position_embeddings, cfg.hidden_size)
+        self.LayerNorm = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_eps)
+
+
 class _Bert(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         self.config = cfg
+        if getattr(cfg, "vocab_size", None) is not None:      # opt-in: older state dicts carry no bert.embeddings.*
+            self.embeddings = _Embeddings(cfg)
         self.encoder = _Encoder(cfg)
 
 
@@ -164,10 +179,13 @@ class VideoChat2Qformer(nn.Module):
 
 def init_Qformer(num_query_token: int, vision_width: int, tau: float, alpha: float, sticky: bool, num_basis: int,
                  num_hidden_layers: int = 12, cross_attention_freq: int = 2, hidden_size: int = 768,
-                 intermediate_size: int = 3072, num_attention_heads: int = 12):
-    """Counterpart of ``Blip2Base.init_Qformer`` (blip2.py:47-77): (Q-former, query tokens).  The last three arguments
-    default to bert-base; tests build small shapes with them."""
-    cfg = _Cfg(encoder_width=vision_width, sticky=sticky, num_basis=num_basis, tau=tau, alpha=alpha,
+                 intermediate_size: int = 3072, num_attention_heads: int = 12, vocab_size: Optional[int] = None,
+                 max_position_embeddings: int = 512):
+    """Counterpart of ``Blip2Base.init_Qformer`` (blip2.py:47-77): (Q-former, query tokens).  The three arguments after
+    ``cross_attention_freq`` default to bert-base; tests build small shapes with them.  ``vocab_size`` creates
+    ``bert.embeddings`` (Qformer.py:54-111)."""
+    cfg = _Cfg(vocab_size=vocab_size, max_position_embeddings=max_position_embeddings,
+               encoder_width=vision_width, sticky=sticky, num_basis=num_basis, tau=tau, alpha=alpha,
                cross_attention_freq=cross_attention_freq, query_length=num_query_token,
                num_hidden_layers=num_hidden_layers, hidden_size=hidden_size, intermediate_size=intermediate_size,
                num_attention_heads=num_attention_heads)
@@ -232,12 +250,16 @@ class VideoChat2Encoder(nn.Module):
     def __init__(self, num_query_token: int = 32, extra_num_query_token: int = 64, vision_width: int = 1024,
                  llm_hidden: int = 4096, num_basis: int = 256, sticky: bool = True, tau: float = 0.75,
                  alpha: float = 0.75, num_hidden_layers: int = 12, cross_attention_freq: int = 2, hidden_size: int = 768,
-                 intermediate_size: int = 3072, num_attention_heads: int = 12, tokens_per_frame: Optional[int] = None):
+                 intermediate_size: int = 3072, num_attention_heads: int = 12, tokens_per_frame: Optional[int] = None,
+                 vocab_size: Optional[int] = None, max_position_embeddings: int = 512, vision_layernorm: bool = False):
         super().__init__()
         self.n_query = num_query_token + extra_num_query_token
         self.qformer, self.query_tokens = init_Qformer(self.n_query, vision_width, tau, alpha, sticky, num_basis,
                                                        num_hidden_layers, cross_attention_freq, hidden_size,
-                                                       intermediate_size, num_attention_heads)
+                                                       intermediate_size, num_attention_heads, vocab_size,
+                                                       max_position_embeddings)
+        if vision_layernorm:                              # blip2.py:88, applied at videochat2_it_mistral.py:195
+            self.vision_layernorm = nn.LayerNorm(vision_width, eps=1e-12)
         self.mistral_proj = nn.Linear(self.qformer.config.hidden_size, llm_hidden)
         self._vqf = None
         self._vqf_dev = None
@@ -259,9 +281,11 @@ class VideoChat2Encoder(nn.Module):
     # ------------------------------------------------------------------ weights
     def load_reference_state_dict(self, sd: dict, strict: bool = True):
         """``sd`` under the reference's names: ``bert.encoder.layer.*``, ``query_tokens`` (query + extra query tokens
-        concatenated, videochat2_it_mistral.py:199-203), ``mistral_proj.*``."""
+        concatenated, videochat2_it_mistral.py:199-203), ``mistral_proj.*``; for a model built with them also
+        ``bert.embeddings.*`` (its ``position_ids`` buffer is dropped) and ``vision_layernorm.*``."""
         t = lambda v: torch.as_tensor(v)
-        own = {"qformer." + k: t(v) for k, v in sd.items() if k.startswith("bert.")}
+        own = {"qformer." + k: t(v) for k, v in sd.items() if k.startswith("bert.") and k != "bert.embeddings.position_ids"}
+        own.update({k: t(v) for k, v in sd.items() if k.startswith("vision_layernorm.")})
         own["query_tokens"] = t(sd["query_tokens"])
         for k in ("mistral_proj.weight", "mistral_proj.bias"):
             own[k] = t(sd[k])
@@ -450,9 +474,139 @@ class VideoChat2Encoder(nn.Module):
         the stream ids ``encode_videos`` gives video id ``video_ids[v]`` (default: v)."""
         return self._vc_call("encode_streams", videos, frame_src, text_embeds, hidden_in, new_video, u, memories, video_ids, want_hidden)
 
-    def _vc_call(self, name, videos, frame_src, text_embeds, hidden_in, new_video, u, memories, video_ids, want_hidden):
-        """Body of :meth:`encode_videos` (``frame_src`` None: video v reads ``videos[v]``) and :meth:`encode_streams`.  Everything
-        a caller can get wrong on the host raises ValueError before any device call."""
+    def _check_input_ids(self, input_ids, V: int) -> List[List[int]]:
+        """Per video / stream the instruction's token ids as a list of ints; ValueError before any device call."""
+        emb = self.qformer.bert.embeddings
+        vocab, max_pos = emb.word_embeddings.num_embeddings, emb.position_embeddings.num_embeddings
+        if isinstance(input_ids, torch.Tensor) or input_ids is None:
+            input_ids = [input_ids] * V
+        input_ids = list(input_ids)
+        if len(input_ids) != V:
+            raise ValueError(f"{len(input_ids)} input_ids for {V} videos")
+        out = []
+        for v, ids in enumerate(input_ids):
+            if ids is None:
+                out.append([])
+                continue
+            ids = torch.as_tensor(ids)
+            if ids.dim() != 1 or ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
+                raise ValueError(f"input_ids[{v}] must be a 1-D integer tensor")
+            n = int(ids.numel())
+            if n > max_pos:
+                raise ValueError(f"input_ids[{v}] has {n} tokens, the position table has {max_pos} rows")
+            if n > MAX_TXT_LEN:
+                raise ValueError(f"video {v} has {n} text tokens, at most {MAX_TXT_LEN} are supported")
+            lst = [int(x) for x in ids.detach().cpu().tolist()]
+            for t_, x in enumerate(lst):
+                if not 0 <= x < vocab:
+                    raise ValueError(f"input_ids[{v}][{t_}] = {x} outside [0, {vocab})")
+            out.append(lst)
+        return out
+
+    def _front(self, device, vision: bool, ids: Optional[List[List[int]]]):
+        """(``infv_vqf_vc_front``, what it points to) with the vision LayerNorm and / or the embedding layer switched on."""
+        keep = []
+
+        def t(x):
+            y = _dev_f32(x, device)
+            keep.append(y)
+            return y.data_ptr()
+
+        vis = _lib.VqfVisionLn(None, None, 0.0)
+        if vision:
+            ln = self.vision_layernorm
+            vis = _lib.VqfVisionLn(t(ln.weight), t(ln.bias), float(ln.eps))
+        emb, ids_p = _lib.VqfVcEmb(None, None, _lib.LayerNorm(None, None), 0, 0, None), None
+        if ids is not None:
+            e = self.qformer.bert.embeddings
+            emb = _lib.VqfVcEmb(t(e.word_embeddings.weight), t(e.position_embeddings.weight),
+                                _lib.LayerNorm(t(e.LayerNorm.weight), t(e.LayerNorm.bias)), e.word_embeddings.num_embeddings,
+                                e.position_embeddings.num_embeddings, t(self.query_tokens[0]))
+            flat = [x for lst in ids for x in lst]
+            arr = (C.c_int32 * max(len(flat), 1))(*flat)
+            keep.append(arr)
+            ids_p = C.cast(arr, C.c_void_p)
+        return _lib.VqfVcFront(vis, emb, ids_p, 0), keep
+
+    def encode_img_videos(self, videos: Sequence[torch.Tensor], input_ids=None, frame_src: Optional[Sequence[int]] = None,
+                          hidden_in=None, new_video: bool = True, u: Optional[torch.Tensor] = None,
+                          memories: Optional[Sequence["VideoChat2Memory"]] = None, video_ids: Optional[Sequence[int]] = None,
+                          want_hidden: bool = False):
+        """``encode_img`` behind the vision encoder in ONE C call (``infv_vqf_vc_encode_img``): from the vision encoder's output
+        and the tokenizer's ids to ``inputs_mistral`` (videochat2_it_mistral.py:195, :204-223, :252).
+
+        ``videos``: the vision encoder's output blocks [C, T*P, width] BEFORE ``vision_layernorm``, all fp32, all fp16 or all
+        bf16, read in place (cloned only where a block is not contiguous or not 16-byte aligned); the LayerNorm runs inside the
+        token pass, no fp32 copy of the tokens is made.  ``frame_src``: None (video v reads ``videos[v]``) or the block of every
+        stream, as in :meth:`encode_streams`.  ``input_ids``: one 1-D integer tensor per video / stream (an entry may be None: no
+        instruction); the embedding layer (Qformer.py:54-111) runs on the device, over the query tokens too.  ``hidden_in``
+        instead of ``input_ids`` hands over ready encoder input rows as :meth:`encode_videos` takes them.  Everything else, and
+        the returned triple, is :meth:`encode_videos`'s.  The results are the bits of
+        ``encode_videos(vision_tokens_layernorm(videos), hidden_in=embed_instructions(input_ids))``.
+        Raises RuntimeError if the model was built without ``vision_layernorm=True``, or without ``vocab_size`` where the
+        embedding layer is needed; ValueError on bad ids (negative, >= vocab, more than ``max_position_embeddings``)."""
+        if not hasattr(self, "vision_layernorm"):
+            raise RuntimeError("encode_img_videos needs the vision LayerNorm: build the model with vision_layernorm=True")
+        if input_ids is not None and hidden_in is not None:
+            raise ValueError("input_ids and hidden_in are both given: one of them makes the encoder input rows")
+        if hidden_in is None and not hasattr(self.qformer.bert, "embeddings"):
+            raise RuntimeError("encode_img_videos needs the embedding layer (build the model with vocab_size=...) or hidden_in")
+        name = "encode_img_videos"
+        return self._vc_call(name, videos, frame_src, None, hidden_in, new_video, u, memories, video_ids, want_hidden,
+                             img=True, input_ids=input_ids)
+
+    def vision_tokens_layernorm(self, tokens: torch.Tensor) -> torch.Tensor:
+        """``vision_layernorm`` of [..., width] fp32 / fp16 / bf16 tokens as an fp32 tensor, by the kernels and the arithmetic of
+        :meth:`encode_img_videos` (``infv_vqf_layernorm_tokens``): the reference form of its bits."""
+        if not hasattr(self, "vision_layernorm"):
+            raise RuntimeError("vision_tokens_layernorm needs the vision LayerNorm: build the model with vision_layernorm=True")
+        if not tokens.is_cuda:
+            raise RuntimeError("the VideoChat2 binding runs on the HIP device only (no CPU fallback)")
+        ln = self.vision_layernorm
+        if tokens.size(-1) != ln.normalized_shape[0]:
+            raise ValueError(f"tokens must have width {ln.normalized_shape[0]}")
+        device = tokens.device
+        x = tokens.detach() if tokens.dtype in TOKEN_DTYPES else tokens.detach().float()
+        if not x.is_contiguous() or x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.contiguous_format)
+        g, b = _dev_f32(ln.weight, device), _dev_f32(ln.bias, device)
+        out = torch.empty(x.shape, device=device, dtype=torch.float32)
+        if x.numel() == 0:
+            return out
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().infv_vqf_layernorm_tokens(
+                C.c_void_p(x.data_ptr()), TOKEN_DTYPES[x.dtype], x.numel() // x.size(-1), x.size(-1), C.c_void_p(g.data_ptr()),
+                C.c_void_p(b.data_ptr()), float(ln.eps), C.c_void_p(out.data_ptr()),
+                C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+        return out
+
+    def embed_instructions(self, input_ids, device=None) -> List[torch.Tensor]:
+        """Per video the encoder input rows [n_query + n_text_v, hidden] the embedding layer gives (Qformer.py:54-111:
+        ``LayerNorm(cat(query_tokens, word(ids) + position))``), by ``infv_vqf_vc_embed``; ``input_ids``: a list with one 1-D
+        integer tensor (or None) per video."""
+        if not hasattr(self.qformer.bert, "embeddings"):
+            raise RuntimeError("embed_instructions needs the embedding layer: build the model with vocab_size=...")
+        device = self.query_tokens.device if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("the VideoChat2 binding runs on the HIP device only (no CPU fallback)")
+        V = len(input_ids)
+        ids = self._check_input_ids(input_ids, V)
+        front, keep = self._front(device, False, ids)
+        Q, Hd = self.n_query, self.qformer.config.hidden_size
+        tl = (C.c_int32 * max(V, 1))(*[len(x) for x in ids])
+        out = torch.empty(sum(Q + len(x) for x in ids), Hd, device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().infv_vqf_vc_embed(self._vc_handle(device), C.byref(front), V, C.cast(tl, C.c_void_p),
+                                                     C.c_void_p(out.data_ptr()),
+                                                     C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+        del keep
+        return list(out.split([Q + len(x) for x in ids]))
+
+    def _vc_call(self, name, videos, frame_src, text_embeds, hidden_in, new_video, u, memories, video_ids, want_hidden,
+                 img=False, input_ids=None):
+        """Body of :meth:`encode_videos` (``frame_src`` None: video v reads ``videos[v]``), :meth:`encode_streams` and
+        :meth:`encode_img_videos` (``img``: the vision LayerNorm, and with ``hidden_in`` None the embedding layer, run inside the
+        call).  Everything a caller can get wrong on the host raises ValueError before any device call."""
         videos = list(videos)
         F = len(videos)
         if F == 0:
@@ -479,8 +633,9 @@ class VideoChat2Encoder(nn.Module):
         block_counts = [int(f.size(0)) for f in videos]
         counts = [block_counts[s_] for s_ in frame_src] if streams else block_counts   # chunks per stream
         total = sum(counts)
-        rows = self._vc_inputs(V, text_embeds, hidden_in)
-        text_len = [int(r.size(0)) - Q for r in rows]
+        ids = self._check_input_ids(input_ids, V) if img and hidden_in is None else None   # (the embedding layer runs in the call)
+        rows = self._vc_inputs(V, text_embeds, hidden_in) if ids is None else None
+        text_len = [int(r.size(0)) - Q for r in rows] if ids is None else [len(x) for x in ids]
         use_ltm = cfg.alpha != 1.0 and n_cross > 0
         if use_ltm and memories is not None:
             memories = _check_vc_memories(self, memories, V)
@@ -501,13 +656,15 @@ class VideoChat2Encoder(nn.Module):
             all(f.dtype == videos[0].dtype and f.device == device for f in videos) else None
         if half is None:
             frames = _dev_f32(torch.cat(videos) if F > 1 else videos[0], device)
+            if img and frames.data_ptr() % 16:
+                frames = frames.clone(memory_format=torch.contiguous_format)
         else:
             frames = torch.cat(videos) if F > 1 else videos[0].detach()
             if not frames.is_contiguous() or frames.data_ptr() % 16:
                 frames = frames.clone(memory_format=torch.contiguous_format)
         tok = () if half is None else (TOKEN_DTYPES[half],)      # the argument the _tok entry points take behind `frames`
         lib = _lib.load()
-        hin = torch.cat([_dev_f32(r, device) for r in rows]).contiguous()
+        hin = torch.cat([_dev_f32(r, device) for r in rows]).contiguous() if rows is not None else None
         handles = None
         if not use_ltm:
             u = None                                          # (no memory: nothing is drawn)
@@ -539,11 +696,26 @@ class VideoChat2Encoder(nn.Module):
         cu = (C.c_int32 * (V + 1))(0, *_cumsum(counts))
         tl = (C.c_int32 * V)(*text_len)
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        tail = (T, C.byref(w), C.c_void_p(hin.data_ptr()), C.cast(tl, C.c_void_p), C.c_void_p(0 if u is None else u.data_ptr()),
+        if img:
+            front, keep_front = self._front(device, True, ids)
+            fcu = (C.c_int32 * (F + 1))(0, *_cumsum(block_counts))
+            src = (C.c_int32 * V)(*frame_src) if streams else None
+            with torch.cuda.device(device):
+                _lib.check(lib.infv_vqf_vc_encode_img(
+                    self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()),
+                    TOKEN_DTYPES[frames.dtype], F, C.cast(fcu, C.c_void_p), C.cast(src, C.c_void_p) if streams else None, T,
+                    C.byref(w), C.byref(front), C.c_void_p(0 if hin is None else hin.data_ptr()), C.cast(tl, C.c_void_p),
+                    C.c_void_p(0 if u is None else u.data_ptr()), int(bool(new_video)),
+                    C.c_void_p(0 if hidden is None else hidden.data_ptr()), C.c_void_p(proj.data_ptr()), C.c_void_p(mean.data_ptr()),
+                    stream))
+            del keep_front
+        tail = (T, C.byref(w), C.c_void_p(0 if hin is None else hin.data_ptr()), C.cast(tl, C.c_void_p), C.c_void_p(0 if u is None else u.data_ptr()),
                 int(bool(new_video)), C.c_void_p(0 if hidden is None else hidden.data_ptr()), C.c_void_p(proj.data_ptr()),
                 C.c_void_p(mean.data_ptr()), stream)
         with torch.cuda.device(device):
-            if streams:
+            if img:
+                pass                                          # (issued above)
+            elif streams:
                 fcu = (C.c_int32 * (F + 1))(0, *_cumsum(block_counts))
                 src = (C.c_int32 * V)(*frame_src)
                 _lib.check((lib.infv_vqf_vc_encode_streams_tok if tok else lib.infv_vqf_vc_encode_streams)(
