@@ -26,7 +26,7 @@
  *     the ABI.  infv_ltm_last_error() returns a thread-local description;
  *   - a handle is not re-entrant (the reference module is mutable, single-threaded state);
  *   - all floating-point data is fp32, row-major, batch size 1 (reference
- *     long_term_attention_gibbs.py:208,346); only the frame tokens may be fp16 or bf16 (infv_ltm_set_token_dtype).
+ *     long_term_attention_gibbs.py:208,346); only the frame tokens may be fp16, bf16 or fp8 e4m3 (infv_ltm_set_token_dtype).
  */
 #ifndef INFV_LTM_H
 #define INFV_LTM_H
@@ -174,17 +174,25 @@ int infv_ltm_has_memory(infv_ltm_handle h);                    /* 1 / 0 */
 
 /* Element type of the frame tokens `k` handed to pool / forward / consolidate.  The reference concatenates fp32
  * tensors (infinityqa.py:317-322), but their values come out of an fp16 producer: the ViT is .half() and the image
- * Q-former runs under fp16 autocast (blip2.py:37-43, infinityqa.py:256-259).  Three layouts are read in place:
+ * Q-former runs under fp16 autocast (blip2.py:37-43, infinityqa.py:256-259).  Four layouts are read in place:
  *   INFV_TOKENS_F32   4 bytes per element.
  *   INFV_TOKENS_F16   2 bytes per element and nothing lost: every fp16 value (subnormals included) is exact in fp32, it
  *                     is widened by the hardware conversion, and the sum, the division by P and everything after run
  *                     in fp32 in the same order -- every result has the bits of the fp32-token run on the same values.
  *   INFV_TOKENS_BF16  2 bytes per element; results differ from the fp32-token run only by the rounding of the tokens
  *                     themselves where the producer rounded them (2^-9 relative each, averaged over P tokens).
- * Either half format halves the bytes of the only HBM-heavy stream of the path; the pooled frames and everything after
+ *   INFV_TOKENS_F8E4M3  (code 4, declared below the enum) 1 byte per element: OCP FP8 e4m3fn, what torch.float8_e4m3fn holds
+ *                     -- not e5m2, not the e4m3fnuz encoding, no scale factor.  fp8 is the CALLER's storage choice (e.g.
+ *                     tokens.to(torch.float8_e4m3fn) when caching features): the library neither quantises nor scales nor
+ *                     judges that choice.  Its contract is equality: each of the 254 finite codes is an exact fp32 number
+ *                     (and exact in bf16), the two NaN codes 0x7F / 0xFF widen to NaN, the hardware conversion widens
+ *                     them, and everything after runs in fp32 in the same order -- every result has the bits of the run on
+ *                     the tokens widened to fp32.  `k` must be 16-byte aligned (INFV_ERR_INVALID before any launch).
+ * Either half format halves the bytes of the only HBM-heavy stream of the path; fp8 quarters them; the pooled frames and everything after
  * stay fp32.  fp16 and bf16 tokens must be 16-byte aligned where the video Q-former reads them (infv_vqf.h).  Codes not
  * listed here (2 among them) are refused.  Default fp32; set before the first call that takes `k`. */
 typedef enum { INFV_TOKENS_F32 = 0, INFV_TOKENS_BF16 = 1, INFV_TOKENS_F16 = 3 } infv_token_dtype;
+#define INFV_TOKENS_F8E4M3 4   /* accepted wherever an infv_token_dtype code is; entry points take the code as int32_t */
 int infv_ltm_set_token_dtype(infv_ltm_handle h, int32_t dtype);
 
 /* Frame mean-pool, long_term_attention_gibbs.py:304:  k [n_frames, P, d] -> kbar [n_frames, d] (fp32). */

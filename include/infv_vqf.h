@@ -4,7 +4,7 @@
  * `encode_video`, infty-Video-LLaMA/InfVideoLLaMA/models/infinityqa.py:280-344).  These entry points are what the
  * Python mirror (infinite_video_amd/video_qformer.py) binds with ctypes.  Plain pointers and sizes only; all
  * pointers are DEVICE pointers (fp32, row-major) unless stated; every call is asynchronous on `stream`.  Only the frame tokens
- * (`frames`) may be fp16 or bf16 instead (infv_vqf_set_token_dtype).
+ * (`frames`) may be fp16, bf16 or fp8 e4m3 instead (infv_vqf_set_token_dtype).
  * Errors: int status as in infv_ltm.h, message via infv_ltm_last_error().
  *
  * Scope: the query-token-only, eval-mode, all-ones-mask case the video Q-former is run in
@@ -74,7 +74,12 @@ int infv_vqf_set_precision(infv_vqf_handle h, int32_t exact_fp32);
  * both contractions run two bf16 MFMA products instead of three.  Results are bit for bit those of the same values passed as
  * fp32.  Where the split path does not apply (exact fp32, token counts that are no multiple of 64) the tokens are copied to
  * fp32 in a workspace of the handle first (fp16 and bf16 alike).  Every shape accepted with fp32 tokens is accepted with
- * fp16 and with bf16 tokens. */
+ * fp16 and with bf16 tokens.
+ * Code 4 = INFV_TOKENS_F8E4M3 (OCP e4m3fn at 1 byte per element, 16-byte aligned; infv_ltm.h) is accepted too: fp8 is the caller's
+ * storage choice and the contract is equality with the run on the tokens widened to fp32.  An e4m3 value is exactly its own bf16
+ * hi piece, so the token pass writes the two hi planes and no lo planes, both contractions run the two-product form as for bf16
+ * tokens, and the plane cache counts 4 bytes per element (2 for bf16, 8 for fp32 / fp16); off the split path the tokens are
+ * widened to fp32 in a workspace of the handle first. */
 int infv_vqf_set_token_dtype(infv_vqf_handle h, int32_t dtype);
 
 /* Layer 0's hidden states entering the cross-attention come from the learned query tokens and the weights only, so
@@ -248,7 +253,9 @@ int infv_vqf_vc_encode_streams(infv_vqf_handle h, const infv_ltm_handle* ltm, in
                                float* hidden_out, float* proj_out, float* proj_mean, void* stream);
 
 /* infv_vqf_vc_encode_videos / infv_vqf_vc_encode_streams with the frame tokens' element type as an ARGUMENT of the call
- * (additive): token_dtype is an infv_token_dtype code -- 0 fp32, 1 bf16, 3 fp16 -- and `frames` holds that type.  The handle's
+ * (additive): token_dtype is an infv_token_dtype code -- 0 fp32, 1 bf16, 3 fp16 -- or 4 (INFV_TOKENS_F8E4M3: OCP e4m3fn at 1 byte
+ * per element, the caller's storage choice; its hi planes F_hi / FT_hi are written, no lo planes, two-product contractions, the
+ * bits of the call on the tokens widened to fp32) and `frames` holds that type.  The handle's
  * infv_vqf_set_token_dtype setting is neither read nor changed.  Code 0 is the call without the argument: its bits, its
  * launches.  fp16 / bf16 tokens are read in place at 2 bytes per element (no fp32 copy) and give the bits of the fp32 call on
  * the same values: an fp16 value is exactly its bf16 hi + lo planes, a bf16 value is its own hi plane (the contractions then take
@@ -299,8 +306,8 @@ typedef struct {
 
 /* infv_vqf_vc_encode_videos_tok (frame_src == NULL; F and fcu are not read) or infv_vqf_vc_encode_streams_tok (frame_src given)
  * with `front` in front.  With front NULL, or both of its parts off, it IS that call: its bits, its launches.
- *   vision LayerNorm on: `frames` is the vision encoder's output in its own type (fp32 / fp16 / bf16, 16-byte aligned), read in
- *     place.  One launch writes (mean, 1 / sqrt(var + eps)) per distinct token row (8 bytes a token; two-pass, biased variance,
+ *   vision LayerNorm on: `frames` is the vision encoder's output in its own type (fp32 / fp16 / bf16, 16-byte aligned; fp8 tokens,
+ *     code 4, are INFV_ERR_UNSUPPORTED here before any device work: no vision encoder emits fp8), read in place.  One launch writes (mean, 1 / sqrt(var + eps)) per distinct token row (8 bytes a token; two-pass, biased variance,
  *     fixed-order wave reductions); the token pass and the pooling then normalise on load:  y = fma((x - mean) * rstd, gamma, beta)
  *     with x widened exactly.  No fp32 copy of the tokens is made.  A normalised value is a general fp32 number, so every source
  *     type writes all four planes and takes the three-product contractions (bf16 too; the planes count 4 x towards
@@ -338,7 +345,8 @@ int infv_vqf_vc_embed(infv_vqf_handle h, const infv_vqf_vc_front* front, int32_t
 /* The token pass alone (exported for tests and measurements, as infv_vqf_self_attention is): the launches the encoders issue for
  * frames [nb][n_tokens][d] of element type token_dtype.
  *   Fh, Fl [nb][n_tokens][d], Th, Tl [nb][d][n_tokens] bf16: the hi / lo planes and their transposed copies.  bf16 tokens are
- *          their own hi plane: Fh, Fl and Tl must be NULL and only Th is written.
+ *          their own hi plane: Fh, Fl and Tl must be NULL and only Th is written.  fp8 tokens (code 4) have no lo piece: Fl and
+ *          Tl must be NULL, Fh and Th are written.
  *   kbar   [nb][n_tokens / tokens_per_frame][d] fp32 frame means, the bits of infv_ltm_pool; NULL: planes only
  * n_tokens a multiple of 32, d a multiple of 64, every pointer 16-byte aligned, tokens_per_frame dividing n_tokens where kbar is
  * given (INFV_ERR_INVALID otherwise).  INFV_ERR_UNSUPPORTED, and no launch, where no one-pass form with the means exists:

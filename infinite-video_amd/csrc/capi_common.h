@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "../../include/infv_ltm.h"
+#include "vqf_internal.h"
 
 namespace infv {
 
@@ -18,9 +19,12 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
             return ::infv::fail(INFV_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// frame-token element types (infv_token_dtype): the codes the entry points accept, and bytes per element
-inline bool token_dtype_known(int dtype) { return dtype == INFV_TOKENS_F32 || dtype == INFV_TOKENS_BF16 || dtype == INFV_TOKENS_F16; }
-inline size_t token_bytes(infv_token_dtype tok) { return tok == INFV_TOKENS_F32 ? 4 : 2; }
+// frame-token element types (tok_code): the codes the entry points accept (bytes per element: token_bytes, vqf_internal.h)
+inline bool token_dtype_known(int dtype) {
+    return dtype == INFV_TOKENS_F32 || dtype == INFV_TOKENS_BF16 || dtype == INFV_TOKENS_F16 || dtype == INFV_TOKENS_F8E4M3;
+}
+// fp8 tokens are read in 4- and 16-byte vectors from wherever `k` / `frames` starts: the address must be 16-byte aligned
+inline bool token_ptr_ok(tok_code tok, const void* p) { return tok != INFV_TOKENS_F8E4M3 || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 struct DeviceBuf {
     void* p = nullptr;

@@ -22,6 +22,9 @@ inline const char* exp_env(const char* name) {
     return nullptr;
 #endif
 }
+// a frame-token element type as the library carries it: one of the infv_token_dtype codes or INFV_TOKENS_F8E4M3 (infv_ltm.h).  A plain
+// integer, not the enum: code 4 is declared beside the enum, outside the enumerators' range.
+typedef int tok_code;
 }  // namespace infv
 
 // ---- launch census: every kernel launch of the library goes through INFV_LAUNCH (same argument order as hipLaunchKernelGGL); it

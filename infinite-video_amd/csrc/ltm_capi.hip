@@ -172,7 +172,7 @@ struct infv_ltm_s {
     // error word of the persistent chain kernel: pinned host memory mapped into the device, so a time-out is
     // visible to the host without any synchronisation or copy
     unsigned int* err_host = nullptr; unsigned int* err_dev = nullptr;
-    infv_token_dtype tok = INFV_TOKENS_F32;   // element type of the frame tokens `k` (infv_ltm_set_token_dtype)
+    tok_code tok = INFV_TOKENS_F32;   // element type of the frame tokens `k` (infv_ltm_set_token_dtype)
     bool v_split = false;               // INFV_VPROJ_SPLIT=1 at create: V' half of the sub-batch projection as a split-bf16 contraction
     // Where the V' half of a sub-batch's projection runs.  Default (round 3): inside the side stream's one [V' | S'] GEMM.  The
     // UC stream (V' GEMM -> softmax weights -> update, serial per sub-batch) was the second-longest stream of the pipeline
@@ -692,16 +692,24 @@ int infv_ltm_has_memory(infv_ltm_handle h) {
     return h->has_memory ? 1 : 0;
 }
 
+// fp8 tokens are read in place in 4-byte vectors at offsets that are multiples of 4: `k` must be 16-byte aligned, refused before any
+// launch or memory change (the other token types keep the alignment rules they had)
+static int check_k_aligned(const char* name, tok_code tok, const void* k) {
+    if (k && !token_ptr_ok(tok, k)) return fail(INFV_ERR_INVALID, "%s: fp8 frame tokens must be 16-byte aligned", name);
+    return INFV_OK;
+}
+
 int infv_ltm_set_token_dtype(infv_ltm_handle h, int32_t dtype) {
     if (int rc = check_handle(h)) return rc;
     if (!token_dtype_known(dtype)) return fail(INFV_ERR_INVALID, "set_token_dtype: unknown dtype %d", dtype);
-    h->tok = static_cast<infv_token_dtype>(dtype);
+    h->tok = static_cast<tok_code>(dtype);
     return INFV_OK;
 }
 
 int infv_ltm_pool(infv_ltm_handle h, const void* k, int64_t n_frames, float* kbar, void* stream) {
     if (int rc = check_handle(h)) return rc;
     if (!k || !kbar || n_frames < 0) return fail(INFV_ERR_INVALID, "pool: bad arguments");
+    if (int rc = check_k_aligned("pool", h->tok, k)) return rc;
     Timed t_(h->prof, INFV_KERNEL_POOL, static_cast<hipStream_t>(stream));
     HIP_TRY(launch_pool(k, h->tok, kbar, n_frames, h->P, h->d, static_cast<hipStream_t>(stream)));
     return INFV_OK;
@@ -718,6 +726,7 @@ int infv_ltm_new_rows(infv_ltm_handle h, int32_t T) {
 int infv_ltm_pool_rows(infv_ltm_handle h, const void* k, int32_t n_chunks, int32_t T, float* R, void* stream_) {
     if (int rc = check_handle(h)) return rc;
     if (!k || !R || n_chunks < 0) return fail(INFV_ERR_INVALID, "pool_rows: bad arguments");
+    if (int rc = check_k_aligned("pool_rows", h->tok, k)) return rc;
     Plan* plan = nullptr;
     if (int rc = find_plan(h, T, &plan)) return rc;
     if (plan->dense.on) return fail(INFV_ERR_UNSUPPORTED, "pool_rows: the plan for T = %d is dense (no box rows)", T);
@@ -832,6 +841,7 @@ int infv_ltm_consolidate_q(infv_ltm_handle h, const void* k, int32_t n_chunks, i
                            void* stream) {
     if (int rc = check_handle(h)) return rc;
     if (!k || n_chunks < 0) return fail(INFV_ERR_INVALID, "consolidate_q: bad arguments");
+    if (int rc = check_k_aligned("consolidate_q", h->tok, k)) return rc;
     if (n_chunks > 0)
         if (int rc = precheck_step(h, q, proj, ctx, T, Q, u, !new_doc, n_chunks)) return rc;
     if (new_doc) infv_ltm_reset(h);
@@ -846,6 +856,7 @@ int infv_ltm_forward(infv_ltm_handle h, const void* k, int32_t T, const float* q
                      const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream) {
     if (int rc = check_handle(h)) return rc;
     if (!k) return fail(INFV_ERR_INVALID, "forward: null k");
+    if (int rc = check_k_aligned("forward", h->tok, k)) return rc;
     if (int rc = precheck_step(h, q, proj, ctx, T, Q, u, !new_doc)) return rc;
     if (new_doc) infv_ltm_reset(h);
     HIP_TRY(h->kbar_ws.reserve((size_t)T * h->d * sizeof(float)));
@@ -858,6 +869,7 @@ int infv_ltm_forward_into(infv_ltm_handle h, const void* k, int32_t token_dtype,
     if (int rc = check_handle(h)) return rc;
     if (!token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "forward_into: unknown token dtype %d", token_dtype);
     if (T <= 0 || !k || !kbar) return fail(INFV_ERR_INVALID, "forward_into: T must be positive, k and kbar non-null");
+    if (int rc = check_k_aligned("forward_into", token_dtype, k)) return rc;
     if (int rc = precheck_step(h, q, proj, ctx, T, Q, u, true)) return rc;
     if (int rc = infv_ltm_set_token_dtype(h, token_dtype)) return rc;
     if (int rc = infv_ltm_pool(h, k, T, kbar, stream)) return rc;
@@ -1739,6 +1751,7 @@ static int consolidate_impl(infv_ltm_handle h, const void* k_, const float* kbar
     if (int rc = check_handle(h)) return rc;
     const char* k = static_cast<const char*>(k_);               // byte addressing: the token element size depends on the handle
     if ((!k && !kbar_pre) || !q || !proj || !ctx || n_chunks < 0) return fail(INFV_ERR_INVALID, "consolidate: bad arguments");
+    if (int rc = check_k_aligned("consolidate", h->tok, k)) return rc;
     if (int rc = check_chain_error(h)) return rc;
     if (int rc = check_q(h, Q)) return rc;
     Plan* plan = nullptr;
@@ -1829,6 +1842,8 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
             return fail(INFV_ERR_INVALID, "%s: handle %d's configuration (N, H, dh, d, P, L, S, sticky%s) differs from handle 0's",
                         name, v, tokens ? ", token dtype" : "");
     infv_ltm_handle h0 = hs[0];
+    if (tokens)
+        if (int rc = check_k_aligned(name, h0->tok, k_)) return rc;
     const bool sticky = h0->cfg.sticky != 0;
     int max_len = 0;
     for (int v = 0; v < V; ++v) max_len = cu[v + 1] - cu[v] > max_len ? cu[v + 1] - cu[v] : max_len;

@@ -65,6 +65,26 @@ struct TokF16 {
     }
 };
 
+// OCP FP8 e4m3fn (what torch.float8_e4m3fn holds), a storage format the caller chose: one byte per element.  v_cvt_pk_f32_fp8 widens
+// two codes per instruction (the low or the high 16 bits of the dword); each of the 254 finite codes (subnormals down to 2^-9, +-448
+// at the top) is an exact fp32 number and 0x7F / 0xFF give NaN, as .float() does -- everything behind widen() sees the values an fp32
+// copy of the tokens would hold.  A lane still owns 4 columns, so the units, the d4 arithmetic and the order of every column's sum are
+// the other types': only the bytes per load differ (256 B a wave).
+typedef float floatx2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ floatx4 widen_f8x4(unsigned v) {
+    const floatx2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v, true);
+    floatx4 r;
+    r.x = lo.x; r.y = lo.y; r.z = hi.x; r.w = hi.y;
+    return r;
+}
+struct TokF8 {
+    typedef unsigned int vec;                          // 4 fp8 columns per lane (4 bytes)
+    static __device__ inline floatx4 widen(unsigned v) { return widen_f8x4(v); }
+    static __device__ inline unsigned load_nt(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+        return __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 2 /* nt */);
+    }
+};
+
 // ---- vision LayerNorm of frame tokens (nn.LayerNorm(width, eps) in front of the Q-former, videochat2_it_mistral.py:195) ----
 // y = fma((x - mu) * r, gamma[c], beta[c]) of one token value: (mu, r) = the token row's mean and 1 / sqrt(var + eps), as
 // token_ln_stats_kernel writes them.  THE definition: ln_tokens_kernel (the fp32 copy), the tile pass and the pooling that apply the

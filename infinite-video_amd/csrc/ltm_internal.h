@@ -61,7 +61,7 @@ struct WSegs {
 };
 
 // ---- launchers (all asynchronous on `stream`) -------------------------------------------
-hipError_t launch_pool(const void* k, infv_token_dtype tok, float* kbar, int64_t n_frames, int P, int d, hipStream_t stream, int lds_pad = 0);
+hipError_t launch_pool(const void* k, tok_code tok, float* kbar, int64_t n_frames, int P, int d, hipStream_t stream, int lds_pad = 0);
 
 // R[c][r][:] = val * sum of the frames of row r of chunk c;  Pnew[sk][c][r][l][kv][dm] = split-K
 // partials of R . W[l][kv]^T  (sk = project_splitk(n_chunks*rows, d) slabs of n_chunks*rows*L*2*dm floats).
@@ -80,11 +80,11 @@ struct PoolCallDesc {
     unsigned int* done;             // [sub-batches] rows written (write-through) so far
     int store_mode;                 // stores of the rows / planes when done == nullptr (a kernel boundary is the hand-off): 0 write-through (sc1), 1 plain, 2 nontemporal
 };
-hipError_t launch_pool_rows2_call(const void* k, infv_token_dtype tok, int T, int P, int d, const OperatorView& op, const PoolCallDesc& pc,
+hipError_t launch_pool_rows2_call(const void* k, tok_code tok, int T, int P, int d, const OperatorView& op, const PoolCallDesc& pc,
                                   hipStream_t stream, int u, int lds_pad);
 // planes (or nullptr): the rows' three bf16 planes for the projection GEMM, k-tile-major over the launch's rows (split3's layout);
 // *planes_done says whether the launched kernel wrote them (the grid-stride and LDS-DMA variants of the experiments build do not)
-hipError_t launch_pool_rows2(const void* k, infv_token_dtype tok, int n_chunks, int T, int P, int d, const OperatorView& op, float* R,
+hipError_t launch_pool_rows2(const void* k, tok_code tok, int n_chunks, int T, int P, int d, const OperatorView& op, float* R,
                              hipStream_t stream, int u, int lds_pad, int max_wgs = 0, void* const* planes = nullptr, bool* planes_done = nullptr);
 int project_splitk(int M, int K);
 hipError_t launch_rows(const float* kbar, int n_chunks, int T, int d, const OperatorView& op, float* R,
@@ -317,7 +317,7 @@ hipError_t launch_video_table(VideoDesc* dst, const VideoDesc* descs, int n, hip
 // the shapes the multi-video kernels take: sparse plans of N <= 256 (multiple of 16), the 4-row attend tiles, S <= 1024
 bool videos_supported(int N, int d, int dm, int L, int S);
 // kbar[j][f][:] = mean over P tokens of frame f of video rank j's chunk of this step (k packed [chunks][T*P][d])
-hipError_t launch_pool_videos(const void* k, infv_token_dtype tok, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream);
+hipError_t launch_pool_videos(const void* k, tok_code tok, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream);
 // out[j][f][:] = kbar[chunk of video rank j at this step][f][:] (kbar packed [chunks][T][d] fp32): bitwise copies
 hipError_t launch_gather_videos(const float* kbar, const VideoStep& vs, int T, int d, float* out, hipStream_t stream);
 // Pnew[j * rows + r][l][kv][dm] = R(j, r) . W[l][kv]^T with the rows built from kbar[j] (no split-K: the summation order of an

@@ -27,20 +27,21 @@ namespace infv {
 //    1 KiB contiguous; P loads per lane are independent, so the whole 32 KiB of a unit is in
 //    flight at once.  This is the only HBM-heavy stage of the path (25.2 MB per chunk).
 // ======================================================================================
-// (the token types TokF32 / TokBF16 / TokF16 -- how a kernel loads and widens frame tokens -- live in ltm_device.h)
-// tok -> the token type: `f` is a generic callable taking a value of TokF32 / TokBF16 / TokF16
+// (the token types TokF32 / TokBF16 / TokF16 / TokF8 -- how a kernel loads and widens frame tokens -- live in ltm_device.h)
+// tok -> the token type: `f` is a generic callable taking a value of TokF32 / TokBF16 / TokF16 / TokF8
 template <class F>
-static hipError_t with_token_type(infv_token_dtype tok, F f) {
+static hipError_t with_token_type(tok_code tok, F f) {
     switch (tok) {
         case INFV_TOKENS_F32: return f(TokF32{});
         case INFV_TOKENS_BF16: return f(TokBF16{});
         case INFV_TOKENS_F16: return f(TokF16{});
+        case INFV_TOKENS_F8E4M3: return f(TokF8{});
     }
     return hipErrorInvalidValue;
 }
 
-// (the kernels' bodies are __device__ templates: the fp32 / bf16 kernels are instantiations over the token type, the fp16 ones are
-//  kernels of their own name over the same body -- the shipped library's kernel census counts the former by name)
+// (the kernels' bodies are __device__ templates: the fp32 / bf16 kernels are instantiations over the token type, the fp16 and fp8
+//  ones are kernels of their own name over the same body -- the shipped library's kernel census counts the former by name)
 template <int UNROLL, int NT, class Tok>
 __device__ __forceinline__ void pool_frames_body(const void* __restrict__ k_, float* __restrict__ kbar,
                                                  long n_units, int P, int d4, int slices) {
@@ -80,15 +81,21 @@ __global__ __launch_bounds__(NT) void pool_frames_f16_kernel(const void* __restr
                                                               long n_units, int P, int d4, int slices) {
     pool_frames_body<UNROLL, NT, TokF16>(k_, kbar, n_units, P, d4, slices);
 }
+template <int UNROLL, int NT>
+__global__ __launch_bounds__(NT) void pool_frames_f8_kernel(const void* __restrict__ k_, float* __restrict__ kbar,
+                                                             long n_units, int P, int d4, int slices) {
+    pool_frames_body<UNROLL, NT, TokF8>(k_, kbar, n_units, P, d4, slices);
+}
 template <int UNROLL, int NT, class Tok> struct PoolFramesFn { static auto get() { return pool_frames_kernel<UNROLL, NT, Tok>; } };
 template <int UNROLL, int NT> struct PoolFramesFn<UNROLL, NT, TokF16> { static auto get() { return pool_frames_f16_kernel<UNROLL, NT>; } };
+template <int UNROLL, int NT> struct PoolFramesFn<UNROLL, NT, TokF8> { static auto get() { return pool_frames_f8_kernel<UNROLL, NT>; } };
 
 // `lds_pad` bytes of (unused) dynamic LDS per workgroup cap how many of them a CU hosts, so that a
 // latency-critical kernel on another stream always finds wave slots and LDS (see consolidate()).
 template <class Tok>
 static hipError_t launch_pool_t(const void* k, float* kbar, int64_t n_frames, int P, int d, hipStream_t stream, int lds_pad);
 
-hipError_t launch_pool(const void* k, infv_token_dtype tok, float* kbar, int64_t n_frames, int P, int d, hipStream_t stream, int lds_pad) {
+hipError_t launch_pool(const void* k, tok_code tok, float* kbar, int64_t n_frames, int P, int d, hipStream_t stream, int lds_pad) {
     return with_token_type(tok, [&](auto t) { return launch_pool_t<decltype(t)>(k, kbar, n_frames, P, d, stream, lds_pad); });
 }
 
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(256) void pool_frames_ln_f16_kernel(const void* __r
     pool_frames_ln_body<TokF16>(k_, stats, gamma, beta, kbar, n_units, P, d4, slices);
 }
 
-hipError_t launch_pool_ln(const void* k, infv_token_dtype tok, const void* stats, const float* gamma, const float* beta, float* kbar,
+hipError_t launch_pool_ln(const void* k, tok_code tok, const void* stats, const float* gamma, const float* beta, float* kbar,
                           int64_t n_frames, int P, int d, hipStream_t stream) {
     const int d4 = d / 4;
     const int slices = (d4 + 63) / 64;
@@ -375,8 +382,15 @@ __global__ __launch_bounds__(1024) void pool_rows2_f16_kernel(const void* __rest
                                                               long long* __restrict__ stamps, int prio, int tid_addr, PoolCallDesc pc) {
     pool_rows2_body<U, TokF16, CALL>(k_, chunk_stride, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
 }
+template <int U, bool CALL>
+__global__ __launch_bounds__(1024) void pool_rows2_f8_kernel(const void* __restrict__ k_, long chunk_stride, int P, int d4, int slices,
+                                                             OperatorView op, long n_rows_total, float* __restrict__ R,
+                                                             long long* __restrict__ stamps, int prio, int tid_addr, PoolCallDesc pc) {
+    pool_rows2_body<U, TokF8, CALL>(k_, chunk_stride, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc);
+}
 template <int U, class Tok, bool CALL> struct PoolRows2Fn { static auto get() { return pool_rows2_kernel<U, Tok, CALL>; } };
 template <int U, bool CALL> struct PoolRows2Fn<U, TokF16, CALL> { static auto get() { return pool_rows2_f16_kernel<U, CALL>; } };
+template <int U, bool CALL> struct PoolRows2Fn<U, TokF8, CALL> { static auto get() { return pool_rows2_f8_kernel<U, CALL>; } };
 
 #ifdef INFV_EXPERIMENTS
 static long long* g_stamps = nullptr;            // [kStampCap][4], launches appended
@@ -476,7 +490,7 @@ static hipError_t launch_pool_rows2_t(const void* k, int n_chunks, int T, int P,
     return hipGetLastError();
 }
 
-hipError_t launch_pool_rows2(const void* k, infv_token_dtype tok, int n_chunks, int T, int P, int d, const OperatorView& op, float* R,
+hipError_t launch_pool_rows2(const void* k, tok_code tok, int n_chunks, int T, int P, int d, const OperatorView& op, float* R,
                              hipStream_t stream, int u, int lds_pad, int max_wgs, void* const* planes, bool* planes_done) {
     if (planes_done != nullptr) *planes_done = false;
     if (op.rows == 0 || n_chunks == 0) return hipSuccess;
@@ -486,7 +500,7 @@ hipError_t launch_pool_rows2(const void* k, infv_token_dtype tok, int n_chunks, 
     });
 }
 
-hipError_t launch_pool_rows2_call(const void* k, infv_token_dtype tok, int T, int P, int d, const OperatorView& op, const PoolCallDesc& pc,
+hipError_t launch_pool_rows2_call(const void* k, tok_code tok, int T, int P, int d, const OperatorView& op, const PoolCallDesc& pc,
                                   hipStream_t stream, int u, int lds_pad) {
     if (op.rows == 0 || pc.n_chunks == 0) return hipSuccess;
     if (pc.R_all == nullptr || pc.sub <= 0) return hipErrorInvalidValue;
@@ -1580,8 +1594,8 @@ hipError_t launch_video_table(VideoDesc* dst, const VideoDesc* descs, int n, hip
 
 // one wave per (slot j, frame f, 256-float column slice), as pool_frames_kernel: P loads in flight, summed in token order, / P
 template <class Tok>
-__global__ __launch_bounds__(256) void pool_videos_kernel(const void* __restrict__ k_, float* __restrict__ kbar, VideoStep vs,
-                                                          int T, int P, int d4, int slices) {
+__device__ __forceinline__ void pool_videos_body(const void* __restrict__ k_, float* __restrict__ kbar, const VideoStep& vs,
+                                                 int T, int P, int d4, int slices) {
     typedef typename Tok::vec tvec;
     constexpr int UNROLL = 16;
     const int lane = threadIdx.x & 63;
@@ -1607,14 +1621,26 @@ __global__ __launch_bounds__(256) void pool_videos_kernel(const void* __restrict
     acc.x /= fp; acc.y /= fp; acc.z /= fp; acc.w /= fp;
     reinterpret_cast<floatx4*>(kbar)[fr * d4 + c4] = acc;
 }
+template <class Tok>
+__global__ __launch_bounds__(256) void pool_videos_kernel(const void* __restrict__ k_, float* __restrict__ kbar, VideoStep vs,
+                                                          int T, int P, int d4, int slices) {
+    pool_videos_body<Tok>(k_, kbar, vs, T, P, d4, slices);
+}
+// (fp8: a kernel of its own name over the same body, as the pooling kernels above)
+__global__ __launch_bounds__(256) void pool_videos_f8_kernel(const void* __restrict__ k_, float* __restrict__ kbar, VideoStep vs,
+                                                             int T, int P, int d4, int slices) {
+    pool_videos_body<TokF8>(k_, kbar, vs, T, P, d4, slices);
+}
+template <class Tok> struct PoolVideosFn { static auto get() { return pool_videos_kernel<Tok>; } };
+template <> struct PoolVideosFn<TokF8> { static auto get() { return pool_videos_f8_kernel; } };
 
-hipError_t launch_pool_videos(const void* k, infv_token_dtype tok, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream) {
+hipError_t launch_pool_videos(const void* k, tok_code tok, const VideoStep& vs, int T, int P, int d, float* kbar, hipStream_t stream) {
     const int d4 = d / 4, slices = (d4 + 63) / 64;
     const long n_units = (long)vs.n * T * slices;
     if (n_units == 0) return hipSuccess;
     const dim3 grid((unsigned)((n_units + 3) / 4));
     return with_token_type(tok, [&](auto t) {
-        INFV_LAUNCH(pool_videos_kernel<decltype(t)>, grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
+        INFV_LAUNCH(PoolVideosFn<decltype(t)>::get(), grid, dim3(256), 0, stream, k, kbar, vs, T, P, d4, slices);
         return hipGetLastError();
     });
 }

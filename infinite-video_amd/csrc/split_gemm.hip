@@ -977,6 +977,76 @@ hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void*
 }
 
 // ------------------------------------------------------------------------------------------------------
+// The token pass for fp8 e4m3 frame tokens (a storage format the caller chose): F [n][d] at 1 byte per element, read in 16-byte
+// vectors of 16.  An e4m3 value widens exactly to fp32 (widen_f8x4, ltm_device.h) and is exactly its own bf16 hi piece with a zero lo
+// piece (4 significand bits), so only the hi planes exist: F_hi [n][d] (the B operand of the score contraction: the caller's buffer
+// holds no bf16) and FT_hi [d][n]; both contractions then run their two-product form, as for bf16 tokens, bit for bit the
+// three-product run on the same values.  With kbar != nullptr the frame means are summed in token order from the widened fp32 tile and
+// divided by P, as the fp32 pass does.  The tile is kept widened, 65 words a row; the transposed half is split_transpose_f16_kernel's.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void split_transpose_f8_kernel(const unsigned char* __restrict__ F, int n, int d,
+                                                                 __bf16* __restrict__ Fh, __bf16* __restrict__ Th,
+                                                                 float* __restrict__ kbar, int P) {
+    __shared__ float tile[64][65];
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const long cb = (long)blockIdx.z * n * d;
+    {
+        const int r = tid >> 2, c16 = (tid & 3) * 16;     // 256 vectors of 16 fp8
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        if (r0 + r < n) raw = *reinterpret_cast<const uint4*>(F + cb + (long)(r0 + r) * d + c0 + c16);
+        const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+        unsigned h2[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const floatx4 x = widen_f8x4(w[q]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) tile[r][c16 + 4 * q + k] = x[k];
+            h2[2 * q] = pack2((__bf16)x[0], (__bf16)x[1]);
+            h2[2 * q + 1] = pack2((__bf16)x[2], (__bf16)x[3]);
+        }
+        if (r0 + r < n) {
+            uint4* dst = reinterpret_cast<uint4*>(Fh + cb + (long)(r0 + r) * d + c0 + c16);
+            dst[0] = make_uint4(h2[0], h2[1], h2[2], h2[3]);
+            dst[1] = make_uint4(h2[4], h2[5], h2[6], h2[7]);
+        }
+    }
+    __syncthreads();
+    // transposed: row = column c of the tile, 8 consecutive tokens per thread
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int e = tid + 256 * p;
+        const int c = e >> 3, r8 = (e & 7) * 8;
+        if (r0 + r8 < n) {                           // n % 8 == 0 (multiple of 32)
+            __bf16 h[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) h[k] = (__bf16)tile[r8 + k][c];
+            *reinterpret_cast<uint4*>(Th + cb + (long)(c0 + c) * n + r0 + r8) =
+                make_uint4(pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7]));
+        }
+    }
+    if (kbar) {
+        const int fpt = 64 / P;                      // frames per tile
+        for (int e = tid; e < fpt * 64; e += 256) {
+            const int f = e >> 6, c = e & 63;
+            if (r0 + (f + 1) * P <= n) {
+                float acc = 0.f;
+                for (int p = 0; p < P; ++p) acc += tile[f * P + p][c];
+                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
+            }
+        }
+    }
+}
+
+hipError_t launch_split_transpose_f8(const void* F, int nb, int n, int d, void* Fh, void* Th, hipStream_t stream, float* kbar, int P) {
+    if (n % 32 || d % 64 || !Fh || !Th) return hipErrorInvalidValue;
+    if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
+    INFV_LAUNCH(split_transpose_f8_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const unsigned char*>(F), n, d,
+                static_cast<__bf16*>(Fh), static_cast<__bf16*>(Th), kbar, P);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------
 // The token pass for bf16 frame tokens: F [n][d] bf16 is the score contraction's B operand as it stands (hi = the token, lo = 0
 // exactly), so only FT_hi [d][n] is written -- and, with kbar != nullptr, the frame means, summed in token order and divided by P
 // as above (the same bits as the fp32 pass on the same values, and as pool_frames_kernel).  64 x 64 tiles, 16-byte loads and
@@ -1037,15 +1107,17 @@ hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, 
 // The token pass of `nb` <= 32768 chunks (grid.z) for any token type: the launch prepare_split issues.  kbar != nullptr needs
 // token_pass_gives_means(P): a frame that divides the 64-token tile.  (A per-frame form for P = 196 -- one workgroup per frame,
 // slab and chunk, the column sums kept in registers across sub-tiles -- was measured at 128 eval-shape chunks and lost to pooling
-// + this pass for fp16 and bf16 tokens alike, profiles/vc_half_tokens.jsonl; it is gone.)  bf16: Fh / Fl / Tl are not written.
+// + this pass for fp16 and bf16 tokens alike, profiles/vc_half_tokens.jsonl; it is gone.)  bf16: Fh / Fl / Tl are not written;
+// fp8: Fl / Tl are not written.
 bool token_pass_gives_means(int P) { return P >= 1 && 64 % P == 0; }
 
-hipError_t launch_token_pass(const void* F, infv_token_dtype tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
+hipError_t launch_token_pass(const void* F, tok_code tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
                              hipStream_t stream, float* kbar, int P) {
     if (kbar && !token_pass_gives_means(P)) return hipErrorInvalidValue;
     switch (tok) {
         case INFV_TOKENS_BF16: return launch_transpose_bf16(F, nb, n, d, Th, stream, kbar, P);
         case INFV_TOKENS_F16: return launch_split_transpose_f16(F, nb, n, d, Fh, Fl, Th, Tl, stream, kbar, P);
+        case INFV_TOKENS_F8E4M3: return launch_split_transpose_f8(F, nb, n, d, Fh, Th, stream, kbar, P);
         case INFV_TOKENS_F32: return launch_split_transpose(static_cast<const float*>(F), nb, n, d, Fh, Fl, Th, Tl, stream, kbar, P);
     }
     return hipErrorInvalidValue;
@@ -1089,6 +1161,25 @@ hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream
     for (long o = 0; o < n; o += (1l << 33)) {          // (grid.x limit)
         const long m = n - o < (1l << 33) ? n - o : (1l << 33);
         INFV_LAUNCH(upcast_f16_kernel, dim3((unsigned)((m / 8 + 255) / 256)), dim3(256), 0, stream, static_cast<const _Float16*>(x) + o, y + o, m / 8);
+    }
+    return hipGetLastError();
+}
+
+// x [n] fp8 e4m3 -> y [n] fp32 (n % 16 == 0), exact: fp8 tokens where the split path does not apply
+__global__ __launch_bounds__(256) void upcast_f8_kernel(const unsigned char* __restrict__ x, float* __restrict__ y, long n16) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n16) return;
+    const uint4 v = reinterpret_cast<const uint4*>(x)[i];
+    floatx4* dst = reinterpret_cast<floatx4*>(y) + 4 * i;
+    dst[0] = widen_f8x4(v.x); dst[1] = widen_f8x4(v.y); dst[2] = widen_f8x4(v.z); dst[3] = widen_f8x4(v.w);
+}
+
+hipError_t launch_upcast_f8(const void* x, float* y, long n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (n % 16) return hipErrorInvalidValue;
+    for (long o = 0; o < n; o += (1l << 33)) {          // (grid.x limit)
+        const long m = n - o < (1l << 33) ? n - o : (1l << 33);
+        INFV_LAUNCH(upcast_f8_kernel, dim3((unsigned)((m / 16 + 255) / 256)), dim3(256), 0, stream, static_cast<const unsigned char*>(x) + o, y + o, m / 16);
     }
     return hipGetLastError();
 }
@@ -1146,7 +1237,7 @@ static hipError_t launch_token_ln_stats_t(const void* F, long n_rows, int d, flo
     return hipGetLastError();
 }
 
-hipError_t launch_token_ln_stats(const void* F, infv_token_dtype tok, long n_rows, int d, float eps, void* stats, hipStream_t stream) {
+hipError_t launch_token_ln_stats(const void* F, tok_code tok, long n_rows, int d, float eps, void* stats, hipStream_t stream) {
     if (n_rows <= 0) return hipSuccess;
     if (d < 64 || d % 64 || d > kTokenLnMaxWidth || (n_rows + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
     float2* st = static_cast<float2*>(stats);
@@ -1171,7 +1262,7 @@ __global__ __launch_bounds__(256) void ln_tokens_kernel(const void* __restrict__
                                                  reinterpret_cast<const floatx4*>(beta)[c4]);
 }
 
-hipError_t launch_ln_tokens(const void* F, infv_token_dtype tok, long n_rows, int d, const void* stats, const float* gamma, const float* beta,
+hipError_t launch_ln_tokens(const void* F, tok_code tok, long n_rows, int d, const void* stats, const float* gamma, const float* beta,
                             float* y, hipStream_t stream) {
     if (n_rows <= 0) return hipSuccess;
     if (d < 64 || d % 64) return hipErrorInvalidValue;
@@ -1182,7 +1273,7 @@ hipError_t launch_ln_tokens(const void* F, infv_token_dtype tok, long n_rows, in
         const long m = n_rows - r0 < step ? n_rows - r0 : step;
         const long n_vec = m * d4;
         const dim3 grid((unsigned)((n_vec + 255) / 256));
-        const void* src = static_cast<const char*>(F) + r0 * d * (tok == INFV_TOKENS_F32 ? 4 : 2);
+        const void* src = static_cast<const char*>(F) + r0 * d * (long)token_bytes(tok);
         float* dst = y + r0 * d;
         switch (tok) {
             case INFV_TOKENS_F32: INFV_LAUNCH(ln_tokens_kernel<TokF32>, grid, dim3(256), 0, stream, src, n_vec, d4, st + r0, gamma, beta, dst); break;
@@ -1254,7 +1345,7 @@ __global__ __launch_bounds__(256) void split_transpose_ln_kernel(const void* __r
     }
 }
 
-hipError_t launch_token_pass_ln(const void* F, infv_token_dtype tok, int nb, int n, int d, const void* stats, const float* gamma,
+hipError_t launch_token_pass_ln(const void* F, tok_code tok, int nb, int n, int d, const void* stats, const float* gamma,
                                 const float* beta, void* Fh_, void* Fl_, void* Th_, void* Tl_, hipStream_t stream, float* kbar, int P) {
     if (nb <= 0) return hipSuccess;
     if (n % 32 || d % 64 || nb > 32768) return hipErrorInvalidValue;

@@ -15,7 +15,7 @@ struct infv_vqf_s {
     infv_vqf_config cfg;
     int dev = 0;
     bool exact_fp32 = false;
-    infv_token_dtype tok = INFV_TOKENS_F32;             // element type of the `frames` arguments (infv_vqf_set_token_dtype)
+    tok_code tok = INFV_TOKENS_F32;             // element type of the `frames` arguments (infv_vqf_set_token_dtype)
     // chunk-independent prefix of layer 0 (embedding LayerNorm, self-attention block, cross query, pre-multiplied query):
     // reused across encode_chunk calls while the host keeps the weights epoch unchanged (0 = never reuse)
     unsigned long long epoch = 0, c_epoch = 0;
@@ -110,7 +110,8 @@ int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
 //   -> merged [nb*Q][hidden] = alpha * short-term context + (1 - alpha) * along   (along == nullptr: short-term only)
 // Split-bf16 copies of frame tokens produced ahead of the attention (prepare_split): [.][n_tokens][d] and [.][d][n_tokens]
 // (bf16 tokens: Fh is the caller's buffer itself, Fl and Tl are nullptr -- the contractions then run their two-product form;
-//  fp16 tokens: four planes as for fp32, written by a pass that reads 2 bytes per element)
+//  fp16 tokens: four planes as for fp32, written by a pass that reads 2 bytes per element;
+//  fp8 tokens: Fh and Th written by a pass that reads 1 byte per element, Fl and Tl nullptr -- an e4m3 value is its own hi piece)
 struct SplitRef { const __bf16 *Fh, *Fl, *Th, *Tl; };
 // infv_vqf_encode_videos takes the short-term attention's split-K counts as for this many chunks per sub-batch, whatever the
 // sub-batch holds: a chunk's summation order then does not depend on the rest of the batch
@@ -126,14 +127,19 @@ static bool split_path(const infv_vqf_s* h, int n_tokens) {
 // and every layer's memory share this pass (the reference reads them once per layer and once more for the pooling:
 // Qformer.py:236, 278-291).  `whole` selects the video-sized buffers of the layer-major path.
 // element `elems` of a token buffer of either dtype
-static const void* tok_at(const void* frames, infv_token_dtype tok, long elems) {
+static const void* tok_at(const void* frames, tok_code tok, long elems) {
     return static_cast<const char*>(frames) + elems * (long)token_bytes(tok);
 }
 
-// fp16 / bf16 tokens where the split path does not apply: an fp32 copy in the handle's workspace for today's fp32 kernels
-static int upcast_tokens(infv_vqf_s* h, const void* frames, infv_token_dtype tok, size_t elems, const float** out, hipStream_t stream) {
+// bytes of bf16 planes prepare_split writes per token element, for the plane-cache budget: bf16 tokens 2 (FT_hi alone), fp8 tokens 4
+// (F_hi and FT_hi), fp32 / fp16 tokens and every normalised token (`ln`: a general fp32 number) 8 (all four planes)
+static double plane_bytes(tok_code tok, bool ln) { return ln ? 8.0 : tok == INFV_TOKENS_BF16 ? 2.0 : tok == INFV_TOKENS_F8E4M3 ? 4.0 : 8.0; }
+
+// fp16 / bf16 / fp8 tokens where the split path does not apply: an fp32 copy in the handle's workspace for today's fp32 kernels
+static int upcast_tokens(infv_vqf_s* h, const void* frames, tok_code tok, size_t elems, const float** out, hipStream_t stream) {
     if (elems * sizeof(float) > h->up.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->up.reserve(elems * sizeof(float))); }
     if (tok == INFV_TOKENS_F16) HIP_TRY(launch_upcast_f16(frames, h->up.as<float>(), (long)elems, stream));
+    else if (tok == INFV_TOKENS_F8E4M3) HIP_TRY(launch_upcast_f8(frames, h->up.as<float>(), (long)elems, stream));
     else HIP_TRY(launch_upcast_bf16(frames, h->up.as<float>(), (long)elems, stream));
     *out = h->up.as<float>();
     return INFV_OK;
@@ -147,7 +153,7 @@ struct TokLn { const float* stats; const float* gamma; const float* beta; };
 
 // dst0 / cap: the planes of these nb chunks go to chunks [dst0, dst0 + nb) of buffers reserved for cap chunks (0, 0: [0, nb) of nb);
 // *ref always addresses chunk 0 of the buffers
-static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype tok, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
+static int prepare_split(infv_vqf_s* h, const void* frames_, tok_code tok, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
                          hipStream_t stream, int dst0 = 0, int cap = 0,
                          const TokLn* ln = nullptr /* the planes (and means) of token_ln(frames); ln->stats addresses frames_' first token */) {
     const int d = h->cfg.enc_width;
@@ -166,6 +172,17 @@ static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype to
                                       kbar ? kbar + (size_t)c0 * (n_tokens / P) * d : nullptr, P));
         }
         *ref = SplitRef{fb, nullptr, Th.as<__bf16>(), nullptr};   // (Fh: THESE chunks, whatever dst0 is)
+        return INFV_OK;
+    }
+    if (tok == INFV_TOKENS_F8E4M3 && !ln) {                  // the hi planes alone: an e4m3 value has no lo piece
+        if (szF > Fh.bytes || szF > Th.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(Fh.reserve(szF)); HIP_TRY(Th.reserve(szF)); }
+        for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
+            const int n = nb - c0 < 32768 ? nb - c0 : 32768;
+            const size_t o = (size_t)c0 * n_tokens * d;
+            HIP_TRY(launch_token_pass(tok_at(frames_, tok, (long)o), tok, n, n_tokens, d, Fh.as<__bf16>() + d0 + o, nullptr,
+                                      Th.as<__bf16>() + d0 + o, nullptr, stream, kbar ? kbar + (size_t)c0 * (n_tokens / P) * d : nullptr, P));
+        }
+        *ref = SplitRef{Fh.as<__bf16>(), nullptr, Th.as<__bf16>(), nullptr};
         return INFV_OK;
     }
     if (szF > Fh.bytes || szF > Fl.bytes || szF > Th.bytes || szF > Tl.bytes) {
@@ -188,7 +205,7 @@ static int prepare_split(infv_vqf_s* h, const void* frames_, infv_token_dtype to
     return INFV_OK;
 }
 
-int short_attention(infv_vqf_s* h, const void* frames_, infv_token_dtype tok /* fp16, bf16: only where split_path() holds */, int nb, int n_tokens, const float* xq, bool shared_q,
+int short_attention(infv_vqf_s* h, const void* frames_, tok_code tok /* fp16, bf16: only where split_path() holds */, int nb, int n_tokens, const float* xq, bool shared_q,
                     const infv_linear* key, const infv_linear* value, const float* along, float* merged,
                     hipStream_t stream, bool use_cache = false, const SplitRef* pre = nullptr,
                     hipEvent_t along_ready = nullptr /* `along` is produced on another stream: wait here, before the merge */,
@@ -262,7 +279,7 @@ int short_attention(infv_vqf_s* h, const void* frames_, infv_token_dtype tok /* 
         p.M = rows; p.N = d; p.K = n_tokens; p.k_per_split = kps; p.splitk = sk; p.nbatch = nb; p.wide = inv_nb > 0; p.b_map = t_identity ? nullptr : b_map;
         HIP_TRY(launch_split_gemm(p, stream));
     } else {
-    if (tok != INFV_TOKENS_F32) return fail(INFV_ERR_INVALID, "fp16 / bf16 tokens reached the fp32 contractions");      // (callers upcast first)
+    if (tok != INFV_TOKENS_F32) return fail(INFV_ERR_INVALID, "fp16 / bf16 / fp8 tokens reached the fp32 contractions");      // (callers upcast first)
     const float* frames = static_cast<const float*>(frames_);
     QfGemm g{};                                             // S[b] = qt[b] . frames[b]^T
     g.A = qt; g.lda = d; g.strideA = shared_q ? 0 : (long)rows * d;
@@ -412,7 +429,7 @@ int infv_vqf_set_precision(infv_vqf_handle h, int32_t exact_fp32) {
 int infv_vqf_set_token_dtype(infv_vqf_handle h, int32_t dtype) {
     if (!h) return fail(INFV_ERR_INVALID, "null handle");
     if (!token_dtype_known(dtype)) return fail(INFV_ERR_INVALID, "set_token_dtype: unknown token dtype %d", dtype);
-    h->tok = static_cast<infv_token_dtype>(dtype);
+    h->tok = static_cast<tok_code>(dtype);
     return INFV_OK;
 }
 
@@ -427,8 +444,8 @@ int infv_vqf_short_attention(infv_vqf_handle h, const void* frames, int32_t n_to
                              float* merged, void* stream) {
     if (!h || !frames || !xq || !key || !value || !merged || !key->w || !value->w || !value->b)
         return fail(INFV_ERR_INVALID, "null argument");
-    infv_token_dtype tok = h->tok;
-    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 frames must be 16-byte aligned");
+    tok_code tok = h->tok;
+    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 / fp8 frames must be 16-byte aligned");
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
     if (tok != INFV_TOKENS_F32 && !split_path(h, n_tokens)) {
         const float* f32 = nullptr;
@@ -450,8 +467,8 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
     if (T < 1) return fail(INFV_ERR_INVALID, "T must be >= 1");
     if (llama_out && (c.proj_out <= 0 || !w->llama_proj.w)) return fail(INFV_ERR_INVALID, "llama_out without llama_proj");
     const int Q = c.n_query, Hd = c.hidden, n_tokens = T * c.tokens_per_frame;
-    infv_token_dtype tok = h->tok;
-    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 frames must be 16-byte aligned");
+    tok_code tok = h->tok;
+    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 / fp8 frames must be 16-byte aligned");
     if (use_ltm)
         if (int rc = ensure_streams(h)) return rc;
     if (tok != INFV_TOKENS_F32 && !split_path(h, n_tokens)) {  // today's fp32 kernels from an fp32 copy
@@ -606,8 +623,8 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     if (use_ltm && !ltm) return fail(INFV_ERR_INVALID, "alpha != 1 needs the per-layer LTM handles");
     if (T < 1) return fail(INFV_ERR_INVALID, "T must be >= 1");
     if ((llama_out || llama_mean) && (c.proj_out <= 0 || !w->llama_proj.w)) return fail(INFV_ERR_INVALID, "llama output without llama_proj");
-    infv_token_dtype tok = h->tok;
-    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 frames must be 16-byte aligned");
+    tok_code tok = h->tok;
+    if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 / fp8 frames must be 16-byte aligned");
     if (int rc = ensure_streams(h)) return rc;
     const int Q = c.n_query, Hd = c.hidden, C = n_chunks, S = c.nb_samples;
     const int n_tokens = T * c.tokens_per_frame;
@@ -650,7 +667,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     SplitRef wref{}; bool have_w = false, have_kbar = false;
     {
         const double budget_gb = h->split_cache_gb;
-        const double need_gb = (tok == INFV_TOKENS_BF16 ? 1.0 : 4.0) * (double)C * (double)chunk_k * 2.0 / 1e9;   // (bf16 tokens: only FT_hi is written; fp16: four planes, as fp32)
+        const double need_gb = plane_bytes(tok, false) * (double)C * (double)chunk_k / 1e9;
         if (h->fuse && split_path(h, n_tokens) && need_gb <= budget_gb) {
             have_kbar = use_ltm && 64 % c.tokens_per_frame == 0;
             if (int rc = prepare_split(h, frames, tok, C, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream)) return rc;
@@ -909,8 +926,10 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     if (emb && hidden_in) return fail(INFV_ERR_INVALID, "%s: the embedding layer and hidden_in are both given (one of them writes the input rows)", name);
     const bool tok_arg = token_dtype >= 0;                     // the dtype is an argument of the call: the handle's setting is not read
     if (tok_arg && !token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "%s: unknown token dtype %d", name, token_dtype);
-    infv_token_dtype tok = tok_arg ? static_cast<infv_token_dtype>(token_dtype) : INFV_TOKENS_F32;
-    if (tok != INFV_TOKENS_F32 && frames && !aligned16(frames)) return fail(INFV_ERR_INVALID, "%s: fp16 / bf16 frames must be 16-byte aligned", name);
+    tok_code tok = tok_arg ? static_cast<tok_code>(token_dtype) : INFV_TOKENS_F32;
+    // (the vision LayerNorm of fp8 tokens is not built: no vision encoder emits fp8)
+    if (vis_ln && tok == INFV_TOKENS_F8E4M3) return fail(INFV_ERR_UNSUPPORTED, "%s: no vision LayerNorm of fp8 frame tokens", name);
+    if (tok != INFV_TOKENS_F32 && frames && !aligned16(frames)) return fail(INFV_ERR_INVALID, "%s: fp16 / bf16 / fp8 frames must be 16-byte aligned", name);
     if (vis_ln && frames && !aligned16(frames)) return fail(INFV_ERR_INVALID, "%s: frames must be 16-byte aligned for the vision LayerNorm", name);
     if (V == 0) return INFV_OK;
     const infv_vqf_config& c = h->cfg;
@@ -1081,7 +1100,7 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     SplitRef wref{}; bool have_w = false, have_kbar = false;
     if (n_cross > 0) {
         // (streams: the distinct chunks only; bf16 tokens: only the transposed plane is written, as in infv_vqf_encode_video)
-        const double need_gb = (tok == INFV_TOKENS_BF16 && !ln ? 1.0 : 4.0) * (double)Cf * (double)chunk_k * 2.0 / 1e9;   // (normalised tokens: four planes)
+        const double need_gb = plane_bytes(tok, ln != nullptr) * (double)Cf * (double)chunk_k / 1e9;
         if (h->fuse && split_path(h, n_tokens) && need_gb <= h->split_cache_gb) {
             have_kbar = use_ltm && token_pass_gives_means(c.tokens_per_frame);   // (where a frame divides the 64-token tile)
             if (int rc = prepare_split(h, frames, tok, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream, 0, 0, ln)) return rc;
@@ -1316,6 +1335,7 @@ int infv_vqf_layernorm_tokens(const void* frames, int32_t token_dtype, int64_t n
                               float eps, float* out_f32, void* stream_) {
     // ---- every refusal before any launch ----
     if (!token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "layernorm_tokens: unknown token dtype %d", token_dtype);
+    if (token_dtype == INFV_TOKENS_F8E4M3) return fail(INFV_ERR_UNSUPPORTED, "layernorm_tokens: no vision LayerNorm of fp8 frame tokens");
     if (!frames || !gamma || !beta || !out_f32 || n_rows < 0) return fail(INFV_ERR_INVALID, "layernorm_tokens: bad arguments");
     if (d < 64 || d % 64) return fail(INFV_ERR_INVALID, "layernorm_tokens: d must be a positive multiple of 64");
     if (d > kTokenLnMaxWidth) return fail(INFV_ERR_UNSUPPORTED, "layernorm_tokens: d = %d, at most %d is supported", d, kTokenLnMaxWidth);
@@ -1332,7 +1352,7 @@ int infv_vqf_layernorm_tokens(const void* frames, int32_t token_dtype, int64_t n
     if ((size_t)n_rows * 2 * sizeof(float) > stats->bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(stats->reserve((size_t)n_rows * 2 * sizeof(float))); }
     if (!last_read) HIP_TRY(hipEventCreateWithFlags(&last_read, hipEventDisableTiming));
     else HIP_TRY(hipStreamWaitEvent(stream, last_read, 0));
-    const infv_token_dtype tok = static_cast<infv_token_dtype>(token_dtype);
+    const tok_code tok = static_cast<tok_code>(token_dtype);
     HIP_TRY(launch_token_ln_stats(frames, tok, (long)n_rows, d, eps, stats->p, stream));
     HIP_TRY(launch_ln_tokens(frames, tok, (long)n_rows, d, stats->p, gamma, beta, out_f32, stream));
     HIP_TRY(hipEventRecord(last_read, stream));
@@ -1358,10 +1378,11 @@ int infv_vqf_token_pass(const void* frames, int32_t token_dtype, int32_t nb, int
                         void* Fh, void* Fl, void* Th, void* Tl, float* kbar, void* stream) {
     // ---- every refusal before any launch ----
     if (!token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "token_pass: unknown token dtype %d", token_dtype);
-    const infv_token_dtype tok = static_cast<infv_token_dtype>(token_dtype);
+    const tok_code tok = static_cast<tok_code>(token_dtype);
     if (!frames || !Th || nb < 0) return fail(INFV_ERR_INVALID, "token_pass: bad arguments");
-    if (tok == INFV_TOKENS_BF16 ? (Fh || Fl || Tl) : (!Fh || !Fl || !Tl))
-        return fail(INFV_ERR_INVALID, "token_pass: bf16 tokens take Th alone (Fh, Fl, Tl NULL), fp32 / fp16 tokens all four planes");
+    if (tok == INFV_TOKENS_BF16 ? (Fh || Fl || Tl) : tok == INFV_TOKENS_F8E4M3 ? (!Fh || Fl || Tl) : (!Fh || !Fl || !Tl))
+        return fail(INFV_ERR_INVALID, "token_pass: bf16 tokens take Th alone (Fh, Fl, Tl NULL), fp8 tokens Fh and Th (Fl, Tl NULL), "
+                                      "fp32 / fp16 tokens all four planes");
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "token_pass: n_tokens must be a positive multiple of 32");
     if (d < 64 || d % 64) return fail(INFV_ERR_INVALID, "token_pass: d must be a positive multiple of 64");
     if (!aligned16(frames) || !aligned16(Fh) || !aligned16(Fl) || !aligned16(Th) || !aligned16(Tl))

@@ -1,7 +1,7 @@
 // Internal interface between the video Q-former C ABI (vqf_capi.hip) and its gfx950 kernels (vqf_kernels.hip).
 #pragma once
 #include "knobs.h"
-#include "../../include/infv_ltm.h"      // infv_token_dtype
+#include "../../include/infv_ltm.h"      // tok_code
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -127,22 +127,29 @@ hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void*
                                       float* kbar = nullptr, int P = 0);
 // x [n] fp16 -> y [n] fp32 (exact), n % 8 == 0
 hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream);
-// the token pass of nb <= 32768 chunks for any token type (bf16: only Th is written); kbar needs token_pass_gives_means(P)
+// F [nb][n][d] fp8 e4m3 -> Fh [nb][n][d] and Th [nb][d][n] (bf16: an e4m3 value is its own hi piece, the lo planes do not exist) and, with kbar,
+// the frame means
+hipError_t launch_split_transpose_f8(const void* F, int nb, int n, int d, void* Fh, void* Th, hipStream_t stream, float* kbar = nullptr, int P = 0);
+// x [n] fp8 e4m3 -> y [n] fp32 (exact), n % 16 == 0
+hipError_t launch_upcast_f8(const void* x, float* y, long n, hipStream_t stream);
+// bytes per element of a token type
+inline size_t token_bytes(tok_code tok) { return tok == INFV_TOKENS_F32 ? 4 : tok == INFV_TOKENS_F8E4M3 ? 1 : 2; }
+// the token pass of nb <= 32768 chunks for any token type (bf16: only Th is written; fp8: Fh and Th); kbar needs token_pass_gives_means(P)
 bool token_pass_gives_means(int P);
-hipError_t launch_token_pass(const void* F, infv_token_dtype tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
+hipError_t launch_token_pass(const void* F, tok_code tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
                              hipStream_t stream, float* kbar, int P);
 // ---- vision LayerNorm of the frame tokens (videochat2_it_mistral.py:195), y = token_ln(x) of ltm_device.h ----
 constexpr int kTokenLnMaxWidth = 4096;   // a token row is held in one wave's registers: 16 float4 per lane
 // stats[row] = (mean, 1 / sqrt(var + eps)) of n_rows token rows of width d (d % 64 == 0, d <= kTokenLnMaxWidth); stats: float2
-hipError_t launch_token_ln_stats(const void* F, infv_token_dtype tok, long n_rows, int d, float eps, void* stats, hipStream_t stream);
+hipError_t launch_token_ln_stats(const void* F, tok_code tok, long n_rows, int d, float eps, void* stats, hipStream_t stream);
 // y [n_rows][d] fp32 = token_ln(F): the reference form of the bits, and the operand of the fp32 contractions
-hipError_t launch_ln_tokens(const void* F, infv_token_dtype tok, long n_rows, int d, const void* stats, const float* gamma, const float* beta,
+hipError_t launch_ln_tokens(const void* F, tok_code tok, long n_rows, int d, const void* stats, const float* gamma, const float* beta,
                             float* y, hipStream_t stream);
 // launch_token_pass over y = token_ln(F) applied on load: all four planes for every token type, kbar as there
-hipError_t launch_token_pass_ln(const void* F, infv_token_dtype tok, int nb, int n, int d, const void* stats, const float* gamma,
+hipError_t launch_token_pass_ln(const void* F, tok_code tok, int nb, int n, int d, const void* stats, const float* gamma,
                                 const float* beta, void* Fh, void* Fl, void* Th, void* Tl, hipStream_t stream, float* kbar, int P);
 // launch_pool (ltm_kernels.hip) over y = token_ln(k) applied on load: the bits of launch_pool on ln_tokens_kernel's tensor
-hipError_t launch_pool_ln(const void* k, infv_token_dtype tok, const void* stats, const float* gamma, const float* beta, float* kbar,
+hipError_t launch_pool_ln(const void* k, tok_code tok, const void* stats, const float* gamma, const float* beta, float* kbar,
                           int64_t n_frames, int P, int d, hipStream_t stream);
 // The VideoChat2 embedding layer (Qformer.py:54-111): out row m = LN(query_tokens[-src[m] - 1]) where src[m] < 0, else
 // LN(word[src[m]] + position[pos[m]]); src / pos: DEVICE int32 [n_rows], validated on the host; width <= 4096

@@ -34,6 +34,30 @@ def _np_f32(a):
 
 
 TOKEN_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 3}      # infv_token_dtype (2 is not a code)
+# INFV_TOKENS_F8E4M3, declared beside the enum: OCP e4m3fn, one byte per element, the caller's storage choice (e.g.
+# ``tokens.to(torch.float8_e4m3fn)`` when caching features).  The library neither quantises nor scales: its results on the fp8 tensor
+# are the bits of its results on ``tensor.float()``.
+F8_TOKEN_DTYPES = {torch.float8_e4m3fn: 4}
+_OTHER_FP8 = tuple(getattr(torch, n) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+
+
+def token_code(dtype) -> Optional[int]:
+    """The token dtype code the kernels read ``dtype`` under (``TOKEN_DTYPES`` and ``F8_TOKEN_DTYPES``), or None for a dtype
+    they do not read in place.  The fp8 encodings other than OCP e4m3fn raise: silently widening them would hide that the one-byte
+    layout the kernels read is ``torch.float8_e4m3fn`` alone."""
+    if dtype in _OTHER_FP8:
+        raise TypeError(f"fp8 frame tokens must be torch.float8_e4m3fn (OCP e4m3, no scale), got {dtype}")
+    code = TOKEN_DTYPES.get(dtype)
+    return F8_TOKEN_DTYPES.get(dtype) if code is None else code
+
+
+def aligned_tokens(k: torch.Tensor) -> torch.Tensor:
+    """``k`` itself where the kernels can read it in place, else a contiguous, 16-byte aligned copy in its own dtype."""
+    if not k.is_contiguous() or k.data_ptr() % 16:
+        k = k.clone(memory_format=torch.contiguous_format)
+        if k.data_ptr() % 16:                       # (an allocator that hands out less than 16-byte alignment: none known)
+            raise RuntimeError("could not allocate a 16-byte aligned copy of the frame tokens")
+    return k
 
 
 def _check_dev(t: torch.Tensor, device: torch.device, name: str, dtype=torch.float32):
@@ -244,19 +268,24 @@ class LTMEngine:
     def _tokens(self, k: torch.Tensor):
         """Frame tokens may be fp32 (the reference's layout), fp16 (what its fp16 producer holds: read at half the bytes, same
         bits as the fp32 run) or bf16 (a producer that rounds them): tell the handle which one this call passes."""
-        if k.dtype not in TOKEN_DTYPES or (k.dtype == torch.float16 and not self.fp16_tokens):
-            raise TypeError(f"frame tokens must be float32 or bfloat16 (float16 on an engine created with fp16_tokens=True), got {k.dtype}")
+        code = token_code(k.dtype)
+        if code is None or (k.dtype == torch.float16 and not self.fp16_tokens):
+            raise TypeError("frame tokens must be float32, bfloat16 or float8_e4m3fn (float16 on an engine created with "
+                            f"fp16_tokens=True), got {k.dtype}")
+        if code == 4 and k.device == self.device:   # fp8 is read in 4-byte vectors: a view off a 16-byte boundary is copied, in fp8
+            k = aligned_tokens(k)
         _check_dev(k, self.device, "k", k.dtype)
         # always: the dtype is sticky state of the handle and other users of the handle (the video Q-former's C path) set it
         # too, so a Python-side cache of it could go stale
-        _lib.check(self.lib.infv_ltm_set_token_dtype(self._h, TOKEN_DTYPES[k.dtype]))
+        _lib.check(self.lib.infv_ltm_set_token_dtype(self._h, code))
         self._token_dtype = k.dtype
-        self._token_code = TOKEN_DTYPES[k.dtype]
+        self._token_code = code
+        return k
 
     # ------------------------------------------------------------------ operators
     def pool(self, k: torch.Tensor) -> torch.Tensor:
-        """k [..., T*P, d] (fp32 or bf16; fp16 on an engine with fp16_tokens=True) -> frame means [..., T, d] fp32   (reference :304)."""
-        self._tokens(k)
+        """k [..., T*P, d] (fp32, bf16 or fp8 e4m3; fp16 on an engine with fp16_tokens=True) -> frame means [..., T, d] fp32   (reference :304)."""
+        k = self._tokens(k)
         if k.shape[-1] != self.d or k.shape[-2] % self.P:
             raise ValueError(f"k must be [..., T*{self.P}, {self.d}], got {tuple(k.shape)}")
         n_frames = k.numel() // (self.P * self.d)
@@ -266,9 +295,9 @@ class LTMEngine:
         return out
 
     def pool_rows(self, k: torch.Tensor) -> torch.Tensor:
-        """k [C, T*P, d] (fp32 or bf16; fp16 with fp16_tokens=True) -> the memory's new rows R [C, rows, d] fp32: frame means (reference :304) summed
+        """k [C, T*P, d] (fp32, bf16 or fp8 e4m3; fp16 with fp16_tokens=True) -> the memory's new rows R [C, rows, d] fp32: frame means (reference :304) summed
         per box row with the operator's weights (reference :216), one pass over the tokens.  Sparse plans only."""
-        self._tokens(k)
+        k = self._tokens(k)
         if k.dim() != 3 or k.shape[-1] != self.d or k.shape[-2] % self.P:
             raise ValueError(f"k must be [C, T*{self.P}, {self.d}], got {tuple(k.shape)}")
         n_chunks, T = int(k.shape[0]), int(k.shape[1]) // self.P
@@ -296,7 +325,7 @@ class LTMEngine:
     # -- lean entry points of the drop-in module's per-call path: the caller has validated shapes / dtypes / devices once for
     #    this call signature; nothing is re-checked here, no context manager is entered (the caller's device is current)
     def pool_into(self, k: torch.Tensor, kbar: torch.Tensor, n_frames: int, token_code: int, stream: C.c_void_p):
-        # (``token_code``: any infv_token_dtype -- 0 fp32, 1 bf16, 3 fp16; the caller vouches for it, ``fp16_tokens`` does not gate it)
+        # (``token_code``: any token dtype code -- 0 fp32, 1 bf16, 3 fp16, 4 fp8 e4m3; the caller vouches for it, ``fp16_tokens`` does not gate it)
         # the token dtype is sticky state of the C handle and other callers of the same handle change it (the video
         # Q-former's C path forces fp32): always set it, one cheap host call, never trust a Python-side cache
         _lib.check(self.lib.infv_ltm_set_token_dtype(self._h, token_code))
@@ -313,7 +342,7 @@ class LTMEngine:
 
     def forward_into_raw(self, k_ptr: int, token_code: int, T: int, kbar_ptr: int, q_ptr: int, Q: int, proj_arr, u_ptr: int,
                          ctx_ptr: int, stream: C.c_void_p):
-        """infv_ltm_forward_into on raw addresses (``token_code``: 0 fp32, 1 bf16, 3 fp16; not gated by ``fp16_tokens``): set the token dtype, pool k into the caller's kbar, step from it -- ONE C call
+        """infv_ltm_forward_into on raw addresses (``token_code``: 0 fp32, 1 bf16, 3 fp16, 4 fp8 e4m3; not gated by ``fp16_tokens``): set the token dtype, pool k into the caller's kbar, step from it -- ONE C call
         (the drop-in module's steady-state forward; ``pool_into`` + ``step_raw`` were three)."""
         rc = self.lib.infv_ltm_forward_into(self._h, C.c_void_p(k_ptr), token_code, T, C.c_void_p(kbar_ptr), C.c_void_p(q_ptr), Q,
                                             proj_arr, C.c_void_p(u_ptr) if u_ptr else None, C.c_void_p(ctx_ptr), stream)
@@ -323,7 +352,7 @@ class LTMEngine:
     def forward(self, k: torch.Tensor, q: torch.Tensor, projs: Sequence[ProjTensors],
                 u: Optional[torch.Tensor] = None, new_doc: bool = False) -> torch.Tensor:
         """LongTermAttention.forward for all layers: k [T*P, d], q [L, Q, dm] -> ctx [L, Q, dm]."""
-        self._tokens(k)
+        k = self._tokens(k)
         if k.dim() != 2 or k.shape[1] != self.d or k.shape[0] % self.P:
             raise ValueError(f"k must be [T*{self.P}, {self.d}], got {tuple(k.shape)}")
         T = k.shape[0] // self.P
@@ -339,8 +368,8 @@ class LTMEngine:
     def consolidate(self, k: torch.Tensor, q: torch.Tensor, projs: Sequence[ProjTensors],
                     u: Optional[torch.Tensor] = None, new_doc: bool = True,
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Whole-video loop: k [C, T*P, d] (fp32 or bf16; fp16 with fp16_tokens=True), q [L, Q, dm], u [C, L, S] -> ctx [C, L, Q, dm]."""
-        self._tokens(k)
+        """Whole-video loop: k [C, T*P, d] (fp32, bf16 or fp8 e4m3; fp16 with fp16_tokens=True), q [L, Q, dm], u [C, L, S] -> ctx [C, L, Q, dm]."""
+        k = self._tokens(k)
         if k.dim() != 3 or k.shape[2] != self.d or k.shape[1] % self.P:
             raise ValueError(f"k must be [C, T*{self.P}, {self.d}], got {tuple(k.shape)}")
         Cn, T = int(k.shape[0]), k.shape[1] // self.P
@@ -378,7 +407,7 @@ class LTMEngine:
         """Whole-video loop with a DIFFERENT query per chunk (a cross-attention layer after the first, Qformer.py:211):
         k [C, T*P, d], q [C, L, Q, dm], u [C, L, S] -> ctx [C, L, Q, dm].  Pooling and new-row projections are batched,
         the memory chain runs chunk by chunk; equals C calls of forward()."""
-        self._tokens(k)
+        k = self._tokens(k)
         if k.dim() != 3 or k.shape[2] != self.d or k.shape[1] % self.P:
             raise ValueError(f"k must be [C, T*{self.P}, {self.d}], got {tuple(k.shape)}")
         Cn, T = int(k.shape[0]), k.shape[1] // self.P
@@ -559,7 +588,7 @@ def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.T
                        u=None, new_doc: bool = True) -> torch.Tensor:
     """Step V independent videos together (infv_ltm_consolidate_videos): engine v holds video v's memory.
 
-    ``k`` is PACKED, [sum C_v, T*P, d] (fp32 or bf16; fp16 if every engine has fp16_tokens=True) with video v's chunks at rows [cu[v], cu[v+1]) where cu is the running
+    ``k`` is PACKED, [sum C_v, T*P, d] (fp32, bf16 or fp8 e4m3; fp16 if every engine has fp16_tokens=True) with video v's chunks at rows [cu[v], cu[v+1]) where cu is the running
     sum of ``chunk_counts`` (a list or 1-D tensor), and ``u`` likewise [sum C_v, L, S] float64 (None when not sticky).
     ``k`` (and ``u``) may also be lists of per-video [C_v, T*P, d] ([C_v, L, S]) tensors: they are then packed, which COPIES
     every video's tokens once.  ``q`` [L, Q, dm] and ``projs`` are shared by all videos.  new_doc=True starts every memory
@@ -574,8 +603,8 @@ def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.T
         u = torch.cat(list(u))
     V, e0 = len(engines), engines[0]
     total = int(cu[-1])
-    if k.dtype not in TOKEN_DTYPES:
-        raise TypeError(f"frame tokens must be float32, float16 or bfloat16, got {k.dtype}")
+    if token_code(k.dtype) is None:
+        raise TypeError(f"frame tokens must be float32, float16, bfloat16 or float8_e4m3fn, got {k.dtype}")
     if k.dtype == torch.float16 and not all(e.fp16_tokens for e in engines):   # (before any handle's dtype is touched)
         raise TypeError("float16 frame tokens need engines created with fp16_tokens=True")
     _check_dev(k, e0.device, "k", k.dtype)
@@ -585,7 +614,7 @@ def consolidate_videos(engines: Sequence[LTMEngine], k, chunk_counts, q: torch.T
     Q = e0._check_q(q)
     e0._check_u(u, (total,))
     for e in engines:
-        e._tokens(k)
+        k = e._tokens(k)                               # (a misaligned fp8 view is copied once: the copy is aligned for the rest)
         e.ensure_plan(T)
         e._check_q(q)
     proj_arr = e0._proj_array(projs)

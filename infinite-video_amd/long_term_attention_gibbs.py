@@ -31,7 +31,7 @@ import torch.nn as nn
 from .basis_maps import NB_SAMPLES
 import ctypes as C
 
-from .engine import TOKEN_DTYPES, LTMEngine
+from .engine import LTMEngine, aligned_tokens, token_code
 
 # raw current-stream handle / current device index: torch's C bindings when present (torch >= 1.10), the public API otherwise
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda i: torch.cuda.current_stream(i).cuda_stream)
@@ -307,18 +307,21 @@ class LongTermAttention(nn.Module):
                 eng.step_raw(kbar.data_ptr(), klen, qf.data_ptr(), qlen, proj_arr, u_addr, ctx.data_ptr(), stream)
         else:
             kf = k
-            if kf.dtype not in TOKEN_DTYPES:                      # fp16 and bf16 tokens are pooled as they are
-                kf = kf.float()
+            code = token_code(kf.dtype)
+            if code is None:                                      # fp16, bf16 and fp8 e4m3fn tokens are pooled as they are
+                kf, code = kf.float(), 0
             if not kf.is_contiguous():
                 kf = kf.contiguous()
+            if code == 4:                                         # (fp8: 16-byte aligned, as the ABI asks)
+                kf = aligned_tokens(kf)
             kbar = torch.empty(klen, self.encoder_width, device=k.device, dtype=torch.float32)
             # pool (:304) + step (:306-346) behind ONE C call
             if other_device:
                 with torch.cuda.device(k.device):
-                    eng.forward_into_raw(kf.data_ptr(), TOKEN_DTYPES[kf.dtype], klen, kbar.data_ptr(), qf.data_ptr(), qlen, proj_arr,
+                    eng.forward_into_raw(kf.data_ptr(), code, klen, kbar.data_ptr(), qf.data_ptr(), qlen, proj_arr,
                                          u_addr, ctx.data_ptr(), stream)
             else:
-                eng.forward_into_raw(kf.data_ptr(), TOKEN_DTYPES[kf.dtype], klen, kbar.data_ptr(), qf.data_ptr(), qlen, proj_arr,
+                eng.forward_into_raw(kf.data_ptr(), code, klen, kbar.data_ptr(), qf.data_ptr(), qlen, proj_arr,
                                      u_addr, ctx.data_ptr(), stream)
             _pool_cache["ref"], _pool_cache["version"], _pool_cache["kbar"] = weakref.ref(k), k._version, kbar
         if sticky_step:

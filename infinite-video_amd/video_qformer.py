@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import _lib
 from .basis_maps import NB_SAMPLES
-from .engine import TOKEN_DTYPES
+from .engine import TOKEN_DTYPES, aligned_tokens, token_code
 from .qformer_hook import build_long_term_attention
 
 
@@ -164,12 +164,16 @@ class ShortMemoryBuffer:
 
     ``dtype=torch.float16`` is for a producer that holds fp16 (the reference's ViT and image Q-former run in fp16): the same
     half-size buffer, read in place by the same entry points, and nothing is rounded -- every result is bit for bit the run on
-    ``tokens.float()``."""
+    ``tokens.float()``.
+
+    ``dtype=torch.float8_e4m3fn`` stores one byte per element (OCP e4m3, no scale factor): a storage choice of the caller's,
+    whose accuracy the library does not judge -- ``replace`` rounds what it is given as ``.to(torch.float8_e4m3fn)`` does.  The
+    same entry points read the buffer in place, and every result is bit for bit the run on ``frames().float()``."""
 
     def __init__(self, tokens_per_frame: int, width: int, capacity_frames: int = 2049, dtype=torch.float32,
                  device=None):
-        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError("ShortMemoryBuffer holds float32, float16 or bfloat16 tokens")
+        if token_code(dtype) is None:                                    # (an fp8 encoding other than e4m3fn raises there)
+            raise TypeError("ShortMemoryBuffer holds float32, float16, bfloat16 or float8_e4m3fn tokens")
         self.P, self.d = int(tokens_per_frame), int(width)
         self.store = torch.empty(int(capacity_frames), self.P, self.d, dtype=dtype, device=device)
         self.n = 0
@@ -211,14 +215,13 @@ def _dev_f32(t: torch.Tensor, device: torch.device) -> torch.Tensor:
 
 
 def _dev_tokens(t: torch.Tensor, device: torch.device):
-    """Frame tokens for the C ABI: (tensor, infv_token_dtype).  Contiguous fp16 / bf16 tokens on the device pass through
-    untouched (16-byte aligned, as the ABI asks; a misaligned view is copied, in its own dtype); everything else becomes fp32
-    as before."""
+    """Frame tokens for the C ABI: (tensor, token dtype code).  Contiguous fp16 / bf16 / fp8 e4m3fn tokens on the device pass
+    through untouched (16-byte aligned, as the ABI asks; a misaligned view is copied, in its own dtype); everything else becomes
+    fp32 as before (the other fp8 encodings raise TypeError)."""
     t = t.detach()
-    if t.dtype in (torch.bfloat16, torch.float16) and t.device == device:
-        if not t.is_contiguous() or t.data_ptr() % 16:
-            t = t.clone(memory_format=torch.contiguous_format)
-        return t, TOKEN_DTYPES[t.dtype]
+    code = token_code(t.dtype)
+    if code and t.device == device:
+        return aligned_tokens(t), code
     return _dev_f32(t, device), 0
 
 

@@ -43,6 +43,7 @@ import torch.nn.functional as F
 from . import _lib
 from .basis_maps import NB_SAMPLES
 from .qformer_hook import LongTermMemoryHook
+from .engine import token_code
 from .video_qformer import TOKEN_DTYPES, VideoMemory, _cumsum, _dev_f32, draw_video_uniforms
 
 MAX_TXT_LEN = 512              # max_txt_len of the instruction (configs/config_mistral.json)
@@ -650,9 +651,11 @@ class VideoChat2Encoder(nn.Module):
         if total == 0 and not (use_ltm and new_video):
             return (torch.empty(0, Q, llm, device=device), torch.full((V, Q, llm), float("nan"), device=device),
                     [torch.empty(0, Q + n, cfg.hidden_size, device=device) for n in text_len] if want_hidden else None)
-        # fp16 / bf16 tokens (every block of one such type) are read in place by the _tok entry points: no fp32 copy, no cat of one
-        # block, a clone only where a view is not contiguous or not 16-byte aligned; anything else goes in as fp32, as before
-        half = videos[0].dtype if videos[0].dtype in (torch.float16, torch.bfloat16) and \
+        # fp16 / bf16 / fp8 e4m3fn tokens (every block of one such type) are read in place by the _tok entry points: no fp32 copy, no
+        # cat of one block, a clone only where a view is not contiguous or not 16-byte aligned; anything else goes in as fp32, as
+        # before (an fp8 encoding other than e4m3fn raises TypeError)
+        codes = [token_code(f.dtype) for f in videos]
+        half = videos[0].dtype if codes[0] and \
             all(f.dtype == videos[0].dtype and f.device == device for f in videos) else None
         if half is None:
             frames = _dev_f32(torch.cat(videos) if F > 1 else videos[0], device)
@@ -662,7 +665,7 @@ class VideoChat2Encoder(nn.Module):
             frames = torch.cat(videos) if F > 1 else videos[0].detach()
             if not frames.is_contiguous() or frames.data_ptr() % 16:
                 frames = frames.clone(memory_format=torch.contiguous_format)
-        tok = () if half is None else (TOKEN_DTYPES[half],)      # the argument the _tok entry points take behind `frames`
+        tok = () if half is None else (token_code(half),)      # the argument the _tok entry points take behind `frames`
         lib = _lib.load()
         hin = torch.cat([_dev_f32(r, device) for r in rows]).contiguous() if rows is not None else None
         handles = None
@@ -703,7 +706,7 @@ class VideoChat2Encoder(nn.Module):
             with torch.cuda.device(device):
                 _lib.check(lib.infv_vqf_vc_encode_img(
                     self._vc_handle(device), handles, V, C.cast(cu, C.c_void_p), C.c_void_p(frames.data_ptr()),
-                    TOKEN_DTYPES[frames.dtype], F, C.cast(fcu, C.c_void_p), C.cast(src, C.c_void_p) if streams else None, T,
+                    token_code(frames.dtype), F, C.cast(fcu, C.c_void_p), C.cast(src, C.c_void_p) if streams else None, T,
                     C.byref(w), C.byref(front), C.c_void_p(0 if hin is None else hin.data_ptr()), C.cast(tl, C.c_void_p),
                     C.c_void_p(0 if u is None else u.data_ptr()), int(bool(new_video)),
                     C.c_void_p(0 if hidden is None else hidden.data_ptr()), C.c_void_p(proj.data_ptr()), C.c_void_p(mean.data_ptr()),

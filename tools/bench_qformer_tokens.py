@@ -14,6 +14,11 @@ One configuration per process; one JSON line appended to profiles/vqf_bf16_token
 then the three-product contractions of leg a), c is "fp16 tokens cast to fp32 first", what a user of fp16 tokens did before.
 The counts from the shapes then are: token pass 2 + 8 bytes per element, contractions as for fp32 tokens.
 
+--dtype float8_e4m3fn runs legs b and c on fp8 e4m3 tokens (the caller's storage choice): b reads them in place (INFV_TOKENS_F8E4M3:
+one token pass at 1 byte per element that writes the two hi planes, then the two-product contractions of bf16 tokens), c is "fp8
+tokens cast to fp32 first".  Counts: token pass 1 + 4 bytes per element, contractions as for bf16 tokens.  Quote it next to a
+--dtype bfloat16 line of the same run (profiles/vqf_f8_tokens.jsonl holds both).
+
 --legs a times leg (a) only and touches nothing of the bf16 interface (the same script then runs against a build of an earlier
 commit: the fp32 path before / after).  Bytes and bf16-MFMA FLOP per chunk are computed from the shapes, so that the
 achieved rates stand next to the counts."""
@@ -47,7 +52,8 @@ def counts_from_shapes():
     bf16 = {"token_pass_bytes": elems * (2 + 2), "contraction_token_bytes": L * 2 * elems * 2,
             "mfma_flop": L * 2 * 2 * 2 * rows * n * D}
     f16 = dict(f32, token_pass_bytes=elems * (2 + 8))
-    return {"fp32_tokens": f32, "bf16_tokens": bf16, "fp16_tokens": f16}
+    f8 = dict(bf16, token_pass_bytes=elems * (1 + 4))
+    return {"fp32_tokens": f32, "bf16_tokens": bf16, "fp16_tokens": f16, "fp8_tokens": f8}
 
 
 def main():
@@ -55,7 +61,7 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), required=True)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--legs", default="abc", choices=["abc", "a", "b"])
-    ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float16"], help="the half format of legs b and c")
+    ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float16", "float8_e4m3fn"], help="the token format of legs b and c")
     ap.add_argument("--tag", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vqf_bf16_tokens.jsonl"))
     a = ap.parse_args()
@@ -71,11 +77,13 @@ def main():
     m = m.to(dev)
     gen = torch.Generator(device=dev).manual_seed(1)
     half = getattr(torch, a.dtype)
-    short = "bf16" if half == torch.bfloat16 else "fp16"
+    short = {torch.bfloat16: "bf16", torch.float16: "fp16", torch.float8_e4m3fn: "fp8"}[half]
     x = torch.empty(total, T * P, D, device=dev, dtype=half)
     for c0 in range(0, total, 32):                                 # (no fp32 tensor of the whole video beside the two below)
         x[c0:c0 + 32] = torch.randn(min(32, total - c0), T * P, D, device=dev, generator=gen).to(half)
     x32 = x.float() if a.legs != "b" else None
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(dev)[0]
     u = torch.rand(total, L, 512, dtype=torch.float64, generator=torch.Generator().manual_seed(2)).to(dev)
     mems = [VideoMemory(m, dev) for _ in range(V)] if entry == "encode_videos" else None
     lib = _lib.load()
@@ -93,9 +101,11 @@ def main():
     legs = {"a": lambda: call(x32), "b": lambda: call(x), "c": lambda: call(x.float())}
     legs = {k: v for k, v in legs.items() if k in a.legs}
     launches, peak, outs = {}, {}, {}
+    first_call = {}
     for k, fn in legs.items():                                      # warm-up of every leg: workspaces, plans, allocator
         fn()
         torch.cuda.synchronize()
+        first_call[k] = int(free0 - torch.cuda.mem_get_info(dev)[0])   # free device memory taken so far (legs run in order a, b, c)
         torch.cuda.reset_peak_memory_stats(dev)
         base = torch.cuda.memory_allocated(dev)
         n0 = lib.infv_ltm_launch_count()
@@ -114,13 +124,14 @@ def main():
             ms[k].append(e0.elapsed_time(e1))
     line = {"config": a.config, "entry": entry, "videos": V, "chunks": total, "T": T, "N": 256, "Q": Q, "layers": L, "alpha": 0.9,
             "llama": 4096, "rounds": a.rounds, "legs": a.legs, "tag": a.tag, "library": os.path.basename(_lib.LIB_PATH),
-            "half_dtype": a.dtype, "tokens_bytes_bf16" if short == "bf16" else "tokens_bytes_fp16": x.numel() * 2, "counts_per_chunk_from_shapes": counts_from_shapes()}
+            "half_dtype": a.dtype, f"tokens_bytes_{short}": x.numel() * x.element_size(), "counts_per_chunk_from_shapes": counts_from_shapes()}
     names = {"a": "fp32_tokens", "b": f"{short}_tokens_native", "c": f"{short}_tokens_upcast_in_window"}
     for k in legs:
         med = statistics.median(ms[k])
         line[names[k]] = {"median_ms": round(med, 3), "min_ms": round(min(ms[k]), 3), "max_ms": round(max(ms[k]), 3),
                           "chunks_per_s": round(total / med * 1e3, 1), "ms_per_chunk": round(med / total, 4),
-                          "launches_per_call": launches[k], "torch_peak_rise_bytes": peak[k]}
+                          "launches_per_call": launches[k], "torch_peak_rise_bytes": peak[k],
+                          "free_drop_after_first_call_bytes": first_call[k]}
     if "a" in legs and "b" in legs:
         line["b_equals_a_bit_for_bit"] = bool(torch.equal(outs["a"], outs["b"]))
         line["b_over_c"] = round(statistics.median(ms["b"]) / statistics.median(ms["c"]), 4)

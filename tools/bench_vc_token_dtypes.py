@@ -1,4 +1,4 @@
-"""fp16 / bf16 frame tokens on the batched VideoChat2 path against fp32 tokens, at the eval shape of the reference's VideoChat2
+"""fp16 / bf16 / fp8 e4m3 frame tokens on the batched VideoChat2 path against fp32 tokens, at the eval shape of the reference's VideoChat2
 drivers (T 16, P 196, width 1024, N 64, 96 query tokens, 12 layers, alpha 0.75, sticky, mistral_proj 4096).  Three measurements,
 each in fresh child processes, one GPU process at a time, the sides alternated round by round; a child warms up once and times
 `--calls` calls.  One JSON line each, appended to profiles/vc_half_tokens.jsonl:
@@ -6,7 +6,8 @@ each in fresh child processes, one GPU process at a time, the sides alternated r
     timeout -k 10 1100 python tools/bench_vc_token_dtypes.py [--parent-tree TREE]
 
 (a) "call": encode_videos at 16 videos x 8 chunks and encode_streams at 8 blocks x 8 chunks with K = 4 instructions, the tokens
-    held as fp32, fp16, bf16, and as fp16 cast to fp32 inside every call (what a half-precision producer paid before).  Wall ms per
+    held as fp32, fp16, bf16, fp8 e4m3 (torch.float8_e4m3fn: the caller's storage choice, quoted next to bf16 of the same run;
+    --out profiles/vc_f8_tokens.jsonl), and as fp16 cast to fp32 inside every call (what a half-precision producer paid before).  Wall ms per
     call around a device synchronisation (median over all calls of all rounds), the library's launches per call, and the drop of
     torch.cuda.mem_get_info's free bytes over the first call (the library's workspaces are not torch's).
 (b) "token_pass": the token pass alone through infv_vqf_token_pass with HIP events, 128 chunks, fp16 and bf16: infv_ltm_pool at the
@@ -30,7 +31,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T, P, D, N_TEXT, CHUNKS = 16, 196, 1024, 16, 8
-KINDS = ("f32", "f16", "bf16", "f16_cast")
+KINDS = ("f32", "f16", "bf16", "f8", "f16_cast")
 PASS_CHUNKS = 128
 
 
@@ -47,7 +48,7 @@ def child_call(a):
     gen = torch.Generator(device=dev).manual_seed(1)
     streams = a.child == "streams"
     F, K = (8, 4) if streams else (16, 1)
-    held = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "f16_cast": torch.float16}[a.kind]
+    held = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "f8": torch.float8_e4m3fn, "f16_cast": torch.float16}[a.kind]
     blocks = [torch.randn(CHUNKS, T * P, D, device=dev, generator=gen).to(held) for _ in range(F)]
     texts = [torch.randn(1, N_TEXT, 768, device=dev, generator=gen) for _ in range(K)]
     V = F * K
@@ -160,6 +161,7 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--only", choices=("call", "token_pass", "parent_vs_branch"), nargs="*")
+    ap.add_argument("--sides", choices=("videos", "streams"), nargs="*", default=("videos", "streams"), help="which calls the \"call\" measure times")
     ap.add_argument("--parent-tree", metavar="TREE")
     ap.add_argument("--child-timeout", type=int, default=300)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vc_half_tokens.jsonl"))
@@ -182,7 +184,7 @@ def main():
         res = run_child(["--child", "pass", "--calls", str(max(a.calls, 10))], ROOT, a.child_timeout)
         emit(dict(measure="token_pass", T=T, P=P, width=D, chunks=PASS_CHUNKS, timing="HIP events", **res))
     if "call" in want:
-        for side in ("videos", "streams"):
+        for side in a.sides:
             per, last = {k: [] for k in KINDS}, {}
             for r in range(a.rounds):
                 for kind in KINDS:                              # alternated child by child, so that drift hits all alike

@@ -8,7 +8,7 @@
 // the setters check the handle for null alone and write nothing but the dtype field (whose fp32 code is 0); formally that is
 // undefined behaviour on these non-trivial structs.  If a handle gains a validity check, give this program real handles.
 // Null handles are refused whatever the code; on a dummy handle (zeroed storage standing in for the handle: the setters touch
-// nothing but the dtype field) the known codes 0, 1 and 3 are taken and every other code is refused and leaves the setting alone.
+// nothing but the dtype field) the known codes 0, 1, 3 and 4 (fp8 e4m3) are taken and every other code is refused and leaves the setting alone.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,8 +21,8 @@ static int failures = 0;
 #define EXPECT(cond) do { if (!(cond)) { std::fprintf(stderr, "FAILED line %d: %s\n", __LINE__, #cond); ++failures; } } while (0)
 
 int main() {
-    const int known[] = {INFV_TOKENS_F32, INFV_TOKENS_BF16, INFV_TOKENS_F16};
-    const int unknown[] = {2, -1, 4, 7, 16, 255, -2147483647 - 1, 2147483647};
+    const int known[] = {INFV_TOKENS_F32, INFV_TOKENS_BF16, INFV_TOKENS_F16, INFV_TOKENS_F8E4M3};
+    const int unknown[] = {2, -1, 5, 7, 16, 255, -2147483647 - 1, 2147483647};
     for (int c : known) { EXPECT(infv_ltm_set_token_dtype(nullptr, c) == INFV_ERR_INVALID); EXPECT(infv_vqf_set_token_dtype(nullptr, c) == INFV_ERR_INVALID); }
     for (int c : unknown) { EXPECT(infv_ltm_set_token_dtype(nullptr, c) == INFV_ERR_INVALID); EXPECT(infv_vqf_set_token_dtype(nullptr, c) == INFV_ERR_INVALID); }
     EXPECT(std::strstr(infv_ltm_last_error(), "null") != nullptr);
@@ -50,6 +50,16 @@ int main() {
     EXPECT(infv_ltm_set_token_dtype(hl, INFV_TOKENS_F32) == INFV_OK && infv_vqf_set_token_dtype(hv, INFV_TOKENS_F32) == INFV_OK);
     std::memset(a0, 0, kDummy);
     EXPECT(std::memcmp(a0, a, kDummy) == 0 && std::memcmp(a0, b, kDummy) == 0);
+    // code 4 wants 16-byte aligned tokens: infv_vqf_token_pass refuses a pointer 1, 2, 4 or 8 bytes off before any launch, and a lo plane
+    alignas(16) static unsigned char tok[64];
+    alignas(16) static unsigned char plane[64];
+    for (int off : {1, 2, 4, 8}) {
+        EXPECT(infv_vqf_token_pass(tok + off, INFV_TOKENS_F8E4M3, 1, 64, 64, 4, plane, nullptr, plane, nullptr, nullptr, nullptr) == INFV_ERR_INVALID);
+        EXPECT(std::strstr(infv_ltm_last_error(), "16-byte") != nullptr);
+    }
+    EXPECT(infv_vqf_token_pass(tok, INFV_TOKENS_F8E4M3, 1, 64, 64, 4, plane, plane, plane, nullptr, nullptr, nullptr) == INFV_ERR_INVALID);
+    EXPECT(infv_vqf_token_pass(tok, 5, 1, 64, 64, 4, plane, nullptr, plane, nullptr, nullptr, nullptr) == INFV_ERR_INVALID);
+    EXPECT(infv_vqf_layernorm_tokens(tok, INFV_TOKENS_F8E4M3, 1, 64, nullptr, nullptr, 1e-12f, nullptr, nullptr) == INFV_ERR_UNSUPPORTED);
     std::free(a); std::free(b); std::free(a0); std::free(b0);
     std::printf(failures ? "token dtype host check: %d FAILED\n" : "token dtype host check: ok\n", failures);
     return failures ? 1 : 0;
