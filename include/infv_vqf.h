@@ -330,6 +330,47 @@ int infv_vqf_vc_encode_img(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_
                            const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out,
                            float* proj_mean, void* stream);
 
+/* ---- the per-frame image Q-former: the producer of the Video-LLaMA frame tokens (additive) ----
+ * The image Q-former of encode_short_memory_frame (infinityqa.py:259-270; Qformer.py BertEncoder with
+ * position_embedding_ext == None, so no long-term memory is called whatever alpha is) over F frames: bert-base with a
+ * cross-attention in every layer whose has_cross is set, n_query learned queries, no text rows.  It is the layer loop of
+ * infv_vqf_vc_encode_videos over F one-chunk "videos" that all start from query_rows.
+ *   vision      device [F][n_tokens][enc_width] in token_dtype (0 fp32, 1 bf16, 3 fp16, 4 fp8 e4m3), 16-byte aligned, read in place.
+ *               With `ln` on it is the vision encoder's output before ln_vision, normalised on load exactly as
+ *               infv_vqf_vc_encode_img does, eps from the struct (the reference's ln_vision is nn.LayerNorm's default 1e-5); fp8
+ *               input with the LayerNorm on is INFV_ERR_UNSUPPORTED.
+ *   n_tokens    >= 1, any value (a ViT hands over 257 = class token + 16 x 16 patches).  It is an argument: the handle's
+ *               tokens_per_frame is not read, nor are its alpha and proj_out.  Where n_tokens is no multiple of 64 the split-bf16
+ *               planes are kept at n_pad = ceil(n_tokens / 64) * 64 tokens a frame with zero rows behind the frame's own; exactly
+ *               n_tokens rows of a frame are read.  The row softmax runs over the first n_tokens columns and writes zeros into
+ *               the pad columns, so the pad keys carry no mass.  bf16 tokens without LayerNorm then get their hi plane written
+ *               too (another stride than the caller's buffer).  n_tokens % 64 == 0: the kernels and launches of
+ *               infv_vqf_vc_encode_videos_tok, bit for bit.
+ *   precision   enc_width must be a multiple of 64.  The call takes the split-bf16 contractions; with infv_vqf_set_precision(h, 1)
+ *               or INFV_VQF_FP32 set it is INFV_ERR_UNSUPPORTED unless n_tokens % 32 == 0, where the fp32 kernels run.
+ *   w           the text FFN members are never read (no text rows exist); mistral_proj must be absent (w and b NULL).
+ *   query_rows  device fp32 [n_query][hidden], 16-byte aligned: the embedded query tokens (embeddings.LayerNorm(query_tokens)).
+ *   out         device [F][n_query][hidden] in out_dtype (0 fp32, 1 bf16, 3 fp16), 16-byte aligned.  bf16 / fp16: the last layer's
+ *               query-FFN LayerNorm epilogue rounds to nearest even and writes the 2-byte rows itself -- the bits of
+ *               (fp32 result).to(dtype), no fp32 copy of the output is made.  fp32: the rows are copied out of the workspace as
+ *               infv_vqf_vc_encode_videos copies hidden_out (its launches, one for one).  fp8 output: INFV_ERR_UNSUPPORTED (the
+ *               library does not quantise).
+ * A frame's output bits do not depend on F, on the frame's position or on the other frames' contents.
+ * Refused before any launch or memory change (INFV_ERR_INVALID unless noted): a null h, w, query_rows, or (F > 0) vision / out;
+ * F < 0 (F == 0 returns INFV_OK); an unknown token or output dtype; vision, out or query_rows not 16-byte aligned; n_tokens < 1;
+ * w->n_layers < 1 or above INFV_VQF_VC_MAX_LAYERS (INFV_ERR_UNSUPPORTED); a projection present; gamma without beta; for bf16 / fp16
+ * output a last-layer q_ffn_out.b / q_ffn_ln that is not 16-byte aligned. */
+int infv_vqf_encode_frames(infv_vqf_handle h, int32_t F, const void* vision, int32_t token_dtype, int32_t n_tokens,
+                           const infv_vqf_vc_weights* w, const infv_vqf_vision_ln* ln /* NULL or gamma NULL: off */,
+                           const float* query_rows /* device [n_query][hidden]: the embedded query tokens, shared by all frames */,
+                           void* out /* [F][n_query][hidden] */, int32_t out_dtype /* 0 fp32, 1 bf16, 3 fp16 */, void* stream);
+
+/* A tap for tests (exported as infv_vqf_self_attention is): the NEXT infv_vqf_encode_frames call on h also copies the cross-attention
+ * context of encoder layer `layer` (Qformer.py:303-304: softmax(q k^T / sqrt(dh)) v with the value bias, before the output dense),
+ * [F][n_query][hidden] fp32, to dst (device) on the call's stream; the tap is cleared when that call returns.  dst NULL: off.  A layer
+ * that is no cross-attention layer of the call's weights makes that call INFV_ERR_INVALID before any launch.  No kernel is added. */
+int infv_vqf_set_context_tap(infv_vqf_handle h, int32_t layer, float* dst);
+
 /* The vision LayerNorm alone (exported for tests and measurements): out_f32 [n_rows][d] = LayerNorm(frames [n_rows][d]) with the
  * kernels and the arithmetic of infv_vqf_vc_encode_img -- the reference form of its bits.  d a multiple of 64 up to 4096; frames,
  * gamma, beta and out_f32 16-byte aligned.  The row statistics go through a process-wide device buffer. */

@@ -220,6 +220,9 @@ _SIGNATURES = {
     "infv_vqf_vc_encode_img": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(VqfVcWeights), C.POINTER(VqfVcFront), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "infv_vqf_encode_frames": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(VqfVcWeights),
+                                         C.POINTER(VqfVisionLn), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "infv_vqf_set_context_tap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "infv_vqf_layernorm_tokens": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                             C.c_void_p]),
     "infv_vqf_vc_embed": (C.c_int, [C.c_void_p, C.POINTER(VqfVcFront), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

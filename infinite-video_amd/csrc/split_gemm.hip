@@ -1471,4 +1471,208 @@ hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------------
+// The padded forms of the token pass and the row softmax (infv_vqf_encode_frames): a frame of n tokens where n is no multiple of
+// 64 -- a ViT hands over 257 = class token + 16 x 16 patches.  The contractions need K and the leading dimensions in multiples of
+// 64, so the planes are kept at n_pad = ceil(n / 64) * 64 tokens per frame: F_hi / F_lo [.][n_pad][d], FT_hi / FT_lo [.][d][n_pad],
+// rows at or beyond n exact zeros.  The softmax gives the pad keys no mass (exact zeros in P_hi / P_lo), so the context
+// contraction over K = n_pad adds exact zeros.  n % 64 == 0 never comes here: it takes the kernels above, launch for launch.
+// ------------------------------------------------------------------------------------------------------
+// split_transpose_kernel / split_transpose_ln_kernel for any token type with the source at n tokens per frame and the planes at
+// n_pad.  The source is read 4 columns per thread inside ONE token row (d % 64 == 0: no load straddles a row), and only rows
+// r < n of this frame: the last tile of a frame never touches the next frame's first rows or the bytes behind the buffer.  Whether
+// a tile is the partial one is uniform over the workgroup (blockIdx.x); inside it the row test predicates the load alone.
+// Fl == nullptr (bf16 / fp8 tokens without LayerNorm: the value is its own hi piece, lo is exactly 0): the lo planes are not written.
+template <class Tok, bool LN>
+__global__ __launch_bounds__(256) void token_pass_pad_kernel(const void* __restrict__ F, int n, int n_pad, int d,
+                                                             const float2* __restrict__ stats, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, __bf16* __restrict__ Fh,
+                                                             __bf16* __restrict__ Fl, __bf16* __restrict__ Th, __bf16* __restrict__ Tl) {
+    __shared__ float tile[64][65];
+    typedef typename Tok::vec tvec;
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const long cin = (long)blockIdx.z * n * d;           // source: n rows a frame
+    const long cout = (long)blockIdx.z * n_pad * d;      // planes: n_pad rows a frame
+    const int live_rows = n - r0 < 64 ? n - r0 : 64;     // (>= 1: grid.x = n_pad / 64 = ceil(n / 64))
+    const tvec* src = reinterpret_cast<const tvec*>(F);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int e = tid + 256 * p;                     // 1024 groups of 4 columns
+        const int r = e >> 4, c4 = (e & 15) * 4;
+        floatx4 v = {0.f, 0.f, 0.f, 0.f};
+        if (r < live_rows) {
+            v = Tok::widen(src[(cin + (long)(r0 + r) * d + c0 + c4) >> 2]);
+            if (LN)
+                v = token_ln4(v, stats[(long)blockIdx.z * n + r0 + r], *reinterpret_cast<const floatx4*>(gamma + c0 + c4),
+                              *reinterpret_cast<const floatx4*>(beta + c0 + c4));
+        }
+        __bf16 h[4], l[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { split2(v[k], h[k], l[k]); tile[r][c4 + k] = v[k]; }
+        const long o = cout + (long)(r0 + r) * d + c0 + c4;                       // (r0 + r < n_pad: pad rows are written as zeros)
+        *reinterpret_cast<uint2*>(Fh + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
+        if (Fl) *reinterpret_cast<uint2*>(Fl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int e = tid + 256 * p;
+        const int c = e >> 4, r4 = (e & 15) * 4;
+        __bf16 h[4], l[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) split2(tile[r4 + k][c], h[k], l[k]);
+        const long o = cout + (long)(c0 + c) * n_pad + r0 + r4;
+        *reinterpret_cast<uint2*>(Th + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
+        if (Tl) *reinterpret_cast<uint2*>(Tl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
+    }
+}
+
+template <class Tok, bool kHasLn = true /* false: no LayerNorm form of this token type exists (fp8) */>
+static hipError_t launch_token_pass_pad_t(const void* F, int nb, int n, int n_pad, int d, const float2* st, const float* gamma,
+                                          const float* beta, __bf16* Fh, __bf16* Fl, __bf16* Th, __bf16* Tl, hipStream_t stream) {
+    const dim3 grid(n_pad / 64, d / 64, nb);
+    if (!st) {
+        INFV_LAUNCH((token_pass_pad_kernel<Tok, false>), grid, dim3(256), 0, stream, F, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl);
+        return hipGetLastError();
+    }
+    if constexpr (kHasLn) {
+        INFV_LAUNCH((token_pass_pad_kernel<Tok, true>), grid, dim3(256), 0, stream, F, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl);
+        return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_token_pass_pad(const void* F, tok_code tok, int nb, int n, int n_pad, int d, const void* stats, const float* gamma,
+                                 const float* beta, void* Fh_, void* Fl_, void* Th_, void* Tl_, hipStream_t stream) {
+    if (nb <= 0) return hipSuccess;
+    if (n < 1 || n_pad % 64 || n_pad < n || n_pad - n >= 64 || d < 64 || d % 64 || nb > 32768 || !Fh_ || !Th_) return hipErrorInvalidValue;
+    if (stats && (!gamma || !beta || tok == INFV_TOKENS_F8E4M3)) return hipErrorInvalidValue;
+    const bool own_hi = !stats && (tok == INFV_TOKENS_BF16 || tok == INFV_TOKENS_F8E4M3);   // no lo planes
+    if (own_hi ? (Fl_ || Tl_) : (!Fl_ || !Tl_)) return hipErrorInvalidValue;
+    const float2* st = static_cast<const float2*>(stats);
+    __bf16 *Fh = static_cast<__bf16*>(Fh_), *Fl = static_cast<__bf16*>(Fl_), *Th = static_cast<__bf16*>(Th_), *Tl = static_cast<__bf16*>(Tl_);
+    switch (tok) {
+        case INFV_TOKENS_F32: return launch_token_pass_pad_t<TokF32>(F, nb, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl, stream);
+        case INFV_TOKENS_BF16: return launch_token_pass_pad_t<TokBF16>(F, nb, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl, stream);
+        case INFV_TOKENS_F16: return launch_token_pass_pad_t<TokF16>(F, nb, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl, stream);
+        case INFV_TOKENS_F8E4M3: return launch_token_pass_pad_t<TokF8, false>(F, nb, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+// softmax_rows_split_reg_kernel over the first `len` columns of a score row of padded length len_pad (len <= len_pad, both below
+// 1024 * NV): columns [len, len_pad) never enter the max or the sum -- whatever finite or non-finite value they hold -- and are
+// written as exact zeros into P_hi / P_lo.  The row is read in 16-byte vectors up to len_pad (inside the row's allocation); the
+// column test selects per element.
+template <int NV>
+__global__ __launch_bounds__(256) void softmax_rows_split_pad_kernel(const float* __restrict__ S, int len, int len_pad, long ld,
+                                                                     __bf16* __restrict__ Ph, __bf16* __restrict__ Pl, long ld_out) {
+    __shared__ float red[4];
+    const float* row = S + (long)blockIdx.x * ld;
+    const int tid = threadIdx.x;
+    floatx4 v[NV];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = tid * 4 + 1024 * i;
+        if (c < len_pad) {
+            const floatx4 raw = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(row + c));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[i][k] = c + k < len ? raw[k] : -INFINITY;
+            mx = fmaxf(mx, fmaxf(fmaxf(v[i][0], v[i][1]), fmaxf(v[i][2], v[i][3])));
+        }
+    }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) red[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = tid * 4 + 1024 * i;
+        if (c < len_pad) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[i][k] = c + k < len ? expf(v[i][k] - mx) : 0.f;
+            sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+        }
+    }
+    sum = wave_sum(sum);
+    if ((tid & 63) == 0) red[tid >> 6] = sum;
+    __syncthreads();
+    const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
+    __bf16* ph = Ph + (long)blockIdx.x * ld_out;
+    __bf16* pl = Pl + (long)blockIdx.x * ld_out;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = tid * 4 + 1024 * i;
+        if (c < len_pad) {
+            __bf16 h[4], l[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) split2(v[i][k] * inv, h[k], l[k]);
+            *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
+            *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
+        }
+    }
+}
+
+// rows beyond 8192 columns: softmax_rows_split_kernel's three passes over the row, with the same column test
+__global__ __launch_bounds__(256) void softmax_rows_split_pad_long_kernel(const float* __restrict__ S, int len, int len_pad, long ld,
+                                                                          __bf16* __restrict__ Ph, __bf16* __restrict__ Pl, long ld_out) {
+    __shared__ float red[4];
+    const float* row = S + (long)blockIdx.x * ld;
+    const int tid = threadIdx.x;
+    float mx = -INFINITY;
+    for (int c = tid * 4; c < len_pad; c += 1024) {
+        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mx = fmaxf(mx, c + k < len ? v[k] : -INFINITY);
+    }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) red[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sum = 0.f;
+    for (int c = tid * 4; c < len_pad; c += 1024) {
+        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
+        float ex[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ex[k] = c + k < len ? expf(v[k] - mx) : 0.f;
+        sum += (ex[0] + ex[1]) + (ex[2] + ex[3]);
+    }
+    sum = wave_sum(sum);
+    if ((tid & 63) == 0) red[tid >> 6] = sum;
+    __syncthreads();
+    const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
+    __bf16* ph = Ph + (long)blockIdx.x * ld_out;
+    __bf16* pl = Pl + (long)blockIdx.x * ld_out;
+    for (int c = tid * 4; c < len_pad; c += 1024) {
+        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
+        __bf16 h[4], l[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) split2(c + k < len ? expf(v[k] - mx) * inv : 0.f, h[k], l[k]);
+        *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
+        *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
+    }
+}
+
+hipError_t launch_softmax_rows_split_pad(const float* S, long n_rows, int len, int len_pad, long ld, void* Ph, void* Pl, long ld_out,
+                                         hipStream_t stream) {
+    if (n_rows <= 0) return hipSuccess;
+    if (len < 1 || len > len_pad || len_pad % 4 || len_pad > ld || len_pad > ld_out || ld % 4 || ld_out % 4 || n_rows > 0x7fffffffL)
+        return hipErrorInvalidValue;
+    if (len_pad <= 2048)
+        INFV_LAUNCH(softmax_rows_split_pad_kernel<2>, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, len_pad, ld,
+                    static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
+    else if (len_pad <= 8192)
+        INFV_LAUNCH(softmax_rows_split_pad_kernel<8>, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, len_pad, ld,
+                    static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
+    else
+        INFV_LAUNCH(softmax_rows_split_pad_long_kernel, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, len_pad, ld,
+                    static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
+    return hipGetLastError();
+}
+
 }  // namespace infv

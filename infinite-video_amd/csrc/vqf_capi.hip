@@ -26,6 +26,7 @@ struct infv_vqf_s {
     DeviceBuf sFh, sFl, sTh, sTl, sPh, sPl, sQh, sQl;   // split-bf16 operands of the short-term attention
     DeviceBuf wFh, wFl, wTh, wTl;                       // the same split of a WHOLE video's frame tokens (layer-major path)
     DeviceBuf up;                                       // fp32 copy of fp16 / bf16 tokens where the split path does not apply
+    int tap_layer = -1; float* tap_dst = nullptr;       // infv_vqf_set_context_tap: consumed by the next infv_vqf_encode_frames
     bool fuse = true;                                   // one pass over the frame tokens: split + transpose + frame means
     double split_cache_gb = 64.0;                       // budget for a whole video's split tokens (INFV_VQF_SPLIT_CACHE_GB at create)
     // whole-video (layer-major) path
@@ -80,6 +81,7 @@ struct LinearCall {
     const infv_layernorm* ln = nullptr;
     float* y;
     bool inv = false;      // batch invariant (infv_vqf_encode_videos): 128 x 128 tiles, no split-K, whatever M is
+    void* y16 = nullptr; tok_code y16_dtype = INFV_TOKENS_F32;   // y16 != nullptr: the rows go out as bf16 / fp16 instead of y (infv_vqf_encode_frames)
 };
 
 int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
@@ -101,7 +103,8 @@ int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
     e.residual = c.residual; e.ld_res = width; e.res_rows = c.res_rows;
     e.gamma = c.ln ? c.ln->gamma : nullptr; e.beta = c.ln ? c.ln->beta : nullptr; e.eps = h->cfg.ln_eps;
     e.out = c.y; e.ld_out = width; e.M = c.M; e.width = width;
-    HIP_TRY(launch_qf_epilogue(e, stream));
+    if (c.y16) HIP_TRY(launch_qf_epilogue_cast(e, c.y16, width, c.y16_dtype, stream));
+    else HIP_TRY(launch_qf_epilogue(e, stream));
     return INFV_OK;
 }
 
@@ -133,7 +136,10 @@ static const void* tok_at(const void* frames, tok_code tok, long elems) {
 
 // bytes of bf16 planes prepare_split writes per token element, for the plane-cache budget: bf16 tokens 2 (FT_hi alone), fp8 tokens 4
 // (F_hi and FT_hi), fp32 / fp16 tokens and every normalised token (`ln`: a general fp32 number) 8 (all four planes)
-static double plane_bytes(tok_code tok, bool ln) { return ln ? 8.0 : tok == INFV_TOKENS_BF16 ? 2.0 : tok == INFV_TOKENS_F8E4M3 ? 4.0 : 8.0; }
+// (padded planes, infv_vqf_encode_frames: bf16 tokens cannot be read in place at another stride, so their F_hi is written too: 4)
+static double plane_bytes(tok_code tok, bool ln, bool padded = false) {
+    return ln ? 8.0 : tok == INFV_TOKENS_BF16 ? (padded ? 4.0 : 2.0) : tok == INFV_TOKENS_F8E4M3 ? 4.0 : 8.0;
+}
 
 // fp16 / bf16 / fp8 tokens where the split path does not apply: an fp32 copy in the handle's workspace for today's fp32 kernels
 static int upcast_tokens(infv_vqf_s* h, const void* frames, tok_code tok, size_t elems, const float** out, hipStream_t stream) {
@@ -155,12 +161,32 @@ struct TokLn { const float* stats; const float* gamma; const float* beta; };
 // *ref always addresses chunk 0 of the buffers
 static int prepare_split(infv_vqf_s* h, const void* frames_, tok_code tok, int nb, int n_tokens, float* kbar, bool whole, SplitRef* ref,
                          hipStream_t stream, int dst0 = 0, int cap = 0,
-                         const TokLn* ln = nullptr /* the planes (and means) of token_ln(frames); ln->stats addresses frames_' first token */) {
+                         const TokLn* ln = nullptr /* the planes (and means) of token_ln(frames); ln->stats addresses frames_' first token */,
+                         int n_live = 0 /* > 0 and != n_tokens: frames_ holds n_live tokens a chunk, the planes n_tokens = ceil(n_live / 64) * 64 (pad: zeros) */) {
     const int d = h->cfg.enc_width;
     const size_t szF = (size_t)(cap > dst0 + nb ? cap : dst0 + nb) * n_tokens * d * 2;
     const size_t d0 = (size_t)dst0 * n_tokens * d;
     DeviceBuf& Fh = whole ? h->wFh : h->sFh; DeviceBuf& Fl = whole ? h->wFl : h->sFl;
     DeviceBuf& Th = whole ? h->wTh : h->sTh; DeviceBuf& Tl = whole ? h->wTl : h->sTl;
+    if (n_live > 0 && n_live != n_tokens) {                  // padded planes: no frame means, bf16 tokens get their F_hi too
+        if (kbar) return fail(INFV_ERR_INVALID, "prepare_split: no frame means from padded planes");
+        const bool own_hi = !ln && (tok == INFV_TOKENS_BF16 || tok == INFV_TOKENS_F8E4M3);
+        if (szF > Fh.bytes || szF > Th.bytes || (!own_hi && (szF > Fl.bytes || szF > Tl.bytes))) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(Fh.reserve(szF)); HIP_TRY(Th.reserve(szF));
+            if (!own_hi) { HIP_TRY(Fl.reserve(szF)); HIP_TRY(Tl.reserve(szF)); }
+        }
+        for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
+            const int n = nb - c0 < 32768 ? nb - c0 : 32768;
+            const size_t o = (size_t)c0 * n_tokens * d, oi = (size_t)c0 * n_live * d;
+            HIP_TRY(launch_token_pass_pad(tok_at(frames_, tok, (long)oi), tok, n, n_live, n_tokens, d, ln ? ln->stats + 2 * (size_t)c0 * n_live : nullptr,
+                                          ln ? ln->gamma : nullptr, ln ? ln->beta : nullptr, Fh.as<__bf16>() + d0 + o,
+                                          own_hi ? nullptr : Fl.as<__bf16>() + d0 + o, Th.as<__bf16>() + d0 + o,
+                                          own_hi ? nullptr : Tl.as<__bf16>() + d0 + o, stream));
+        }
+        *ref = SplitRef{Fh.as<__bf16>(), own_hi ? nullptr : Fl.as<__bf16>(), Th.as<__bf16>(), own_hi ? nullptr : Tl.as<__bf16>()};
+        return INFV_OK;
+    }
     const int P = h->cfg.tokens_per_frame;
     if (tok == INFV_TOKENS_BF16 && !ln) {                    // read in place: only the transposed copy is written
         if (szF > Th.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(Th.reserve(szF)); }
@@ -211,8 +237,11 @@ int short_attention(infv_vqf_s* h, const void* frames_, tok_code tok /* fp16, bf
                     hipEvent_t along_ready = nullptr /* `along` is produced on another stream: wait here, before the merge */,
                     int inv_nb = 0 /* > 0: batch invariant -- split-K counts and kernel shapes as for inv_nb chunks, whatever nb is */,
                     const int32_t* b_map = nullptr /* device [nb]: chunk b reads chunk b_map[b] of frames_ / *pre (several streams over one block) */,
-                    bool t_identity = false /* the transposed plane of *pre holds the sub-batch's chunks in order: only the untransposed operand goes through b_map */) {
+                    bool t_identity = false /* the transposed plane of *pre holds the sub-batch's chunks in order: only the untransposed operand goes through b_map */,
+                    int n_live = 0 /* > 0 and != n_tokens: *pre holds planes padded to n_tokens, only the first n_live keys of a chunk exist */) {
     const infv_vqf_config& c = h->cfg;
+    const bool padded = n_live > 0 && n_live != n_tokens;
+    if (padded && (!pre || !split_path(h, n_tokens) || n_live > n_tokens)) return fail(INFV_ERR_INVALID, "padded keys need the caller's split planes");
     const int Q = c.n_query, H = c.n_heads, d = c.enc_width, rows = H * Q;
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
     const int nb_pick = inv_nb > 0 ? inv_nb : nb;
@@ -271,7 +300,8 @@ int short_attention(infv_vqf_s* h, const void* frames_, tok_code tok /* fp16, bf
         g.C = h->S.as<float>(); g.ldc = ldS; g.strideC = (long)rows * ldS; g.split_stride = 0;
         g.M = rows; g.N = n_tokens; g.K = d; g.k_per_split = d; g.splitk = 1; g.nbatch = nb; g.wide = inv_nb > 0; g.b_map = b_map;
         HIP_TRY(launch_split_gemm(g, stream));
-        HIP_TRY(launch_softmax_rows_split(h->S.as<float>(), (long)nb * rows, n_tokens, ldS, h->sPh.p, h->sPl.p, n_tokens, stream));
+        if (padded) HIP_TRY(launch_softmax_rows_split_pad(h->S.as<float>(), (long)nb * rows, n_live, n_tokens, ldS, h->sPh.p, h->sPl.p, n_tokens, stream));
+        else HIP_TRY(launch_softmax_rows_split(h->S.as<float>(), (long)nb * rows, n_tokens, ldS, h->sPh.p, h->sPl.p, n_tokens, stream));
         SplitGemm p{};                                        // O[b] = P[b] . frames[b]
         p.A_hi = h->sPh.as<__bf16>(); p.A_lo = h->sPl.as<__bf16>(); p.lda = n_tokens; p.strideA = (long)rows * n_tokens;
         p.B_hi = sr.Th; p.B_lo = sr.Tl; p.ldb = n_tokens; p.strideB = (long)d * n_tokens;
@@ -910,13 +940,19 @@ int infv_vqf_self_attention(infv_vqf_handle h, const float* qkv, int32_t nb, int
     return INFV_OK;
 }
 
+// infv_vqf_encode_frames through vc_impl: F one-chunk "videos" without text rows or memories.  The token count of a frame is an
+// argument (any value >= 1: the planes are padded to the next multiple of 64), every frame starts from the same query rows, and
+// the last layer's rows go out in out_dtype.  The handle's tokens_per_frame, alpha and proj_out are not read.
+struct FrameCall { int n_tokens; void* out; tok_code out_dtype; };
+
 // The body of infv_vqf_vc_encode_videos (fcu == nullptr: stream v reads its own chunks [cu[v], cu[v+1]) of `frames`) and of
 // infv_vqf_vc_encode_streams (stream v reads block frame_src[v] of the F blocks packed by fcu).  `name` prefixes the refusals.
 static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
                    int32_t token_dtype /* < 0: the entry points without the argument -- fp32, refused unless the handle's setting is fp32 too */,
                    int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in,
                    const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
-                   void* stream_, const infv_vqf_vc_front* front = nullptr /* infv_vqf_vc_encode_img: vision LayerNorm and / or embedding layer in front */) {
+                   void* stream_, const infv_vqf_vc_front* front = nullptr /* infv_vqf_vc_encode_img: vision LayerNorm and / or embedding layer in front */,
+                   const FrameCall* fc = nullptr /* infv_vqf_encode_frames: every chunk is one frame of fc->n_tokens tokens */) {
     // ---- validation before any device work or memory change ----
     if (!h || !cu || !w || !text_len || V < 0) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
     if (front && front->reserved != 0) return fail(INFV_ERR_INVALID, "%s: front->reserved must be 0", name);
@@ -965,8 +1001,18 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     if (emb)
         if (int rc = check_front_emb(name, front, V, text_len)) return rc;
     if (T < 1) return fail(INFV_ERR_INVALID, "%s: T must be >= 1", name);
-    const int n_tokens = T * c.tokens_per_frame;
-    if (n_tokens % 32) return fail(INFV_ERR_UNSUPPORTED, "%s: T * tokens_per_frame = %d is no multiple of 32", name, n_tokens);
+    const int n_live = fc ? fc->n_tokens : T * c.tokens_per_frame;   // tokens a chunk holds in `frames`
+    if (!fc && n_live % 32) return fail(INFV_ERR_UNSUPPORTED, "%s: T * tokens_per_frame = %d is no multiple of 32", name, n_live);
+    bool pad = false;                                          // frames: planes and score rows padded to the next multiple of 64
+    if (fc) {
+        if (n_live < 1) return fail(INFV_ERR_INVALID, "%s: n_tokens = %d, must be >= 1", name, n_live);
+        if (n_live > 0x7fffffff - 128) return fail(INFV_ERR_UNSUPPORTED, "%s: n_tokens = %d is too large", name, n_live);
+        if (c.enc_width % 64) return fail(INFV_ERR_UNSUPPORTED, "%s: enc_width = %d is no multiple of 64", name, c.enc_width);
+        pad = n_live % 64 != 0 && split_path(h, 64);
+        if (n_live % 32 && !pad)
+            return fail(INFV_ERR_UNSUPPORTED, "%s: the fp32 contractions (set_precision(h, 1) / INFV_VQF_FP32) need n_tokens %% 32 == 0, got %d", name, n_live);
+    }
+    const int n_tokens = pad ? (n_live + 63) / 64 * 64 : n_live;   // keys a chunk has in the contractions (pad keys: zeros, no mass)
     if (vis_ln && (c.enc_width % 64 || c.enc_width > kTokenLnMaxWidth))
         return fail(INFV_ERR_UNSUPPORTED, "%s: the vision LayerNorm needs enc_width = %d to be a multiple of 64, at most %d", name, c.enc_width,
                     kTokenLnMaxWidth);
@@ -974,7 +1020,7 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
         return fail(INFV_ERR_UNSUPPORTED, "%s: fp16 / bf16 frame tokens are not supported on this path (the _tok entry point takes them)", name);
     int n_cross = 0;
     for (int l = 0; l < Ln; ++l) n_cross += w->layers[l].has_cross != 0;
-    const bool use_ltm = c.alpha != 1.0f && n_cross > 0;
+    const bool use_ltm = !fc && c.alpha != 1.0f && n_cross > 0;   // (frames: position_embedding_ext == None, no memory is called)
     const int n_h = use_ltm ? V * n_cross : 0;
     if (use_ltm) {
         if (!ltm) return fail(INFV_ERR_INVALID, "%s: alpha != 1 needs the LTM handles of every video and cross layer", name);
@@ -987,6 +1033,13 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     }
     if ((proj_out || proj_mean) && (c.proj_out <= 0 || !w->mistral_proj.w))
         return fail(INFV_ERR_INVALID, "%s: projected output without mistral_proj", name);
+    if (fc && fc->out_dtype != INFV_TOKENS_F32) {             // the last layer's epilogue writes the 2-byte rows: its 16-byte form only
+        const infv_vqf_vc_layer& L = w->layers[Ln - 1];
+        if (!aligned16(L.q_ffn_out.b) || !aligned16(L.q_ffn_ln.gamma) || !aligned16(L.q_ffn_ln.beta) || !L.q_ffn_ln.gamma || !L.q_ffn_ln.beta)
+            return fail(INFV_ERR_INVALID, "%s: bf16 / fp16 output needs the last layer's q_ffn_out.b and q_ffn_ln 16-byte aligned", name);
+    }
+    if (fc && h->tap_dst && (h->tap_layer >= Ln || !w->layers[h->tap_layer].has_cross))
+        return fail(INFV_ERR_INVALID, "%s: the context tap names layer %d, which is no cross-attention layer of these weights", name, h->tap_layer);
     const int C = cu[V];
     if (C == 0) {                                             // no chunk: new_video still starts every memory afresh
         if (use_ltm && new_video)
@@ -1005,19 +1058,20 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
         for (int v = 0; v < V; ++v) {
             for (int cc = cu[v]; cc < cu[v + 1]; ++cc, ++c_i) {
                 tl[cc] = text_len[v]; n_valid[cc] = Q + text_len[v]; toff[cc + 1] = toff[cc] + text_len[v];
-                q_dst[cc] = cc * Q; q_src[cc] = in_row; t_src[cc] = in_row + Q;
+                q_dst[cc] = cc * Q; q_src[cc] = fc ? 0 : in_row; t_src[cc] = in_row + Q;   // (frames: one block of query rows for all)
                 o_q[cc] = cc * Q + toff[cc]; o_t[cc] = o_q[cc] + Q;
             }
             in_row += Q + text_len[v];
         }
     }
     const long M = (long)C * Q, Tt = toff[C];
-    const long chunk_k = (long)n_tokens * c.enc_width;
+    const long chunk_k = (long)n_tokens * c.enc_width;         // elements of a chunk in the planes ...
+    const long src_k = (long)n_live * c.enc_width;             // ... and in `frames` (the same unless padded)
     const int Cf = streams ? fcu[F] : C;                       // distinct chunks of frame tokens
     TokLn ln_{}; const TokLn* ln = nullptr;                    // the vision LayerNorm on load (split path), else nullptr
     if (vis_ln && n_cross > 0) {
         // (mean, 1 / sqrt(var + eps)) of every DISTINCT token row, once per call: 8 bytes per token
-        const size_t rows = (size_t)Cf * n_tokens;
+        const size_t rows = (size_t)Cf * n_live;
         if (rows * 2 * sizeof(float) > h->lnstats.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->lnstats.reserve(rows * 2 * sizeof(float))); }
         HIP_TRY(launch_token_ln_stats(frames, tok, (long)rows, c.enc_width, front->vision_ln.eps, h->lnstats.p, stream));
         if (split_path(h, n_tokens)) {
@@ -1100,10 +1154,11 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     SplitRef wref{}; bool have_w = false, have_kbar = false;
     if (n_cross > 0) {
         // (streams: the distinct chunks only; bf16 tokens: only the transposed plane is written, as in infv_vqf_encode_video)
-        const double need_gb = plane_bytes(tok, ln != nullptr) * (double)Cf * (double)chunk_k / 1e9;
+        const double need_gb = plane_bytes(tok, ln != nullptr, pad) * (double)Cf * (double)chunk_k / 1e9;
         if (h->fuse && split_path(h, n_tokens) && need_gb <= h->split_cache_gb) {
             have_kbar = use_ltm && token_pass_gives_means(c.tokens_per_frame);   // (where a frame divides the 64-token tile)
-            if (int rc = prepare_split(h, frames, tok, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream, 0, 0, ln)) return rc;
+            if (int rc = prepare_split(h, frames, tok, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream, 0, 0, ln,
+                                       pad ? n_live : 0)) return rc;
             have_w = true;
         }
         if (use_ltm && !have_kbar && ln) {                     // pooling with the LayerNorm on load: the means of the normalised tokens
@@ -1124,15 +1179,16 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     //   streams: the cached planes of the DISTINCT chunks, or the caller's tokens on the fp32 path, read through the map; where the
     //            planes do not fit, each contiguous run of source chunks is split into the sub-batch's own planes (identity map)
     auto operand_at = [&](int c0, int nb, SplitRef* r, const SplitRef** pre, const void** fr, const int32_t** map, bool* t_identity) -> int {
-        *pre = nullptr; *map = nullptr; *t_identity = false; *fr = tok_at(frames, tok, (long)c0 * chunk_k);
+        *pre = nullptr; *map = nullptr; *t_identity = false; *fr = tok_at(frames, tok, (long)c0 * src_k);
         if (!streams) {
             if (have_w) {
                 const long o = (long)c0 * chunk_k;
                 *r = SplitRef{wref.Fh + o, wref.Fl ? wref.Fl + o : nullptr, wref.Th + o, wref.Tl ? wref.Tl + o : nullptr};
                 *pre = r;
-            } else if (ln) {                                   // the split per sub-batch short_attention would issue, with the LayerNorm on load
-                const TokLn lc{ln->stats + 2 * (size_t)c0 * n_tokens, ln->gamma, ln->beta};
-                if (int rc = prepare_split(h, *fr, tok, nb, n_tokens, nullptr, false, r, stream, 0, 0, &lc)) return rc;
+            } else if (ln || pad) {                            // the split per sub-batch short_attention would issue, with the LayerNorm on load / padded
+                TokLn lc{};
+                if (ln) lc = TokLn{ln->stats + 2 * (size_t)c0 * n_live, ln->gamma, ln->beta};
+                if (int rc = prepare_split(h, *fr, tok, nb, n_tokens, nullptr, false, r, stream, 0, 0, ln ? &lc : nullptr, pad ? n_live : 0)) return rc;
                 *pre = r;
             }
             return INFV_OK;
@@ -1217,7 +1273,7 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
                 if (int rc = operand_at(c0, nb, &sr, &pre, &fr, &map, &t_identity)) return rc;
                 if (int rc = short_attention(h, fr, tok, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
                                              nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
-                                             pre, nullptr, kInvariantNb, map, t_identity)) return rc;
+                                             pre, nullptr, kInvariantNb, map, t_identity, pad ? n_live : 0)) return rc;
             }
             if (use_ltm) {
                 HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
@@ -1230,6 +1286,8 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
                     HIP_TRY(launch_qf_epilogue(em, stream));
                 }
             }
+            if (fc && h->tap_dst && l == h->tap_layer)         // (tests: this layer's cross-attention context, Qformer.py:303-304)
+                HIP_TRY(hipMemcpyAsync(h->tap_dst, vmerged, (size_t)M * Hd * sizeof(float), hipMemcpyDeviceToDevice, stream));
             for (int c0 = 0; c0 < C; c0 += RB) {
                 const int nb = C - c0 < RB ? C - c0 : RB;
                 const long r0 = (long)c0 * Q * Hd;
@@ -1249,6 +1307,9 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
             if (int rc = run_linear(h, fi, stream)) return rc;
             LinearCall fo{h->vinter.as<float>(), nb * Q, c.inter, {&L.q_ffn_out}, 1, Hd};
             fo.inv = true; fo.residual = qin + r0; fo.res_rows = nb * Q; fo.ln = &L.q_ffn_ln; fo.y = vA + r0;
+            if (fc && last && fc->out_dtype != INFV_TOKENS_F32) {   // the frame tokens leave in the type their consumer reads: no fp32 row is written
+                fo.y16 = static_cast<char*>(fc->out) + 2 * r0; fo.y16_dtype = fc->out_dtype;
+            }
             if (int rc = run_linear(h, fo, stream)) return rc;
         }
         if (text_out)
@@ -1329,6 +1390,41 @@ int infv_vqf_vc_encode_img(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_
     const bool streams = frame_src != nullptr;                 // NULL: videos (F and fcu are not read)
     return vc_impl("vc_encode_img", h, ltm, V, cu, frames, token_dtype, streams ? F : 0, streams ? fcu : nullptr, frame_src, T, w, hidden_in,
                    text_len, u, new_video, hidden_out, proj_out, proj_mean, stream_, front);
+}
+
+int infv_vqf_encode_frames(infv_vqf_handle h, int32_t F, const void* vision, int32_t token_dtype, int32_t n_tokens,
+                           const infv_vqf_vc_weights* w, const infv_vqf_vision_ln* ln, const float* query_rows, void* out, int32_t out_dtype,
+                           void* stream_) {
+    // ---- what vc_impl does not see; everything else is refused there, before any launch or memory change ----
+    const char* name = "encode_frames";
+    if (!h || !w || !query_rows) return fail(INFV_ERR_INVALID, "%s: null handle, weights or query_rows", name);
+    if (F < 0) return fail(INFV_ERR_INVALID, "%s: F = %d is negative", name, F);
+    if (!token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "%s: unknown token dtype %d", name, token_dtype);
+    if (out_dtype == INFV_TOKENS_F8E4M3) return fail(INFV_ERR_UNSUPPORTED, "%s: no fp8 output (the library does not quantise)", name);
+    if (out_dtype != INFV_TOKENS_F32 && out_dtype != INFV_TOKENS_BF16 && out_dtype != INFV_TOKENS_F16)
+        return fail(INFV_ERR_INVALID, "%s: unknown output dtype %d", name, out_dtype);
+    if (w->mistral_proj.w || w->mistral_proj.b) return fail(INFV_ERR_INVALID, "%s: the image Q-former has no projection (mistral_proj must be absent)", name);
+    if (F > 0 && (!vision || !out)) return fail(INFV_ERR_INVALID, "%s: null vision or out", name);
+    if (!aligned16(vision) || !aligned16(out)) return fail(INFV_ERR_INVALID, "%s: vision and out must be 16-byte aligned", name);
+    if (!aligned16(query_rows)) return fail(INFV_ERR_INVALID, "%s: query_rows must be 16-byte aligned", name);
+    if (n_tokens < 1) return fail(INFV_ERR_INVALID, "%s: n_tokens = %d, must be >= 1", name, n_tokens);
+    if ((long)F * h->cfg.n_query > 0x3fffffffL) return fail(INFV_ERR_UNSUPPORTED, "%s: %d frames in one call", name, F);
+    infv_vqf_vc_front front{};
+    if (ln && ln->gamma) front.vision_ln = *ln;
+    std::vector<int32_t> cu((size_t)F + 1), text_len((size_t)(F > 0 ? F : 1), 0);
+    for (int f = 0; f <= F; ++f) cu[f] = f;
+    const FrameCall fc{n_tokens, out, static_cast<tok_code>(out_dtype)};
+    const int rc = vc_impl(name, h, nullptr, F, cu.data(), vision, token_dtype, 0, nullptr, nullptr, 1, w, query_rows, text_len.data(), nullptr, 0,
+                           out_dtype == INFV_TOKENS_F32 ? static_cast<float*>(out) : nullptr, nullptr, nullptr, stream_, &front, &fc);
+    h->tap_layer = -1; h->tap_dst = nullptr;                  // a tap serves one call
+    return rc;
+}
+
+int infv_vqf_set_context_tap(infv_vqf_handle h, int32_t layer, float* dst) {
+    if (!h) return fail(INFV_ERR_INVALID, "null handle");
+    if (dst && (layer < 0 || layer >= INFV_VQF_VC_MAX_LAYERS)) return fail(INFV_ERR_INVALID, "set_context_tap: layer %d outside [0, %d)", layer, INFV_VQF_VC_MAX_LAYERS);
+    h->tap_layer = dst ? layer : -1; h->tap_dst = dst;
+    return INFV_OK;
 }
 
 int infv_vqf_layernorm_tokens(const void* frames, int32_t token_dtype, int64_t n_rows, int32_t d, const float* gamma, const float* beta,

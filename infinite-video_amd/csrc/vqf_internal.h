@@ -159,6 +159,20 @@ hipError_t launch_qf_vc_embed(const float* word, const float* position, const fl
 // softmax of fp32 score rows, written as bf16 hi/lo
 hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long ld, void* Ph, void* Pl, long ld_out, hipStream_t stream);
 
+// ---- padded forms for frames whose token count is no multiple of 64 (infv_vqf_encode_frames) ----
+// F [nb][n][d] of any token type (stats != nullptr: token_ln(F) applied on load, not for fp8) -> Fh/Fl [nb][n_pad][d] and
+// Th/Tl [nb][d][n_pad], n_pad = ceil(n / 64) * 64, rows at or beyond n zeros; rows of the next frame are never read.
+// bf16 / fp8 tokens without LayerNorm: Fl and Tl must be nullptr (Fh IS written: the caller's buffer has another stride).  nb <= 32768
+hipError_t launch_token_pass_pad(const void* F, tok_code tok, int nb, int n, int n_pad, int d, const void* stats, const float* gamma,
+                                 const float* beta, void* Fh, void* Fl, void* Th, void* Tl, hipStream_t stream);
+// softmax over columns [0, len) of fp32 score rows of padded length len_pad; columns [len, len_pad) of Ph / Pl are written as zeros
+hipError_t launch_softmax_rows_split_pad(const float* S, long n_rows, int len, int len_pad, long ld, void* Ph, void* Pl, long ld_out,
+                                         hipStream_t stream);
+// launch_qf_epilogue with the row written as bf16 / fp16 (round to nearest even) into out16 [M][ld_out16]; e.out is not read.
+// Needs what the 16-byte form of the epilogue needs (qf_epilogue_cast_applies); no scalar form exists.
+bool qf_epilogue_cast_applies(const QfEpilogue& e, const void* out16, long ld_out16);
+hipError_t launch_qf_epilogue_cast(const QfEpilogue& e, void* out16, long ld_out16, tok_code out_dtype, hipStream_t stream);
+
 // out[m][:] = mean over nb of in[b][m][:]
 hipError_t launch_qf_mean(const float* in, int nb, long n, float* out, hipStream_t stream);
 constexpr int kMeanSegs = 256;           // videos per launch of launch_qf_mean_segments (the table travels in kernel arguments)

@@ -385,6 +385,109 @@ hipError_t launch_qf_epilogue(const QfEpilogue& e, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// qf_epilogue_vec_kernel writing its row as bf16 or fp16 (infv_vqf_encode_frames: the frame tokens in the type their consumer reads):
+// the same loads, the same order of every fp32 / fp64 operation, then one round-to-nearest-even conversion per element and an
+// 8-byte store -- the bits of (the fp32 epilogue's row).to(dtype), with no fp32 row written.  e.out is not read; out16 [M][ld_out16].
+template <int NV, class Out>
+__global__ __launch_bounds__(256) void qf_epilogue_vec_cast_kernel(QfEpilogue e, Out* __restrict__ out16, long ld_out16) {
+    __shared__ double scratch[4];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const float* in = e.parts + (long)m * e.ld_in;
+    const float* res = e.residual ? e.residual + (long)(m % e.res_rows) * e.ld_res : nullptr;
+    floatx4 x[NV], bias_v[NV], res_v[NV], gam_v[NV], bet_v[NV];
+    bool on[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int c = 4 * (tid + 256 * v);
+        on[v] = c < e.width;
+        x[v] = floatx4{0.f, 0.f, 0.f, 0.f}; bias_v[v] = x[v]; res_v[v] = x[v]; bet_v[v] = x[v];
+        gam_v[v] = floatx4{1.f, 1.f, 1.f, 1.f};
+        if (on[v]) {
+            const int seg = c / e.seg_cols;
+            if (e.bias[seg]) bias_v[v] = *reinterpret_cast<const floatx4*>(e.bias[seg] + (c - seg * e.seg_cols));
+            if (res) res_v[v] = *reinterpret_cast<const floatx4*>(res + c);
+            if (e.gamma) { gam_v[v] = *reinterpret_cast<const floatx4*>(e.gamma + c); bet_v[v] = *reinterpret_cast<const floatx4*>(e.beta + c); }
+        }
+    }
+    for (int s = 0; s < e.nsplit; s += 8) {             // eight slabs in flight
+        floatx4 t[NV][8];
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                t[v][k] = (on[v] && s + k < e.nsplit) ? *reinterpret_cast<const floatx4*>(in + (long)(s + k) * e.split_stride + 4 * (tid + 256 * v))
+                                                      : floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[v] += t[v][k];
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float y = x[v][j] + bias_v[v][j];
+            if (e.act == QF_ACT_GELU) y = 0.5f * y * (1.0f + erff(y * 0.70710678118654752440f));
+            y *= e.scale;
+            if (res) y += e.res_scale * res_v[v][j];
+            x[v][j] = y;
+        }
+    if (e.gamma) {
+        double sum = 0.0;
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+            if (on[v]) sum += ((double)x[v][0] + (double)x[v][1]) + ((double)x[v][2] + (double)x[v][3]);
+        const float mean = (float)(block_sum<256>(sum, scratch) / e.width);
+        double sq = 0.0;
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+            if (on[v]) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const float dlt = x[v][j] - mean; sq += (double)dlt * dlt; }
+            }
+        const float var = (float)(block_sum<256>(sq, scratch) / e.width);
+        const float rstd = 1.0f / sqrtf(var + e.eps);
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[v][j] = (x[v][j] - mean) * rstd * gam_v[v][j] + bet_v[v][j];
+    }
+    Out* out = out16 + (long)m * ld_out16;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+        if (on[v]) {
+            typedef Out outx4 __attribute__((ext_vector_type(4)));
+            const outx4 o = {(Out)x[v][0], (Out)x[v][1], (Out)x[v][2], (Out)x[v][3]};      // v_cvt: round to nearest even
+            *reinterpret_cast<outx4*>(out + 4 * (tid + 256 * v)) = o;
+        }
+}
+
+bool qf_epilogue_cast_applies(const QfEpilogue& e, const void* out16, long ld_out16) {
+    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    bool vec = e.width % 4 == 0 && e.width <= 4096 && e.seg_cols > 0 && e.seg_cols % 4 == 0 && (e.width + e.seg_cols - 1) / e.seg_cols <= kQfMaxSeg &&
+               e.ld_in % 4 == 0 && e.split_stride % 4 == 0 && ld_out16 % 4 == 0 && al(e.parts) &&
+               (reinterpret_cast<uintptr_t>(out16) & 7) == 0 && (!e.residual || (al(e.residual) && e.ld_res % 4 == 0)) &&
+               (!e.gamma || (al(e.gamma) && al(e.beta)));
+    for (int sg = 0; sg < kQfMaxSeg; ++sg) vec = vec && (!e.bias[sg] || al(e.bias[sg]));
+    return vec;
+}
+
+hipError_t launch_qf_epilogue_cast(const QfEpilogue& e, void* out16, long ld_out16, tok_code out_dtype, hipStream_t stream) {
+    if (e.M <= 0) return hipSuccess;
+    if (!qf_epilogue_cast_applies(e, out16, ld_out16)) return hipErrorInvalidValue;   // (the callers check before their first launch)
+    const bool one = e.width <= 1024;
+    if (out_dtype == INFV_TOKENS_BF16) {
+        if (one) INFV_LAUNCH((qf_epilogue_vec_cast_kernel<1, __bf16>), dim3(e.M), dim3(256), 0, stream, e, static_cast<__bf16*>(out16), ld_out16);
+        else INFV_LAUNCH((qf_epilogue_vec_cast_kernel<4, __bf16>), dim3(e.M), dim3(256), 0, stream, e, static_cast<__bf16*>(out16), ld_out16);
+    } else if (out_dtype == INFV_TOKENS_F16) {
+        if (one) INFV_LAUNCH((qf_epilogue_vec_cast_kernel<1, _Float16>), dim3(e.M), dim3(256), 0, stream, e, static_cast<_Float16*>(out16), ld_out16);
+        else INFV_LAUNCH((qf_epilogue_vec_cast_kernel<4, _Float16>), dim3(e.M), dim3(256), 0, stream, e, static_cast<_Float16*>(out16), ld_out16);
+    } else {
+        return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------------
 // The embedding layer of the VideoChat2 Q-former (Qformer.py:54-111): one workgroup per packed encoder input row.  Row m is
 // LN(query_tokens[q]) where src[m] = -(q + 1), else LN(word[src[m]] + position[pos[m]]) -- ONE LayerNorm over query and text rows
