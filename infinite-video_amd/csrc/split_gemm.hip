@@ -22,6 +22,13 @@ __device__ inline void split2(float x, __bf16& hi, __bf16& lo) {
     hi = (__bf16)x;
     lo = (__bf16)(x - (float)hi);
 }
+// a * b split the same way, the residual taken from the exact product (one fma).  That is what the compiler's contraction makes
+// of split2(a * b, ...) wherever the product meets the subtraction directly; spelled out, every row softmax below rounds P_lo the
+// same way whatever stands between the two (the column test of the padded kernels did, in the long one alone).
+__device__ inline void split2_mul(float a, float b, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)(a * b);
+    lo = (__bf16)fmaf(b, a, -(float)hi);
+}
 __device__ inline unsigned pack2(__bf16 a, __bf16 b) {
     return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
 }
@@ -1395,7 +1402,7 @@ __global__ __launch_bounds__(256) void softmax_rows_split_kernel(const float* __
         const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
         __bf16 h[4], l[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) split2(expf(v[k] - mx) * inv, h[k], l[k]);
+        for (int k = 0; k < 4; ++k) split2_mul(expf(v[k] - mx), inv, h[k], l[k]);
         *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
         *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
     }
@@ -1446,7 +1453,7 @@ __global__ __launch_bounds__(256) void softmax_rows_split_reg_kernel(const float
         if (c < len) {
             __bf16 h[4], l[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) split2(v[i][k] * inv, h[k], l[k]);
+            for (int k = 0; k < 4; ++k) split2_mul(v[i][k], inv, h[k], l[k]);
             *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
             *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
         }
@@ -1610,7 +1617,7 @@ __global__ __launch_bounds__(256) void softmax_rows_split_pad_kernel(const float
         if (c < len_pad) {
             __bf16 h[4], l[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) split2(v[i][k] * inv, h[k], l[k]);
+            for (int k = 0; k < 4; ++k) split2_mul(v[i][k], inv, h[k], l[k]);
             *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
             *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
         }
@@ -1652,7 +1659,7 @@ __global__ __launch_bounds__(256) void softmax_rows_split_pad_long_kernel(const 
         const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
         __bf16 h[4], l[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) split2(c + k < len ? expf(v[k] - mx) * inv : 0.f, h[k], l[k]);
+        for (int k = 0; k < 4; ++k) split2_mul(c + k < len ? expf(v[k] - mx) : 0.f, inv, h[k], l[k]);
         *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
         *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
     }

@@ -4,7 +4,6 @@ Small model unless stated: 4 layers (cross layers 0 and 2), 2 heads, hidden 128,
 from the synthetic generators.  ATOL is the project's own 2e-4 (tests/test_vc_gpu.py)."""
 import ctypes as C
 import functools
-import math
 
 import numpy as np
 import pytest
@@ -19,6 +18,7 @@ from oracle.videochat2_oracle import VideoChat2Oracle
 from tests.conftest import record_parity
 from tests.golden.frame_qformer_cases import (FULL, GOLDEN_FRAMES, GOLDEN_PATH, GOLDEN_TAPS, GOLDEN_TOKENS, LN_VISION_EPS, SMALL,
                                               frame_qformer_weights, oracle_weights, vision_rows)
+from tests.golden.softmax_tier_cases import ref64           # the float64 restatement of the image Q-former
 
 pytestmark = pytest.mark.gpu
 ATOL = 2e-4
@@ -76,38 +76,6 @@ def raw_encode(m: FrameQformerEncoder, x: torch.Tensor, out: torch.Tensor, *, ln
 
 def launches() -> int:
     return int(_lib.load().infv_ltm_launch_count())
-
-
-# ---------------------------------------------------------------------------------------------------- float64 restatement
-def ref64(sd: dict, shape: dict, vision: torch.Tensor, ln: bool) -> torch.Tensor:
-    """The image Q-former in float64 (Qformer.py BertEmbeddings + BertEncoder, all-ones masks, eval mode, no long-term memory):
-    vision [F, n, width] (before ``ln_vision`` when ``ln``) -> last hidden state [F, Q, hidden]."""
-    w = {k: torch.from_numpy(np.asarray(v)).double() for k, v in sd.items()}
-    H, Hd = shape["n_heads"], shape["hidden"]
-    dh = Hd // H
-    lin = lambda x, n: F.linear(x, w[n + ".weight"], w[n + ".bias"])
-    lnorm = lambda x, n, eps=1e-12: F.layer_norm(x, (x.size(-1),), w[n + ".weight"], w[n + ".bias"], eps)
-    heads = lambda x: x.reshape(x.size(0), x.size(1), H, dh).permute(0, 2, 1, 3)
-
-    def attend(q, k, v):
-        p = torch.softmax(torch.matmul(heads(q), heads(k).transpose(-1, -2)) / math.sqrt(dh), dim=-1)
-        return torch.matmul(p, heads(v)).permute(0, 2, 1, 3).reshape(q.size(0), q.size(1), Hd)
-
-    k = vision.detach().cpu().double()
-    if ln:
-        k = lnorm(k, "ln_vision", LN_VISION_EPS)
-    h = lnorm(w["query_tokens"], "Qformer.bert.embeddings.LayerNorm").expand(k.size(0), -1, -1)
-    for l in range(shape["n_layers"]):
-        p = f"Qformer.bert.encoder.layer.{l}."
-        a = p + "attention."
-        h = lnorm(lin(attend(lin(h, a + "self.query"), lin(h, a + "self.key"), lin(h, a + "self.value")), a + "output.dense") + h,
-                  a + "output.LayerNorm")
-        if l % 2 == 0:
-            x = p + "crossattention."
-            ctx = attend(lin(h, x + "self.query"), lin(k, x + "self.key"), lin(k, x + "self.value"))
-            h = lnorm(lin(ctx, x + "output.dense") + h, x + "output.LayerNorm")
-        h = lnorm(lin(F.gelu(lin(h, p + "intermediate_query.dense")), p + "output_query.dense") + h, p + "output_query.LayerNorm")
-    return h
 
 
 # ---------------------------------------------------------------------------------------------------- 1. bit anchor
