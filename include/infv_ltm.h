@@ -316,6 +316,28 @@ int infv_ltm_steps_videos_from(const infv_ltm_handle* hs, int32_t V, const int32
                                const int32_t* kbar_chunk0, int32_t T, const float* q, int32_t q_per_chunk, int32_t Q,
                                const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream);
 
+/* The hand-over payload of a consolidate call in ONE kernel launch: everything a peer needs from this handle after
+ * infv_ltm_consolidate, as one fp32 DEVICE buffer
+ *   B [L][n_basis][d] | sticky bin masses [L][n_bins-1] | (with_scores: bias-free scores [L][H][Q][n_basis]) |
+ *   ctx_sum [L][Q][dm] | count
+ * -- the first n_basis (<= num_basis) rows / columns of the handle's padded basis; B and the masses are the bits of
+ * infv_ltm_export_state, the scores those of the blob of infv_ltm_export_chain_state, count = (float)n_chunks, and ctx_sum is
+ * the sum over the call's chunks of ctx [n_chunks][L][Q][dm].  The call refuses where infv_ltm_export_state would, and with
+ * with_scores where infv_ltm_export_chain_state would.  Asynchronous on `stream`, which must be the consolidate call's.
+ * ctx_sum, order of the fp32 additions.  With infv_ltm_set_ctx_sum(h, 1) the update + read-out kernels of a fused
+ * infv_ltm_consolidate / _pooled call with Q <= 32 add up the values they store, and pack_memory only copies the result:
+ *   sum = (...((0 + S_0) + S_1) + ...) over the call's update + read-out launches in launch order; S_b is the left-to-right sum of
+ *   launch b's chunks, starting from the first one.  Launch 0 is the document's first chunk when the call starts a document;
+ *   the sub-batches follow (max_batch_chunks chunks each, 32 for calls under 768 chunks, the last one shorter).
+ * That sum is valid for exactly the (ctx, n_chunks, Q) of the call that produced it, until any entry point steps, resets or
+ * imports the memory.  In every other case -- sums off, the chunk-by-chunk path (dense / psi plans, shapes the fused chain does
+ * not hold), another ctx -- one extra launch adds ctx up first:
+ *   left-to-right sums over blocks of 64 consecutive chunks, each from 0, then the block sums left to right from 0.
+ * The two orders agree to fp32 rounding, not bit for bit. */
+int infv_ltm_set_ctx_sum(infv_ltm_handle h, int32_t on);
+int infv_ltm_pack_memory(infv_ltm_handle h, int32_t n_basis, int32_t Q, const float* ctx, int32_t n_chunks, int32_t with_scores,
+                         float* payload, void* stream);
+
 /* Consolidated memory of one layer: B_past [N,d] (long_term_attention_gibbs.py:220) and the
  * unnormalised sticky bin masses p[n_bins-1] derived from the last scores (:200-202).
  * Export copies device -> caller's DEVICE buffers (async on stream). */

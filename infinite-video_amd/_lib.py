@@ -170,6 +170,8 @@ _SIGNATURES = {
                                              C.c_int32, C.c_int32, C.POINTER(Proj), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "infv_ltm_export_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infv_ltm_import_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Proj), C.c_void_p]),
+    "infv_ltm_set_ctx_sum": (C.c_int, [C.c_void_p, C.c_int32]),
+    "infv_ltm_pack_memory": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "infv_ltm_chain_state_bytes": (C.c_int64, [C.c_void_p, C.c_int32]),
     "infv_ltm_export_chain_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "infv_ltm_import_chain_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -191,6 +191,12 @@ struct infv_ltm_s {
     DeviceBuf psi_Y, psi_E, psi_Eg, psi_alpha;   // general-psi step: resampled rows, edge scores, grid scores / probabilities, read-out weights
     DeviceBuf R_all, planes_all[3];    // one pooling launch per call: every new row of the call (fp32, and as three bf16 planes per sub-batch for the projection GEMM)
     DeviceBuf pool_done;               // ... and its per-sub-batch completion counts
+    // Sum of a consolidate call's outputs, kept by the UC kernels as they store them (infv_ltm_set_ctx_sum; the hand-over payload
+    // of infv_ltm_pack_memory): valid for exactly the (ctx, n_chunks, Q) of the fused call that filled it, until the memory steps again
+    bool ctx_sum_on = false;
+    DeviceBuf ctx_sum;                 // [L][Q][dm]
+    const float* ctx_sum_for = nullptr; int ctx_sum_chunks = 0, ctx_sum_Q = 0;   // ctx_sum_for == nullptr: not valid
+    void ctx_sum_drop() { ctx_sum_for = nullptr; }
     DeviceBuf vid_tab, vid_kbar, vid_P;   // infv_ltm_consolidate_videos with this handle first: video table, pooled frames and projected rows of one step
     int sc = 0;
     int n_bins = 128;
@@ -242,7 +248,7 @@ int check_chain_error(infv_ltm_handle h) {
     if (h->err_host && *reinterpret_cast<volatile unsigned int*>(h->err_host)) {
         const unsigned int code = *reinterpret_cast<volatile unsigned int*>(h->err_host);
         *reinterpret_cast<volatile unsigned int*>(h->err_host) = 0;
-        h->has_memory = false; h->parts = 0; h->k_stale = false; h->pos = 0;
+        h->has_memory = false; h->parts = 0; h->k_stale = false; h->pos = 0; h->ctx_sum_drop();
         if (code == kErrBlobMismatch)
             return fail(INFV_ERR_STATE, "the blob handed to an earlier infv_ltm_import_chain_state was not exported by a handle of "
                                         "this shape (magic / version / L, N, d, dm, H, Q, n_bins in its header); the memory has been reset");
@@ -338,7 +344,7 @@ int chain_step(infv_ltm_handle h, const Plan& plan, const float* R, const float*
                           h->KV[nxt].as<float>(), stream, kbar_rows, (inf && h->cfg.sticky && draw_done) ? tab : nullptr));
     }
     h->cur = nxt;
-    h->has_memory = true;
+    h->has_memory = true; h->ctx_sum_drop();
     const int parts = attend_parts(Q, h->H, h->N);
     {
     Timed t_(h->prof, INFV_KERNEL_ATTEND, stream);
@@ -400,7 +406,7 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
                                     h->B[h->cur].as<float>(), kbar, h->B[nxt].as<float>(), h->N, h->d, h->L, stream));
     }
     h->cur = nxt;
-    h->has_memory = true;
+    h->has_memory = true; h->ctx_sum_drop();
     HIP_TRY(launch_reproject(h->B[h->cur].as<float>(), h->N, h->d, h->dm, h->L, pp, h->KV[h->cur].as<float>(), stream));
     h->k_stale = false;
     {
@@ -684,6 +690,7 @@ int infv_ltm_reset(infv_ltm_handle h) {
     h->parts = 0;
     h->k_stale = false;
     h->pos = 0;
+    h->ctx_sum_drop();
     return INFV_OK;
 }
 
@@ -893,6 +900,7 @@ constexpr int kPollDelay = 0;       // units of 64 clocks between role S's depos
 struct FastPipe {
     infv_ltm_handle h; const Plan& plan; int Q; const ProjPtrs& pp; hipStream_t stream;
     long counter = 0;                // chunks that entered the chain in this call
+    float* ctx_sum = nullptr;        // the handle's output sum, when this call keeps it (every UC launch adds its chunks)
 
     size_t alpha_slot() const { return (size_t)h->L * h->H * Q * h->N; }
     size_t asum_slot() const { return (size_t)h->L * h->H * Q; }
@@ -1079,7 +1087,7 @@ struct FastPipe {
         u.B_prev = h->B[h->cur].as<float>(); u.KV_prev = h->KV[h->cur].as<float>();
         u.B_next = h->B[h->cur ^ 1].as<float>(); u.KV_next = h->KV[h->cur ^ 1].as<float>();
         for (int l = 0; l < h->L; ++l) u.bv[l] = pp.bv[l];
-        u.ctx = ctx;
+        u.ctx = ctx; u.ctx_sum = ctx_sum;
         {
             static long long* dbg = [] { long long* p = nullptr; if (exp_env("INFV_UC_STAMPS")) { (void)hipMalloc(&p, 16 * sizeof(long long)); (void)hipMemset(p, 0, 16 * sizeof(long long)); } return p; }();
             u.dbg = dbg;
@@ -1096,6 +1104,7 @@ struct FastPipe {
         }
         h->cur ^= 1;
         h->has_memory = true;
+        h->ctx_sum_drop();                                      // (consolidate_join declares the finished call's sum valid)
         return INFV_OK;
     }
 };
@@ -1309,6 +1318,8 @@ int consolidate_setup(infv_ltm_handle h, ConsolidateCall& cc, const FastPipe& pi
     }
     HIP_TRY(hipEventRecord(h->ev_start, stream));
     HIP_TRY(hipMemsetAsync(h->mass_acc[0].p, 0, h->mass_acc[0].bytes, stream));   // slot of the call's first step
+    // the call's output sum restarts: behind the previous call's pack on this stream, ahead of the first UC launch (ev_s)
+    if (pipe.ctx_sum) HIP_TRY(hipMemsetAsync(pipe.ctx_sum, 0, cc.chunk_ctx * sizeof(float), stream));
     {   // rings of role S's per-chunk outputs (sized for this call's Q)
         const size_t need_a = (size_t)h->ring * pipe.alpha_slot() * sizeof(float);
         if (need_a > h->alpha_ring.bytes) {
@@ -1736,6 +1747,7 @@ int consolidate_join(infv_ltm_handle h, const ConsolidateCall& cc, const FastPip
         h->parts = 1;
     }
     h->k_stale = true;                                        // K' is re-projected from B on demand (per-call path, continuation)
+    if (pipe.ctx_sum) { h->ctx_sum_for = cc.ctx; h->ctx_sum_chunks = cc.n_chunks; h->ctx_sum_Q = cc.Q; }
     return INFV_OK;
 }
 
@@ -1769,6 +1781,8 @@ static int consolidate_impl(infv_ltm_handle h, const void* k_, const float* kbar
     if (!fused_chain_holds(h, *plan, Q)) return consolidate_per_chunk(h, cc);
     if (int rc = ensure_side_stream(h)) return rc;
     FastPipe pipe{h, *plan, Q, pp, stream};
+    h->ctx_sum_drop();
+    if (h->ctx_sum_on && uc_ctx_sum_supported(Q)) pipe.ctx_sum = h->ctx_sum.as<float>();
     if (int rc = consolidate_setup(h, cc, pipe)) return rc;
     consolidate_schedule(h, cc);
     if (int rc = consolidate_first_chunk(h, cc, pipe)) return rc;
@@ -1983,7 +1997,7 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
             if (len == 0) continue;
             h->cur ^= len & 1;
             h->pos += (uint32_t)len;
-            h->has_memory = true;
+            h->has_memory = true; h->ctx_sum_drop();
             h->parts = parts;
             h->lastQ = Q;
             h->last_fast = false;
@@ -2088,6 +2102,47 @@ int infv_ltm_export_state(infv_ltm_handle h, int32_t layer, float* B, float* bin
     return INFV_OK;
 }
 
+int infv_ltm_set_ctx_sum(infv_ltm_handle h, int32_t on) {
+    if (int rc = check_handle(h)) return rc;
+    if (on) HIP_TRY(h->ctx_sum.reserve((size_t)h->L * h->maxQ * h->dm * sizeof(float)));
+    h->ctx_sum_on = on != 0;
+    h->ctx_sum_drop();
+    return INFV_OK;
+}
+
+int infv_ltm_pack_memory(infv_ltm_handle h, int32_t n_basis, int32_t Q, const float* ctx, int32_t n_chunks, int32_t with_scores,
+                         float* payload, void* stream_) {
+    if (int rc = check_handle(h)) return rc;
+    if (!ctx || !payload || n_chunks < 0 || n_basis <= 0 || n_basis > h->N) return fail(INFV_ERR_INVALID, "pack_memory: bad arguments");
+    if (int rc = check_q(h, Q)) return rc;
+    if (int rc = check_chain_error(h)) return rc;
+    if (!h->has_memory) return fail(INFV_ERR_STATE, "no memory to export (B_past is None)");
+    if (with_scores && (!h->last_fast || h->lastQ != Q || h->parts != 1))
+        return fail(INFV_ERR_STATE, "pack_memory: the scores need a memory whose last step came from infv_ltm_consolidate with Q=%d", Q);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const size_t nC = (size_t)h->L * Q * h->dm;
+    if (!(h->ctx_sum_for == ctx && h->ctx_sum_chunks == n_chunks && h->ctx_sum_Q == Q)) {
+        // no sum kept for these outputs (dense / psi plans, the per-chunk path, sums switched off, someone else's ctx): add them up
+        // now, in ctx_sum_kernel's fixed order; that overwrites whatever sum the handle held
+        h->ctx_sum_drop();
+        if (h->ctx_sum.bytes < (size_t)h->L * h->maxQ * h->dm * sizeof(float)) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(h->ctx_sum.reserve((size_t)h->L * h->maxQ * h->dm * sizeof(float)));
+        }
+        HIP_TRY(launch_ctx_sum(ctx, n_chunks, (long)nC, h->ctx_sum.as<float>(), stream));
+    }
+    PackMemoryArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = h->B[h->cur].as<float>(); a.N = n_basis; a.Np = h->N; a.d = h->d;
+    a.part = h->bin_part[h->pc].as<float>(); a.parts = h->parts; a.pitch = h->n_bins; a.n_mass = h->n_bins - 1;
+    a.scores = with_scores ? h->Sp[h->sc].as<float>() : nullptr;
+    a.ctx_sum = h->ctx_sum.as<float>(); a.count = (float)n_chunks;
+    a.nB = (long)h->L * n_basis * h->d; a.nM = (long)h->L * a.n_mass; a.nS = with_scores ? (long)h->L * h->H * Q * n_basis : 0; a.nC = (long)nC;
+    a.out = payload;
+    HIP_TRY(launch_pack_memory(a, stream));
+    return INFV_OK;
+}
+
 int64_t infv_ltm_chain_state_bytes(infv_ltm_handle h, int32_t Q) {
     if (!h || Q <= 0 || Q > h->maxQ) return -1;
     return (int64_t)sizeof(float) * (kBlobHeaderInts + (int64_t)h->L * h->N * h->d + (int64_t)h->L * h->N * 2 * h->dm +
@@ -2139,7 +2194,7 @@ int infv_ltm_import_chain_state(infv_ltm_handle h, int32_t Q, const void* blob, 
     HIP_TRY(hipMemcpyAsync(h->KV[h->cur].p, in + nB, nKV * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(h->Sp[h->sc].p, in + nB + nKV, nS * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(h->bin_part[h->pc].p, in + nB + nKV + nS, nM * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    h->has_memory = true; h->parts = 1; h->lastQ = Q; h->last_fast = true;
+    h->has_memory = true; h->parts = 1; h->lastQ = Q; h->last_fast = true; h->ctx_sum_drop();
     h->k_stale = true;                 // the K' half came from a fast-path handle: re-projected on demand
     h->carry_scores = true;
     return INFV_OK;
@@ -2175,7 +2230,7 @@ int infv_ltm_import_state(infv_ltm_handle h, int32_t layer, const float* B, cons
     one.wk[0] = proj->wk; one.bk[0] = proj->bk; one.wv[0] = proj->wv; one.bv[0] = proj->bv;
     HIP_TRY(launch_reproject(h->B[h->cur].as<float>() + (size_t)layer * h->N * h->d, h->N, h->d, h->dm, 1, one,
                              h->KV[h->cur].as<float>() + (size_t)layer * h->N * 2 * h->dm, stream));
-    h->has_memory = true;
+    h->has_memory = true; h->ctx_sum_drop();
     // the fused chain's scores (Sp) describe the memory this one replaces: nothing may hand them on any more -- neither
     // export_chain_state nor the one-shot carry of an import_chain_state that no call consumed
     h->last_fast = false;

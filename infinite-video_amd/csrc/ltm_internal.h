@@ -245,6 +245,7 @@ struct UcArgs {
     const float* B_prev; const float* KV_prev; float* B_next; float* KV_next;
     const float* bv[kMaxLayers];
     float* ctx;                     // [n_chunks][L][Q][dm] outputs of the launch's chunks
+    float* ctx_sum;                 // [L][Q][dm] += left-to-right fp32 sum of the launch's ctx (uc_ctx_sum_supported), or nullptr
     long long* dbg;                 // timing experiments: phase stamps of one V' workgroup, or nullptr
     int v16;                        // uc_fast_kernel: V' slices of 16 columns (twice the workgroups, half the read-out each)
     long long* wg_stamps;           // residency experiment (wg_stamps.h), or nullptr
@@ -254,6 +255,7 @@ struct UcArgs {
 hipError_t launch_alpha_rows(float* alpha_ring, long alpha_slot, float* asum_ring, long asum_slot, long slot0, int ring,
                              int n_steps, int rows_per_step, int N, const float* w, float w_out, hipStream_t stream);
 bool uc_supported(int N, int d, int dm, int tabw, int rows_max);
+bool uc_ctx_sum_supported(int Q);
 hipError_t launch_uc(const UcArgs& a, hipStream_t stream);
 
 // S'new[c][l][h][q][r] = (q_h[q]/sqrt(dh)) . Kmat(c,r,l)_h ; optionally cq[l][h][q] = q_h[q].bk_h/sqrt(dh)
@@ -285,6 +287,20 @@ hipError_t launch_psi_ctx(const float* alpha, const float* KV, const ProjPtrs& p
 hipError_t launch_acc_to_part(const unsigned long long* acc, int n_layers, int parts_pitch, float* part, hipStream_t stream);
 // bin_mass[j] = sum over parts of bin_part[layer][p][j]
 hipError_t launch_sum_parts(const float* bin_part_layer, int parts, int pitch, float* bin_mass, hipStream_t stream);
+
+// ---- hand-over payload (infv_ltm_pack_memory) ----
+constexpr int kCtxSumBlock = 64;   // chunks per sequential block of the fallback sum (include/infv_ltm.h states the order)
+constexpr int kCtxSumWaves = 16;
+hipError_t launch_ctx_sum(const float* ctx, int n_chunks, long E, float* out, hipStream_t stream);
+struct PackMemoryArgs {
+    const float* B; int N, Np, d;                       // [L][Np][d]: the first N rows of every layer
+    const float* part; int parts, pitch, n_mass;        // [L][parts][pitch] sticky partial rows: n_mass bins per layer
+    const float* scores;                                // [L][H][Q][Np] bias-free scores, or nullptr (nS = 0)
+    const float* ctx_sum; float count;
+    long nB, nM, nS, nC;                                // floats per segment
+    float* out;
+};
+hipError_t launch_pack_memory(const PackMemoryArgs& a, hipStream_t stream);
 
 }  // namespace infv
 

@@ -1783,3 +1783,75 @@ hipError_t launch_sum_parts(const float* bin_part_layer, int parts, int pitch, f
     return hipGetLastError();
 }
 }  // namespace infv
+
+// ---- the hand-over payload (infv_ltm_pack_memory): one launch writes every segment of video_memory.unpack_memory's layout ----
+namespace infv {
+// Fallback sum of a call's outputs, ctx [n_chunks][E] -> out [E], in a fixed order: left-to-right fp32 sums over blocks of
+// kCtxSumBlock consecutive chunks, then the blocks left to right.  A workgroup owns 64 consecutive elements (E % 64 == 0: dm is a
+// multiple of the head size); its waves take kCtxSumWaves blocks at a time and wave 0 adds their sums in block order.
+__global__ __launch_bounds__(64 * kCtxSumWaves) void ctx_sum_kernel(const float* __restrict__ ctx, int n_chunks, long E, float* __restrict__ out) {
+    __shared__ float part[kCtxSumWaves][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long e = (long)blockIdx.x * 64 + lane;
+    const int n_blocks = (n_chunks + kCtxSumBlock - 1) / kCtxSumBlock;
+    float total = 0.f;
+    for (int b0 = 0; b0 < n_blocks; b0 += kCtxSumWaves) {
+        const int b = b0 + wave;
+        float acc = 0.f;
+        if (b < n_blocks && e < E) {
+            const int c0 = b * kCtxSumBlock, c1 = min(c0 + kCtxSumBlock, n_chunks);
+            const float* p = ctx + (long)c0 * E + e;
+#pragma unroll 8
+            for (int c = c0; c < c1; ++c, p += E) acc += *p;
+        }
+        part[wave][lane] = acc;
+        __syncthreads();
+        if (wave == 0) {
+            const int nb = min(kCtxSumWaves, n_blocks - b0);
+            for (int w = 0; w < nb; ++w) total += part[w][lane];
+        }
+        __syncthreads();
+    }
+    if (wave == 0 && e < E) out[e] = total;
+}
+hipError_t launch_ctx_sum(const float* ctx, int n_chunks, long E, float* out, hipStream_t stream) {
+    if (E <= 0 || E % 64) return hipErrorInvalidValue;
+    INFV_LAUNCH(ctx_sum_kernel, dim3((unsigned)(E / 64)), dim3(64 * kCtxSumWaves), 0, stream, ctx, n_chunks, E, out);
+    return hipGetLastError();
+}
+
+// [ B_0 .. B_{L-1} (the first N of Np rows) | masses (sum_parts_kernel's fp64 sum of the partial rows, first n_mass bins) |
+//   scores [L][H][Q][N] (optional) | ctx_sum | count ]: one thread per payload element
+__global__ void pack_memory_kernel(PackMemoryArgs a) {
+    long e = (long)blockIdx.x * 256 + threadIdx.x;
+    float* o = a.out + e;
+    if (e < a.nB) {
+        const long per = (long)a.N * a.d, l = e / per;
+        *o = a.B[l * (long)a.Np * a.d + (e - l * per)];
+        return;
+    }
+    e -= a.nB;
+    if (e < a.nM) {
+        const int l = (int)(e / a.n_mass), j = (int)(e - (long)l * a.n_mass);
+        const float* part = a.part + (long)l * a.parts * a.pitch;
+        double acc = 0.0;
+        for (int p = 0; p < a.parts; ++p) acc += (double)part[(long)p * a.pitch + j];
+        *o = (float)acc;
+        return;
+    }
+    e -= a.nM;
+    if (e < a.nS) {
+        const long row = e / a.N;
+        *o = a.scores[row * a.Np + (e - row * a.N)];
+        return;
+    }
+    e -= a.nS;
+    if (e < a.nC) { *o = a.ctx_sum[e]; return; }
+    if (e == a.nC) *o = a.count;
+}
+hipError_t launch_pack_memory(const PackMemoryArgs& a, hipStream_t stream) {
+    const long total = a.nB + a.nM + a.nS + a.nC + 1;
+    INFV_LAUNCH(pack_memory_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+}  // namespace infv

@@ -146,6 +146,7 @@ __global__ __launch_bounds__(kUcNT) void uc_kernel(UcArgs a) {
     const bool stamp_me = a.dbg != nullptr && tid == 0 && blockIdx.x == sb && a.n_chunks > 4;   // first V' slice of layer 0
 #define USTAMP(k) do { if (stamp_me && i == 3) a.dbg[k] = wall_clock64(); } while (0)
     prefetch(0);
+    float csum[4] = {0.f, 0.f, 0.f, 0.f};               // a.ctx_sum: running sums of the ctx values this lane stores (one query tile)
     for (int i = 0; i < a.n_chunks; ++i) {
         USTAMP(0);
         const long slot = slot_cur;                      // ring slot of this chunk's alpha / tab
@@ -275,7 +276,9 @@ __global__ __launch_bounds__(kUcNT) void uc_kernel(UcArgs a) {
                         const int rr = 16 * qt + 4 * g + r;
                         if (rr < qn) {
                             const int col = 16 * ct + c;
-                            ctx[(long)(q0 + rr) * dm + col] = tot[r] + asum[rr] * bv[col];
+                            const float v = tot[r] + asum[rr] * bv[col];
+                            ctx[(long)(q0 + rr) * dm + col] = v;
+                            csum[r] += v;
                         }
                     }
                 }
@@ -287,6 +290,16 @@ __global__ __launch_bounds__(kUcNT) void uc_kernel(UcArgs a) {
         //  cur and red -- so one barrier is needed before Asm / asum are overwritten)
         if (isV && one_qtile) lds_barrier();
         USTAMP(7);
+    }
+    // ---- a.ctx_sum: this launch's sums join the call's (every (l, q, col) belongs to one lane; launches are stream-ordered) ----
+    if (a.ctx_sum != nullptr && isV && one_qtile && (wave >> 2) == 0) {
+        const int c = lane & 15, g = lane >> 4, qt = wave & 1, ct = (wave >> 1) & 1;
+        float* cs = a.ctx_sum + (long)l * Q * dm + col0 + 16 * ct + c;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rr = 16 * qt + 4 * g + r;
+            if (rr < Q) cs[(long)rr * dm] = cs[(long)rr * dm] + csum[r];
+        }
     }
     // ---- write the slice back ----
     for (int e = tid; e < N * kUcCols; e += kUcNT) {
@@ -460,6 +473,7 @@ __global__ __launch_bounds__(kUcNT) void uc_fast_kernel(UcArgs a) {
     const float* bvp = a.bv[l] + col0;
     const float bvc = isV ? bvp[16 * ct + c] : 0.f;
     const bool stamp_me = a.dbg != nullptr && tid == 0 && blockIdx.x == sb && a.n_chunks > 4;
+    floatx4 csum = {0.f, 0.f, 0.f, 0.f};                // a.ctx_sum: running sums of the ctx values this lane stores
     lds_barrier();
     for (int i = 0; i < a.n_chunks; ++i) {
         USTAMP(0);
@@ -549,11 +563,24 @@ __global__ __launch_bounds__(kUcNT) void uc_fast_kernel(UcArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int rr = 16 * qt + 4 * g + r;
-                    if (rr < Q) ctx[(long)rr * dm + 16 * ct + c] = tot[r] + asr[r] * bvc;
+                    if (rr < Q) {
+                        const float v = tot[r] + asr[r] * bvc;
+                        ctx[(long)rr * dm + 16 * ct + c] = v;
+                        csum[r] += v;
+                    }
                 }
             }
         }
         USTAMP(7);
+    }
+    // ---- a.ctx_sum: this launch's sums join the call's (every (l, q, col) belongs to one lane; launches are stream-ordered) ----
+    if (a.ctx_sum != nullptr && isV && ks == 0) {
+        float* cs = a.ctx_sum + (long)l * Q * dm + col0 + 16 * ct + c;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rr = 16 * qt + 4 * g + r;
+            if (rr < Q) cs[(long)rr * dm] = cs[(long)rr * dm] + csum[r];
+        }
     }
     lds_barrier();
     // ---- write the slice back ----
@@ -564,6 +591,8 @@ __global__ __launch_bounds__(kUcNT) void uc_fast_kernel(UcArgs a) {
     }
     wg_stamp_end(a.wg_stamps);
 }
+
+bool uc_ctx_sum_supported(int Q) { return Q <= kUcQ; }   // (both kernels: one query tile, four running sums per lane)
 
 bool uc_fast_supported(int N, int Q, int tabw) { return tabw == 4 && Q <= kUcQ && N % 64 == 0 && N <= 256; }
 

@@ -107,6 +107,7 @@ class LTMEngine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.infv_ltm_create(C.byref(cfg), C.byref(handle)))
         self._h = handle
+        self.ctx_sum_on = False
         self._plans = {}
         self._token_dtype = torch.float32
         self.rng_seed, self.rng_stream = None, 0
@@ -446,6 +447,38 @@ class LTMEngine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.infv_ltm_import_state(self._h, layer, _ptr(B), _ptr(bin_mass), C.byref(p),
                                                        _stream(self.device)))
+
+    def set_ctx_sum(self, on: bool = True):
+        """Have the fused ``consolidate`` keep the sum of its outputs as it stores them (infv_ltm_set_ctx_sum): ``pack_memory``
+        of that call's ``ctx`` is then one launch that re-reads none of them."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.infv_ltm_set_ctx_sum(self._h, int(bool(on))))
+        self.ctx_sum_on = bool(on)
+
+    def payload_numel(self, Q: int, with_scores: bool = False) -> int:
+        """Floats of the hand-over payload: B | bin masses | (scores) | ctx_sum | count (video_memory.unpack_memory's layout)."""
+        return (self.L * self.N * self.d + self.L * (NB_BINS - 1) + (self.L * self.H * Q * self.N if with_scores else 0) +
+                self.L * Q * self.dm + 1)
+
+    def pack_memory(self, ctx: torch.Tensor, with_scores: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The hand-over payload of the ``consolidate`` call that returned ``ctx`` [C, L, Q, dm], written by one kernel launch
+        (infv_ltm_pack_memory; one more when the engine holds no sum for this ``ctx``): what ``video_memory.pack_local_memory``
+        assembles, with ``ctx.sum(0)`` in the order include/infv_ltm.h states."""
+        _check_dev(ctx, self.device, "ctx")
+        if ctx.dim() != 4 or ctx.shape[1] != self.L or ctx.shape[3] != self.dm or ctx.shape[2] > self.max_q or not ctx.is_contiguous():
+            raise ValueError(f"ctx must be contiguous [C, {self.L}, Q <= {self.max_q}, {self.dm}], got {tuple(ctx.shape)}")
+        Cn, Q = int(ctx.shape[0]), int(ctx.shape[2])
+        if out is None:
+            payload = torch.empty(self.payload_numel(Q, with_scores), device=self.device, dtype=torch.float32)
+        else:
+            payload = out
+            _check_dev(payload, self.device, "out")
+            if payload.dim() != 1 or payload.numel() != self.payload_numel(Q, with_scores) or not payload.is_contiguous():
+                raise ValueError(f"out must be a contiguous fp32 vector of {self.payload_numel(Q, with_scores)} elements")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.infv_ltm_pack_memory(self._h, self.N, Q, _ptr(ctx), Cn, int(bool(with_scores)), _ptr(payload),
+                                                     _stream(self.device)))
+        return payload
 
     def export_chain_state(self, Q: int) -> torch.Tensor:
         """Everything ``consolidate`` carries from chunk to chunk as one fp32 device tensor (infv_ltm_export_chain_state):

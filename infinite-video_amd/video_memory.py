@@ -57,7 +57,11 @@ class ConsolidatedMemory:
 
 def pack_local_memory(engine, ctx_local: torch.Tensor, with_scores: bool = False) -> torch.Tensor:
     """Flatten this rank's consolidated memory into one fp32 payload (one collective, not four).  ``with_scores``: also the last
-    step's scores [L, H, Q, N] (SURVEY.md section 8e's full payload: +0.79 MB per rank at the headline shape)."""
+    step's scores [L, H, Q, N] (SURVEY.md section 8e's full payload: +0.79 MB per rank at the headline shape).  An engine with
+    ``pack_memory`` writes it in one kernel launch (``ctx_sum`` then in the library's stated order: equal to ``ctx_local.sum(0)`` to
+    fp32 rounding); the torch assembly below serves every other engine."""
+    if hasattr(engine, "pack_memory"):                       # one launch on the HIP path (LTMEngine.pack_memory)
+        return engine.pack_memory(ctx_local, with_scores)
     L = engine.L
     parts = []
     masses = []
@@ -162,6 +166,8 @@ def consolidate_video(engine, k_local: torch.Tensor, q: torch.Tensor, projs: Seq
         blob = torch.empty(engine.chain_state_numel(Q), device=k_local.device, dtype=torch.float32)
         blob = _recv(blob, rank - 1, group)
         engine.import_chain_state(Q, blob)
+    if getattr(engine, "ctx_sum_on", None) is False:
+        engine.set_ctx_sum(True)                     # once per engine: the call below keeps the sum that the pack hands over
     ctx = engine.consolidate(k_local, q, projs, u_local, new_doc=not (chained and rank > 0))
     if chained and rank < world - 1:
         blob = engine.export_chain_state(Q)
