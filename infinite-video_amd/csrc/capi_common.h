@@ -3,6 +3,7 @@
 #include "knobs.h"
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <initializer_list>
 
 #include "../../include/infv_ltm.h"
 #include "vqf_internal.h"
@@ -42,6 +43,21 @@ struct DeviceBuf {
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+
+// Workspace growth: every listed buffer ends up with at least its size (0: left alone).  If any of them must grow, the device is
+// synchronised once, before the first is freed -- work in flight may still read the old allocation.  No host allocation: this runs
+// on the launch-bound per-chunk path.  *grew (optional): whether a buffer was reallocated, i.e. lost its contents.
+struct BufNeed { DeviceBuf& buf; size_t bytes; };
+inline hipError_t reserve_all(std::initializer_list<BufNeed> needs, bool* grew = nullptr) {
+    bool grow = false;
+    for (const BufNeed& n : needs) grow = grow || n.bytes > n.buf.bytes;
+    if (grew) *grew = grow;
+    if (!grow) return hipSuccess;
+    hipError_t e = hipDeviceSynchronize();
+    for (const BufNeed& n : needs)
+        if (e == hipSuccess) e = n.buf.reserve(n.bytes);
+    return e;
+}
 
 template <class T>
 hipError_t upload(DeviceBuf& buf, const T* host, size_t n) {

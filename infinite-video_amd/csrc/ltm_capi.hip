@@ -487,9 +487,7 @@ int project_chunks(infv_ltm_handle h, const Plan& plan, bool inf, const float* k
     DeviceBuf& Rw = h->R_ws[set];
     DeviceBuf& Pw = h->P_ws[set];
     const size_t needR = (size_t)(M ? M : 1) * h->d * sizeof(float), needP = (size_t)(M ? M : 1) * n_cols * sk * sizeof(float);
-    if (needR > Rw.bytes || needP > Pw.bytes) HIP_TRY(hipDeviceSynchronize());   // growing frees: nothing may still read it
-    HIP_TRY(Rw.reserve(needR));
-    HIP_TRY(Pw.reserve(needP));
+    HIP_TRY(reserve_all({{Rw, needR}, {Pw, needP}}));          // growing frees: nothing may still read it
     {
     Timed t_(h->prof, INFV_KERNEL_ROWS, stream);
     HIP_TRY(launch_rows(kbar, n_chunks, T, h->d, op.view(), Rw.as<float>(), stream));
@@ -747,7 +745,7 @@ int infv_ltm_pool_rows(infv_ltm_handle h, const void* k, int32_t n_chunks, int32
     }
     // widths without a pool_rows2 shape: the two kernels, one chunk group at a time through the pooled-frame workspace
     const size_t need = (size_t)n_chunks * T * h->d * sizeof(float);
-    if (need > h->kbar_side[0].bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->kbar_side[0].reserve(need)); }
+    HIP_TRY(reserve_all({{h->kbar_side[0], need}}));
     HIP_TRY(launch_pool(k, h->tok, h->kbar_side[0].as<float>(), (int64_t)n_chunks * T, h->P, h->d, stream));
     HIP_TRY(launch_rows(h->kbar_side[0].as<float>(), n_chunks, T, h->d, plan->inf.view(), R, stream));
     return INFV_OK;
@@ -773,7 +771,7 @@ int infv_ltm_step(infv_ltm_handle h, const float* kbar, int32_t T, const float* 
     const long n_cols = (long)h->L * 2 * h->dm;
     const int sk_max = project_splitk(op.rows > 0 ? op.rows : 1, h->d);
     const size_t needP = (size_t)(op.rows ? op.rows : 1) * n_cols * sk_max * sizeof(float);
-    if (needP > h->P_ws[0].bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->P_ws[0].reserve(needP)); }
+    HIP_TRY(reserve_all({{h->P_ws[0], needP}}));
     StepDraw dr;
     memset(&dr, 0, sizeof(dr));
     if (inf && h->cfg.sticky) {
@@ -787,7 +785,7 @@ int infv_ltm_step(infv_ltm_handle h, const float* kbar, int32_t T, const float* 
         // the draw also resolves the gather table of the step (per layer: source box of every (box, slot) entry)
         const size_t need_t = (size_t)h->L * h->N * op.tabw * sizeof(int32_t);
         if (op.tabw > 0 && op.slot_tab.p != nullptr) {
-            if (need_t > h->step_tab.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->step_tab.reserve(need_t)); }
+            HIP_TRY(reserve_all({{h->step_tab, need_t}}));
             dr.slot_tab = op.slot_tab.as<int32_t>(); dr.tab_entries = h->N * op.tabw; dr.tab_out = h->step_tab.as<int32_t>();
         }
     }
@@ -854,7 +852,7 @@ int infv_ltm_consolidate_q(infv_ltm_handle h, const void* k, int32_t n_chunks, i
     if (new_doc) infv_ltm_reset(h);
     if (n_chunks == 0) return INFV_OK;
     const size_t need = (size_t)n_chunks * T * h->d * sizeof(float);
-    if (need > h->kbar_all.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->kbar_all.reserve(need)); }
+    HIP_TRY(reserve_all({{h->kbar_all, need}}));
     if (int rc = infv_ltm_pool(h, k, (int64_t)n_chunks * T, h->kbar_all.as<float>(), stream)) return rc;
     return infv_ltm_steps(h, h->kbar_all.as<float>(), n_chunks, T, q, Q, proj, u, ctx, stream);
 }
@@ -1170,8 +1168,7 @@ int batch_scores(infv_ltm_handle h, const Operator& op, int n_chunks, const floa
                  const ProjPtrs& pp, int set, int sk, long ss, bool want_cq, hipStream_t stream) {
     const long n_cols = (long)h->L * 2 * h->dm;
     const size_t need = (size_t)n_chunks * h->L * h->H * Q * (op.rows ? op.rows : 1) * sizeof(float);
-    if (need > h->Snew_ws[set].bytes) HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(h->Snew_ws[set].reserve(need));
+    HIP_TRY(reserve_all({{h->Snew_ws[set], need}}));
     Timed t_(h->prof, INFV_KERNEL_SCORES, stream);
     HIP_TRY(launch_new_scores(q, Q, h->H, h->L, n_chunks, op.rows, h->P_ws[set].as<float>(), (long)op.rows * n_cols, n_cols,
                               2L * h->dm, sk, ss, pp, h->Snew_ws[set].as<float>(), want_cq ? h->cqbuf.as<float>() : nullptr,
@@ -1338,10 +1335,7 @@ int consolidate_setup(infv_ltm_handle h, ConsolidateCall& cc, const FastPipe& pi
     if (h->proj_x6 && h->d % 32 == 0 && n_rows % 8 == 0) {
         // bf16 planes of the projection GEMM's weight rows [Wv_0 ; ... ; Wv_{L-1} ; q~] (the caller's weights may change between calls)
         const size_t szW = (size_t)n_rows * h->d * sizeof(__bf16);
-        if (szW > h->w3[0].bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            for (int i = 0; i < 3; ++i) HIP_TRY(h->w3[i].reserve(szW));
-        }
+        HIP_TRY(reserve_all({{h->w3[0], szW}, {h->w3[1], szW}, {h->w3[2], szW}}));
         for (int l = 0; l < h->L; ++l)
             HIP_TRY(launch_split3_rows(pp.wv[l], h->d, h->dm, h->d, h->w3[0].p, h->w3[1].p, h->w3[2].p, (long)l * h->dm, n_rows, stream));
         HIP_TRY(launch_split3_rows(h->qt_buf.as<float>(), h->d, (long)h->L * h->H * cc.Q, h->d, h->w3[0].p, h->w3[1].p, h->w3[2].p,
@@ -1357,7 +1351,7 @@ int consolidate_setup(infv_ltm_handle h, ConsolidateCall& cc, const FastPipe& pi
     // chain_batch_kernel) generate their own.
     if ((cc.u || h->rng_on) && h->cfg.sticky && chain_batch3_shape_ok(1, plan.sticky().points_ok, plan.inf.rows, h->S, cc.Q)) {
         const size_t need_u = (size_t)cc.n_chunks * cc.chunk_u * sizeof(float);
-        if (need_u > h->uf_all.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->uf_all.reserve(need_u)); }
+        HIP_TRY(reserve_all({{h->uf_all, need_u}}));
         if (cc.u) HIP_TRY(launch_round_up_uniforms(cc.u, h->uf_all.as<float>(), (long)cc.n_chunks * (long)cc.chunk_u, stream));
         else HIP_TRY(launch_rng_fill(h->rng_view(h->pos), cc.n_chunks, h->L, h->S, nullptr, h->uf_all.as<float>(), stream));
         cc.uf = h->uf_all.as<float>();
@@ -1431,8 +1425,7 @@ int consolidate_first_chunk(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pi
     if (!h->has_memory) {
         const float* kb0 = cc.kbar_pre;
         if (!kb0) {
-            if ((size_t)cc.T * h->d * sizeof(float) > h->kbar_ws.bytes) HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h->kbar_ws.reserve((size_t)cc.T * h->d * sizeof(float)));
+            HIP_TRY(reserve_all({{h->kbar_ws, (size_t)cc.T * h->d * sizeof(float)}}));
             if (int rc = infv_ltm_pool(h, cc.k, cc.T, h->kbar_ws.as<float>(), cc.stream_)) return rc;
             kb0 = h->kbar_ws.as<float>();
         }
@@ -1538,12 +1531,9 @@ int project_values_on_uc(infv_ltm_handle h, const ConsolidateCall& cc, int set, 
     // split-bf16 contraction (three bf16 MFMA products, ~1e-5 relative); bench.py then labels its dtype accordingly
     if (h->v_split && h->d % 64 == 0 && v_cols % 128 == 0) {
         const size_t szW = (size_t)v_cols * h->d * 2, szR = (size_t)h->maxC * plan.inf.rows * h->d * 2;
-        if (szW > h->wv_hi.bytes || szR > h->R_hi.bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h->wv_hi.reserve(szW)); HIP_TRY(h->wv_lo.reserve(szW));
-            HIP_TRY(h->R_hi.reserve(szR)); HIP_TRY(h->R_lo.reserve(szR));
-            h->wv_split_valid = false;
-        }
+        bool grew = false;
+        HIP_TRY(reserve_all({{h->wv_hi, szW}, {h->wv_lo, szW}, {h->R_hi, szR}, {h->R_lo, szR}}, &grew));
+        if (grew) h->wv_split_valid = false;
         if (!h->wv_split_valid) {
             for (int l = 0; l < h->L; ++l)
                 HIP_TRY(launch_split_rows(pp.wv[l], h->d, h->dm, h->d, h->wv_hi.as<__bf16>() + (size_t)l * h->dm * h->d,
@@ -1923,12 +1913,7 @@ int videos_impl(const char* name, const infv_ltm_handle* hs, int32_t V, const in
         const size_t need_t = (size_t)group * sizeof(VideoDesc);
         const size_t need_k = (size_t)group * T * d * sizeof(float);
         const size_t need_p = (size_t)group * (rows_max > 0 ? rows_max : 1) * L * 2 * dm * sizeof(float);
-        if (need_t > h0->vid_tab.bytes || need_k > h0->vid_kbar.bytes || need_p > h0->vid_P.bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h0->vid_tab.reserve(need_t));
-            HIP_TRY(h0->vid_kbar.reserve(need_k));
-            HIP_TRY(h0->vid_P.reserve(need_p));
-        }
+        HIP_TRY(reserve_all({{h0->vid_tab, need_t}, {h0->vid_kbar, need_k}, {h0->vid_P, need_p}}));
     }
     const int mask_step = new_doc ? 1 : 0;
     const int parts = attend_parts(Q, h0->H, N);
@@ -2125,10 +2110,7 @@ int infv_ltm_pack_memory(infv_ltm_handle h, int32_t n_basis, int32_t Q, const fl
         // no sum kept for these outputs (dense / psi plans, the per-chunk path, sums switched off, someone else's ctx): add them up
         // now, in ctx_sum_kernel's fixed order; that overwrites whatever sum the handle held
         h->ctx_sum_drop();
-        if (h->ctx_sum.bytes < (size_t)h->L * h->maxQ * h->dm * sizeof(float)) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h->ctx_sum.reserve((size_t)h->L * h->maxQ * h->dm * sizeof(float)));
-        }
+        HIP_TRY(reserve_all({{h->ctx_sum, (size_t)h->L * h->maxQ * h->dm * sizeof(float)}}));
         HIP_TRY(launch_ctx_sum(ctx, n_chunks, (long)nC, h->ctx_sum.as<float>(), stream));
     }
     PackMemoryArgs a;

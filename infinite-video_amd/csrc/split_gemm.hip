@@ -901,8 +901,8 @@ __global__ __launch_bounds__(256) void split_transpose_kernel(const float* __res
     }
 }
 
-hipError_t launch_split_transpose(const float* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
-                                  hipStream_t stream, float* kbar, int P) {
+static hipError_t launch_split_transpose(const float* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
+                                         hipStream_t stream, float* kbar, int P) {
     if (n % 32 || d % 64) return hipErrorInvalidValue;
     if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
     INFV_LAUNCH(split_transpose_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, F, n, d,
@@ -974,8 +974,8 @@ __global__ __launch_bounds__(256) void split_transpose_f16_kernel(const _Float16
     }
 }
 
-hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
-                                      hipStream_t stream, float* kbar, int P) {
+static hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
+                                             hipStream_t stream, float* kbar, int P) {
     if (n % 32 || d % 64) return hipErrorInvalidValue;
     if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
     INFV_LAUNCH(split_transpose_f16_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const _Float16*>(F), n, d,
@@ -1045,7 +1045,7 @@ __global__ __launch_bounds__(256) void split_transpose_f8_kernel(const unsigned 
     }
 }
 
-hipError_t launch_split_transpose_f8(const void* F, int nb, int n, int d, void* Fh, void* Th, hipStream_t stream, float* kbar, int P) {
+static hipError_t launch_split_transpose_f8(const void* F, int nb, int n, int d, void* Fh, void* Th, hipStream_t stream, float* kbar, int P) {
     if (n % 32 || d % 64 || !Fh || !Th) return hipErrorInvalidValue;
     if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
     INFV_LAUNCH(split_transpose_f8_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const unsigned char*>(F), n, d,
@@ -1103,7 +1103,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const __bf16* __res
     }
 }
 
-hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, hipStream_t stream, float* kbar, int P) {
+static hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, hipStream_t stream, float* kbar, int P) {
     if (n % 32 || d % 64) return hipErrorInvalidValue;
     if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
     INFV_LAUNCH(transpose_bf16_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const __bf16*>(F), n, d,

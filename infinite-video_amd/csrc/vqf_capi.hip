@@ -88,7 +88,7 @@ int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
     const int width = c.n_lin * c.n_out;
     const int sk = c.inv ? 1 : qf_pick_splitk(c.M, width, c.K, 1);
     const size_t need = (size_t)sk * c.M * width * sizeof(float);
-    if (need > h->part.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->part.reserve(need)); }
+    HIP_TRY(reserve_all({{h->part, need}}));
     QfGemm g{};
     g.A = c.x; g.lda = c.K; g.strideA = 0;
     for (int i = 0; i < c.n_lin; ++i) g.B[i] = c.lin[i]->w;
@@ -141,13 +141,14 @@ static double plane_bytes(tok_code tok, bool ln, bool padded = false) {
     return ln ? 8.0 : tok == INFV_TOKENS_BF16 ? (padded ? 4.0 : 2.0) : tok == INFV_TOKENS_F8E4M3 ? 4.0 : 8.0;
 }
 
-// fp16 / bf16 / fp8 tokens where the split path does not apply: an fp32 copy in the handle's workspace for today's fp32 kernels
-static int upcast_tokens(infv_vqf_s* h, const void* frames, tok_code tok, size_t elems, const float** out, hipStream_t stream) {
-    if (elems * sizeof(float) > h->up.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->up.reserve(elems * sizeof(float))); }
+// fp16 / bf16 / fp8 tokens where the split path does not apply: frames / tok become an fp32 copy in the handle's workspace, for the fp32 kernels
+static int fp32_tokens_unless_split(infv_vqf_s* h, const void*& frames, tok_code& tok, int n_tokens, size_t elems, hipStream_t stream) {
+    if (tok == INFV_TOKENS_F32 || split_path(h, n_tokens)) return INFV_OK;
+    HIP_TRY(reserve_all({{h->up, elems * sizeof(float)}}));
     if (tok == INFV_TOKENS_F16) HIP_TRY(launch_upcast_f16(frames, h->up.as<float>(), (long)elems, stream));
     else if (tok == INFV_TOKENS_F8E4M3) HIP_TRY(launch_upcast_f8(frames, h->up.as<float>(), (long)elems, stream));
     else HIP_TRY(launch_upcast_bf16(frames, h->up.as<float>(), (long)elems, stream));
-    *out = h->up.as<float>();
+    frames = h->up.p; tok = INFV_TOKENS_F32;
     return INFV_OK;
 }
 
@@ -163,73 +164,41 @@ static int prepare_split(infv_vqf_s* h, const void* frames_, tok_code tok, int n
                          hipStream_t stream, int dst0 = 0, int cap = 0,
                          const TokLn* ln = nullptr /* the planes (and means) of token_ln(frames); ln->stats addresses frames_' first token */,
                          int n_live = 0 /* > 0 and != n_tokens: frames_ holds n_live tokens a chunk, the planes n_tokens = ceil(n_live / 64) * 64 (pad: zeros) */) {
-    const int d = h->cfg.enc_width;
+    const int d = h->cfg.enc_width, P = h->cfg.tokens_per_frame;
+    const bool padded = n_live > 0 && n_live != n_tokens;   // padded planes: no frame means
+    if (padded && kbar) return fail(INFV_ERR_INVALID, "prepare_split: no frame means from padded planes");
+    // Which planes the pass writes.  A normalised value is a general fp32 number, as an fp32 / fp16 token is: all four.  An e4m3
+    // value has no lo piece: F_hi and T_hi.  bf16 tokens are read in place, only the transposed copy is written -- except into padded
+    // planes, whose stride the caller's buffer does not have: F_hi too.
+    const bool lo = ln || tok == INFV_TOKENS_F32 || tok == INFV_TOKENS_F16;
+    const bool hi = lo || tok == INFV_TOKENS_F8E4M3 || padded;
     const size_t szF = (size_t)(cap > dst0 + nb ? cap : dst0 + nb) * n_tokens * d * 2;
     const size_t d0 = (size_t)dst0 * n_tokens * d;
     DeviceBuf& Fh = whole ? h->wFh : h->sFh; DeviceBuf& Fl = whole ? h->wFl : h->sFl;
     DeviceBuf& Th = whole ? h->wTh : h->sTh; DeviceBuf& Tl = whole ? h->wTl : h->sTl;
-    if (n_live > 0 && n_live != n_tokens) {                  // padded planes: no frame means, bf16 tokens get their F_hi too
-        if (kbar) return fail(INFV_ERR_INVALID, "prepare_split: no frame means from padded planes");
-        const bool own_hi = !ln && (tok == INFV_TOKENS_BF16 || tok == INFV_TOKENS_F8E4M3);
-        if (szF > Fh.bytes || szF > Th.bytes || (!own_hi && (szF > Fl.bytes || szF > Tl.bytes))) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(Fh.reserve(szF)); HIP_TRY(Th.reserve(szF));
-            if (!own_hi) { HIP_TRY(Fl.reserve(szF)); HIP_TRY(Tl.reserve(szF)); }
-        }
-        for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
-            const int n = nb - c0 < 32768 ? nb - c0 : 32768;
-            const size_t o = (size_t)c0 * n_tokens * d, oi = (size_t)c0 * n_live * d;
-            HIP_TRY(launch_token_pass_pad(tok_at(frames_, tok, (long)oi), tok, n, n_live, n_tokens, d, ln ? ln->stats + 2 * (size_t)c0 * n_live : nullptr,
-                                          ln ? ln->gamma : nullptr, ln ? ln->beta : nullptr, Fh.as<__bf16>() + d0 + o,
-                                          own_hi ? nullptr : Fl.as<__bf16>() + d0 + o, Th.as<__bf16>() + d0 + o,
-                                          own_hi ? nullptr : Tl.as<__bf16>() + d0 + o, stream));
-        }
-        *ref = SplitRef{Fh.as<__bf16>(), own_hi ? nullptr : Fl.as<__bf16>(), Th.as<__bf16>(), own_hi ? nullptr : Tl.as<__bf16>()};
-        return INFV_OK;
-    }
-    const int P = h->cfg.tokens_per_frame;
-    if (tok == INFV_TOKENS_BF16 && !ln) {                    // read in place: only the transposed copy is written
-        if (szF > Th.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(Th.reserve(szF)); }
-        const __bf16* fb = static_cast<const __bf16*>(frames_);
-        for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
-            const int n = nb - c0 < 32768 ? nb - c0 : 32768;
-            const size_t o = (size_t)c0 * n_tokens * d;
-            HIP_TRY(launch_token_pass(fb + o, tok, n, n_tokens, d, nullptr, nullptr, Th.as<__bf16>() + d0 + o, nullptr, stream,
-                                      kbar ? kbar + (size_t)c0 * (n_tokens / P) * d : nullptr, P));
-        }
-        *ref = SplitRef{fb, nullptr, Th.as<__bf16>(), nullptr};   // (Fh: THESE chunks, whatever dst0 is)
-        return INFV_OK;
-    }
-    if (tok == INFV_TOKENS_F8E4M3 && !ln) {                  // the hi planes alone: an e4m3 value has no lo piece
-        if (szF > Fh.bytes || szF > Th.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(Fh.reserve(szF)); HIP_TRY(Th.reserve(szF)); }
-        for (int c0 = 0; c0 < nb; c0 += 32768) {               // grid.z limit
-            const int n = nb - c0 < 32768 ? nb - c0 : 32768;
-            const size_t o = (size_t)c0 * n_tokens * d;
-            HIP_TRY(launch_token_pass(tok_at(frames_, tok, (long)o), tok, n, n_tokens, d, Fh.as<__bf16>() + d0 + o, nullptr,
-                                      Th.as<__bf16>() + d0 + o, nullptr, stream, kbar ? kbar + (size_t)c0 * (n_tokens / P) * d : nullptr, P));
-        }
-        *ref = SplitRef{Fh.as<__bf16>(), nullptr, Th.as<__bf16>(), nullptr};
-        return INFV_OK;
-    }
-    if (szF > Fh.bytes || szF > Fl.bytes || szF > Th.bytes || szF > Tl.bytes) {
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(Fh.reserve(szF)); HIP_TRY(Fl.reserve(szF)); HIP_TRY(Th.reserve(szF)); HIP_TRY(Tl.reserve(szF));
-    }
+    HIP_TRY(reserve_all({{Fh, hi ? szF : 0}, {Fl, lo ? szF : 0}, {Th, szF}, {Tl, lo ? szF : 0}}));
+    const int rows_in = padded ? n_live : n_tokens;           // token rows a chunk holds in frames_
     for (int c0 = 0; c0 < nb; c0 += 32768) {                   // grid.z limit
         const int n = nb - c0 < 32768 ? nb - c0 : 32768;
-        const size_t o = (size_t)c0 * n_tokens * d;
+        const size_t o = d0 + (size_t)c0 * n_tokens * d;
+        const void* src = tok_at(frames_, tok, (long)((size_t)c0 * rows_in * d));
+        const float* stats = ln ? ln->stats + 2 * (size_t)c0 * rows_in : nullptr;
+        __bf16* fh = hi ? Fh.as<__bf16>() + o : nullptr; __bf16* fl = lo ? Fl.as<__bf16>() + o : nullptr;
+        __bf16* th = Th.as<__bf16>() + o;                 __bf16* tl = lo ? Tl.as<__bf16>() + o : nullptr;
         float* kb = kbar ? kbar + (size_t)c0 * (n_tokens / P) * d : nullptr;
-        if (ln) {                                              // a normalised value is a general fp32 number: four planes for every token type
-            HIP_TRY(launch_token_pass_ln(tok_at(frames_, tok, (long)o), tok, n, n_tokens, d, ln->stats + 2 * (size_t)c0 * n_tokens, ln->gamma, ln->beta,
-                                         Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o, Th.as<__bf16>() + d0 + o, Tl.as<__bf16>() + d0 + o, stream, kb, P));
-            continue;
-        }
-        HIP_TRY(launch_token_pass(tok_at(frames_, tok, (long)o), tok, n, n_tokens, d, Fh.as<__bf16>() + d0 + o, Fl.as<__bf16>() + d0 + o,
-                                  Th.as<__bf16>() + d0 + o, Tl.as<__bf16>() + d0 + o, stream, kb, P));
+        if (padded)
+            HIP_TRY(launch_token_pass_pad(src, tok, n, n_live, n_tokens, d, stats, ln ? ln->gamma : nullptr, ln ? ln->beta : nullptr, fh, fl, th, tl, stream));
+        else if (ln)
+            HIP_TRY(launch_token_pass_ln(src, tok, n, n_tokens, d, stats, ln->gamma, ln->beta, fh, fl, th, tl, stream, kb, P));
+        else
+            HIP_TRY(launch_token_pass(src, tok, n, n_tokens, d, fh, fl, th, tl, stream, kb, P));
     }
-    *ref = SplitRef{Fh.as<__bf16>(), Fl.as<__bf16>(), Th.as<__bf16>(), Tl.as<__bf16>()};
+    // (bf16 read in place: Fh is THESE chunks of the caller's buffer, whatever dst0 is)
+    *ref = SplitRef{hi ? Fh.as<__bf16>() : static_cast<const __bf16*>(frames_), lo ? Fl.as<__bf16>() : nullptr, Th.as<__bf16>(),
+                    lo ? Tl.as<__bf16>() : nullptr};
     return INFV_OK;
 }
+
 
 int short_attention(infv_vqf_s* h, const void* frames_, tok_code tok /* fp16, bf16: only where split_path() holds */, int nb, int n_tokens, const float* xq, bool shared_q,
                     const infv_linear* key, const infv_linear* value, const float* along, float* merged,
@@ -255,20 +224,14 @@ int short_attention(infv_vqf_s* h, const void* frames_, tok_code tok /* fp16, bf
     const size_t needS = (size_t)nb * rows * ldS * sizeof(float);
     const size_t needO = (size_t)sk * nb * rows * d * sizeof(float);
     const size_t needQt = (size_t)nq * rows * d * sizeof(float);
-    if (needS > h->S.bytes || needO > h->O.bytes || needQt > h->qt.bytes) {
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(h->S.reserve(needS)); HIP_TRY(h->O.reserve(needO)); HIP_TRY(h->qt.reserve(needQt));
-    }
+    HIP_TRY(reserve_all({{h->S, needS}, {h->O, needO}, {h->qt, needQt}}));
     float* qt = h->qt.as<float>();
-    void* qh = h->sQh.p; void* ql = h->sQl.p;
     if (use_cache) {                                           // nq == 1: the cached query block of layer 0
         const size_t szq = (size_t)rows * d;
-        if (szq * 4 > h->c_qt.bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h->c_qt.reserve(szq * 4)); HIP_TRY(h->c_qh.reserve(szq * 2)); HIP_TRY(h->c_ql.reserve(szq * 2));
-            h->c_qt_valid = h->c_qsplit_valid = false;
-        }
-        qt = h->c_qt.as<float>(); qh = h->c_qh.p; ql = h->c_ql.p;
+        bool grew = false;
+        HIP_TRY(reserve_all({{h->c_qt, szq * 4}, {h->c_qh, szq * 2}, {h->c_ql, szq * 2}}, &grew));
+        if (grew) h->c_qt_valid = h->c_qsplit_valid = false;
+        qt = h->c_qt.as<float>();
     }
     if (!use_cache || !h->c_qt_valid) {
         HIP_TRY(launch_qf_qtilde(xq, nq, Q, H, d, key->w, qt, stream));
@@ -278,18 +241,11 @@ int short_attention(infv_vqf_s* h, const void* frames_, tok_code tok /* fp16, bf
     // their rounding (~1e-5) only feeds the read-out.  INFV_VQF_FP32=1 selects the exact-fp32 MFMA kernels instead.
     if (split_path(h, n_tokens)) {
         const size_t szP = (size_t)nb * rows * n_tokens * 2, szQ = (size_t)nq * rows * d * 2;
-        if (szP > h->sPh.bytes || szQ > h->sQh.bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(h->sPh.reserve(szP)); HIP_TRY(h->sPl.reserve(szP)); HIP_TRY(h->sQh.reserve(szQ)); HIP_TRY(h->sQl.reserve(szQ));
-        }
+        HIP_TRY(reserve_all({{h->sPh, szP}, {h->sPl, szP}, {h->sQh, szQ}, {h->sQl, szQ}}));
         SplitRef sr;
         if (pre) sr = *pre;                                   // the caller split these tokens already (shared by the layers)
         else if (int rc = prepare_split(h, frames_, tok, nb, n_tokens, nullptr, false, &sr, stream)) return rc;
-        if (use_cache) {                                      // (the buffers may just have been (re)allocated above)
-            qh = h->c_qh.p; ql = h->c_ql.p;
-        } else {
-            qh = h->sQh.p; ql = h->sQl.p;
-        }
+        void* qh = use_cache ? h->c_qh.p : h->sQh.p; void* ql = use_cache ? h->c_ql.p : h->sQl.p;
         if (!use_cache || !h->c_qsplit_valid) {
             HIP_TRY(launch_split_rows(qt, d, (long)nq * rows, d, qh, ql, d, stream));
             if (use_cache) h->c_qsplit_valid = true;
@@ -333,7 +289,7 @@ int short_attention(infv_vqf_s* h, const void* frames_, tok_code tok /* fp16, bf
     int sk2 = 8;
     while (sk2 > 1 && (d % (32 * sk2) || nb_pick * H * sk2 > 4096)) sk2 >>= 1;
     const size_t needP = (size_t)sk2 * M2 * hidden * sizeof(float);
-    if (needP > h->part.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->part.reserve(needP)); }
+    HIP_TRY(reserve_all({{h->part, needP}}));
     QfGemm v{};
     v.A = h->O.as<float>(); v.lda = d; v.strideA = (long)Q * d; v.strideA2 = (long)rows * d;   // inner = head, outer = chunk
     v.B[0] = value->w; v.ldb = d; v.strideB = 64L * d; v.strideB2 = 0; v.seg_rows = 64;
@@ -400,7 +356,7 @@ int run_embed(infv_vqf_s* h, const infv_vqf_vc_front* f, int V, const int32_t* t
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->ids_pin), (size_t)(2 * n) * sizeof(int32_t), hipHostMallocDefault));
         h->ids_pin_n = (size_t)(2 * n);
     }
-    if ((size_t)(2 * n) * sizeof(int32_t) > h->ids_dev.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->ids_dev.reserve((size_t)(2 * n) * sizeof(int32_t))); }
+    HIP_TRY(reserve_all({{h->ids_dev, (size_t)(2 * n) * sizeof(int32_t)}}));
     int32_t* src = h->ids_pin; int32_t* pos = h->ids_pin + n;
     long m = 0, i = 0;
     for (int v = 0; v < V; ++v) {
@@ -413,6 +369,54 @@ int run_embed(infv_vqf_s* h, const infv_vqf_vc_front* f, int V, const int32_t* t
     HIP_TRY(launch_qf_vc_embed(f->emb.word, f->emb.pos, f->emb.query_tokens, f->emb.ln.gamma, f->emb.ln.beta, h->cfg.ln_eps,
                                h->ids_dev.as<int32_t>(), h->ids_dev.as<int32_t>() + n, (int)n, Hd, out, stream));
     return INFV_OK;
+}
+
+// a table of packed offsets t [n + 1] (cu, fcu): starts at 0, never decreases
+int check_offsets(const char* name, const char* tab, const int32_t* t, int n) {
+    if (t[0] != 0) return fail(INFV_ERR_INVALID, "%s: %s[0] = %d, not 0", name, tab, t[0]);
+    for (int i = 0; i < n; ++i)
+        if (t[i + 1] < t[i])
+            return fail(INFV_ERR_INVALID, "%s: %s is not non-decreasing (%s[%d] = %d > %s[%d] = %d)", name, tab, tab, i, t[i], tab, i + 1, t[i + 1]);
+    return INFV_OK;
+}
+
+// the n memory handles of a batched call: none null, none twice (`per`: what each memory belongs to beside its video)
+int check_distinct_handles(const char* name, const infv_ltm_handle* ltm, int n, const char* per) {
+    std::vector<infv_ltm_handle> all(ltm, ltm + n);
+    for (int i = 0; i < n; ++i)
+        if (!all[i]) return fail(INFV_ERR_INVALID, "%s: LTM handle %d is null", name, i);
+    std::sort(all.begin(), all.end());
+    if (std::adjacent_find(all.begin(), all.end()) != all.end())
+        return fail(INFV_ERR_INVALID, "%s: an LTM handle appears twice (every video and %s needs its own memory)", name, per);
+    return INFV_OK;
+}
+
+// embeddings of the video Q-former: LayerNorm of the learned query tokens (Qformer.py:108-112; chunk-independent) -> h->h_a
+int embed_query_tokens(infv_vqf_s* h, const infv_vqf_weights* w, hipStream_t stream) {
+    const int Hd = h->cfg.hidden;
+    QfEpilogue e{};
+    e.parts = w->query_tokens; e.nsplit = 1; e.ld_in = Hd; e.seg_cols = Hd; e.scale = 1.f; e.res_scale = 1.f;
+    e.gamma = w->emb_ln.gamma; e.beta = w->emb_ln.beta; e.eps = h->cfg.ln_eps;
+    e.out = h->h_a.as<float>(); e.ld_out = Hd; e.M = h->cfg.n_query; e.width = Hd; e.res_rows = 1;
+    HIP_TRY(launch_qf_epilogue(e, stream));
+    return INFV_OK;
+}
+
+// Self-attention over the query tokens of the nb chunks at x + output dense + LayerNorm -> h1 (Qformer.py:442-470 -> BertAttention),
+// then the cross query -> xq.  whole: through the row-block scratch of the layer-major calls, else the one-chunk scratch.
+int query_self_block(infv_vqf_s* h, const infv_vqf_layer& L, const float* x, int nb, bool inv, bool whole, float* h1, float* xq, hipStream_t stream) {
+    const int Q = h->cfg.n_query, Hd = h->cfg.hidden;
+    float* qkv_y = (whole ? h->vqkv : h->qkv).as<float>(); float* sa = (whole ? h->vsa : h->sa).as<float>();
+    LinearCall qkv{x, nb * Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
+    qkv.inv = inv; qkv.y = qkv_y;
+    if (int rc = run_linear(h, qkv, stream)) return rc;
+    HIP_TRY(launch_qf_self_attention(qkv_y, nb, Q, h->cfg.n_heads, sa, stream));
+    LinearCall so{sa, nb * Q, Hd, {&L.self_o}, 1, Hd};
+    so.inv = inv; so.residual = x; so.res_rows = nb * Q; so.ln = &L.self_ln; so.y = h1;
+    if (int rc = run_linear(h, so, stream)) return rc;
+    LinearCall q{h1, nb * Q, Hd, {&L.x_q}, 1, Hd};
+    q.inv = inv; q.y = xq;
+    return run_linear(h, q, stream);
 }
 
 }  // namespace
@@ -477,11 +481,7 @@ int infv_vqf_short_attention(infv_vqf_handle h, const void* frames, int32_t n_to
     tok_code tok = h->tok;
     if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 / fp8 frames must be 16-byte aligned");
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
-    if (tok != INFV_TOKENS_F32 && !split_path(h, n_tokens)) {
-        const float* f32 = nullptr;
-        if (int rc = upcast_tokens(h, frames, tok, (size_t)n_tokens * h->cfg.enc_width, &f32, static_cast<hipStream_t>(stream))) return rc;
-        frames = f32; tok = INFV_TOKENS_F32;
-    }
+    if (int rc = fp32_tokens_unless_split(h, frames, tok, n_tokens, (size_t)n_tokens * h->cfg.enc_width, static_cast<hipStream_t>(stream))) return rc;
     return short_attention(h, frames, tok, 1, n_tokens, xq, false, key, value, a_long, merged, static_cast<hipStream_t>(stream));
 }
 
@@ -501,11 +501,7 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
     if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 / fp8 frames must be 16-byte aligned");
     if (use_ltm)
         if (int rc = ensure_streams(h)) return rc;
-    if (tok != INFV_TOKENS_F32 && !split_path(h, n_tokens)) {  // today's fp32 kernels from an fp32 copy
-        const float* f32 = nullptr;
-        if (int rc = upcast_tokens(h, frames, tok, (size_t)n_tokens * c.enc_width, &f32, stream)) return rc;
-        frames = f32; tok = INFV_TOKENS_F32;
-    }
+    if (int rc = fp32_tokens_unless_split(h, frames, tok, n_tokens, (size_t)n_tokens * c.enc_width, stream)) return rc;
 
     // The prefix of layer 0 (embedding LayerNorm -> self-attention block -> cross query) depends on the weights only,
     // not on the chunk: with a non-zero weights epoch it is computed once and reused until the epoch changes.
@@ -513,23 +509,16 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
     const bool prefix_cached = caching && h->c_valid && h->c_epoch == h->epoch;
     if (caching && !prefix_cached) {
         const size_t sz = (size_t)Q * Hd * sizeof(float);
-        if (sz > h->c_h1.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->c_h1.reserve(sz)); HIP_TRY(h->c_xq.reserve(sz)); }
+        HIP_TRY(reserve_all({{h->c_h1, sz}, {h->c_xq, sz}}));
         h->c_valid = false; h->c_qt_valid = false; h->c_qsplit_valid = false;
     }
-    if (!prefix_cached) {
-        // embeddings: LayerNorm of the learned query tokens (Qformer.py:108-112)
-        QfEpilogue e{};
-        e.parts = w->query_tokens; e.nsplit = 1; e.split_stride = 0; e.ld_in = Hd; e.seg_cols = Hd;
-        e.gamma = w->emb_ln.gamma; e.beta = w->emb_ln.beta; e.eps = c.ln_eps; e.scale = 1.f; e.res_scale = 1.f;
-        e.out = h->h_a.as<float>(); e.ld_out = Hd; e.M = Q; e.width = Hd; e.res_rows = 1;
-        HIP_TRY(launch_qf_epilogue(e, stream));
-    }
+    if (!prefix_cached)
+        if (int rc = embed_query_tokens(h, w, stream)) return rc;
     float* hcur = h->h_a.as<float>();
     float* hnext = h->h_b.as<float>();
 
     if (use_ltm) {
-        const size_t need = (size_t)T * c.enc_width * sizeof(float);
-        if (need > h->kbar.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->kbar.reserve(need)); }
+        HIP_TRY(reserve_all({{h->kbar, (size_t)T * c.enc_width * sizeof(float)}}));
         if (new_video)
             for (int l = 0; l < c.n_layers; ++l)
                 if (int rc = infv_ltm_reset(ltm[l])) return rc;
@@ -553,18 +542,7 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
         float* h1 = l0c ? h->c_h1.as<float>() : h->h1.as<float>();
         float* xqb = l0c ? h->c_xq.as<float>() : h->xq.as<float>();
         if (!(l0c && prefix_cached)) {
-            // ---- self-attention over the query tokens + output (Qformer.py:442-470 -> BertAttention)
-            LinearCall qkv{hcur, Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
-            qkv.y = h->qkv.as<float>();
-            if (int rc = run_linear(h, qkv, stream)) return rc;
-            HIP_TRY(launch_qf_self_attention(h->qkv.as<float>(), 1, Q, c.n_heads, h->sa.as<float>(), stream));
-            LinearCall so{h->sa.as<float>(), Q, Hd, {&L.self_o}, 1, Hd};
-            so.residual = hcur; so.res_rows = Q; so.ln = &L.self_ln; so.y = h1;
-            if (int rc = run_linear(h, so, stream)) return rc;
-            // ---- cross-attention: query, long-term memory, short-term attention, merge, output
-            LinearCall xq{h1, Q, Hd, {&L.x_q}, 1, Hd};
-            xq.y = xqb;
-            if (int rc = run_linear(h, xq, stream)) return rc;
+            if (int rc = query_self_block(h, L, hcur, 1, false, false, h1, xqb, stream)) return rc;
             if (l0c) { h->c_valid = true; h->c_epoch = h->epoch; }
         }
         const float* along = nullptr;
@@ -640,6 +618,70 @@ static int pick_short_nb(const infv_vqf_s* h, int C, int n_tokens) {
     return NB;
 }
 
+// ---- steps shared by the layer-major calls (encode_impl and the stages of vc_impl) ----
+
+// Chunks [0, C) in blocks of B:  for (RowBlock b : RowBlocks{C, B, stride})  yields the first chunk, the chunk count and the first
+// element of chunk c0 in a [C][stride] activation buffer.
+struct RowBlock { int c0, nb; long r0; };
+struct RowBlocks {                                            // (the range is its own iterator)
+    int C, B; long stride; int c0 = 0;
+    RowBlocks begin() const { return *this; }
+    RowBlocks end() const { return *this; }
+    bool operator!=(const RowBlocks&) const { return c0 < C; }
+    void operator++() { c0 += B; }
+    RowBlock operator*() const { return RowBlock{c0, C - c0 < B ? C - c0 : B, c0 * stride}; }
+};
+
+// the cached planes of a whole call, from chunk c0 on
+static SplitRef split_ref_at(const SplitRef& w, int c0, long chunk_k) {
+    const long o = (long)c0 * chunk_k;
+    return SplitRef{w.Fh + o, w.Fl ? w.Fl + o : nullptr, w.Th + o, w.Tl ? w.Tl + o : nullptr};
+}
+
+// u[:, l, :] of u [C][n_layers_in_u][S] -> contiguous [C][S] in h->vu, for the one-layer memory handles (u == nullptr: nothing)
+static int ltm_u_slice(infv_vqf_s* h, const double* u, int l, int n_layers_in_u, int C, hipStream_t stream) {
+    if (!u) return INFV_OK;
+    const size_t S = (size_t)h->cfg.nb_samples;
+    HIP_TRY(hipMemcpy2DAsync(h->vu.p, S * sizeof(double), u + (size_t)l * S, (size_t)n_layers_in_u * S * sizeof(double), S * sizeof(double),
+                             (size_t)C, hipMemcpyDeviceToDevice, stream));
+    return INFV_OK;
+}
+
+// vmerged = alpha * vshort + (1 - alpha) * valong over the M rows of the whole call
+static int alpha_merge(infv_vqf_s* h, long M, hipStream_t stream) {
+    const infv_vqf_config& c = h->cfg;
+    const long Hd = c.hidden;
+    for (long m0 = 0; m0 < M; m0 += kMergeRows) {
+        QfEpilogue em{};
+        em.parts = h->vshort.as<float>() + m0 * Hd; em.nsplit = 1; em.ld_in = Hd; em.seg_cols = c.hidden;
+        em.scale = c.alpha; em.res_scale = (float)(1.0 - (double)c.alpha);
+        em.residual = h->valong.as<float>() + m0 * Hd; em.ld_res = Hd; em.res_rows = (int)(M - m0 < kMergeRows ? M - m0 : kMergeRows);
+        em.out = h->vmerged.as<float>() + m0 * Hd; em.ld_out = Hd; em.M = em.res_rows; em.width = c.hidden; em.eps = c.ln_eps;
+        HIP_TRY(launch_qf_epilogue(em, stream));
+    }
+    return INFV_OK;
+}
+
+// The tail of a call: out (nullptr: scratch, only the mean is wanted) = the rows of h->vA through `proj`, block by block; then
+// mean (nullptr: none) = the mean of every video's chunks (cu [V + 1]), or of all chunks (cu == nullptr).
+static int project_and_mean(infv_vqf_s* h, RowBlocks blocks, const infv_linear* proj, bool inv, float* out, float* mean, const int32_t* cu,
+                            int V, hipStream_t stream) {
+    const infv_vqf_config& c = h->cfg;
+    const long row = (long)c.n_query * c.proj_out;             // projected elements of a chunk
+    if (!out) {
+        HIP_TRY(reserve_all({{h->S, (size_t)blocks.C * row * sizeof(float)}}));
+        out = h->S.as<float>();
+    }
+    for (RowBlock b : blocks) {
+        LinearCall pj{h->vA.as<float>() + b.r0, b.nb * c.n_query, c.hidden, {proj}, 1, c.proj_out};
+        pj.inv = inv; pj.y = out + b.c0 * row;
+        if (int rc = run_linear(h, pj, stream)) return rc;
+    }
+    if (mean && cu) HIP_TRY(launch_qf_mean_segments(out, cu, V, row, mean, stream));
+    else if (mean) HIP_TRY(launch_qf_mean(out, blocks.C, row, mean, stream));
+    return INFV_OK;
+}
+
 // The layer-major body of infv_vqf_encode_video (multi = false: one video, ltm [n_layers]) and infv_vqf_encode_videos (multi:
 // V videos packed by the host array cu, ltm [V][n_layers]; every choice that shapes a GEMM or contraction is taken from
 // per-chunk quantities or constants, and each layer's memories step through infv_ltm_steps_videos).
@@ -659,11 +701,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     const int Q = c.n_query, Hd = c.hidden, C = n_chunks, S = c.nb_samples;
     const int n_tokens = T * c.tokens_per_frame;
     const long chunk_k = (long)n_tokens * c.enc_width;
-    if (tok != INFV_TOKENS_F32 && !split_path(h, n_tokens)) {  // today's fp32 kernels from an fp32 copy
-        const float* f32 = nullptr;
-        if (int rc = upcast_tokens(h, frames, tok, (size_t)C * chunk_k, &f32, stream)) return rc;
-        frames = f32; tok = INFV_TOKENS_F32;
-    }
+    if (int rc = fp32_tokens_unless_split(h, frames, tok, n_tokens, (size_t)C * chunk_k, stream)) return rc;
     const long M = (long)C * Q;                               // rows of the whole-video activations
     // ---- workspaces: whole-video activations + per-block scratch ----
     const int rb_max = multi ? kRowBlockVideos : kRowBlockVideo;   // (batch invariant: the row count does not shape the GEMMs)
@@ -673,23 +711,11 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     // of the 256 CUs (16 chunks = 288 tiles ran at 56 % of 14 chunks' rate per tile)
     const int NB = pick_short_nb(h, C, n_tokens);
     {
-        const size_t act = (size_t)M * Hd * sizeof(float);
-        bool grow = act > h->vA.bytes || (size_t)RB * Q * 3 * Hd * sizeof(float) > h->vqkv.bytes ||
-                    (size_t)RB * Q * c.inter * sizeof(float) > h->vinter.bytes ||
-                    (use_ltm && ((size_t)C * S * sizeof(double) > h->vu.bytes || (size_t)C * T * c.enc_width * sizeof(float) > h->vkbar.bytes));
-        if (grow) HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(h->vA.reserve(act)); HIP_TRY(h->v1.reserve(act)); HIP_TRY(h->v2.reserve(act)); HIP_TRY(h->vxq.reserve(act));
-        HIP_TRY(h->vshort.reserve(act)); HIP_TRY(h->vmerged.reserve(act));
-        if (use_ltm) {
-            HIP_TRY(h->valong.reserve(act));
-            HIP_TRY(h->vu.reserve((size_t)C * S * sizeof(double)));
-            HIP_TRY(h->vkbar.reserve((size_t)C * T * c.enc_width * sizeof(float)));
-        }
-        HIP_TRY(h->vqkv.reserve((size_t)RB * Q * 3 * Hd * sizeof(float)));
-        HIP_TRY(h->vsa.reserve((size_t)RB * Q * Hd * sizeof(float)));
-        HIP_TRY(h->vinter.reserve((size_t)RB * Q * c.inter * sizeof(float)));
-        HIP_TRY(h->v_h1s.reserve((size_t)Q * Hd * sizeof(float)));
-        HIP_TRY(h->v_xqs.reserve((size_t)Q * Hd * sizeof(float)));
+        const size_t act = (size_t)M * Hd * sizeof(float), row = (size_t)Q * Hd * sizeof(float), f = sizeof(float);
+        HIP_TRY(reserve_all({{h->vA, act}, {h->v1, act}, {h->v2, act}, {h->vxq, act}, {h->vshort, act}, {h->vmerged, act},
+                             {h->valong, use_ltm ? act : 0}, {h->vu, use_ltm ? (size_t)C * S * sizeof(double) : 0},
+                             {h->vkbar, use_ltm ? (size_t)C * T * c.enc_width * f : 0}, {h->vqkv, (size_t)RB * 3 * row},
+                             {h->vsa, (size_t)RB * row}, {h->vinter, (size_t)RB * Q * c.inter * f}, {h->v_h1s, row}, {h->v_xqs, row}}));
     }
     // ---- ONE pass over the whole video's frame tokens: split-bf16 operands of every layer's short-term attention and
     //      the frame means of every layer's memory.  The copies take 2 x the tokens' bytes (12.7 GB for the headline's
@@ -704,12 +730,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
             have_w = true;
         }
     }
-    auto pre_at = [&](int c0, SplitRef* r) -> const SplitRef* {  // the cached split of chunks c0.. (nullptr: split per sub-batch)
-        if (!have_w) return nullptr;
-        const long o = (long)c0 * chunk_k;
-        *r = SplitRef{wref.Fh + o, wref.Fl ? wref.Fl + o : nullptr, wref.Th + o, wref.Tl ? wref.Tl + o : nullptr};
-        return r;
-    };
+    const RowBlocks row_blocks{C, RB, (long)Q * Hd}, short_blocks{C, NB, (long)Q * Hd};
     const int ltm_dtype = tok;   // (what the fallbacks below hand the memories)
     if (multi && use_ltm && !have_kbar) {                    // the frame means every layer's memories step from
         if (int rc = infv_ltm_set_token_dtype(ltm[0], ltm_dtype)) return rc;
@@ -721,19 +742,9 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
     float* vxq = h->vxq.as<float>(); float* valong = h->valong.as<float>();
     float* vshort = h->vshort.as<float>(); float* vmerged = h->vmerged.as<float>();
 
-    // embeddings: LayerNorm of the learned query tokens (chunk-independent)
-    QfEpilogue e0{};
-    e0.parts = w->query_tokens; e0.nsplit = 1; e0.ld_in = Hd; e0.seg_cols = Hd; e0.scale = 1.f; e0.res_scale = 1.f;
-    e0.gamma = w->emb_ln.gamma; e0.beta = w->emb_ln.beta; e0.eps = c.ln_eps;
-    e0.out = h->h_a.as<float>(); e0.ld_out = Hd; e0.M = Q; e0.width = Hd; e0.res_rows = 1;
-    HIP_TRY(launch_qf_epilogue(e0, stream));
+    if (int rc = embed_query_tokens(h, w, stream)) return rc;
 
-    auto ltm_u = [&](int l) -> int {                          // u[:, l, :] -> contiguous [C][S] for a one-layer handle
-        if (!u) return INFV_OK;
-        HIP_TRY(hipMemcpy2DAsync(h->vu.p, (size_t)S * sizeof(double), u + (size_t)l * S, (size_t)c.n_layers * S * sizeof(double),
-                                 (size_t)S * sizeof(double), (size_t)C, hipMemcpyDeviceToDevice, stream));
-        return INFV_OK;
-    };
+    auto ltm_u = [&](int l) { return ltm_u_slice(h, u, l, c.n_layers, C, stream); };
 
     for (int l = 0; l < c.n_layers; ++l) {
         const infv_vqf_layer& L = w->layer[l];
@@ -744,19 +755,7 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
         int res1_rows;
         if (shared) {
             // ---- self-attention block + cross query once ----
-            LinearCall qkv{h->h_a.as<float>(), Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
-            qkv.inv = multi;
-            qkv.y = h->qkv.as<float>();
-            if (int rc = run_linear(h, qkv, stream)) return rc;
-            HIP_TRY(launch_qf_self_attention(h->qkv.as<float>(), 1, Q, c.n_heads, h->sa.as<float>(), stream));
-            LinearCall so{h->sa.as<float>(), Q, Hd, {&L.self_o}, 1, Hd};
-            so.inv = multi;
-            so.residual = h->h_a.as<float>(); so.res_rows = Q; so.ln = &L.self_ln; so.y = h->v_h1s.as<float>();
-            if (int rc = run_linear(h, so, stream)) return rc;
-            LinearCall xq{h->v_h1s.as<float>(), Q, Hd, {&L.x_q}, 1, Hd};
-            xq.inv = multi;
-            xq.y = h->v_xqs.as<float>();
-            if (int rc = run_linear(h, xq, stream)) return rc;
+            if (int rc = query_self_block(h, L, h->h_a.as<float>(), 1, multi, false, h->v_h1s.as<float>(), h->v_xqs.as<float>(), stream)) return rc;
             res1 = h->v_h1s.as<float>(); res1_rows = Q;
             // ---- long-term memory of every chunk with the constant query: the whole-video fast path ----
             if (use_ltm && multi) {                           // every video's memory with the shared query, in lockstep
@@ -775,32 +774,16 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
                                                          u ? h->vu.as<double>() : nullptr, new_video, valong, stream_)) return rc;
             }
             // ---- short-term attention, merged with the long-term context ----
-            for (int c0 = 0; c0 < C; c0 += NB) {
-                const int nb = C - c0 < NB ? C - c0 : NB;
-                SplitRef sr;
-                if (int rc = short_attention(h, tok_at(frames, tok, c0 * chunk_k), tok, nb, n_tokens, h->v_xqs.as<float>(), true, &L.x_k, &L.x_v,
-                                             use_ltm ? valong + (long)c0 * Q * Hd : nullptr, vmerged + (long)c0 * Q * Hd, stream,
-                                             false, pre_at(c0, &sr), nullptr, multi ? kInvariantNb : 0)) return rc;
+            for (RowBlock b : short_blocks) {
+                const SplitRef sr = split_ref_at(wref, b.c0, chunk_k);   // the cached split of chunks c0.. (else: split per sub-batch)
+                if (int rc = short_attention(h, tok_at(frames, tok, b.c0 * chunk_k), tok, b.nb, n_tokens, h->v_xqs.as<float>(), true, &L.x_k, &L.x_v,
+                                             use_ltm ? valong + b.r0 : nullptr, vmerged + b.r0, stream,
+                                             false, have_w ? &sr : nullptr, nullptr, multi ? kInvariantNb : 0)) return rc;
             }
         } else {
             // ---- self-attention block + cross query of every chunk (row blocks) ----
-            for (int c0 = 0; c0 < C; c0 += RB) {
-                const int nb = C - c0 < RB ? C - c0 : RB;
-                const long r0 = (long)c0 * Q * Hd;
-                LinearCall qkv{vA + r0, nb * Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
-                qkv.inv = multi;
-                qkv.y = h->vqkv.as<float>();
-                if (int rc = run_linear(h, qkv, stream)) return rc;
-                HIP_TRY(launch_qf_self_attention(h->vqkv.as<float>(), nb, Q, c.n_heads, h->vsa.as<float>(), stream));
-                LinearCall so{h->vsa.as<float>(), nb * Q, Hd, {&L.self_o}, 1, Hd};
-                so.inv = multi;
-                so.residual = vA + r0; so.res_rows = nb * Q; so.ln = &L.self_ln; so.y = v1 + r0;
-                if (int rc = run_linear(h, so, stream)) return rc;
-                LinearCall xq{v1 + r0, nb * Q, Hd, {&L.x_q}, 1, Hd};
-                xq.inv = multi;
-                xq.y = vxq + r0;
-                if (int rc = run_linear(h, xq, stream)) return rc;
-            }
+            for (RowBlock b : row_blocks)
+                if (int rc = query_self_block(h, L, vA + b.r0, b.nb, multi, true, v1 + b.r0, vxq + b.r0, stream)) return rc;
             res1 = v1; res1_rows = (int)M;
             // ---- long-term memory with per-chunk queries: the sequential per-call chain, on the side stream, while
             //      the main stream runs this layer's short-term attention ----
@@ -825,62 +808,35 @@ static int encode_impl(infv_vqf_handle h, const infv_ltm_handle* ltm, const void
                 }
                 HIP_TRY(hipEventRecord(h->ev_side, h->side));
             }
-            for (int c0 = 0; c0 < C; c0 += NB) {
-                const int nb = C - c0 < NB ? C - c0 : NB;
-                SplitRef sr;
-                if (int rc = short_attention(h, tok_at(frames, tok, c0 * chunk_k), tok, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
-                                             nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
-                                             pre_at(c0, &sr), nullptr, multi ? kInvariantNb : 0)) return rc;
+            for (RowBlock b : short_blocks) {
+                const SplitRef sr = split_ref_at(wref, b.c0, chunk_k);
+                if (int rc = short_attention(h, tok_at(frames, tok, b.c0 * chunk_k), tok, b.nb, n_tokens, vxq + b.r0, false, &L.x_k, &L.x_v,
+                                             nullptr, (use_ltm ? vshort : vmerged) + b.r0, stream, false,
+                                             have_w ? &sr : nullptr, nullptr, multi ? kInvariantNb : 0)) return rc;
             }
             if (use_ltm) {
                 HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
-                for (long m0 = 0; m0 < M; m0 += kMergeRows) {  // merged = alpha * short + (1 - alpha) * long
-                    QfEpilogue em{};
-                    em.parts = vshort + m0 * Hd; em.nsplit = 1; em.ld_in = Hd; em.seg_cols = Hd;
-                    em.scale = c.alpha; em.res_scale = (float)(1.0 - (double)c.alpha);
-                    em.residual = valong + m0 * Hd; em.ld_res = Hd; em.res_rows = (int)(M - m0 < kMergeRows ? M - m0 : kMergeRows);
-                    em.out = vmerged + m0 * Hd; em.ld_out = Hd; em.M = em.res_rows; em.width = Hd; em.eps = c.ln_eps;
-                    HIP_TRY(launch_qf_epilogue(em, stream));
-                }
+                if (int rc = alpha_merge(h, M, stream)) return rc;
             }
         }
         // ---- cross-attention output + query FFN of every chunk (row blocks) ----
-        for (int c0 = 0; c0 < C; c0 += RB) {
-            const int nb = C - c0 < RB ? C - c0 : RB;
-            const long r0 = (long)c0 * Q * Hd;
+        for (RowBlock b : row_blocks) {
+            const int nb = b.nb; const long r0 = b.r0;
             LinearCall xo{vmerged + r0, nb * Q, Hd, {&L.x_o}, 1, Hd};
-            xo.inv = multi;
-            xo.residual = shared ? res1 : res1 + r0; xo.res_rows = shared ? res1_rows : nb * Q; xo.ln = &L.x_ln; xo.y = v2 + r0;
+            xo.inv = multi; xo.residual = shared ? res1 : res1 + r0; xo.res_rows = shared ? res1_rows : nb * Q; xo.ln = &L.x_ln; xo.y = v2 + r0;
             if (int rc = run_linear(h, xo, stream)) return rc;
             LinearCall fi{v2 + r0, nb * Q, Hd, {&L.ffn_in}, 1, c.inter};
-            fi.inv = multi;
-            fi.act = QF_ACT_GELU; fi.y = h->vinter.as<float>();
+            fi.inv = multi; fi.act = QF_ACT_GELU; fi.y = h->vinter.as<float>();
             if (int rc = run_linear(h, fi, stream)) return rc;
             LinearCall fo{h->vinter.as<float>(), nb * Q, c.inter, {&L.ffn_out}, 1, Hd};
-            fo.inv = multi;
-            fo.residual = v2 + r0; fo.res_rows = nb * Q; fo.ln = &L.ffn_ln; fo.y = vA + r0;
+            fo.inv = multi; fo.residual = v2 + r0; fo.res_rows = nb * Q; fo.ln = &L.ffn_ln; fo.y = vA + r0;
             if (int rc = run_linear(h, fo, stream)) return rc;
         }
     }
     if (hidden_out)
         HIP_TRY(hipMemcpyAsync(hidden_out, vA, (size_t)M * Hd * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    if (llama_out || llama_mean) {
-        float* lo = llama_out;
-        if (!lo) {                                             // only the mean is wanted: project into scratch
-            const size_t need = (size_t)M * c.proj_out * sizeof(float);
-            if (need > h->S.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->S.reserve(need)); }
-            lo = h->S.as<float>();
-        }
-        for (int c0 = 0; c0 < C; c0 += RB) {
-            const int nb = C - c0 < RB ? C - c0 : RB;
-            LinearCall pj{vA + (long)c0 * Q * Hd, nb * Q, Hd, {&w->llama_proj}, 1, c.proj_out};
-            pj.inv = multi;
-            pj.y = lo + (long)c0 * Q * c.proj_out;
-            if (int rc = run_linear(h, pj, stream)) return rc;
-        }
-        if (llama_mean && multi) HIP_TRY(launch_qf_mean_segments(lo, cu, V, (long)Q * c.proj_out, llama_mean, stream));
-        else if (llama_mean) HIP_TRY(launch_qf_mean(lo, C, (long)Q * c.proj_out, llama_mean, stream));
-    }
+    if (llama_out || llama_mean)
+        if (int rc = project_and_mean(h, row_blocks, &w->llama_proj, multi, llama_out, llama_mean, multi ? cu : nullptr, V, stream)) return rc;
     return INFV_OK;
 }
 
@@ -897,20 +853,12 @@ int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_
     // ---- validation before any device work or memory change ----
     if (!h || !cu || !w || V < 0) return fail(INFV_ERR_INVALID, "encode_videos: bad arguments");
     if (V == 0) return INFV_OK;
-    if (cu[0] != 0) return fail(INFV_ERR_INVALID, "encode_videos: cu[0] = %d, not 0", cu[0]);
-    for (int v = 0; v < V; ++v)
-        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "encode_videos: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)",
-                                            v, cu[v], v + 1, cu[v + 1]);
+    if (int rc = check_offsets("encode_videos", "cu", cu, V)) return rc;
     const bool use_ltm = h->cfg.alpha != 1.0f;
     const int n_h = use_ltm ? V * h->cfg.n_layers : 0;
     if (use_ltm) {
         if (!ltm) return fail(INFV_ERR_INVALID, "encode_videos: alpha != 1 needs the per-layer LTM handles of every video");
-        std::vector<infv_ltm_handle> all(ltm, ltm + n_h);
-        for (int i = 0; i < n_h; ++i)
-            if (!all[i]) return fail(INFV_ERR_INVALID, "encode_videos: LTM handle %d is null", i);
-        std::sort(all.begin(), all.end());
-        if (std::adjacent_find(all.begin(), all.end()) != all.end())
-            return fail(INFV_ERR_INVALID, "encode_videos: an LTM handle appears twice (every video and layer needs its own memory)");
+        if (int rc = check_distinct_handles("encode_videos", ltm, n_h, "layer")) return rc;
     }
     if (cu[V] == 0) {                                         // no chunk: new_video still starts every memory afresh
         if (use_ltm && new_video)
@@ -945,43 +893,80 @@ int infv_vqf_self_attention(infv_vqf_handle h, const float* qkv, int32_t nb, int
 // the last layer's rows go out in out_dtype.  The handle's tokens_per_frame, alpha and proj_out are not read.
 struct FrameCall { int n_tokens; void* out; tok_code out_dtype; };
 
-// The body of infv_vqf_vc_encode_videos (fcu == nullptr: stream v reads its own chunks [cu[v], cu[v+1]) of `frames`) and of
-// infv_vqf_vc_encode_streams (stream v reads block frame_src[v] of the F blocks packed by fcu).  `name` prefixes the refusals.
-static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
-                   int32_t token_dtype /* < 0: the entry points without the argument -- fp32, refused unless the handle's setting is fp32 too */,
-                   int32_t F, const int32_t* fcu, const int32_t* frame_src, int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in,
-                   const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
-                   void* stream_, const infv_vqf_vc_front* front = nullptr /* infv_vqf_vc_encode_img: vision LayerNorm and / or embedding layer in front */,
-                   const FrameCall* fc = nullptr /* infv_vqf_encode_frames: every chunk is one frame of fc->n_tokens tokens */) {
-    // ---- validation before any device work or memory change ----
+// One call of the VideoChat2 encoder.  The entry points fill the arguments by name; vc_validate adds what it decides from them, the
+// token stages what they leave for the layers.  Stream v reads its own chunks [cu[v], cu[v+1]) of `frames` (fcu == nullptr:
+// videos) or block frame_src[v] of the F blocks packed by fcu (streams).
+struct VcCall {
+    // ---- arguments
+    const char* name = nullptr;                                // prefixes the refusals
+    const infv_ltm_handle* ltm = nullptr;
+    int32_t V = 0; const int32_t* cu = nullptr;
+    const void* frames = nullptr;                              // (vc_front_tokens may replace frames and tok by an fp32 copy)
+    bool tok_arg = false;                                      // token_dtype is an argument of the call: the handle's setting is not read
+    int32_t token_dtype = INFV_TOKENS_F32;                     // (else fp32, refused unless the handle's setting is fp32 too)
+    int32_t F = 0; const int32_t* fcu = nullptr; const int32_t* frame_src = nullptr;
+    int32_t T = 0;
+    const infv_vqf_vc_weights* w = nullptr;
+    const float* hidden_in = nullptr;                          // (vc_input_rows replaces it by the embedding layer's rows)
+    const int32_t* text_len = nullptr;
+    const double* u = nullptr;
+    int32_t new_video = 0;
+    float* hidden_out = nullptr; float* proj_out = nullptr; float* proj_mean = nullptr;
+    hipStream_t stream = nullptr;
+    const infv_vqf_vc_front* front = nullptr;                  // infv_vqf_vc_encode_img: vision LayerNorm and / or embedding layer in front
+    const FrameCall* fc = nullptr;                             // infv_vqf_encode_frames: every chunk is one frame of fc->n_tokens tokens
+    // ---- decided by vc_validate
+    tok_code tok = INFV_TOKENS_F32;
+    bool streams = false;
+    bool vis_ln = false, emb = false;                          // the vision LayerNorm runs inside the token pass; the embedding layer writes the input rows
+    bool pad = false;                                          // frames: planes and score rows padded to the next multiple of 64
+    int n_live = 0, n_tokens = 0;                              // tokens a chunk holds in `frames`; keys it has in the contractions (pad keys: zeros, no mass)
+    int n_cross = 0, n_h = 0; bool use_ltm = false;
+    int C = 0, Cf = 0;                                         // chunks (0 after validation: the call is complete); distinct chunks of frame tokens
+    long chunk_k = 0, src_k = 0;                               // elements of a chunk in the planes, and in `frames` (the same unless padded)
+    int RB = 0, NB = 0;                                        // chunks per row block of the token GEMMs, per sub-batch of the short-term attention
+    long M = 0;                                                // query rows of the call
+    long Tt = 0, TB = 0, tb_max = 0;                           // (vc_tables) text rows: all, per block of the text FFN, of the largest row block
+    // ---- left by vc_front_tokens and vc_token_pass
+    TokLn ln_{}; const TokLn* ln = nullptr;                    // the vision LayerNorm on load (split path), else nullptr
+    SplitRef wref{}; bool have_w = false, have_kbar = false;   // the planes of all Cf chunks, kept for the call; the frame means came with them
+};
+
+// The per-chunk host tables: its video's text length, the offset of its packed text rows, its rows in hidden_in / hidden_out
+struct VcTables {
+    std::vector<int32_t> n_valid, toff, q_dst, q_src, t_src, tl, o_q, o_t, q_n;
+    std::vector<int32_t> src_chunk, kbar0;                     // streams: each stream-chunk's source chunk, each stream's first one
+    std::vector<int32_t> off1;                                 // scratch of vc_self_block [RB]
+    std::vector<infv_ltm_handle> hs_l;                         // scratch of vc_cross_block: one layer's memories [V]
+};
+
+// ---- validation before any device work or memory change.  Returns with k.C == 0 where nothing is left to do.
+static int vc_validate(const infv_vqf_s* h, VcCall& k) {
+    const char* name = k.name;
+    const infv_vqf_vc_front* front = k.front; const FrameCall* fc = k.fc;
+    const int32_t V = k.V, F = k.F; const int32_t *cu = k.cu, *fcu = k.fcu, *text_len = k.text_len;
+    const infv_vqf_vc_weights* w = k.w;
     if (!h || !cu || !w || !text_len || V < 0) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
     if (front && front->reserved != 0) return fail(INFV_ERR_INVALID, "%s: front->reserved must be 0", name);
-    const bool vis_ln = front && front->vision_ln.gamma;       // the vision LayerNorm runs inside the token pass
-    const bool emb = front && front->emb.word;                 // the embedding layer writes the encoder input rows
-    if (vis_ln && !front->vision_ln.beta) return fail(INFV_ERR_INVALID, "%s: vision_ln.gamma without vision_ln.beta", name);
-    if (emb && hidden_in) return fail(INFV_ERR_INVALID, "%s: the embedding layer and hidden_in are both given (one of them writes the input rows)", name);
-    const bool tok_arg = token_dtype >= 0;                     // the dtype is an argument of the call: the handle's setting is not read
-    if (tok_arg && !token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "%s: unknown token dtype %d", name, token_dtype);
-    tok_code tok = tok_arg ? static_cast<tok_code>(token_dtype) : INFV_TOKENS_F32;
+    k.vis_ln = front && front->vision_ln.gamma;
+    k.emb = front && front->emb.word;
+    if (k.vis_ln && !front->vision_ln.beta) return fail(INFV_ERR_INVALID, "%s: vision_ln.gamma without vision_ln.beta", name);
+    if (k.emb && k.hidden_in) return fail(INFV_ERR_INVALID, "%s: the embedding layer and hidden_in are both given (one of them writes the input rows)", name);
+    if (k.tok_arg && !token_dtype_known(k.token_dtype)) return fail(INFV_ERR_INVALID, "%s: unknown token dtype %d", name, k.token_dtype);
+    k.tok = k.tok_arg ? static_cast<tok_code>(k.token_dtype) : INFV_TOKENS_F32;
     // (the vision LayerNorm of fp8 tokens is not built: no vision encoder emits fp8)
-    if (vis_ln && tok == INFV_TOKENS_F8E4M3) return fail(INFV_ERR_UNSUPPORTED, "%s: no vision LayerNorm of fp8 frame tokens", name);
-    if (tok != INFV_TOKENS_F32 && frames && !aligned16(frames)) return fail(INFV_ERR_INVALID, "%s: fp16 / bf16 / fp8 frames must be 16-byte aligned", name);
-    if (vis_ln && frames && !aligned16(frames)) return fail(INFV_ERR_INVALID, "%s: frames must be 16-byte aligned for the vision LayerNorm", name);
+    if (k.vis_ln && k.tok == INFV_TOKENS_F8E4M3) return fail(INFV_ERR_UNSUPPORTED, "%s: no vision LayerNorm of fp8 frame tokens", name);
+    if (k.tok != INFV_TOKENS_F32 && k.frames && !aligned16(k.frames)) return fail(INFV_ERR_INVALID, "%s: fp16 / bf16 / fp8 frames must be 16-byte aligned", name);
+    if (k.vis_ln && k.frames && !aligned16(k.frames)) return fail(INFV_ERR_INVALID, "%s: frames must be 16-byte aligned for the vision LayerNorm", name);
     if (V == 0) return INFV_OK;
     const infv_vqf_config& c = h->cfg;
-    if (cu[0] != 0) return fail(INFV_ERR_INVALID, "%s: cu[0] = %d, not 0", name, cu[0]);
-    for (int v = 0; v < V; ++v)
-        if (cu[v + 1] < cu[v]) return fail(INFV_ERR_INVALID, "%s: cu is not non-decreasing (cu[%d] = %d > cu[%d] = %d)", name,
-                                            v, cu[v], v + 1, cu[v + 1]);
-    const bool streams = fcu != nullptr;
-    if (streams) {
-        if (!frame_src || F < 1) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
-        if (fcu[0] != 0) return fail(INFV_ERR_INVALID, "%s: fcu[0] = %d, not 0", name, fcu[0]);
-        for (int f = 0; f < F; ++f)
-            if (fcu[f + 1] < fcu[f]) return fail(INFV_ERR_INVALID, "%s: fcu is not non-decreasing (fcu[%d] = %d > fcu[%d] = %d)",
-                                                name, f, fcu[f], f + 1, fcu[f + 1]);
+    if (int rc = check_offsets(name, "cu", cu, V)) return rc;
+    k.streams = fcu != nullptr;
+    if (k.streams) {
+        if (!k.frame_src || F < 1) return fail(INFV_ERR_INVALID, "%s: bad arguments", name);
+        if (int rc = check_offsets(name, "fcu", fcu, F)) return rc;
         for (int v = 0; v < V; ++v) {
-            const int s = frame_src[v];
+            const int s = k.frame_src[v];
             if (s < 0 || s >= F) return fail(INFV_ERR_INVALID, "%s: frame_src[%d] = %d outside [0, %d)", name, v, s, F);
             if (cu[v + 1] - cu[v] != fcu[s + 1] - fcu[s])
                 return fail(INFV_ERR_INVALID, "%s: stream %d has %d chunks, its block %d has %d", name, v, cu[v + 1] - cu[v], s,
@@ -991,47 +976,40 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     if (w->n_layers < 1 || !w->layers) return fail(INFV_ERR_INVALID, "%s: no layers", name);
     if (w->n_layers > INFV_VQF_VC_MAX_LAYERS)
         return fail(INFV_ERR_UNSUPPORTED, "%s: %d layers, at most %d are supported", name, w->n_layers, INFV_VQF_VC_MAX_LAYERS);
-    const int Q = c.n_query, Hd = c.hidden, S = c.nb_samples, Ln = w->n_layers;
+    const int Q = c.n_query, Ln = w->n_layers;
     for (int v = 0; v < V; ++v) {
         if (text_len[v] < 0) return fail(INFV_ERR_INVALID, "%s: text_len[%d] = %d is negative", name, v, text_len[v]);
         if (Q + text_len[v] > INFV_VQF_VC_MAX_TOKENS)
             return fail(INFV_ERR_UNSUPPORTED, "%s: video %d attends over %d + %d tokens, at most %d are supported", name,
                         v, Q, text_len[v], INFV_VQF_VC_MAX_TOKENS);
     }
-    if (emb)
+    if (k.emb)
         if (int rc = check_front_emb(name, front, V, text_len)) return rc;
-    if (T < 1) return fail(INFV_ERR_INVALID, "%s: T must be >= 1", name);
-    const int n_live = fc ? fc->n_tokens : T * c.tokens_per_frame;   // tokens a chunk holds in `frames`
+    if (k.T < 1) return fail(INFV_ERR_INVALID, "%s: T must be >= 1", name);
+    const int n_live = k.n_live = fc ? fc->n_tokens : k.T * c.tokens_per_frame;
     if (!fc && n_live % 32) return fail(INFV_ERR_UNSUPPORTED, "%s: T * tokens_per_frame = %d is no multiple of 32", name, n_live);
-    bool pad = false;                                          // frames: planes and score rows padded to the next multiple of 64
     if (fc) {
         if (n_live < 1) return fail(INFV_ERR_INVALID, "%s: n_tokens = %d, must be >= 1", name, n_live);
         if (n_live > 0x7fffffff - 128) return fail(INFV_ERR_UNSUPPORTED, "%s: n_tokens = %d is too large", name, n_live);
         if (c.enc_width % 64) return fail(INFV_ERR_UNSUPPORTED, "%s: enc_width = %d is no multiple of 64", name, c.enc_width);
-        pad = n_live % 64 != 0 && split_path(h, 64);
-        if (n_live % 32 && !pad)
+        k.pad = n_live % 64 != 0 && split_path(h, 64);
+        if (n_live % 32 && !k.pad)
             return fail(INFV_ERR_UNSUPPORTED, "%s: the fp32 contractions (set_precision(h, 1) / INFV_VQF_FP32) need n_tokens %% 32 == 0, got %d", name, n_live);
     }
-    const int n_tokens = pad ? (n_live + 63) / 64 * 64 : n_live;   // keys a chunk has in the contractions (pad keys: zeros, no mass)
-    if (vis_ln && (c.enc_width % 64 || c.enc_width > kTokenLnMaxWidth))
+    k.n_tokens = k.pad ? (n_live + 63) / 64 * 64 : n_live;
+    if (k.vis_ln && (c.enc_width % 64 || c.enc_width > kTokenLnMaxWidth))
         return fail(INFV_ERR_UNSUPPORTED, "%s: the vision LayerNorm needs enc_width = %d to be a multiple of 64, at most %d", name, c.enc_width,
                     kTokenLnMaxWidth);
-    if (!tok_arg && h->tok != INFV_TOKENS_F32)
+    if (!k.tok_arg && h->tok != INFV_TOKENS_F32)
         return fail(INFV_ERR_UNSUPPORTED, "%s: fp16 / bf16 frame tokens are not supported on this path (the _tok entry point takes them)", name);
-    int n_cross = 0;
-    for (int l = 0; l < Ln; ++l) n_cross += w->layers[l].has_cross != 0;
-    const bool use_ltm = !fc && c.alpha != 1.0f && n_cross > 0;   // (frames: position_embedding_ext == None, no memory is called)
-    const int n_h = use_ltm ? V * n_cross : 0;
-    if (use_ltm) {
-        if (!ltm) return fail(INFV_ERR_INVALID, "%s: alpha != 1 needs the LTM handles of every video and cross layer", name);
-        std::vector<infv_ltm_handle> all(ltm, ltm + n_h);
-        for (int i = 0; i < n_h; ++i)
-            if (!all[i]) return fail(INFV_ERR_INVALID, "%s: LTM handle %d is null", name, i);
-        std::sort(all.begin(), all.end());
-        if (std::adjacent_find(all.begin(), all.end()) != all.end())
-            return fail(INFV_ERR_INVALID, "%s: an LTM handle appears twice (every video and cross layer needs its own memory)", name);
+    for (int l = 0; l < Ln; ++l) k.n_cross += w->layers[l].has_cross != 0;
+    k.use_ltm = !fc && c.alpha != 1.0f && k.n_cross > 0;       // (frames: position_embedding_ext == None, no memory is called)
+    k.n_h = k.use_ltm ? V * k.n_cross : 0;
+    if (k.use_ltm) {
+        if (!k.ltm) return fail(INFV_ERR_INVALID, "%s: alpha != 1 needs the LTM handles of every video and cross layer", name);
+        if (int rc = check_distinct_handles(name, k.ltm, k.n_h, "cross layer")) return rc;
     }
-    if ((proj_out || proj_mean) && (c.proj_out <= 0 || !w->mistral_proj.w))
+    if ((k.proj_out || k.proj_mean) && (c.proj_out <= 0 || !w->mistral_proj.w))
         return fail(INFV_ERR_INVALID, "%s: projected output without mistral_proj", name);
     if (fc && fc->out_dtype != INFV_TOKENS_F32) {             // the last layer's epilogue writes the 2-byte rows: its 16-byte form only
         const infv_vqf_vc_layer& L = w->layers[Ln - 1];
@@ -1040,317 +1018,332 @@ static int vc_impl(const char* name, infv_vqf_handle h, const infv_ltm_handle* l
     }
     if (fc && h->tap_dst && (h->tap_layer >= Ln || !w->layers[h->tap_layer].has_cross))
         return fail(INFV_ERR_INVALID, "%s: the context tap names layer %d, which is no cross-attention layer of these weights", name, h->tap_layer);
-    const int C = cu[V];
-    if (C == 0) {                                             // no chunk: new_video still starts every memory afresh
-        if (use_ltm && new_video)
-            for (int i = 0; i < n_h; ++i) infv_ltm_reset(ltm[i]);
+    if (cu[V] == 0) {                                         // no chunk: new_video still starts every memory afresh
+        if (k.use_ltm && k.new_video)
+            for (int i = 0; i < k.n_h; ++i) infv_ltm_reset(k.ltm[i]);
         return INFV_OK;
     }
-    if (!frames || (!hidden_in && !emb)) return fail(INFV_ERR_INVALID, "%s: null frames or hidden_in", name);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (use_ltm)
-        if (int rc = ensure_streams(h)) return rc;
+    if (!k.frames || (!k.hidden_in && !k.emb)) return fail(INFV_ERR_INVALID, "%s: null frames or hidden_in", name);
+    const int C = k.C = cu[V];
+    k.Cf = k.streams ? fcu[F] : C;
+    k.M = (long)C * Q;
+    k.chunk_k = (long)k.n_tokens * c.enc_width;
+    k.src_k = (long)n_live * c.enc_width;
+    k.RB = C < kRowBlockVideos ? C : kRowBlockVideos;
+    k.NB = pick_short_nb(h, C, k.n_tokens);
+    return INFV_OK;
+}
 
-    // ---- host tables: per chunk its video's text length, the offset of its packed text rows, its rows in hidden_in / hidden_out
-    std::vector<int32_t> n_valid(C), toff(C + 1, 0), q_dst(C), q_src(C), t_src(C), tl(C), o_q(C), o_t(C), q_n(C, Q);
-    {
-        int32_t in_row = 0, c_i = 0;
+static void vc_tables(const infv_vqf_s* h, VcCall& k, VcTables& t) {
+    const int Q = h->cfg.n_query, C = k.C, V = k.V;
+    const int32_t* cu = k.cu;
+    t.n_valid.resize(C); t.toff.assign(C + 1, 0); t.q_dst.resize(C); t.q_src.resize(C); t.t_src.resize(C); t.tl.resize(C);
+    t.o_q.resize(C); t.o_t.resize(C); t.q_n.assign(C, Q);
+    int32_t in_row = 0;
+    for (int v = 0; v < V; ++v) {
+        for (int cc = cu[v]; cc < cu[v + 1]; ++cc) {
+            t.tl[cc] = k.text_len[v]; t.n_valid[cc] = Q + k.text_len[v]; t.toff[cc + 1] = t.toff[cc] + k.text_len[v];
+            t.q_dst[cc] = cc * Q; t.q_src[cc] = k.fc ? 0 : in_row; t.t_src[cc] = in_row + Q;   // (frames: one block of query rows for all)
+            t.o_q[cc] = cc * Q + t.toff[cc]; t.o_t[cc] = t.o_q[cc] + Q;
+        }
+        in_row += Q + k.text_len[v];
+    }
+    if (k.streams) {
+        t.src_chunk.resize(C); t.kbar0.resize(V);
         for (int v = 0; v < V; ++v) {
-            for (int cc = cu[v]; cc < cu[v + 1]; ++cc, ++c_i) {
-                tl[cc] = text_len[v]; n_valid[cc] = Q + text_len[v]; toff[cc + 1] = toff[cc] + text_len[v];
-                q_dst[cc] = cc * Q; q_src[cc] = fc ? 0 : in_row; t_src[cc] = in_row + Q;   // (frames: one block of query rows for all)
-                o_q[cc] = cc * Q + toff[cc]; o_t[cc] = o_q[cc] + Q;
-            }
-            in_row += Q + text_len[v];
+            t.kbar0[v] = k.fcu[k.frame_src[v]];
+            for (int i = 0; i < cu[v + 1] - cu[v]; ++i) t.src_chunk[cu[v] + i] = t.kbar0[v] + i;
         }
     }
-    const long M = (long)C * Q, Tt = toff[C];
-    const long chunk_k = (long)n_tokens * c.enc_width;         // elements of a chunk in the planes ...
-    const long src_k = (long)n_live * c.enc_width;             // ... and in `frames` (the same unless padded)
-    const int Cf = streams ? fcu[F] : C;                       // distinct chunks of frame tokens
-    TokLn ln_{}; const TokLn* ln = nullptr;                    // the vision LayerNorm on load (split path), else nullptr
-    if (vis_ln && n_cross > 0) {
+    const long Tt = k.Tt = t.toff[C];
+    k.TB = Tt < kTextFfnRows ? Tt : kTextFfnRows;
+    for (RowBlock b : RowBlocks{C, k.RB, 0}) k.tb_max = std::max<long>(k.tb_max, t.toff[b.c0 + b.nb] - t.toff[b.c0]);
+    t.off1.resize(k.RB);
+    t.hs_l.resize(k.use_ltm ? V : 0);
+}
+
+// The vision LayerNorm's statistics, and -- where the fp32 contractions run -- the fp32 copy of the distinct chunks they read
+static int vc_front_tokens(infv_vqf_s* h, VcCall& k) {
+    const infv_vqf_config& c = h->cfg;
+    if (k.vis_ln && k.n_cross > 0) {
         // (mean, 1 / sqrt(var + eps)) of every DISTINCT token row, once per call: 8 bytes per token
-        const size_t rows = (size_t)Cf * n_live;
-        if (rows * 2 * sizeof(float) > h->lnstats.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->lnstats.reserve(rows * 2 * sizeof(float))); }
-        HIP_TRY(launch_token_ln_stats(frames, tok, (long)rows, c.enc_width, front->vision_ln.eps, h->lnstats.p, stream));
-        if (split_path(h, n_tokens)) {
-            ln_ = TokLn{h->lnstats.as<float>(), front->vision_ln.gamma, front->vision_ln.beta};
-            ln = &ln_;
-        } else {                                               // the fp32 contractions from the normalised fp32 copy of the distinct chunks
-            const size_t elems = rows * c.enc_width;
-            if (elems * sizeof(float) > h->up.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->up.reserve(elems * sizeof(float))); }
-            HIP_TRY(launch_ln_tokens(frames, tok, (long)rows, c.enc_width, h->lnstats.p, front->vision_ln.gamma, front->vision_ln.beta,
-                                     h->up.as<float>(), stream));
-            frames = h->up.p; tok = INFV_TOKENS_F32;
+        const infv_vqf_vision_ln& vl = k.front->vision_ln;
+        const size_t rows = (size_t)k.Cf * k.n_live;
+        HIP_TRY(reserve_all({{h->lnstats, rows * 2 * sizeof(float)}}));
+        HIP_TRY(launch_token_ln_stats(k.frames, k.tok, (long)rows, c.enc_width, vl.eps, h->lnstats.p, k.stream));
+        if (split_path(h, k.n_tokens)) {
+            k.ln_ = TokLn{h->lnstats.as<float>(), vl.gamma, vl.beta};
+            k.ln = &k.ln_;
+        } else {                                               // the fp32 contractions from the normalised fp32 copy
+            HIP_TRY(reserve_all({{h->up, rows * c.enc_width * sizeof(float)}}));
+            HIP_TRY(launch_ln_tokens(k.frames, k.tok, (long)rows, c.enc_width, h->lnstats.p, vl.gamma, vl.beta, h->up.as<float>(), k.stream));
+            k.frames = h->up.p; k.tok = INFV_TOKENS_F32;
         }
     }
-    if (tok != INFV_TOKENS_F32 && n_cross > 0 && !split_path(h, n_tokens)) {   // today's fp32 kernels from an fp32 copy of the distinct chunks
-        const float* f32 = nullptr;
-        if (int rc = upcast_tokens(h, frames, tok, (size_t)Cf * chunk_k, &f32, stream)) return rc;
-        frames = f32; tok = INFV_TOKENS_F32;
-    }
-    std::vector<int32_t> src_chunk, kbar0;                     // streams: each stream-chunk's source chunk, each stream's first one
-    if (streams) {
-        src_chunk.resize(C); kbar0.resize(V);
-        for (int v = 0; v < V; ++v) {
-            kbar0[v] = fcu[frame_src[v]];
-            for (int i = 0; i < cu[v + 1] - cu[v]; ++i) src_chunk[cu[v] + i] = kbar0[v] + i;
-        }
-    }
-    const int RB = C < kRowBlockVideos ? C : kRowBlockVideos;  // chunks per row block of the token GEMMs (batch invariant: any size)
-    const long TB = Tt < kTextFfnRows ? Tt : kTextFfnRows;     // text rows per block of the text FFN
-    long tb_max = 0;                                           // text rows of the largest row block
-    for (int c0 = 0; c0 < C; c0 += RB) { const int c1 = c0 + RB < C ? c0 + RB : C; tb_max = std::max<long>(tb_max, toff[c1] - toff[c0]); }
-    const int NB = pick_short_nb(h, C, n_tokens);
-    {
-        const size_t act = (size_t)M * Hd * sizeof(float), tact = (size_t)Tt * Hd * sizeof(float);
-        const bool grow = act > h->vA.bytes || act > h->v1.bytes || act > h->v2.bytes || act > h->vxq.bytes || act > h->vshort.bytes ||
-                          act > h->vmerged.bytes || (use_ltm && act > h->valong.bytes) ||
-                          (size_t)RB * Q * 3 * Hd * sizeof(float) > h->vqkv.bytes || (size_t)RB * Q * Hd * sizeof(float) > h->vsa.bytes ||
-                          (size_t)RB * Q * c.inter * sizeof(float) > h->vinter.bytes || tact > h->tA.bytes || tact > h->t1.bytes ||
-                          (size_t)tb_max * 3 * Hd * sizeof(float) > h->tqkv.bytes || (size_t)tb_max * Hd * sizeof(float) > h->tsa.bytes ||
-                          (size_t)TB * c.inter * sizeof(float) > h->tinter.bytes ||
-                          (use_ltm && ((size_t)C * S * sizeof(double) > h->vu.bytes || (size_t)Cf * T * c.enc_width * sizeof(float) > h->vkbar.bytes)) ||
-                          (streams && (size_t)C * sizeof(int32_t) > h->smap.bytes);
-        if (grow) HIP_TRY(hipDeviceSynchronize());
-        if (streams) HIP_TRY(h->smap.reserve((size_t)C * sizeof(int32_t)));
-        HIP_TRY(h->vA.reserve(act)); HIP_TRY(h->v1.reserve(act)); HIP_TRY(h->v2.reserve(act)); HIP_TRY(h->vxq.reserve(act));
-        HIP_TRY(h->vshort.reserve(act)); HIP_TRY(h->vmerged.reserve(act));
-        if (use_ltm) {
-            HIP_TRY(h->valong.reserve(act));
-            HIP_TRY(h->vu.reserve((size_t)C * S * sizeof(double)));
-            HIP_TRY(h->vkbar.reserve((size_t)Cf * T * c.enc_width * sizeof(float)));
-        }
-        HIP_TRY(h->vqkv.reserve((size_t)RB * Q * 3 * Hd * sizeof(float)));
-        HIP_TRY(h->vsa.reserve((size_t)RB * Q * Hd * sizeof(float)));
-        HIP_TRY(h->vinter.reserve((size_t)RB * Q * c.inter * sizeof(float)));
-        if (Tt > 0) {
-            HIP_TRY(h->tA.reserve(tact)); HIP_TRY(h->t1.reserve(tact));
-            HIP_TRY(h->tqkv.reserve((size_t)tb_max * 3 * Hd * sizeof(float)));
-            HIP_TRY(h->tsa.reserve((size_t)tb_max * Hd * sizeof(float)));
-            HIP_TRY(h->tinter.reserve((size_t)TB * c.inter * sizeof(float)));
-        }
-    }
-    float* vA = h->vA.as<float>(); float* v1 = h->v1.as<float>(); float* v2 = h->v2.as<float>();
-    float* vxq = h->vxq.as<float>(); float* valong = h->valong.as<float>();
-    float* vshort = h->vshort.as<float>(); float* vmerged = h->vmerged.as<float>();
-    float* tA = h->tA.as<float>(); float* t1 = h->t1.as<float>();
+    if (k.n_cross == 0) return INFV_OK;
+    return fp32_tokens_unless_split(h, k.frames, k.tok, k.n_tokens, (size_t)k.Cf * k.chunk_k, k.stream);
+}
 
-    if (emb) {                                                 // the embedding layer writes the packed encoder input rows (Qformer.py:54-111)
+static int vc_workspaces(infv_vqf_s* h, const VcCall& k) {
+    const infv_vqf_config& c = h->cfg;
+    const size_t f = sizeof(float), Hd = c.hidden, rb = (size_t)k.RB * c.n_query;
+    const size_t act = (size_t)k.M * Hd * f, tact = (size_t)k.Tt * Hd * f;
+    HIP_TRY(reserve_all({{h->smap, k.streams ? (size_t)k.C * sizeof(int32_t) : 0},
+                         {h->vA, act}, {h->v1, act}, {h->v2, act}, {h->vxq, act}, {h->vshort, act}, {h->vmerged, act},
+                         {h->valong, k.use_ltm ? act : 0}, {h->vu, k.use_ltm ? (size_t)k.C * c.nb_samples * sizeof(double) : 0},
+                         {h->vkbar, k.use_ltm ? (size_t)k.Cf * k.T * c.enc_width * f : 0},
+                         {h->vqkv, rb * 3 * Hd * f}, {h->vsa, rb * Hd * f}, {h->vinter, rb * c.inter * f},
+                         {h->tA, tact}, {h->t1, tact}, {h->tqkv, (size_t)k.tb_max * 3 * Hd * f}, {h->tsa, (size_t)k.tb_max * Hd * f},
+                         {h->tinter, (size_t)k.TB * c.inter * f}}));
+    return INFV_OK;
+}
+
+// Every chunk starts from its video's encoder input rows: the embedding layer's (Qformer.py:54-111) or hidden_in
+static int vc_input_rows(infv_vqf_s* h, VcCall& k, const VcTables& t) {
+    const int Q = h->cfg.n_query, Hd = h->cfg.hidden;
+    if (k.emb) {
         long n_in = 0;
-        for (int v = 0; v < V; ++v) n_in += Q + text_len[v];
-        const size_t need = (size_t)n_in * Hd * sizeof(float);
-        if (need > h->embrows.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->embrows.reserve(need)); }
-        if (int rc = run_embed(h, front, V, text_len, h->embrows.as<float>(), stream)) return rc;
-        hidden_in = h->embrows.as<float>();
+        for (int v = 0; v < k.V; ++v) n_in += Q + k.text_len[v];
+        HIP_TRY(reserve_all({{h->embrows, (size_t)n_in * Hd * sizeof(float)}}));
+        if (int rc = run_embed(h, k.front, k.V, k.text_len, h->embrows.as<float>(), k.stream)) return rc;
+        k.hidden_in = h->embrows.as<float>();
     }
-    // ---- every chunk starts from its video's encoder input rows
-    HIP_TRY(launch_qf_copy_rows(hidden_in, vA, q_dst.data(), q_src.data(), q_n.data(), C, Hd, stream));
-    if (Tt > 0) HIP_TRY(launch_qf_copy_rows(hidden_in, tA, toff.data(), t_src.data(), tl.data(), C, Hd, stream));
+    HIP_TRY(launch_qf_copy_rows(k.hidden_in, h->vA.as<float>(), t.q_dst.data(), t.q_src.data(), t.q_n.data(), k.C, Hd, k.stream));
+    if (k.Tt > 0) HIP_TRY(launch_qf_copy_rows(k.hidden_in, h->tA.as<float>(), t.toff.data(), t.t_src.data(), t.tl.data(), k.C, Hd, k.stream));
+    return INFV_OK;
+}
 
-    // ---- ONE pass over the frame tokens: split-bf16 operands of every cross layer's short-term attention (kept for the call
-    //      when they fit INFV_VQF_SPLIT_CACHE_GB) and the frame means every cross layer's memories step from
-    SplitRef wref{}; bool have_w = false, have_kbar = false;
-    if (n_cross > 0) {
-        // (streams: the distinct chunks only; bf16 tokens: only the transposed plane is written, as in infv_vqf_encode_video)
-        const double need_gb = plane_bytes(tok, ln != nullptr, pad) * (double)Cf * (double)chunk_k / 1e9;
-        if (h->fuse && split_path(h, n_tokens) && need_gb <= h->split_cache_gb) {
-            have_kbar = use_ltm && token_pass_gives_means(c.tokens_per_frame);   // (where a frame divides the 64-token tile)
-            if (int rc = prepare_split(h, frames, tok, Cf, n_tokens, have_kbar ? h->vkbar.as<float>() : nullptr, true, &wref, stream, 0, 0, ln,
-                                       pad ? n_live : 0)) return rc;
-            have_w = true;
-        }
-        if (use_ltm && !have_kbar && ln) {                     // pooling with the LayerNorm on load: the means of the normalised tokens
-            HIP_TRY(launch_pool_ln(frames, tok, ln->stats, ln->gamma, ln->beta, h->vkbar.as<float>(), (int64_t)Cf * T, c.tokens_per_frame,
-                                   c.enc_width, stream));
-        } else if (use_ltm && !have_kbar) {
-            if (int rc = infv_ltm_set_token_dtype(ltm[0], tok)) return rc;
-            const int rc_pool = infv_ltm_pool(ltm[0], frames, (int64_t)Cf * T, h->vkbar.as<float>(), stream_);
-            if (int rc = infv_ltm_set_token_dtype(ltm[0], INFV_TOKENS_F32)) return rc;   // (left on fp32, as before)
-            if (rc_pool) return rc_pool;
-        }
+// ONE pass over the frame tokens: split-bf16 operands of every cross layer's short-term attention (kept for the call when they fit
+// INFV_VQF_SPLIT_CACHE_GB) and the frame means every cross layer's memories step from; then the stream map.
+static int vc_token_pass(infv_vqf_s* h, VcCall& k, const VcTables& t) {
+    if (k.n_cross == 0) return INFV_OK;
+    const infv_vqf_config& c = h->cfg;
+    float* kbar = h->vkbar.as<float>();
+    // (streams: the distinct chunks only; bf16 tokens: only the transposed plane is written, as in infv_vqf_encode_video)
+    const double need_gb = plane_bytes(k.tok, k.ln != nullptr, k.pad) * (double)k.Cf * (double)k.chunk_k / 1e9;
+    if (h->fuse && split_path(h, k.n_tokens) && need_gb <= h->split_cache_gb) {
+        k.have_kbar = k.use_ltm && token_pass_gives_means(c.tokens_per_frame);   // (where a frame divides the 64-token tile)
+        if (int rc = prepare_split(h, k.frames, k.tok, k.Cf, k.n_tokens, k.have_kbar ? kbar : nullptr, true, &k.wref, k.stream, 0, 0, k.ln,
+                                   k.pad ? k.n_live : 0)) return rc;
+        k.have_w = true;
+    }
+    if (k.use_ltm && !k.have_kbar && k.ln) {                   // pooling with the LayerNorm on load: the means of the normalised tokens
+        HIP_TRY(launch_pool_ln(k.frames, k.tok, k.ln->stats, k.ln->gamma, k.ln->beta, kbar, (int64_t)k.Cf * k.T, c.tokens_per_frame, c.enc_width,
+                               k.stream));
+    } else if (k.use_ltm && !k.have_kbar) {
+        if (int rc = infv_ltm_set_token_dtype(k.ltm[0], k.tok)) return rc;
+        const int rc_pool = infv_ltm_pool(k.ltm[0], k.frames, (int64_t)k.Cf * k.T, kbar, k.stream);
+        if (int rc = infv_ltm_set_token_dtype(k.ltm[0], INFV_TOKENS_F32)) return rc;   // (left on fp32, as before)
+        if (rc_pool) return rc_pool;
     }
     // the chunk map reaches the device in kernel arguments, once per call: no host buffer outlives the call, nothing waits on the host
-    if (streams && n_cross > 0) HIP_TRY(launch_qf_write_map(h->smap.as<int32_t>(), src_chunk.data(), C, stream));
-    // The frame operand of the short-term attention of stream-chunks [c0, c0 + nb): *fr (fp32 path) or the planes *r, and the map
-    // the contractions read them through (nullptr: chunk b of the sub-batch is entry b).
-    //   videos:  today's -- the cached planes at c0, else the caller's tokens at c0 (split per sub-batch inside short_attention)
-    //   streams: the cached planes of the DISTINCT chunks, or the caller's tokens on the fp32 path, read through the map; where the
-    //            planes do not fit, each contiguous run of source chunks is split into the sub-batch's own planes (identity map)
-    auto operand_at = [&](int c0, int nb, SplitRef* r, const SplitRef** pre, const void** fr, const int32_t** map, bool* t_identity) -> int {
-        *pre = nullptr; *map = nullptr; *t_identity = false; *fr = tok_at(frames, tok, (long)c0 * src_k);
-        if (!streams) {
-            if (have_w) {
-                const long o = (long)c0 * chunk_k;
-                *r = SplitRef{wref.Fh + o, wref.Fl ? wref.Fl + o : nullptr, wref.Th + o, wref.Tl ? wref.Tl + o : nullptr};
-                *pre = r;
-            } else if (ln || pad) {                            // the split per sub-batch short_attention would issue, with the LayerNorm on load / padded
-                TokLn lc{};
-                if (ln) lc = TokLn{ln->stats + 2 * (size_t)c0 * n_live, ln->gamma, ln->beta};
-                if (int rc = prepare_split(h, *fr, tok, nb, n_tokens, nullptr, false, r, stream, 0, 0, ln ? &lc : nullptr, pad ? n_live : 0)) return rc;
-                *pre = r;
-            }
-            return INFV_OK;
-        }
-        if (have_w) { *r = wref; *pre = r; *map = h->smap.as<int32_t>() + c0; return INFV_OK; }
-        if (!split_path(h, n_tokens)) { *fr = frames; *map = h->smap.as<int32_t>() + c0; return INFV_OK; }
-        for (int b0 = 0; b0 < nb;) {
-            int b1 = b0 + 1;
-            while (b1 < nb && src_chunk[c0 + b1] == src_chunk[c0 + b1 - 1] + 1) ++b1;
-            TokLn lc{};
-            if (ln) lc = TokLn{ln->stats + 2 * (size_t)src_chunk[c0 + b0] * n_tokens, ln->gamma, ln->beta};
-            if (int rc = prepare_split(h, tok_at(frames, tok, (long)src_chunk[c0 + b0] * chunk_k), tok, b1 - b0, n_tokens, nullptr, false, r,
-                                       stream, b0, nb, ln ? &lc : nullptr)) return rc;
-            b0 = b1;
-        }
-        if (tok == INFV_TOKENS_BF16 && !ln) {                         // the untransposed operand is the caller's buffer: read through the map,
-            r->Fh = static_cast<const __bf16*>(frames);        // while the transposed plane just written holds the sub-batch in order
-            *map = h->smap.as<int32_t>() + c0; *t_identity = true;
-        }
-        *pre = r;
-        return INFV_OK;
-    };
-    std::vector<infv_ltm_handle> hs_l(use_ltm ? V : 0);
-    std::vector<int32_t> off1(RB);
+    if (k.streams) HIP_TRY(launch_qf_write_map(h->smap.as<int32_t>(), t.src_chunk.data(), k.C, k.stream));
+    return INFV_OK;
+}
 
-    int j_cross = 0;
-    for (int l = 0; l < Ln; ++l) {
-        const infv_vqf_vc_layer& L = w->layers[l];
-        const bool cross = L.has_cross != 0;
-        const bool last = l == Ln - 1;
-        const bool text_out = Tt > 0 && (!last || hidden_out);   // the last layer's text rows feed nothing but hidden_out
-        // ---- self-attention over query + text tokens, output dense + LayerNorm, cross query (row blocks of chunks) ----
-        for (int c0 = 0; c0 < C; c0 += RB) {
-            const int nb = C - c0 < RB ? C - c0 : RB;
-            const long r0 = (long)c0 * Q * Hd, t0 = toff[c0], tn = toff[c0 + nb] - t0;
-            LinearCall qkv{vA + r0, nb * Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
-            qkv.inv = true; qkv.y = h->vqkv.as<float>();
-            if (int rc = run_linear(h, qkv, stream)) return rc;
-            if (tn > 0) {
-                LinearCall qkt{tA + t0 * Hd, (int)tn, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
-                qkt.inv = true; qkt.y = h->tqkv.as<float>();
-                if (int rc = run_linear(h, qkt, stream)) return rc;
-            }
-            for (int b = 0; b < nb; ++b) off1[b] = toff[c0 + b] - (int32_t)t0;
-            VcAttn a{};
-            a.qkv0 = h->vqkv.as<float>(); a.rows0 = Q; a.nsplit = Q; a.qkv1 = h->tqkv.as<float>();
-            a.ctx0 = h->vsa.as<float>(); a.ctx1 = h->tsa.as<float>(); a.H = c.n_heads; a.n_alloc = 0;
-            HIP_TRY(launch_qf_vc_self_attention(a, nb, n_valid.data() + c0, off1.data(), stream));
-            LinearCall so{h->vsa.as<float>(), nb * Q, Hd, {&L.self_o}, 1, Hd};
-            so.inv = true; so.residual = vA + r0; so.res_rows = nb * Q; so.ln = &L.self_ln; so.y = v1 + r0;
-            if (int rc = run_linear(h, so, stream)) return rc;
-            if (tn > 0 && text_out) {
-                LinearCall st{h->tsa.as<float>(), (int)tn, Hd, {&L.self_o}, 1, Hd};
-                st.inv = true; st.residual = tA + t0 * Hd; st.res_rows = (int)tn; st.ln = &L.self_ln; st.y = t1 + t0 * Hd;
-                if (int rc = run_linear(h, st, stream)) return rc;
-            }
-            if (cross) {
-                LinearCall xq{v1 + r0, nb * Q, Hd, {&L.x_q}, 1, Hd};
-                xq.inv = true; xq.y = vxq + r0;
-                if (int rc = run_linear(h, xq, stream)) return rc;
-            }
+// The frame operand of the short-term attention of stream-chunks [c0, c0 + nb): `frames` (fp32 path) or the planes `pre`, and the
+// map the contractions read them through (nullptr: chunk b of the sub-batch is entry b).
+//   videos:  the cached planes at c0, else the caller's tokens at c0 (split per sub-batch inside short_attention)
+//   streams: the cached planes of the DISTINCT chunks, or the caller's tokens on the fp32 path, read through the map; where the
+//            planes do not fit, each contiguous run of source chunks is split into the sub-batch's own planes (identity map)
+struct VcOperand {
+    int rc = INFV_OK;
+    SplitRef pre{}; bool has_pre = false;
+    const void* frames = nullptr;
+    const int32_t* map = nullptr;
+    bool t_identity = false;   // the transposed plane holds the sub-batch in order: only the untransposed operand goes through the map
+};
+static VcOperand vc_operand_at(infv_vqf_s* h, const VcCall& k, const VcTables& t, int c0, int nb) {
+    VcOperand op;
+    const TokLn* ln = k.ln;
+    op.frames = tok_at(k.frames, k.tok, (long)c0 * k.src_k);
+    if (!k.streams) {
+        if (k.have_w) {
+            op.pre = split_ref_at(k.wref, c0, k.chunk_k); op.has_pre = true;
+        } else if (ln || k.pad) {                              // the split per sub-batch short_attention would issue, with the LayerNorm on load / padded
+            TokLn lc{};
+            if (ln) lc = TokLn{ln->stats + 2 * (size_t)c0 * k.n_live, ln->gamma, ln->beta};
+            op.rc = prepare_split(h, op.frames, k.tok, nb, k.n_tokens, nullptr, false, &op.pre, k.stream, 0, 0, ln ? &lc : nullptr, k.pad ? k.n_live : 0);
+            op.has_pre = true;
         }
-        const float* qin = v1;                                 // the query rows entering the query FFN
-        if (cross) {
-            // ---- this layer's V memories with per-chunk queries on the worker stream, beside the short-term attention ----
-            if (use_ltm) {
-                infv_ltm_proj pr{};
-                pr.wk = L.x_k.w; pr.bk = L.x_k.b; pr.wv = L.x_v.w; pr.bv = L.x_v.b;
-                if (u)                                         // u[:, j, :] -> contiguous [C][S] for the one-layer handles
-                    HIP_TRY(hipMemcpy2DAsync(h->vu.p, (size_t)S * sizeof(double), u + (size_t)j_cross * S, (size_t)n_cross * S * sizeof(double),
-                                             (size_t)S * sizeof(double), (size_t)C, hipMemcpyDeviceToDevice, stream));
-                HIP_TRY(hipEventRecord(h->ev_main, stream));
-                HIP_TRY(hipStreamWaitEvent(h->side, h->ev_main, 0));
-                for (int v = 0; v < V; ++v) hs_l[v] = ltm[(size_t)v * n_cross + j_cross];
-                if (int rc = infv_ltm_steps_videos_from(hs_l.data(), V, cu, h->vkbar.as<float>(), streams ? kbar0.data() : nullptr, T, vxq, 1,
-                                                        Q, &pr, u ? h->vu.as<double>() : nullptr, new_video, valong, h->side)) return rc;
-                HIP_TRY(hipEventRecord(h->ev_side, h->side));
-            }
-            for (int c0 = 0; c0 < C; c0 += NB) {
-                const int nb = C - c0 < NB ? C - c0 : NB;
-                SplitRef sr; const SplitRef* pre; const void* fr; const int32_t* map; bool t_identity;
-                if (int rc = operand_at(c0, nb, &sr, &pre, &fr, &map, &t_identity)) return rc;
-                if (int rc = short_attention(h, fr, tok, nb, n_tokens, vxq + (long)c0 * Q * Hd, false, &L.x_k, &L.x_v,
-                                             nullptr, (use_ltm ? vshort : vmerged) + (long)c0 * Q * Hd, stream, false,
-                                             pre, nullptr, kInvariantNb, map, t_identity, pad ? n_live : 0)) return rc;
-            }
-            if (use_ltm) {
-                HIP_TRY(hipStreamWaitEvent(stream, h->ev_side, 0));
-                for (long m0 = 0; m0 < M; m0 += kMergeRows) {  // merged = alpha * short + (1 - alpha) * long
-                    QfEpilogue em{};
-                    em.parts = vshort + m0 * Hd; em.nsplit = 1; em.ld_in = Hd; em.seg_cols = Hd;
-                    em.scale = c.alpha; em.res_scale = (float)(1.0 - (double)c.alpha);
-                    em.residual = valong + m0 * Hd; em.ld_res = Hd; em.res_rows = (int)(M - m0 < kMergeRows ? M - m0 : kMergeRows);
-                    em.out = vmerged + m0 * Hd; em.ld_out = Hd; em.M = em.res_rows; em.width = Hd; em.eps = c.ln_eps;
-                    HIP_TRY(launch_qf_epilogue(em, stream));
-                }
-            }
-            if (fc && h->tap_dst && l == h->tap_layer)         // (tests: this layer's cross-attention context, Qformer.py:303-304)
-                HIP_TRY(hipMemcpyAsync(h->tap_dst, vmerged, (size_t)M * Hd * sizeof(float), hipMemcpyDeviceToDevice, stream));
-            for (int c0 = 0; c0 < C; c0 += RB) {
-                const int nb = C - c0 < RB ? C - c0 : RB;
-                const long r0 = (long)c0 * Q * Hd;
-                LinearCall xo{vmerged + r0, nb * Q, Hd, {&L.x_o}, 1, Hd};
-                xo.inv = true; xo.residual = v1 + r0; xo.res_rows = nb * Q; xo.ln = &L.x_ln; xo.y = v2 + r0;
-                if (int rc = run_linear(h, xo, stream)) return rc;
-            }
-            qin = v2;
-            ++j_cross;
-        }
-        // ---- query FFN on the query rows, text FFN on the text rows (Qformer.py:483-496) ----
-        for (int c0 = 0; c0 < C; c0 += RB) {
-            const int nb = C - c0 < RB ? C - c0 : RB;
-            const long r0 = (long)c0 * Q * Hd;
-            LinearCall fi{qin + r0, nb * Q, Hd, {&L.q_ffn_in}, 1, c.inter};
-            fi.inv = true; fi.act = QF_ACT_GELU; fi.y = h->vinter.as<float>();
-            if (int rc = run_linear(h, fi, stream)) return rc;
-            LinearCall fo{h->vinter.as<float>(), nb * Q, c.inter, {&L.q_ffn_out}, 1, Hd};
-            fo.inv = true; fo.residual = qin + r0; fo.res_rows = nb * Q; fo.ln = &L.q_ffn_ln; fo.y = vA + r0;
-            if (fc && last && fc->out_dtype != INFV_TOKENS_F32) {   // the frame tokens leave in the type their consumer reads: no fp32 row is written
-                fo.y16 = static_cast<char*>(fc->out) + 2 * r0; fo.y16_dtype = fc->out_dtype;
-            }
-            if (int rc = run_linear(h, fo, stream)) return rc;
-        }
-        if (text_out)
-            for (long m0 = 0; m0 < Tt; m0 += TB) {
-                const int m = (int)(Tt - m0 < TB ? Tt - m0 : TB);
-                LinearCall fi{t1 + m0 * Hd, m, Hd, {&L.t_ffn_in}, 1, c.inter};
-                fi.inv = true; fi.act = QF_ACT_GELU; fi.y = h->tinter.as<float>();
-                if (int rc = run_linear(h, fi, stream)) return rc;
-                LinearCall fo{h->tinter.as<float>(), m, c.inter, {&L.t_ffn_out}, 1, Hd};
-                fo.inv = true; fo.residual = t1 + m0 * Hd; fo.res_rows = m; fo.ln = &L.t_ffn_ln; fo.y = tA + m0 * Hd;
-                if (int rc = run_linear(h, fo, stream)) return rc;
-            }
+        return op;
     }
-    if (hidden_out) {
-        HIP_TRY(launch_qf_copy_rows(vA, hidden_out, o_q.data(), q_dst.data(), q_n.data(), C, Hd, stream));
-        if (Tt > 0) HIP_TRY(launch_qf_copy_rows(tA, hidden_out, o_t.data(), toff.data(), tl.data(), C, Hd, stream));
+    op.map = h->smap.as<int32_t>() + c0;
+    if (k.have_w) { op.pre = k.wref; op.has_pre = true; return op; }
+    if (!split_path(h, k.n_tokens)) { op.frames = k.frames; return op; }
+    op.map = nullptr;
+    const int32_t* src = t.src_chunk.data() + c0;
+    for (int b0 = 0; b0 < nb && op.rc == INFV_OK;) {
+        int b1 = b0 + 1;
+        while (b1 < nb && src[b1] == src[b1 - 1] + 1) ++b1;
+        TokLn lc{};
+        if (ln) lc = TokLn{ln->stats + 2 * (size_t)src[b0] * k.n_tokens, ln->gamma, ln->beta};
+        op.rc = prepare_split(h, tok_at(k.frames, k.tok, (long)src[b0] * k.chunk_k), k.tok, b1 - b0, k.n_tokens, nullptr, false, &op.pre, k.stream,
+                              b0, nb, ln ? &lc : nullptr);
+        b0 = b1;
     }
-    if (proj_out || proj_mean) {
-        float* lo = proj_out;
-        if (!lo) {                                             // only the mean is wanted: project into scratch
-            const size_t need = (size_t)M * c.proj_out * sizeof(float);
-            if (need > h->S.bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(h->S.reserve(need)); }
-            lo = h->S.as<float>();
+    if (k.tok == INFV_TOKENS_BF16 && !ln) {                   // the untransposed operand is the caller's buffer: read through the map,
+        op.pre.Fh = static_cast<const __bf16*>(k.frames);      // while the transposed plane just written holds the sub-batch in order
+        op.map = h->smap.as<int32_t>() + c0; op.t_identity = true;
+    }
+    op.has_pre = true;
+    return op;
+}
+
+// Layer l: self-attention over query + text tokens, output dense + LayerNorm, cross query (row blocks of chunks)
+static int vc_self_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l) {
+    const infv_vqf_config& c = h->cfg;
+    const infv_vqf_vc_layer& L = k.w->layers[l];
+    const int Q = c.n_query, Hd = c.hidden;
+    const bool text_out = k.Tt > 0 && (l < k.w->n_layers - 1 || k.hidden_out);   // the last layer's text rows feed nothing but hidden_out
+    float* vA = h->vA.as<float>(); float* v1 = h->v1.as<float>(); float* tA = h->tA.as<float>(); float* t1 = h->t1.as<float>();
+    for (RowBlock b : RowBlocks{k.C, k.RB, (long)Q * Hd}) {
+        const int nb = b.nb;
+        const long r0 = b.r0, t0 = t.toff[b.c0], tn = t.toff[b.c0 + nb] - t0;
+        LinearCall qkv{vA + r0, nb * Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
+        qkv.inv = true; qkv.y = h->vqkv.as<float>();
+        if (int rc = run_linear(h, qkv, k.stream)) return rc;
+        if (tn > 0) {
+            LinearCall qkt{tA + t0 * Hd, (int)tn, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
+            qkt.inv = true; qkt.y = h->tqkv.as<float>();
+            if (int rc = run_linear(h, qkt, k.stream)) return rc;
         }
-        for (int c0 = 0; c0 < C; c0 += RB) {
-            const int nb = C - c0 < RB ? C - c0 : RB;
-            LinearCall pj{vA + (long)c0 * Q * Hd, nb * Q, Hd, {&w->mistral_proj}, 1, c.proj_out};
-            pj.inv = true; pj.y = lo + (long)c0 * Q * c.proj_out;
-            if (int rc = run_linear(h, pj, stream)) return rc;
+        for (int i = 0; i < nb; ++i) t.off1[i] = t.toff[b.c0 + i] - (int32_t)t0;
+        VcAttn a{};
+        a.qkv0 = h->vqkv.as<float>(); a.rows0 = Q; a.nsplit = Q; a.qkv1 = h->tqkv.as<float>();
+        a.ctx0 = h->vsa.as<float>(); a.ctx1 = h->tsa.as<float>(); a.H = c.n_heads; a.n_alloc = 0;
+        HIP_TRY(launch_qf_vc_self_attention(a, nb, t.n_valid.data() + b.c0, t.off1.data(), k.stream));
+        LinearCall so{h->vsa.as<float>(), nb * Q, Hd, {&L.self_o}, 1, Hd};
+        so.inv = true; so.residual = vA + r0; so.res_rows = nb * Q; so.ln = &L.self_ln; so.y = v1 + r0;
+        if (int rc = run_linear(h, so, k.stream)) return rc;
+        if (tn > 0 && text_out) {
+            LinearCall st{h->tsa.as<float>(), (int)tn, Hd, {&L.self_o}, 1, Hd};
+            st.inv = true; st.residual = tA + t0 * Hd; st.res_rows = (int)tn; st.ln = &L.self_ln; st.y = t1 + t0 * Hd;
+            if (int rc = run_linear(h, st, k.stream)) return rc;
         }
-        if (proj_mean) HIP_TRY(launch_qf_mean_segments(lo, cu, V, (long)Q * c.proj_out, proj_mean, stream));
+        if (L.has_cross) {
+            LinearCall xq{v1 + r0, nb * Q, Hd, {&L.x_q}, 1, Hd};
+            xq.inv = true; xq.y = h->vxq.as<float>() + r0;
+            if (int rc = run_linear(h, xq, k.stream)) return rc;
+        }
     }
     return INFV_OK;
+}
+
+// Cross layer l, the j-th of them: its V memories with per-chunk queries on the worker stream, beside the short-term attention;
+// the merge of the two; the context tap; the cross output
+static int vc_cross_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l, int j) {
+    const infv_vqf_config& c = h->cfg;
+    const infv_vqf_vc_layer& L = k.w->layers[l];
+    const int Q = c.n_query, Hd = c.hidden;
+    float* vxq = h->vxq.as<float>(); float* vmerged = h->vmerged.as<float>();
+    if (k.use_ltm) {
+        infv_ltm_proj pr{};
+        pr.wk = L.x_k.w; pr.bk = L.x_k.b; pr.wv = L.x_v.w; pr.bv = L.x_v.b;
+        if (int rc = ltm_u_slice(h, k.u, j, k.n_cross, k.C, k.stream)) return rc;
+        HIP_TRY(hipEventRecord(h->ev_main, k.stream));
+        HIP_TRY(hipStreamWaitEvent(h->side, h->ev_main, 0));
+        for (int v = 0; v < k.V; ++v) t.hs_l[v] = k.ltm[(size_t)v * k.n_cross + j];
+        if (int rc = infv_ltm_steps_videos_from(t.hs_l.data(), k.V, k.cu, h->vkbar.as<float>(), k.streams ? t.kbar0.data() : nullptr, k.T, vxq, 1,
+                                                Q, &pr, k.u ? h->vu.as<double>() : nullptr, k.new_video, h->valong.as<float>(), h->side)) return rc;
+        HIP_TRY(hipEventRecord(h->ev_side, h->side));
+    }
+    for (RowBlock b : RowBlocks{k.C, k.NB, (long)Q * Hd}) {
+        const VcOperand op = vc_operand_at(h, k, t, b.c0, b.nb);
+        if (op.rc) return op.rc;
+        if (int rc = short_attention(h, op.frames, k.tok, b.nb, k.n_tokens, vxq + b.r0, false, &L.x_k, &L.x_v, nullptr,
+                                     (k.use_ltm ? h->vshort.as<float>() : vmerged) + b.r0, k.stream, false, op.has_pre ? &op.pre : nullptr,
+                                     nullptr, kInvariantNb, op.map, op.t_identity, k.pad ? k.n_live : 0)) return rc;
+    }
+    if (k.use_ltm) {
+        HIP_TRY(hipStreamWaitEvent(k.stream, h->ev_side, 0));
+        if (int rc = alpha_merge(h, k.M, k.stream)) return rc;
+    }
+    if (k.fc && h->tap_dst && l == h->tap_layer)               // (tests: this layer's cross-attention context, Qformer.py:303-304)
+        HIP_TRY(hipMemcpyAsync(h->tap_dst, vmerged, (size_t)k.M * Hd * sizeof(float), hipMemcpyDeviceToDevice, k.stream));
+    for (RowBlock b : RowBlocks{k.C, k.RB, (long)Q * Hd}) {
+        LinearCall xo{vmerged + b.r0, b.nb * Q, Hd, {&L.x_o}, 1, Hd};
+        xo.inv = true; xo.residual = h->v1.as<float>() + b.r0; xo.res_rows = b.nb * Q; xo.ln = &L.x_ln; xo.y = h->v2.as<float>() + b.r0;
+        if (int rc = run_linear(h, xo, k.stream)) return rc;
+    }
+    return INFV_OK;
+}
+
+// Layer l: query FFN on the query rows, text FFN on the text rows (Qformer.py:483-496)
+static int vc_ffn_block(infv_vqf_s* h, const VcCall& k, int l) {
+    const infv_vqf_config& c = h->cfg;
+    const infv_vqf_vc_layer& L = k.w->layers[l];
+    const int Q = c.n_query, Hd = c.hidden;
+    const bool last = l == k.w->n_layers - 1;
+    const float* qin = L.has_cross ? h->v2.as<float>() : h->v1.as<float>();   // the query rows entering the query FFN
+    for (RowBlock b : RowBlocks{k.C, k.RB, (long)Q * Hd}) {
+        LinearCall fi{qin + b.r0, b.nb * Q, Hd, {&L.q_ffn_in}, 1, c.inter};
+        fi.inv = true; fi.act = QF_ACT_GELU; fi.y = h->vinter.as<float>();
+        if (int rc = run_linear(h, fi, k.stream)) return rc;
+        LinearCall fo{h->vinter.as<float>(), b.nb * Q, c.inter, {&L.q_ffn_out}, 1, Hd};
+        fo.inv = true; fo.residual = qin + b.r0; fo.res_rows = b.nb * Q; fo.ln = &L.q_ffn_ln; fo.y = h->vA.as<float>() + b.r0;
+        if (k.fc && last && k.fc->out_dtype != INFV_TOKENS_F32) {   // the frame tokens leave in the type their consumer reads: no fp32 row is written
+            fo.y16 = static_cast<char*>(k.fc->out) + 2 * b.r0; fo.y16_dtype = k.fc->out_dtype;
+        }
+        if (int rc = run_linear(h, fo, k.stream)) return rc;
+    }
+    if (!(k.Tt > 0 && (!last || k.hidden_out))) return INFV_OK;   // the last layer's text rows feed nothing but hidden_out
+    float* tA = h->tA.as<float>(); float* t1 = h->t1.as<float>();
+    const long Tt = k.Tt, TB = k.TB;
+    for (long m0 = 0; m0 < Tt; m0 += TB) {
+        const int m = (int)(Tt - m0 < TB ? Tt - m0 : TB);
+        LinearCall fi{t1 + m0 * Hd, m, Hd, {&L.t_ffn_in}, 1, c.inter};
+        fi.inv = true; fi.act = QF_ACT_GELU; fi.y = h->tinter.as<float>();
+        if (int rc = run_linear(h, fi, k.stream)) return rc;
+        LinearCall fo{h->tinter.as<float>(), m, c.inter, {&L.t_ffn_out}, 1, Hd};
+        fo.inv = true; fo.residual = t1 + m0 * Hd; fo.res_rows = m; fo.ln = &L.t_ffn_ln; fo.y = tA + m0 * Hd;
+        if (int rc = run_linear(h, fo, k.stream)) return rc;
+    }
+    return INFV_OK;
+}
+
+static int vc_outputs(infv_vqf_s* h, const VcCall& k, const VcTables& t) {
+    const int Hd = h->cfg.hidden;
+    if (k.hidden_out) {
+        HIP_TRY(launch_qf_copy_rows(h->vA.as<float>(), k.hidden_out, t.o_q.data(), t.q_dst.data(), t.q_n.data(), k.C, Hd, k.stream));
+        if (k.Tt > 0) HIP_TRY(launch_qf_copy_rows(h->tA.as<float>(), k.hidden_out, t.o_t.data(), t.toff.data(), t.tl.data(), k.C, Hd, k.stream));
+    }
+    if (k.proj_out || k.proj_mean)
+        return project_and_mean(h, RowBlocks{k.C, k.RB, (long)h->cfg.n_query * Hd}, &k.w->mistral_proj, true, k.proj_out, k.proj_mean, k.cu, k.V,
+                                k.stream);
+    return INFV_OK;
+}
+
+// The body of the six entry points below: the stages above, in call order
+static int vc_impl(infv_vqf_handle h, VcCall& k) {
+    if (int rc = vc_validate(h, k)) return rc;
+    if (k.C == 0) return INFV_OK;                              // no video or no chunk
+    if (k.use_ltm)
+        if (int rc = ensure_streams(h)) return rc;
+    VcTables t;
+    vc_tables(h, k, t);
+    if (int rc = vc_front_tokens(h, k)) return rc;
+    if (int rc = vc_workspaces(h, k)) return rc;
+    if (int rc = vc_input_rows(h, k, t)) return rc;
+    if (int rc = vc_token_pass(h, k, t)) return rc;
+    for (int l = 0, j_cross = 0; l < k.w->n_layers; ++l) {
+        if (int rc = vc_self_block(h, k, t, l)) return rc;
+        if (k.w->layers[l].has_cross)
+            if (int rc = vc_cross_block(h, k, t, l, j_cross++)) return rc;
+        if (int rc = vc_ffn_block(h, k, l)) return rc;
+    }
+    return vc_outputs(h, k, t);
 }
 
 int infv_vqf_vc_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
                               int32_t T, const infv_vqf_vc_weights* w, const float* hidden_in, const int32_t* text_len,
                               const double* u, int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean,
                               void* stream_) {
-    return vc_impl("vc_encode_videos", h, ltm, V, cu, frames, -1, 0, nullptr, nullptr, T, w, hidden_in, text_len, u, new_video, hidden_out,
-                   proj_out, proj_mean, stream_);
+    VcCall k;
+    k.name = "vc_encode_videos"; k.ltm = ltm; k.V = V; k.cu = cu; k.frames = frames; k.T = T; k.w = w; k.hidden_in = hidden_in;
+    k.text_len = text_len; k.u = u; k.new_video = new_video; k.hidden_out = hidden_out; k.proj_out = proj_out; k.proj_mean = proj_mean;
+    k.stream = static_cast<hipStream_t>(stream_);
+    return vc_impl(h, k);
 }
 
 int infv_vqf_vc_encode_streams(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const float* frames,
@@ -1358,8 +1351,11 @@ int infv_vqf_vc_encode_streams(infv_vqf_handle h, const infv_ltm_handle* ltm, in
                                const float* hidden_in, const int32_t* text_len, const double* u, int32_t new_video,
                                float* hidden_out, float* proj_out, float* proj_mean, void* stream_) {
     if (!fcu || !frame_src) return fail(INFV_ERR_INVALID, "vc_encode_streams: bad arguments");
-    return vc_impl("vc_encode_streams", h, ltm, V, cu, frames, -1, F, fcu, frame_src, T, w, hidden_in, text_len, u, new_video, hidden_out,
-                   proj_out, proj_mean, stream_);
+    VcCall k;
+    k.name = "vc_encode_streams"; k.ltm = ltm; k.V = V; k.cu = cu; k.frames = frames; k.F = F; k.fcu = fcu; k.frame_src = frame_src; k.T = T;
+    k.w = w; k.hidden_in = hidden_in; k.text_len = text_len; k.u = u; k.new_video = new_video; k.hidden_out = hidden_out;
+    k.proj_out = proj_out; k.proj_mean = proj_mean; k.stream = static_cast<hipStream_t>(stream_);
+    return vc_impl(h, k);
 }
 
 int infv_vqf_vc_encode_videos_tok(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
@@ -1367,8 +1363,11 @@ int infv_vqf_vc_encode_videos_tok(infv_vqf_handle h, const infv_ltm_handle* ltm,
                                   const int32_t* text_len, const double* u, int32_t new_video, float* hidden_out, float* proj_out,
                                   float* proj_mean, void* stream_) {
     if (token_dtype < 0) return fail(INFV_ERR_INVALID, "vc_encode_videos_tok: unknown token dtype %d", token_dtype);
-    return vc_impl("vc_encode_videos_tok", h, ltm, V, cu, frames, token_dtype, 0, nullptr, nullptr, T, w, hidden_in, text_len, u, new_video,
-                   hidden_out, proj_out, proj_mean, stream_);
+    VcCall k;
+    k.name = "vc_encode_videos_tok"; k.ltm = ltm; k.V = V; k.cu = cu; k.frames = frames; k.tok_arg = true; k.token_dtype = token_dtype; k.T = T;
+    k.w = w; k.hidden_in = hidden_in; k.text_len = text_len; k.u = u; k.new_video = new_video; k.hidden_out = hidden_out;
+    k.proj_out = proj_out; k.proj_mean = proj_mean; k.stream = static_cast<hipStream_t>(stream_);
+    return vc_impl(h, k);
 }
 
 int infv_vqf_vc_encode_streams_tok(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames,
@@ -1377,8 +1376,12 @@ int infv_vqf_vc_encode_streams_tok(infv_vqf_handle h, const infv_ltm_handle* ltm
                                    int32_t new_video, float* hidden_out, float* proj_out, float* proj_mean, void* stream_) {
     if (!fcu || !frame_src) return fail(INFV_ERR_INVALID, "vc_encode_streams_tok: bad arguments");
     if (token_dtype < 0) return fail(INFV_ERR_INVALID, "vc_encode_streams_tok: unknown token dtype %d", token_dtype);
-    return vc_impl("vc_encode_streams_tok", h, ltm, V, cu, frames, token_dtype, F, fcu, frame_src, T, w, hidden_in, text_len, u, new_video,
-                   hidden_out, proj_out, proj_mean, stream_);
+    VcCall k;
+    k.name = "vc_encode_streams_tok"; k.ltm = ltm; k.V = V; k.cu = cu; k.frames = frames; k.tok_arg = true; k.token_dtype = token_dtype;
+    k.F = F; k.fcu = fcu; k.frame_src = frame_src; k.T = T; k.w = w; k.hidden_in = hidden_in; k.text_len = text_len; k.u = u;
+    k.new_video = new_video; k.hidden_out = hidden_out; k.proj_out = proj_out; k.proj_mean = proj_mean;
+    k.stream = static_cast<hipStream_t>(stream_);
+    return vc_impl(h, k);
 }
 
 int infv_vqf_vc_encode_img(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_t V, const int32_t* cu, const void* frames, int32_t token_dtype,
@@ -1387,15 +1390,18 @@ int infv_vqf_vc_encode_img(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_
                            float* hidden_out, float* proj_out, float* proj_mean, void* stream_) {
     if (token_dtype < 0) return fail(INFV_ERR_INVALID, "vc_encode_img: unknown token dtype %d", token_dtype);
     if (frame_src && !fcu) return fail(INFV_ERR_INVALID, "vc_encode_img: bad arguments");
-    const bool streams = frame_src != nullptr;                 // NULL: videos (F and fcu are not read)
-    return vc_impl("vc_encode_img", h, ltm, V, cu, frames, token_dtype, streams ? F : 0, streams ? fcu : nullptr, frame_src, T, w, hidden_in,
-                   text_len, u, new_video, hidden_out, proj_out, proj_mean, stream_, front);
+    VcCall k;
+    k.name = "vc_encode_img"; k.ltm = ltm; k.V = V; k.cu = cu; k.frames = frames; k.tok_arg = true; k.token_dtype = token_dtype;
+    if (frame_src) { k.F = F; k.fcu = fcu; k.frame_src = frame_src; }   // NULL: videos (F and fcu are not read)
+    k.T = T; k.w = w; k.front = front; k.hidden_in = hidden_in; k.text_len = text_len; k.u = u; k.new_video = new_video;
+    k.hidden_out = hidden_out; k.proj_out = proj_out; k.proj_mean = proj_mean; k.stream = static_cast<hipStream_t>(stream_);
+    return vc_impl(h, k);
 }
 
 int infv_vqf_encode_frames(infv_vqf_handle h, int32_t F, const void* vision, int32_t token_dtype, int32_t n_tokens,
                            const infv_vqf_vc_weights* w, const infv_vqf_vision_ln* ln, const float* query_rows, void* out, int32_t out_dtype,
                            void* stream_) {
-    // ---- what vc_impl does not see; everything else is refused there, before any launch or memory change ----
+    // ---- what vc_validate does not see; everything else is refused there, before any launch or memory change ----
     const char* name = "encode_frames";
     if (!h || !w || !query_rows) return fail(INFV_ERR_INVALID, "%s: null handle, weights or query_rows", name);
     if (F < 0) return fail(INFV_ERR_INVALID, "%s: F = %d is negative", name, F);
@@ -1414,11 +1420,15 @@ int infv_vqf_encode_frames(infv_vqf_handle h, int32_t F, const void* vision, int
     std::vector<int32_t> cu((size_t)F + 1), text_len((size_t)(F > 0 ? F : 1), 0);
     for (int f = 0; f <= F; ++f) cu[f] = f;
     const FrameCall fc{n_tokens, out, static_cast<tok_code>(out_dtype)};
-    const int rc = vc_impl(name, h, nullptr, F, cu.data(), vision, token_dtype, 0, nullptr, nullptr, 1, w, query_rows, text_len.data(), nullptr, 0,
-                           out_dtype == INFV_TOKENS_F32 ? static_cast<float*>(out) : nullptr, nullptr, nullptr, stream_, &front, &fc);
+    VcCall k;
+    k.name = name; k.V = F; k.cu = cu.data(); k.frames = vision; k.tok_arg = true; k.token_dtype = token_dtype; k.T = 1; k.w = w;
+    k.hidden_in = query_rows; k.text_len = text_len.data(); k.hidden_out = out_dtype == INFV_TOKENS_F32 ? static_cast<float*>(out) : nullptr;
+    k.stream = static_cast<hipStream_t>(stream_); k.front = &front; k.fc = &fc;
+    const int rc = vc_impl(h, k);
     h->tap_layer = -1; h->tap_dst = nullptr;                  // a tap serves one call
     return rc;
 }
+
 
 int infv_vqf_set_context_tap(infv_vqf_handle h, int32_t layer, float* dst) {
     if (!h) return fail(INFV_ERR_INVALID, "null handle");
@@ -1445,7 +1455,7 @@ int infv_vqf_layernorm_tokens(const void* frames, int32_t token_dtype, int64_t n
     static DeviceBuf* stats = new DeviceBuf();
     static hipEvent_t last_read = nullptr;
     std::lock_guard<std::mutex> lock(mu);
-    if ((size_t)n_rows * 2 * sizeof(float) > stats->bytes) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(stats->reserve((size_t)n_rows * 2 * sizeof(float))); }
+    HIP_TRY(reserve_all({{*stats, (size_t)n_rows * 2 * sizeof(float)}}));
     if (!last_read) HIP_TRY(hipEventCreateWithFlags(&last_read, hipEventDisableTiming));
     else HIP_TRY(hipStreamWaitEvent(stream, last_read, 0));
     const tok_code tok = static_cast<tok_code>(token_dtype);

@@ -115,26 +115,17 @@ int split_gemm_pick_splitk(int M, int N, int K, int nbatch, int* k_per_split);
 long split_gemm_wide_tile_count(int M, int N);   // tiles of the 384 x 256 kernel per batch entry, 0 if the shape has no whole ones   // fills the chip with the tile shape that will run
 // x [rows][cols] fp32 -> hi = bf16(x), lo = bf16(x - hi)
 hipError_t launch_split_rows(const float* x, long ld_in, long rows, int cols, void* hi, void* lo, long ld_out, hipStream_t stream);
-// F [nb][n][d] fp32 -> Fh/Fl [nb][n][d] and Th/Tl [nb][d][n] (bf16 hi/lo)
-hipError_t launch_split_transpose(const float* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl, hipStream_t stream,
-                                  float* kbar = nullptr, int P = 0);   // kbar: also the frame means [nb][n / P][d]
-// F [nb][n][d] bf16 -> Th [nb][d][n] bf16 (the untransposed operand is F itself) and, with kbar, the frame means [nb][n / P][d]
-hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, hipStream_t stream, float* kbar = nullptr, int P = 0);
 // x [n] bf16 -> y [n] fp32, n % 8 == 0
 hipError_t launch_upcast_bf16(const void* x, float* y, long n, hipStream_t stream);
-// F [nb][n][d] fp16 -> Fh/Fl [nb][n][d] and Th/Tl [nb][d][n] (bf16 hi/lo: the fp32 pass's planes) and, with kbar, the frame means
-hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl, hipStream_t stream,
-                                      float* kbar = nullptr, int P = 0);
 // x [n] fp16 -> y [n] fp32 (exact), n % 8 == 0
 hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream);
-// F [nb][n][d] fp8 e4m3 -> Fh [nb][n][d] and Th [nb][d][n] (bf16: an e4m3 value is its own hi piece, the lo planes do not exist) and, with kbar,
-// the frame means
-hipError_t launch_split_transpose_f8(const void* F, int nb, int n, int d, void* Fh, void* Th, hipStream_t stream, float* kbar = nullptr, int P = 0);
 // x [n] fp8 e4m3 -> y [n] fp32 (exact), n % 16 == 0
 hipError_t launch_upcast_f8(const void* x, float* y, long n, hipStream_t stream);
 // bytes per element of a token type
 inline size_t token_bytes(tok_code tok) { return tok == INFV_TOKENS_F32 ? 4 : tok == INFV_TOKENS_F8E4M3 ? 1 : 2; }
-// the token pass of nb <= 32768 chunks for any token type (bf16: only Th is written; fp8: Fh and Th); kbar needs token_pass_gives_means(P)
+// The token pass of nb <= 32768 chunks F [nb][n][d] of any token type -> the bf16 planes Fh/Fl [nb][n][d] and Th/Tl [nb][d][n] and, with kbar,
+// the frame means [nb][n / P][d] (needs token_pass_gives_means(P)).  fp32 / fp16: all four planes (hi/lo); bf16: Th alone, the untransposed
+// operand is F itself; fp8 e4m3: Fh and Th, a value is its own hi piece
 bool token_pass_gives_means(int P);
 hipError_t launch_token_pass(const void* F, tok_code tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
                              hipStream_t stream, float* kbar, int P);

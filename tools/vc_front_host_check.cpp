@@ -8,7 +8,8 @@
 // only while every refusal exercised here is decided before the handle is written and from its config alone (all zeros: no query
 // tokens, no cross layer); formally that is undefined behaviour on the non-trivial struct.  Every call below must be refused --
 // null handle, reserved != 0, gamma without beta, the embedding layer beside hidden_in, ids below 0 or at vocab, a text longer than
-// the position table, a negative text_len -- and none may touch the handle, the tables (their pointers are never dereferenced) or
+// the position table, a negative text_len, and through the streams form cu[0] != 0, a decreasing cu or fcu, frame_src outside [0, F),
+// a stream whose chunk count differs from its block's, reserved != 0 -- and none may touch the handle, the tables (their pointers are never dereferenced) or
 // the device.
 #include <cstdio>
 #include <cstdlib>
@@ -99,6 +100,21 @@ int main() {
     text_len[0] = 2;
     const int32_t src[2] = {0, 0};
     EXPECT(img(h, &f, nullptr, 0, tab, src) == INFV_ERR_INVALID);                       // frame_src without fcu
+
+    // ---- the table refusals of the streams form (three streams over two blocks of 1 and 2 chunks)
+    const int32_t scu[4] = {0, 1, 3, 4}, sfcu[3] = {0, 1, 3}, ssrc[3] = {0, 1, 0}, stl[3] = {0, 0, 0};
+    auto streams = [&](const int32_t* cu_, const int32_t* fcu_, const int32_t* src_, const infv_vqf_vc_front* fr) {
+        return infv_vqf_vc_encode_img(h, nullptr, 3, cu_, tab, 0, 2, fcu_, src_, 16, &w, fr, tab, stl, nullptr, 1, nullptr, nullptr, nullptr,
+                                      nullptr);
+    };
+    { const int32_t c[4] = {1, 1, 3, 4}; EXPECT(streams(c, sfcu, ssrc, nullptr) == INFV_ERR_INVALID && said("cu[0] = 1")); }
+    { const int32_t c[4] = {0, 3, 1, 4}; EXPECT(streams(c, sfcu, ssrc, nullptr) == INFV_ERR_INVALID && said("cu is not non-decreasing")); }
+    { const int32_t c[3] = {1, 1, 3}; EXPECT(streams(scu, c, ssrc, nullptr) == INFV_ERR_INVALID && said("fcu[0] = 1")); }
+    { const int32_t c[3] = {0, 3, 1}; EXPECT(streams(scu, c, ssrc, nullptr) == INFV_ERR_INVALID && said("fcu is not non-decreasing")); }
+    { const int32_t c[3] = {0, 2, 0}; EXPECT(streams(scu, sfcu, c, nullptr) == INFV_ERR_INVALID && said("frame_src[1] = 2 outside [0, 2)")); }
+    { const int32_t c[3] = {0, -1, 0}; EXPECT(streams(scu, sfcu, c, nullptr) == INFV_ERR_INVALID && said("frame_src[1] = -1 outside")); }
+    { const int32_t c[3] = {0, 0, 1}; EXPECT(streams(scu, sfcu, c, nullptr) == INFV_ERR_INVALID && said("stream 1 has 2 chunks, its block 0 has 1")); }
+    { infv_vqf_vc_front g{}; g.reserved = 1; EXPECT(streams(scu, sfcu, ssrc, &g) == INFV_ERR_INVALID && said("reserved")); }
 
     EXPECT(std::memcmp(a0, a, kDummy) == 0);                                            // no refusal wrote to the handle
     std::free(a); std::free(a0); std::free(ids); std::free(text_len);
