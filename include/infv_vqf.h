@@ -365,6 +365,41 @@ int infv_vqf_encode_frames(infv_vqf_handle h, int32_t F, const void* vision, int
                            const float* query_rows /* device [n_query][hidden]: the embedded query tokens, shared by all frames */,
                            void* out /* [F][n_query][hidden] */, int32_t out_dtype /* 0 fp32, 1 bf16, 3 fp16 */, void* stream);
 
+/* The arithmetic of the QUERY-SIDE linears of infv_vqf_encode_frames (additive: the ABI version stays 6).  mode:
+ *   0 (default)  fp32 MFMA: the path and the bits of a handle that never called this.
+ *   1            split-bf16: the fp32 activation and the fp32 weight are each carried as hi = bf16(x), lo = bf16(x - hi); per k-step
+ *                three bf16 MFMA products in the order lo.hi, hi.lo, hi.hi, fp32 accumulation (the scheme of the short-term
+ *                attention's contractions).  fp32-class: about 1e-5 of a sum of |x w| at K = 3072.
+ *   2            fp16: activation and weight rounded to nearest-even fp16, as `.half()` does (beyond 65504: inf, as under autocast);
+ *                one f16 MFMA product, fp32 accumulation.  Bias, GELU, residual and LayerNorm stay fp32.  What the f16 MFMA does
+ *                with SUBNORMAL fp16 operands (magnitudes below 2^-14) on gfx950 is not measured.
+ * The mode governs the eight linears per layer on the query rows -- the stacked self q/k/v, the self output, the cross query, the
+ * cross output, q_ffn_in and q_ffn_out (with its 2-byte cast epilogue) -- and nothing else: the short-term attention and the token
+ * pass run as before, a linear stays two launches (GEMM + epilogue), the activations are split / rounded between the registers and
+ * LDS (no activation plane in memory), and a frame's bits still do not depend on F or on the other frames.
+ * The weights arrive as fp32; their 2-byte planes ([N][K], a stacked q/k/v as one [3 * hidden][K] set) are made on the device and
+ * cached in the handle, keyed on (weight pointers, shape), while the NON-ZERO weights epoch (infv_vqf_set_weights_epoch) stands;
+ * a change of the epoch or of the mode drops them, infv_vqf_destroy frees them.  With epoch 0 every linear rebuilds its planes into
+ * one scratch pair (correct, and 1 or 2 more launches per weight matrix).  Cost for the model's image Q-former (12 layers, hidden 768,
+ * inter 3072: about 92 M weight elements): about 370 MB in mode 1 (two planes), about 185 MB in mode 2.
+ * While the mode is not 0, EVERY OTHER entry point that takes the handle -- infv_vqf_short_attention, infv_vqf_encode_chunk /
+ * _video / _videos, the infv_vqf_vc_encode_* family, infv_vqf_vc_embed -- returns INFV_ERR_UNSUPPORTED before any launch or workspace
+ * change, naming this function: those calls feed their cross query into the long-term memories' Gibbs draw, and reduced products
+ * never feed the scores of the draw (csrc/split_gemm.hip).  (infv_vqf_self_attention runs no linear and is not refused.)
+ * A null handle or a mode outside 0..2 is INFV_ERR_INVALID and leaves the setting as it was. */
+int infv_vqf_set_linear_precision(infv_vqf_handle h, int32_t mode);
+
+/* One linear of the layer-major calls in its batch-invariant form, under the handle's linear precision (exported for tests and
+ * measurements, as infv_vqf_self_attention and infv_vqf_token_pass are):
+ *   y [M][n_lin * n_out] = LN?( act( x [M][K] . [lin[0].w; ...; lin[n_lin-1].w]^T + bias ) + residual[m % res_rows] )
+ * lin: HOST array of n_lin linears with device pointers, each w [n_out][K] (b may be NULL); act 0 none, 1 GELU; residual NULL or
+ * device [res_rows][n_lin * n_out]; ln NULL or gamma / beta [n_lin * n_out] (eps: the handle's ln_eps).  128 x 128 tiles, no split-K,
+ * whatever M is.  Refused before any launch or memory change: a null h, x, lin, y or lin[i].w; M < 1; n_lin outside 1..4; an
+ * unknown act; res_rows < 1 with a residual; gamma without beta; a pointer that is not 16-byte aligned (INFV_ERR_INVALID); K or
+ * n_out no positive multiple of 64, K or n_lin * n_out above 4096 (INFV_ERR_UNSUPPORTED). */
+int infv_vqf_linear(infv_vqf_handle h, const float* x, int32_t M, int32_t K, const infv_linear* lin, int32_t n_lin, int32_t n_out,
+                    int32_t act, const float* residual, int32_t res_rows, const infv_layernorm* ln, float* y, void* stream);
+
 /* A tap for tests (exported as infv_vqf_self_attention is): the NEXT infv_vqf_encode_frames call on h also copies the cross-attention
  * context of encoder layer `layer` (Qformer.py:303-304: softmax(q k^T / sqrt(dh)) v with the value bias, before the output dense),
  * [F][n_query][hidden] fp32, to dst (device) on the call's stream; the tap is cleared when that call returns.  dst NULL: off.  A layer

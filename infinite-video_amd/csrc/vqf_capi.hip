@@ -2,6 +2,7 @@
 #include "../../include/infv_vqf.h"
 #include "capi_common.h"
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <vector>
 #include "vqf_internal.h"
@@ -10,6 +11,12 @@
 #include <new>
 
 using namespace infv;
+
+// The 2-byte planes of one (stacked) weight of a reduced-precision linear: [n_lin * n_out][K] bf16 hi and lo (mode 1) or fp16 (mode 2, hi alone)
+struct LinPlanes {
+    const float* w[infv::kQfMaxSeg] = {}; int n_lin = 0, n_out = 0, K = 0;
+    infv::DeviceBuf hi, lo;
+};
 
 struct infv_vqf_s {
     infv_vqf_config cfg;
@@ -42,6 +49,12 @@ struct infv_vqf_s {
     bool ids_in_flight = false;
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
+    // infv_vqf_set_linear_precision: the arithmetic of the query-side linears of infv_vqf_encode_frames, and the weight planes of the
+    // reduced modes -- kept while the non-zero weights epoch lp_epoch stands (epoch 0: one scratch pair, rewritten by every linear)
+    int lin_mode = 0;
+    std::vector<std::unique_ptr<LinPlanes>> lp;
+    unsigned long long lp_epoch = 0;
+    LinPlanes lp_scratch;
     ~infv_vqf_s() {
         if (side) (void)hipStreamSynchronize(side);           // (a stream of the process-wide set: not destroyed here)
         if (ev_main) (void)hipEventDestroy(ev_main);
@@ -72,6 +85,14 @@ int check_layer_cfg(const infv_vqf_config& c) {       // what the fused per-laye
     return INFV_OK;
 }
 
+// Every entry point but infv_vqf_encode_frames (and infv_vqf_linear) while a reduced linear precision is set: their query rows feed
+// the memories' Gibbs draw, and reduced products never feed the scores of the draw (split_gemm.hip)
+int refuse_reduced(const infv_vqf_s* h, const char* name) {
+    if (h->lin_mode == 0) return INFV_OK;
+    return fail(INFV_ERR_UNSUPPORTED, "%s: the handle's linear precision is %d, which only infv_vqf_encode_frames runs "
+                                      "(infv_vqf_set_linear_precision(h, 0) selects fp32 again)", name, h->lin_mode);
+}
+
 // y = epilogue( x [M][K] . W^T ) with up to 3 stacked weight matrices of n_out rows each
 struct LinearCall {
     const float* x; int M, K;
@@ -81,23 +102,82 @@ struct LinearCall {
     const infv_layernorm* ln = nullptr;
     float* y;
     bool inv = false;      // batch invariant (infv_vqf_encode_videos): 128 x 128 tiles, no split-K, whatever M is
+    bool reduced = false;  // a query-side linear of infv_vqf_encode_frames (or infv_vqf_linear): the handle's linear precision applies
     void* y16 = nullptr; tok_code y16_dtype = INFV_TOKENS_F32;   // y16 != nullptr: the rows go out as bf16 / fp16 instead of y (infv_vqf_encode_frames)
 };
 
+// Drops the cached weight planes (work in flight may still read them: the device is synchronised first)
+int drop_linear_planes(infv_vqf_s* h) {
+    if (h->lp.empty()) return INFV_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    h->lp.clear();
+    return INFV_OK;
+}
+
+// The planes of c's (stacked) weight in the handle's reduced mode: one contiguous [n_lin * n_out][K] set, so the GEMM sees one B and
+// a tile may straddle the segments.  Keyed on (weight pointers, shape); the mode and the epoch are the whole cache's.
+int linear_planes(infv_vqf_s* h, const LinearCall& c, const LinPlanes** out, hipStream_t stream) {
+    const int mode = h->lin_mode;
+    LinPlanes* p = nullptr;
+    if (h->epoch == 0) {
+        p = &h->lp_scratch;
+    } else {
+        if (h->lp_epoch != h->epoch) {
+            if (int rc = drop_linear_planes(h)) return rc;
+            h->lp_epoch = h->epoch;
+        }
+        for (const auto& e : h->lp) {
+            bool same = e->n_lin == c.n_lin && e->n_out == c.n_out && e->K == c.K;
+            for (int i = 0; same && i < c.n_lin; ++i) same = e->w[i] == c.lin[i]->w;
+            if (same) { *out = e.get(); return INFV_OK; }
+        }
+        std::unique_ptr<LinPlanes> fresh(new (std::nothrow) LinPlanes());
+        if (!fresh) return fail(INFV_ERR_INVALID, "out of host memory");
+        p = fresh.get();
+        h->lp.push_back(std::move(fresh));
+    }
+    const size_t bytes = (size_t)c.n_lin * c.n_out * c.K * 2;
+    hipError_t e = reserve_all({{p->hi, bytes}, {p->lo, mode == 1 ? bytes : 0}});
+    for (int i = 0; e == hipSuccess && i < c.n_lin; ++i) {
+        const size_t o = (size_t)i * c.n_out * c.K * 2;
+        if (mode == 1) e = launch_split_rows(c.lin[i]->w, c.K, c.n_out, c.K, p->hi.as<char>() + o, p->lo.as<char>() + o, c.K, stream);
+        else e = launch_round_rows_f16(c.lin[i]->w, c.K, c.n_out, c.K, p->hi.as<char>() + o, c.K, stream);
+    }
+    if (e != hipSuccess) {
+        if (p != &h->lp_scratch) h->lp.pop_back();             // (nothing in flight reads planes that were never handed out)
+        return fail(INFV_ERR_HIP, "weight planes of a reduced-precision linear: %s", hipGetErrorString(e));
+    }
+    for (int i = 0; i < c.n_lin; ++i) p->w[i] = c.lin[i]->w;
+    p->n_lin = c.n_lin; p->n_out = c.n_out; p->K = c.K;
+    *out = p;
+    return INFV_OK;
+}
+
 int run_linear(infv_vqf_s* h, const LinearCall& c, hipStream_t stream) {
     const int width = c.n_lin * c.n_out;
-    const int sk = c.inv ? 1 : qf_pick_splitk(c.M, width, c.K, 1);
+    const int mode = c.reduced ? h->lin_mode : 0;
+    const int sk = c.inv || mode ? 1 : qf_pick_splitk(c.M, width, c.K, 1);
     const size_t need = (size_t)sk * c.M * width * sizeof(float);
     HIP_TRY(reserve_all({{h->part, need}}));
+    const long split_stride = (long)c.M * width;
+    if (mode) {                                                // split-bf16 / fp16: one launch, as the fp32 GEMM is
+        const LinPlanes* p = nullptr;
+        if (int rc = linear_planes(h, c, &p, stream)) return rc;
+        LinearGemm g{};
+        g.A = c.x; g.lda = c.K; g.B_hi = p->hi.p; g.B_lo = p->lo.p; g.ldb = c.K;
+        g.C = h->part.as<float>(); g.ldc = width; g.M = c.M; g.N = width; g.K = c.K;
+        HIP_TRY(launch_linear_gemm(g, mode, stream));
+    } else {
     QfGemm g{};
     g.A = c.x; g.lda = c.K; g.strideA = 0;
     for (int i = 0; i < c.n_lin; ++i) g.B[i] = c.lin[i]->w;
     g.ldb = c.K; g.strideB = 0; g.seg_rows = c.n_out;
-    g.C = h->part.as<float>(); g.ldc = width; g.strideC = 0; g.split_stride = (long)c.M * width;
+    g.C = h->part.as<float>(); g.ldc = width; g.strideC = 0; g.split_stride = split_stride;
     g.M = c.M; g.N = width; g.k_per_split = c.K / sk; g.splitk = sk; g.nbatch = 1; g.tile = c.inv ? 128 : 0;
     HIP_TRY(launch_qf_gemm(g, false, stream));
+    }
     QfEpilogue e{};
-    e.parts = h->part.as<float>(); e.nsplit = sk; e.split_stride = g.split_stride; e.ld_in = width;
+    e.parts = h->part.as<float>(); e.nsplit = sk; e.split_stride = split_stride; e.ld_in = width;
     for (int i = 0; i < c.n_lin; ++i) e.bias[i] = c.lin[i]->b;
     e.seg_cols = c.n_out; e.act = c.act; e.scale = 1.f; e.res_scale = 1.f;
     e.residual = c.residual; e.ld_res = width; e.res_rows = c.res_rows;
@@ -473,11 +553,45 @@ int infv_vqf_set_weights_epoch(infv_vqf_handle h, uint64_t epoch) {
     return INFV_OK;
 }
 
+int infv_vqf_set_linear_precision(infv_vqf_handle h, int32_t mode) {
+    if (!h) return fail(INFV_ERR_INVALID, "null handle");
+    if (mode < 0 || mode > 2) return fail(INFV_ERR_INVALID, "set_linear_precision: unknown mode %d (0 fp32, 1 split-bf16, 2 fp16)", mode);
+    if (mode != h->lin_mode)
+        if (int rc = drop_linear_planes(h)) return rc;        // the planes are the old mode's
+    h->lin_mode = mode;
+    return INFV_OK;
+}
+
+int infv_vqf_linear(infv_vqf_handle h, const float* x, int32_t M, int32_t K, const infv_linear* lin, int32_t n_lin, int32_t n_out,
+                    int32_t act, const float* residual, int32_t res_rows, const infv_layernorm* ln, float* y, void* stream) {
+    // ---- every refusal before any launch or memory change ----
+    if (!h || !x || !lin || !y) return fail(INFV_ERR_INVALID, "linear: null handle, x, lin or y");
+    if (n_lin < 1 || n_lin > kQfMaxSeg) return fail(INFV_ERR_INVALID, "linear: n_lin = %d outside 1..%d", n_lin, kQfMaxSeg);
+    if (M < 1) return fail(INFV_ERR_INVALID, "linear: M = %d, must be >= 1", M);
+    if (K < 64 || K % 64 || n_out < 64 || n_out % 64) return fail(INFV_ERR_UNSUPPORTED, "linear: K and n_out must be positive multiples of 64");
+    if (K > 4096 || (long)n_lin * n_out > 4096) return fail(INFV_ERR_UNSUPPORTED, "linear: row widths above 4096 are not supported");
+    if ((long)M * n_lin * n_out > 0x7fffffffL) return fail(INFV_ERR_UNSUPPORTED, "linear: %d rows of %d in one call", M, n_lin * n_out);
+    if (act != QF_ACT_NONE && act != QF_ACT_GELU) return fail(INFV_ERR_INVALID, "linear: unknown activation %d", act);
+    if (residual && res_rows < 1) return fail(INFV_ERR_INVALID, "linear: res_rows = %d, must be >= 1", res_rows);
+    if (ln && (!ln->gamma || !ln->beta)) return fail(INFV_ERR_INVALID, "linear: LayerNorm without gamma or beta");
+    bool aligned = aligned16(x) && aligned16(y) && aligned16(residual) && (!ln || (aligned16(ln->gamma) && aligned16(ln->beta)));
+    for (int i = 0; i < n_lin; ++i) {
+        if (!lin[i].w) return fail(INFV_ERR_INVALID, "linear: lin[%d].w is null", i);
+        aligned = aligned && aligned16(lin[i].w) && aligned16(lin[i].b);
+    }
+    if (!aligned) return fail(INFV_ERR_INVALID, "linear: every pointer must be 16-byte aligned");
+    LinearCall c{x, M, K, {}, n_lin, n_out};
+    for (int i = 0; i < n_lin; ++i) c.lin[i] = &lin[i];
+    c.act = act; c.residual = residual; c.res_rows = residual ? res_rows : 1; c.ln = ln; c.y = y; c.inv = true; c.reduced = true;
+    return run_linear(h, c, static_cast<hipStream_t>(stream));
+}
+
 int infv_vqf_short_attention(infv_vqf_handle h, const void* frames, int32_t n_tokens, const float* xq,
                              const infv_linear* key, const infv_linear* value, const float* a_long,
                              float* merged, void* stream) {
     if (!h || !frames || !xq || !key || !value || !merged || !key->w || !value->w || !value->b)
         return fail(INFV_ERR_INVALID, "null argument");
+    if (int rc = refuse_reduced(h, "short_attention")) return rc;
     tok_code tok = h->tok;
     if (tok != INFV_TOKENS_F32 && !aligned16(frames)) return fail(INFV_ERR_INVALID, "fp16 / bf16 / fp8 frames must be 16-byte aligned");
     if (n_tokens < 32 || n_tokens % 32) return fail(INFV_ERR_INVALID, "n_tokens must be a positive multiple of 32");
@@ -489,6 +603,7 @@ int infv_vqf_encode_chunk(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
                           const infv_vqf_weights* w, const double* u, int32_t new_video,
                           float* hidden_out, float* llama_out, void* stream_) {
     if (!h || !frames || !w) return fail(INFV_ERR_INVALID, "null argument");
+    if (int rc = refuse_reduced(h, "encode_chunk")) return rc;
     const infv_vqf_config& c = h->cfg;
     if (int rc = check_layer_cfg(c)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -844,6 +959,7 @@ int infv_vqf_encode_video(infv_vqf_handle h, const infv_ltm_handle* ltm, const v
                           int32_t T, const infv_vqf_weights* w, const double* u, int32_t new_video,
                           float* hidden_out, float* llama_out, float* llama_mean, void* stream_) {
     if (!h || !frames || !w || n_chunks < 1) return fail(INFV_ERR_INVALID, "bad argument");
+    if (int rc = refuse_reduced(h, "encode_video")) return rc;
     return encode_impl(h, ltm, frames, n_chunks, T, w, u, new_video, hidden_out, llama_out, llama_mean, stream_, 1, nullptr, false);
 }
 
@@ -854,6 +970,7 @@ int infv_vqf_encode_videos(infv_vqf_handle h, const infv_ltm_handle* ltm, int32_
     if (!h || !cu || !w || V < 0) return fail(INFV_ERR_INVALID, "encode_videos: bad arguments");
     if (V == 0) return INFV_OK;
     if (int rc = check_offsets("encode_videos", "cu", cu, V)) return rc;
+    if (int rc = refuse_reduced(h, "encode_videos")) return rc;      // (the first read of the handle)
     const bool use_ltm = h->cfg.alpha != 1.0f;
     const int n_h = use_ltm ? V * h->cfg.n_layers : 0;
     if (use_ltm) {
@@ -976,6 +1093,8 @@ static int vc_validate(const infv_vqf_s* h, VcCall& k) {
     if (w->n_layers < 1 || !w->layers) return fail(INFV_ERR_INVALID, "%s: no layers", name);
     if (w->n_layers > INFV_VQF_VC_MAX_LAYERS)
         return fail(INFV_ERR_UNSUPPORTED, "%s: %d layers, at most %d are supported", name, w->n_layers, INFV_VQF_VC_MAX_LAYERS);
+    if (!fc)                                                   // (the first read of the handle: what the arguments alone decide comes first)
+        if (int rc = refuse_reduced(h, name)) return rc;
     const int Q = c.n_query, Ln = w->n_layers;
     for (int v = 0; v < V; ++v) {
         if (text_len[v] < 0) return fail(INFV_ERR_INVALID, "%s: text_len[%d] = %d is negative", name, v, text_len[v]);
@@ -1201,7 +1320,7 @@ static int vc_self_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l) {
         const int nb = b.nb;
         const long r0 = b.r0, t0 = t.toff[b.c0], tn = t.toff[b.c0 + nb] - t0;
         LinearCall qkv{vA + r0, nb * Q, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
-        qkv.inv = true; qkv.y = h->vqkv.as<float>();
+        qkv.inv = true; qkv.reduced = k.fc != nullptr; qkv.y = h->vqkv.as<float>();
         if (int rc = run_linear(h, qkv, k.stream)) return rc;
         if (tn > 0) {
             LinearCall qkt{tA + t0 * Hd, (int)tn, Hd, {&L.self_q, &L.self_k, &L.self_v}, 3, Hd};
@@ -1214,7 +1333,7 @@ static int vc_self_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l) {
         a.ctx0 = h->vsa.as<float>(); a.ctx1 = h->tsa.as<float>(); a.H = c.n_heads; a.n_alloc = 0;
         HIP_TRY(launch_qf_vc_self_attention(a, nb, t.n_valid.data() + b.c0, t.off1.data(), k.stream));
         LinearCall so{h->vsa.as<float>(), nb * Q, Hd, {&L.self_o}, 1, Hd};
-        so.inv = true; so.residual = vA + r0; so.res_rows = nb * Q; so.ln = &L.self_ln; so.y = v1 + r0;
+        so.inv = true; so.reduced = k.fc != nullptr; so.residual = vA + r0; so.res_rows = nb * Q; so.ln = &L.self_ln; so.y = v1 + r0;
         if (int rc = run_linear(h, so, k.stream)) return rc;
         if (tn > 0 && text_out) {
             LinearCall st{h->tsa.as<float>(), (int)tn, Hd, {&L.self_o}, 1, Hd};
@@ -1223,7 +1342,7 @@ static int vc_self_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l) {
         }
         if (L.has_cross) {
             LinearCall xq{v1 + r0, nb * Q, Hd, {&L.x_q}, 1, Hd};
-            xq.inv = true; xq.y = h->vxq.as<float>() + r0;
+            xq.inv = true; xq.reduced = k.fc != nullptr; xq.y = h->vxq.as<float>() + r0;
             if (int rc = run_linear(h, xq, k.stream)) return rc;
         }
     }
@@ -1263,7 +1382,7 @@ static int vc_cross_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l, in
         HIP_TRY(hipMemcpyAsync(h->tap_dst, vmerged, (size_t)k.M * Hd * sizeof(float), hipMemcpyDeviceToDevice, k.stream));
     for (RowBlock b : RowBlocks{k.C, k.RB, (long)Q * Hd}) {
         LinearCall xo{vmerged + b.r0, b.nb * Q, Hd, {&L.x_o}, 1, Hd};
-        xo.inv = true; xo.residual = h->v1.as<float>() + b.r0; xo.res_rows = b.nb * Q; xo.ln = &L.x_ln; xo.y = h->v2.as<float>() + b.r0;
+        xo.inv = true; xo.reduced = k.fc != nullptr; xo.residual = h->v1.as<float>() + b.r0; xo.res_rows = b.nb * Q; xo.ln = &L.x_ln; xo.y = h->v2.as<float>() + b.r0;
         if (int rc = run_linear(h, xo, k.stream)) return rc;
     }
     return INFV_OK;
@@ -1278,10 +1397,10 @@ static int vc_ffn_block(infv_vqf_s* h, const VcCall& k, int l) {
     const float* qin = L.has_cross ? h->v2.as<float>() : h->v1.as<float>();   // the query rows entering the query FFN
     for (RowBlock b : RowBlocks{k.C, k.RB, (long)Q * Hd}) {
         LinearCall fi{qin + b.r0, b.nb * Q, Hd, {&L.q_ffn_in}, 1, c.inter};
-        fi.inv = true; fi.act = QF_ACT_GELU; fi.y = h->vinter.as<float>();
+        fi.inv = true; fi.reduced = k.fc != nullptr; fi.act = QF_ACT_GELU; fi.y = h->vinter.as<float>();
         if (int rc = run_linear(h, fi, k.stream)) return rc;
         LinearCall fo{h->vinter.as<float>(), b.nb * Q, c.inter, {&L.q_ffn_out}, 1, Hd};
-        fo.inv = true; fo.residual = qin + b.r0; fo.res_rows = b.nb * Q; fo.ln = &L.q_ffn_ln; fo.y = h->vA.as<float>() + b.r0;
+        fo.inv = true; fo.reduced = k.fc != nullptr; fo.residual = qin + b.r0; fo.res_rows = b.nb * Q; fo.ln = &L.q_ffn_ln; fo.y = h->vA.as<float>() + b.r0;
         if (k.fc && last && k.fc->out_dtype != INFV_TOKENS_F32) {   // the frame tokens leave in the type their consumer reads: no fp32 row is written
             fo.y16 = static_cast<char*>(k.fc->out) + 2 * b.r0; fo.y16_dtype = k.fc->out_dtype;
         }
@@ -1468,6 +1587,7 @@ int infv_vqf_layernorm_tokens(const void* frames, int32_t token_dtype, int64_t n
 int infv_vqf_vc_embed(infv_vqf_handle h, const infv_vqf_vc_front* front, int32_t V, const int32_t* text_len, float* out_rows, void* stream_) {
     // ---- every refusal before any launch or memory change ----
     if (!h || !front || !text_len || V < 0) return fail(INFV_ERR_INVALID, "vc_embed: bad arguments");
+    if (int rc = refuse_reduced(h, "vc_embed")) return rc;
     if (front->reserved != 0) return fail(INFV_ERR_INVALID, "vc_embed: front->reserved must be 0");
     if (!front->emb.word) return fail(INFV_ERR_INVALID, "vc_embed: no embedding tables (emb.word is NULL)");
     if (int rc = check_front_emb("vc_embed", front, V, text_len)) return rc;

@@ -115,6 +115,19 @@ int split_gemm_pick_splitk(int M, int N, int K, int nbatch, int* k_per_split);
 long split_gemm_wide_tile_count(int M, int N);   // tiles of the 384 x 256 kernel per batch entry, 0 if the shape has no whole ones   // fills the chip with the tile shape that will run
 // x [rows][cols] fp32 -> hi = bf16(x), lo = bf16(x - hi)
 hipError_t launch_split_rows(const float* x, long ld_in, long rows, int cols, void* hi, void* lo, long ld_out, hipStream_t stream);
+// ---- the query-side linears of infv_vqf_encode_frames in reduced arithmetic (linear_gemm.hip; infv_vqf_set_linear_precision) ----
+// C [M][N] fp32 = A [M][K] fp32 (prepared on the way into LDS) . B [N][K]^T from 2-byte planes.  mode 1: bf16 hi / lo planes, three
+// products per k-step (lo.hi, hi.lo, hi.hi); mode 2: one fp16 plane (B_lo unused), one product.  K % 64 == 0, lda % 4 == 0,
+// ldb % 8 == 0, 16-byte aligned operands.  128 x 128 x 64 tiles and one k order whatever M is, no split-K.
+struct LinearGemm {
+    const float* A; long lda;
+    const void* B_hi; const void* B_lo; long ldb;
+    float* C; long ldc;
+    int M, N, K;
+};
+hipError_t launch_linear_gemm(const LinearGemm& g, int mode, hipStream_t stream);
+// x [rows][cols] fp32 -> out [rows][cols] fp16, round to nearest even (beyond 65504: inf)
+hipError_t launch_round_rows_f16(const float* x, long ld_in, long rows, int cols, void* out, long ld_out, hipStream_t stream);
 // x [n] bf16 -> y [n] fp32, n % 8 == 0
 hipError_t launch_upcast_bf16(const void* x, float* y, long n, hipStream_t stream);
 // x [n] fp16 -> y [n] fp32 (exact), n % 8 == 0

@@ -28,6 +28,13 @@ from .video_qformer import ShortMemoryBuffer, _dev_f32
 from .videochat2_qformer import _Cfg, _Intermediate, _Output, _SelfOutput
 
 OUT_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 3}       # out_dtype codes of infv_vqf_encode_frames
+LINEAR_PRECISIONS = {"fp32": 0, "split_bf16": 1, "fp16": 2}                # mode codes of infv_vqf_set_linear_precision
+
+
+def _linear_precision_code(name) -> int:
+    if not isinstance(name, str) or name not in LINEAR_PRECISIONS:
+        raise ValueError(f"linear_precision must be one of {sorted(LINEAR_PRECISIONS)}, got {name!r}")
+    return LINEAR_PRECISIONS[name]
 
 
 class _SelfAttention(nn.Module):                       # Qformer.py:115-175 without the LongTermAttention (never called here)
@@ -107,8 +114,10 @@ class FrameQformerEncoder(nn.Module):
 
     def __init__(self, num_query_token: int = 32, vision_width: int = 1408, num_hidden_layers: int = 12,
                  cross_attention_freq: int = 2, vision_layernorm: bool = True, ln_eps: float = 1e-5, hidden_size: int = 768,
-                 intermediate_size: int = 3072, num_attention_heads: int = 12):
+                 intermediate_size: int = 3072, num_attention_heads: int = 12, linear_precision: str = "fp32"):
         super().__init__()
+        _linear_precision_code(linear_precision)
+        self.linear_precision = linear_precision
         cfg = _Cfg(encoder_width=vision_width, num_hidden_layers=num_hidden_layers, cross_attention_freq=cross_attention_freq,
                    query_length=num_query_token, hidden_size=hidden_size, intermediate_size=intermediate_size,
                    num_attention_heads=num_attention_heads, alpha=1.0)
@@ -119,6 +128,8 @@ class FrameQformerEncoder(nn.Module):
         if vision_layernorm:                              # blip2.py:83 (nn.LayerNorm's default eps)
             self.ln_vision = nn.LayerNorm(vision_width, eps=ln_eps)
         self._vqf = None                                  # (handle, device)
+        self._vqf_state = None                            # (linear precision, weights epoch) the handle was last given
+        self._plane_gen = 0                               # bumped by set_linear_precision: part of the weights epoch
         self._w_cache = None
         self._q_cache = None
 
@@ -142,6 +153,16 @@ class FrameQformerEncoder(nn.Module):
         if strict and (res.missing_keys or res.unexpected_keys):
             raise KeyError(f"state dict mismatch: missing {res.missing_keys}, unexpected {res.unexpected_keys}")
         return res
+
+    def set_linear_precision(self, name: str) -> None:
+        """The arithmetic of the query-side linears (``infv_vqf_set_linear_precision``): ``"fp32"`` (default), ``"split_bf16"``
+        (three bf16 MFMA products on hi / lo pieces, fp32-class) or ``"fp16"`` (operands rounded to fp16, fp32 accumulation: what the
+        reference's fp16 autocast computes).  Applied to this encoder's own handle at the next call; the weight planes of the reduced
+        modes are cached in the handle until a parameter moves or changes in place.  A write through ``p.data`` does not bump
+        ``p._version`` and is therefore not seen: after one, call this method again (every call starts a new set of planes)."""
+        _linear_precision_code(name)
+        self.linear_precision = name
+        self._plane_gen = getattr(self, "_plane_gen", 0) + 1
 
     def _weights(self, device):
         """ctypes view of the parameters (``infv_vqf_vc_weights``; the text FFN members stay NULL, they are never read), rebuilt only
@@ -207,7 +228,21 @@ class FrameQformerEncoder(nn.Module):
         with torch.cuda.device(device):
             _lib.check(_lib.load().infv_vqf_create(C.byref(c), C.byref(h)))
         self._vqf = (h, device)
+        self._vqf_state = None
         return h
+
+    def _apply_linear_precision(self, h, device) -> None:
+        """The mode, and the weights epoch the handle's plane cache lives by: the signature ``_weights`` computes (storage address,
+        in-place version and dtype of every parameter), so an in-place update or ``load_state_dict`` invalidates the planes."""
+        mode = LINEAR_PRECISIONS[self.linear_precision]
+        epoch = (hash((self._w_cache[0], getattr(self, "_plane_gen", 0))) & 0x7FFFFFFFFFFFFFFF) | 1 if mode else 0
+        if self._vqf_state == (mode, epoch):
+            return
+        lib = _lib.load()
+        with torch.cuda.device(device):
+            _lib.check(lib.infv_vqf_set_linear_precision(h, mode))
+            _lib.check(lib.infv_vqf_set_weights_epoch(h, C.c_uint64(epoch)))
+        self._vqf_state = (mode, epoch)
 
     def _release(self):
         vqf, self._vqf = getattr(self, "_vqf", None), None
@@ -260,9 +295,11 @@ class FrameQformerEncoder(nn.Module):
             return out
         (w, vis), keep = self._weights(device)
         rows = self.query_rows(device)
+        h = self._handle(device)
+        self._apply_linear_precision(h, device)
         with torch.cuda.device(device):
             _lib.check(_lib.load().infv_vqf_encode_frames(
-                self._handle(device), n_f, C.c_void_p(x.data_ptr()), code, int(x.size(1)), C.byref(w),
+                h, n_f, C.c_void_p(x.data_ptr()), code, int(x.size(1)), C.byref(w),
                 C.byref(vis) if with_ln else None, C.c_void_p(rows.data_ptr()), C.c_void_p(out.data_ptr()), OUT_DTYPES[out_dtype],
                 C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
         del keep

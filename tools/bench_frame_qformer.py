@@ -15,6 +15,12 @@ Two legs, each in fresh child processes, one GPU process at a time, alternated r
 One JSON line, appended to profiles/frame_qformer.jsonl: per leg the median of the round medians (ms per call), the round medians,
 the drop of ``torch.cuda.mem_get_info``'s free bytes over the first call, the library's launches per call (``infv_ltm_launch_count``),
 and the largest difference between the two legs' frame tokens.
+
+``--linear-precision fp32,split_bf16,fp16`` runs one "hip" leg per arithmetic of the query-side linears
+(``FrameQformerEncoder.set_linear_precision``) beside the torch leg, and adds each leg's ratio to torch and to the fp32 leg; the drop
+of free device memory over a leg's first call then includes its weight planes.  ``--parent-root DIR`` adds a leg that runs the fp32
+path of another build of the library (a checkout with its own ``libinfv_ltm.so``), alternated with the others: the parent-against-
+branch comparison.  Either option needs ``--out``: the default file keeps the two-leg lines.
 """
 from __future__ import annotations
 
@@ -65,6 +71,8 @@ def child(a):
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     m = FrameQformerEncoder().to(dev).eval()
+    if a.precision != "fp32":                                          # (a parent build has no such method and is never asked)
+        m.set_linear_precision(a.precision)
     for p in m.parameters():
         p.requires_grad = False
     x = torch.randn(a.frames, TOKENS, WIDTH, device=dev, generator=torch.Generator(device=dev).manual_seed(1)).half()
@@ -125,6 +133,9 @@ def run_child(args, timeout):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", choices=("torch", "hip"))
+    ap.add_argument("--precision", default="fp32", help="(child) linear precision of the hip leg")
+    ap.add_argument("--linear-precision", default="", help="comma-separated: one hip leg per name (fp32, split_bf16, fp16)")
+    ap.add_argument("--parent-root", default="", help="a checkout of another build: one more fp32 hip leg from there")
     ap.add_argument("--root", default=ROOT)
     ap.add_argument("--frames", type=int, default=FRAMES)
     ap.add_argument("--calls", type=int, default=5)
@@ -134,6 +145,8 @@ def main():
     a = ap.parse_args()
     if a.child:
         return child(a)
+    if a.linear_precision or a.parent_root:
+        return main_legs(a)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     meds, last = {"torch": [], "hip": []}, {}
     for _ in range(a.rounds):
@@ -148,6 +161,40 @@ def main():
                      "free_drop_bytes": last[leg]["free_drop_bytes"], "launches": last[leg]["launches"]}
     line["hip"]["max_abs_diff_to_torch_leg"] = last["hip"]["max_abs_diff_to_torch_leg"]
     line["torch_over_hip"] = round(line["torch"]["ms"] / line["hip"]["ms"], 3)
+    print(json.dumps(line), flush=True)
+    with open(a.out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+
+
+def main_legs(a):
+    """torch, one hip leg per linear precision, and the parent build's fp32 leg, alternated child by child."""
+    if os.path.abspath(a.out) == os.path.join(ROOT, "profiles", "frame_qformer.jsonl"):
+        raise SystemExit("--linear-precision / --parent-root need --out (profiles/frame_qformer.jsonl keeps the two-leg lines)")
+    names = [n for n in a.linear_precision.split(",") if n] or ["fp32"]
+    legs = {"torch": ["--child", "torch"]}
+    for n in names:
+        legs["hip_" + n] = ["--child", "hip", "--precision", n]
+    if a.parent_root:
+        legs["parent_fp32"] = ["--root", os.path.abspath(a.parent_root), "--child", "hip"]
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    meds, last = {k: [] for k in legs}, {}
+    for _ in range(a.rounds):
+        for leg, args in legs.items():
+            res = run_child(args + ["--frames", str(a.frames), "--calls", str(a.calls)], a.child_timeout)
+            meds[leg].append(statistics.median(res["ms"]))
+            last[leg] = res
+    line = {"measure": "encode_short_memory_frame", "frames": a.frames, "tokens": TOKENS, "width": WIDTH, "vision_dtype": "fp16",
+            "layers": 12, "queries": 32, "hidden": 768, "buffer_dtype": "fp16", "rounds": a.rounds, "calls_per_round": a.calls}
+    for leg in legs:
+        line[leg] = {"ms": round(statistics.median(meds[leg]), 3), "round_medians_ms": [round(v, 3) for v in meds[leg]],
+                     "free_drop_bytes": last[leg]["free_drop_bytes"], "launches": last[leg]["launches"]}
+        if "max_abs_diff_to_torch_leg" in last[leg]:
+            line[leg]["max_abs_diff_to_torch_leg"] = last[leg]["max_abs_diff_to_torch_leg"]
+    for leg in legs:
+        if leg != "torch":
+            line[leg]["over_torch"] = round(line[leg]["ms"] / line["torch"]["ms"], 3)
+            if "hip_fp32" in line and leg != "hip_fp32":
+                line[leg]["over_hip_fp32"] = round(line[leg]["ms"] / line["hip_fp32"]["ms"], 3)
     print(json.dumps(line), flush=True)
     with open(a.out, "a") as f:
         f.write(json.dumps(line) + "\n")
