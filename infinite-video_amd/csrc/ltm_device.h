@@ -1,5 +1,7 @@
 // Device-side building blocks shared by the per-stage kernels (ltm_kernels.hip) and the fused
 // whole-video chain kernel (ltm_chain.hip).  All assume 256-thread workgroups (4 waves of 64).
+// Also the token types (how a kernel loads and widens frame tokens of each dtype) and, beside them because it names them, the
+// host-side dispatch from a tok_code to one of them (with_token_type), for every file that launches a kernel over a token type.
 #pragma once
 #include "ltm_internal.h"
 #include "philox.h"
@@ -84,6 +86,37 @@ struct TokF8 {
         return __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 2 /* nt */);
     }
 };
+
+// tok -> the token type: `f` is a generic callable taking a value of TokF32 / TokBF16 / TokF16 / TokF8
+template <class F>
+inline hipError_t with_token_type(tok_code tok, F f) {
+    switch (tok) {
+        case INFV_TOKENS_F32: return f(TokF32{});
+        case INFV_TOKENS_BF16: return f(TokBF16{});
+        case INFV_TOKENS_F16: return f(TokF16{});
+        case INFV_TOKENS_F8E4M3: return f(TokF8{});
+    }
+    return hipErrorInvalidValue;
+}
+// (no LayerNorm form of fp8 tokens exists: the launchers that apply token_ln() refuse them)
+template <class Tok> inline constexpr bool kTokHasLn = true;
+template <> inline constexpr bool kTokHasLn<TokF8> = false;
+
+// ---- split bf16: an fp32 value x carried as hi = bf16(x), lo = bf16(x - hi) (split_gemm.hip) ----
+__device__ inline void split2(float x, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)x;
+    lo = (__bf16)(x - (float)hi);
+}
+// a * b split the same way, the residual taken from the exact product (one fma).  That is what the compiler's contraction makes
+// of split2(a * b, ...) wherever the product meets the subtraction directly; spelled out, every row softmax of token_pass.hip rounds
+// P_lo the same way whatever stands between the two (the column test of the padded kernels did, in the long one alone).
+__device__ inline void split2_mul(float a, float b, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)(a * b);
+    lo = (__bf16)fmaf(b, a, -(float)hi);
+}
+__device__ inline unsigned pack2(__bf16 a, __bf16 b) {
+    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
+}
 
 // ---- vision LayerNorm of frame tokens (nn.LayerNorm(width, eps) in front of the Q-former, videochat2_it_mistral.py:195) ----
 // y = fma((x - mu) * r, gamma[c], beta[c]) of one token value: (mu, r) = the token row's mean and 1 / sqrt(var + eps), as

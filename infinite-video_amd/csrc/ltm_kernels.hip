@@ -27,18 +27,8 @@ namespace infv {
 //    1 KiB contiguous; P loads per lane are independent, so the whole 32 KiB of a unit is in
 //    flight at once.  This is the only HBM-heavy stage of the path (25.2 MB per chunk).
 // ======================================================================================
-// (the token types TokF32 / TokBF16 / TokF16 / TokF8 -- how a kernel loads and widens frame tokens -- live in ltm_device.h)
-// tok -> the token type: `f` is a generic callable taking a value of TokF32 / TokBF16 / TokF16 / TokF8
-template <class F>
-static hipError_t with_token_type(tok_code tok, F f) {
-    switch (tok) {
-        case INFV_TOKENS_F32: return f(TokF32{});
-        case INFV_TOKENS_BF16: return f(TokBF16{});
-        case INFV_TOKENS_F16: return f(TokF16{});
-        case INFV_TOKENS_F8E4M3: return f(TokF8{});
-    }
-    return hipErrorInvalidValue;
-}
+// (the token types TokF32 / TokBF16 / TokF16 / TokF8 -- how a kernel loads and widens frame tokens -- and with_token_type, the
+//  dispatch from a tok_code to one of them, live in ltm_device.h)
 
 // (the kernels' bodies are __device__ templates: the fp32 / bf16 kernels are instantiations over the token type, the fp16 and fp8
 //  ones are kernels of their own name over the same body -- the shipped library's kernel census counts the former by name)
@@ -174,6 +164,8 @@ __global__ __launch_bounds__(256) void pool_frames_ln_f16_kernel(const void* __r
                                                                  float* __restrict__ kbar, long n_units, int P, int d4, int slices) {
     pool_frames_ln_body<TokF16>(k_, stats, gamma, beta, kbar, n_units, P, d4, slices);
 }
+template <class Tok> struct PoolFramesLnFn { static auto get() { return pool_frames_ln_kernel<Tok>; } };
+template <> struct PoolFramesLnFn<TokF16> { static auto get() { return pool_frames_ln_f16_kernel; } };
 
 hipError_t launch_pool_ln(const void* k, tok_code tok, const void* stats, const float* gamma, const float* beta, float* kbar,
                           int64_t n_frames, int P, int d, hipStream_t stream) {
@@ -184,13 +176,14 @@ hipError_t launch_pool_ln(const void* k, tok_code tok, const void* stats, const 
     if (d % 4 || P < 1) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((n_units + 3) / 4));
     const float2* st = static_cast<const float2*>(stats);
-    switch (tok) {
-        case INFV_TOKENS_F32: INFV_LAUNCH(pool_frames_ln_kernel<TokF32>, grid, dim3(256), 0, stream, k, st, gamma, beta, kbar, n_units, P, d4, slices); break;
-        case INFV_TOKENS_BF16: INFV_LAUNCH(pool_frames_ln_kernel<TokBF16>, grid, dim3(256), 0, stream, k, st, gamma, beta, kbar, n_units, P, d4, slices); break;
-        case INFV_TOKENS_F16: INFV_LAUNCH(pool_frames_ln_f16_kernel, grid, dim3(256), 0, stream, k, st, gamma, beta, kbar, n_units, P, d4, slices); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_token_type(tok, [&](auto t) {
+        using Tok = decltype(t);
+        if constexpr (kTokHasLn<Tok>) {
+            INFV_LAUNCH(PoolFramesLnFn<Tok>::get(), grid, dim3(256), 0, stream, k, st, gamma, beta, kbar, n_units, P, d4, slices);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    });
 }
 
 // ======================================================================================

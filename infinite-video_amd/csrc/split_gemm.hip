@@ -4,6 +4,7 @@
 // the work of the fp32 32x32x2 one per cycle, so three of them are ~5x cheaper than an exact fp32 MFMA contraction.
 // Used where the result only feeds the 1e-3 read-out budget (short-term attention of the video Q-former, V' half of
 // the LTM projection) -- never for the LTM scores, whose rounding feeds the bit-exact Gibbs draw.
+// (What makes the operands' planes from frame tokens and score rows -- the token pass, the split softmax -- is token_pass.hip.)
 #include "vqf_internal.h"
 #include "ltm_device.h"
 
@@ -17,21 +18,6 @@ constexpr int kSPitch = 2 * kSBK + 16;            // bytes per LDS row: 64 bf16 
 constexpr int kSArr = 128 * kSPitch;              // bytes of one operand array tile (128 rows)
 constexpr int kSLds = 4 * kSArr;                  // A_hi, A_lo, B_hi, B_lo tiles (73.7 KB: dynamic LDS)
 constexpr int kSVec = kSBK / 16;                  // 16-byte vectors per thread per array tile (a thread owns half a row)
-
-__device__ inline void split2(float x, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)x;
-    lo = (__bf16)(x - (float)hi);
-}
-// a * b split the same way, the residual taken from the exact product (one fma).  That is what the compiler's contraction makes
-// of split2(a * b, ...) wherever the product meets the subtraction directly; spelled out, every row softmax below rounds P_lo the
-// same way whatever stands between the two (the column test of the padded kernels did, in the long one alone).
-__device__ inline void split2_mul(float a, float b, __bf16& hi, __bf16& lo) {
-    hi = (__bf16)(a * b);
-    lo = (__bf16)fmaf(b, a, -(float)hi);
-}
-__device__ inline unsigned pack2(__bf16 a, __bf16 b) {
-    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------
@@ -839,847 +825,5 @@ extern "C" int infv_exp_gemm(int which, const float* A, const float* B, float* C
 }
 namespace infv {
 #endif
-
-// ------------------------------------------------------------------------------------------------------
-// Frame tokens of a chunk, both ways round:  F [n][d] fp32 ->  F_hi/F_lo [n][d]   (B operand of the score contraction)
-//                                                             FT_hi/FT_lo [d][n]  (B operand of the token-mean contraction)
-// 64 x 64 tiles through LDS; grid (n / 64, d / 64, chunks).
-// ------------------------------------------------------------------------------------------------------
-// With kbar != nullptr the same pass also writes the frame means kbar[chunk][n / P][d] (the long-term memory's pooled
-// frames, Qformer.py:236): P divides 64, so a tile holds 64 / P whole frames; their P tokens are summed in token order and
-// divided by P exactly as pool_frames_kernel does, so the two agree bit for bit and the frame tokens are read once.
-__global__ __launch_bounds__(256) void split_transpose_kernel(const float* __restrict__ F, int n, int d,
-                                                              __bf16* __restrict__ Fh, __bf16* __restrict__ Fl,
-                                                              __bf16* __restrict__ Th, __bf16* __restrict__ Tl,
-                                                              float* __restrict__ kbar, int P) {
-    __shared__ float tile[64][65];
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const long cb = (long)blockIdx.z * n * d;
-    const float* src = F + cb;
-    // load 64 x 64 fp32 (float4 along d), write the untransposed hi/lo
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int e = tid + 256 * p;                 // 1024 float4 of the tile
-        const int r = e >> 4, c4 = (e & 15) * 4;
-        floatx4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r0 + r < n) v = *reinterpret_cast<const floatx4*>(src + (long)(r0 + r) * d + c0 + c4);
-        __bf16 h[4], l[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { split2(v[k], h[k], l[k]); tile[r][c4 + k] = v[k]; }
-        if (r0 + r < n) {
-            const long o = cb + (long)(r0 + r) * d + c0 + c4;
-            *reinterpret_cast<uint2*>(Fh + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-            *reinterpret_cast<uint2*>(Fl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-        }
-    }
-    __syncthreads();
-    // transposed: row = column c of the tile, 4 consecutive tokens per thread
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int e = tid + 256 * p;
-        const int c = e >> 4, r4 = (e & 15) * 4;
-        if (r0 + r4 < n) {                           // n % 4 == 0 (multiple of 32)
-            __bf16 h[4], l[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) split2(tile[r4 + k][c], h[k], l[k]);
-            const long o = cb + (long)(c0 + c) * n + r0 + r4;
-            *reinterpret_cast<uint2*>(Th + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-            *reinterpret_cast<uint2*>(Tl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-        }
-    }
-    if (kbar) {
-        const int fpt = 64 / P;                      // frames per tile
-        for (int e = tid; e < fpt * 64; e += 256) {
-            const int f = e >> 6, c = e & 63;
-            if (r0 + (f + 1) * P <= n) {
-                float acc = 0.f;
-                for (int p = 0; p < P; ++p) acc += tile[f * P + p][c];
-                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
-            }
-        }
-    }
-}
-
-static hipError_t launch_split_transpose(const float* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
-                                         hipStream_t stream, float* kbar, int P) {
-    if (n % 32 || d % 64) return hipErrorInvalidValue;
-    if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
-    INFV_LAUNCH(split_transpose_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, F, n, d,
-                       static_cast<__bf16*>(Fh), static_cast<__bf16*>(Fl), static_cast<__bf16*>(Th), static_cast<__bf16*>(Tl),
-                       kbar, P);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The token pass for fp16 frame tokens (what the reference's fp16 producer holds): split_transpose_kernel with F [n][d] fp16, read
-// at 2 bytes per element in 16-byte vectors of 8.  An fp16 value is exact in fp32 and split2() is the function the fp32 pass applies,
-// so F_hi / F_lo, FT_hi / FT_lo and (kbar != nullptr) the frame means -- summed in token order from the same fp32 tile and divided
-// by P -- are the fp32 pass's bits on the same values (hi + lo is the token exactly: 11 significand bits = 8 + 3).
-// The tile is kept widened, 65 words a row, as the fp32 pass keeps it.  ds_write_b32 / ds_read_b32 are served per 32-lane half
-// over 32 banks: a half writes 4 rows x 8 column groups at banks (r + 8 j + k) % 32 and reads 4 columns x 8 row groups at
-// (8 i + k + c) % 32 -- 16 distinct banks, each twice: the 2-way pattern of the fp32 pass in both directions (not measured with
-// the conflict counter; the pass is bound by its global traffic).  Stores are 16 bytes of 8 bf16.
-// ------------------------------------------------------------------------------------------------------
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-__global__ __launch_bounds__(256) void split_transpose_f16_kernel(const _Float16* __restrict__ F, int n, int d,
-                                                                  __bf16* __restrict__ Fh, __bf16* __restrict__ Fl,
-                                                                  __bf16* __restrict__ Th, __bf16* __restrict__ Tl,
-                                                                  float* __restrict__ kbar, int P) {
-    __shared__ float tile[64][65];
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const long cb = (long)blockIdx.z * n * d;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int e = tid + 256 * p;                 // 512 vectors of 8 fp16
-        const int r = e >> 3, c8 = (e & 7) * 8;
-        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
-        if (r0 + r < n) raw = *reinterpret_cast<const uint4*>(F + cb + (long)(r0 + r) * d + c0 + c8);
-        const halfx8 v = __builtin_bit_cast(halfx8, raw);
-        __bf16 h[8], l[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { const float x = (float)v[k]; split2(x, h[k], l[k]); tile[r][c8 + k] = x; }
-        if (r0 + r < n) {
-            const long o = cb + (long)(r0 + r) * d + c0 + c8;
-            *reinterpret_cast<uint4*>(Fh + o) = make_uint4(pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7]));
-            *reinterpret_cast<uint4*>(Fl + o) = make_uint4(pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7]));
-        }
-    }
-    __syncthreads();
-    // transposed: row = column c of the tile, 8 consecutive tokens per thread
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int e = tid + 256 * p;
-        const int c = e >> 3, r8 = (e & 7) * 8;
-        if (r0 + r8 < n) {                           // n % 8 == 0 (multiple of 32)
-            __bf16 h[8], l[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) split2(tile[r8 + k][c], h[k], l[k]);
-            const long o = cb + (long)(c0 + c) * n + r0 + r8;
-            *reinterpret_cast<uint4*>(Th + o) = make_uint4(pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7]));
-            *reinterpret_cast<uint4*>(Tl + o) = make_uint4(pack2(l[0], l[1]), pack2(l[2], l[3]), pack2(l[4], l[5]), pack2(l[6], l[7]));
-        }
-    }
-    if (kbar) {
-        const int fpt = 64 / P;                      // frames per tile
-        for (int e = tid; e < fpt * 64; e += 256) {
-            const int f = e >> 6, c = e & 63;
-            if (r0 + (f + 1) * P <= n) {
-                float acc = 0.f;
-                for (int p = 0; p < P; ++p) acc += tile[f * P + p][c];
-                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
-            }
-        }
-    }
-}
-
-static hipError_t launch_split_transpose_f16(const void* F, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
-                                             hipStream_t stream, float* kbar, int P) {
-    if (n % 32 || d % 64) return hipErrorInvalidValue;
-    if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
-    INFV_LAUNCH(split_transpose_f16_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const _Float16*>(F), n, d,
-                static_cast<__bf16*>(Fh), static_cast<__bf16*>(Fl), static_cast<__bf16*>(Th), static_cast<__bf16*>(Tl), kbar, P);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The token pass for fp8 e4m3 frame tokens (a storage format the caller chose): F [n][d] at 1 byte per element, read in 16-byte
-// vectors of 16.  An e4m3 value widens exactly to fp32 (widen_f8x4, ltm_device.h) and is exactly its own bf16 hi piece with a zero lo
-// piece (4 significand bits), so only the hi planes exist: F_hi [n][d] (the B operand of the score contraction: the caller's buffer
-// holds no bf16) and FT_hi [d][n]; both contractions then run their two-product form, as for bf16 tokens, bit for bit the
-// three-product run on the same values.  With kbar != nullptr the frame means are summed in token order from the widened fp32 tile and
-// divided by P, as the fp32 pass does.  The tile is kept widened, 65 words a row; the transposed half is split_transpose_f16_kernel's.
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void split_transpose_f8_kernel(const unsigned char* __restrict__ F, int n, int d,
-                                                                 __bf16* __restrict__ Fh, __bf16* __restrict__ Th,
-                                                                 float* __restrict__ kbar, int P) {
-    __shared__ float tile[64][65];
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const long cb = (long)blockIdx.z * n * d;
-    {
-        const int r = tid >> 2, c16 = (tid & 3) * 16;     // 256 vectors of 16 fp8
-        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
-        if (r0 + r < n) raw = *reinterpret_cast<const uint4*>(F + cb + (long)(r0 + r) * d + c0 + c16);
-        const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
-        unsigned h2[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const floatx4 x = widen_f8x4(w[q]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) tile[r][c16 + 4 * q + k] = x[k];
-            h2[2 * q] = pack2((__bf16)x[0], (__bf16)x[1]);
-            h2[2 * q + 1] = pack2((__bf16)x[2], (__bf16)x[3]);
-        }
-        if (r0 + r < n) {
-            uint4* dst = reinterpret_cast<uint4*>(Fh + cb + (long)(r0 + r) * d + c0 + c16);
-            dst[0] = make_uint4(h2[0], h2[1], h2[2], h2[3]);
-            dst[1] = make_uint4(h2[4], h2[5], h2[6], h2[7]);
-        }
-    }
-    __syncthreads();
-    // transposed: row = column c of the tile, 8 consecutive tokens per thread
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int e = tid + 256 * p;
-        const int c = e >> 3, r8 = (e & 7) * 8;
-        if (r0 + r8 < n) {                           // n % 8 == 0 (multiple of 32)
-            __bf16 h[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) h[k] = (__bf16)tile[r8 + k][c];
-            *reinterpret_cast<uint4*>(Th + cb + (long)(c0 + c) * n + r0 + r8) =
-                make_uint4(pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7]));
-        }
-    }
-    if (kbar) {
-        const int fpt = 64 / P;                      // frames per tile
-        for (int e = tid; e < fpt * 64; e += 256) {
-            const int f = e >> 6, c = e & 63;
-            if (r0 + (f + 1) * P <= n) {
-                float acc = 0.f;
-                for (int p = 0; p < P; ++p) acc += tile[f * P + p][c];
-                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
-            }
-        }
-    }
-}
-
-static hipError_t launch_split_transpose_f8(const void* F, int nb, int n, int d, void* Fh, void* Th, hipStream_t stream, float* kbar, int P) {
-    if (n % 32 || d % 64 || !Fh || !Th) return hipErrorInvalidValue;
-    if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
-    INFV_LAUNCH(split_transpose_f8_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const unsigned char*>(F), n, d,
-                static_cast<__bf16*>(Fh), static_cast<__bf16*>(Th), kbar, P);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The token pass for bf16 frame tokens: F [n][d] bf16 is the score contraction's B operand as it stands (hi = the token, lo = 0
-// exactly), so only FT_hi [d][n] is written -- and, with kbar != nullptr, the frame means, summed in token order and divided by P
-// as above (the same bits as the fp32 pass on the same values, and as pool_frames_kernel).  64 x 64 tiles, 16-byte loads and
-// stores of 8 bf16; grid (n / 64, d / 64, chunks).  LDS rows are 66 bf16 (33 words) apart: the transposed read of a wave (8 columns x
-// 8 row groups) touches 32 distinct banks.
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void transpose_bf16_kernel(const __bf16* __restrict__ F, int n, int d, __bf16* __restrict__ Th,
-                                                             float* __restrict__ kbar, int P) {
-    __shared__ unsigned tile[64 * 33];               // [64 tokens][66 bf16]
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const long cb = (long)blockIdx.z * n * d;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int e = tid + 256 * p;                 // 512 vectors of 8 bf16
-        const int r = e >> 3, c8 = (e & 7) * 8;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (r0 + r < n) v = *reinterpret_cast<const uint4*>(F + cb + (long)(r0 + r) * d + c0 + c8);
-        unsigned* t = tile + r * 33 + (c8 >> 1);
-        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-    }
-    __syncthreads();
-    const unsigned short* th = reinterpret_cast<const unsigned short*>(tile);
-    // transposed: row = column c of the tile, 8 consecutive tokens per thread
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int e = tid + 256 * p;
-        const int c = e >> 3, r8 = (e & 7) * 8;
-        if (r0 + r8 < n) {                           // n % 8 == 0 (multiple of 32)
-            unsigned w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                w[k] = (unsigned)th[(r8 + 2 * k) * 66 + c] | ((unsigned)th[(r8 + 2 * k + 1) * 66 + c] << 16);
-            *reinterpret_cast<uint4*>(Th + cb + (long)(c0 + c) * n + r0 + r8) = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-    if (kbar) {
-        const int fpt = 64 / P;                      // frames per tile
-        for (int e = tid; e < fpt * 64; e += 256) {
-            const int f = e >> 6, c = e & 63;
-            if (r0 + (f + 1) * P <= n) {
-                float acc = 0.f;
-                for (int p = 0; p < P; ++p) acc += __uint_as_float((unsigned)th[(f * P + p) * 66 + c] << 16);
-                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
-            }
-        }
-    }
-}
-
-static hipError_t launch_transpose_bf16(const void* F, int nb, int n, int d, void* Th, hipStream_t stream, float* kbar, int P) {
-    if (n % 32 || d % 64) return hipErrorInvalidValue;
-    if (kbar && (P < 1 || 64 % P || n % P)) return hipErrorInvalidValue;
-    INFV_LAUNCH(transpose_bf16_kernel, dim3((n + 63) / 64, d / 64, nb), dim3(256), 0, stream, static_cast<const __bf16*>(F), n, d,
-                static_cast<__bf16*>(Th), kbar, P);
-    return hipGetLastError();
-}
-
-// The token pass of `nb` <= 32768 chunks (grid.z) for any token type: the launch prepare_split issues.  kbar != nullptr needs
-// token_pass_gives_means(P): a frame that divides the 64-token tile.  (A per-frame form for P = 196 -- one workgroup per frame,
-// slab and chunk, the column sums kept in registers across sub-tiles -- was measured at 128 eval-shape chunks and lost to pooling
-// + this pass for fp16 and bf16 tokens alike, profiles/vc_half_tokens.jsonl; it is gone.)  bf16: Fh / Fl / Tl are not written;
-// fp8: Fl / Tl are not written.
-bool token_pass_gives_means(int P) { return P >= 1 && 64 % P == 0; }
-
-hipError_t launch_token_pass(const void* F, tok_code tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
-                             hipStream_t stream, float* kbar, int P) {
-    if (kbar && !token_pass_gives_means(P)) return hipErrorInvalidValue;
-    switch (tok) {
-        case INFV_TOKENS_BF16: return launch_transpose_bf16(F, nb, n, d, Th, stream, kbar, P);
-        case INFV_TOKENS_F16: return launch_split_transpose_f16(F, nb, n, d, Fh, Fl, Th, Tl, stream, kbar, P);
-        case INFV_TOKENS_F8E4M3: return launch_split_transpose_f8(F, nb, n, d, Fh, Th, stream, kbar, P);
-        case INFV_TOKENS_F32: return launch_split_transpose(static_cast<const float*>(F), nb, n, d, Fh, Fl, Th, Tl, stream, kbar, P);
-    }
-    return hipErrorInvalidValue;
-}
-
-// x [n] bf16 -> y [n] fp32 (n % 8 == 0): bf16 tokens where the split path does not apply run the fp32 kernels from this copy
-__global__ __launch_bounds__(256) void upcast_bf16_kernel(const __bf16* __restrict__ x, float* __restrict__ y, long n8) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    const uint4 v = reinterpret_cast<const uint4*>(x)[i];
-    floatx4 a = {__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u)};
-    floatx4 b = {__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u), __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xffff0000u)};
-    reinterpret_cast<floatx4*>(y)[2 * i] = a;
-    reinterpret_cast<floatx4*>(y)[2 * i + 1] = b;
-}
-
-hipError_t launch_upcast_bf16(const void* x, float* y, long n, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    if (n % 8) return hipErrorInvalidValue;
-    for (long o = 0; o < n; o += (1l << 33)) {          // (grid.x limit)
-        const long m = n - o < (1l << 33) ? n - o : (1l << 33);
-        INFV_LAUNCH(upcast_bf16_kernel, dim3((unsigned)((m / 8 + 255) / 256)), dim3(256), 0, stream, static_cast<const __bf16*>(x) + o, y + o, m / 8);
-    }
-    return hipGetLastError();
-}
-
-// x [n] fp16 -> y [n] fp32 (n % 8 == 0), exact: fp16 tokens where the split path does not apply
-__global__ __launch_bounds__(256) void upcast_f16_kernel(const _Float16* __restrict__ x, float* __restrict__ y, long n8) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    const halfx8 v = __builtin_bit_cast(halfx8, reinterpret_cast<const uint4*>(x)[i]);
-    floatx4 a = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-    floatx4 b = {(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
-    reinterpret_cast<floatx4*>(y)[2 * i] = a;
-    reinterpret_cast<floatx4*>(y)[2 * i + 1] = b;
-}
-
-hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    if (n % 8) return hipErrorInvalidValue;
-    for (long o = 0; o < n; o += (1l << 33)) {          // (grid.x limit)
-        const long m = n - o < (1l << 33) ? n - o : (1l << 33);
-        INFV_LAUNCH(upcast_f16_kernel, dim3((unsigned)((m / 8 + 255) / 256)), dim3(256), 0, stream, static_cast<const _Float16*>(x) + o, y + o, m / 8);
-    }
-    return hipGetLastError();
-}
-
-// x [n] fp8 e4m3 -> y [n] fp32 (n % 16 == 0), exact: fp8 tokens where the split path does not apply
-__global__ __launch_bounds__(256) void upcast_f8_kernel(const unsigned char* __restrict__ x, float* __restrict__ y, long n16) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n16) return;
-    const uint4 v = reinterpret_cast<const uint4*>(x)[i];
-    floatx4* dst = reinterpret_cast<floatx4*>(y) + 4 * i;
-    dst[0] = widen_f8x4(v.x); dst[1] = widen_f8x4(v.y); dst[2] = widen_f8x4(v.z); dst[3] = widen_f8x4(v.w);
-}
-
-hipError_t launch_upcast_f8(const void* x, float* y, long n, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    if (n % 16) return hipErrorInvalidValue;
-    for (long o = 0; o < n; o += (1l << 33)) {          // (grid.x limit)
-        const long m = n - o < (1l << 33) ? n - o : (1l << 33);
-        INFV_LAUNCH(upcast_f8_kernel, dim3((unsigned)((m / 16 + 255) / 256)), dim3(256), 0, stream, static_cast<const unsigned char*>(x) + o, y + o, m / 16);
-    }
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The vision LayerNorm of the frame tokens (videochat2_it_mistral.py:195: nn.LayerNorm(width, eps = 1e-12) between the vision
-// encoder's fp16 output and the Q-former), applied while the tokens are read at their own dtype -- no fp32 copy of them.
-//   token_ln_stats_kernel   (mean, 1 / sqrt(var + eps)) per token row, 8 bytes per token
-//   ln_tokens_kernel        y = token_ln(x) as an fp32 tensor: the reference form of the bits, and the fallback where the split path
-//                           does not apply (as upcast_f16_kernel / upcast_bf16_kernel are for plain tokens)
-//   split_transpose_ln_kernel   split_transpose_kernel's body over y computed on load (the pooling form is in ltm_kernels.hip)
-// Every consumer calls token_ln() of ltm_device.h on values widened exactly, so all of them see the bits ln_tokens_kernel writes.
-// ------------------------------------------------------------------------------------------------------
-// One wave per token row: the row is read once into registers (NV float4 per lane, lanes beyond the row idle), the mean is a
-// fixed-order reduction (per lane in column order, then an xor butterfly over the wave) divided by d, the variance a second
-// reduction of (x - mean)^2 from the registers (two-pass, biased, as nn.LayerNorm).  No atomics; the order does not depend on the grid.
-template <class Tok, int NV>
-__global__ __launch_bounds__(256) void token_ln_stats_kernel(const void* __restrict__ F, long n_rows, int d4, float eps,
-                                                             float2* __restrict__ stats) {
-    typedef typename Tok::vec tvec;
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_rows) return;
-    const tvec* src = reinterpret_cast<const tvec*>(F) + row * d4;
-    floatx4 x[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        x[i] = floatx4{0.f, 0.f, 0.f, 0.f};
-        if (lane + 64 * i < d4) x[i] = Tok::widen(src[lane + 64 * i]);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) s += (x[i].x + x[i].y) + (x[i].z + x[i].w);      // (idle slots hold zeros)
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    const float mu = s / (float)(4 * d4);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-        if (lane + 64 * i < d4) {
-            const floatx4 dx = x[i] - mu;
-            q += (dx.x * dx.x + dx.y * dx.y) + (dx.z * dx.z + dx.w * dx.w);
-        }
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
-    const float var = q / (float)(4 * d4);
-    if (lane == 0) stats[row] = make_float2(mu, 1.0f / sqrtf(var + eps));
-}
-
-template <class Tok>
-static hipError_t launch_token_ln_stats_t(const void* F, long n_rows, int d, float eps, float2* stats, hipStream_t stream) {
-    const int d4 = d / 4;
-    const dim3 grid((unsigned)((n_rows + 3) / 4));
-    if (d4 <= 64) INFV_LAUNCH((token_ln_stats_kernel<Tok, 1>), grid, dim3(256), 0, stream, F, n_rows, d4, eps, stats);
-    else if (d4 <= 256) INFV_LAUNCH((token_ln_stats_kernel<Tok, 4>), grid, dim3(256), 0, stream, F, n_rows, d4, eps, stats);
-    else INFV_LAUNCH((token_ln_stats_kernel<Tok, 16>), grid, dim3(256), 0, stream, F, n_rows, d4, eps, stats);
-    return hipGetLastError();
-}
-
-hipError_t launch_token_ln_stats(const void* F, tok_code tok, long n_rows, int d, float eps, void* stats, hipStream_t stream) {
-    if (n_rows <= 0) return hipSuccess;
-    if (d < 64 || d % 64 || d > kTokenLnMaxWidth || (n_rows + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
-    float2* st = static_cast<float2*>(stats);
-    switch (tok) {
-        case INFV_TOKENS_F32: return launch_token_ln_stats_t<TokF32>(F, n_rows, d, eps, st, stream);
-        case INFV_TOKENS_BF16: return launch_token_ln_stats_t<TokBF16>(F, n_rows, d, eps, st, stream);
-        case INFV_TOKENS_F16: return launch_token_ln_stats_t<TokF16>(F, n_rows, d, eps, st, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <class Tok>
-__global__ __launch_bounds__(256) void ln_tokens_kernel(const void* __restrict__ F, long n_vec, int d4, const float2* __restrict__ stats,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        float* __restrict__ y) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_vec) return;
-    const long row = i / d4;
-    const int c4 = (int)(i - row * d4);
-    const floatx4 x = Tok::widen(reinterpret_cast<const typename Tok::vec*>(F)[i]);
-    reinterpret_cast<floatx4*>(y)[i] = token_ln4(x, stats[row], reinterpret_cast<const floatx4*>(gamma)[c4],
-                                                 reinterpret_cast<const floatx4*>(beta)[c4]);
-}
-
-hipError_t launch_ln_tokens(const void* F, tok_code tok, long n_rows, int d, const void* stats, const float* gamma, const float* beta,
-                            float* y, hipStream_t stream) {
-    if (n_rows <= 0) return hipSuccess;
-    if (d < 64 || d % 64) return hipErrorInvalidValue;
-    const int d4 = d / 4;
-    const long step = 0x7fffffffL * 256 / d4;           // rows per launch (grid.x limit)
-    const float2* st = static_cast<const float2*>(stats);
-    for (long r0 = 0; r0 < n_rows; r0 += step) {
-        const long m = n_rows - r0 < step ? n_rows - r0 : step;
-        const long n_vec = m * d4;
-        const dim3 grid((unsigned)((n_vec + 255) / 256));
-        const void* src = static_cast<const char*>(F) + r0 * d * (long)token_bytes(tok);
-        float* dst = y + r0 * d;
-        switch (tok) {
-            case INFV_TOKENS_F32: INFV_LAUNCH(ln_tokens_kernel<TokF32>, grid, dim3(256), 0, stream, src, n_vec, d4, st + r0, gamma, beta, dst); break;
-            case INFV_TOKENS_BF16: INFV_LAUNCH(ln_tokens_kernel<TokBF16>, grid, dim3(256), 0, stream, src, n_vec, d4, st + r0, gamma, beta, dst); break;
-            case INFV_TOKENS_F16: INFV_LAUNCH(ln_tokens_kernel<TokF16>, grid, dim3(256), 0, stream, src, n_vec, d4, st + r0, gamma, beta, dst); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-    return hipGetLastError();
-}
-
-// split_transpose_kernel over y = token_ln(F): F [n][d] of the token type is read once (4 columns per thread), normalised on load
-// into the 64 x 64 fp32 tile (65-word pitch) and from there everything is the fp32 pass's -- F_hi / F_lo, FT_hi / FT_lo and, with
-// kbar, the frame means in token order.  A normalised value is a general fp32 number, so every token type writes all four planes.
-// stats [chunks * n] addresses the launch's first chunk.
-template <class Tok>
-__global__ __launch_bounds__(256) void split_transpose_ln_kernel(const void* __restrict__ F, int n, int d, const float2* __restrict__ stats,
-                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                 __bf16* __restrict__ Fh, __bf16* __restrict__ Fl,
-                                                                 __bf16* __restrict__ Th, __bf16* __restrict__ Tl,
-                                                                 float* __restrict__ kbar, int P) {
-    __shared__ float tile[64][65];
-    typedef typename Tok::vec tvec;
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const long cb = (long)blockIdx.z * n * d;
-    const tvec* src = reinterpret_cast<const tvec*>(F);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int e = tid + 256 * p;                 // 1024 groups of 4 columns
-        const int r = e >> 4, c4 = (e & 15) * 4;
-        floatx4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r0 + r < n)
-            v = token_ln4(Tok::widen(src[(cb + (long)(r0 + r) * d + c0 + c4) >> 2]), stats[(long)blockIdx.z * n + r0 + r],
-                          *reinterpret_cast<const floatx4*>(gamma + c0 + c4), *reinterpret_cast<const floatx4*>(beta + c0 + c4));
-        __bf16 h[4], l[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { split2(v[k], h[k], l[k]); tile[r][c4 + k] = v[k]; }
-        if (r0 + r < n) {
-            const long o = cb + (long)(r0 + r) * d + c0 + c4;
-            *reinterpret_cast<uint2*>(Fh + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-            *reinterpret_cast<uint2*>(Fl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int e = tid + 256 * p;
-        const int c = e >> 4, r4 = (e & 15) * 4;
-        if (r0 + r4 < n) {                           // n % 4 == 0 (multiple of 32)
-            __bf16 h[4], l[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) split2(tile[r4 + k][c], h[k], l[k]);
-            const long o = cb + (long)(c0 + c) * n + r0 + r4;
-            *reinterpret_cast<uint2*>(Th + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-            *reinterpret_cast<uint2*>(Tl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-        }
-    }
-    if (kbar) {
-        const int fpt = 64 / P;                      // frames per tile
-        for (int e = tid; e < fpt * 64; e += 256) {
-            const int f = e >> 6, c = e & 63;
-            if (r0 + (f + 1) * P <= n) {
-                float acc = 0.f;
-                for (int p = 0; p < P; ++p) acc += tile[f * P + p][c];
-                kbar[((long)blockIdx.z * (n / P) + r0 / P + f) * d + c0 + c] = acc / (float)P;
-            }
-        }
-    }
-}
-
-hipError_t launch_token_pass_ln(const void* F, tok_code tok, int nb, int n, int d, const void* stats, const float* gamma,
-                                const float* beta, void* Fh_, void* Fl_, void* Th_, void* Tl_, hipStream_t stream, float* kbar, int P) {
-    if (nb <= 0) return hipSuccess;
-    if (n % 32 || d % 64 || nb > 32768) return hipErrorInvalidValue;
-    if (kbar && (!token_pass_gives_means(P) || n % P)) return hipErrorInvalidValue;
-    const dim3 grid((n + 63) / 64, d / 64, nb);
-    const float2* st = static_cast<const float2*>(stats);
-    __bf16 *Fh = static_cast<__bf16*>(Fh_), *Fl = static_cast<__bf16*>(Fl_), *Th = static_cast<__bf16*>(Th_), *Tl = static_cast<__bf16*>(Tl_);
-    switch (tok) {
-        case INFV_TOKENS_F32: INFV_LAUNCH(split_transpose_ln_kernel<TokF32>, grid, dim3(256), 0, stream, F, n, d, st, gamma, beta, Fh, Fl, Th, Tl, kbar, P); break;
-        case INFV_TOKENS_BF16: INFV_LAUNCH(split_transpose_ln_kernel<TokBF16>, grid, dim3(256), 0, stream, F, n, d, st, gamma, beta, Fh, Fl, Th, Tl, kbar, P); break;
-        case INFV_TOKENS_F16: INFV_LAUNCH(split_transpose_ln_kernel<TokF16>, grid, dim3(256), 0, stream, F, n, d, st, gamma, beta, Fh, Fl, Th, Tl, kbar, P); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Row softmax of fp32 scores [n_rows][len] (leading dimension ld), written as split bf16 P_hi / P_lo (ld_out)
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void softmax_rows_split_kernel(const float* __restrict__ S, int len, long ld,
-                                                                 __bf16* __restrict__ Ph, __bf16* __restrict__ Pl, long ld_out) {
-    __shared__ float red[4];
-    const float* row = S + (long)blockIdx.x * ld;
-    const int tid = threadIdx.x;
-    float mx = -INFINITY;
-    for (int c = tid * 4; c < len; c += 1024) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
-        mx = fmaxf(mx, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-    }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-    for (int c = tid * 4; c < len; c += 1024) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
-        sum += (expf(v[0] - mx) + expf(v[1] - mx)) + (expf(v[2] - mx) + expf(v[3] - mx));
-    }
-    sum = wave_sum(sum);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
-    __bf16* ph = Ph + (long)blockIdx.x * ld_out;
-    __bf16* pl = Pl + (long)blockIdx.x * ld_out;
-    for (int c = tid * 4; c < len; c += 1024) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
-        __bf16 h[4], l[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) split2_mul(expf(v[k] - mx), inv, h[k], l[k]);
-        *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-        *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-    }
-}
-
-// The same softmax for rows of up to 1024 * NV floats, each row read ONCE: a thread keeps its NV float4 in registers
-// between the max, the sum and the write (same per-thread order of operations as the three-pass kernel above: same bits).
-template <int NV>
-__global__ __launch_bounds__(256) void softmax_rows_split_reg_kernel(const float* __restrict__ S, int len, long ld,
-                                                                     __bf16* __restrict__ Ph, __bf16* __restrict__ Pl, long ld_out) {
-    __shared__ float red[4];
-    const float* row = S + (long)blockIdx.x * ld;
-    const int tid = threadIdx.x;
-    floatx4 v[NV];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid * 4 + 1024 * i;
-        if (c < len) {
-            v[i] = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(row + c));
-            mx = fmaxf(mx, fmaxf(fmaxf(v[i][0], v[i][1]), fmaxf(v[i][2], v[i][3])));
-        }
-    }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid * 4 + 1024 * i;
-        if (c < len) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[i][k] = expf(v[i][k] - mx);
-            sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-        }
-    }
-    sum = wave_sum(sum);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
-    __bf16* ph = Ph + (long)blockIdx.x * ld_out;
-    __bf16* pl = Pl + (long)blockIdx.x * ld_out;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid * 4 + 1024 * i;
-        if (c < len) {
-            __bf16 h[4], l[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) split2_mul(v[i][k], inv, h[k], l[k]);
-            *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-            *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-        }
-    }
-}
-
-hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long ld, void* Ph, void* Pl, long ld_out,
-                                     hipStream_t stream) {
-    if (len % 4 || ld % 4 || ld_out % 4) return hipErrorInvalidValue;
-    if (len <= 2048) {
-        INFV_LAUNCH(softmax_rows_split_reg_kernel<2>, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, ld,
-                           static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
-        return hipGetLastError();
-    }
-    if (len <= 8192) {
-        INFV_LAUNCH(softmax_rows_split_reg_kernel<8>, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, ld,
-                           static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
-        return hipGetLastError();
-    }
-    INFV_LAUNCH(softmax_rows_split_kernel, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, ld,
-                       static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The padded forms of the token pass and the row softmax (infv_vqf_encode_frames): a frame of n tokens where n is no multiple of
-// 64 -- a ViT hands over 257 = class token + 16 x 16 patches.  The contractions need K and the leading dimensions in multiples of
-// 64, so the planes are kept at n_pad = ceil(n / 64) * 64 tokens per frame: F_hi / F_lo [.][n_pad][d], FT_hi / FT_lo [.][d][n_pad],
-// rows at or beyond n exact zeros.  The softmax gives the pad keys no mass (exact zeros in P_hi / P_lo), so the context
-// contraction over K = n_pad adds exact zeros.  n % 64 == 0 never comes here: it takes the kernels above, launch for launch.
-// ------------------------------------------------------------------------------------------------------
-// split_transpose_kernel / split_transpose_ln_kernel for any token type with the source at n tokens per frame and the planes at
-// n_pad.  The source is read 4 columns per thread inside ONE token row (d % 64 == 0: no load straddles a row), and only rows
-// r < n of this frame: the last tile of a frame never touches the next frame's first rows or the bytes behind the buffer.  Whether
-// a tile is the partial one is uniform over the workgroup (blockIdx.x); inside it the row test predicates the load alone.
-// Fl == nullptr (bf16 / fp8 tokens without LayerNorm: the value is its own hi piece, lo is exactly 0): the lo planes are not written.
-template <class Tok, bool LN>
-__global__ __launch_bounds__(256) void token_pass_pad_kernel(const void* __restrict__ F, int n, int n_pad, int d,
-                                                             const float2* __restrict__ stats, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, __bf16* __restrict__ Fh,
-                                                             __bf16* __restrict__ Fl, __bf16* __restrict__ Th, __bf16* __restrict__ Tl) {
-    __shared__ float tile[64][65];
-    typedef typename Tok::vec tvec;
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const long cin = (long)blockIdx.z * n * d;           // source: n rows a frame
-    const long cout = (long)blockIdx.z * n_pad * d;      // planes: n_pad rows a frame
-    const int live_rows = n - r0 < 64 ? n - r0 : 64;     // (>= 1: grid.x = n_pad / 64 = ceil(n / 64))
-    const tvec* src = reinterpret_cast<const tvec*>(F);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int e = tid + 256 * p;                     // 1024 groups of 4 columns
-        const int r = e >> 4, c4 = (e & 15) * 4;
-        floatx4 v = {0.f, 0.f, 0.f, 0.f};
-        if (r < live_rows) {
-            v = Tok::widen(src[(cin + (long)(r0 + r) * d + c0 + c4) >> 2]);
-            if (LN)
-                v = token_ln4(v, stats[(long)blockIdx.z * n + r0 + r], *reinterpret_cast<const floatx4*>(gamma + c0 + c4),
-                              *reinterpret_cast<const floatx4*>(beta + c0 + c4));
-        }
-        __bf16 h[4], l[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { split2(v[k], h[k], l[k]); tile[r][c4 + k] = v[k]; }
-        const long o = cout + (long)(r0 + r) * d + c0 + c4;                       // (r0 + r < n_pad: pad rows are written as zeros)
-        *reinterpret_cast<uint2*>(Fh + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-        if (Fl) *reinterpret_cast<uint2*>(Fl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int e = tid + 256 * p;
-        const int c = e >> 4, r4 = (e & 15) * 4;
-        __bf16 h[4], l[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) split2(tile[r4 + k][c], h[k], l[k]);
-        const long o = cout + (long)(c0 + c) * n_pad + r0 + r4;
-        *reinterpret_cast<uint2*>(Th + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-        if (Tl) *reinterpret_cast<uint2*>(Tl + o) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-    }
-}
-
-template <class Tok, bool kHasLn = true /* false: no LayerNorm form of this token type exists (fp8) */>
-static hipError_t launch_token_pass_pad_t(const void* F, int nb, int n, int n_pad, int d, const float2* st, const float* gamma,
-                                          const float* beta, __bf16* Fh, __bf16* Fl, __bf16* Th, __bf16* Tl, hipStream_t stream) {
-    const dim3 grid(n_pad / 64, d / 64, nb);
-    if (!st) {
-        INFV_LAUNCH((token_pass_pad_kernel<Tok, false>), grid, dim3(256), 0, stream, F, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl);
-        return hipGetLastError();
-    }
-    if constexpr (kHasLn) {
-        INFV_LAUNCH((token_pass_pad_kernel<Tok, true>), grid, dim3(256), 0, stream, F, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl);
-        return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_token_pass_pad(const void* F, tok_code tok, int nb, int n, int n_pad, int d, const void* stats, const float* gamma,
-                                 const float* beta, void* Fh_, void* Fl_, void* Th_, void* Tl_, hipStream_t stream) {
-    if (nb <= 0) return hipSuccess;
-    if (n < 1 || n_pad % 64 || n_pad < n || n_pad - n >= 64 || d < 64 || d % 64 || nb > 32768 || !Fh_ || !Th_) return hipErrorInvalidValue;
-    if (stats && (!gamma || !beta || tok == INFV_TOKENS_F8E4M3)) return hipErrorInvalidValue;
-    const bool own_hi = !stats && (tok == INFV_TOKENS_BF16 || tok == INFV_TOKENS_F8E4M3);   // no lo planes
-    if (own_hi ? (Fl_ || Tl_) : (!Fl_ || !Tl_)) return hipErrorInvalidValue;
-    const float2* st = static_cast<const float2*>(stats);
-    __bf16 *Fh = static_cast<__bf16*>(Fh_), *Fl = static_cast<__bf16*>(Fl_), *Th = static_cast<__bf16*>(Th_), *Tl = static_cast<__bf16*>(Tl_);
-    switch (tok) {
-        case INFV_TOKENS_F32: return launch_token_pass_pad_t<TokF32>(F, nb, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl, stream);
-        case INFV_TOKENS_BF16: return launch_token_pass_pad_t<TokBF16>(F, nb, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl, stream);
-        case INFV_TOKENS_F16: return launch_token_pass_pad_t<TokF16>(F, nb, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl, stream);
-        case INFV_TOKENS_F8E4M3: return launch_token_pass_pad_t<TokF8, false>(F, nb, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
-// softmax_rows_split_reg_kernel over the first `len` columns of a score row of padded length len_pad (len <= len_pad, both below
-// 1024 * NV): columns [len, len_pad) never enter the max or the sum -- whatever finite or non-finite value they hold -- and are
-// written as exact zeros into P_hi / P_lo.  The row is read in 16-byte vectors up to len_pad (inside the row's allocation); the
-// column test selects per element.
-template <int NV>
-__global__ __launch_bounds__(256) void softmax_rows_split_pad_kernel(const float* __restrict__ S, int len, int len_pad, long ld,
-                                                                     __bf16* __restrict__ Ph, __bf16* __restrict__ Pl, long ld_out) {
-    __shared__ float red[4];
-    const float* row = S + (long)blockIdx.x * ld;
-    const int tid = threadIdx.x;
-    floatx4 v[NV];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid * 4 + 1024 * i;
-        if (c < len_pad) {
-            const floatx4 raw = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(row + c));
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[i][k] = c + k < len ? raw[k] : -INFINITY;
-            mx = fmaxf(mx, fmaxf(fmaxf(v[i][0], v[i][1]), fmaxf(v[i][2], v[i][3])));
-        }
-    }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid * 4 + 1024 * i;
-        if (c < len_pad) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[i][k] = c + k < len ? expf(v[i][k] - mx) : 0.f;
-            sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-        }
-    }
-    sum = wave_sum(sum);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
-    __bf16* ph = Ph + (long)blockIdx.x * ld_out;
-    __bf16* pl = Pl + (long)blockIdx.x * ld_out;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = tid * 4 + 1024 * i;
-        if (c < len_pad) {
-            __bf16 h[4], l[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) split2_mul(v[i][k], inv, h[k], l[k]);
-            *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-            *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-        }
-    }
-}
-
-// rows beyond 8192 columns: softmax_rows_split_kernel's three passes over the row, with the same column test
-__global__ __launch_bounds__(256) void softmax_rows_split_pad_long_kernel(const float* __restrict__ S, int len, int len_pad, long ld,
-                                                                          __bf16* __restrict__ Ph, __bf16* __restrict__ Pl, long ld_out) {
-    __shared__ float red[4];
-    const float* row = S + (long)blockIdx.x * ld;
-    const int tid = threadIdx.x;
-    float mx = -INFINITY;
-    for (int c = tid * 4; c < len_pad; c += 1024) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) mx = fmaxf(mx, c + k < len ? v[k] : -INFINITY);
-    }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-    for (int c = tid * 4; c < len_pad; c += 1024) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
-        float ex[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ex[k] = c + k < len ? expf(v[k] - mx) : 0.f;
-        sum += (ex[0] + ex[1]) + (ex[2] + ex[3]);
-    }
-    sum = wave_sum(sum);
-    if ((tid & 63) == 0) red[tid >> 6] = sum;
-    __syncthreads();
-    const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
-    __bf16* ph = Ph + (long)blockIdx.x * ld_out;
-    __bf16* pl = Pl + (long)blockIdx.x * ld_out;
-    for (int c = tid * 4; c < len_pad; c += 1024) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(row + c);
-        __bf16 h[4], l[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) split2_mul(c + k < len ? expf(v[k] - mx) : 0.f, inv, h[k], l[k]);
-        *reinterpret_cast<uint2*>(ph + c) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-        *reinterpret_cast<uint2*>(pl + c) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
-    }
-}
-
-hipError_t launch_softmax_rows_split_pad(const float* S, long n_rows, int len, int len_pad, long ld, void* Ph, void* Pl, long ld_out,
-                                         hipStream_t stream) {
-    if (n_rows <= 0) return hipSuccess;
-    if (len < 1 || len > len_pad || len_pad % 4 || len_pad > ld || len_pad > ld_out || ld % 4 || ld_out % 4 || n_rows > 0x7fffffffL)
-        return hipErrorInvalidValue;
-    if (len_pad <= 2048)
-        INFV_LAUNCH(softmax_rows_split_pad_kernel<2>, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, len_pad, ld,
-                    static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
-    else if (len_pad <= 8192)
-        INFV_LAUNCH(softmax_rows_split_pad_kernel<8>, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, len_pad, ld,
-                    static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
-    else
-        INFV_LAUNCH(softmax_rows_split_pad_long_kernel, dim3((unsigned)n_rows), dim3(256), 0, stream, S, len, len_pad, ld,
-                    static_cast<__bf16*>(Ph), static_cast<__bf16*>(Pl), ld_out);
-    return hipGetLastError();
-}
 
 }  // namespace infv

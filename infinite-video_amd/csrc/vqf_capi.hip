@@ -225,9 +225,7 @@ static double plane_bytes(tok_code tok, bool ln, bool padded = false) {
 static int fp32_tokens_unless_split(infv_vqf_s* h, const void*& frames, tok_code& tok, int n_tokens, size_t elems, hipStream_t stream) {
     if (tok == INFV_TOKENS_F32 || split_path(h, n_tokens)) return INFV_OK;
     HIP_TRY(reserve_all({{h->up, elems * sizeof(float)}}));
-    if (tok == INFV_TOKENS_F16) HIP_TRY(launch_upcast_f16(frames, h->up.as<float>(), (long)elems, stream));
-    else if (tok == INFV_TOKENS_F8E4M3) HIP_TRY(launch_upcast_f8(frames, h->up.as<float>(), (long)elems, stream));
-    else HIP_TRY(launch_upcast_bf16(frames, h->up.as<float>(), (long)elems, stream));
+    HIP_TRY(launch_upcast(frames, tok, h->up.as<float>(), (long)elems, stream));
     frames = h->up.p; tok = INFV_TOKENS_F32;
     return INFV_OK;
 }

@@ -128,12 +128,9 @@ struct LinearGemm {
 hipError_t launch_linear_gemm(const LinearGemm& g, int mode, hipStream_t stream);
 // x [rows][cols] fp32 -> out [rows][cols] fp16, round to nearest even (beyond 65504: inf)
 hipError_t launch_round_rows_f16(const float* x, long ld_in, long rows, int cols, void* out, long ld_out, hipStream_t stream);
-// x [n] bf16 -> y [n] fp32, n % 8 == 0
-hipError_t launch_upcast_bf16(const void* x, float* y, long n, hipStream_t stream);
-// x [n] fp16 -> y [n] fp32 (exact), n % 8 == 0
-hipError_t launch_upcast_f16(const void* x, float* y, long n, hipStream_t stream);
-// x [n] fp8 e4m3 -> y [n] fp32 (exact), n % 16 == 0
-hipError_t launch_upcast_f8(const void* x, float* y, long n, hipStream_t stream);
+// ---- frame tokens and score rows -> the contractions' bf16 planes (token_pass.hip) ----
+// x [n] bf16 / fp16 / fp8 e4m3 -> y [n] fp32 (exact); n % 8 == 0, fp8: n % 16 == 0.  fp32 tokens are refused
+hipError_t launch_upcast(const void* x, tok_code tok, float* y, long n, hipStream_t stream);
 // bytes per element of a token type
 inline size_t token_bytes(tok_code tok) { return tok == INFV_TOKENS_F32 ? 4 : tok == INFV_TOKENS_F8E4M3 ? 1 : 2; }
 // The token pass of nb <= 32768 chunks F [nb][n][d] of any token type -> the bf16 planes Fh/Fl [nb][n][d] and Th/Tl [nb][d][n] and, with kbar,
@@ -142,7 +139,7 @@ inline size_t token_bytes(tok_code tok) { return tok == INFV_TOKENS_F32 ? 4 : to
 bool token_pass_gives_means(int P);
 hipError_t launch_token_pass(const void* F, tok_code tok, int nb, int n, int d, void* Fh, void* Fl, void* Th, void* Tl,
                              hipStream_t stream, float* kbar, int P);
-// ---- vision LayerNorm of the frame tokens (videochat2_it_mistral.py:195), y = token_ln(x) of ltm_device.h ----
+// ---- vision LayerNorm of the frame tokens (videochat2_it_mistral.py:195), y = token_ln(x) of ltm_device.h (token_pass.hip) ----
 constexpr int kTokenLnMaxWidth = 4096;   // a token row is held in one wave's registers: 16 float4 per lane
 // stats[row] = (mean, 1 / sqrt(var + eps)) of n_rows token rows of width d (d % 64 == 0, d <= kTokenLnMaxWidth); stats: float2
 hipError_t launch_token_ln_stats(const void* F, tok_code tok, long n_rows, int d, float eps, void* stats, hipStream_t stream);
@@ -160,10 +157,10 @@ hipError_t launch_pool_ln(const void* k, tok_code tok, const void* stats, const 
 hipError_t launch_qf_vc_embed(const float* word, const float* position, const float* query_tokens, const float* gamma, const float* beta,
                               float eps, const int32_t* src, const int32_t* pos, int n_rows, int width, float* out, hipStream_t stream);
 
-// softmax of fp32 score rows, written as bf16 hi/lo
+// softmax of fp32 score rows, written as bf16 hi/lo (token_pass.hip)
 hipError_t launch_softmax_rows_split(const float* S, long n_rows, int len, long ld, void* Ph, void* Pl, long ld_out, hipStream_t stream);
 
-// ---- padded forms for frames whose token count is no multiple of 64 (infv_vqf_encode_frames) ----
+// ---- padded forms for frames whose token count is no multiple of 64 (infv_vqf_encode_frames; token_pass.hip) ----
 // F [nb][n][d] of any token type (stats != nullptr: token_ln(F) applied on load, not for fp8) -> Fh/Fl [nb][n_pad][d] and
 // Th/Tl [nb][d][n_pad], n_pad = ceil(n / 64) * 64, rows at or beyond n zeros; rows of the next frame are never read.
 // bf16 / fp8 tokens without LayerNorm: Fl and Tl must be nullptr (Fh IS written: the caller's buffer has another stride).  nb <= 32768

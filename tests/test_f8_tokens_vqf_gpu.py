@@ -98,15 +98,11 @@ def test_three_way_fp8_fp32_bf16_and_batch_invariance():
     B.assert_same_state(B.engine_state(mem[0].engines, case), out["f8"][1][case.n_layers:], "video 1 alone: memories")
 
 
-def test_token_pass_alone():
-    """infv_vqf_token_pass with code 4 (Fl, Tl NULL): Fh is the tokens as bf16 and Th its transpose -- the plane the bf16 pass
-    writes on x.bfloat16() -- nothing is written outside them, and the frame means equal infv_ltm_pool's on the fp8 tokens and on
-    x.float()."""
+def _token_pass_alone(nb, T, P, d):
     from infinite_video_amd import _lib
     from infinite_video_amd.engine import LTMEngine
     from tests.test_vc_token_pass_gpu import Out
     lib = _lib.load()
-    nb, T, P, d = 3, 24, 4, 128                                       # 96 tokens: a second, half-filled 64-token tile
     n = T * P
     gen = torch.Generator().manual_seed(451)
     x = (torch.randn(nb, n, d, generator=gen) * 3).to(F8).to(DEV)
@@ -140,6 +136,21 @@ def test_token_pass_alone():
     # a lo plane with code 4 is refused before any launch
     rc, launches, _, _ = run(x, CODE, ("Fh", "Fl", "Th", "Tl"))
     assert rc == -1 and launches == 0
+
+
+def test_token_pass_alone():
+    """infv_vqf_token_pass with code 4 (Fl, Tl NULL): Fh is the tokens as bf16 and Th its transpose -- the plane the bf16 pass
+    writes on x.bfloat16() -- nothing is written outside them, and the frame means equal infv_ltm_pool's on the fp8 tokens and on
+    x.float()."""
+    _token_pass_alone(nb=3, T=24, P=4, d=128)                         # 96 tokens: a second, half-filled 64-token tile
+
+
+@pytest.mark.parametrize("P,T,d,nb", [(4, 8, 64, 1),                  # n = 32: one tile, partial
+                                      (4, 24, 64, 2)],                # n = 96: a whole tile plus a partial one, two chunks
+                         ids=lambda v: str(v))
+def test_token_pass_alone_partial_tiles(P, T, d, nb):
+    """The same checks at the partial-tile shapes of tests/test_vc_token_pass_gpu.py."""
+    _token_pass_alone(nb=nb, T=T, P=P, d=d)
 
 
 def test_refusals_launch_nothing():

@@ -1,6 +1,7 @@
-"""The token pass alone, through ``infv_vqf_token_pass``: fp16 / bf16 frame tokens -> the split planes, their transposed copies and
-the frame means.  Everything is ``torch.equal``: the planes do not depend on tokens_per_frame, so the same call with
-tokens_per_frame = 4 is their reference; the frame means are ``infv_ltm_pool``'s bits at the token dtype and on ``tokens.float()``.
+"""The token pass alone, through ``infv_vqf_token_pass``: fp32 / fp16 / bf16 frame tokens -> the split planes, their transposed copies
+and the frame means.  Everything is ``torch.equal``: the planes do not depend on tokens_per_frame, so the same call with
+tokens_per_frame = 4 is their reference -- and, for fp32 and fp16 tokens, the split computed on the host (hi = bf16(x),
+lo = bf16(x - hi), round to nearest even); the frame means are ``infv_ltm_pool``'s bits at the token dtype and on ``tokens.float()``.
 
 A one-pass form WITH the means exists where a frame divides the pass's 64-token tile.  For the other frame sizes (12, 68, 196, 6) a
 per-frame kernel was built, passed every check below bit for bit on an MI355X and was then measured against pooling + this pass
@@ -19,13 +20,16 @@ from tests.conftest import record_parity
 pytestmark = pytest.mark.gpu
 UNSUPPORTED = -2
 PAD = 64                                            # sentinel elements on either side of every output
-CODES = {torch.float16: 3, torch.bfloat16: 1}
+CODES = {torch.float32: 0, torch.float16: 3, torch.bfloat16: 1}
 # (P, T, d, nb)
 CASES = [(12, 16, 64, 2),                           # frames straddle tiles
          (68, 16, 64, 1),                           # one full tile plus 4 rows
          (196, 16, 64, 2),                          # the real frame
          (196, 16, 128, 3),                         # slab and chunk strides
          (4, 16, 64, 2), (32, 4, 128, 2),           # P divides 64: planes and means in one launch
+         (4, 8, 64, 1),                             # n = 32: one tile, partial
+         (4, 24, 64, 2),                            # n = 96: a whole tile plus a partial one, two chunks
+         (32, 3, 128, 2),                           # n = 96: the partial tile holds exactly one frame, two column tiles
          (6, 32, 64, 1)]                            # no one-pass form: refused without a launch
 
 
@@ -35,15 +39,19 @@ def dev0():
 
 def tokens(P, T, d, nb, dtype, seed):
     """normal(0, 1) x 2^k, k per element from [-8, 8]; a few elements forced to +-0, the largest finite value, the smallest
-    subnormal and its negative -- of the dtype's own range."""
+    subnormal and its negative -- of the dtype's own range.  fp32: +-0 alone -- no subnormals and nothing beyond the bf16 range, so
+    both pieces of the split are exact round-to-nearest conversions of normal numbers on the host as on the device."""
     rng = np.random.default_rng(seed)
     n = T * P
     x = rng.standard_normal((nb, n, d)) * np.exp2(rng.integers(-8, 9, (nb, n, d)))
     t = torch.from_numpy(x).to(dtype)
-    fi = torch.finfo(dtype)
-    tiny = fi.smallest_normal * fi.eps              # the smallest subnormal: 2^-24 (fp16), 2^-133 (bf16)
-    edge = torch.tensor([0.0, -0.0, fi.max, tiny, -tiny, -fi.max], dtype=torch.float64).to(dtype)
-    assert float(edge[3]) > 0 and float(edge[3].double()) == tiny
+    if dtype == torch.float32:
+        edge = torch.tensor([0.0, -0.0], dtype=dtype)
+    else:
+        fi = torch.finfo(dtype)
+        tiny = fi.smallest_normal * fi.eps          # the smallest subnormal: 2^-24 (fp16), 2^-133 (bf16)
+        edge = torch.tensor([0.0, -0.0, fi.max, tiny, -tiny, -fi.max], dtype=torch.float64).to(dtype)
+        assert float(edge[3]) > 0 and float(edge[3].double()) == tiny
     flat = t.view(-1)
     flat[(torch.arange(edge.numel()) * 1031 + 7) % flat.numel()] = edge
     return t
@@ -106,7 +114,7 @@ def run_pass(lib, t, P, with_means):
     return rc, lib.infv_ltm_launch_count() - n0, planes, kbar
 
 
-@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float32], ids=["fp16", "bf16", "fp32"])
 @pytest.mark.parametrize("P,T,d,nb", CASES, ids=lambda v: str(v))
 def test_token_pass_planes_and_frame_means(P, T, d, nb, dtype):
     from infinite_video_amd import _lib
@@ -140,13 +148,19 @@ def test_token_pass_planes_and_frame_means(P, T, d, nb, dtype):
         assert torch.equal(planes[k].check(f"{tag} {k}"), ref[k].check(f"{tag} reference {k}")), f"{tag}: plane {k} differs"
     # (what the planes are: hi + lo is the token exactly, transposed copies are transposes)
     n = T * P
-    if dtype == torch.float16:
-        hi, lo = planes["Fh"].mid.view(nb, n, d).float(), planes["Fl"].mid.view(nb, n, d).float()
-        assert torch.equal(hi + lo, t.float())
+    if dtype == torch.bfloat16:
+        assert torch.equal(planes["Th"].mid.view(nb, d, n), t.transpose(1, 2))
+    else:
+        if dtype == torch.float16:
+            hi, lo = planes["Fh"].mid.view(nb, n, d).float(), planes["Fl"].mid.view(nb, n, d).float()
+            assert torch.equal(hi + lo, t.float())
+        # the split on the host: torch rounds float32 -> bfloat16 to nearest even, as the device's conversion does
+        ref_hi = host.float().bfloat16()
+        ref_lo = (host.float() - ref_hi.float()).bfloat16()
+        assert torch.equal(planes["Fh"].mid.view(nb, n, d).cpu(), ref_hi), f"{tag}: Fh differs from bf16(x) on the host"
+        assert torch.equal(planes["Fl"].mid.view(nb, n, d).cpu(), ref_lo), f"{tag}: Fl differs from bf16(x - bf16(x)) on the host"
         assert torch.equal(planes["Tl"].mid.view(nb, d, n), planes["Fl"].mid.view(nb, n, d).transpose(1, 2))
         assert torch.equal(planes["Th"].mid.view(nb, d, n), planes["Fh"].mid.view(nb, n, d).transpose(1, 2))
-    else:
-        assert torch.equal(planes["Th"].mid.view(nb, d, n), t.transpose(1, 2))
 
     eng = LTMEngine(32, 2, 64, d, P, 0.75, True, device=dev, fp16_tokens=True)
     if one_pass:

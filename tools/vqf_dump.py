@@ -10,8 +10,10 @@ The list (shapes: tests/golden/seam_cases.py's BASE and VQF_BASE, the frame Q-fo
 and texts (5, 0, 17) and ``encode_streams`` with blocks (5, 2) and frame_src [0, 1, 0, 0, 1], from fp32, fp16, bf16 and fp8 tokens, each
 on a default handle, on one created under INFV_VQF_SPLIT_CACHE_GB=0 and on one with set_precision(h, 1); ``encode_img_videos`` from fp16
 vision output with the vision LayerNorm and ids; ``encode_frames`` at 65 and 128 tokens per frame with bf16 output; ``encode_chunk``,
-``encode_video`` and ``infv_vqf_encode_videos``; every call with memories followed by one with new_video = 0 on the same memories.  The
+``encode_video`` and ``infv_vqf_encode_videos``; every call with memories followed by one with new_video = 0 on the same memories;
+``infv_vqf_token_pass`` with the frame means from each token dtype at (P, T, d, nb) = (4, 24, 64, 2), a whole tile plus a partial one.  The
 whole list runs twice on the same handles, the second time in reverse order: a handle sees growing, then non-growing calls."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -145,9 +147,29 @@ def child(path):
                         out[f"{key}/B{v}.{l}"], out[f"{key}/mass{v}.{l}"] = host(B), host(mass)
         return run
 
+    # ---- the token pass alone, with the frame means: 96 tokens a chunk, a whole 64-token tile plus a partial one
+    def pass_case(tag, dt):
+        def run():
+            P, T, d, nb = 4, 24, 64, 2
+            n = T * P
+            x = torch.from_numpy(np.random.default_rng(80).standard_normal((nb, n, d))).float().to(dtypes[dt]).to(dev)
+            names = {"bf16": ("Th",), "f8": ("Fh", "Th")}.get(dt, ("Fh", "Fl", "Th", "Tl"))
+            planes = {k: torch.zeros(nb * n * d, dtype=torch.bfloat16, device=dev) for k in names}
+            kbar = torch.zeros(nb * T * d, dtype=torch.float32, device=dev)
+            ptr = lambda k: C.c_void_p(planes[k].data_ptr()) if k in planes else None
+            key = f"{tag}/pass/{dt}"
+            with torch.cuda.device(dev):
+                _lib.check(counted(key, lambda: lib.infv_vqf_token_pass(
+                    C.c_void_p(x.data_ptr()), {"f32": 0, "bf16": 1, "f16": 3, "f8": 4}[dt], nb, n, d, P, ptr("Fh"), ptr("Fl"), ptr("Th"),
+                    ptr("Tl"), C.c_void_p(kbar.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))))
+            out[key + "/kbar"] = host(kbar)
+            for k, t in planes.items():
+                out[f"{key}/{k}"] = host(t)
+        return run
+
     def cases(tag):
         lst = [vc_case(tag, model, form, dt) for model in models for dt in dtypes for form in ("videos", "streams")]
-        lst += [img_case(tag), frames_case(tag, 65), frames_case(tag, 128)]
+        lst += [img_case(tag), frames_case(tag, 65), frames_case(tag, 128)] + [pass_case(tag, dt) for dt in dtypes]
         return lst + [vqf_case(tag, op) for op in ("chunk", "video", "videos")]
 
     for run in cases("forward") + cases("reverse")[::-1]:
