@@ -1,4 +1,4 @@
-// Shared by the C-ABI translation units (ltm_capi.hip, vqf_capi.hip): error reporting and device buffers.
+// Shared by the C-ABI translation units (ltm_capi.hip, ltm_consolidate.hip, vqf_capi.hip): error reporting and device buffers.
 #pragma once
 #include "knobs.h"
 #include <hip/hip_runtime.h>
@@ -48,16 +48,44 @@ struct DeviceBuf {
 // synchronised once, before the first is freed -- work in flight may still read the old allocation.  No host allocation: this runs
 // on the launch-bound per-chunk path.  *grew (optional): whether a buffer was reallocated, i.e. lost its contents.
 struct BufNeed { DeviceBuf& buf; size_t bytes; };
-inline hipError_t reserve_all(std::initializer_list<BufNeed> needs, bool* grew = nullptr) {
+// Sets of buffers (a ring, the rotating workspace sets) go in through add_each: a fixed-capacity list on the stack.
+struct BufList {
+    static constexpr int kCap = 48;
+    DeviceBuf* buf[kCap]; size_t bytes[kCap]; int n = 0;
+    BufList() {}
+    BufList& add(DeviceBuf& b, size_t need) { if (n < kCap) { buf[n] = &b; bytes[n] = need; } ++n; return *this; }   // (past kCap: reserve_all fails)
+    template <int K> BufList& add_each(DeviceBuf (&bs)[K], size_t need, int count = K) { for (int i = 0; i < count; ++i) add(bs[i], need); return *this; }
+};
+inline hipError_t reserve_all(const BufList& l, bool* grew = nullptr) {
+    if (l.n > BufList::kCap) return hipErrorInvalidValue;
     bool grow = false;
-    for (const BufNeed& n : needs) grow = grow || n.bytes > n.buf.bytes;
+    for (int i = 0; i < l.n; ++i) grow = grow || l.bytes[i] > l.buf[i]->bytes;
     if (grew) *grew = grow;
     if (!grow) return hipSuccess;
     hipError_t e = hipDeviceSynchronize();
-    for (const BufNeed& n : needs)
-        if (e == hipSuccess) e = n.buf.reserve(n.bytes);
+    for (int i = 0; i < l.n && e == hipSuccess; ++i) e = l.buf[i]->reserve(l.bytes[i]);
     return e;
 }
+inline hipError_t reserve_all(std::initializer_list<BufNeed> needs, bool* grew = nullptr) {
+    BufList l;
+    for (const BufNeed& n : needs) l.add(n.buf, n.bytes);
+    return reserve_all(l, grew);
+}
+
+// An event of a fused call that knows whether THIS call has recorded it: a wait for a record of an earlier call would order
+// nothing that stream order does not already (wait_on is then a no-op; wait_always is the plain wait).  clear() at the start of a call.
+struct CallEvent {
+    hipEvent_t ev = nullptr; bool recorded = false;
+    CallEvent() = default;
+    CallEvent(const CallEvent&) = delete;
+    CallEvent& operator=(const CallEvent&) = delete;
+    ~CallEvent() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t create() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+    hipError_t record(hipStream_t s) { recorded = true; return hipEventRecord(ev, s); }
+    hipError_t wait_on(hipStream_t s) const { return recorded ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+    hipError_t wait_always(hipStream_t s) const { return hipStreamWaitEvent(s, ev, 0); }
+    void clear() { recorded = false; }
+};
 
 template <class T>
 hipError_t upload(DeviceBuf& buf, const T* host, size_t n) {

@@ -22,6 +22,11 @@ inline const char* exp_env(const char* name) {
     return nullptr;
 #endif
 }
+// An integer / on-off knob of the experiments build with its shipped value (the call site keeps the caching `static`):
+//   static const int sub_env = exp_int("INFV_SUB_BATCH", 0);
+inline long exp_long(const char* name, long dflt) { const char* e = exp_env(name); return e ? std::atol(e) : dflt; }
+inline int exp_int(const char* name, int dflt) { const char* e = exp_env(name); return e ? std::atoi(e) : dflt; }
+inline bool exp_set(const char* name) { return exp_env(name) != nullptr; }
 // a frame-token element type as the library carries it: one of the infv_token_dtype codes or INFV_TOKENS_F8E4M3 (infv_ltm.h).  A plain
 // integer, not the enum: code 4 is declared beside the enum, outside the enumerators' range.
 typedef int tok_code;
@@ -39,3 +44,21 @@ namespace infv { extern std::atomic<long long> g_kernel_launches; }
         ::infv::g_kernel_launches.fetch_add(1, std::memory_order_relaxed);                                        \
         (kernelName)<<<(numBlocks), (numThreads), (memPerBlock), (streamId)>>>(__VA_ARGS__);                      \
     } while (0)
+
+// In-kernel stamp read-outs of the experiments build: a zeroed device buffer of `words` 64-bit stamps if the knob is set (else
+// dev stays null and the kernel writes none); read() is true on every `every`-th call, after it has synchronised `stream` and
+// copied the stamps to `host`.  The prints themselves stay with their launchers (tools/stamps*.sh parse them).
+namespace infv {
+struct StampBuf {
+    long long* dev = nullptr; int words; int calls = 0;
+    StampBuf(const char* knob, int words_) : words(words_) {
+        if (exp_set(knob) && hipMalloc(&dev, words * sizeof(long long)) == hipSuccess) (void)hipMemset(dev, 0, words * sizeof(long long));
+    }
+    bool read(int every, hipStream_t stream, long long* host) {
+        if (!dev || (++calls % every) != 0) return false;
+        (void)hipStreamSynchronize(stream);
+        (void)hipMemcpy(host, dev, words * sizeof(long long), hipMemcpyDeviceToHost);
+        return true;
+    }
+};
+}  // namespace infv

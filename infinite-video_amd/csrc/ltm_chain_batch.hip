@@ -1111,28 +1111,27 @@ hipError_t launch_alpha_rows2(const AlphaRows2Args& a_, hipStream_t stream) {
     // (one lane per four boxes: 16-byte stores of the weight rows)
     if (a_.N > 256 || a_.N % 4 || a_.tabw % 4 || (reinterpret_cast<unsigned long>(a_.alpha_ring) & 15) || a_.alpha_slot % 4) return hipErrorInvalidValue;
     AlphaRows2Args a = a_;
-    static const int prio = [] { const char* e = exp_env("INFV_ALPHA_PRIO"); return e ? atoi(e) : 0; }();
+    static const int prio = exp_int("INFV_ALPHA_PRIO", 0);
     a.prio = prio;
     // the register stage of the next unit: the table and the S'new tile fit two 16-byte vectors per thread, rows 16-byte aligned
-    static const bool force_direct = [] { const char* e = exp_env("INFV_ALPHA_DIRECT"); return e && atoi(e) != 0; }();   // (tests: the fallback staging)
+    static const bool force_direct = exp_int("INFV_ALPHA_DIRECT", 0) != 0;   // (tests: the fallback staging)
     a.regs_ok = !force_direct && a.N * (a.tabw / 4) <= 2 * kA2NT && a.rows * (kA2Q / 4) <= 2 * kA2NT && a.Q % 4 == 0 && a.snew_ld % 4 == 0 &&
                 a.snew_split_stride % 4 == 0 && (reinterpret_cast<unsigned long>(a.Snew) & 15) == 0;
     const size_t lds = (size_t)(((a.N * a.tabw + 3) & ~3) + kA2Q * kScPitch + (a.rows + 1) * (kA2Q + 1)) * sizeof(float);   // (+ a zero row behind the S'new tile)
     // two work units per workgroup (experiments build: INFV_ALPHA_UPW; 1 / 2 / 4 on one box: 14.1 / 13.8 / 15.1 ms per video): the next unit's loads fly behind the present one's arithmetic
-    static const int upw = [] { const char* e = exp_env("INFV_ALPHA_UPW"); const int v = e ? atoi(e) : 2; return v > 0 ? v : 1; }();
+    static const int upw_env = exp_int("INFV_ALPHA_UPW", 2);
+    const int upw = upw_env > 0 ? upw_env : 1;
     const long n_units = (long)a.n_steps * a.L * a.H * ((a.Q + kA2Q - 1) / kA2Q);
     const unsigned grid = (unsigned)((n_units + upw - 1) / upw);
     a.wg_stamps = exp_stamps_reserve(WG_ALPHA, (long)grid);
     a.dbg = nullptr;
 #ifdef INFV_EXPERIMENTS
     {   // INFV_ALPHA_STAMPS=1: phase time sums over all workgroups, printed every 64 launches
-        static long long* dbg = [] { long long* p = nullptr; if (exp_env("INFV_ALPHA_STAMPS")) { (void)hipMalloc(&p, 8 * sizeof(long long)); (void)hipMemset(p, 0, 8 * sizeof(long long)); } return p; }();
+        static StampBuf stamps("INFV_ALPHA_STAMPS", 8);
+        long long* const dbg = stamps.dev;
         a.dbg = dbg;
-        static int calls = 0;
-        if (dbg && (++calls % 64) == 0) {
-            long long hb[8];
-            (void)hipStreamSynchronize(stream);
-            (void)hipMemcpy(hb, dbg, sizeof(hb), hipMemcpyDeviceToHost);
+        long long hb[8];
+        if (stamps.read(64, stream, hb)) {
             (void)hipMemset(dbg, 0, 8 * sizeof(long long));
             if (hb[0] > 0 && hb[4] > 0)
                 fprintf(stderr, "[alpha stamps] units %lld workgroups %lld: per unit stage (sync + registers -> LDS, incl. waiting for the loads) %.2f us, issue of the next unit's loads %.2f us, arithmetic + stores %.2f us; per workgroup %.2f us\n",
@@ -1141,7 +1140,7 @@ hipError_t launch_alpha_rows2(const AlphaRows2Args& a_, hipStream_t stream) {
     }
 #endif
     // (experiments: INFV_ALPHA_LDS pads the workgroup's LDS -- who may share a CU with whom is decided by LDS and registers)
-    static const size_t lds_pad = [] { const char* e = exp_env("INFV_ALPHA_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
+    static const size_t lds_pad = (size_t)exp_long("INFV_ALPHA_LDS", 0);
     size_t lds_launch = lds;
     if (lds_pad > lds_launch && lds_pad <= 160 * 1024) {
         static bool attr = false;
@@ -1259,7 +1258,7 @@ static hipError_t chain_batch_attr() {
 // query reads one high for some SGPR counts (MI355X_MICROARCH.md, residency).
 static int chain_batch3_rpw(int rows, int Q);
 bool chain_batch3_shape_ok(int draw_mode, int points_ok, int rows, int S, int Q) {
-    static const bool want_v3 = [] { const char* e = exp_env("INFV_CHAIN_V1"); return !e || atoi(e) == 0; }();
+    static const bool want_v3 = exp_int("INFV_CHAIN_V1", 0) == 0;
     return want_v3 && draw_mode == 1 && points_ok && 2 * rows <= 64 * kB2Ld && S <= 512 && S % 4 == 0 && Q % 4 == 0 &&
            chain_batch3_rpw(rows, Q) > 0;
 }
@@ -1268,7 +1267,7 @@ bool chain_batch3_shape_ok(int draw_mode, int points_ok, int rows, int S, int Q)
 // whole CU by its registers -- and half the arrivals per exchange) when the loader's register tile holds 16 scores per new
 // row; INFV_CHAIN_RPW=1 (experiments build) selects 8-row tiles.
 static int chain_batch3_rpw(int rows, int Q) {
-    static const int want = [] { const char* e = exp_env("INFV_CHAIN_RPW"); return e ? atoi(e) : kDefRpw; }();
+    static const int want = exp_int("INFV_CHAIN_RPW", kDefRpw);
     if (want >= 2 && 4 * rows <= 64 * kB2Ld && Q > kBRows) return 2;
 #ifdef INFV_EXPERIMENTS
     return 1;
@@ -1289,7 +1288,7 @@ int chain_batch_blocks(int H, int Q, int L, int draw_mode, int points_ok, int ro
 
 static size_t chain_batch3_launch_lds(int N, int S, int rows, int tabw, int rpw) {
     // padding LDS keeps the workgroup's CU footprint what the stream layout of consolidate() was tuned for
-    static const int pad = [] { const char* e = exp_env("INFV_S_LDS"); return e ? atoi(e) : 0; }();
+    static const int pad = exp_int("INFV_S_LDS", 0);
     size_t lds = (size_t)batch3_smem(N, S, rows, tabw, rpw).total * sizeof(float);
     if ((size_t)pad > lds) lds = pad;
     return lds;

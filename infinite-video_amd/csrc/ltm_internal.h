@@ -1,4 +1,4 @@
-// Internal interface between the C ABI (ltm_capi.hip) and the gfx950 kernels (ltm_kernels.hip).
+// Internal interface between the C ABI (ltm_capi.hip, ltm_consolidate.hip) and the gfx950 kernels (ltm_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

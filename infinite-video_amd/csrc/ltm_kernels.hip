@@ -393,7 +393,7 @@ static int g_log_kind[1 << 12];                   // launch log: kind and record
 static long g_log_first[1 << 12], g_log_n[1 << 12];
 static int g_log_fill = 0;
 long long* exp_stamps_reserve(int kind, long n_wgs) {
-    static const bool want = exp_env("INFV_WG_STAMPS") != nullptr;
+    static const bool want = exp_set("INFV_WG_STAMPS");
     if (!want) return nullptr;
     if (!g_stamps) {
         if (hipMalloc(&g_stamps, kStampCap * 4 * sizeof(long long)) != hipSuccess) return nullptr;
@@ -456,18 +456,18 @@ static hipError_t launch_pool_rows2_t(const void* k, int n_chunks, int T, int P,
     unsigned grid = (unsigned)n_rows_total;
     if (max_wgs > 0 && grid > (unsigned)max_wgs) grid = (unsigned)max_wgs;
     const dim3 block(4 * slices * 64);
-    static const int prio = [] { const char* e = exp_env("INFV_POOL_PRIO"); return e ? atoi(e) : 0; }();
+    static const int prio = exp_int("INFV_POOL_PRIO", 0);
     PoolCallDesc one;                                                         // rows + planes of ONE sub-batch: the call-long kernel without a completion count
     if (call == nullptr && planes != nullptr && (long)grid == n_rows_total && n_rows_total * (long)d * 2 < (1l << 31)) {   // (a grid-stride grid writes rows only)
         memset(&one, 0, sizeof(one));
         one.sub = n_chunks; one.n_chunks = n_chunks; one.R_all = R;
         for (int i = 0; i < 3; ++i) one.plane[i] = planes[i];
-        { static const int sm = [] { const char* e = exp_env("INFV_POOL_STORE"); return e ? atoi(e) : 0; }(); one.store_mode = sm; }
+        { static const int sm = exp_int("INFV_POOL_STORE", 0); one.store_mode = sm; }
         call = &one; pc = one;
         if (planes_done != nullptr) *planes_done = true;
     }
     long long* stamps = exp_stamps_reserve(WG_POOL, grid);
-    static const int want_tid = [] { const char* e = exp_env("INFV_POOL_TID"); return e ? atoi(e) : kPoolTidAddr; }();
+    static const int want_tid = exp_int("INFV_POOL_TID", kPoolTidAddr);
     const int tid_addr = (want_tid && d4 % 64 == 0) ? 1 : 0;               // every lane of every slice holds a column
 #ifdef INFV_EXPERIMENTS
     if (call == nullptr && u >= 32 && P % 32 == 0) { INFV_LAUNCH((PoolRows2Fn<32, Tok, false>::get()), dim3(grid), block, lds, stream, k, (long)T * P * d4, P, d4, slices, op, n_rows_total, R, stamps, prio, tid_addr, pc); return hipGetLastError(); }
@@ -872,7 +872,7 @@ static hipError_t launch_gemm(const float* A, int M, int K, const WSegs& segs,
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    static const bool want_lw = [] { const char* e = exp_env("INFV_GEMM_LW"); return !e || atoi(e) != 0; }();   // default on
+    static const bool want_lw = exp_int("INFV_GEMM_LW", 1) != 0;   // default on
     if (want_lw && M >= 1024 && lds_pad <= 0 && k_per_split == 24 * kBK) {
         static bool attr_lw = false;
         if (!attr_lw) {
@@ -891,9 +891,9 @@ static hipError_t launch_gemm(const float* A, int M, int K, const WSegs& segs,
             // Column slices launched one after the other on the stream (experiment INFV_GEMM_SLICES): a launch whose workgroups do not
             // all find a seat leaves a backlog at the dispatcher, and while it stands the pooling stream's workgroups are not
             // dispatched either (tools/residency.py timelines); slices of <= ~200 workgroups never queue.
-            static const int slices = [] { const char* e = exp_env("INFV_GEMM_SLICES"); return e ? atoi(e) : 1; }();
+            static const int slices = exp_int("INFV_GEMM_SLICES", 1);
             // (experiment INFV_GEMM_LW_LDS: total dynamic LDS of the launch; 90 KB keeps pooling workgroups off the GEMM's CUs)
-            static const size_t lw_lds = [] { const char* e = exp_env("INFV_GEMM_LW_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
+            static const size_t lw_lds = (size_t)exp_long("INFV_GEMM_LW_LDS", 0);
             size_t lds_bytes = 2 * (128 + 128) * kLdsStride * sizeof(float);
             if (lw_lds > lds_bytes && lw_lds <= 96 * 1024) lds_bytes = lw_lds;
             const int gy = n_cols / 128;
@@ -1500,11 +1500,11 @@ size_t attend_small_lds_bytes(int N) {
 
 // query rows per attend workgroup: 4 (one row per wave) where the small kernel applies, else one 16-row MFMA tile
 static bool attend_small_wanted() {
-    static const bool want_small = [] { const char* e = exp_env("INFV_ATTEND_SMALL"); return !e || atoi(e) != 0; }();
+    static const bool want_small = exp_int("INFV_ATTEND_SMALL", 1) != 0;
     return want_small;
 }
 static int attend_tile_rows(int N) {
-    static const int rt_env = [] { const char* e = exp_env("INFV_ATTEND_RT"); return e ? atoi(e) : 4; }();
+    static const int rt_env = exp_int("INFV_ATTEND_RT", 4);
     return (attend_small_wanted() && N <= 256 && N % 16 == 0 && rt_env == 4) ? 4 : kQTile;
 }
 int attend_parts(int Q, int H, int N) { const int rt = attend_tile_rows(N); return H * ((Q + rt - 1) / rt); }

@@ -616,7 +616,7 @@ hipError_t launch_uc(const UcArgs& a, hipStream_t stream) {
     if (a.n_chunks <= 0) return hipSuccess;
     if (!uc_supported(a.N, a.d, a.dm, a.tabw, a.op.rows)) return hipErrorInvalidValue;
     const int blocks = a.L * (a.d / kUcCols + a.dm / kUcCols);
-    static const bool want_fast = [] { const char* e = exp_env("INFV_UC_FAST"); return !e || atoi(e) != 0; }();
+    static const bool want_fast = exp_int("INFV_UC_FAST", 1) != 0;
     if (want_fast && uc_fast_supported(a.N, a.Q, a.tabw)) {
         // 16-column V' slices (32-column B slices): twice the read-out workgroups of round 1's 32-column form with half the
         // MFMA work each, 73 KB of LDS (the 32-column instantiation measured 10.0 against 7.8 ms per video and is gone;
@@ -625,8 +625,8 @@ hipError_t launch_uc(const UcArgs& a, hipStream_t stream) {
         b.v16 = 1;
         const int nblk = a.L * (a.d / kUcCols + a.dm / 16);
         b.wg_stamps = exp_stamps_reserve(WG_UC, nblk);
-        static const int prio = [] { const char* e = exp_env("INFV_UC_PRIO"); return e ? atoi(e) : 0; }();
-        static const int skipm = [] { const char* e = exp_env("INFV_UC_SKIPLOADS"); return e ? atoi(e) : 0; }();   // timing experiments: garbage results
+        static const int prio = exp_int("INFV_UC_PRIO", 0);
+        static const int skipm = exp_int("INFV_UC_SKIPLOADS", 0);   // timing experiments: garbage results
         b.prio = prio | (skipm << 4);
         const size_t vfl = (size_t)2 * a.N * 16 + 8 * 64 * 4 + kUcQ * (a.N + 4), bfl = (size_t)2 * a.N * 32;
         const size_t lds_floats = vfl > bfl ? vfl : bfl;

@@ -328,7 +328,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // the wide tiles need whole 384 x 256 tiles and enough of them to fill the chip
 bool split_gemm_wide_applies(const SplitGemm& g) {
-    static const int mode = [] { const char* e = exp_env("INFV_SPLIT_GEMM_WIDE"); return e ? atoi(e) : 1; }();
+    static const int mode = exp_int("INFV_SPLIT_GEMM_WIDE", 1);
     if (!mode) return false;
     if (g.M % kWRowsA || g.N % kWRowsB) return false;               // whole tiles only (unconditional loads and stores)
     if (g.wide) return true;
@@ -391,7 +391,7 @@ hipError_t launch_split_gemm(const SplitGemm& g, hipStream_t stream, int lds_pad
             return hipGetLastError();
         };
 #ifdef INFV_EXPERIMENTS
-        static const int probe = [] { const char* e = exp_env("INFV_WIDE_MODE"); return e ? atoi(e) : 0; }();
+        static const int probe = exp_int("INFV_WIDE_MODE", 0);
         if (probe == 1 && g.B_lo) return go(split_gemm_wide_kernel<1, 3>);
         if (probe == 2 && g.B_lo) return go(split_gemm_wide_kernel<2, 3>);
 #endif
@@ -741,7 +741,7 @@ hipError_t launch_gemm_x6(const SplitGemm6& g, hipStream_t stream) {
     SplitGemm6 gg = g;
     gg.wg_stamps = exp_stamps_reserve(WG_GEMM, (long)grid.x * grid.y);
     // (experiment INFV_X6_LDS: total dynamic LDS; above 80 KB only one of these workgroups fits a CU)
-    static const size_t lds_x = [] { const char* e = exp_env("INFV_X6_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
+    static const size_t lds_x = (size_t)exp_long("INFV_X6_LDS", 0);
     INFV_LAUNCH(gemm_x6_kernel, grid, dim3(256), lds_x > (size_t)kXLds && lds_x <= 96 * 1024 ? lds_x : (size_t)kXLds, stream, gg);
     return hipGetLastError();
 }

@@ -725,7 +725,7 @@ static int pick_short_nb(const infv_vqf_s* h, int C, int n_tokens) {
         }
     }
     {
-        static const int nb_env = [] { const char* e = exp_env("INFV_VQF_NB"); return e ? atoi(e) : 0; }();   // (sweeps)
+        static const int nb_env = exp_int("INFV_VQF_NB", 0);   // (sweeps)
         if (nb_env > 0) NB = nb_env < C ? nb_env : C;
     }
     return NB;

@@ -130,7 +130,7 @@ def uc_supported(pt, ps) -> bool:                   # ltm_uc.hip
             pt.dm % 64 == 0 and ps.tabw % 4 == 0 and uc_lds_bytes(pt.N, ps.tabw, ps.rows_max) <= 160 * 1024)
 
 
-def fast_path(pt, ps) -> bool:                      # ltm_capi.hip, consolidate_impl: the gate in front of the fused chain
+def fast_path(pt, ps) -> bool:                      # ltm_consolidate.hip, consolidate_impl: the gate in front of the fused chain
     return (not ps.dense and chain_supported(pt, ps) and (pt.L * pt.H * pt.Q) % 128 == 0 and (pt.L * pt.dm) % 128 == 0 and
             uc_supported(pt, ps) and pt.Q <= 256)         # (Q <= 256: qtilde_supported, the fused chain's pre-multiplied queries)
 

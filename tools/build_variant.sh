@@ -4,7 +4,5 @@
 set -e
 name=$1; shift
 cd "$(dirname "$0")/.."
-src="ltm_kernels ltm_chain ltm_chain_batch ltm_uc ltm_dense ltm_psi ltm_capi vqf_kernels split_gemm vqf_capi"
-files=""; for s in $src; do files="$files infinite-video_amd/csrc/$s.hip"; done
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -I include -DINFV_EXPERIMENTS "$@" -o infinite-video_amd/libinfv_ltm_v_$name.so $files
+/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -I include -DINFV_EXPERIMENTS "$@" -o infinite-video_amd/libinfv_ltm_v_$name.so infinite-video_amd/csrc/*.hip
 echo "built infinite-video_amd/libinfv_ltm_v_$name.so"
