@@ -371,8 +371,9 @@ int infv_vqf_encode_frames(infv_vqf_handle h, int32_t F, const void* vision, int
  *                three bf16 MFMA products in the order lo.hi, hi.lo, hi.hi, fp32 accumulation (the scheme of the short-term
  *                attention's contractions).  fp32-class: about 1e-5 of a sum of |x w| at K = 3072.
  *   2            fp16: activation and weight rounded to nearest-even fp16, as `.half()` does (beyond 65504: inf, as under autocast);
- *                one f16 MFMA product, fp32 accumulation.  Bias, GELU, residual and LayerNorm stay fp32.  What the f16 MFMA does
- *                with SUBNORMAL fp16 operands (magnitudes below 2^-14) on gfx950 is not measured.
+ *                one f16 MFMA product, fp32 accumulation.  Bias, GELU, residual and LayerNorm stay fp32.  The f16 MFMA KEEPS
+ *                subnormal fp16 operands (magnitudes below 2^-14) on gfx950: 2^-20 x 2^10 through this mode gives 2^-10, not 0
+ *                (tests/test_attention_precision_gpu.py, one MI355X); whether subnormal operands cost it time is not measured.
  * The mode governs the eight linears per layer on the query rows -- the stacked self q/k/v, the self output, the cross query, the
  * cross output, q_ffn_in and q_ffn_out (with its 2-byte cast epilogue) -- and nothing else: the short-term attention and the token
  * pass run as before, a linear stays two launches (GEMM + epilogue), the activations are split / rounded between the registers and
@@ -399,6 +400,56 @@ int infv_vqf_set_linear_precision(infv_vqf_handle h, int32_t mode);
  * n_out no positive multiple of 64, K or n_lin * n_out above 4096 (INFV_ERR_UNSUPPORTED). */
 int infv_vqf_linear(infv_vqf_handle h, const float* x, int32_t M, int32_t K, const infv_linear* lin, int32_t n_lin, int32_t n_out,
                     int32_t act, const float* residual, int32_t res_rows, const infv_layernorm* ln, float* y, void* stream);
+
+/* The arithmetic of the CROSS-ATTENTION of infv_vqf_encode_frames (additive: the ABI version stays 6).  mode:
+ *   0 (default)  the split-bf16 (or, with infv_vqf_set_precision(h, 1), fp32) contractions: the path, the launches and the bits of a
+ *                handle that never called this.
+ *   1            fp16 operands, fp32 accumulation, one f16 MFMA product per contraction -- what the reference's fp16 autocast runs.
+ *                Per frame and head (dh = 64), with q the fp32 output of the cross-query linear (in the handle's linear precision):
+ *                  x^  = fp16(LN(x)) with the vision LayerNorm on (its fp32 arithmetic, from the same statistics launch), else
+ *                        fp16(float(x)); round to nearest even AFTER widening, so fp16, bf16 and fp8 sources give the bits of the
+ *                        run on the same values as fp32; rows n_tokens .. n_pad - 1 (n_pad = ceil(n_tokens / 64) * 64) exact zeros
+ *                  q~' = fp16(32 * sum_c fp16(q[c]) * fp16(Wk[c][:]))          32 = 2^8 / sqrt(64); the key bias is dropped, as in mode 0
+ *                  s   = 2^-8 * sum_e q~'[e] * x^[j][e];  p = softmax over the first n_tokens columns in fp32, maximum subtracted
+ *                  p'  = fp16(2^10 * p), exact zeros in the pad columns
+ *                  o'  = fp16(2^-10 * sum_j p'[j] * x^[j][:])
+ *                  ctx = sum_e o'[e] * fp16(Wv[c][e]) + bv[c]                   fp32 bias, added once
+ *                The two powers of two keep q~' and p' out of fp16's subnormal range (an unscaled q~ of the test models has about
+ *                1 % of its entries below 2^-14, a peaked row most of its p), so the result does not rest on how the MFMA treats
+ *                subnormal operands.  Beyond fp16's range a value becomes inf, as `.half()` gives: |q~| >= 256, or a token above
+ *                65504 in magnitude without the LayerNorm; nothing guards against it.  The score matrix never reaches memory, the
+ *                context product has no split-K; a frame's tiles and summation orders depend on n_tokens alone, so a frame's bits
+ *                do not depend on F or on the other frames.  n_tokens above 512 is INFV_ERR_UNSUPPORTED in this mode;
+ *                infv_vqf_set_precision and INFV_VQF_FP32, which choose between the two forms of mode 0, are not read in it.
+ *                Bias, merge, output dense, LayerNorms and the query-side linears are unchanged.
+ * One pass over the vision output writes the fp16 plane [F][n_pad][enc_width] and its transposed copy (4 bytes per padded token
+ * element, written once per call and shared by all its cross layers; 461 MB at 256 x 257 x 1408); a sub-batch of up to 256
+ * frames keeps its q~' and o' rows as fp16 (2 x 277 MB at 12 heads x 32 queries x 1408).  All four are workspaces of the handle, grown
+ * on demand like the split-bf16 planes of mode 0 and NOT released after the call: about 1 GB at that shape until infv_vqf_destroy.  The key and value weights arrive as fp32; their fp16 planes
+ * (Wk per head transposed [H][enc_width][64], Wv as it lies) are made on the device and kept in the cache of the linears' planes, by
+ * its rules: keyed on the weight pointers while the NON-ZERO weights epoch stands, dropped by a change of the epoch, of this mode or
+ * of the linear precision, rebuilt in every call with epoch 0 (two more launches per cross layer).  Cost for the model's image
+ * Q-former (6 cross layers of 768 x 1408): 26 MB.
+ * Independent of infv_vqf_set_linear_precision: all six combinations run.  While the mode is not 0, every other entry point that
+ * takes the handle -- the list of infv_vqf_set_linear_precision -- returns INFV_ERR_UNSUPPORTED before any launch or workspace change,
+ * naming this function; infv_vqf_set_context_tap works in both modes.  A null handle or a mode outside 0..1 is INFV_ERR_INVALID and
+ * leaves the setting as it was. */
+int infv_vqf_set_attention_precision(infv_vqf_handle h, int32_t mode);
+
+/* One cross-attention of infv_vqf_encode_frames alone, under the handle's attention precision (exported for tests and measurements,
+ * as infv_vqf_linear and infv_vqf_token_pass are): the vision statistics and the token pass of that call, then one layer's attention.
+ *   vision, token_dtype, n_tokens, ln   as in infv_vqf_encode_frames
+ *   xq     device fp32 [F][n_query][hidden]: the cross query (bias applied), 16-byte aligned
+ *   key, value   the layer's linears (HOST structs, device pointers; key->b is not read, value->b may be NULL)
+ *   ctx    device fp32 [F][n_query][hidden]: the context, value bias included, before the output dense -- what the context tap copies
+ * Mode 0 issues the launches of the default path (its bits: the context tap of the same layer), mode 1 the fp16 ones.
+ * Refused before any launch or memory change (INFV_ERR_INVALID unless noted): a null h, key, value or weight, or (F > 0) vision, xq or
+ * ctx; F < 0 (F == 0 returns INFV_OK); an unknown token dtype; a pointer that is not 16-byte aligned; n_tokens < 1; gamma without
+ * beta; fp8 tokens with the LayerNorm, enc_width no multiple of 64, n_tokens % 32 != 0 on the fp32 contractions, n_tokens > 512 in
+ * mode 1 (INFV_ERR_UNSUPPORTED). */
+int infv_vqf_frame_cross_attention(infv_vqf_handle h, int32_t F, const void* vision, int32_t token_dtype, int32_t n_tokens,
+                                   const infv_vqf_vision_ln* ln /* NULL or gamma NULL: off */, const float* xq, const infv_linear* key,
+                                   const infv_linear* value, float* ctx, void* stream);
 
 /* A tap for tests (exported as infv_vqf_self_attention is): the NEXT infv_vqf_encode_frames call on h also copies the cross-attention
  * context of encoder layer `layer` (Qformer.py:303-304: softmax(q k^T / sqrt(dh)) v with the value bias, before the output dense),

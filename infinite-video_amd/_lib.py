@@ -227,6 +227,9 @@ _SIGNATURES = {
     "infv_vqf_set_linear_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "infv_vqf_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Linear), C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p, C.c_int32, C.POINTER(LayerNorm), C.c_void_p, C.c_void_p]),
+    "infv_vqf_set_attention_precision": (C.c_int, [C.c_void_p, C.c_int32]),
+    "infv_vqf_frame_cross_attention": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(VqfVisionLn), C.c_void_p,
+                                                 C.POINTER(Linear), C.POINTER(Linear), C.c_void_p, C.c_void_p]),
     "infv_vqf_set_context_tap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "infv_vqf_layernorm_tokens": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                             C.c_void_p]),

@@ -1,7 +1,8 @@
 // The token side of the split-bf16 contractions (split_gemm.hip) for gfx950: what stands between the frame tokens as the producer
 // stores them -- fp32, bf16, fp16 or fp8 e4m3, with or without the vision LayerNorm -- and the bf16 hi / lo planes the GEMMs read.
 //   the token pass        F [n][d] -> F_hi / F_lo [n][d], FT_hi / FT_lo [d][n] and the frame means, 64 x 64 tiles through LDS;
-//                         plain, with the LayerNorm applied on load, and padded (frames of 257 tokens)
+//                         plain, with the LayerNorm applied on load, and padded (frames of 257 tokens); the padded stages with
+//                         another output policy also write the fp16 plane and its transpose for attention_f16.hip
 //   the upcasts           tokens -> an fp32 copy, where the split path does not apply
 //   the LayerNorm pieces  token_ln_stats_kernel, ln_tokens_kernel
 //   the row softmax       fp32 scores -> split bf16 P_hi / P_lo, whole rows and padded rows
@@ -24,6 +25,23 @@ typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
 // ------------------------------------------------------------------------------------------------------
 typedef float TokenTile[64][65];
 
+// What the stages store from an fp32 tile value: the element type of the planes and the conversion.  SplitBf16 (the default of
+// every stage) is the split-bf16 contractions' hi = bf16(x), lo = bf16(x - hi); RoundF16 is the fp16 attention's single plane,
+// fp16(x) to nearest even (beyond 65504: inf), which has no lo piece.
+struct SplitBf16 {
+    typedef __bf16 elem;
+    static constexpr bool kHasLo = true;
+    static __device__ __forceinline__ void cvt(float x, __bf16& hi, __bf16& lo) { split2(x, hi, lo); }
+};
+struct RoundF16 {
+    typedef _Float16 elem;
+    static constexpr bool kHasLo = false;
+    static __device__ __forceinline__ void cvt(float x, _Float16& hi, _Float16& lo) { hi = (_Float16)x; lo = (_Float16)0.f; }
+};
+__device__ inline unsigned pack2(_Float16 a, _Float16 b) {
+    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
+}
+
 // Fill stage, 4 columns per thread: load the rows r0 + r < n of the tile at (r0, c0) of chunk blockIdx.z from the source F
 // (n rows a chunk), widen, apply the LayerNorm (LN: stats [chunks * n] addresses the launch's first chunk), split, store
 // F_hi / F_lo (`ld` rows a chunk), fill the tile.  Rows at or beyond n are zeros in the tile.  The source is read inside ONE token
@@ -33,18 +51,20 @@ typedef float TokenTile[64][65];
 // touches the next frame's first rows or the bytes behind the buffer -- the row test predicates the load alone.  Whether a tile is
 // the partial one is uniform over the workgroup (blockIdx.x).  Fl == nullptr (bf16 / fp8 tokens without LayerNorm: the value is its
 // own hi piece, lo is exactly 0): the lo plane is not written.
-template <class Tok, bool LN, bool PAD>
+template <class Tok, bool LN, bool PAD, class Out = SplitBf16>
 __device__ __forceinline__ void tile_fill4(TokenTile& tile, const void* __restrict__ F, int n, int ld, int d,
                                            const float2* __restrict__ stats, const float* __restrict__ gamma,
-                                           const float* __restrict__ beta, __bf16* __restrict__ Fh, __bf16* __restrict__ Fl) {
+                                           const float* __restrict__ beta, typename Out::elem* __restrict__ Fh,
+                                           typename Out::elem* __restrict__ Fl) {
     typedef typename Tok::vec tvec;
+    typedef typename Out::elem oelem;
     const int tid = threadIdx.x;
     const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
     const long cin = (long)blockIdx.z * n * d, cout = (long)blockIdx.z * ld * d;     // the chunk's first element in F, in the planes
     const tvec* src = reinterpret_cast<const tvec*>(F);
     // (the compile-time halves of the two store rules)
     auto stored = [&](int r) { if constexpr (PAD) return true; else return r0 + r < n; };
-    auto has_lo = [&](const __bf16* lo) { if constexpr (PAD) return lo != nullptr; else return true; };
+    auto has_lo = [&](const oelem* lo) { if constexpr (!Out::kHasLo) return false; else if constexpr (PAD) return lo != nullptr; else return true; };
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const int e = tid + 256 * p;                 // 1024 groups of 4 columns
@@ -56,9 +76,9 @@ __device__ __forceinline__ void tile_fill4(TokenTile& tile, const void* __restri
                 v = token_ln4(v, stats[(long)blockIdx.z * n + r0 + r], *reinterpret_cast<const floatx4*>(gamma + c0 + c4),
                               *reinterpret_cast<const floatx4*>(beta + c0 + c4));
         }
-        __bf16 h[4], l[4];
+        oelem h[4], l[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { split2(v[k], h[k], l[k]); tile[r][c4 + k] = v[k]; }
+        for (int k = 0; k < 4; ++k) { Out::cvt(v[k], h[k], l[k]); tile[r][c4 + k] = v[k]; }
         if (stored(r)) {
             const long o = cout + (long)(r0 + r) * d + c0 + c4;
             *reinterpret_cast<uint2*>(Fh + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
@@ -74,9 +94,10 @@ __device__ __forceinline__ void tile_fill4(TokenTile& tile, const void* __restri
 // groups at banks (r + 8 j + k) % 32 and reads 4 columns x 8 row groups at (8 i + k + c) % 32 -- 16 distinct banks, each twice: the
 // 2-way pattern of the 4-wide fp32 pass in both directions (not measured with the conflict counter; the pass is bound by its
 // global traffic).
-template <int TPT, bool LO, bool PAD>
-__device__ __forceinline__ void tile_to_planes(const TokenTile& tile, long cb, int n, int ld, __bf16* __restrict__ Th,
-                                               __bf16* __restrict__ Tl) {
+template <int TPT, bool LO, bool PAD, class Out = SplitBf16>
+__device__ __forceinline__ void tile_to_planes(const TokenTile& tile, long cb, int n, int ld, typename Out::elem* __restrict__ Th,
+                                               typename Out::elem* __restrict__ Tl) {
+    static_assert(!LO || Out::kHasLo, "no lo plane of this element type");
     static_assert(TPT == 4 || TPT == 8, "8- or 16-byte stores");
     constexpr int SH = TPT == 4 ? 4 : 3;             // 64 / TPT = 1 << SH threads along the tokens of one column
     const int tid = threadIdx.x;
@@ -88,9 +109,9 @@ __device__ __forceinline__ void tile_to_planes(const TokenTile& tile, long cb, i
         const int e = tid + 256 * p;
         const int c = e >> SH, rt = (e & ((1 << SH) - 1)) * TPT;
         if (stored(rt)) {
-            __bf16 h[TPT], l[TPT];
+            typename Out::elem h[TPT], l[TPT];
 #pragma unroll
-            for (int k = 0; k < TPT; ++k) split2(tile[rt + k][c], h[k], l[k]);
+            for (int k = 0; k < TPT; ++k) Out::cvt(tile[rt + k][c], h[k], l[k]);
             const long o = cb + (long)(c0 + c) * ld + r0 + rt;
             if constexpr (TPT == 4) {
                 *reinterpret_cast<uint2*>(Th + o) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
@@ -497,6 +518,46 @@ hipError_t launch_token_pass_pad(const void* F, tok_code tok, int nb, int n, int
         }
         if constexpr (kTokHasLn<Tok>) {
             INFV_LAUNCH((token_pass_pad_kernel<Tok, true>), grid, dim3(256), 0, stream, F, n, n_pad, d, st, gamma, beta, Fh, Fl, Th, Tl);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    });
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The fp16 form of the padded pass (infv_vqf_set_attention_precision(h, 1); the consumer is attention_f16.hip): the PAD stages with
+// RoundF16 in place of the split -- the same fill (a token type's widen(), token_ln4() where the LayerNorm is on, exactly n rows
+// of a frame read), ONE rounding of the fp32 tile value to fp16 on the way out, so every source type gives the bits of its values
+// passed as fp32.  Writes X [.][n_pad][d] and XT [.][d][n_pad], rows at or beyond n exact zeros.  n % 64 == 0 comes here too
+// (n_pad == n).
+// ------------------------------------------------------------------------------------------------------
+template <class Tok, bool LN>
+__global__ __launch_bounds__(256) void token_pass_f16_kernel(const void* __restrict__ F, int n, int n_pad, int d,
+                                                             const float2* __restrict__ stats, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, _Float16* __restrict__ X,
+                                                             _Float16* __restrict__ XT) {
+    __shared__ TokenTile tile;
+    tile_fill4<Tok, LN, true, RoundF16>(tile, F, n, n_pad, d, stats, gamma, beta, X, nullptr);
+    __syncthreads();
+    tile_to_planes<8, false, true, RoundF16>(tile, (long)blockIdx.z * n_pad * d, n, n_pad, XT, nullptr);
+}
+
+hipError_t launch_token_pass_f16(const void* F, tok_code tok, int nb, int n, int n_pad, int d, const void* stats, const float* gamma,
+                                 const float* beta, void* X_, void* XT_, hipStream_t stream) {
+    if (nb <= 0) return hipSuccess;
+    if (n < 1 || n_pad % 64 || n_pad < n || n_pad - n >= 64 || d < 64 || d % 64 || nb > 32768 || !X_ || !XT_) return hipErrorInvalidValue;
+    if (stats && (!gamma || !beta || tok == INFV_TOKENS_F8E4M3)) return hipErrorInvalidValue;
+    const dim3 grid(n_pad / 64, d / 64, nb);
+    const float2* st = static_cast<const float2*>(stats);
+    _Float16 *X = static_cast<_Float16*>(X_), *XT = static_cast<_Float16*>(XT_);
+    return with_token_type(tok, [&](auto t) {
+        using Tok = decltype(t);
+        if (!st) {
+            INFV_LAUNCH((token_pass_f16_kernel<Tok, false>), grid, dim3(256), 0, stream, F, n, n_pad, d, st, gamma, beta, X, XT);
+            return hipGetLastError();
+        }
+        if constexpr (kTokHasLn<Tok>) {
+            INFV_LAUNCH((token_pass_f16_kernel<Tok, true>), grid, dim3(256), 0, stream, F, n, n_pad, d, st, gamma, beta, X, XT);
             return hipGetLastError();
         }
         return hipErrorInvalidValue;

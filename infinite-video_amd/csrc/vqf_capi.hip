@@ -18,6 +18,13 @@ struct LinPlanes {
     infv::DeviceBuf hi, lo;
 };
 
+// The fp16 planes of one cross layer's key and value weights (infv_vqf_set_attention_precision(h, 1)): kT [H][d][64] = Wk per head,
+// transposed; v16 [hidden][d] = Wv as it lies
+struct AttnPlanes {
+    const float* wk = nullptr; const float* wv = nullptr; int H = 0, d = 0;
+    infv::DeviceBuf kT, v16;
+};
+
 struct infv_vqf_s {
     infv_vqf_config cfg;
     int dev = 0;
@@ -55,6 +62,13 @@ struct infv_vqf_s {
     std::vector<std::unique_ptr<LinPlanes>> lp;
     unsigned long long lp_epoch = 0;
     LinPlanes lp_scratch;
+    // infv_vqf_set_attention_precision: the arithmetic of the cross-attention of infv_vqf_encode_frames.  The key / value weight
+    // planes of mode 1 live by the rules of the linears' planes (lp_epoch); aX / aXT are a call's fp16 token planes, aQt / aO the
+    // fp16 pre-multiplied queries and context rows of one sub-batch
+    int attn_mode = 0;
+    std::vector<std::unique_ptr<AttnPlanes>> ap;
+    AttnPlanes ap_scratch;
+    DeviceBuf aX, aXT, aQt, aO;
     ~infv_vqf_s() {
         if (side) (void)hipStreamSynchronize(side);           // (a stream of the process-wide set: not destroyed here)
         if (ev_main) (void)hipEventDestroy(ev_main);
@@ -85,10 +99,15 @@ int check_layer_cfg(const infv_vqf_config& c) {       // what the fused per-laye
     return INFV_OK;
 }
 
-// Every entry point but infv_vqf_encode_frames (and infv_vqf_linear) while a reduced linear precision is set: their query rows feed
-// the memories' Gibbs draw, and reduced products never feed the scores of the draw (split_gemm.hip)
+// Every entry point but infv_vqf_encode_frames (and infv_vqf_linear, infv_vqf_frame_cross_attention) while a reduced linear precision
+// or the fp16 attention precision is set: their query rows feed the memories' Gibbs draw, and reduced products never feed the scores
+// of the draw (split_gemm.hip); the fp16 attention exists for the frame call alone
 int refuse_reduced(const infv_vqf_s* h, const char* name) {
-    if (h->lin_mode == 0) return INFV_OK;
+    if (h->lin_mode == 0 && h->attn_mode == 0) return INFV_OK;
+    if (h->lin_mode == 0)
+        return fail(INFV_ERR_UNSUPPORTED, "%s: the handle's attention precision is %d, which only infv_vqf_encode_frames and "
+                                          "infv_vqf_frame_cross_attention run (infv_vqf_set_attention_precision(h, 0) selects the "
+                                          "split-bf16 attention again)", name, h->attn_mode);
     return fail(INFV_ERR_UNSUPPORTED, "%s: the handle's linear precision is %d, which only infv_vqf_encode_frames runs "
                                       "(infv_vqf_set_linear_precision(h, 0) selects fp32 again)", name, h->lin_mode);
 }
@@ -108,9 +127,42 @@ struct LinearCall {
 
 // Drops the cached weight planes (work in flight may still read them: the device is synchronised first)
 int drop_linear_planes(infv_vqf_s* h) {
-    if (h->lp.empty()) return INFV_OK;
+    if (h->lp.empty() && h->ap.empty()) return INFV_OK;
     HIP_TRY(hipDeviceSynchronize());
     h->lp.clear();
+    h->ap.clear();
+    return INFV_OK;
+}
+
+// The fp16 planes of a cross layer's key and value weights, cached as the linears' planes are: keyed on (weight pointers, shape)
+// while the non-zero weights epoch stands; epoch 0 rebuilds them into one scratch pair in every call.
+int attn_planes(infv_vqf_s* h, const infv_linear* key, const infv_linear* value, const AttnPlanes** out, hipStream_t stream) {
+    const int H = h->cfg.n_heads, d = h->cfg.enc_width;
+    AttnPlanes* p = nullptr;
+    if (h->epoch == 0) {
+        p = &h->ap_scratch;
+    } else {
+        if (h->lp_epoch != h->epoch) {
+            if (int rc = drop_linear_planes(h)) return rc;
+            h->lp_epoch = h->epoch;
+        }
+        for (const auto& e : h->ap)
+            if (e->wk == key->w && e->wv == value->w && e->H == H && e->d == d) { *out = e.get(); return INFV_OK; }
+        std::unique_ptr<AttnPlanes> fresh(new (std::nothrow) AttnPlanes());
+        if (!fresh) return fail(INFV_ERR_INVALID, "out of host memory");
+        p = fresh.get();
+        h->ap.push_back(std::move(fresh));
+    }
+    const size_t bytes = (size_t)H * 64 * d * 2;
+    hipError_t e = reserve_all({{p->kT, bytes}, {p->v16, bytes}});
+    if (e == hipSuccess) e = launch_attn_f16_key_plane(key->w, H, d, p->kT.p, stream);
+    if (e == hipSuccess) e = launch_round_rows_f16(value->w, d, (long)H * 64, d, p->v16.p, d, stream);
+    if (e != hipSuccess) {
+        if (p != &h->ap_scratch) h->ap.pop_back();
+        return fail(INFV_ERR_HIP, "weight planes of the fp16 cross-attention: %s", hipGetErrorString(e));
+    }
+    p->wk = key->w; p->wv = value->w; p->H = H; p->d = d;
+    *out = p;
     return INFV_OK;
 }
 
@@ -557,6 +609,15 @@ int infv_vqf_set_linear_precision(infv_vqf_handle h, int32_t mode) {
     if (mode != h->lin_mode)
         if (int rc = drop_linear_planes(h)) return rc;        // the planes are the old mode's
     h->lin_mode = mode;
+    return INFV_OK;
+}
+
+int infv_vqf_set_attention_precision(infv_vqf_handle h, int32_t mode) {
+    if (!h) return fail(INFV_ERR_INVALID, "null handle");
+    if (mode < 0 || mode > 1) return fail(INFV_ERR_INVALID, "set_attention_precision: unknown mode %d (0 split-bf16 / fp32, 1 fp16)", mode);
+    if (mode != h->attn_mode)
+        if (int rc = drop_linear_planes(h)) return rc;        // (one cache, one rule: a change of mode drops it)
+    h->attn_mode = mode;
     return INFV_OK;
 }
 
@@ -1035,6 +1096,7 @@ struct VcCall {
     bool streams = false;
     bool vis_ln = false, emb = false;                          // the vision LayerNorm runs inside the token pass; the embedding layer writes the input rows
     bool pad = false;                                          // frames: planes and score rows padded to the next multiple of 64
+    bool attn16 = false;                                       // frames: the handle's attention precision is fp16 (attention_f16.hip)
     int n_live = 0, n_tokens = 0;                              // tokens a chunk holds in `frames`; keys it has in the contractions (pad keys: zeros, no mass)
     int n_cross = 0, n_h = 0; bool use_ltm = false;
     int C = 0, Cf = 0;                                         // chunks (0 after validation: the call is complete); distinct chunks of frame tokens
@@ -1055,6 +1117,51 @@ struct VcTables {
     std::vector<infv_ltm_handle> hs_l;                         // scratch of vc_cross_block: one layer's memories [V]
 };
 
+// ---- what infv_vqf_encode_frames (through vc_validate) and infv_vqf_frame_cross_attention both decide about a frame call, written once
+// The vision LayerNorm's arguments: what the struct and the token type alone decide ...
+static int check_vision_ln_args(const char* name, bool vis_ln, const infv_vqf_vision_ln& vl, tok_code tok) {
+    if (vis_ln && !vl.beta) return fail(INFV_ERR_INVALID, "%s: vision_ln.gamma without vision_ln.beta", name);
+    // (the vision LayerNorm of fp8 tokens is not built: no vision encoder emits fp8)
+    if (vis_ln && tok == INFV_TOKENS_F8E4M3) return fail(INFV_ERR_UNSUPPORTED, "%s: no vision LayerNorm of fp8 frame tokens", name);
+    return INFV_OK;
+}
+// ... and what the handle's width decides
+static int check_vision_ln_width(const char* name, bool vis_ln, const infv_vqf_config& c) {
+    if (vis_ln && (c.enc_width % 64 || c.enc_width > kTokenLnMaxWidth))
+        return fail(INFV_ERR_UNSUPPORTED, "%s: the vision LayerNorm needs enc_width = %d to be a multiple of 64, at most %d", name, c.enc_width,
+                    kTokenLnMaxWidth);
+    return INFV_OK;
+}
+// The token count of a frame: k.n_live, k.pad, k.n_tokens and k.attn16 from n_live and the handle's precisions
+static int frame_token_shape(const infv_vqf_s* h, VcCall& k, int n_live) {
+    const char* name = k.name;
+    const infv_vqf_config& c = h->cfg;
+    k.n_live = n_live;
+    if (n_live < 1) return fail(INFV_ERR_INVALID, "%s: n_tokens = %d, must be >= 1", name, n_live);
+    if (n_live > 0x7fffffff - 128) return fail(INFV_ERR_UNSUPPORTED, "%s: n_tokens = %d is too large", name, n_live);
+    if (c.enc_width % 64) return fail(INFV_ERR_UNSUPPORTED, "%s: enc_width = %d is no multiple of 64", name, c.enc_width);
+    k.attn16 = h->attn_mode != 0;
+    k.pad = n_live % 64 != 0 && (k.attn16 || split_path(h, 64));                  // (the fp16 attention always reads padded planes)
+    if (k.attn16 && (n_live + 63) / 64 * 64 > kAttnF16MaxPad)
+        return fail(INFV_ERR_UNSUPPORTED, "%s: the fp16 attention (infv_vqf_set_attention_precision) takes at most %d tokens a frame, got %d",
+                    name, kAttnF16MaxPad, n_live);
+    if (n_live % 32 && !k.pad)
+        return fail(INFV_ERR_UNSUPPORTED, "%s: the fp32 contractions (set_precision(h, 1) / INFV_VQF_FP32) need n_tokens %% 32 == 0, got %d", name, n_live);
+    k.n_tokens = k.pad ? (n_live + 63) / 64 * 64 : n_live;
+    return INFV_OK;
+}
+// The sizes the stages read, once the call has C chunks over Cf distinct ones of k.n_tokens (k.n_live in `frames`) tokens
+static void vc_call_sizes(const infv_vqf_s* h, VcCall& k, int C, int Cf) {
+    const infv_vqf_config& c = h->cfg;
+    k.C = C;
+    k.Cf = Cf;
+    k.M = (long)C * c.n_query;
+    k.chunk_k = (long)k.n_tokens * c.enc_width;
+    k.src_k = (long)k.n_live * c.enc_width;
+    k.RB = C < kRowBlockVideos ? C : kRowBlockVideos;
+    k.NB = pick_short_nb(h, C, k.n_tokens);
+}
+
 // ---- validation before any device work or memory change.  Returns with k.C == 0 where nothing is left to do.
 static int vc_validate(const infv_vqf_s* h, VcCall& k) {
     const char* name = k.name;
@@ -1065,12 +1172,11 @@ static int vc_validate(const infv_vqf_s* h, VcCall& k) {
     if (front && front->reserved != 0) return fail(INFV_ERR_INVALID, "%s: front->reserved must be 0", name);
     k.vis_ln = front && front->vision_ln.gamma;
     k.emb = front && front->emb.word;
-    if (k.vis_ln && !front->vision_ln.beta) return fail(INFV_ERR_INVALID, "%s: vision_ln.gamma without vision_ln.beta", name);
     if (k.emb && k.hidden_in) return fail(INFV_ERR_INVALID, "%s: the embedding layer and hidden_in are both given (one of them writes the input rows)", name);
     if (k.tok_arg && !token_dtype_known(k.token_dtype)) return fail(INFV_ERR_INVALID, "%s: unknown token dtype %d", name, k.token_dtype);
     k.tok = k.tok_arg ? static_cast<tok_code>(k.token_dtype) : INFV_TOKENS_F32;
-    // (the vision LayerNorm of fp8 tokens is not built: no vision encoder emits fp8)
-    if (k.vis_ln && k.tok == INFV_TOKENS_F8E4M3) return fail(INFV_ERR_UNSUPPORTED, "%s: no vision LayerNorm of fp8 frame tokens", name);
+    if (k.vis_ln)
+        if (int rc = check_vision_ln_args(name, true, front->vision_ln, k.tok)) return rc;
     if (k.tok != INFV_TOKENS_F32 && k.frames && !aligned16(k.frames)) return fail(INFV_ERR_INVALID, "%s: fp16 / bf16 / fp8 frames must be 16-byte aligned", name);
     if (k.vis_ln && k.frames && !aligned16(k.frames)) return fail(INFV_ERR_INVALID, "%s: frames must be 16-byte aligned for the vision LayerNorm", name);
     if (V == 0) return INFV_OK;
@@ -1103,20 +1209,13 @@ static int vc_validate(const infv_vqf_s* h, VcCall& k) {
     if (k.emb)
         if (int rc = check_front_emb(name, front, V, text_len)) return rc;
     if (k.T < 1) return fail(INFV_ERR_INVALID, "%s: T must be >= 1", name);
-    const int n_live = k.n_live = fc ? fc->n_tokens : k.T * c.tokens_per_frame;
-    if (!fc && n_live % 32) return fail(INFV_ERR_UNSUPPORTED, "%s: T * tokens_per_frame = %d is no multiple of 32", name, n_live);
     if (fc) {
-        if (n_live < 1) return fail(INFV_ERR_INVALID, "%s: n_tokens = %d, must be >= 1", name, n_live);
-        if (n_live > 0x7fffffff - 128) return fail(INFV_ERR_UNSUPPORTED, "%s: n_tokens = %d is too large", name, n_live);
-        if (c.enc_width % 64) return fail(INFV_ERR_UNSUPPORTED, "%s: enc_width = %d is no multiple of 64", name, c.enc_width);
-        k.pad = n_live % 64 != 0 && split_path(h, 64);
-        if (n_live % 32 && !k.pad)
-            return fail(INFV_ERR_UNSUPPORTED, "%s: the fp32 contractions (set_precision(h, 1) / INFV_VQF_FP32) need n_tokens %% 32 == 0, got %d", name, n_live);
+        if (int rc = frame_token_shape(h, k, fc->n_tokens)) return rc;
+    } else {
+        k.n_live = k.n_tokens = k.T * c.tokens_per_frame;
+        if (k.n_live % 32) return fail(INFV_ERR_UNSUPPORTED, "%s: T * tokens_per_frame = %d is no multiple of 32", name, k.n_live);
     }
-    k.n_tokens = k.pad ? (n_live + 63) / 64 * 64 : n_live;
-    if (k.vis_ln && (c.enc_width % 64 || c.enc_width > kTokenLnMaxWidth))
-        return fail(INFV_ERR_UNSUPPORTED, "%s: the vision LayerNorm needs enc_width = %d to be a multiple of 64, at most %d", name, c.enc_width,
-                    kTokenLnMaxWidth);
+    if (int rc = check_vision_ln_width(name, k.vis_ln, c)) return rc;
     if (!k.tok_arg && h->tok != INFV_TOKENS_F32)
         return fail(INFV_ERR_UNSUPPORTED, "%s: fp16 / bf16 frame tokens are not supported on this path (the _tok entry point takes them)", name);
     for (int l = 0; l < Ln; ++l) k.n_cross += w->layers[l].has_cross != 0;
@@ -1141,13 +1240,7 @@ static int vc_validate(const infv_vqf_s* h, VcCall& k) {
         return INFV_OK;
     }
     if (!k.frames || (!k.hidden_in && !k.emb)) return fail(INFV_ERR_INVALID, "%s: null frames or hidden_in", name);
-    const int C = k.C = cu[V];
-    k.Cf = k.streams ? fcu[F] : C;
-    k.M = (long)C * Q;
-    k.chunk_k = (long)k.n_tokens * c.enc_width;
-    k.src_k = (long)n_live * c.enc_width;
-    k.RB = C < kRowBlockVideos ? C : kRowBlockVideos;
-    k.NB = pick_short_nb(h, C, k.n_tokens);
+    vc_call_sizes(h, k, cu[V], k.streams ? fcu[F] : cu[V]);
     return INFV_OK;
 }
 
@@ -1188,7 +1281,7 @@ static int vc_front_tokens(infv_vqf_s* h, VcCall& k) {
         const size_t rows = (size_t)k.Cf * k.n_live;
         HIP_TRY(reserve_all({{h->lnstats, rows * 2 * sizeof(float)}}));
         HIP_TRY(launch_token_ln_stats(k.frames, k.tok, (long)rows, c.enc_width, vl.eps, h->lnstats.p, k.stream));
-        if (split_path(h, k.n_tokens)) {
+        if (k.attn16 || split_path(h, k.n_tokens)) {
             k.ln_ = TokLn{h->lnstats.as<float>(), vl.gamma, vl.beta};
             k.ln = &k.ln_;
         } else {                                               // the fp32 contractions from the normalised fp32 copy
@@ -1197,7 +1290,7 @@ static int vc_front_tokens(infv_vqf_s* h, VcCall& k) {
             k.frames = h->up.p; k.tok = INFV_TOKENS_F32;
         }
     }
-    if (k.n_cross == 0) return INFV_OK;
+    if (k.n_cross == 0 || k.attn16) return INFV_OK;           // (the fp16 token pass reads every token type in place)
     return fp32_tokens_unless_split(h, k.frames, k.tok, k.n_tokens, (size_t)k.Cf * k.chunk_k, k.stream);
 }
 
@@ -1235,6 +1328,18 @@ static int vc_input_rows(infv_vqf_s* h, VcCall& k, const VcTables& t) {
 static int vc_token_pass(infv_vqf_s* h, VcCall& k, const VcTables& t) {
     if (k.n_cross == 0) return INFV_OK;
     const infv_vqf_config& c = h->cfg;
+    if (k.attn16) {                                            // the fp16 plane and its transposed copy, once per call, for all cross layers
+        const size_t sz = (size_t)k.Cf * k.chunk_k * 2;
+        HIP_TRY(reserve_all({{h->aX, sz}, {h->aXT, sz}}));
+        for (int c0 = 0; c0 < k.Cf; c0 += 32768) {             // grid.z limit
+            const int n = k.Cf - c0 < 32768 ? k.Cf - c0 : 32768;
+            const size_t o = (size_t)c0 * k.chunk_k * 2;
+            HIP_TRY(launch_token_pass_f16(tok_at(k.frames, k.tok, (long)c0 * k.src_k), k.tok, n, k.n_live, k.n_tokens, c.enc_width,
+                                          k.ln ? k.ln->stats + 2 * (size_t)c0 * k.n_live : nullptr, k.ln ? k.ln->gamma : nullptr,
+                                          k.ln ? k.ln->beta : nullptr, h->aX.as<char>() + o, h->aXT.as<char>() + o, k.stream));
+        }
+        return INFV_OK;
+    }
     float* kbar = h->vkbar.as<float>();
     // (streams: the distinct chunks only; bf16 tokens: only the transposed plane is written, as in infv_vqf_encode_video)
     const double need_gb = plane_bytes(k.tok, k.ln != nullptr, k.pad) * (double)k.Cf * (double)k.chunk_k / 1e9;
@@ -1347,6 +1452,37 @@ static int vc_self_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l) {
     return INFV_OK;
 }
 
+// The short-term attention of every chunk of the call, in sub-batches, from the operands vc_token_pass left:
+// xq [C * Q][hidden] -> out [C * Q][hidden].  Frames under the fp16 attention precision take attention_f16.hip's three launches.
+static int vc_short_attention(infv_vqf_s* h, const VcCall& k, const VcTables& t, const float* xq, const infv_linear* key,
+                              const infv_linear* value, float* out) {
+    const infv_vqf_config& c = h->cfg;
+    const int Q = c.n_query, Hd = c.hidden;
+    if (k.attn16) {
+        const AttnPlanes* p = nullptr;
+        if (int rc = attn_planes(h, key, value, &p, k.stream)) return rc;
+        const int NB = k.C < kAttnF16Frames ? k.C : kAttnF16Frames;
+        const size_t sz = (size_t)NB * c.n_heads * Q * c.enc_width * 2;
+        HIP_TRY(reserve_all({{h->aQt, sz}, {h->aO, sz}}));
+        for (RowBlock b : RowBlocks{k.C, NB, (long)Q * Hd}) {
+            AttnF16 a{};
+            a.xq = xq + b.r0; a.wkT = p->kT.p; a.wv16 = p->v16.p; a.bv = value->b;
+            a.X = h->aX.as<char>() + (size_t)b.c0 * k.chunk_k * 2; a.XT = h->aXT.as<char>() + (size_t)b.c0 * k.chunk_k * 2;
+            a.qt = h->aQt.p; a.o = h->aO.p; a.ctx = out + b.r0;
+            a.nb = b.nb; a.Q = Q; a.H = c.n_heads; a.d = c.enc_width; a.n = k.n_live; a.n_pad = k.n_tokens;
+            HIP_TRY(launch_attn_f16(a, k.stream));
+        }
+        return INFV_OK;
+    }
+    for (RowBlock b : RowBlocks{k.C, k.NB, (long)Q * Hd}) {
+        const VcOperand op = vc_operand_at(h, k, t, b.c0, b.nb);
+        if (op.rc) return op.rc;
+        if (int rc = short_attention(h, op.frames, k.tok, b.nb, k.n_tokens, xq + b.r0, false, key, value, nullptr, out + b.r0, k.stream, false,
+                                     op.has_pre ? &op.pre : nullptr, nullptr, kInvariantNb, op.map, op.t_identity, k.pad ? k.n_live : 0)) return rc;
+    }
+    return INFV_OK;
+}
+
 // Cross layer l, the j-th of them: its V memories with per-chunk queries on the worker stream, beside the short-term attention;
 // the merge of the two; the context tap; the cross output
 static int vc_cross_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l, int j) {
@@ -1365,13 +1501,7 @@ static int vc_cross_block(infv_vqf_s* h, const VcCall& k, VcTables& t, int l, in
                                                 Q, &pr, k.u ? h->vu.as<double>() : nullptr, k.new_video, h->valong.as<float>(), h->side)) return rc;
         HIP_TRY(hipEventRecord(h->ev_side, h->side));
     }
-    for (RowBlock b : RowBlocks{k.C, k.NB, (long)Q * Hd}) {
-        const VcOperand op = vc_operand_at(h, k, t, b.c0, b.nb);
-        if (op.rc) return op.rc;
-        if (int rc = short_attention(h, op.frames, k.tok, b.nb, k.n_tokens, vxq + b.r0, false, &L.x_k, &L.x_v, nullptr,
-                                     (k.use_ltm ? h->vshort.as<float>() : vmerged) + b.r0, k.stream, false, op.has_pre ? &op.pre : nullptr,
-                                     nullptr, kInvariantNb, op.map, op.t_identity, k.pad ? k.n_live : 0)) return rc;
-    }
+    if (int rc = vc_short_attention(h, k, t, vxq, &L.x_k, &L.x_v, k.use_ltm ? h->vshort.as<float>() : vmerged)) return rc;
     if (k.use_ltm) {
         HIP_TRY(hipStreamWaitEvent(k.stream, h->ev_side, 0));
         if (int rc = alpha_merge(h, k.M, k.stream)) return rc;
@@ -1546,6 +1676,42 @@ int infv_vqf_encode_frames(infv_vqf_handle h, int32_t F, const void* vision, int
     return rc;
 }
 
+// One cross-attention of infv_vqf_encode_frames alone: the stages of vc_impl that a cross layer's attention consists of, over a call
+// descriptor filled here (no weights, no query rows: xq is given)
+int infv_vqf_frame_cross_attention(infv_vqf_handle h, int32_t F, const void* vision, int32_t token_dtype, int32_t n_tokens,
+                                   const infv_vqf_vision_ln* ln, const float* xq, const infv_linear* key, const infv_linear* value,
+                                   float* ctx, void* stream_) {
+    // ---- every refusal before any launch or memory change ----
+    const char* name = "frame_cross_attention";
+    if (!h || !key || !value || !key->w || !value->w) return fail(INFV_ERR_INVALID, "%s: null handle, key or value", name);
+    if (F < 0) return fail(INFV_ERR_INVALID, "%s: F = %d is negative", name, F);
+    if (!token_dtype_known(token_dtype)) return fail(INFV_ERR_INVALID, "%s: unknown token dtype %d", name, token_dtype);
+    if (F > 0 && (!vision || !xq || !ctx)) return fail(INFV_ERR_INVALID, "%s: null vision, xq or ctx", name);
+    if (!aligned16(vision) || !aligned16(xq) || !aligned16(ctx) || !aligned16(key->w) || !aligned16(value->w))
+        return fail(INFV_ERR_INVALID, "%s: vision, xq, ctx and the weights must be 16-byte aligned", name);
+    const infv_vqf_config& c = h->cfg;
+    if ((long)F * c.n_query > 0x3fffffffL) return fail(INFV_ERR_UNSUPPORTED, "%s: %d frames in one call", name, F);
+    // ---- the frame checks of infv_vqf_encode_frames (vc_validate), through the helpers the two share ----
+    infv_vqf_vc_front front{};
+    if (ln && ln->gamma) front.vision_ln = *ln;
+    VcCall k;
+    k.name = name; k.V = F; k.frames = vision; k.tok_arg = true; k.token_dtype = token_dtype; k.T = 1; k.front = &front;
+    k.stream = static_cast<hipStream_t>(stream_);
+    k.tok = static_cast<tok_code>(token_dtype);
+    k.vis_ln = front.vision_ln.gamma != nullptr;
+    if (int rc = check_vision_ln_args(name, k.vis_ln, front.vision_ln, k.tok)) return rc;
+    if (int rc = frame_token_shape(h, k, n_tokens)) return rc;
+    if (int rc = check_vision_ln_width(name, k.vis_ln, c)) return rc;
+    if (F == 0) return INFV_OK;
+    k.n_cross = 1;
+    vc_call_sizes(h, k, F, F);                                 // (no workspace of vc_workspaces is used: xq and ctx are the caller's)
+    const FrameCall fc{n_tokens, nullptr, INFV_TOKENS_F32};
+    k.fc = &fc;
+    VcTables t;
+    if (int rc = vc_front_tokens(h, k)) return rc;
+    if (int rc = vc_token_pass(h, k, t)) return rc;
+    return vc_short_attention(h, k, t, xq, key, value, ctx);
+}
 
 int infv_vqf_set_context_tap(infv_vqf_handle h, int32_t layer, float* dst) {
     if (!h) return fail(INFV_ERR_INVALID, "null handle");

@@ -128,6 +128,26 @@ struct LinearGemm {
 hipError_t launch_linear_gemm(const LinearGemm& g, int mode, hipStream_t stream);
 // x [rows][cols] fp32 -> out [rows][cols] fp16, round to nearest even (beyond 65504: inf)
 hipError_t launch_round_rows_f16(const float* x, long ld_in, long rows, int cols, void* out, long ld_out, hipStream_t stream);
+// ---- the cross-attention of infv_vqf_encode_frames with fp16 operands (attention_f16.hip; infv_vqf_set_attention_precision) ----
+constexpr int kAttnF16MaxPad = 512;      // keys a frame may have, padded: the scores of a 64-row block stay in accumulators
+constexpr int kAttnF16Frames = 256;      // frames per sub-batch (the fp16 q~' and o' workspaces are sized by it): 1536 workgroups at 12 x 32 rows
+// F [nb][n][d] of any token type (stats != nullptr: token_ln(F) applied on load, not for fp8) -> X [nb][n_pad][d] = fp16(value),
+// round to nearest even, and its transposed copy XT [nb][d][n_pad]; rows at or beyond n zeros; n_pad % 64 == 0, nb <= 32768
+// (token_pass.hip)
+hipError_t launch_token_pass_f16(const void* F, tok_code tok, int nb, int n, int n_pad, int d, const void* stats, const float* gamma,
+                                 const float* beta, void* X, void* XT, hipStream_t stream);
+// plane [H][d][64] = fp16(wk [H * 64][d]) transposed per head
+hipError_t launch_attn_f16_key_plane(const float* wk, int H, int d, void* plane, hipStream_t stream);
+// ctx [nb * Q][H * 64] fp32 = the cross-attention context of nb frames (three launches: q~', scores + softmax + context, value
+// projection).  xq [nb * Q][H * 64] fp32; wkT from launch_attn_f16_key_plane; wv16 [H * 64][d] fp16; bv [H * 64] or nullptr;
+// X / XT the frames' planes; qt, o: fp16 workspaces [nb][H * Q][d].  n_pad <= kAttnF16MaxPad, d % 64 == 0
+struct AttnF16 {
+    const float* xq; const void* wkT; const void* wv16; const float* bv;
+    const void* X; const void* XT;
+    void* qt; void* o; float* ctx;
+    int nb, Q, H, d, n, n_pad;
+};
+hipError_t launch_attn_f16(const AttnF16& a, hipStream_t stream);
 // ---- frame tokens and score rows -> the contractions' bf16 planes (token_pass.hip) ----
 // x [n] bf16 / fp16 / fp8 e4m3 -> y [n] fp32 (exact); n % 8 == 0, fp8: n % 16 == 0.  fp32 tokens are refused
 hipError_t launch_upcast(const void* x, tok_code tok, float* y, long n, hipStream_t stream);

@@ -29,12 +29,19 @@ from .videochat2_qformer import _Cfg, _Intermediate, _Output, _SelfOutput
 
 OUT_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 3}       # out_dtype codes of infv_vqf_encode_frames
 LINEAR_PRECISIONS = {"fp32": 0, "split_bf16": 1, "fp16": 2}                # mode codes of infv_vqf_set_linear_precision
+ATTENTION_PRECISIONS = {"fp32": 0, "fp16": 1}                              # mode codes of infv_vqf_set_attention_precision
 
 
 def _linear_precision_code(name) -> int:
     if not isinstance(name, str) or name not in LINEAR_PRECISIONS:
         raise ValueError(f"linear_precision must be one of {sorted(LINEAR_PRECISIONS)}, got {name!r}")
     return LINEAR_PRECISIONS[name]
+
+
+def _attention_precision_code(name) -> int:
+    if not isinstance(name, str) or name not in ATTENTION_PRECISIONS:
+        raise ValueError(f"attention_precision must be one of {sorted(ATTENTION_PRECISIONS)}, got {name!r}")
+    return ATTENTION_PRECISIONS[name]
 
 
 class _SelfAttention(nn.Module):                       # Qformer.py:115-175 without the LongTermAttention (never called here)
@@ -114,10 +121,13 @@ class FrameQformerEncoder(nn.Module):
 
     def __init__(self, num_query_token: int = 32, vision_width: int = 1408, num_hidden_layers: int = 12,
                  cross_attention_freq: int = 2, vision_layernorm: bool = True, ln_eps: float = 1e-5, hidden_size: int = 768,
-                 intermediate_size: int = 3072, num_attention_heads: int = 12, linear_precision: str = "fp32"):
+                 intermediate_size: int = 3072, num_attention_heads: int = 12, linear_precision: str = "fp32",
+                 attention_precision: str = "fp32"):
         super().__init__()
         _linear_precision_code(linear_precision)
+        _attention_precision_code(attention_precision)
         self.linear_precision = linear_precision
+        self.attention_precision = attention_precision
         cfg = _Cfg(encoder_width=vision_width, num_hidden_layers=num_hidden_layers, cross_attention_freq=cross_attention_freq,
                    query_length=num_query_token, hidden_size=hidden_size, intermediate_size=intermediate_size,
                    num_attention_heads=num_attention_heads, alpha=1.0)
@@ -162,6 +172,16 @@ class FrameQformerEncoder(nn.Module):
         ``p._version`` and is therefore not seen: after one, call this method again (every call starts a new set of planes)."""
         _linear_precision_code(name)
         self.linear_precision = name
+        self._plane_gen = getattr(self, "_plane_gen", 0) + 1
+
+    def set_attention_precision(self, name: str) -> None:
+        """The arithmetic of the cross-attention (``infv_vqf_set_attention_precision``): ``"fp32"`` (default: the split-bf16
+        contractions, fp32-class) or ``"fp16"`` (tokens, pre-multiplied query, probabilities and context rounded to fp16, fp32
+        accumulation: what the reference's fp16 autocast computes; values beyond fp16's range become inf).  Independent of
+        :meth:`set_linear_precision`.  Applied at the next call; the fp16 key / value weight planes live in the handle's plane cache
+        and follow its rules."""
+        _attention_precision_code(name)
+        self.attention_precision = name
         self._plane_gen = getattr(self, "_plane_gen", 0) + 1
 
     def _weights(self, device):
@@ -235,14 +255,16 @@ class FrameQformerEncoder(nn.Module):
         """The mode, and the weights epoch the handle's plane cache lives by: the signature ``_weights`` computes (storage address,
         in-place version and dtype of every parameter), so an in-place update or ``load_state_dict`` invalidates the planes."""
         mode = LINEAR_PRECISIONS[self.linear_precision]
-        epoch = (hash((self._w_cache[0], getattr(self, "_plane_gen", 0))) & 0x7FFFFFFFFFFFFFFF) | 1 if mode else 0
-        if self._vqf_state == (mode, epoch):
+        attn = ATTENTION_PRECISIONS[getattr(self, "attention_precision", "fp32")]
+        epoch = (hash((self._w_cache[0], getattr(self, "_plane_gen", 0))) & 0x7FFFFFFFFFFFFFFF) | 1 if mode or attn else 0
+        if self._vqf_state == (mode, attn, epoch):
             return
         lib = _lib.load()
         with torch.cuda.device(device):
             _lib.check(lib.infv_vqf_set_linear_precision(h, mode))
+            _lib.check(lib.infv_vqf_set_attention_precision(h, attn))
             _lib.check(lib.infv_vqf_set_weights_epoch(h, C.c_uint64(epoch)))
-        self._vqf_state = (mode, epoch)
+        self._vqf_state = (mode, attn, epoch)
 
     def _release(self):
         vqf, self._vqf = getattr(self, "_vqf", None), None

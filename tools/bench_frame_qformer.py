@@ -20,7 +20,9 @@ and the largest difference between the two legs' frame tokens.
 (``FrameQformerEncoder.set_linear_precision``) beside the torch leg, and adds each leg's ratio to torch and to the fp32 leg; the drop
 of free device memory over a leg's first call then includes its weight planes.  ``--parent-root DIR`` adds a leg that runs the fp32
 path of another build of the library (a checkout with its own ``libinfv_ltm.so``), alternated with the others: the parent-against-
-branch comparison.  Either option needs ``--out``: the default file keeps the two-leg lines.
+branch comparison.  ``--attention-precision fp32,fp16`` multiplies the hip legs: one per (linear, attention) pair asked for
+(``FrameQformerEncoder.set_attention_precision``; a leg with the fp16 attention is named ``hip_<linear>_attn_fp16`` and its memory drop
+includes the fp16 token planes).  Any of these options needs ``--out``: the default file keeps the two-leg lines.
 """
 from __future__ import annotations
 
@@ -73,6 +75,8 @@ def child(a):
     m = FrameQformerEncoder().to(dev).eval()
     if a.precision != "fp32":                                          # (a parent build has no such method and is never asked)
         m.set_linear_precision(a.precision)
+    if a.attention != "fp32":
+        m.set_attention_precision(a.attention)
     for p in m.parameters():
         p.requires_grad = False
     x = torch.randn(a.frames, TOKENS, WIDTH, device=dev, generator=torch.Generator(device=dev).manual_seed(1)).half()
@@ -134,6 +138,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", choices=("torch", "hip"))
     ap.add_argument("--precision", default="fp32", help="(child) linear precision of the hip leg")
+    ap.add_argument("--attention", default="fp32", help="(child) attention precision of the hip leg")
+    ap.add_argument("--attention-precision", default="", help="comma-separated: the hip legs run per (linear, attention) pair (fp32, fp16)")
     ap.add_argument("--linear-precision", default="", help="comma-separated: one hip leg per name (fp32, split_bf16, fp16)")
     ap.add_argument("--parent-root", default="", help="a checkout of another build: one more fp32 hip leg from there")
     ap.add_argument("--root", default=ROOT)
@@ -145,7 +151,7 @@ def main():
     a = ap.parse_args()
     if a.child:
         return child(a)
-    if a.linear_precision or a.parent_root:
+    if a.linear_precision or a.attention_precision or a.parent_root:
         return main_legs(a)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     meds, last = {"torch": [], "hip": []}, {}
@@ -167,13 +173,14 @@ def main():
 
 
 def main_legs(a):
-    """torch, one hip leg per linear precision, and the parent build's fp32 leg, alternated child by child."""
+    """torch, one hip leg per (linear, attention) precision pair, and the parent build's fp32 leg, alternated child by child."""
     if os.path.abspath(a.out) == os.path.join(ROOT, "profiles", "frame_qformer.jsonl"):
-        raise SystemExit("--linear-precision / --parent-root need --out (profiles/frame_qformer.jsonl keeps the two-leg lines)")
+        raise SystemExit("--linear-precision / --attention-precision / --parent-root need --out (profiles/frame_qformer.jsonl keeps the two-leg lines)")
     names = [n for n in a.linear_precision.split(",") if n] or ["fp32"]
     legs = {"torch": ["--child", "torch"]}
     for n in names:
-        legs["hip_" + n] = ["--child", "hip", "--precision", n]
+        for att in [t for t in a.attention_precision.split(",") if t] or ["fp32"]:
+            legs["hip_" + n + ("" if att == "fp32" else "_attn_" + att)] = ["--child", "hip", "--precision", n, "--attention", att]
     if a.parent_root:
         legs["parent_fp32"] = ["--root", os.path.abspath(a.parent_root), "--child", "hip"]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
