@@ -350,7 +350,8 @@ int infv_ltm_import_state(infv_ltm_handle h, int32_t layer, const float* B, cons
  * The blob is a 64-byte header (magic, version, L, N, d, dm, H, Q, n_bins as int32) and everything infv_ltm_consolidate
  * carries from chunk to chunk, in fp32:
  *   B [L][N][d] | projected memory [L][N][2][dm] | bias-free scores under the call's query [L][H][Q][N] | sticky bin
- *   masses [L][n_bins]
+ *   masses [L][n_bins] | key-bias term of those scores [L][H][Q] (q_h . b_k,h / sqrt(dh): what infv_ltm_density, infv_ltm_masses
+ *   and the scores of infv_ltm_get_draw add back on the importing side)
  * so a consolidate call that follows an import (new_doc = 0) continues BIT FOR BIT as if the exporting handle had gone on
  * itself -- unlike export_state/import_state, which hand over B and the masses only and re-derive the rest (same values up
  * to fp32 rounding).  Conditions, none of which the library can check for the caller: the SAME q and proj on both sides (the
@@ -385,6 +386,71 @@ int infv_ltm_set_bins(infv_ltm_handle h, int32_t layer, const int32_t* bins);
  * (DEVICE buffers owned by the caller, either may be NULL; rows of a document's first chunk,
  * which draws nothing, are left untouched).  capacity_chunks = 0 clears the trace. */
 int infv_ltm_set_trace(infv_ltm_handle h, int32_t* bins_all, float* probs_all, int64_t capacity_chunks);
+
+/* ---- Read-outs of the memory's attention density (additive in ABI 6) ----
+ * The reference's Video-LLaMA operator evaluates, on every forward, the density of the step it just took on a 768-point grid and
+ * pickles it to ./alphas_uniform (long_term_attention_gibbs.py:320-343; relevant_frames.py reads that file).  Neither read-out
+ * below is on a default path: with no trace set and no density call, no entry point launches, records or allocates anything more
+ * than before.  General-psi plans (infv_ltm_set_psi_plan) have no box density: all four calls refuse a handle that holds one
+ * (INFV_ERR_UNSUPPORTED), and infv_ltm_set_psi_plan refuses a handle with a grid plan or a trace set.  Sparse and dense box plans
+ * are taken.
+ *
+ * The grid (:328-334: three torch.linspace segments of 256 points) as host tables, copied: n_points M <= 4096 in n_segments
+ * G <= 16 consecutive segments, segment g = points [seg_begin[g], seg_begin[g+1]) (at least two each); pt_weight[m] the
+ * trapezoid weight of point m inside its own segment (torch.trapz, :248, over the fp32 grid values); and psi at every point as a
+ * CSR over boxes: entries [pt_ptr[m], pt_ptr[m+1]) of pt_box / pt_val.  A box partition gives one entry of value 1, a point where
+ * two fp32 boxes overlap (num_basis 96, ...) two, a point in no box (t = 1.0) none.  s(t_m) = sum of pt_val * S[pt_box] is added
+ * in CSR order in fp32.  Refused with INFV_ERR_INVALID before any device work: null tables, M outside [2, 4096], G outside
+ * [1, 16], seg_begin not running from 0 to M or a segment of fewer than two points, pt_ptr not starting at 0 or not monotone,
+ * a pt_box outside [0, num_basis), a weight that is negative or not finite, a value that is not finite, num_basis + M above
+ * 16384 (a wave keeps the score row and the grid in LDS). */
+typedef struct {
+    int32_t n_points;
+    int32_t n_segments;
+    const int32_t* seg_begin;         /* [n_segments+1] */
+    const float*   pt_weight;         /* [n_points]     */
+    const int32_t* pt_ptr;            /* [n_points+1]   */
+    const int32_t* pt_box;            /* [pt_ptr[n_points]] */
+    const float*   pt_val;            /* [pt_ptr[n_points]] */
+} infv_ltm_grid_plan;
+int infv_ltm_set_grid_plan(infv_ltm_handle h, const infv_ltm_grid_plan* plan);
+
+/* The reference's `alphas` (:328-337) of the memory's LAST step, one layer: with S[h,q,n] the step's full scores (key-bias term
+ * included: a grid point in no box enters as exp(0)) and s(t) as above,
+ *     e = exp(s - max of s over the point's segment);  z_g = sum over segment g of pt_weight * e;  dens = e / z_g;
+ *     alphas[q][h][m] = dens_m / sum_m' dens_m'
+ * written to the DEVICE buffer alphas [Q][H][M] -- the [Q, 1, H, M] of the permute at :337.  (The reference subtracts no
+ * maximum, :248, and overflows where this does not; dens is normalised inside a segment, so the segment's own maximum keeps it in range.)  One launch on `stream`: a wave per (h, q) row, exp is expf, the sums run in
+ * float64.  Works after every single-handle entry point that leaves a memory: step, steps, forward, forward_into, consolidate,
+ * consolidate_pooled, consolidate_q, import_chain_state -- and after the lockstep calls.  INFV_ERR_STATE: no memory, no grid plan,
+ * a Q other than the last step's, or after infv_ltm_import_state, which keeps no scores. */
+int infv_ltm_density(infv_ltm_handle h, int32_t layer, int32_t Q, float* alphas, void* stream);
+
+/* What the read-out of the last step actually used, one layer: mass[n] = mean over (h, q) of alpha[h,q,n] with
+ * alpha[h,q,n] = w_n e^{S_n} / (sum_m w_m e^{S_m} + w_out), the `integral` of expected_value (:282); w and w_out are the plan's
+ * readout_w and readout_w_out.  mass: DEVICE [num_basis].  One launch; same conditions and refusals as infv_ltm_density except
+ * that no grid plan is needed; num_basis above 512 is INFV_ERR_UNSUPPORTED.
+ * Order of the sum over the H*Q rows r = h * Q + q (both this call and the trace below): eight partial sums, partial k adds rows
+ * k, k + 8, k + 16, ... in increasing order from 0; the partials are added in order 0..7 from 0; the total is multiplied by
+ * 1 / (H*Q).  All in float64, rounded to fp32 once -- so the order is part of the description, not of the result. */
+int infv_ltm_masses(infv_ltm_handle h, int32_t layer, int32_t Q, float* mass, void* stream);
+
+/* Box-mass trace of the multi-chunk calls, modelled on infv_ltm_set_trace: while set, chunk c < capacity_chunks of an
+ * infv_ltm_steps / infv_ltm_consolidate / infv_ltm_consolidate_pooled / infv_ltm_consolidate_q call writes the masses of its
+ * step, every layer, to mass_all[c][L][num_basis] (DEVICE buffer owned by the caller).  Every chunk writes, a document's first
+ * included; rows at and beyond capacity_chunks are not touched; capacity_chunks = 0 clears the trace.  The single-chunk calls
+ * (step, forward, forward_into) leave the trace alone: read them with infv_ltm_masses.
+ * Added launches while set, none otherwise: the fused chain of consolidate / consolidate_pooled adds exactly ONE per update +
+ * read-out launch -- one per sub-batch, plus one for a document's first chunk, which is a launch of its own -- on the stream of
+ * those launches, behind the sub-batch's softmax weights and ahead of the reuse of their ring slots; it reads the weights the
+ * update + read-out kernel reads.  The per-chunk stages (steps, consolidate_q, and consolidate where it runs them: dense plans,
+ * shapes the fused chain does not hold) add exactly ONE per chunk, from the chunk's full scores: there the last row has the
+ * bits of infv_ltm_masses called afterwards.  No existing kernel changes, no event or allocation is added.
+ * infv_ltm_consolidate_videos, infv_ltm_steps_videos and infv_ltm_steps_videos_from refuse a handle with a trace set
+ * (INFV_ERR_UNSUPPORTED before any device work, every memory untouched).  The video Q-former drives these same handles:
+ * infv_vqf_encode_video steps each layer's handle with infv_ltm_consolidate / _pooled / infv_ltm_steps (infv_vqf.h), so a trace
+ * set on a layer's handle is honoured by it without further work; its batched calls run the lockstep entry points and refuse. */
+int infv_ltm_set_mass_trace(infv_ltm_handle h, float* mass_all, int64_t capacity_chunks);
 
 /* Synchronises `stream`, then reports a latched device-side failure (see Conventions). */
 int infv_ltm_sync(infv_ltm_handle h, void* stream);

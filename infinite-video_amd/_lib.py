@@ -66,6 +66,13 @@ class DensePlanStruct(C.Structure):
     ]
 
 
+class GridPlanStruct(C.Structure):
+    _fields_ = [
+        ("n_points", C.c_int32), ("n_segments", C.c_int32),
+        ("seg_begin", i32p), ("pt_weight", f32p), ("pt_ptr", i32p), ("pt_box", i32p), ("pt_val", f32p),
+    ]
+
+
 class Proj(C.Structure):
     _fields_ = [("wk", C.c_void_p), ("bk", C.c_void_p), ("wv", C.c_void_p), ("bv", C.c_void_p)]
 
@@ -180,6 +187,10 @@ _SIGNATURES = {
     "infv_ltm_set_probs": (C.c_int, [C.c_void_p, C.c_int32, f32p]),
     "infv_ltm_set_bins": (C.c_int, [C.c_void_p, C.c_int32, i32p]),
     "infv_ltm_set_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "infv_ltm_set_grid_plan": (C.c_int, [C.c_void_p, C.POINTER(GridPlanStruct)]),
+    "infv_ltm_density": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "infv_ltm_masses": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "infv_ltm_set_mass_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "infv_ltm_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
     "infv_ltm_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "infv_ltm_profile_read": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

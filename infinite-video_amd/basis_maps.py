@@ -378,3 +378,53 @@ def _build_sparse_plan(T: int, N: int, tau: float, S: int) -> Plan:
         edge_box=box_of(mod, N).astype(np.int32), edge_dx=edge_dx,
         bin_box=box_of(bins[:-1], N).astype(np.int32), uniform_idx=box_of(t_uni, N).astype(np.int32),
     )
+
+
+# ---- grid of the attention-density read-out (infv_ltm_set_grid_plan) ----
+# reference long_term_attention_gibbs.py:328-334: linspace(0, .25, 256), linspace(.25, .5, 256), linspace(.5, 1, 256)
+REFERENCE_DENSITY_SEGMENTS = ((0.0, 0.25, 256), (0.25, 0.5, 256), (0.5, 1.0, 256))
+
+
+@dataclass(frozen=True)
+class GridPlan:
+    N: int
+    segments: Tuple[Tuple[float, float, int], ...]
+    t: np.ndarray             # [M] fp32 grid values, segment after segment
+    seg_begin: np.ndarray     # [G + 1] int32
+    pt_weight: np.ndarray     # [M] fp32 trapezoid weight of a point inside its own segment
+    pt_ptr: np.ndarray        # [M + 1] int32 CSR over boxes of psi(t_m)
+    pt_box: np.ndarray        # [nnz] int32
+    pt_val: np.ndarray        # [nnz] fp32 (ones for the rectangular family)
+
+
+@lru_cache(maxsize=64)
+def build_grid_plan(num_basis: int, segments=REFERENCE_DENSITY_SEGMENTS) -> GridPlan:
+    """Host tables of the density grid: the points are ``torch.linspace(lo, hi, M_g)`` as fp32 values, segment after segment;
+    the weights are those ``torch.trapz(y, t)`` (:248) gives the points of one segment, from the fp32 differences of its grid
+    values; psi at every point is the reference's own fp32 box test (``membership``): one box, two where fp32 boxes overlap
+    (num_basis 96, ...), none at ``t = 1.0``."""
+    segments = tuple((float(lo), float(hi), int(m)) for lo, hi, m in segments)
+    if not segments or len(segments) > 16:
+        raise ValueError("a density grid has 1..16 segments")
+    ts, ws, begin = [], [], [0]
+    for lo, hi, m in segments:
+        if m < 2:
+            raise ValueError("a segment needs at least two points (torch.trapz over one point is empty)")
+        t = torch.linspace(lo, hi, m)
+        dx = (t[1:] - t[:-1]).double().numpy()
+        w = np.zeros(m)
+        w[:-1] += dx / 2
+        w[1:] += dx / 2
+        ts.append(t)
+        ws.append(w)
+        begin.append(begin[-1] + m)
+    if begin[-1] > 4096:
+        raise ValueError("a density grid has at most 4096 points")
+    t = torch.cat(ts)
+    inside = membership(t, num_basis).numpy() > 0
+    ptr = np.zeros(len(t) + 1, dtype=np.int32)
+    ptr[1:] = np.cumsum(inside.sum(1))
+    box = np.nonzero(inside)[1].astype(np.int32)              # row-major: the boxes of a point in ascending order
+    return GridPlan(N=num_basis, segments=segments, t=t.numpy().astype(np.float32),
+                    seg_begin=np.asarray(begin, dtype=np.int32), pt_weight=np.concatenate(ws).astype(np.float32),
+                    pt_ptr=ptr, pt_box=box, pt_val=np.ones(len(box), dtype=np.float32))

@@ -28,7 +28,7 @@ int check_chain_error(infv_ltm_handle h) {
     if (h->err_host && *reinterpret_cast<volatile unsigned int*>(h->err_host)) {
         const unsigned int code = *reinterpret_cast<volatile unsigned int*>(h->err_host);
         *reinterpret_cast<volatile unsigned int*>(h->err_host) = 0;
-        h->has_memory = false; h->parts = 0; h->k_stale = false; h->pos = 0; h->ctx_sum_drop();
+        h->has_memory = false; h->parts = 0; h->k_stale = false; h->pos = 0; h->ctx_sum_drop(); h->scores_ok = false;
         if (code == kErrBlobMismatch)
             return fail(INFV_ERR_STATE, "the blob handed to an earlier infv_ltm_import_chain_state was not exported by a handle of "
                                         "this shape (magic / version / L, N, d, dm, H, Q, n_bins in its header); the memory has been reset");
@@ -149,8 +149,9 @@ int chain_step(infv_ltm_handle h, const Plan& plan, const float* R, const float*
     h->parts = parts;
     h->lastQ = Q;
     h->last_fast = false;
+    h->scores_ok = true; h->last_plan = &plan;
     ++h->pos;
-    return INFV_OK;
+    return trace_masses_of_step(h, plan, Q, stream);
 }
 
 // One step with dense operators (ltm_dense.hip): draw -> B = x . G -> project the whole memory -> scores, softmax weights,
@@ -235,8 +236,9 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
     h->parts = h->H;
     h->lastQ = Q;
     h->last_fast = false;
+    h->scores_ok = true; h->last_plan = &plan;
     ++h->pos;
-    return INFV_OK;
+    return trace_masses_of_step(h, plan, Q, stream);
 }
 
 // What infv_ltm_step would refuse over the `n_chunks` chunks of a call, for the entry points that reset the memory or pool the
@@ -386,7 +388,10 @@ int infv_ltm_set_plan(infv_ltm_handle h, const infv_ltm_plan* p) {
     if (e == hipSuccess) e = upload(plan->uniform_idx, p->uniform_idx, h->S);
     if (e != hipSuccess) { delete plan; return fail(INFV_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e)); }
     auto it = h->plans.find(p->T);
-    if (it != h->plans.end()) { delete it->second; h->plans.erase(it); }
+    if (it != h->plans.end()) {
+        if (h->last_plan == it->second) h->last_plan = nullptr;   // (infv_ltm_masses then takes the read-out weights of any plan: they depend on num_basis only)
+        delete it->second; h->plans.erase(it);
+    }
     h->plans[p->T] = plan;
     return INFV_OK;
 }
@@ -429,6 +434,8 @@ int infv_ltm_set_psi_plan(infv_ltm_handle h, const infv_ltm_psi_plan* p) {
     if (int rc = find_plan(h, p->T, &plan)) return rc;
     DensePlan& d = plan->dense;
     if (!d.on) return fail(INFV_ERR_STATE, "psi plan: set the dense plan of T=%d first (infv_ltm_set_dense_plan)", p->T);
+    if (h->grid.on || h->mass_trace)
+        return fail(INFV_ERR_UNSUPPORTED, "psi plan: the handle has a grid plan or a mass trace set (box plans only: infv_ltm_set_grid_plan)");
     HIP_TRY(hipDeviceSynchronize());                            // a step of this length may still be reading the old tables
     HIP_TRY(upload(d.psi_edge, p->psi_edge, (size_t)(h->n_bins + 1) * h->N));
     HIP_TRY(upload(d.psi_bin, p->psi_bin, (size_t)h->n_bins * h->N));
@@ -447,6 +454,7 @@ int infv_ltm_reset(infv_ltm_handle h) {
     h->k_stale = false;
     h->pos = 0;
     h->ctx_sum_drop();
+    h->scores_ok = false;
     return INFV_OK;
 }
 
@@ -562,12 +570,15 @@ int infv_ltm_steps(infv_ltm_handle h, const float* kbar, int32_t n_chunks, int32
     const size_t chunk_kbar = (size_t)T * h->d, chunk_q = (size_t)h->L * Q * h->dm, chunk_u = (size_t)h->L * h->S;
     int c = 0;
     if (plan->dense.on) {                                     // dense operators: chunk by chunk
-        for (; c < n_chunks; ++c)
+        for (; c < n_chunks; ++c) {
+            MassTraceChunk tr_(h, c);
             if (int rc = infv_ltm_step(h, kbar + c * chunk_kbar, T, q + c * chunk_q, Q, proj, u ? u + c * chunk_u : nullptr,
                                        ctx + c * chunk_q, stream_)) return rc;
+        }
         return INFV_OK;
     }
     if (!h->has_memory && n_chunks > 0) {                     // first chunk of a document: its own operator
+        MassTraceChunk tr_(h, 0);
         if (int rc = infv_ltm_step(h, kbar, T, q, Q, proj, u, ctx, stream_)) return rc;
         c = 1;
     }
@@ -594,10 +605,12 @@ int infv_ltm_steps(infv_ltm_handle h, const float* kbar, int32_t n_chunks, int32
             Timed t_(h->prof, INFV_KERNEL_PROJECT, stream);
             HIP_TRY(launch_project(nb, h->d, h->dm, h->L, plan->inf.view(), pp, h->R_ws[0].as<float>(), h->P_ws[0].as<float>(), stream, 0));
         }
-        for (int i = 0; i < nb; ++i)
+        for (int i = 0; i < nb; ++i) {
+            MassTraceChunk tr_(h, c + i);
             if (int rc = chain_step(h, *plan, h->R_ws[0].as<float>() + (size_t)i * rows * h->d,
                                     h->P_ws[0].as<float>() + (size_t)i * rows * n_cols, sk, ss, q + (c + i) * chunk_q, Q, pp,
                                     u ? u + (c + i) * chunk_u : nullptr, ctx + (c + i) * chunk_q, stream)) return rc;
+        }
         c += nb;
     }
     return INFV_OK;
@@ -706,6 +719,9 @@ int videos_validate(VideosCall& vc) {
             if (hs[w] == hs[v]) return fail(INFV_ERR_INVALID, "%s: handle %d is also handle %d (a memory steps once per step)", name, v, w);
     }
     if (vc.total > 0 && ((vc.tokens ? !vc.k : !vc.kbar) || !vc.q || !vc.proj || !vc.ctx)) return fail(INFV_ERR_INVALID, "%s: null argument", name);
+    for (int v = 0; v < V; ++v)                    // (the first read of a handle: the checks above refuse without one)
+        if (hs[v]->mass_trace)
+            return fail(INFV_ERR_UNSUPPORTED, "%s: handle %d has a mass trace set (infv_ltm_set_mass_trace): the lockstep calls do not write it", name, v);
     for (int v = 1; v < V; ++v)
         if (!same_config(hs[0], hs[v], vc.tokens))
             return fail(INFV_ERR_INVALID, "%s: handle %d's configuration (N, H, dh, d, P, L, S, sticky%s) differs from handle 0's",
@@ -849,6 +865,7 @@ void videos_bookkeeping(const VideosCall& vc) {
         h->parts = vc.parts;
         h->lastQ = vc.Q;
         h->last_fast = false;
+        h->scores_ok = true; h->last_plan = vc.plans[v];
         if (vc.sticky && len > vc.mask_step()) { h->override_mask = 0; h->forced_mask = 0; }
     }
 }
@@ -1023,7 +1040,7 @@ int infv_ltm_pack_memory(infv_ltm_handle h, int32_t n_basis, int32_t Q, const fl
 int64_t infv_ltm_chain_state_bytes(infv_ltm_handle h, int32_t Q) {
     if (!h || Q <= 0 || Q > h->maxQ) return -1;
     return (int64_t)sizeof(float) * (kBlobHeaderInts + (int64_t)h->L * h->N * h->d + (int64_t)h->L * h->N * 2 * h->dm +
-                                     (int64_t)h->L * h->H * Q * h->N + (int64_t)h->L * h->n_bins);
+                                     (int64_t)h->L * h->H * Q * h->N + (int64_t)h->L * h->n_bins + (int64_t)h->L * h->H * Q);
 }
 
 namespace {
@@ -1052,6 +1069,7 @@ int infv_ltm_export_chain_state(infv_ltm_handle h, int32_t Q, void* blob, void* 
     HIP_TRY(hipMemcpyAsync(out + nB, h->KV[h->cur].p, nKV * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(out + nB + nKV, h->Sp[h->sc].p, nS * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(out + nB + nKV + nS, h->bin_part[h->pc].p, nM * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(out + nB + nKV + nS + nM, h->cqbuf.p, (size_t)h->L * h->H * Q * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return INFV_OK;
 }
 
@@ -1071,7 +1089,9 @@ int infv_ltm_import_chain_state(infv_ltm_handle h, int32_t Q, const void* blob, 
     HIP_TRY(hipMemcpyAsync(h->KV[h->cur].p, in + nB, nKV * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(h->Sp[h->sc].p, in + nB + nKV, nS * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(h->bin_part[h->pc].p, in + nB + nKV + nS, nM * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(h->cqbuf.p, in + nB + nKV + nS + nM, (size_t)h->L * h->H * Q * sizeof(float), hipMemcpyDeviceToDevice, stream));
     h->has_memory = true; h->parts = 1; h->lastQ = Q; h->last_fast = true; h->ctx_sum_drop();
+    h->scores_ok = true; h->last_plan = nullptr;
     h->k_stale = true;                 // the K' half came from a fast-path handle: re-projected on demand
     h->carry_scores = true;
     return INFV_OK;
@@ -1112,6 +1132,7 @@ int infv_ltm_import_state(infv_ltm_handle h, int32_t layer, const float* B, cons
     // export_chain_state nor the one-shot carry of an import_chain_state that no call consumed
     h->last_fast = false;
     h->carry_scores = false;
+    h->scores_ok = false;
     return INFV_OK;
 }
 

@@ -99,6 +99,7 @@ struct FastPipe {
         h->sc ^= 1;
         h->lastQ = Q;
         h->last_fast = true;
+        h->scores_ok = true; h->last_plan = &plan;
         counter += n;
         h->pos += (uint32_t)n;
     }
@@ -234,6 +235,20 @@ struct FastPipe {
         h->cur ^= 1;
         h->has_memory = true;
         h->ctx_sum_drop();                                      // (consolidate_join declares the finished call's sum valid)
+        return INFV_OK;
+    }
+
+    // mass trace (infv_ltm_set_mass_trace): rows [c0, c0 + n) of the call from the softmax weights in ring slots slot0.., one launch
+    // on the UC stream between the weights and the UC kernel that reads the same slots (ev_uc, recorded behind it, guards their reuse)
+    int launch_mass_trace(long c0, int n, long slot0) {
+        if (!h->mass_trace || c0 >= h->mass_cap) return INFV_OK;
+        BoxMassArgs a;
+        memset(&a, 0, sizeof(a));
+        a.src = h->alpha_ring.as<float>(); a.item_stride = (long)alpha_slot(); a.slot0 = slot0 % h->ring; a.ring = h->ring;
+        a.from_alpha = 1;
+        a.n_items = (int)(h->mass_cap - c0 < n ? h->mass_cap - c0 : n); a.L = h->L; a.rows = h->H * Q; a.N = h->N;
+        a.out = h->mass_trace + (size_t)c0 * h->L * h->N; a.out_item_stride = (long)h->L * h->N;
+        HIP_TRY(launch_box_mass(a, h->ucs));
         return INFV_OK;
     }
 };
@@ -391,6 +406,7 @@ bool fused_chain_holds(infv_ltm_handle h, const Plan& plan, int Q) {
 
 int consolidate_per_chunk(infv_ltm_handle h, const ConsolidateCall& cc) {
     for (int c = 0; c < cc.n_chunks; ++c) {
+        MassTraceChunk tr_(h, c);
         const double* uc = cc.u ? cc.u + c * cc.chunk_u : nullptr;
         if (cc.kbar_pre) {
             if (int rc = infv_ltm_step(h, cc.kbar_pre + (size_t)c * cc.T * h->d, cc.T, cc.q, cc.Q, cc.proj, uc, cc.ctx + c * cc.chunk_ctx,
@@ -590,6 +606,7 @@ int consolidate_first_chunk(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pi
         if (int rc = pipe.launch_s(st)) return rc;
         HIP_TRY(h->ev_s[2].record(stream));
         HIP_TRY(h->ev_s[2].wait_always(ucs));
+        if (int rc = pipe.launch_mass_trace(0, 1, 0)) return rc;
         if (int rc = pipe.launch_uc(plan.first, false, sb, 0, cc.ctx)) return rc;
         HIP_TRY(h->ev_uc[2].record(ucs));
     } else if (h->carry_scores && h->last_fast && h->lastQ == cc.Q) {
@@ -796,6 +813,7 @@ int uc_of(infv_ltm_handle h, const ConsolidateCall& cc, FastPipe& pipe, const Su
     }
     if (cc.persistent)
         if (int rc = pipe.launch_alpha(sb.nb, slot0, ucs, sb.b == cc.n_batches - 1)) return rc;
+    if (int rc = pipe.launch_mass_trace(sb.c0, sb.nb, slot0)) return rc;
     if (int rc = pipe.launch_uc(cc.plan->inf, true, sb, slot0, cc.ctx + (size_t)sb.c0 * cc.chunk_ctx)) return rc;
     HIP_TRY(h->ev_uc[sb.set].record(ucs));
     HIP_TRY(h->ev_r[sb.rset].record(ucs));

@@ -70,6 +70,20 @@ struct Plan {
     }
 };
 
+// Grid of infv_ltm_density (infv_ltm_set_grid_plan): the host tables, uploaded
+struct GridPlan {
+    bool on = false;
+    int M = 0, G = 0;
+    DeviceBuf seg_begin, pt_weight, pt_ptr, pt_box, pt_val;
+    GridView view() const {
+        GridView g;
+        g.M = M; g.G = G;
+        g.seg_begin = seg_begin.as<int32_t>(); g.pt_weight = pt_weight.as<float>();
+        g.pt_ptr = pt_ptr.as<int32_t>(); g.pt_box = pt_box.as<int32_t>(); g.pt_val = pt_val.as<float>();
+        return g;
+    }
+};
+
 struct Profiler {
     bool on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[INFV_KERNEL_COUNT];
@@ -187,6 +201,13 @@ struct infv_ltm_s {
     bool rng_on = false; uint64_t rng_seed = 0; uint32_t rng_stream = 0; uint32_t pos = 0;
     bool gen(const void* u) const { return !u && rng_on; }                       // this call's uniforms are generated
     infv::RngView rng_view(uint32_t at) const { infv::RngView g = infv::make_rng_view(rng_seed, rng_stream, at); g.on = rng_on ? 1u : 0u; return g; }
+    // read-outs of the attention density (ltm_density.hip).  scores_ok: the handle holds the full scores of the memory's last step
+    // (`scores`, or Sp[sc] + cqbuf after the fused chain); import_state, which re-derives nothing, clears it.
+    infv::GridPlan grid;
+    bool scores_ok = false;
+    const infv::Plan* last_plan = nullptr;     // plan of the last step (its read-out weights)
+    float* mass_trace = nullptr; long mass_cap = 0;   // box-mass trace of the multi-chunk calls (caller's device buffer [cap][L][N])
+    long mass_at = -1;                 // chunk index inside the multi-chunk call that is running its per-chunk stages, or -1
     infv::Profiler prof;
     ~infv_ltm_s() {
         for (auto& kv : plans) delete kv.second;
@@ -213,6 +234,14 @@ constexpr unsigned int kErrBlobMismatch = 0x100u;  // error-latch code (1 = chai
 // that would use or extend the memory, or at infv_ltm_sync) and forget the memory.
 int check_chain_error(infv_ltm_handle h);
 int find_plan(infv_ltm_handle h, int T, Plan** out);
+// one launch: the masses of the step that just left its full scores in h->scores -> row h->mass_at of the trace (per-chunk stages)
+int trace_masses_of_step(infv_ltm_handle h, const Plan& plan, int Q, hipStream_t stream);
+// brackets the per-chunk stages of a multi-chunk call: chunk `c` of the call is about to step
+struct MassTraceChunk {
+    infv_ltm_handle h;
+    MassTraceChunk(infv_ltm_handle h_, long c) : h(h_) { h->mass_at = h->mass_trace ? c : -1; }
+    ~MassTraceChunk() { h->mass_at = -1; }
+};
 
 inline int check_q(infv_ltm_handle h, int Q) {
     if (Q <= 0 || Q > h->maxQ) return fail(INFV_ERR_INVALID, "Q=%d outside (0, max_q=%d]", Q, h->maxQ);

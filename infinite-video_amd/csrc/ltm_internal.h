@@ -283,6 +283,32 @@ hipError_t launch_psi_grid(float* Eg, int ldg, int n_grid, long n_rows, const fl
 hipError_t launch_psi_ctx(const float* alpha, const float* KV, const ProjPtrs& proj, int Q, int N, int H, int dh, int n_layers, float* ctx,
                           hipStream_t stream);
 
+// ---- read-outs of the attention density (ltm_density.hip) ----
+// Device view of a grid plan (infv_ltm_set_grid_plan): M points in G segments, psi at every point as a CSR over boxes.
+struct GridView {
+    int32_t M, G;
+    const int32_t* seg_begin;     // [G+1]
+    const float* pt_weight;       // [M]
+    const int32_t* pt_ptr;        // [M+1]
+    const int32_t* pt_box;        // [pt_ptr[M]]
+    const float* pt_val;          // [pt_ptr[M]]
+};
+// alphas[q][h][m] of one layer from its score rows scores[h * Q + q][N] (+ cq[h * Q + q] when the rows are bias-free)
+hipError_t launch_density_grid(const float* scores, const float* cq, int H, int Q, int N, const GridView& g, float* alphas,
+                               hipStream_t stream);
+// out[i][l][n] = mean over the rows of layer l of item i of alpha[row][n]; item i sits at src + ((slot0 + i) % ring) * item_stride
+// (ring = 0: at src + i * item_stride), its layers [L][rows][N] apart
+struct BoxMassArgs {
+    const float* src; long item_stride; long slot0; int ring;
+    int from_alpha;               // 1: the rows are softmax weights already (the fused chain's alpha ring); 0: score rows
+    const float* cq;              // [L][rows] bias term of bias-free score rows, or nullptr
+    int n_items, L, rows, N;
+    const float* w; float w_out;  // the plan's read-out weights (score rows only)
+    float* out; long out_item_stride;
+};
+bool box_mass_supported(int N);
+hipError_t launch_box_mass(const BoxMassArgs& a, hipStream_t stream);
+
 // part[l][0][j] = acc[l][j] / 2^40 (fast path -> per-call path hand-over of the sticky histogram)
 hipError_t launch_acc_to_part(const unsigned long long* acc, int n_layers, int parts_pitch, float* part, hipStream_t stream);
 // bin_mass[j] = sum over parts of bin_part[layer][p][j]

@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .basis_maps import NB_BINS, NB_SAMPLES, Plan, build_gaussian_plan, build_plan, padded_N
+from .basis_maps import (NB_BINS, NB_SAMPLES, REFERENCE_DENSITY_SEGMENTS, GridPlan, Plan, build_gaussian_plan, build_grid_plan,
+                         build_plan, padded_N)
 
 ProjTensors = Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]   # (wk, bk, wv, bv)
 
@@ -424,6 +425,26 @@ class LTMEngine:
                                                         _ptr(u), int(new_doc), _ptr(out), _stream(self.device)))
         return out
 
+    def steps(self, kbar: torch.Tensor, q: torch.Tensor, projs: Sequence[ProjTensors],
+              u: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``consolidate_q`` from frame means, on the memory as it stands (infv_ltm_steps): kbar [C, T, d] fp32, q [C, L, Q, dm],
+        u [C, L, S] -> ctx [C, L, Q, dm]."""
+        _check_dev(kbar, self.device, "kbar")
+        _check_dev(q, self.device, "q")
+        if kbar.dim() != 3 or kbar.shape[2] != self.d:
+            raise ValueError(f"kbar must be fp32 [C, T, {self.d}], got {tuple(kbar.shape)}")
+        Cn, T = int(kbar.shape[0]), int(kbar.shape[1])
+        if q.dim() != 4 or q.shape[0] != Cn or q.shape[1] != self.L or q.shape[3] != self.dm or q.shape[2] > self.max_q:
+            raise ValueError(f"q must be [{Cn}, {self.L}, Q <= {self.max_q}, {self.dm}], got {tuple(q.shape)}")
+        Q = int(q.shape[2])
+        self._check_u(u, (Cn,))
+        self.ensure_plan(T)
+        out = torch.empty(Cn, self.L, Q, self.dm, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.infv_ltm_steps(self._h, _ptr(kbar), Cn, T, _ptr(q), Q, self._proj_array(projs), _ptr(u),
+                                               _ptr(out), _stream(self.device)))
+        return out
+
     # ------------------------------------------------------------------ state
     def export_state(self, layer: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """(B_past [N, d], unnormalised sticky bin masses [127]) of one layer."""
@@ -560,6 +581,53 @@ class LTMEngine:
         self._trace = (bins, probs)                       # keep the buffers alive while the library writes them
         _lib.check(self.lib.infv_ltm_set_trace(self._h, _ptr(bins), _ptr(probs), n_chunks))
         return bins, probs
+
+    # ------------------------------------------------------------------ attention density (include/infv_ltm.h, "Read-outs ...")
+    def set_grid_plan(self, segments=REFERENCE_DENSITY_SEGMENTS) -> GridPlan:
+        """Register the grid of ``density``: ``segments`` of ``(lo, hi, n_points)`` (default: the reference's three 256-point
+        segments, long_term_attention_gibbs.py:328-334).  Re-registered only when the segments change."""
+        gp = build_grid_plan(self.N, tuple(tuple(s) for s in segments))
+        if getattr(self, "_grid_plan", None) is gp:
+            return gp
+        arrs = (_np_i32(gp.seg_begin), _np_f32(gp.pt_weight), _np_i32(gp.pt_ptr), _np_i32(gp.pt_box), _np_f32(gp.pt_val))
+        s = _lib.GridPlanStruct(
+            n_points=len(gp.pt_weight), n_segments=len(gp.seg_begin) - 1, seg_begin=arrs[0].ctypes.data_as(_lib.i32p),
+            pt_weight=arrs[1].ctypes.data_as(_lib.f32p), pt_ptr=arrs[2].ctypes.data_as(_lib.i32p),
+            pt_box=arrs[3].ctypes.data_as(_lib.i32p), pt_val=arrs[4].ctypes.data_as(_lib.f32p))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.infv_ltm_set_grid_plan(self._h, C.byref(s)))
+        self._grid_plan = gp
+        return gp
+
+    def density(self, layer: int, Q: int, segments=REFERENCE_DENSITY_SEGMENTS) -> torch.Tensor:
+        """The reference's ``alphas`` of the memory's last step of ``layer`` (infv_ltm_density): device fp32 ``[Q, 1, H, M]``,
+        the layout the reference pickles (:337)."""
+        gp = self.set_grid_plan(segments)
+        out = torch.empty(Q, 1, self.H, len(gp.pt_weight), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.infv_ltm_density(self._h, layer, Q, _ptr(out), _stream(self.device)))
+        return out
+
+    def masses(self, layer: int, Q: int) -> torch.Tensor:
+        """What the read-out of the last step used: the mean over heads and queries of the softmax weights of every basis
+        function (infv_ltm_masses), device fp32 ``[N]``."""
+        out = torch.empty(self.Np, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.infv_ltm_masses(self._h, layer, Q, _ptr(out), _stream(self.device)))
+        return out[:self.N]
+
+    def set_mass_trace(self, n_chunks: int) -> Optional[torch.Tensor]:
+        """Record the masses of every chunk of the following ``steps`` / ``consolidate*`` calls (infv_ltm_set_mass_trace):
+        returns the device tensor ``[n_chunks, L, N]`` fp32, NaN-initialised, that chunk c < n_chunks of a call writes row c
+        of; ``n_chunks = 0`` stops tracing."""
+        if n_chunks <= 0:
+            self._mass_trace = None
+            _lib.check(self.lib.infv_ltm_set_mass_trace(self._h, None, 0))
+            return None
+        buf = torch.full((n_chunks, self.L, self.Np), float("nan"), device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.infv_ltm_set_mass_trace(self._h, _ptr(buf), n_chunks))
+        self._mass_trace = buf                             # keep the buffer alive while the library writes it
+        return buf[..., :self.N]
 
     def sync(self):
         """Wait for the engine's work on the current stream and raise if a device-side failure was latched

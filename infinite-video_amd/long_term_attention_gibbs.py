@@ -14,8 +14,13 @@ Differences from the reference, all deliberate:
 
 * ``get_basis`` is not rebuilt on every call: the operator tables depend only on
   ``(T, num_basis, tau)`` and are cached (``basis_maps.build_plan``).
-* The density-pickle side effect of the Video-LLaMA variant (reference :320-345, writes
-  ``./alphas_uniform`` on every call, result unused by the model) is not reproduced.
+* The density read-out of the Video-LLaMA variant (reference :320-345: on every call, the attention density of the step on a
+  768-point grid, pickled to ``./alphas_uniform`` for ``relevant_frames.py``; unused by the model) is opt-in:
+  ``output_density = False`` by default, and the forward is then what it always was.  With ``output_density = True`` every
+  forward leaves ``self.alphas`` (``[Q, 1, H, 768]`` fp32 on the device, the reference's layout; one more kernel launch,
+  ``infv_ltm_density``); with ``density_path`` set as well it pickles ``alphas.cpu()`` there as the reference does -- set it
+  to ``"./alphas_uniform"`` and ``relevant_frames.py`` runs unchanged.  The kernel subtracts each segment's maximum before ``exp``;
+  the reference does not (:248) and overflows where this does not.
 * The Gibbs draw consumes torch's global **CPU** generator exactly like the reference's CPU path:
   512 float64 uniforms for the bin draw, then 512 more for the degenerate in-bin draw (:204-206).
   Seed it with ``torch.manual_seed`` to reproduce the reference CPU run draw for draw.
@@ -46,6 +51,10 @@ _pool_cache = {"ref": None, "version": -1, "kbar": None}
 class LongTermAttention(nn.Module):
     tokens_per_frame = 32      # reference :291,304 hard-codes k.reshape(B, klen, 32, 768)
     encoder_width = 768
+    # reference :320-343 (always on there): leave the step's density in self.alphas; pickle it to density_path when that is set
+    output_density = False
+    density_path: Optional[str] = None
+    alphas: Optional[torch.Tensor] = None
 
     def __init__(self, head_size: int, length: int, target_len: int, attn_func: str, attn_num_basis: int,
                  continuous: bool, attn_drop: float, infinite_memory: bool, n_layers: int,
@@ -255,6 +264,15 @@ class LongTermAttention(nn.Module):
             ev.record(torch.cuda.current_stream(device))
             ring["ev"][g] = ev
 
+    def _read_density(self, eng: LTMEngine, qlen: int):
+        """``alphas`` of the step just taken (reference :328-337), and its pickle (:342-343) when ``density_path`` is set."""
+        with torch.cuda.device(eng.device):
+            self.alphas = eng.density(0, qlen)
+        if self.density_path:
+            import pickle
+            with open(self.density_path, "wb") as f:
+                pickle.dump(self.alphas.cpu(), f)
+
     # ------------------------------------------------------------------ forward
     def forward(self, k, q, new_doc, layer_n):
         """k [1, T*P, d] frame tokens, q [1, Q, H*dh] -> [1, Q, H*dh]   (reference :288-346)."""
@@ -326,6 +344,8 @@ class LongTermAttention(nn.Module):
             _pool_cache["ref"], _pool_cache["version"], _pool_cache["kbar"] = weakref.ref(k), k._version, kbar
         if sticky_step:
             self._uniforms_used(k.device)
+        if self.output_density:
+            self._read_density(eng, qlen)
         self.count += 1
         return ctx if q.dtype == torch.float32 else ctx.to(q.dtype)
 
