@@ -16,6 +16,9 @@
 namespace infv {
 
 // C[z][m][n] = sum_k A[z][m][k] * (TB ? B[z][n][k] : B[z][k][n]);  any M, Nc, K (tiles and k are masked)
+// The k mask (k < K) cannot be reached from the ABI: dense_step's K is the handle's basis count (padded to a multiple of 16) or
+// the 1000 points of the read-out grid, both multiples of 4.  The row mask (M = L*H*Q, or 128 / S positions) and the column mask
+// (Nc = 129 edges, 1000 grid points, d, N) are swept by tests/test_dense_sweep_gpu.py.
 template <bool TB>
 __global__ __launch_bounds__(256) void psi_gemm_kernel(const float* __restrict__ A, int lda, long sA, const float* __restrict__ B, int ldb, long sB,
                                                        float* __restrict__ C, int ldc, long sC, int M, int Nc, int K) {

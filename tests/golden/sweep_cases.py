@@ -4,7 +4,9 @@ A data module like ``cases.py`` -- but it holds no fixtures: every input is rege
 ``infinite_video_amd.synth`` and the expected values come from ``oracle.ltm_oracle.ClosedFormOracle`` /
 ``oracle.qformer_oracle`` at test time.  ``tests/test_config_sweep_cpu.py`` checks the table itself (the two oracles
 agree at every point, the host plans match the oracle's maps, every gate is crossed in both directions);
-``tests/test_config_sweep_gpu.py`` drives every point through the library.
+``tests/test_config_sweep_gpu.py`` drives every point through the library.  Every point here has a SPARSE plan; the dense and
+general-psi plans (most ``num_basis`` values: every N off 16, most multiples of 16, the Gaussian family) are swept in
+``dense_sweep_cases.py`` / ``tests/test_dense_sweep_cpu.py`` / ``tests/test_dense_sweep_gpu.py``.
 
 The library picks its kernels from the shape through a cascade of host-side gates.  They are written down ONCE here, as
 plain Python predicates over a point and its host plan (``GATES``), next to the C expression they mirror.  Every point
@@ -294,7 +296,7 @@ def _one_factor() -> List[SweepPoint]:
     pts += [_p("L1", "one layer (L*H*Q = 384)", "fast", L=1), _p("L3", "L*H*Q = 1152", "fast", L=3),
             _p("L5", "L*H*Q = 1920", "fast", L=5), _p("L8", "INFV_LTM_MAX_LAYERS", "fast", L=8),
             _p("vc2_wgs", "VideoChat2 H 12, Q 96, L 6: 432 role-S workgroups > 384", "fast", Q=96, L=6)]
-    # N at S 512 (48-class dense values are covered by the golden cases; 192 plans dense)
+    # N at S 512 (48, 96, 192, ... plan dense: dense_sweep_cases.py)
     pts += [_p("N16", "44 slots per box > kMaxTabw, N % 64 != 0", "stages", N=16),
             _p("N32", "24 slots per box > kMaxTabw", "stages", N=32),
             _p("N128", "tabw 8", "fast", N=128),
@@ -374,7 +376,7 @@ def _random_sample() -> List[SweepPoint]:
         pt = replace(SMALL, name=f"rand{len(pts):02d}", gate="random combination", families="", **kw)
         try:
             if basis_maps.build_plan(pt.T, pt.N, pt.tau, pt.S).dense:
-                continue                                      # (dense plans: the golden cases' territory)
+                continue                                      # (dense plans: swept in dense_sweep_cases.py)
         except (basis_maps.UnsupportedBasis, ValueError):
             continue
         if device_bytes(pt) > 2 << 30:
