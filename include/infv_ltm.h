@@ -452,6 +452,62 @@ int infv_ltm_masses(infv_ltm_handle h, int32_t layer, int32_t Q, float* mass, vo
  * set on a layer's handle is honoured by it without further work; its batched calls run the lockstep entry points and refuse. */
 int infv_ltm_set_mass_trace(infv_ltm_handle h, float* mass_all, int64_t capacity_chunks);
 
+/* ---- Source weights: the memory traced back to its frames (additive in ABI 6) ----
+ * The masses above say how much the read-out attends to each BASIS FUNCTION.  The reference's relevant_frames.py:53-69 turns that
+ * into frames by taking grid point m of segment i of `alphas` for frame m + 256 * i of the video -- right only for a memory that
+ * was never consolidated: after the first sticky update every basis function mixes resampled older content with new frames.
+ * The update is linear in the frame means (long_term_attention_gibbs.py:207-216 in closed form: B_new[n] = val[n] * (sum of the
+ * resampled old rows of box n + sum of its new frames)), so there is a W with B[n] = sum over sources of W[n][source] *
+ * kbar[source], and W obeys the same recurrence with one-hot rows in place of the frame means.
+ * Columns of W are SOURCES: groups of g = frames_per_source consecutive frames (g >= 1, g divides T).  Frame f of chunk c of the
+ * call belongs to column col_begin + (c * T + f) / g.  For one layer and chunk c, W_old being the matrix before the chunk:
+ *   first chunk of a document (new_doc and c == 0):
+ *       W_new[n][m] = first_box_val[n] * cnt_first(n, m)
+ *     cnt_first = number of frames of box n's [first_row_begin, first_row_end) whose column is m; every column below col_begin
+ *     becomes 0 (the document's memory was reset);
+ *   otherwise, with idx[s] = bin_box[bins[c][l][s]] on a sticky handle and uniform_idx[s] on others:
+ *       acc = 0
+ *       for s in inf_old_slot[inf_old_ptr[n] : inf_old_ptr[n+1]], in stored order:
+ *           if idx[s] >= 0: acc += W_old[idx[s]][m]
+ *       acc += float(cnt_inf(n, m))          -- the box's new frames that fall in column m, added LAST as one fp32 number
+ *       W_new[n][m] = inf_box_val[n] * acc
+ * This order is part of the contract: fp32 additions in that order and one multiplication, nothing an FMA could contract;
+ * density.source_weights(dtype=float32) restates it in numpy and equals the device bit for bit.  Boxes with no rows and the pad
+ * basis functions of a padded num_basis keep W = 0.
+ * A bin outside [0, n_bins - 1) -- an unwritten trace row holds -1 -- is never used as an index: it resamples a zero row.
+ * bad_bins[l] (if given) is increased by the number of such bins among the S bins of every resampling chunk of layer l (every
+ * chunk but a document's first), counted once per layer whatever the number of columns; the caller zeroes it.
+ * With mass_all (the trace infv_ltm_set_mass_trace wrote during the same call) the pass also writes the attention map of the
+ * video while it holds W_c, the matrix after chunk c:
+ *       attn_all[c][l][m] = sum_n mass_all[c][l][n] * W_c[n][m]
+ * accumulated in float64 (eight partial sums on num_basis <= 256, sixteen above: partial k adds rows k, k + 8 (16), ... in
+ * increasing order; the partials are added in order from 0) and rounded once.  It is raw, not normalised: rows do not sum to 1
+ * because of the ridge and readout_w_out.
+ *   bins_all   DEVICE [C][L][S], the layout infv_ltm_set_trace writes -- which the fused chain, the per-chunk stages and the
+ *              lockstep calls all fill; NULL iff the handle is not sticky
+ *   W          DEVICE [L][num_basis][ld], 16-byte aligned, in/out: columns < col_begin are read unless new_doc; columns
+ *              [col_begin, col_begin + C * T / g) need no initialisation; columns beyond are not touched
+ *   mass_all   DEVICE [C][L][num_basis] or NULL;  attn_all DEVICE [C][L][ld] or NULL (NULL iff mass_all is NULL): every column
+ *              below col_begin + C * T / g of every chunk is written, the rest not touched
+ * ONE launch on `stream`: a workgroup per (tile of 64 columns -- 32 when num_basis > 256 --, layer) keeps its slice of W in LDS
+ * over the whole call.  It reads nothing of the handle but the plan tables for T, and neither reads nor changes the memory.
+ * Carrying W and col_begin + C * T / g from one call into the next equals one call over all the chunks, bit for bit.
+ * Refused before any device work, nothing written -- INFV_ERR_INVALID: null descriptor or W, C < 1, g < 1 or g not dividing T,
+ * negative col_begin, ld below col_begin + C * T / g or no multiple of 4, W not 16-byte aligned, bins_all NULL on a sticky handle
+ * (or given on another), exactly one of mass_all / attn_all; INFV_ERR_STATE: no plan registered for T; INFV_ERR_UNSUPPORTED: a
+ * dense or general-psi plan for T (they resample psi-combinations of two boxes through a dense operator: another kernel), or
+ * num_basis above 512. */
+typedef struct {
+    int32_t n_chunks;           /* C >= 1 */
+    int32_t T;                  /* frames per chunk */
+    int32_t new_doc;            /* chunk 0 starts a document */
+    int32_t frames_per_source;  /* g */
+    int64_t col_begin;          /* column of the call's first source */
+    int64_t ld;                 /* row stride of W and attn_all in floats: multiple of 4, >= col_begin + C*T/g */
+} infv_ltm_sources_desc;
+int infv_ltm_source_weights(infv_ltm_handle h, const infv_ltm_sources_desc* d, const int32_t* bins_all, float* W,
+                            const float* mass_all, float* attn_all, int32_t* bad_bins, void* stream);
+
 /* Synchronises `stream`, then reports a latched device-side failure (see Conventions). */
 int infv_ltm_sync(infv_ltm_handle h, void* stream);
 

@@ -73,6 +73,12 @@ class GridPlanStruct(C.Structure):
     ]
 
 
+class SourcesDesc(C.Structure):
+    """infv_ltm_sources_desc: one call of infv_ltm_source_weights."""
+    _fields_ = [("n_chunks", C.c_int32), ("T", C.c_int32), ("new_doc", C.c_int32), ("frames_per_source", C.c_int32),
+                ("col_begin", C.c_int64), ("ld", C.c_int64)]
+
+
 class Proj(C.Structure):
     _fields_ = [("wk", C.c_void_p), ("bk", C.c_void_p), ("wv", C.c_void_p), ("bv", C.c_void_p)]
 
@@ -191,6 +197,8 @@ _SIGNATURES = {
     "infv_ltm_density": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "infv_ltm_masses": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "infv_ltm_set_mass_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "infv_ltm_source_weights": (C.c_int, [C.c_void_p, C.POINTER(SourcesDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "infv_ltm_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
     "infv_ltm_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "infv_ltm_profile_read": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

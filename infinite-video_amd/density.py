@@ -60,3 +60,101 @@ def box_masses(scores, readout_w, w_out: float) -> np.ndarray:
     order) runs in float64 too, so the order does not show at fp32."""
     a = box_weights(scores, readout_w, w_out)
     return a.reshape(-1, a.shape[-1]).mean(0)
+
+
+# ---- source weights: the memory traced back to its frames (infv_ltm_source_weights; kernel: csrc/ltm_sources.hip) ----
+# The sparse update is linear in the frame means (long_term_attention_gibbs.py:207-216 in closed form), so B[n] = sum over sources
+# of W[n][source] * kbar[source] with a W that obeys the update's own recurrence on one-hot rows.  The reference's
+# relevant_frames.py:53-69 reads grid point m of segment i of ``alphas`` as frame m + 256 * i, which holds only for a memory that
+# was never consolidated.  include/infv_ltm.h states the recurrence and its order; the functions below restate it in numpy.
+def _source_steps(plan, bins, n_chunks, new_doc, W, col_begin, frames_per_source, dtype):
+    """Yields ``(c, W_c)`` for the chunks of one call; ``W_c`` [N, M] is the matrix after chunk c (a fresh array each time)."""
+    T, N = int(plan.T), int(plan.N)
+    if plan.dense or plan.psi:
+        raise ValueError("source weights exist for sparse box plans only (dense and general-psi plans mix boxes through a dense operator)")
+    g = T if frames_per_source is None else int(frames_per_source)
+    C, col_begin = int(n_chunks), int(col_begin)
+    if C < 1 or g < 1 or T % g or col_begin < 0:
+        raise ValueError("need n_chunks >= 1, frames_per_source >= 1 dividing T, col_begin >= 0")
+    per = T // g
+    M = col_begin + C * per
+    cur = np.zeros((N, M), dtype=dtype)
+    if not new_doc and col_begin:
+        if W is None or np.shape(W)[0] != N or np.shape(W)[1] < col_begin:
+            raise ValueError(f"W must be [{N}, >= {col_begin}] to continue a document")
+        cur[:, :col_begin] = np.asarray(W)[:, :col_begin]
+    if bins is not None:
+        bins = np.asarray(bins)
+        if bins.shape != (C, plan.S):
+            raise ValueError(f"bins must be [{C}, {plan.S}] (one layer of the draw trace), got {bins.shape}")
+    ptr, slot = plan.inf_old_ptr, plan.inf_old_slot
+    count = np.diff(ptr)
+    n_draw = len(plan.bin_box) - 1                             # the draw has n_bins - 1 outcomes
+
+    def injected(row_box, row_begin, row_end, c):
+        cnt = np.zeros((N, per), dtype=np.int64)
+        for b, lo, hi in zip(row_box, row_begin, row_end):
+            np.add.at(cnt[b], np.arange(lo, hi) // g, 1)
+        return cnt.astype(dtype), col_begin + c * per
+
+    for c in range(C):
+        live = col_begin + (c + 1) * per                       # columns at and beyond are still zero
+        new = np.zeros((N, M), dtype=dtype)
+        if new_doc and c == 0:
+            cnt, at = injected(plan.first_row_box, plan.first_row_begin, plan.first_row_end, c)
+            new[:, at:at + per] = plan.first_box_val.astype(dtype)[:, None] * cnt
+        else:
+            if bins is not None:
+                b = bins[c].astype(np.int64)
+                ok = (b >= 0) & (b < n_draw)                   # a bin out of range is never an index: a zero row
+                idx = np.where(ok, plan.bin_box[np.where(ok, b, 0)], -1)
+            else:
+                idx = plan.uniform_idx
+            acc = np.zeros((N, live), dtype=dtype)
+            for j in range(int(count.max(initial=0))):         # j-th stored slot of every box that has one: the CSR order
+                boxes = np.flatnonzero(count > j)
+                src = idx[slot[ptr[boxes] + j]]
+                boxes, src = boxes[src >= 0], src[src >= 0]
+                acc[boxes] = acc[boxes] + cur[src, :live]
+            cnt, at = injected(plan.inf_row_box, plan.inf_row_begin, plan.inf_row_end, c)
+            acc[:, at:at + per] = acc[:, at:at + per] + cnt    # the new frames' count: added last, one number
+            new[:, :live] = plan.inf_box_val.astype(dtype)[:, None] * acc
+        cur = new
+        yield c, cur
+
+
+def source_weights(plan, bins, n_chunks, new_doc=True, W=None, col_begin=0, frames_per_source=None, dtype=np.float64):
+    """``W`` [N, col_begin + n_chunks * T / g] of ONE layer after the call's chunks: ``B[n] = sum_m W[n][m] * kbar[source m]``, source
+    m being frames ``[m * g, (m + 1) * g)`` of the video, ``g = frames_per_source`` (default T: one column per chunk).
+    ``bins`` [n_chunks, S]: the layer's rows of the draw trace (``LTMEngine.set_trace``), ``None`` for a memory that is not sticky.
+    ``new_doc=False`` continues from ``W`` [N, >= col_begin].  With ``dtype=np.float64`` this is the float64 recurrence; with
+    ``np.float32`` it is the ordered fp32 form that ``infv_ltm_source_weights`` equals bit for bit."""
+    out = None
+    for _, out in _source_steps(plan, bins, n_chunks, new_doc, W, col_begin, frames_per_source, dtype):
+        pass
+    return out
+
+
+def source_attention(mass_trace, plan, bins, n_chunks, new_doc=True, W=None, col_begin=0, frames_per_source=None,
+                     dtype=np.float64, normalise=False):
+    """The attention map of the video, chunk by chunk: ``attn[c][m] = sum_n mass_trace[c][n] * W_c[n][m]`` in float64, with
+    ``W_c`` the source weights after chunk c -- the mirror of ``attn_all``.  ``mass_trace`` [n_chunks, N]: one layer of
+    ``LTMEngine.set_mass_trace``.  Raw by default (rows do not sum to 1: the ridge and the read-out's ``w_out``);
+    ``normalise=True`` divides every row by its sum.  Returns ``(W, attn)``."""
+    mass = np.asarray(mass_trace, dtype=np.float64)
+    rows, out = [], None
+    for c, out in _source_steps(plan, bins, n_chunks, new_doc, W, col_begin, frames_per_source, dtype):
+        rows.append(mass[c] @ out.astype(np.float64))
+    attn = np.stack(rows)
+    if normalise:
+        attn = attn / attn.sum(-1, keepdims=True)
+    return out, attn
+
+
+def top_sources(attn_row, k, frames_per_source=1):
+    """The k most attended sources of one row of the attention map, most attended first:
+    ``[(source, first_frame, end_frame, weight), ...]`` with the source's frames ``[first_frame, end_frame)`` of the video."""
+    a = np.asarray(attn_row, dtype=np.float64).reshape(-1)
+    g = int(frames_per_source)
+    order = np.argsort(-a, kind="stable")[:max(int(k), 0)]
+    return [(int(m), int(m) * g, (int(m) + 1) * g, float(a[m])) for m in order]

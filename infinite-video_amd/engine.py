@@ -629,6 +629,66 @@ class LTMEngine:
         self._mass_trace = buf                             # keep the buffer alive while the library writes it
         return buf[..., :self.N]
 
+    def source_weights(self, bins: Optional[torch.Tensor], T: int, new_doc: bool = True, W: Optional[torch.Tensor] = None,
+                       col_begin: int = 0, frames_per_source: Optional[int] = None, mass: Optional[torch.Tensor] = None,
+                       normalise: bool = False):
+        """Trace the memory back to the frames of the video (infv_ltm_source_weights; ``density.source_weights`` is its numpy
+        mirror): ``W`` [L, N, M] with ``B[l][n] = sum_m W[l][n][m] * kbar[source m]``, source m being frames
+        ``[m * g, (m + 1) * g)``, ``g = frames_per_source`` (default T: one column per chunk), ``M = col_begin + C * T / g``.
+
+        ``bins`` [C, L, S] int32: the draws of the C chunks as ``set_trace`` recorded them (an engine that is not sticky reads only
+        the chunk count ``bins.shape[0]`` of it, or takes ``None`` and the count from ``mass``).  ``new_doc=False`` continues a
+        document: pass the ``W`` the call before returned and its column count as ``col_begin``; the result equals one call over
+        all the chunks.  With ``mass`` [C, L, N] (``set_mass_trace`` of the same call) also returns ``attn`` [C, L, M], the
+        attention map of the video after every chunk -- raw, or every row divided by its sum with ``normalise``.
+        The call is one launch, but this wrapper then reads a counter of out-of-range bins back: a HOST SYNC.  Any such bin (an
+        unwritten trace row holds -1) raises ``ValueError``; the raw entry point resamples a zero row for it instead."""
+        if bins is None and mass is None:
+            raise ValueError("bins or mass must say how many chunks the call has")
+        C_ = int(bins.shape[0] if bins is not None else mass.shape[0])
+        g = int(T if frames_per_source is None else frames_per_source)
+        if C_ < 1 or g < 1 or T % g or col_begin < 0:
+            raise ValueError("need at least one chunk, frames_per_source >= 1 dividing T, col_begin >= 0")
+        self.ensure_plan(T)
+        if self.sticky:
+            if bins is None or tuple(bins.shape) != (C_, self.L, self.S):
+                raise ValueError(f"a sticky engine needs bins [{C_}, {self.L}, {self.S}]")
+            _check_dev(bins, self.device, "bins", torch.int32)
+        else:
+            bins = None
+        if mass is not None:
+            if tuple(mass.shape) != (C_, self.L, self.N):
+                raise ValueError(f"mass must be [{C_}, {self.L}, {self.N}]")
+            if self.Np != self.N:
+                mass = torch.nn.functional.pad(mass, (0, self.Np - self.N))
+            mass = mass.contiguous()
+            _check_dev(mass, self.device, "mass")
+        M = int(col_begin) + C_ * (T // g)
+        ld = (M + 3) // 4 * 4
+        buf = torch.empty(self.L, self.Np, ld, device=self.device, dtype=torch.float32)
+        if not new_doc and col_begin:
+            if W is None or tuple(W.shape[:2]) != (self.L, self.N) or W.shape[2] < col_begin:
+                raise ValueError(f"W must be [{self.L}, {self.N}, >= {col_begin}] to continue a document")
+            buf[:, :self.N, :col_begin] = W[:, :, :col_begin]
+            buf[:, self.N:, :col_begin] = 0
+        attn = torch.empty(C_, self.L, ld, device=self.device, dtype=torch.float32) if mass is not None else None
+        bad = torch.zeros(self.L, device=self.device, dtype=torch.int32)
+        desc = _lib.SourcesDesc(n_chunks=C_, T=int(T), new_doc=int(bool(new_doc)), frames_per_source=g,
+                                col_begin=int(col_begin), ld=ld)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.infv_ltm_source_weights(self._h, C.byref(desc), _ptr(bins), _ptr(buf), _ptr(mass), _ptr(attn),
+                                                        _ptr(bad), _stream(self.device)))
+        n_bad = bad.cpu()                                  # (the host sync)
+        if int(n_bad.sum()):
+            raise ValueError(f"bins outside [0, {NB_BINS - 1}) per layer: {n_bad.tolist()} (an unwritten trace row holds -1)")
+        Wout = buf[:, :self.N, :M]
+        if attn is None:
+            return Wout
+        attn = attn[:, :, :M]
+        if normalise:
+            attn = attn / attn.sum(-1, keepdim=True)
+        return Wout, attn
+
     def sync(self):
         """Wait for the engine's work on the current stream and raise if a device-side failure was latched
         (the persistent chain kernel of consolidate() timed out: its outputs are invalid)."""
