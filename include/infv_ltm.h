@@ -17,7 +17,22 @@
  *     the sticky histogram) and its workspaces;
  *   - all work is enqueued asynchronously on `stream` (a hipStream_t passed as void*,
  *     NULL = the null stream); no entry point synchronises except infv_ltm_sync and the
- *     get calls that copy to HOST buffers;
+ *     get calls that copy to HOST buffers, with the host waits listed below;
+ *   - `stream` may be any stream, a non-blocking side stream included (tests/test_stream_order_gpu.py runs every entry point
+ *     that takes one behind a delay on such a stream).  What a caller may rely on: a call reads its device inputs no earlier than
+ *     the work queued on `stream` before it, and when it returns, work queued on `stream` behind it may overwrite every input and
+ *     read every output and every exported state -- the worker streams the library forks over (infv_ltm_consolidate*: three
+ *     process-wide non-blocking streams shared by all handles of a device) start behind `stream` and are joined into it before the
+ *     call returns.  Handles on different streams do not disturb each other's results.
+ *     Host waits, none of which changes a result: a call that has to GROW a workspace synchronises the device first (the first
+ *     call of a handle, or of a larger shape; a handle that has run a shape once runs it again without a host wait);
+ *     infv_ltm_set_plan / _set_dense_plan / _set_psi_plan / _set_grid_plan upload host tables; infv_ltm_set_probs and
+ *     infv_ltm_set_bins, which take no stream, synchronise the device and then copy, so they take effect in PROGRAM order: steps
+ *     issued before the setter use the old override (or none), steps issued after it the new one; infv_ltm_destroy waits for
+ *     the handle's work.
+ *     Not promised: ordering between calls of ONE handle on DIFFERENT streams.  The memory, the workspaces and the override
+ *     buffers are ordered by the stream of the call alone, so a caller who moves a handle to another stream orders the two
+ *     streams itself (an event, or infv_ltm_sync) before the first call on the new one;
  *   - a failure that only shows on the device (the persistent chain kernel of
  *     infv_ltm_consolidate timed out waiting for workgroups that never became resident, e.g.
  *     on a partitioned or shared GPU) is latched in host-visible memory: infv_ltm_sync and
@@ -373,7 +388,8 @@ int infv_ltm_reproject(infv_ltm_handle h, const infv_ltm_proj* proj, void* strea
 int infv_ltm_get_draw(infv_ltm_handle h, int32_t layer, int32_t* bins, int32_t* idx, float* probs,
                       float* scores, void* stream);
 /* Teacher forcing for tests: the next step of `layer` draws from these HOST probs[n_bins-1]
- * instead of the ones derived from its own scores (one-shot). */
+ * instead of the ones derived from its own scores (one-shot).  No stream argument: this setter and infv_ltm_set_bins synchronise
+ * the device, then copy -- steps already queued on any stream keep the override they were issued under (see Conventions). */
 int infv_ltm_set_probs(infv_ltm_handle h, int32_t layer, const float* probs);
 /* Forced draw (one-shot, per-call step/forward only): the next step of `layer` resamples the
  * rows of these HOST bins[S] (values in [0, n_bins-1)) instead of its own draw.  The step still

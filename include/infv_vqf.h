@@ -5,6 +5,15 @@
  * Python mirror (infinite_video_amd/video_qformer.py) binds with ctypes.  Plain pointers and sizes only; all
  * pointers are DEVICE pointers (fp32, row-major) unless stated; every call is asynchronous on `stream`.  Only the frame tokens
  * (`frames`) may be fp16, bf16 or fp8 e4m3 instead (infv_vqf_set_token_dtype).
+ * `stream` may be a non-blocking side stream, under the contract of infv_ltm.h (Conventions): inputs are read behind the work queued
+ * on `stream` before the call, and inputs, outputs and the memories belong to `stream` again when the call returns -- the layer-major
+ * calls run the later layers' memories on the library's shared worker stream behind an event of `stream` and join it before the
+ * merge.  Host waits beside workspace growth: infv_vqf_vc_embed and infv_vqf_vc_encode_img stage the instruction ids through one
+ * pinned buffer per handle and wait for the previous call's copy out of it before rewriting it; under a reduced linear or
+ * attention precision the first call of a NEW weights epoch drops the cached weight planes (device synchronisation) and
+ * allocates the new ones, later calls of that epoch reuse them without a host wait; infv_vqf_layernorm_tokens keeps its row
+ * statistics in one process-wide buffer and orders calls on different streams with an event (no host wait, but such calls
+ * serialise); infv_vqf_destroy synchronises the device.  Not promised: one handle on two streams without the caller ordering them.
  * Errors: int status as in infv_ltm.h, message via infv_ltm_last_error().
  *
  * Scope: the query-token-only, eval-mode, all-ones-mask case the video Q-former is run in

@@ -1165,6 +1165,9 @@ int infv_ltm_get_draw(infv_ltm_handle h, int32_t layer, int32_t* bins, int32_t* 
 int infv_ltm_set_probs(infv_ltm_handle h, int32_t layer, const float* probs) {
     if (int rc = check_handle(h)) return rc;
     if (layer < 0 || layer >= h->L || !probs) return fail(INFV_ERR_INVALID, "set_probs: bad arguments");
+    // The setter has no stream: it takes effect in PROGRAM order.  A step queued on a non-blocking stream may still be waiting to
+    // read an earlier override, and the null stream's copy below would overtake it.
+    HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h->probs_override.as<float>() + (size_t)layer * h->n_bins, probs,
                       (h->n_bins - 1) * sizeof(float), hipMemcpyHostToDevice));
     h->override_mask |= 1u << layer;
@@ -1176,6 +1179,7 @@ int infv_ltm_set_bins(infv_ltm_handle h, int32_t layer, const int32_t* bins) {
     if (layer < 0 || layer >= h->L || !bins) return fail(INFV_ERR_INVALID, "set_bins: bad arguments");
     for (int s = 0; s < h->S; ++s)
         if (bins[s] < 0 || bins[s] >= h->n_bins - 1) return fail(INFV_ERR_INVALID, "set_bins: bins[%d]=%d outside [0,%d)", s, bins[s], h->n_bins - 1);
+    HIP_TRY(hipDeviceSynchronize());                            // program order, as in infv_ltm_set_probs: a queued step may still read the old bins
     HIP_TRY(hipMemcpy(h->bins_forced.as<int32_t>() + (size_t)layer * h->S, bins, h->S * sizeof(int32_t), hipMemcpyHostToDevice));
     h->forced_mask |= 1u << layer;
     return INFV_OK;
