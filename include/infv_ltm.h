@@ -463,10 +463,34 @@ int infv_ltm_masses(infv_ltm_handle h, int32_t layer, int32_t Q, float* mass, vo
  * shapes the fused chain does not hold) add exactly ONE per chunk, from the chunk's full scores: there the last row has the
  * bits of infv_ltm_masses called afterwards.  No existing kernel changes, no event or allocation is added.
  * infv_ltm_consolidate_videos, infv_ltm_steps_videos and infv_ltm_steps_videos_from refuse a handle with a trace set
- * (INFV_ERR_UNSUPPORTED before any device work, every memory untouched).  The video Q-former drives these same handles:
+ * (INFV_ERR_UNSUPPORTED before any device work, every memory untouched; their own trace is the packed one of
+ * infv_ltm_set_videos_mass_trace below).  The video Q-former drives these same handles:
  * infv_vqf_encode_video steps each layer's handle with infv_ltm_consolidate / _pooled / infv_ltm_steps (infv_vqf.h), so a trace
  * set on a layer's handle is honoured by it without further work; its batched calls run the lockstep entry points and refuse. */
 int infv_ltm_set_mass_trace(infv_ltm_handle h, float* mass_all, int64_t capacity_chunks);
+
+/* Packed box-mass trace of the LOCKSTEP calls (additive in ABI 6) -- a call-level trace with its own setter; the refusal above
+ * stays.  While set, every infv_ltm_consolidate_videos / infv_ltm_steps_videos / infv_ltm_steps_videos_from call whose handle 0
+ * is `lead` writes mass_all[c][L][num_basis] (DEVICE buffer owned by the caller) for every packed chunk c < capacity_chunks,
+ * where c indexes the call's packed arrays exactly as ctx does: chunk i of video v is row cu[v] + i, whatever the number of
+ * videos (calls of more than 256 run in groups; the row index does not depend on group or rank).  Every chunk writes, a video's
+ * first included; rows at and beyond the capacity are not touched; capacity_chunks = 0 clears the trace.
+ * ONE added launch per lockstep step while set, none otherwise (a workgroup per 64 columns, layer and video still running, 8
+ * waves), issued directly behind the step's attend launch on the call's stream: it reads each video's full score rows, key bias
+ * included, which stream order protects from the next step's attend.  The per-row arithmetic and the order of the sums are those
+ * stated at infv_ltm_masses, so the last row of each video has the bits of infv_ltm_masses called on that video's handle after
+ * the call, and a video's rows do not depend on what else is in the batch.  No existing kernel changes.
+ * Shapes the lockstep kernels do not take (dense plans, num_basis above 256, ...) run each video's own per-call path; there the
+ * trace is served through that path's per-chunk trace on the video's slice mass_all + cu[v] * L * num_basis with the capacity
+ * that remains, so the rows have the bits infv_ltm_set_mass_trace would have given that video's own call.
+ * Refusals, before any device work, every memory untouched: by the setter, a handle with a general-psi plan or num_basis above
+ * 512 (INFV_ERR_UNSUPPORTED, as infv_ltm_set_mass_trace), a negative capacity or a NULL buffer with a positive one
+ * (INFV_ERR_INVALID); by the lockstep calls, a handle other than hs[0] that carries a videos trace (INFV_ERR_INVALID: a trace
+ * that would silently stay empty is worse than a refusal); infv_ltm_set_psi_plan refuses a handle with a videos trace set.
+ * The batched video Q-formers (infv_vqf_encode_videos, infv_vqf_vc_encode_videos*, infv_vqf_vc_encode_streams*,
+ * infv_vqf_vc_encode_img) drive these same entry points with video 0's handle of the layer as handle 0, so a trace set on that
+ * handle is honoured by them without further work. */
+int infv_ltm_set_videos_mass_trace(infv_ltm_handle lead, float* mass_all, int64_t capacity_chunks);
 
 /* ---- Source weights: the memory traced back to its frames (additive in ABI 6) ----
  * The masses above say how much the read-out attends to each BASIS FUNCTION.  The reference's relevant_frames.py:53-69 turns that
@@ -523,6 +547,42 @@ typedef struct {
 } infv_ltm_sources_desc;
 int infv_ltm_source_weights(infv_ltm_handle h, const infv_ltm_sources_desc* d, const int32_t* bins_all, float* W,
                             const float* mass_all, float* attn_all, int32_t* bad_bins, void* stream);
+
+/* The source weights of MANY videos in one launch (additive in ABI 6): the pass above over the packed bins and masses of a
+ * lockstep call.  Every video is a new document with col_begin = 0 (continuing a document stays the single-video call's job).
+ * For every video v of len_v = cu[v+1] - cu[v] chunks and M_v = len_v * T / g columns, W_all[v] equals bit for bit what
+ * infv_ltm_source_weights writes for that video's slice of the packed arrays (new_doc = 1, col_begin = 0, the same ld), and its
+ * rows [cu[v], cu[v+1]) of attn_all equal that call's attn_all bit for bit; columns at and beyond M_v are not touched, and a video
+ * with no chunk writes nothing.  bad_bins[l] is increased by the count over all videos.  `h` supplies only the plan tables for T.
+ * The packed bins come for free: the draw trace is per handle and indexed by step, so infv_ltm_set_trace(h_v, bins + cu[v]*L*S,
+ * probs + cu[v]*L*n_bins, len_v) on every handle makes a lockstep call fill one packed [cu[V]][L][S] tensor; the packed masses
+ * are infv_ltm_set_videos_mass_trace's.
+ * ONE launch for up to 512 videos (ceil(V / 512) launches beyond): grid (tiles of the longest video, L, videos); workgroup
+ * (tile, l, v) walks chunks [cu[v], cu[v+1]) and returns at once when its tile starts at or beyond M_v.  cu is read on the host
+ * during the call and travels in the kernel's arguments: nothing is copied to the device, nothing outlives the call, and the call
+ * may be captured.
+ * The stream is a FIELD of the descriptor, not a `void* stream` parameter, on purpose: the table of stream-order cases
+ * (tests/golden/stream_cases.py) lists every function that declares such a parameter; this call's stream-order scenario lives in
+ * tests/test_videos_trace_gpu.py instead.  Do not move it into the parameter list.
+ * Refused before any device work, nothing written: everything infv_ltm_source_weights refuses (g, ld below the longest video's
+ * columns or no multiple of 4, alignment of W_all, the sticky / bins_all pairing, the mass_all / attn_all pairing, no plan for T,
+ * a dense or general-psi plan for T, num_basis above 512), and INFV_ERR_INVALID for a null descriptor, cu or W_all, V < 1, cu not
+ * non-decreasing from a non-negative start, cu[V] = 0, reserved != 0. */
+typedef struct {
+    int32_t n_videos;            /* V >= 1 */
+    int32_t T;                   /* frames per chunk */
+    int32_t frames_per_source;   /* g >= 1, divides T */
+    int32_t reserved;            /* 0 */
+    int64_t ld;                  /* row stride of W_all and attn_all in floats: multiple of 4, >= max_v len_v * T / g */
+    const int32_t* cu;           /* HOST [V+1], as the lockstep calls take it */
+    const int32_t* bins_all;     /* DEVICE packed [cu[V]][L][S]; NULL iff the handle is not sticky */
+    float*         W_all;        /* DEVICE [V][L][num_basis][ld], 16-byte aligned */
+    const float*   mass_all;     /* DEVICE packed [cu[V]][L][num_basis] or NULL */
+    float*         attn_all;     /* DEVICE packed [cu[V]][L][ld] or NULL (NULL iff mass_all is NULL) */
+    int32_t*       bad_bins;     /* DEVICE [L] or NULL, summed over videos */
+    void*          hip_stream;   /* the stream of the launch (see above) */
+} infv_ltm_sources_videos_desc;
+int infv_ltm_source_weights_videos(infv_ltm_handle h, const infv_ltm_sources_videos_desc* d);
 
 /* Synchronises `stream`, then reports a latched device-side failure (see Conventions). */
 int infv_ltm_sync(infv_ltm_handle h, void* stream);

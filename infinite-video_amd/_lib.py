@@ -79,6 +79,13 @@ class SourcesDesc(C.Structure):
                 ("col_begin", C.c_int64), ("ld", C.c_int64)]
 
 
+class SourcesVideosDesc(C.Structure):
+    """infv_ltm_sources_videos_desc: one call of infv_ltm_source_weights_videos (the stream is a field, see the header)."""
+    _fields_ = [("n_videos", C.c_int32), ("T", C.c_int32), ("frames_per_source", C.c_int32), ("reserved", C.c_int32),
+                ("ld", C.c_int64), ("cu", C.c_void_p), ("bins_all", C.c_void_p), ("W_all", C.c_void_p), ("mass_all", C.c_void_p),
+                ("attn_all", C.c_void_p), ("bad_bins", C.c_void_p), ("hip_stream", C.c_void_p)]
+
+
 class Proj(C.Structure):
     _fields_ = [("wk", C.c_void_p), ("bk", C.c_void_p), ("wv", C.c_void_p), ("bv", C.c_void_p)]
 
@@ -199,6 +206,8 @@ _SIGNATURES = {
     "infv_ltm_set_mass_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "infv_ltm_source_weights": (C.c_int, [C.c_void_p, C.POINTER(SourcesDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "infv_ltm_set_videos_mass_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "infv_ltm_source_weights_videos": (C.c_int, [C.c_void_p, C.POINTER(SourcesVideosDesc)]),
     "infv_ltm_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
     "infv_ltm_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "infv_ltm_profile_read": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -434,7 +434,7 @@ int infv_ltm_set_psi_plan(infv_ltm_handle h, const infv_ltm_psi_plan* p) {
     if (int rc = find_plan(h, p->T, &plan)) return rc;
     DensePlan& d = plan->dense;
     if (!d.on) return fail(INFV_ERR_STATE, "psi plan: set the dense plan of T=%d first (infv_ltm_set_dense_plan)", p->T);
-    if (h->grid.on || h->mass_trace)
+    if (h->grid.on || h->mass_trace || h->vmass_trace)
         return fail(INFV_ERR_UNSUPPORTED, "psi plan: the handle has a grid plan or a mass trace set (box plans only: infv_ltm_set_grid_plan)");
     HIP_TRY(hipDeviceSynchronize());                            // a step of this length may still be reading the old tables
     HIP_TRY(upload(d.psi_edge, p->psi_edge, (size_t)(h->n_bins + 1) * h->N));
@@ -722,6 +722,9 @@ int videos_validate(VideosCall& vc) {
     for (int v = 0; v < V; ++v)                    // (the first read of a handle: the checks above refuse without one)
         if (hs[v]->mass_trace)
             return fail(INFV_ERR_UNSUPPORTED, "%s: handle %d has a mass trace set (infv_ltm_set_mass_trace): the lockstep calls do not write it", name, v);
+    for (int v = 1; v < V; ++v)                    // (a trace that would silently stay empty: only the lead's is served)
+        if (hs[v]->vmass_trace)
+            return fail(INFV_ERR_INVALID, "%s: handle %d has a videos mass trace set (infv_ltm_set_videos_mass_trace): only handle 0's is written", name, v);
     for (int v = 1; v < V; ++v)
         if (!same_config(hs[0], hs[v], vc.tokens))
             return fail(INFV_ERR_INVALID, "%s: handle %d's configuration (N, H, dh, d, P, L, S, sticky%s) differs from handle 0's",
@@ -760,11 +763,25 @@ int videos_validate(VideosCall& vc) {
 }
 
 // shapes the lockstep kernels do not take (dense / psi plans, N above 256, ...): each video's own per-call path, in turn
-// (the handles were reset by videos_validate when new_doc is set)
+// (the handles were reset by videos_validate when new_doc is set).  The lead's packed mass trace is served through each handle's
+// own per-chunk trace (infv_ltm_set_mass_trace's fields, empty here: videos_validate refuses a handle that has one) on the
+// video's slice of the packed buffer, for the length of its call.
+struct MassTraceSlice {
+    infv_ltm_handle h; float* was; long was_cap;
+    MassTraceSlice(infv_ltm_handle h_, float* slice, long cap) : h(h_), was(h_->mass_trace), was_cap(h_->mass_cap) {
+        if (slice && cap > 0) { h->mass_trace = slice; h->mass_cap = cap; }
+    }
+    ~MassTraceSlice() { h->mass_trace = was; h->mass_cap = was_cap; }
+};
+
 int videos_per_video(const VideosCall& vc) {
+    infv_ltm_handle h0 = vc.hs[0];
+    float* const vmass = h0->vmass_trace;
+    const long vcap = h0->vmass_cap;
     for (int v = 0; v < vc.V; ++v) {
         const int n = vc.len(v);
         if (n == 0) continue;
+        MassTraceSlice tr_(vc.hs[v], vmass ? vmass + (size_t)vc.cu[v] * h0->L * h0->N : nullptr, vcap - vc.cu[v]);
         const double* uv = vc.u ? vc.u + (size_t)vc.cu[v] * vc.chunk_u : nullptr;
         float* cv = vc.ctx + (size_t)vc.cu[v] * vc.chunk_ctx;
         int rc;
@@ -813,7 +830,9 @@ int videos_group_table(VideosCall& vc, int g0, int gn, int* g_len) {
     return INFV_OK;
 }
 
-// The lockstep steps of the present group (vc.order): five launches per step, for the videos still running
+// The lockstep steps of the present group (vc.order): five launches per step, for the videos still running -- six while the lead
+// carries a packed mass trace (infv_ltm_set_videos_mass_trace): the masses follow the attend launch whose scores they read, and
+// stream order keeps the next step's attend behind them
 int videos_steps(const VideosCall& vc, int g_len) {
     infv_ltm_handle h0 = vc.hs[0];
     const Plan& plan = *vc.plans[0];
@@ -849,6 +868,8 @@ int videos_steps(const VideosCall& vc, int g_len) {
             HIP_TRY(launch_attend_videos(vs, vc.q, q_stride, vc.Q, N, h0->H, L, vc.pp, plan.w.as<float>(), plan.w_out, plan.sticky(), vc.ctx,
                                          stream));
         }
+        if (h0->vmass_trace)
+            HIP_TRY(launch_box_mass_videos(vs, h0->H * vc.Q, N, L, plan.w.as<float>(), plan.w_out, h0->vmass_trace, h0->vmass_cap, stream));
     }
     return INFV_OK;
 }

@@ -1,16 +1,19 @@
-// Read-outs of the memory's attention density (include/infv_ltm.h: infv_ltm_density, infv_ltm_masses, infv_ltm_set_mass_trace).
+// Read-outs of the memory's attention density (include/infv_ltm.h: infv_ltm_density, infv_ltm_masses, infv_ltm_set_mass_trace,
+// infv_ltm_set_videos_mass_trace).
 //
 // The reference evaluates the density of the last step on a 768-point grid on every forward and pickles it
 // (long_term_attention_gibbs.py:320-343):
 //     s(t) = sum_n psi_n(t) S[n];  e = exp(s);  dens = e / trapz(e over the point's segment);  alphas = dens / sum dens
 // (here with the segment's maximum of s subtracted before exp: the same dens, in range for any scores)
 // and the read-out itself weighs basis function n with  alpha[n] = w_n e^{S_n} / (sum_m w_m e^{S_m} + w_out)  (the `integral`
-// of expected_value, :282).  Two kernels, neither on a default path:
+// of expected_value, :282).  Three kernels, none on a default path:
 //     density_grid_kernel   one wave per (h, q) score row: the row goes to LDS once, s(t) is gathered through the grid plan's
 //                           CSR in fp32 in CSR order, max / exp / per-segment trapezoid sums / grand sum are wave reductions
 //     box_mass_kernel       mass[n] = mean over the H*Q rows of alpha[row][n], from full score rows (the per-chunk stages and
 //                           the last-step call) or from the alpha rows the fused chain leaves in its ring -- two loaders in
 //                           front of ONE reduction
+//     box_mass_videos_kernel  that reduction over the score rows of every video a lockstep step just advanced, written at the
+//                           packed chunk index (infv_ltm_set_videos_mass_trace)
 // exp is expf (1 ulp), never the fast form: the outputs are compared with a float64 restatement (density.py) at a few ulp.
 // Sums over points and over rows run in float64, so their order does not show in the fp32 result.
 #include "ltm_device.h"
@@ -143,6 +146,55 @@ __global__ __launch_bounds__(64 * kBmWaves) void box_mass_kernel(BoxMassArgs a) 
     }
 }
 
+// The packed trace of the lockstep calls (infv_ltm_set_videos_mass_trace): grid (column blocks of 64, layers, videos still running).
+// Workgroup (cb, l, j) reduces the full score rows attend_videos_kernel just left in video rank j's handle (key bias included: no
+// cq) into row chunk0 + s of mass_all -- the packed index of ctx, whatever the group and the rank.  Rows at and beyond `cap` are
+// not written.  The arithmetic is box_mass_kernel<true>'s, restated: sharing one __device__ body changed that kernel's registers.
+__global__ __launch_bounds__(64 * kBmWaves) void box_mass_videos_kernel(VideoStep vs, int rows, int N, int n_layers,
+                                                                         const float* __restrict__ w, float w_out,
+                                                                         float* __restrict__ mass_all, long cap) {
+    __shared__ double part[kBmWaves][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cb = blockIdx.x, l = blockIdx.y;
+    const int n = cb * 64 + lane;
+    const VideoDesc* v = vs.vd + blockIdx.z;
+    const long chunk = v->chunk0 + vs.s;
+    if (chunk >= cap) return;                                // (uniform over the workgroup: ahead of the barrier)
+    const float* src = v->scores + (long)l * rows * N;
+    double acc = 0.0;
+    for (int r = wave; r < rows; r += kBmWaves) {
+        const float* row = src + (long)r * N;
+        float sv[kBmMaxN / 64];
+        float m = 0.f;                                       // max(row maximum, 0)
+#pragma unroll
+        for (int k = 0; k < kBmMaxN / 64; ++k) {
+            const int c = lane + 64 * k;
+            sv[k] = (c < N) ? row[c] : -INFINITY;            // (full scores, key bias included: no cq term)
+            m = fmaxf(m, sv[k]);
+        }
+        m = wave_max(m);
+        double esum = 0.0;
+        float mine = 0.f;
+#pragma unroll
+        for (int k = 0; k < kBmMaxN / 64; ++k) {
+            const int c = lane + 64 * k;
+            const float e = (c < N) ? w[c] * expf(sv[k] - m) : 0.f;
+            esum += (double)e;
+            if (k == cb) mine = e;
+        }
+        esum = wave_sum_f64(esum);
+        acc += (double)mine / (esum + (double)(w_out * expf(-m)));
+    }
+    part[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && n < N) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < kBmWaves; ++k) t += part[k][lane];
+        mass_all[(chunk * n_layers + l) * N + n] = (float)(t * (1.0 / (double)rows));
+    }
+}
+
 bool box_mass_supported(int N) { return N > 0 && N <= kBmMaxN; }
 
 hipError_t launch_box_mass(const BoxMassArgs& a, hipStream_t stream) {
@@ -151,6 +203,15 @@ hipError_t launch_box_mass(const BoxMassArgs& a, hipStream_t stream) {
     const dim3 grid((unsigned)((a.N + 63) / 64), (unsigned)a.L, (unsigned)a.n_items);
     if (a.from_alpha) INFV_LAUNCH(box_mass_kernel<false>, grid, dim3(64 * kBmWaves), 0, stream, a);
     else INFV_LAUNCH(box_mass_kernel<true>, grid, dim3(64 * kBmWaves), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_box_mass_videos(const VideoStep& vs, int rows, int N, int n_layers, const float* w, float w_out, float* mass_all,
+                                  long cap, hipStream_t stream) {
+    if (vs.n == 0 || cap <= 0) return hipSuccess;
+    if (!box_mass_supported(N) || n_layers > 65535 || vs.n > 65535) return hipErrorInvalidValue;
+    INFV_LAUNCH(box_mass_videos_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)n_layers, (unsigned)vs.n), dim3(64 * kBmWaves), 0,
+                stream, vs, rows, N, n_layers, w, w_out, mass_all, cap);
     return hipGetLastError();
 }
 
@@ -286,6 +347,19 @@ int infv_ltm_set_mass_trace(infv_ltm_handle h, float* mass_all, int64_t capacity
     if (capacity_chunks > 0 && !box_mass_supported(h->N)) return fail(INFV_ERR_UNSUPPORTED, "set_mass_trace: num_basis=%d above 512", h->N);
     h->mass_trace = capacity_chunks ? mass_all : nullptr;
     h->mass_cap = (long)capacity_chunks;
+    return INFV_OK;
+}
+
+int infv_ltm_set_videos_mass_trace(infv_ltm_handle lead, float* mass_all, int64_t capacity_chunks) {
+    if (int rc = check_handle(lead)) return rc;
+    if (capacity_chunks < 0) return fail(INFV_ERR_INVALID, "set_videos_mass_trace: negative capacity");
+    if (capacity_chunks > 0 && !mass_all) return fail(INFV_ERR_INVALID, "set_videos_mass_trace: null buffer");
+    if (capacity_chunks > 0 && any_psi_plan(lead))
+        return fail(INFV_ERR_UNSUPPORTED, "set_videos_mass_trace: general-psi plans (infv_ltm_set_psi_plan) have no box masses");
+    if (capacity_chunks > 0 && !box_mass_supported(lead->N))
+        return fail(INFV_ERR_UNSUPPORTED, "set_videos_mass_trace: num_basis=%d above 512", lead->N);
+    lead->vmass_trace = capacity_chunks ? mass_all : nullptr;
+    lead->vmass_cap = (long)capacity_chunks;
     return INFV_OK;
 }
 

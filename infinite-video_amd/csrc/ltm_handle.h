@@ -208,6 +208,7 @@ struct infv_ltm_s {
     const infv::Plan* last_plan = nullptr;     // plan of the last step (its read-out weights)
     float* mass_trace = nullptr; long mass_cap = 0;   // box-mass trace of the multi-chunk calls (caller's device buffer [cap][L][N])
     long mass_at = -1;                 // chunk index inside the multi-chunk call that is running its per-chunk stages, or -1
+    float* vmass_trace = nullptr; long vmass_cap = 0; // packed box-mass trace of the lockstep calls this handle leads ([cap][L][N], infv_ltm_set_videos_mass_trace)
     infv::Profiler prof;
     ~infv_ltm_s() {
         for (auto& kv : plans) delete kv.second;

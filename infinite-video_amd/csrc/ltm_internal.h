@@ -375,4 +375,8 @@ hipError_t launch_update_videos(const VideoStep& vs, const OperatorView& op, int
 hipError_t launch_attend_videos(const VideoStep& vs, const float* q, long q_stride, int Q, int N, int H, int n_layers,
                                 const ProjPtrs& proj, const float* readout_w, float readout_w_out, const StickyView& sticky,
                                 float* ctx, hipStream_t stream);
+// mass_all[chunk0 + s][l][:] of every video rank j < vs.n whose packed chunk index lies below cap, from the full score rows
+// [L][rows][N] the attend launch of this step left in vd[j].scores (ltm_density.hip: box_mass_kernel<true>'s arithmetic)
+hipError_t launch_box_mass_videos(const VideoStep& vs, int rows, int N, int n_layers, const float* w, float w_out, float* mass_all,
+                                  long cap, hipStream_t stream);
 }  // namespace infv

@@ -9,6 +9,8 @@
 //                                   keeps its [N x TILE] slice of W twice in LDS (old / new), walks the chunks of the call in
 //                                   order with ONE barrier per chunk and writes the slice back once.  Nothing crosses
 //                                   workgroups: no flags, no atomics on W.
+//     source_weights_videos_kernel<TILE>   the same walk with a video index in the grid (infv_ltm_source_weights_videos): one
+//                                   launch for the packed bins / masses of a lockstep call.
 // Lane mapping: a thread owns 4 consecutive columns (one 16-byte LDS slot) of a box; with TILE = 64 a row is one 256-byte bank
 // row and the 16 lanes of every ds_read_b128 group hold the 16 different slots of it, whatever rows they gather: conflict-free.
 // With TILE = 32 (num_basis above 256) two rows share a bank row and a gather may be 2-way.
@@ -41,11 +43,12 @@ __device__ inline float frames_in(long lo, int g, int begin, int end) {
     return b > a ? (float)(b - a) : 0.f;
 }
 
+// the walk of workgroup (tile, layer l) over the chunks of one call: both kernels below run it
 template <int TILE>
-__global__ __launch_bounds__(kSwNT) void source_weights_kernel(SourcesArgs a) {
+__device__ __forceinline__ void source_weights_body(const SourcesArgs& a, const unsigned tile, const int l) {
     constexpr int QUADS = TILE / 4, ROWS = kSwNT / QUADS, GROUPS = kSwNT / TILE;
     extern __shared__ floatx4 sw_lds[];
-    const int N = a.N, t = threadIdx.x, l = blockIdx.y;
+    const int N = a.N, t = threadIdx.x;
     const size_t slice = (size_t)N * QUADS;                                      // W before the chunk: sw_lds + cur * slice; after it: the other one
     double* part = reinterpret_cast<double*>(sw_lds + 2 * slice);                // [2][GROUPS][TILE]
     int32_t* src = reinterpret_cast<int32_t*>(part + 2 * kSwNT);                 // [2][kMaxSamples] source box of CSR entry j, -1: none
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(kSwNT) void source_weights_kernel(SourcesArgs a) {
     int32_t* re = rb + N;
     float* val = reinterpret_cast<float*>(re + N);                               // [N]
 
-    const long m0 = (long)blockIdx.x * TILE;
+    const long m0 = (long)tile * TILE;
     const int quad = t % QUADS, row0 = t / QUADS;
     const long mq = m0 + 4 * quad;                                               // first column of this thread's slot
     float* Wl = a.W + (long)l * N * a.ld;
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(kSwNT) void source_weights_kernel(SourcesArgs a) {
         my_slot[k] = j < nnz ? a.inf.old_slot[j] : -1;
         bnext[k] = ball[k] = 0;
     }
-    const bool count_bad = a.bad_bins && a.sticky && blockIdx.x == 0;
+    const bool count_bad = a.bad_bins && a.sticky && tile == 0;
     auto fetch = [&](int c) {
         if (!a.sticky || (a.new_doc && c == 0)) return;
         const int32_t* b = a.bins_all + ((long)c * a.L + l) * a.S;
@@ -204,6 +207,39 @@ __global__ __launch_bounds__(kSwNT) void source_weights_kernel(SourcesArgs a) {
     if (count_bad && bad) atomicAdd(a.bad_bins + l, bad);
 }
 
+template <int TILE>
+__global__ __launch_bounds__(kSwNT) void source_weights_kernel(SourcesArgs a) {
+    source_weights_body<TILE>(a, blockIdx.x, blockIdx.y);
+}
+
+// Many videos in one grid (infv_ltm_source_weights_videos): workgroup (tile, l, v) runs the walk above over video v's chunks
+// [cu[v], cu[v + 1]) of the packed arrays as a new document from column 0, into W_all[v] and its own rows of attn_all.  The grid
+// is as wide as the longest video: a workgroup whose tile starts at or beyond its video's M_v returns at once (a video with no
+// chunk has M_v = 0).  cu travels in the kernel's arguments: no device table, nothing that outlives the launch.
+constexpr int kSwVideos = 512;                 // videos per launch
+struct SourcesVideosArgs {
+    SourcesArgs base;                          // C, M, col_begin, new_doc are set per video; W is W_all of this launch's first video
+    int32_t cu[kSwVideos + 1];                 // cu[v0 .. v0 + n] of the call
+};
+static_assert(sizeof(SourcesVideosArgs) <= 3072, "kernel arguments stay well inside the 4 KiB limit");
+
+template <int TILE>
+__global__ __launch_bounds__(kSwNT) void source_weights_videos_kernel(SourcesVideosArgs va) {
+    const int v = blockIdx.z;
+    const long c_begin = va.cu[v];
+    SourcesArgs a = va.base;
+    a.C = va.cu[v + 1] - va.cu[v];
+    a.M = (long)a.C * (a.T / a.g);
+    if ((long)blockIdx.x * TILE >= a.M) return;
+    if (a.bins_all) a.bins_all += c_begin * a.L * a.S;
+    a.W += (long)v * a.L * a.N * a.ld;
+    if (a.attn_all) {
+        a.mass_all += c_begin * a.L * a.N;
+        a.attn_all += c_begin * a.L * a.ld;
+    }
+    source_weights_body<TILE>(a, blockIdx.x, blockIdx.y);
+}
+
 size_t source_weights_lds_bytes(int N, int tile) {
     return 2 * (size_t)N * tile * sizeof(float) + 2 * kSwNT * sizeof(double) + 2 * kMaxSamples * sizeof(int32_t) +
            (size_t)(4 * N + 1) * sizeof(int32_t);
@@ -229,12 +265,89 @@ hipError_t launch_source_weights(const SourcesArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// `a`: the call's tables, strides and packed arrays (W = W_all; C, M, col_begin and new_doc are the kernel's to set); cu: HOST [V + 1].
+// ceil(V / kSwVideos) launches; a launch whose videos all have no chunk is not issued.
+hipError_t launch_source_weights_videos(const SourcesArgs& a, const int32_t* cu, int V, hipStream_t stream) {
+    if (a.N <= 0 || a.N > kSwMaxN || a.S > kMaxSamples || a.L <= 0 || a.L > 65535 || V <= 0) return hipErrorInvalidValue;
+    const int tile = a.N <= 256 ? 64 : 32;
+    const size_t lds = source_weights_lds_bytes(a.N, tile);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(source_weights_videos_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(source_weights_videos_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    for (int v0 = 0; v0 < V; v0 += kSwVideos) {
+        const int n = V - v0 < kSwVideos ? V - v0 : kSwVideos;
+        SourcesVideosArgs va{};
+        va.base = a;
+        va.base.new_doc = 1; va.base.col_begin = 0;
+        va.base.W = a.W + (long)v0 * a.L * a.N * a.ld;
+        int longest = 0;
+        for (int i = 0; i <= n; ++i) va.cu[i] = cu[v0 + i];
+        for (int i = 0; i < n; ++i) longest = va.cu[i + 1] - va.cu[i] > longest ? va.cu[i + 1] - va.cu[i] : longest;
+        const long tiles = ((long)longest * (a.T / a.g) + tile - 1) / tile;
+        if (tiles == 0) continue;
+        if (tiles > 0x7fffffffl) return hipErrorInvalidValue;
+        const dim3 grid((unsigned)tiles, (unsigned)a.L, (unsigned)n);
+        if (tile == 64) INFV_LAUNCH(source_weights_videos_kernel<64>, grid, dim3(kSwNT), lds, stream, va);
+        else INFV_LAUNCH(source_weights_videos_kernel<32>, grid, dim3(kSwNT), lds, stream, va);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace infv
 
-// ---- the entry point (include/infv_ltm.h) ----
+// ---- the entry points (include/infv_ltm.h) ----
 #include "ltm_handle.h"
 
 using namespace infv;
+
+extern "C" int infv_ltm_source_weights_videos(infv_ltm_handle h, const infv_ltm_sources_videos_desc* d) {
+    if (int rc = check_handle(h)) return rc;
+    if (!d || !d->cu || !d->W_all) return fail(INFV_ERR_INVALID, "source_weights_videos: null descriptor, cu or W_all");
+    const int V = d->n_videos;
+    if (V < 1) return fail(INFV_ERR_INVALID, "source_weights_videos: n_videos=%d", V);
+    if (d->reserved != 0) return fail(INFV_ERR_INVALID, "source_weights_videos: reserved must be 0");
+    if (d->cu[0] < 0) return fail(INFV_ERR_INVALID, "source_weights_videos: cu[0] = %d is negative", d->cu[0]);
+    int longest = 0;
+    for (int v = 0; v < V; ++v) {
+        if (d->cu[v + 1] < d->cu[v]) return fail(INFV_ERR_INVALID, "source_weights_videos: cu is not non-decreasing at video %d", v);
+        longest = d->cu[v + 1] - d->cu[v] > longest ? d->cu[v + 1] - d->cu[v] : longest;
+    }
+    if (d->cu[V] == 0) return fail(INFV_ERR_INVALID, "source_weights_videos: no chunk at all (cu[V] = 0)");
+    if (d->T < 1) return fail(INFV_ERR_INVALID, "source_weights_videos: T=%d", d->T);
+    const int g = d->frames_per_source;
+    if (g < 1 || d->T % g) return fail(INFV_ERR_INVALID, "source_weights_videos: frames_per_source=%d does not divide T=%d", g, d->T);
+    const int64_t M = (int64_t)longest * (d->T / g);
+    if (d->ld < M || d->ld % 4)
+        return fail(INFV_ERR_INVALID, "source_weights_videos: ld=%lld must be a multiple of 4 and at least %lld (the longest video)",
+                    (long long)d->ld, (long long)M);
+    if (reinterpret_cast<uintptr_t>(d->W_all) & 15u) return fail(INFV_ERR_INVALID, "source_weights_videos: W_all must be 16-byte aligned");
+    if (h->cfg.sticky && !d->bins_all)
+        return fail(INFV_ERR_INVALID, "source_weights_videos: a sticky handle needs the packed bins of the call (infv_ltm_set_trace on every handle)");
+    if (!h->cfg.sticky && d->bins_all) return fail(INFV_ERR_INVALID, "source_weights_videos: bins given to a handle that is not sticky");
+    if ((d->mass_all == nullptr) != (d->attn_all == nullptr))
+        return fail(INFV_ERR_INVALID, "source_weights_videos: mass_all and attn_all go together");
+    auto it = h->plans.find(d->T);
+    if (it == h->plans.end()) return fail(INFV_ERR_STATE, "source_weights_videos: no plan registered for chunk length T=%d", d->T);
+    const Plan& plan = *it->second;
+    if (plan.dense.on || plan.dense.psi_on)
+        return fail(INFV_ERR_UNSUPPORTED, "source_weights_videos: the plan for T=%d is dense or general-psi (its update mixes two boxes through a dense operator)", d->T);
+    if (h->N > kSwMaxN) return fail(INFV_ERR_UNSUPPORTED, "source_weights_videos: num_basis=%d above %d", h->N, kSwMaxN);
+    SourcesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = h->N; a.S = h->S; a.T = d->T; a.L = h->L; a.g = g; a.new_doc = 1;
+    a.sticky = h->cfg.sticky ? 1 : 0; a.n_bins = plan.n_bins;
+    a.ld = d->ld;
+    a.first = plan.first.view(); a.inf = plan.inf.view();
+    a.bin_box = plan.bin_box.as<int32_t>(); a.uniform_idx = plan.uniform_idx.as<int32_t>();
+    a.bins_all = d->bins_all; a.W = d->W_all; a.mass_all = d->mass_all; a.attn_all = d->attn_all; a.bad_bins = d->bad_bins;
+    HIP_TRY(launch_source_weights_videos(a, d->cu, V, static_cast<hipStream_t>(d->hip_stream)));
+    return INFV_OK;
+}
 
 extern "C" int infv_ltm_source_weights(infv_ltm_handle h, const infv_ltm_sources_desc* d, const int32_t* bins_all, float* W,
                                        const float* mass_all, float* attn_all, int32_t* bad_bins, void* stream) {

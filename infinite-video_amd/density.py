@@ -151,6 +151,49 @@ def source_attention(mass_trace, plan, bins, n_chunks, new_doc=True, W=None, col
     return out, attn
 
 
+def _video_slices(chunk_counts):
+    counts = [int(c) for c in chunk_counts]
+    if any(c < 0 for c in counts):
+        raise ValueError(f"chunk_counts must be non-negative, got {counts}")
+    cu = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return counts, cu
+
+
+def source_weights_videos(plan, bins, chunk_counts, frames_per_source=None, dtype=np.float64):
+    """``source_weights`` of V videos whose chunks are PACKED as the lockstep calls pack them (video v's rows at
+    ``[cu[v], cu[v+1])``, ``cu`` the running sum of ``chunk_counts``), every video a new document: ``W`` [V, N, M_max] of ONE
+    layer, ``M_max = max_v C_v * T / g``; video v's columns at and beyond its own ``M_v`` -- all of them for a video with no
+    chunk -- are 0.  ``bins`` [sum C_v, S], or ``None`` for a memory that is not sticky.  The mirror of
+    ``infv_ltm_source_weights_videos``: a loop over ``source_weights``."""
+    counts, cu = _video_slices(chunk_counts)
+    g = int(plan.T if frames_per_source is None else frames_per_source)
+    per = plan.T // g
+    out = np.zeros((len(counts), int(plan.N), max(counts, default=0) * per), dtype=dtype)
+    for v, n in enumerate(counts):
+        if n:
+            b = None if bins is None else bins[cu[v]:cu[v + 1]]
+            out[v, :, :n * per] = source_weights(plan, b, n, frames_per_source=g, dtype=dtype)
+    return out
+
+
+def source_attention_videos(mass_trace, plan, bins, chunk_counts, frames_per_source=None, dtype=np.float64, normalise=False):
+    """``source_attention`` of V packed videos: ``(W [V, N, M_max], attn [sum C_v, M_max])``, row ``cu[v] + i`` of ``attn`` being
+    chunk i of video v (0 at and beyond the video's ``M_v``).  ``mass_trace`` [sum C_v, N]: one layer of the packed trace
+    (``engine.trace_videos``)."""
+    counts, cu = _video_slices(chunk_counts)
+    g = int(plan.T if frames_per_source is None else frames_per_source)
+    per = plan.T // g
+    mass = np.asarray(mass_trace, dtype=np.float64)
+    W = np.zeros((len(counts), int(plan.N), max(counts, default=0) * per), dtype=dtype)
+    attn = np.zeros((int(cu[-1]), W.shape[2]), dtype=np.float64)
+    for v, n in enumerate(counts):
+        if n:
+            b = None if bins is None else bins[cu[v]:cu[v + 1]]
+            W[v, :, :n * per], attn[cu[v]:cu[v + 1], :n * per] = source_attention(
+                mass[cu[v]:cu[v + 1]], plan, b, n, frames_per_source=g, dtype=dtype, normalise=normalise)
+    return W, attn
+
+
 def top_sources(attn_row, k, frames_per_source=1):
     """The k most attended sources of one row of the attention map, most attended first:
     ``[(source, first_frame, end_frame, weight), ...]`` with the source's frames ``[first_frame, end_frame)`` of the video."""

@@ -848,3 +848,111 @@ def steps_videos(engines: Sequence[LTMEngine], kbar, chunk_counts, q: torch.Tens
             _lib.check(e0.lib.infv_ltm_steps_videos(C.cast(hs, C.c_void_p), V, C.c_void_p(cu.ctypes.data), _ptr(kbar), T, _ptr(q),
                                                     per_chunk, Q, proj_arr, _ptr(u), int(new_doc), _ptr(out), _stream(e0.device)))
     return out
+
+
+class VideosTrace:
+    """The packed traces of the lockstep calls, as ``trace_videos`` armed them: ``bins`` [total, L, S] int32 (-1 where nothing
+    drew: a video's first chunk), ``probs`` [total, L, 128] and ``mass`` [total, L, N] fp32 (NaN where nothing wrote; ``None``
+    without ``masses``), row ``cu[v] + i`` being chunk i of video v.  The object keeps the buffers alive while the library
+    writes them; ``stop()`` clears every trace it set."""
+
+    def __init__(self, engines, cu, bins, probs, mass_buf):
+        self.engines, self.cu = engines, cu
+        self.bins, self.probs, self._mass_buf = bins, probs, mass_buf
+        self.mass = None if mass_buf is None else mass_buf[..., :engines[0].N]
+
+    def stop(self):
+        for e in self.engines:
+            _lib.check(e.lib.infv_ltm_set_trace(e._h, None, None, 0))
+            e._trace = None
+        e0 = self.engines[0]
+        _lib.check(e0.lib.infv_ltm_set_videos_mass_trace(e0._h, None, 0))
+        e0._videos_mass_trace = None
+
+
+def trace_videos(engines: Sequence[LTMEngine], chunk_counts, masses: bool = True) -> VideosTrace:
+    """Record the draws and the box masses of the following lockstep calls (``consolidate_videos`` / ``steps_videos``, and the
+    batched encoders that run on them) over ``engines`` with these ``chunk_counts``, PACKED as those calls pack ctx.
+
+    The draw trace is per handle and indexed by the call's step, so engine v is armed (infv_ltm_set_trace) with its own slice
+    ``[cu[v], cu[v+1])`` of one packed tensor; the masses are the call-level trace of the lead engine
+    (infv_ltm_set_videos_mass_trace on ``engines[0]``), one launch more per lockstep step.  Returns a ``VideosTrace``; its
+    ``bins`` and ``mass`` are what ``source_weights_videos`` takes.  Call ``.stop()`` when done."""
+    engines, cu = _video_engines(engines, chunk_counts, "trace_videos")
+    e0 = engines[0]
+    total = int(cu[-1])
+    if total < 1:
+        raise ValueError("trace_videos needs at least one chunk")
+    bins = torch.full((total, e0.L, e0.S), -1, device=e0.device, dtype=torch.int32)
+    probs = torch.zeros(total, e0.L, NB_BINS, device=e0.device, dtype=torch.float32)
+    mass_buf = torch.full((total, e0.L, e0.Np), float("nan"), device=e0.device, dtype=torch.float32) if masses else None
+    tr = VideosTrace(engines, cu, bins, probs, mass_buf)
+    for v, e in enumerate(engines):
+        n = int(cu[v + 1] - cu[v])
+        if n:
+            _lib.check(e.lib.infv_ltm_set_trace(e._h, _ptr(bins[cu[v]:]), _ptr(probs[cu[v]:]), n))
+            e._trace = (bins, probs)
+        else:
+            _lib.check(e.lib.infv_ltm_set_trace(e._h, None, None, 0))
+            e._trace = None
+    if masses:
+        _lib.check(e0.lib.infv_ltm_set_videos_mass_trace(e0._h, _ptr(mass_buf), total))
+        e0._videos_mass_trace = mass_buf
+    return tr
+
+
+def source_weights_videos(engine: LTMEngine, chunk_counts, T: int, bins: Optional[torch.Tensor], mass: Optional[torch.Tensor] = None,
+                          frames_per_source: Optional[int] = None, normalise: bool = False):
+    """Trace the memories of V videos back to their frames in ONE launch per 512 videos (infv_ltm_source_weights_videos;
+    ``density.source_weights_videos`` is its numpy mirror).  ``bins`` [total, L, S] and ``mass`` [total, L, N] are PACKED as
+    ``trace_videos`` records them; every video is a new document.  Returns ``W`` [V, L, N, M_max] with
+    ``M_max = max_v C_v * T / g`` (video v's columns at and beyond ``C_v * T / g`` are 0) and, with ``mass``, ``attn``
+    [total, L, M_max] -- raw, or every row divided by its sum with ``normalise``.  ``engine`` supplies only the plan for T; an
+    engine that is not sticky takes ``bins=None``.
+    Like ``LTMEngine.source_weights`` this wrapper reads a counter of out-of-range bins back: a HOST SYNC.  Any such bin (an
+    unwritten trace row holds -1) raises ``ValueError``."""
+    counts = [int(c) for c in (chunk_counts.tolist() if isinstance(chunk_counts, torch.Tensor) else chunk_counts)]
+    if not counts or any(c < 0 for c in counts) or sum(counts) < 1:
+        raise ValueError("chunk_counts must be non-negative with at least one chunk")
+    V, total = len(counts), sum(counts)
+    cu = np.zeros(V + 1, np.int32)
+    cu[1:] = np.cumsum(counts)
+    g = int(T if frames_per_source is None else frames_per_source)
+    if g < 1 or T % g:
+        raise ValueError("frames_per_source must be >= 1 and divide T")
+    e = engine
+    e.ensure_plan(T)
+    if e.sticky:
+        if bins is None or tuple(bins.shape) != (total, e.L, e.S):
+            raise ValueError(f"a sticky engine needs bins [{total}, {e.L}, {e.S}]")
+        _check_dev(bins, e.device, "bins", torch.int32)
+        bins = bins.contiguous()
+    else:
+        bins = None
+    if mass is not None:
+        if tuple(mass.shape) != (total, e.L, e.N):
+            raise ValueError(f"mass must be [{total}, {e.L}, {e.N}]")
+        if e.Np != e.N:
+            mass = torch.nn.functional.pad(mass, (0, e.Np - e.N))
+        mass = mass.contiguous()
+        _check_dev(mass, e.device, "mass")
+    M = max(counts) * (T // g)
+    ld = (M + 3) // 4 * 4
+    buf = torch.zeros(V, e.L, e.Np, ld, device=e.device, dtype=torch.float32)
+    attn = torch.zeros(total, e.L, ld, device=e.device, dtype=torch.float32) if mass is not None else None
+    bad = torch.zeros(e.L, device=e.device, dtype=torch.int32)
+    desc = _lib.SourcesVideosDesc(n_videos=V, T=int(T), frames_per_source=g, reserved=0, ld=ld, cu=cu.ctypes.data,
+                                  bins_all=_ptr(bins), W_all=_ptr(buf), mass_all=_ptr(mass), attn_all=_ptr(attn), bad_bins=_ptr(bad),
+                                  hip_stream=_stream(e.device))
+    with torch.cuda.device(e.device):
+        _lib.check(e.lib.infv_ltm_source_weights_videos(e._h, C.byref(desc)))
+    n_bad = bad.cpu()                                      # (the host sync)
+    if int(n_bad.sum()):
+        raise ValueError(f"bins outside [0, {NB_BINS - 1}) per layer: {n_bad.tolist()} (an unwritten trace row holds -1)")
+    Wout = buf[:, :, :e.N, :M]
+    if attn is None:
+        return Wout
+    attn = attn[:, :, :M]
+    if normalise:
+        attn = attn / attn.sum(-1, keepdim=True)
+    return Wout, attn

@@ -229,7 +229,15 @@ class VideoMemory:
     """One video's long-term memories for :meth:`InfVideoEncoder.encode_videos`: one one-layer ``LTMEngine`` per
     cross-attention layer, created as ``LongTermAttention._get_engine`` creates the model's own.  ``export_state(l)`` and
     ``last_draw(l)`` read layer l's memory.  ``video_id`` names the video's device-rng streams
-    (:meth:`InfVideoEncoder.use_device_rng`): layer l draws from stream ``(video_id + 1) * n_layers + l``."""
+    (:meth:`InfVideoEncoder.use_device_rng`): layer l draws from stream ``(video_id + 1) * n_layers + l``.
+
+    Attention read-outs of a batch: the lockstep call of layer l has ``memories[0].engines[l]`` as its lead handle, so the packed
+    traces go around the call, one per layer::
+
+        traces = [engine.trace_videos([m.engines[l] for m in memories], counts) for l in range(n_layers)]
+        model.encode_videos(frames, counts, memories=memories)
+        W, attn = engine.source_weights_videos(memories[0].engines[l], counts, T, traces[l].bins, mass=traces[l].mass)
+        for t in traces: t.stop()"""
 
     def __init__(self, model: "InfVideoEncoder", device: torch.device, video_id: int = 0):
         from .engine import LTMEngine

@@ -200,7 +200,9 @@ class VideoChat2Memory(VideoMemory):
     """One video's long-term memories for :meth:`VideoChat2Encoder.encode_videos`: a one-layer ``LTMEngine`` per
     cross-attention layer (six in the model), created as ``LongTermAttentionVC._get_engine`` creates the model's own.
     ``export_state(i)`` / ``last_draw(i)`` read cross layer i's memory.  ``video_id`` names the video's device-rng streams:
-    cross layer i draws from stream ``(video_id + 1) * n_cross + i`` (the model's own modules keep stream i)."""
+    cross layer i draws from stream ``(video_id + 1) * n_cross + i`` (the model's own modules keep stream i).
+    Attention read-outs of a batch go around the call as for :class:`VideoMemory`, one packed trace per cross layer:
+    ``engine.trace_videos([m.engines[i] for m in memories], counts)`` before ``encode_videos(..., memories=memories)``."""
 
     def __init__(self, model: "VideoChat2Encoder", device: torch.device, video_id: int = 0):
         from .engine import LTMEngine
