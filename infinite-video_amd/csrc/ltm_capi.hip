@@ -28,7 +28,7 @@ int check_chain_error(infv_ltm_handle h) {
     if (h->err_host && *reinterpret_cast<volatile unsigned int*>(h->err_host)) {
         const unsigned int code = *reinterpret_cast<volatile unsigned int*>(h->err_host);
         *reinterpret_cast<volatile unsigned int*>(h->err_host) = 0;
-        h->has_memory = false; h->parts = 0; h->k_stale = false; h->pos = 0; h->ctx_sum_drop(); h->scores_ok = false;
+        h->mem.forget();
         if (code == kErrBlobMismatch)
             return fail(INFV_ERR_STATE, "the blob handed to an earlier infv_ltm_import_chain_state was not exported by a handle of "
                                         "this shape (magic / version / L, N, d, dm, H, Q, n_bins in its header); the memory has been reset");
@@ -107,7 +107,7 @@ int upload_operator(Operator& op, int N, int rows, const int32_t* row_box, const
 int chain_step(infv_ltm_handle h, const Plan& plan, const float* R, const float* Pnew, int splitk,
                long split_stride, const float* q, int Q, const ProjPtrs& pp, const double* u, float* ctx,
                hipStream_t stream, const float* kbar_rows = nullptr, bool draw_done = false, const int32_t* tab = nullptr) {
-    const bool inf = h->has_memory;
+    const bool inf = h->mem.has_memory();
     const Operator& op = inf ? plan.inf : plan.first;
     const int32_t* idx = nullptr;
     int idx_stride = 0;
@@ -115,12 +115,12 @@ int chain_step(infv_ltm_handle h, const Plan& plan, const float* R, const float*
         if (h->cfg.sticky) {
             if (!draw_done) {
                 if (!u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
-                if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
+                if (h->mem.parts() <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
                 Timed t_(h->prof, INFV_KERNEL_DRAW, stream);
-                HIP_TRY(launch_draw(h->bin_part[h->pc].as<float>(), h->parts, h->probs_override.as<float>(),
+                HIP_TRY(launch_draw(h->bin_part.as<float>(), h->mem.parts(), h->probs_override.as<float>(),
                                     h->override_mask, plan.sticky(), u, h->S, h->L,
                                     h->probs.as<float>(), h->bins.as<int32_t>(), h->idx.as<int32_t>(), stream,
-                                    h->bins_forced.as<int32_t>(), h->forced_mask, h->rng_view(h->pos)));
+                                    h->bins_forced.as<int32_t>(), h->forced_mask, h->rng_view(h->mem.pos())));
             }
             h->override_mask = 0;
             h->forced_mask = 0;
@@ -131,26 +131,20 @@ int chain_step(infv_ltm_handle h, const Plan& plan, const float* R, const float*
             idx_stride = 0;
         }
     }
-    const int nxt = h->cur ^ 1;
+    const int nxt = h->mem.cur() ^ 1;
     {
     Timed t_(h->prof, INFV_KERNEL_UPDATE, stream);
     HIP_TRY(launch_update(op.view(), h->N, h->d, h->dm, h->L, h->S, idx, idx_stride, R, Pnew, splitk, split_stride,
-                          h->B[h->cur].as<float>(), h->KV[h->cur].as<float>(), h->B[nxt].as<float>(),
+                          h->B[h->mem.cur()].as<float>(), h->KV[h->mem.cur()].as<float>(), h->B[nxt].as<float>(),
                           h->KV[nxt].as<float>(), stream, kbar_rows, (inf && h->cfg.sticky && draw_done) ? tab : nullptr));
     }
-    h->cur = nxt;
-    h->has_memory = true; h->ctx_sum_drop();
-    const int parts = attend_parts(Q, h->H, h->N);
+    h->mem.memory_written(1);
     {
     Timed t_(h->prof, INFV_KERNEL_ATTEND, stream);
-    HIP_TRY(launch_attend(q, Q, h->N, h->H, h->L, h->KV[h->cur].as<float>(), pp, plan.w.as<float>(), plan.w_out,
-                          plan.sticky(), ctx, h->bin_part[h->pc].as<float>(), h->scores.as<float>(), stream));
+    HIP_TRY(launch_attend(q, Q, h->N, h->H, h->L, h->KV[h->mem.cur()].as<float>(), pp, plan.w.as<float>(), plan.w_out,
+                          plan.sticky(), ctx, h->bin_part.as<float>(), h->scores.as<float>(), stream));
     }
-    h->parts = parts;
-    h->lastQ = Q;
-    h->last_fast = false;
-    h->scores_ok = true; h->last_plan = &plan;
-    ++h->pos;
+    h->mem.attended(&plan, Q, attend_parts(Q, h->H, h->N), 1);
     return trace_masses_of_step(h, plan, Q, stream);
 }
 
@@ -158,21 +152,21 @@ int chain_step(infv_ltm_handle h, const Plan& plan, const float* R, const float*
 // read-out -> sticky masses with two-box edges.  Same state layout as chain_step; the K'/V' rows are re-projected from B.
 int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, const float* q, int Q, const ProjPtrs& pp,
                const double* u, float* ctx, hipStream_t stream) {
-    const bool inf = h->has_memory;
+    const bool inf = h->mem.has_memory();
     const DensePlan& dp = plan.dense;
     const int32_t* bins = nullptr;
     int bins_stride = 0;
     const int32_t* pos_box2 = dp.uniform_box2.as<int32_t>();
     if (inf && h->cfg.sticky) {
         if (!u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
-        if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
+        if (h->mem.parts() <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
         // (checked BEFORE the draw consumes the one-shot masks: an unsupported request leaves the handle as it was)
         if (h->forced_mask && h->forced_mask != (1u << h->L) - 1u)
             return fail(INFV_ERR_UNSUPPORTED, "dense plans: infv_ltm_set_bins must force every layer of the handle or none");
         Timed t_(h->prof, INFV_KERNEL_DRAW, stream);
-        HIP_TRY(launch_draw(h->bin_part[h->pc].as<float>(), h->parts, h->probs_override.as<float>(), h->override_mask,
+        HIP_TRY(launch_draw(h->bin_part.as<float>(), h->mem.parts(), h->probs_override.as<float>(), h->override_mask,
                             plan.sticky(), u, h->S, h->L, h->probs.as<float>(), h->bins.as<int32_t>(), h->idx.as<int32_t>(),
-                            stream, h->bins_forced.as<int32_t>(), h->forced_mask, h->rng_view(h->pos)));
+                            stream, h->bins_forced.as<int32_t>(), h->forced_mask, h->rng_view(h->mem.pos())));
         h->override_mask = 0;
         // a forced draw replaces the resampled bins (infv_ltm_set_bins); get_draw still returns the step's own
         bins = h->forced_mask ? h->bins_forced.as<int32_t>() : h->bins.as<int32_t>();
@@ -180,7 +174,7 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
         bins_stride = h->S;
         pos_box2 = dp.bin_box2.as<int32_t>();
     }
-    const int nxt = h->cur ^ 1;
+    const int nxt = h->mem.cur() ^ 1;
     if (dp.psi_on) {
         // psi(t) is a dense row: the resampled rows are rows of Y = Psi_pos . B_past (128 positions when sticky, S otherwise)
         Timed t_(h->prof, INFV_KERNEL_UPDATE, stream);
@@ -189,7 +183,7 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
         if (inf) {
             HIP_TRY(h->psi_Y.reserve((size_t)h->L * n_pos * h->d * sizeof(float)));
             HIP_TRY(launch_psi_gemm(false, use_bins ? dp.psi_bin.as<float>() : dp.psi_uniform.as<float>(), h->N, 0,
-                                    h->B[h->cur].as<float>(), h->d, (long)h->N * h->d, h->psi_Y.as<float>(), h->d, (long)n_pos * h->d,
+                                    h->B[h->mem.cur()].as<float>(), h->d, (long)h->N * h->d, h->psi_Y.as<float>(), h->d, (long)n_pos * h->d,
                                     n_pos, h->d, h->N, h->L, stream));
         }
         HIP_TRY(launch_psi_update(inf ? dp.inf_GT.as<float>() : dp.first_GT.as<float>(), inf ? dp.inf_K : dp.first_K,
@@ -199,16 +193,15 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
         Timed t_(h->prof, INFV_KERNEL_UPDATE, stream);
         HIP_TRY(launch_dense_update(inf ? dp.inf_GT.as<float>() : dp.first_GT.as<float>(), inf ? dp.inf_K : dp.first_K,
                                     inf ? dp.inf_K : dp.first_K, inf ? h->S : 0, bins, bins_stride, pos_box2,
-                                    h->B[h->cur].as<float>(), kbar, h->B[nxt].as<float>(), h->N, h->d, h->L, stream));
+                                    h->B[h->mem.cur()].as<float>(), kbar, h->B[nxt].as<float>(), h->N, h->d, h->L, stream));
     }
-    h->cur = nxt;
-    h->has_memory = true; h->ctx_sum_drop();
-    HIP_TRY(launch_reproject(h->B[h->cur].as<float>(), h->N, h->d, h->dm, h->L, pp, h->KV[h->cur].as<float>(), stream));
-    h->k_stale = false;
+    h->mem.memory_written(1);
+    HIP_TRY(launch_reproject(h->B[h->mem.cur()].as<float>(), h->N, h->d, h->dm, h->L, pp, h->KV[h->mem.cur()].as<float>(), stream));
+    h->mem.reprojected();
     {
         Timed t_(h->prof, INFV_KERNEL_ATTEND, stream);
-        HIP_TRY(launch_attend(q, Q, h->N, h->H, h->L, h->KV[h->cur].as<float>(), pp, plan.w.as<float>(), plan.w_out,
-                              plan.sticky(), ctx, h->bin_part[h->pc].as<float>(), h->scores.as<float>(), stream));
+        HIP_TRY(launch_attend(q, Q, h->N, h->H, h->L, h->KV[h->mem.cur()].as<float>(), pp, plan.w.as<float>(), plan.w_out,
+                              plan.sticky(), ctx, h->bin_part.as<float>(), h->scores.as<float>(), stream));
         if (dp.psi_on) {
             // the attend kernel above supplied the scores S = q K^T / sqrt(dh); its read-out and masses assume boxes.  Dense forms:
             const long rows_hq = (long)h->L * h->H * Q;
@@ -219,25 +212,21 @@ int dense_step(infv_ltm_handle h, const Plan& plan, const float* kbar, int T, co
             // edge scores z(t_j) = sum_n S[n] psi_n(t_j) -> sticky masses (LTM.py:197-203,224-230)
             HIP_TRY(launch_psi_gemm(true, h->scores.as<float>(), h->N, 0, dp.psi_edge.as<float>(), h->N, 0, h->psi_E.as<float>(), ldE, 0,
                                     (int)rows_hq, h->n_bins + 1, h->N, 1, stream));
-            HIP_TRY(launch_psi_masses(h->psi_E.as<float>(), ldE, Q, h->H, h->L, plan.edge_dx.as<float>(), h->bin_part[h->pc].as<float>(), stream));
+            HIP_TRY(launch_psi_masses(h->psi_E.as<float>(), ldE, Q, h->H, h->L, plan.edge_dx.as<float>(), h->bin_part.as<float>(), stream));
             // read-out on the 1000-point grid (LTM.py:251-286): z -> w o prob -> alpha = (w o prob) . Psi_grid -> ctx = alpha . (V' + bv)
             HIP_TRY(launch_psi_gemm(true, h->scores.as<float>(), h->N, 0, dp.psi_grid.as<float>(), h->N, 0, h->psi_Eg.as<float>(), ldG, 0,
                                     (int)rows_hq, dp.n_grid, h->N, 1, stream));
             HIP_TRY(launch_psi_grid(h->psi_Eg.as<float>(), ldG, dp.n_grid, rows_hq, dp.grid_w.as<float>(), stream));
             HIP_TRY(launch_psi_gemm(false, h->psi_Eg.as<float>(), ldG, 0, dp.psi_grid.as<float>(), h->N, 0, h->psi_alpha.as<float>(), h->N, 0,
                                     (int)rows_hq, h->N, dp.n_grid, 1, stream));
-            HIP_TRY(launch_psi_ctx(h->psi_alpha.as<float>(), h->KV[h->cur].as<float>(), pp, Q, h->N, h->H, h->dm / h->H, h->L, ctx, stream));
+            HIP_TRY(launch_psi_ctx(h->psi_alpha.as<float>(), h->KV[h->mem.cur()].as<float>(), pp, Q, h->N, h->H, h->dm / h->H, h->L, ctx, stream));
         } else {
         // the attend kernel's partials assume one box per edge: recompute them from the scores with the two-box table
         HIP_TRY(launch_dense_masses(h->scores.as<float>(), Q, h->N, h->H, h->L, dp.edge_box2.as<int32_t>(),
-                                    plan.edge_dx.as<float>(), h->bin_part[h->pc].as<float>(), stream));
+                                    plan.edge_dx.as<float>(), h->bin_part.as<float>(), stream));
         }
     }
-    h->parts = h->H;
-    h->lastQ = Q;
-    h->last_fast = false;
-    h->scores_ok = true; h->last_plan = &plan;
-    ++h->pos;
+    h->mem.attended(&plan, Q, h->H, 1);
     return trace_masses_of_step(h, plan, Q, stream);
 }
 
@@ -250,11 +239,11 @@ int precheck_step(infv_ltm_handle h, int T, int Q, const void* u, bool keeps_mem
     if (int rc = check_q(h, Q)) return rc;
     Plan* plan = nullptr;
     if (int rc = find_plan(h, T, &plan)) return rc;
-    const bool on_memory = keeps_memory && h->has_memory;          // the call's first step resamples an existing memory
+    const bool on_memory = keeps_memory && h->mem.has_memory();    // the call's first step resamples an existing memory
     if (h->cfg.sticky && !u && !h->rng_on && (on_memory || n_chunks > 1))   // (every step after the call's first one does)
         return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
     if (h->cfg.sticky && on_memory) {
-        if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
+        if (h->mem.parts() <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
         if (plan->dense.on && h->forced_mask && h->forced_mask != (1u << h->L) - 1u)
             return fail(INFV_ERR_UNSUPPORTED, "dense plans: infv_ltm_set_bins must force every layer of the handle or none");
     }
@@ -294,11 +283,9 @@ int infv_ltm_create(const infv_ltm_config* cfg, infv_ltm_handle* out) {
         if (e == hipSuccess) e = h->KV[i].reserve(nb * 2 * h->dm * sizeof(float));
     }
     const size_t nsq = (size_t)h->L * h->H * h->maxQ * h->N;
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = h->bin_part[i].reserve((size_t)h->L * max_parts * h->n_bins * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(h->bin_part[i].p, 0, h->bin_part[i].bytes);
-        if (e == hipSuccess) e = h->Sp[i].reserve(nsq * sizeof(float));
-    }
+    if (e == hipSuccess) e = h->bin_part.reserve((size_t)h->L * max_parts * h->n_bins * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(h->bin_part.p, 0, h->bin_part.bytes);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = h->Sp[i].reserve(nsq * sizeof(float));
     for (int i = 0; i < 3 && e == hipSuccess; ++i) {
         e = h->mass_acc[i].reserve((size_t)h->L * kAccShards * 128 * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMemset(h->mass_acc[i].p, 0, h->mass_acc[i].bytes);
@@ -389,7 +376,7 @@ int infv_ltm_set_plan(infv_ltm_handle h, const infv_ltm_plan* p) {
     if (e != hipSuccess) { delete plan; return fail(INFV_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e)); }
     auto it = h->plans.find(p->T);
     if (it != h->plans.end()) {
-        if (h->last_plan == it->second) h->last_plan = nullptr;   // (infv_ltm_masses then takes the read-out weights of any plan: they depend on num_basis only)
+        h->mem.plan_erased(it->second);
         delete it->second; h->plans.erase(it);
     }
     h->plans[p->T] = plan;
@@ -449,18 +436,13 @@ int infv_ltm_set_psi_plan(infv_ltm_handle h, const infv_ltm_psi_plan* p) {
 
 int infv_ltm_reset(infv_ltm_handle h) {
     if (int rc = check_handle(h)) return rc;
-    h->has_memory = false;
-    h->parts = 0;
-    h->k_stale = false;
-    h->pos = 0;
-    h->ctx_sum_drop();
-    h->scores_ok = false;
+    h->mem.forget();
     return INFV_OK;
 }
 
 int infv_ltm_has_memory(infv_ltm_handle h) {
     if (int rc = check_handle(h)) return rc;
-    return h->has_memory ? 1 : 0;
+    return h->mem.has_memory() ? 1 : 0;
 }
 
 int infv_ltm_set_token_dtype(infv_ltm_handle h, int32_t dtype) {
@@ -521,11 +503,11 @@ int infv_ltm_step(infv_ltm_handle h, const float* kbar, int32_t T, const float* 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const ProjPtrs pp = make_proj(proj, h->L);
     if (plan->dense.on) return dense_step(h, *plan, kbar, T, q, Q, pp, u, ctx, stream);
-    if (h->k_stale && h->has_memory)
+    if (h->mem.k_stale() && h->mem.has_memory())
         if (int rc = infv_ltm_reproject(h, proj, stream_)) return rc;
     // Three launches per step (six in round 2): [new-row projection with the rows built on the fly + the draw] -> update
     // (its new B rows built from the pooled frames too) -> attend.  Same arithmetic in the same order as the batched path.
-    const bool inf = h->has_memory;
+    const bool inf = h->mem.has_memory();
     const Operator& op = inf ? plan->inf : plan->first;
     const long n_cols = (long)h->L * 2 * h->dm;
     const int sk_max = project_splitk(op.rows > 0 ? op.rows : 1, h->d);
@@ -535,9 +517,9 @@ int infv_ltm_step(infv_ltm_handle h, const float* kbar, int32_t T, const float* 
     memset(&dr, 0, sizeof(dr));
     if (inf && h->cfg.sticky) {
         if (!u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky step on an existing memory needs the Gibbs uniforms u");
-        if (h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
-        dr.rng = h->rng_view(h->pos);
-        dr.n_layers = h->L; dr.bin_part = h->bin_part[h->pc].as<float>(); dr.parts = h->parts;
+        if (h->mem.parts() <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available (import_state or step first)");
+        dr.rng = h->rng_view(h->mem.pos());
+        dr.n_layers = h->L; dr.bin_part = h->bin_part.as<float>(); dr.parts = h->mem.parts();
         dr.probs_override = h->probs_override.as<float>(); dr.override_mask = h->override_mask; dr.sticky = plan->sticky();
         dr.u = u; dr.S = h->S; dr.probs_out = h->probs.as<float>(); dr.bins_out = h->bins.as<int32_t>(); dr.idx_out = h->idx.as<int32_t>();
         dr.bins_forced = h->bins_forced.as<int32_t>(); dr.forced_mask = h->forced_mask;
@@ -577,12 +559,12 @@ int infv_ltm_steps(infv_ltm_handle h, const float* kbar, int32_t n_chunks, int32
         }
         return INFV_OK;
     }
-    if (!h->has_memory && n_chunks > 0) {                     // first chunk of a document: its own operator
+    if (!h->mem.has_memory() && n_chunks > 0) {               // first chunk of a document: its own operator
         MassTraceChunk tr_(h, 0);
         if (int rc = infv_ltm_step(h, kbar, T, q, Q, proj, u, ctx, stream_)) return rc;
         c = 1;
     }
-    if (c < n_chunks && h->k_stale)
+    if (c < n_chunks && h->mem.k_stale())
         if (int rc = infv_ltm_reproject(h, proj, stream_)) return rc;
     const size_t rows = plan->inf.rows;
     const long n_cols = (long)h->L * 2 * h->dm;
@@ -750,9 +732,9 @@ int videos_validate(VideosCall& vc) {
         if (!same_plan(*vc.plans[0], *vc.plans[v]))
             return fail(INFV_ERR_INVALID, "%s: handle %d's plan for T = %d differs from handle 0's (tau, num_basis or "
                                           "the tables themselves): every video steps with one plan", name, v, vc.T);
-        if (!vc.new_doc && !h->has_memory)
+        if (!vc.new_doc && !h->mem.has_memory())
             return fail(INFV_ERR_STATE, "%s: new_doc = 0 but handle %d holds no memory", name, v);
-        if (!vc.new_doc && vc.sticky && h->parts <= 0)
+        if (!vc.new_doc && vc.sticky && h->mem.parts() <= 0)
             return fail(INFV_ERR_STATE, "%s: handle %d has no sticky histogram (import_state or step first)", name, v);
     }
     if (vc.new_doc)
@@ -812,16 +794,16 @@ int videos_group_table(VideosCall& vc, int g0, int gn, int* g_len) {
         infv_ltm_handle h = vc.hs[v];
         VideoDesc& e = tab[j];
         for (int i = 0; i < 2; ++i) { e.B[i] = h->B[i].as<float>(); e.KV[i] = h->KV[i].as<float>(); }
-        e.bin_part = h->bin_part[h->pc].as<float>();
+        e.bin_part = h->bin_part.as<float>();
         e.probs = h->probs.as<float>(); e.bins = h->bins.as<int32_t>(); e.idx = h->idx.as<int32_t>(); e.scores = h->scores.as<float>();
         e.probs_override = h->probs_override.as<float>(); e.bins_forced = h->bins_forced.as<int32_t>();
         e.override_mask = h->override_mask; e.forced_mask = h->forced_mask;
         e.trace_bins = h->trace_bins; e.trace_probs = h->trace_probs; e.trace_cap = h->trace_cap;
         e.chunk0 = cu[v];
         e.kbar0 = (long long)vc.kbar_base(v);
-        e.cur0 = h->cur;
-        e.parts0 = vc.new_doc ? vc.parts : h->parts;
-        e.rng = h->rng_view(h->pos);          // (reset by videos_validate when new_doc: step s of the call draws at position pos + s)
+        e.cur0 = h->mem.cur();
+        e.parts0 = vc.new_doc ? vc.parts : h->mem.parts();
+        e.rng = h->rng_view(h->mem.pos());    // (reset by videos_validate when new_doc: step s of the call draws at position pos + s)
         *g_len = vc.len(v) > *g_len ? vc.len(v) : *g_len;
     }
     // the table travels in kernel arguments (launch_video_table): no host buffer outlives the call, nothing waits on the host,
@@ -874,19 +856,14 @@ int videos_steps(const VideosCall& vc, int g_len) {
     return INFV_OK;
 }
 
-// the handles' host state after their chunks (chain_step's bookkeeping), for the present group
+// the handles' host state after their chunks (chain_step's transitions, `len` steps at once), for the present group
 void videos_bookkeeping(const VideosCall& vc) {
     for (int v : vc.order) {
         infv_ltm_handle h = vc.hs[v];
         const int len = vc.len(v);
         if (len == 0) continue;
-        h->cur ^= len & 1;
-        h->pos += (uint32_t)len;
-        h->has_memory = true; h->ctx_sum_drop();
-        h->parts = vc.parts;
-        h->lastQ = vc.Q;
-        h->last_fast = false;
-        h->scores_ok = true; h->last_plan = vc.plans[v];
+        h->mem.memory_written(len);
+        h->mem.attended(vc.plans[v], vc.Q, vc.parts, len);
         if (vc.sticky && len > vc.mask_step()) { h->override_mask = 0; h->forced_mask = 0; }
     }
 }
@@ -903,7 +880,7 @@ int videos_impl(VideosCall& vc) {
     vc.stream = static_cast<hipStream_t>(vc.stream_);
     vc.pp = make_proj(vc.proj, h0->L);
     for (int v = 0; v < V; ++v)                    // the per-call step re-derives a stale K' half before stepping (infv_ltm_step)
-        if (vc.len(v) > 0 && vc.hs[v]->k_stale && vc.hs[v]->has_memory)
+        if (vc.len(v) > 0 && vc.hs[v]->mem.k_stale() && vc.hs[v]->mem.has_memory())
             if (int rc = infv_ltm_reproject(vc.hs[v], vc.proj, vc.stream_)) return rc;
     const int rows_max = plan.first.rows > plan.inf.rows ? plan.first.rows : plan.inf.rows;
     const int group = V < kVideoGroup ? V : kVideoGroup;
@@ -964,13 +941,13 @@ int infv_ltm_set_rng(infv_ltm_handle h, int32_t on, uint64_t seed, uint32_t stre
 int infv_ltm_get_rng_position(infv_ltm_handle h, uint32_t* pos) {
     if (int rc = check_handle(h)) return rc;
     if (!pos) return fail(INFV_ERR_INVALID, "get_rng_position: null pos");
-    *pos = h->pos;
+    *pos = h->mem.pos();
     return INFV_OK;
 }
 
 int infv_ltm_set_rng_position(infv_ltm_handle h, uint32_t pos) {
     if (int rc = check_handle(h)) return rc;
-    h->pos = pos;
+    h->mem.set_rng_position(pos);
     return INFV_OK;
 }
 
@@ -1009,12 +986,12 @@ int infv_ltm_export_state(infv_ltm_handle h, int32_t layer, float* B, float* bin
     if (int rc = check_handle(h)) return rc;
     if (layer < 0 || layer >= h->L) return fail(INFV_ERR_INVALID, "layer out of range");
     if (int rc = check_chain_error(h)) return rc;
-    if (!h->has_memory) return fail(INFV_ERR_STATE, "no memory to export (B_past is None)");
+    if (!h->mem.has_memory()) return fail(INFV_ERR_STATE, "no memory to export (B_past is None)");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (B) HIP_TRY(hipMemcpyAsync(B, h->B[h->cur].as<float>() + (size_t)layer * h->N * h->d,
+    if (B) HIP_TRY(hipMemcpyAsync(B, h->B[h->mem.cur()].as<float>() + (size_t)layer * h->N * h->d,
                                   (size_t)h->N * h->d * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (bin_mass) {
-        HIP_TRY(launch_sum_parts(h->bin_part[h->pc].as<float>() + (size_t)layer * h->parts * h->n_bins, h->parts, h->n_bins,
+        HIP_TRY(launch_sum_parts(h->bin_part.as<float>() + (size_t)layer * h->mem.parts() * h->n_bins, h->mem.parts(), h->n_bins,
                                  bin_mass, stream));
     }
     return INFV_OK;
@@ -1024,7 +1001,7 @@ int infv_ltm_set_ctx_sum(infv_ltm_handle h, int32_t on) {
     if (int rc = check_handle(h)) return rc;
     if (on) HIP_TRY(h->ctx_sum.reserve((size_t)h->L * h->maxQ * h->dm * sizeof(float)));
     h->ctx_sum_on = on != 0;
-    h->ctx_sum_drop();
+    h->mem.drop_ctx_sum();
     return INFV_OK;
 }
 
@@ -1034,23 +1011,23 @@ int infv_ltm_pack_memory(infv_ltm_handle h, int32_t n_basis, int32_t Q, const fl
     if (!ctx || !payload || n_chunks < 0 || n_basis <= 0 || n_basis > h->N) return fail(INFV_ERR_INVALID, "pack_memory: bad arguments");
     if (int rc = check_q(h, Q)) return rc;
     if (int rc = check_chain_error(h)) return rc;
-    if (!h->has_memory) return fail(INFV_ERR_STATE, "no memory to export (B_past is None)");
-    if (with_scores && (!h->last_fast || h->lastQ != Q || h->parts != 1))
+    if (!h->mem.has_memory()) return fail(INFV_ERR_STATE, "no memory to export (B_past is None)");
+    if (with_scores && !h->mem.chain_exportable(Q))          // (has_memory, which the predicate includes, holds here: refused above)
         return fail(INFV_ERR_STATE, "pack_memory: the scores need a memory whose last step came from infv_ltm_consolidate with Q=%d", Q);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const size_t nC = (size_t)h->L * Q * h->dm;
-    if (!(h->ctx_sum_for == ctx && h->ctx_sum_chunks == n_chunks && h->ctx_sum_Q == Q)) {
+    if (!h->mem.ctx_sum_holds(ctx, n_chunks, Q)) {
         // no sum kept for these outputs (dense / psi plans, the per-chunk path, sums switched off, someone else's ctx): add them up
         // now, in ctx_sum_kernel's fixed order; that overwrites whatever sum the handle held
-        h->ctx_sum_drop();
+        h->mem.drop_ctx_sum();
         HIP_TRY(reserve_all({{h->ctx_sum, (size_t)h->L * h->maxQ * h->dm * sizeof(float)}}));
         HIP_TRY(launch_ctx_sum(ctx, n_chunks, (long)nC, h->ctx_sum.as<float>(), stream));
     }
     PackMemoryArgs a;
     memset(&a, 0, sizeof(a));
-    a.B = h->B[h->cur].as<float>(); a.N = n_basis; a.Np = h->N; a.d = h->d;
-    a.part = h->bin_part[h->pc].as<float>(); a.parts = h->parts; a.pitch = h->n_bins; a.n_mass = h->n_bins - 1;
-    a.scores = with_scores ? h->Sp[h->sc].as<float>() : nullptr;
+    a.B = h->B[h->mem.cur()].as<float>(); a.N = n_basis; a.Np = h->N; a.d = h->d;
+    a.part = h->bin_part.as<float>(); a.parts = h->mem.parts(); a.pitch = h->n_bins; a.n_mass = h->n_bins - 1;
+    a.scores = with_scores ? h->Sp[h->mem.sc()].as<float>() : nullptr;
     a.ctx_sum = h->ctx_sum.as<float>(); a.count = (float)n_chunks;
     a.nB = (long)h->L * n_basis * h->d; a.nM = (long)h->L * a.n_mass; a.nS = with_scores ? (long)h->L * h->H * Q * n_basis : 0; a.nC = (long)nC;
     a.out = payload;
@@ -1078,7 +1055,7 @@ int infv_ltm_export_chain_state(infv_ltm_handle h, int32_t Q, void* blob, void* 
     if (!blob) return fail(INFV_ERR_INVALID, "export_chain_state: null blob");
     if (int rc = check_q(h, Q)) return rc;
     if (int rc = check_chain_error(h)) return rc;
-    if (!h->has_memory || !h->last_fast || h->lastQ != Q || h->parts != 1)
+    if (!h->mem.chain_exportable(Q))
         return fail(INFV_ERR_STATE, "export_chain_state: the memory's last step must come from infv_ltm_consolidate with Q=%d", Q);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     INFV_LAUNCH(blob_header_write_kernel, dim3(1), dim3(64), 0, stream, static_cast<int*>(blob), blob_header(h, Q));
@@ -1086,10 +1063,10 @@ int infv_ltm_export_chain_state(infv_ltm_handle h, int32_t Q, void* blob, void* 
     float* out = static_cast<float*>(blob) + kBlobHeaderInts;
     const size_t nB = (size_t)h->L * h->N * h->d, nKV = (size_t)h->L * h->N * 2 * h->dm, nS = (size_t)h->L * h->H * Q * h->N,
                  nM = (size_t)h->L * h->n_bins;
-    HIP_TRY(hipMemcpyAsync(out, h->B[h->cur].p, nB * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(out + nB, h->KV[h->cur].p, nKV * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(out + nB + nKV, h->Sp[h->sc].p, nS * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(out + nB + nKV + nS, h->bin_part[h->pc].p, nM * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(out, h->B[h->mem.cur()].p, nB * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(out + nB, h->KV[h->mem.cur()].p, nKV * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(out + nB + nKV, h->Sp[h->mem.sc()].p, nS * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(out + nB + nKV + nS, h->bin_part.p, nM * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(out + nB + nKV + nS + nM, h->cqbuf.p, (size_t)h->L * h->H * Q * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return INFV_OK;
 }
@@ -1106,26 +1083,23 @@ int infv_ltm_import_chain_state(infv_ltm_handle h, int32_t Q, const void* blob, 
     const float* in = static_cast<const float*>(blob) + kBlobHeaderInts;
     const size_t nB = (size_t)h->L * h->N * h->d, nKV = (size_t)h->L * h->N * 2 * h->dm, nS = (size_t)h->L * h->H * Q * h->N,
                  nM = (size_t)h->L * h->n_bins;
-    HIP_TRY(hipMemcpyAsync(h->B[h->cur].p, in, nB * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(h->KV[h->cur].p, in + nB, nKV * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(h->Sp[h->sc].p, in + nB + nKV, nS * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(h->bin_part[h->pc].p, in + nB + nKV + nS, nM * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(h->B[h->mem.cur()].p, in, nB * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(h->KV[h->mem.cur()].p, in + nB, nKV * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(h->Sp[h->mem.sc()].p, in + nB + nKV, nS * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(h->bin_part.p, in + nB + nKV + nS, nM * sizeof(float), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipMemcpyAsync(h->cqbuf.p, in + nB + nKV + nS + nM, (size_t)h->L * h->H * Q * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    h->has_memory = true; h->parts = 1; h->lastQ = Q; h->last_fast = true; h->ctx_sum_drop();
-    h->scores_ok = true; h->last_plan = nullptr;
-    h->k_stale = true;                 // the K' half came from a fast-path handle: re-projected on demand
-    h->carry_scores = true;
+    h->mem.chain_imported(Q);
     return INFV_OK;
 }
 
 int infv_ltm_reproject(infv_ltm_handle h, const infv_ltm_proj* proj, void* stream_) {
     if (int rc = check_handle(h)) return rc;
     if (!proj) return fail(INFV_ERR_INVALID, "reproject: null proj");
-    if (!h->has_memory) return INFV_OK;
+    if (!h->mem.has_memory()) return INFV_OK;
     const ProjPtrs pp = make_proj(proj, h->L);
-    HIP_TRY(launch_reproject(h->B[h->cur].as<float>(), h->N, h->d, h->dm, h->L, pp, h->KV[h->cur].as<float>(),
+    HIP_TRY(launch_reproject(h->B[h->mem.cur()].as<float>(), h->N, h->d, h->dm, h->L, pp, h->KV[h->mem.cur()].as<float>(),
                              static_cast<hipStream_t>(stream_)));
-    h->k_stale = false;
+    h->mem.reprojected();
     return INFV_OK;
 }
 
@@ -1135,25 +1109,20 @@ int infv_ltm_import_state(infv_ltm_handle h, int32_t layer, const float* B, cons
     if (layer < 0 || layer >= h->L) return fail(INFV_ERR_INVALID, "layer out of range");
     if (!B || !proj) return fail(INFV_ERR_INVALID, "import: null argument");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP_TRY(hipMemcpyAsync(h->B[h->cur].as<float>() + (size_t)layer * h->N * h->d, B,
+    HIP_TRY(hipMemcpyAsync(h->B[h->mem.cur()].as<float>() + (size_t)layer * h->N * h->d, B,
                            (size_t)h->N * h->d * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    if (h->parts <= 0) h->parts = 1;
-    float* part = h->bin_part[h->pc].as<float>() + (size_t)layer * h->parts * h->n_bins;
-    HIP_TRY(hipMemsetAsync(part, 0, (size_t)h->parts * h->n_bins * sizeof(float), stream));
+    h->mem.layer_import_begins();
+    float* part = h->bin_part.as<float>() + (size_t)layer * h->mem.parts() * h->n_bins;
+    HIP_TRY(hipMemsetAsync(part, 0, (size_t)h->mem.parts() * h->n_bins * sizeof(float), stream));
     if (bin_mass)
         HIP_TRY(hipMemcpyAsync(part, bin_mass, (size_t)(h->n_bins - 1) * sizeof(float), hipMemcpyDeviceToDevice, stream));
     // re-project this layer's memory with its weights
     ProjPtrs one;
     memset(&one, 0, sizeof(one));
     one.wk[0] = proj->wk; one.bk[0] = proj->bk; one.wv[0] = proj->wv; one.bv[0] = proj->bv;
-    HIP_TRY(launch_reproject(h->B[h->cur].as<float>() + (size_t)layer * h->N * h->d, h->N, h->d, h->dm, 1, one,
-                             h->KV[h->cur].as<float>() + (size_t)layer * h->N * 2 * h->dm, stream));
-    h->has_memory = true; h->ctx_sum_drop();
-    // the fused chain's scores (Sp) describe the memory this one replaces: nothing may hand them on any more -- neither
-    // export_chain_state nor the one-shot carry of an import_chain_state that no call consumed
-    h->last_fast = false;
-    h->carry_scores = false;
-    h->scores_ok = false;
+    HIP_TRY(launch_reproject(h->B[h->mem.cur()].as<float>() + (size_t)layer * h->N * h->d, h->N, h->d, h->dm, 1, one,
+                             h->KV[h->mem.cur()].as<float>() + (size_t)layer * h->N * 2 * h->dm, stream));
+    h->mem.layer_imported();
     return INFV_OK;
 }
 
@@ -1168,11 +1137,11 @@ int infv_ltm_get_draw(infv_ltm_handle h, int32_t layer, int32_t* bins, int32_t* 
     if (idx) HIP_TRY(hipMemcpy(idx, h->idx.as<int32_t>() + (size_t)layer * h->S, h->S * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (probs) HIP_TRY(hipMemcpy(probs, h->probs.as<float>() + (size_t)layer * h->n_bins, (h->n_bins - 1) * sizeof(float), hipMemcpyDeviceToHost));
     if (scores) {
-        if (h->lastQ <= 0) return fail(INFV_ERR_STATE, "no scores yet");
-        const size_t n = (size_t)h->H * h->lastQ * h->N;
-        if (h->last_fast) {
-            std::vector<float> cq((size_t)h->H * h->lastQ);
-            HIP_TRY(hipMemcpy(scores, h->Sp[h->sc].as<float>() + (size_t)layer * n, n * sizeof(float), hipMemcpyDeviceToHost));
+        if (h->mem.lastQ() <= 0) return fail(INFV_ERR_STATE, "no scores yet");
+        const size_t n = (size_t)h->H * h->mem.lastQ() * h->N;
+        if (h->mem.last_fast()) {
+            std::vector<float> cq((size_t)h->H * h->mem.lastQ());
+            HIP_TRY(hipMemcpy(scores, h->Sp[h->mem.sc()].as<float>() + (size_t)layer * n, n * sizeof(float), hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(cq.data(), h->cqbuf.as<float>() + (size_t)layer * cq.size(), cq.size() * sizeof(float), hipMemcpyDeviceToHost));
             for (size_t r = 0; r < cq.size(); ++r)
                 for (int j = 0; j < h->N; ++j) scores[r * h->N + j] += cq[r];

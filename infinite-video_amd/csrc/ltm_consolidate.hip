@@ -77,14 +77,14 @@ struct FastPipe {
     int refuse_draw(int draw_mode, const double* u) const {
         if (draw_mode != 1) return INFV_OK;
         if (!u && !h->rng_on) return fail(INFV_ERR_INVALID, "sticky consolidation needs the Gibbs uniforms u");
-        if (counter == 0 && h->parts <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available");
+        if (counter == 0 && h->mem.parts() <= 0) return fail(INFV_ERR_STATE, "no sticky histogram available");
         return INFV_OK;
     }
     // the fields ChainRoleS and ChainBatchArgs share by name: the draw's inputs and outputs, the trace rows, the new-row scores
     template <class A> void fill_role_s(A& a, const float* Snew, int sk, long ss, const double* u) const {
-        a.part_prev = h->bin_part[h->pc].as<float>(); a.parts = h->parts;
+        a.part_prev = h->bin_part.as<float>(); a.parts = h->mem.parts();
         a.probs_override = h->probs_override.as<float>(); a.override_mask = h->override_mask;
-        a.u = u; a.rng = h->rng_view(h->pos); a.uniform_idx = plan.uniform_idx.as<int32_t>();
+        a.u = u; a.rng = h->rng_view(h->mem.pos()); a.uniform_idx = plan.uniform_idx.as<int32_t>();
         a.probs_out = h->probs.as<float>(); a.bins_out = h->bins.as<int32_t>(); a.idx_out = h->idx.as<int32_t>();
         if (h->trace_cap > counter) {
             a.probs_tr = h->trace_probs ? h->trace_probs + (size_t)counter * h->L * h->n_bins : nullptr;
@@ -96,12 +96,8 @@ struct FastPipe {
     // the handle's host state after role S of `n` steps
     void after_role_s(int draw_mode, int n) {
         if (draw_mode == 1) h->override_mask = 0;
-        h->sc ^= 1;
-        h->lastQ = Q;
-        h->last_fast = true;
-        h->scores_ok = true; h->last_plan = &plan;
+        h->mem.role_s_done(&plan, Q, n);
         counter += n;
-        h->pos += (uint32_t)n;
     }
 
     int launch_s(const StepS& st) {
@@ -123,7 +119,7 @@ struct FastPipe {
         s.acc_next = h->mass_acc[counter % 3].as<unsigned long long>();
         s.acc_clear = h->mass_acc[(counter + 1) % 3].as<unsigned long long>();
         s.tab_out = h->tab_ring.as<int32_t>() + slot * tab_slot();
-        s.Sp_prev = h->Sp[h->sc].as<float>(); s.Sp_next = h->Sp[h->sc ^ 1].as<float>();
+        s.Sp_prev = h->Sp[h->mem.sc()].as<float>(); s.Sp_next = h->Sp[h->mem.sc() ^ 1].as<float>();
         s.alpha_out = h->alpha_ring.as<float>() + slot * alpha_slot();
         s.asum_out = h->asum_ring.as<float>() + slot * asum_slot();
         static StampBuf stamps("INFV_CHAIN_STAMPS", 32);
@@ -164,7 +160,7 @@ struct FastPipe {
         b.publish_init = (batch_launches == 0) ? 1 : 0;
         b.alpha_ring = h->alpha_ring.as<float>(); b.alpha_slot = (long)alpha_slot();
         b.asum_ring = h->asum_ring.as<float>(); b.asum_slot = (long)asum_slot();
-        b.Sp_in = h->Sp[h->sc].as<float>(); b.Sp_out = h->Sp[h->sc ^ 1].as<float>();
+        b.Sp_in = h->Sp[h->mem.sc()].as<float>(); b.Sp_out = h->Sp[h->mem.sc() ^ 1].as<float>();
         static StampBuf stamps("INFV_CHAIN_STAMPS", 32);
         b.dbg = stamps.dev;
         long long hb[32];
@@ -215,13 +211,13 @@ struct FastPipe {
         u.N = h->N; u.H = h->H; u.Q = Q; u.L = h->L; u.d = h->d; u.dm = h->dm; u.tabw = op.tabw;
         u.op = op.view();
         u.gather = inf ? 1 : 0;
-        u.have_state = h->has_memory ? 1 : 0;
+        u.have_state = h->mem.has_memory() ? 1 : 0;
         u.n_chunks = sb.nb; u.slot0 = slot0 % h->ring; u.ring = h->ring;
         u.tab = h->tab_ring.as<int32_t>(); u.tab_slot = (long)tab_slot();
         u.alpha = h->alpha_ring.as<float>(); u.asum = h->asum_ring.as<float>();
         u.R = sb.r_rows; u.Pnew = h->P_ws[sb.set].as<float>(); u.p_ld = p_ld(); u.splitk = sb.splitk; u.split_stride = sb.split_stride;
-        u.B_prev = h->B[h->cur].as<float>(); u.KV_prev = h->KV[h->cur].as<float>();
-        u.B_next = h->B[h->cur ^ 1].as<float>(); u.KV_next = h->KV[h->cur ^ 1].as<float>();
+        u.B_prev = h->B[h->mem.cur()].as<float>(); u.KV_prev = h->KV[h->mem.cur()].as<float>();
+        u.B_next = h->B[h->mem.cur() ^ 1].as<float>(); u.KV_next = h->KV[h->mem.cur() ^ 1].as<float>();
         for (int l = 0; l < h->L; ++l) u.bv[l] = pp.bv[l];
         u.ctx = ctx; u.ctx_sum = ctx_sum;
         static StampBuf stamps("INFV_UC_STAMPS", 16);
@@ -232,9 +228,7 @@ struct FastPipe {
             Timed t_(h->prof, INFV_KERNEL_UC, ucs);
             if (!(skip_mask() & (4 | 32))) HIP_TRY(::infv::launch_uc(u, ucs));
         }
-        h->cur ^= 1;
-        h->has_memory = true;
-        h->ctx_sum_drop();                                      // (consolidate_join declares the finished call's sum valid)
+        h->mem.memory_written(1);                               // (consolidate_join declares the finished call's output sum valid)
         return INFV_OK;
     }
 
@@ -475,7 +469,7 @@ int consolidate_setup(infv_ltm_handle h, ConsolidateCall& cc, const FastPipe& pi
         const size_t need_u = (size_t)cc.n_chunks * cc.chunk_u * sizeof(float);
         HIP_TRY(reserve_all({{h->uf_all, need_u}}));
         if (cc.u) HIP_TRY(launch_round_up_uniforms(cc.u, h->uf_all.as<float>(), (long)cc.n_chunks * (long)cc.chunk_u, stream));
-        else HIP_TRY(launch_rng_fill(h->rng_view(h->pos), cc.n_chunks, h->L, h->S, nullptr, h->uf_all.as<float>(), stream));
+        else HIP_TRY(launch_rng_fill(h->rng_view(h->mem.pos()), cc.n_chunks, h->L, h->S, nullptr, h->uf_all.as<float>(), stream));
         cc.uf = h->uf_all.as<float>();
     }
     return INFV_OK;
@@ -492,7 +486,7 @@ void consolidate_schedule(infv_ltm_handle h, ConsolidateCall& cc) {
         chain_batch_resident(h->N, h->S, plan.inf.rows, plan.inf.tabw,
                              chain_batch_blocks(h->H, cc.Q, h->L, mode, plan.sticky().points_ok, plan.inf.rows, h->S),
                              mode, plan.sticky().points_ok, cc.Q);
-    cc.first_c = h->has_memory ? 0 : 1;                      // the first chunk of a document runs on its own (consolidate_first_chunk)
+    cc.first_c = h->mem.has_memory() ? 0 : 1;                // the first chunk of a document runs on its own (consolidate_first_chunk)
     // sub-batch size: long calls amortise the per-launch gap of role S over more chunks (42 x 64 new rows = 21 row tiles:
     // 126 score tiles, 252 V' tiles); short ones (e.g. a 256-chunk shard of a multi-GPU run) keep 32 so that the
     // pipeline fills and drains quickly.  INFV_SUB_BATCH overrides.  Every sub-batch but the last has `sub` chunks.
@@ -590,7 +584,7 @@ SubBatch sub_batch_of(infv_ltm_handle h, const ConsolidateCall& cc, int b) {
 int consolidate_first_chunk(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pipe) {
     const Plan& plan = *cc.plan;
     hipStream_t stream = cc.stream, ucs = h->ucs;
-    if (!h->has_memory) {
+    if (!h->mem.has_memory()) {
         const float* kb0 = cc.kbar_pre;
         if (!kb0) {
             HIP_TRY(reserve_all({{h->kbar_ws, (size_t)cc.T * h->d * sizeof(float)}}));
@@ -609,18 +603,18 @@ int consolidate_first_chunk(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pi
         if (int rc = pipe.launch_mass_trace(0, 1, 0)) return rc;
         if (int rc = pipe.launch_uc(plan.first, false, sb, 0, cc.ctx)) return rc;
         HIP_TRY(h->ev_uc[2].record(ucs));
-    } else if (h->carry_scores && h->last_fast && h->lastQ == cc.Q) {
+    } else if (h->mem.carry_fits(cc.Q)) {
         // ... handed over by infv_ltm_import_chain_state: the scores under this query and the projected memory are the
         // exporting handle's own; nothing is re-derived, the chain goes on bit for bit
     } else {
         // ... bias-free scores of the current K' rows under this query
-        if (h->k_stale)
+        if (h->mem.k_stale())
             if (int rc = infv_ltm_reproject(h, cc.proj, cc.stream_)) return rc;
         Timed t_(h->prof, INFV_KERNEL_SCORES, stream);
-        HIP_TRY(launch_new_scores(cc.q, cc.Q, h->H, h->L, 1, h->N, h->KV[h->cur].as<float>(), 0, 2L * h->dm,
-                                  (long)h->N * 2 * h->dm, 1, 0, *cc.pp, h->Sp[h->sc].as<float>(), h->cqbuf.as<float>(), stream));
+        HIP_TRY(launch_new_scores(cc.q, cc.Q, h->H, h->L, 1, h->N, h->KV[h->mem.cur()].as<float>(), 0, 2L * h->dm,
+                                  (long)h->N * 2 * h->dm, 1, 0, *cc.pp, h->Sp[h->mem.sc()].as<float>(), h->cqbuf.as<float>(), stream));
     }
-    h->carry_scores = false;
+    h->mem.carry_consumed();
     return INFV_OK;
 }
 
@@ -845,13 +839,10 @@ int consolidate_sub_batches(infv_ltm_handle h, ConsolidateCall& cc, FastPipe& pi
 // float partial row and bring the K' half of the projected memory up to date.
 int consolidate_join(infv_ltm_handle h, const ConsolidateCall& cc, const FastPipe& pipe) {
     for (int i = 0; i < kPSets; ++i) HIP_TRY(h->ev_uc[i].wait_on(cc.stream));
-    if (pipe.counter > 0) {
+    if (pipe.counter > 0)
         HIP_TRY(launch_acc_to_part(h->mass_acc[(pipe.counter + 2) % 3].as<unsigned long long>(), h->L, 1,
-                                   h->bin_part[h->pc].as<float>(), cc.stream));
-        h->parts = 1;
-    }
-    h->k_stale = true;                                        // K' is re-projected from B on demand (per-call path, continuation)
-    if (pipe.ctx_sum) { h->ctx_sum_for = cc.ctx; h->ctx_sum_chunks = cc.n_chunks; h->ctx_sum_Q = cc.Q; }
+                                   h->bin_part.as<float>(), cc.stream));
+    h->mem.fused_call_joined(pipe.counter > 0, pipe.ctx_sum ? cc.ctx : nullptr, cc.n_chunks, cc.Q);
     return INFV_OK;
 }
 
@@ -877,7 +868,7 @@ int consolidate_impl(infv_ltm_handle h, ConsolidateCall& cc, int32_t new_doc) {
     if (int rc = ensure_side_stream(h)) return rc;
     h->clear_call_events();
     FastPipe pipe{h, *plan, cc.Q, pp, cc.stream};
-    h->ctx_sum_drop();
+    h->mem.drop_ctx_sum();
     if (h->ctx_sum_on && uc_ctx_sum_supported(cc.Q)) pipe.ctx_sum = h->ctx_sum.as<float>();
     if (int rc = consolidate_setup(h, cc, pipe)) return rc;
     consolidate_schedule(h, cc);

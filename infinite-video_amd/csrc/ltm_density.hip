@@ -240,10 +240,10 @@ int check_last_step(infv_ltm_handle h, const char* name, int32_t layer, int32_t 
     if (int rc = check_q(h, Q)) return rc;
     if (int rc = check_chain_error(h)) return rc;
     if (any_psi_plan(h)) return fail(INFV_ERR_UNSUPPORTED, "%s: general-psi plans (infv_ltm_set_psi_plan) have no box density", name);
-    if (!h->has_memory || !h->scores_ok)
+    if (!h->mem.last_scores_readable())
         return fail(INFV_ERR_STATE, "%s: the handle holds no scores of a last step (no memory yet, or infv_ltm_import_state replaced it)", name);
-    if (h->lastQ != Q) return fail(INFV_ERR_STATE, "%s: the last step ran with Q=%d, not %d", name, h->lastQ, Q);
-    *plan = h->last_plan ? h->last_plan : (h->plans.empty() ? nullptr : h->plans.begin()->second);
+    if (h->mem.lastQ() != Q) return fail(INFV_ERR_STATE, "%s: the last step ran with Q=%d, not %d", name, h->mem.lastQ(), Q);
+    *plan = h->mem.last_plan() ? h->mem.last_plan() : (h->plans.empty() ? nullptr : h->plans.begin()->second);
     if (!*plan) return fail(INFV_ERR_NO_PLAN, "%s: no plan registered (its read-out weights are needed)", name);
     return INFV_OK;
 }
@@ -251,8 +251,8 @@ int check_last_step(infv_ltm_handle h, const char* name, int32_t layer, int32_t 
 // rows of `layer`: after the fused chain the bias-free scores + their bias term, else the attend kernel's full scores
 void last_rows(infv_ltm_handle h, int layer, int Q, const float** rows, const float** cq) {
     const size_t n = (size_t)h->H * Q * h->N;
-    if (h->last_fast) {
-        *rows = h->Sp[h->sc].as<float>() + (size_t)layer * n;
+    if (h->mem.last_fast()) {
+        *rows = h->Sp[h->mem.sc()].as<float>() + (size_t)layer * n;
         *cq = h->cqbuf.as<float>() + (size_t)layer * h->H * Q;
     } else {
         *rows = h->scores.as<float>() + (size_t)layer * n;

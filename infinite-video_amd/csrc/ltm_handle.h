@@ -4,6 +4,7 @@
 #include "../../include/infv_ltm.h"
 #include "ltm_internal.h"
 #include "capi_common.h"
+#include "ltm_memory_state.h"
 #include "vqf_internal.h"
 
 #include <cstring>
@@ -120,16 +121,9 @@ struct infv_ltm_s {
     infv_ltm_config cfg;
     int N, H, dh, d, dm, P, L, S, maxQ, maxC;
     std::map<int, infv::Plan*> plans;
-    infv::DeviceBuf B[2], KV[2];       // [L][N][d], [L][N][2][dm]   ping-pong
-    int cur = 0;
-    bool has_memory = false;
-    int lastQ = 0;                     // query length of the last attend
-    bool last_fast = false;            // last step ran in the fused chain kernel (scores = Sp + cq)
-    bool k_stale = false;              // the K' half of KV is out of date (the fast path does not maintain it)
-    bool carry_scores = false;         // one-shot (import_chain_state): the next consolidate continues from Sp / V' as they are
-    int parts = 0;                     // row count of bin_part per layer, set by the last attend
-    infv::DeviceBuf bin_part[2];       // [L][max_parts][n_bins]  sticky partials (ping-pong in the fast path)
-    int pc = 0;                        // which bin_part holds the latest partials
+    infv::MemoryState mem;             // which buffers are live, what the last step left behind, the rng position (ltm_memory_state.h)
+    infv::DeviceBuf B[2], KV[2];       // [L][N][d], [L][N][2][dm]   ping-pong (mem.cur())
+    infv::DeviceBuf bin_part;          // [L][max_parts][n_bins]  sticky partials, mem.parts() rows per layer in use
     infv::DeviceBuf probs, probs_override, bins, idx, scores;
     unsigned override_mask = 0;        // layers whose next draw uses probs_override (teacher forcing)
     // workspaces of the chunk-parallel stage.  consolidate() fills P set b % kPSets (projections; pooled frames when the rows
@@ -189,23 +183,17 @@ struct infv_ltm_s {
     infv::DeviceBuf R_all, planes_all[3];    // one pooling launch per call: every new row of the call (fp32, and as three bf16 planes per sub-batch for the projection GEMM)
     infv::DeviceBuf pool_done;         // ... and its per-sub-batch completion counts
     // Sum of a consolidate call's outputs, kept by the UC kernels as they store them (infv_ltm_set_ctx_sum; the hand-over payload
-    // of infv_ltm_pack_memory): valid for exactly the (ctx, n_chunks, Q) of the fused call that filled it, until the memory steps again
+    // of infv_ltm_pack_memory): valid for exactly the (ctx, n_chunks, Q) that mem holds for it (mem.ctx_sum_holds)
     bool ctx_sum_on = false;
     infv::DeviceBuf ctx_sum;           // [L][Q][dm]
-    const float* ctx_sum_for = nullptr; int ctx_sum_chunks = 0, ctx_sum_Q = 0;   // ctx_sum_for == nullptr: not valid
-    void ctx_sum_drop() { ctx_sum_for = nullptr; }
     infv::DeviceBuf vid_tab, vid_kbar, vid_P;   // infv_ltm_consolidate_videos with this handle first: video table, pooled frames and projected rows of one step
-    int sc = 0;
     int n_bins = 128;
-    // device rng (infv_ltm_set_rng): with it on, a NULL u is generated by the kernels (philox.h).  pos = steps since the last reset.
-    bool rng_on = false; uint64_t rng_seed = 0; uint32_t rng_stream = 0; uint32_t pos = 0;
+    // device rng (infv_ltm_set_rng): with it on, a NULL u is generated by the kernels (philox.h), at position mem.pos()
+    bool rng_on = false; uint64_t rng_seed = 0; uint32_t rng_stream = 0;
     bool gen(const void* u) const { return !u && rng_on; }                       // this call's uniforms are generated
     infv::RngView rng_view(uint32_t at) const { infv::RngView g = infv::make_rng_view(rng_seed, rng_stream, at); g.on = rng_on ? 1u : 0u; return g; }
-    // read-outs of the attention density (ltm_density.hip).  scores_ok: the handle holds the full scores of the memory's last step
-    // (`scores`, or Sp[sc] + cqbuf after the fused chain); import_state, which re-derives nothing, clears it.
+    // read-outs of the attention density (ltm_density.hip), which need mem.last_scores_readable()
     infv::GridPlan grid;
-    bool scores_ok = false;
-    const infv::Plan* last_plan = nullptr;     // plan of the last step (its read-out weights)
     float* mass_trace = nullptr; long mass_cap = 0;   // box-mass trace of the multi-chunk calls (caller's device buffer [cap][L][N])
     long mass_at = -1;                 // chunk index inside the multi-chunk call that is running its per-chunk stages, or -1
     float* vmass_trace = nullptr; long vmass_cap = 0; // packed box-mass trace of the lockstep calls this handle leads ([cap][L][N], infv_ltm_set_videos_mass_trace)

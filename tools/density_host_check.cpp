@@ -121,10 +121,12 @@ int main() {
     EXPECT(infv_ltm_masses(h, 0, 8, nullptr, nullptr) == INFV_ERR_INVALID);
     EXPECT(infv_ltm_density(h, 0, 8, dummy, nullptr) == INFV_ERR_STATE);                 // no memory
     EXPECT(infv_ltm_masses(h, 0, 8, dummy, nullptr) == INFV_ERR_STATE);
-    h->has_memory = true; h->scores_ok = false; h->lastQ = 8;                            // as infv_ltm_import_state leaves it
+    h->mem.memory_written(1); h->mem.attended(h->plans[8], 8, 24, 1);                    // a step with Q = 8 ...
+    h->mem.layer_import_begins(); h->mem.layer_imported();                               // ... then as infv_ltm_import_state leaves it
+    EXPECT(h->mem.has_memory() && !h->mem.scores_ok() && h->mem.lastQ() == 8);
     EXPECT(infv_ltm_density(h, 0, 8, dummy, nullptr) == INFV_ERR_STATE);
     EXPECT(infv_ltm_masses(h, 0, 8, dummy, nullptr) == INFV_ERR_STATE);
-    h->scores_ok = true;
+    h->mem.memory_written(1); h->mem.attended(h->plans[8], 8, 24, 1);                    // another step: its scores are there
     EXPECT(infv_ltm_density(h, 0, 9, dummy, nullptr) == INFV_ERR_STATE);                 // another Q than the last step's
     EXPECT(infv_ltm_masses(h, 0, 9, dummy, nullptr) == INFV_ERR_STATE);
     EXPECT(infv_ltm_density(h, 0, 8, dummy, nullptr) == INFV_ERR_STATE);                 // no grid plan
