@@ -1,4 +1,4 @@
-// Shared by the C-ABI translation units (ltm_capi.hip, ltm_consolidate.hip, vqf_capi.hip): error reporting and device buffers.
+// Shared by the C-ABI translation units (the ltm_* host units, vqf_capi.hip, vqf_video.hip, vqf_vc.hip): error reporting and device buffers.
 #pragma once
 #include "knobs.h"
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// Internal interface between the video Q-former C ABI (vqf_capi.hip) and its gfx950 kernels (vqf_kernels.hip).
+// Internal interface between the video Q-former C ABI (vqf_capi.hip, vqf_video.hip, vqf_vc.hip) and its gfx950 kernels (vqf_kernels.hip).
 #pragma once
 #include "knobs.h"
 #include "../../include/infv_ltm.h"      // tok_code
@@ -9,7 +9,7 @@ namespace infv {
 
 constexpr int kQfMaxSeg = 4;
 
-// Host-side seams of the layer-major calls (vqf_capi.hip): a large call is cut into pieces of these sizes, each with its own
+// Host-side seams of the layer-major calls (vqf_video.hip, vqf_vc.hip): a large call is cut into pieces of these sizes, each with its own
 // offset arithmetic.  tests/golden/seam_cases.py reads them from here.
 constexpr int kRowBlockVideo = 64;       // chunks per row block of the query-token GEMMs, infv_vqf_encode_video
 constexpr int kRowBlockVideos = 128;     // ... of the batch-invariant calls (infv_vqf_encode_videos, infv_vqf_vc_encode_videos)

@@ -46,8 +46,8 @@ MECHANISMS: Dict[str, str] = {
     "shared_streams": "two handles on two caller streams share ucs / pools / side (shared_streams) and process-wide buffers",
     "uniform_ring": "LongTermAttention._draw_uniforms: the draw kernel reads a 64-slot pinned ring guarded by an event every 16 calls",
     "pool_cache": "the drop-in module's _pool_cache: a second module steps from the frame means the first one pooled",
-    "vqf_side_stream": "vqf_capi.hip runs the memories of the later layers on the shared worker stream under ev_main / ev_side",
-    "weights_epoch": "vqf_capi.hip caches layer 0's prefix and the weight planes across calls while the weights epoch stands",
+    "vqf_side_stream": "vqf_video.hip / vqf_vc.hip run the memories of the later layers on the shared worker stream under ev_main / ev_side",
+    "weights_epoch": "vqf_video.hip caches layer 0's prefix, vqf_capi.hip the weight planes, across calls while the weights epoch stands",
     "ids_staging": "run_embed reuses a pinned id staging buffer behind ev_ids",
     "ln_stats": "infv_vqf_layernorm_tokens keeps its row statistics in a process-wide buffer behind the last_read event",
     "caller_stream_only": "single-stream helpers exported for tests: every launch on the caller's stream",
