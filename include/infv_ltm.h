@@ -331,6 +331,56 @@ int infv_ltm_steps_videos_from(const infv_ltm_handle* hs, int32_t V, const int32
                                const int32_t* kbar_chunk0, int32_t T, const float* q, int32_t q_per_chunk, int32_t Q,
                                const infv_ltm_proj* proj, const double* u, int32_t new_doc, float* ctx, void* stream);
 
+/* The lockstep calls for videos whose LAST chunk is short (additive in ABI 6).  The reference's drivers cut a video with
+ * torch.split(video, n_frames, dim=1) (run_inference_inf_video_llama_nextqa.py:228): a video whose frame count is no multiple of T
+ * ends in a chunk of fewer frames, which steps with the plan for ITS length.  One descriptor serves both forms of the call: frame
+ * tokens (`k`, pooled per step: infv_ltm_consolidate_videos) or frame means (`kbar`, infv_ltm_steps_videos); exactly one is set.
+ *   tail_T [V]  HOST int32: frames of video v's last chunk; 0 or T: a full chunk.  Ignored for a video with no chunk.
+ * Layout.  k and kbar are packed by FRAME: video v has frames(v) = (len_v - 1) * T + tail(v) frames (len_v = cu[v+1] - cu[v], 0
+ * without a chunk) and they start at frame sum_{w<v} frames(w): k is [sum frames, P, d], kbar [sum frames, d].  With no short
+ * tail that is byte for byte the layout of the calls above.  u, ctx and a per-chunk q stay packed by CHUNK through cu.
+ * Contract.  Per video, every output and every piece of handle state equals BIT FOR BIT what two of the calls above leave:
+ *   infv_ltm_consolidate_videos (k) or infv_ltm_steps_videos (kbar) on the video's full chunks, then the same entry point with
+ *   new_doc = 0 and T = tail(v) on its last chunk (with the call's new_doc if that chunk is the video's only one)
+ * -- ctx, B and K'/V', the sticky bin partials, probs / bins / idx / scores of the last step (infv_ltm_get_draw), the rows of an
+ * armed draw trace and of the lead's packed mass trace, the rng position and what the handle remembers of its last step (its plan
+ * is the one for tail(v)).  A video's bits do not depend on the rest of the batch.  Everything is enqueued on hip_stream; no host
+ * buffer outlives the call (the per-video frame counts travel in kernel arguments beside the video table, the operator of a short
+ * chunk is read from its plan on the device).
+ * A step is still five launches (six with the packed mass trace) whatever mix of tail lengths it holds: pooling / gather, the
+ * new-row projection and the update take the frames and the operator per video; the draw, the attend and the box masses do not
+ * depend on T.  The projected-row workspace holds, per video, the most rows of any plan involved rounded up to 64.
+ * Shapes the lockstep kernels do not take (a dense or psi plan for T or for any tail length, N above 256 or not a multiple of 16,
+ * S above 1024) run per handle: infv_ltm_consolidate / infv_ltm_steps / infv_ltm_consolidate_pooled on the full chunks, then one
+ * chunk at the tail length.
+ * The stream is a FIELD of the descriptor, not a `void* stream` parameter, as in infv_ltm_sources_videos_desc and for its reason
+ * (tests/golden/stream_cases.py lists every function that declares such a parameter); this call's stream-order scenario lives in
+ * tests/test_videos_tail_gpu.py.
+ * Refused before any handle changes (the resets of new_doc included): a null descriptor or tail_T; both k and kbar, or neither;
+ * tail_T[v] outside {0} and [2, T] (a chunk of one frame has an empty operator, LTM.py:79-82); a handle without a plan for its
+ * tail length (INFV_ERR_NO_PLAN); handles that share a tail length but whose plans for it differ; a tail plan that differs from the
+ * plan for T in a table that does not depend on the chunk length (read-out weights, sticky histogram, uniform resampling table);
+ * reserved != 0; and everything infv_ltm_consolidate_videos / infv_ltm_steps_videos refuse.  kbar_chunk0 is not offered here. */
+typedef struct {
+    const infv_ltm_handle* hs;   /* HOST [V] */
+    int32_t V;
+    int32_t T;                   /* frames of a full chunk */
+    const int32_t* cu;           /* HOST [V+1], in chunks, as the lockstep calls take it */
+    const int32_t* tail_T;       /* HOST [V] */
+    const void*    k;            /* DEVICE [sum frames, P, d] in the handles' token dtype, or NULL */
+    const float*   kbar;         /* DEVICE [sum frames, d] fp32, 16-byte aligned, or NULL */
+    const float*   q;            /* DEVICE [L, Q, dm], or [cu[V], L, Q, dm] with q_per_chunk */
+    int32_t q_per_chunk;         /* 0 / 1 */
+    int32_t Q;
+    const infv_ltm_proj* proj;   /* HOST [L] */
+    const double*  u;            /* DEVICE [cu[V], L, S] or NULL */
+    int32_t new_doc;
+    int32_t reserved;            /* 0 */
+    float*         ctx;          /* DEVICE [cu[V], L, Q, dm], output */
+    void*          hip_stream;   /* the stream of every launch (see above) */
+} infv_ltm_videos_tail_desc;
+int infv_ltm_videos_tail(const infv_ltm_videos_tail_desc* d);
+
 /* The hand-over payload of a consolidate call in ONE kernel launch: everything a peer needs from this handle after
  * infv_ltm_consolidate, as one fp32 DEVICE buffer
  *   B [L][n_basis][d] | sticky bin masses [L][n_bins-1] | (with_scores: bias-free scores [L][H][Q][n_basis]) |

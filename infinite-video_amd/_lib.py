@@ -86,6 +86,14 @@ class SourcesVideosDesc(C.Structure):
                 ("attn_all", C.c_void_p), ("bad_bins", C.c_void_p), ("hip_stream", C.c_void_p)]
 
 
+class VideosTailDesc(C.Structure):
+    """infv_ltm_videos_tail_desc: one lockstep call over videos whose last chunk may be short (the stream is a field)."""
+    _fields_ = [("hs", C.c_void_p), ("V", C.c_int32), ("T", C.c_int32), ("cu", C.c_void_p), ("tail_T", C.c_void_p),
+                ("k", C.c_void_p), ("kbar", C.c_void_p), ("q", C.c_void_p), ("q_per_chunk", C.c_int32), ("Q", C.c_int32),
+                ("proj", C.c_void_p), ("u", C.c_void_p), ("new_doc", C.c_int32), ("reserved", C.c_int32), ("ctx", C.c_void_p),
+                ("hip_stream", C.c_void_p)]
+
+
 class Proj(C.Structure):
     _fields_ = [("wk", C.c_void_p), ("bk", C.c_void_p), ("wv", C.c_void_p), ("bv", C.c_void_p)]
 
@@ -188,6 +196,7 @@ _SIGNATURES = {
                                         C.c_int32, C.POINTER(Proj), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "infv_ltm_steps_videos_from": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                              C.c_int32, C.c_int32, C.POINTER(Proj), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "infv_ltm_videos_tail": (C.c_int, [C.POINTER(VideosTailDesc)]),
     "infv_ltm_export_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "infv_ltm_import_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Proj), C.c_void_p]),
     "infv_ltm_set_ctx_sum": (C.c_int, [C.c_void_p, C.c_int32]),

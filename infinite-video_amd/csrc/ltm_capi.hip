@@ -367,12 +367,23 @@ int infv_ltm_set_plan(infv_ltm_handle h, const infv_ltm_plan* p) {
         mix(p->edge_box, (size_t)(p->n_bins + 1) * 4); mix(p->edge_dx, (size_t)p->n_bins * 4); mix(p->bin_box, (size_t)p->n_bins * 4);
         mix(p->uniform_idx, (size_t)h->S * 4);
         plan->digest = x;
+        // the tables basis_maps builds from (num_basis, tau, nb_samples) alone, whatever T
+        x = 1469598103934665603ull;
+        mix(&p->n_bins, 4);
+        mix(p->readout_w, (size_t)h->N * 4); mix(&p->readout_w_out, 4);
+        mix(p->edge_box, (size_t)(p->n_bins + 1) * 4); mix(p->edge_dx, (size_t)p->n_bins * 4); mix(p->bin_box, (size_t)p->n_bins * 4);
+        mix(p->uniform_idx, (size_t)h->S * 4);
+        plan->shared_digest = x;
     }
     hipError_t e = upload(plan->w, p->readout_w, h->N);
     if (e == hipSuccess) e = upload(plan->edge_box, p->edge_box, p->n_bins + 1);
     if (e == hipSuccess) e = upload(plan->edge_dx, p->edge_dx, p->n_bins);
     if (e == hipSuccess) e = upload(plan->bin_box, p->bin_box, p->n_bins);
     if (e == hipSuccess) e = upload(plan->uniform_idx, p->uniform_idx, h->S);
+    if (e == hipSuccess) {
+        const OperatorView views[2] = {plan->first.view(), plan->inf.view()};
+        e = upload(plan->views, views, 2);
+    }
     if (e != hipSuccess) { delete plan; return fail(INFV_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e)); }
     auto it = h->plans.find(p->T);
     if (it != h->plans.end()) {
@@ -673,9 +684,18 @@ struct VideosCall {
     const char* name; const infv_ltm_handle* hs; int V; const int32_t* cu;
     bool tokens; const char* k; const float* kbar; const int32_t* kbar_chunk0;
     int T; const float* q; bool q_per_chunk; int Q; const infv_ltm_proj* proj; const double* u; int new_doc; float* ctx; void* stream_;
+    // infv_ltm_videos_tail: frames of every video's LAST chunk (0 or T: full), k / kbar then packed by FRAME; nullptr for the other calls
+    const int32_t* tail_T = nullptr;
     // derived by videos_validate
     int total = 0; bool sticky = false; std::vector<Plan*> plans;
     size_t chunk_k = 0, chunk_kbar = 0, chunk_ctx = 0, chunk_u = 0;
+    bool ragged = false;               // some video's last chunk is short: the stages that depend on T take it per video
+    std::vector<Plan*> last_plans;     // plan of video v's last chunk (ragged only)
+    std::vector<long long> frame0;     // first frame of video v in the packed k / kbar (ragged only)
+    int rows_max = 0;                  // most new rows of any operator the call may use
+    int tail(int v) const { return (tail_T && tail_T[v] != 0 && len(v) > 0) ? tail_T[v] : T; }
+    bool short_tail(int v) const { return len(v) > 0 && tail(v) != T; }
+    const Plan* last_plan(int v) const { return ragged ? last_plans[v] : plans[v]; }
     // the lockstep stages
     hipStream_t stream = nullptr; ProjPtrs pp; int parts = 0;
     std::vector<int> order;            // the present group's videos by decreasing length: those still running at step s are ranks [0, n_s)
@@ -737,6 +757,35 @@ int videos_validate(VideosCall& vc) {
         if (!vc.new_doc && vc.sticky && h->mem.parts() <= 0)
             return fail(INFV_ERR_STATE, "%s: handle %d has no sticky histogram (import_state or step first)", name, v);
     }
+    if (vc.tail_T) {
+        // a short last chunk steps with the handle's plan for ITS length; videos that share a length share that plan, and every
+        // plan of the call agrees on the tables the draw and the attend take once per step (Plan::shared_digest)
+        vc.last_plans = vc.plans;
+        vc.frame0.assign(V, 0);
+        std::map<int, Plan*> by_tail;
+        long long frame = 0;
+        for (int v = 0; v < V; ++v) {
+            vc.frame0[v] = frame;
+            if (vc.len(v) == 0) continue;                        // (its tail_T entry is ignored)
+            const int t = vc.tail_T[v];
+            if (t != 0 && (t < 2 || t > vc.T))
+                return fail(INFV_ERR_INVALID, "%s: tail_T[%d] = %d is neither 0 nor in [2, T = %d] (a chunk of one frame has an empty "
+                                              "operator)", name, v, t, vc.T);
+            frame += (long long)(vc.len(v) - 1) * vc.T + vc.tail(v);
+            if (!vc.short_tail(v)) continue;
+            if (int rc = find_plan(hs[v], t, &vc.last_plans[v])) return rc;
+            const Plan& lp = *vc.last_plans[v];
+            auto seen = by_tail.emplace(t, vc.last_plans[v]);
+            if (!same_plan(*seen.first->second, lp))
+                return fail(INFV_ERR_INVALID, "%s: handle %d's plan for its tail length %d differs from that of an earlier handle "
+                                              "with the same tail length", name, v, t);
+            if (lp.shared_digest != vc.plans[0]->shared_digest || lp.n_bins != vc.plans[0]->n_bins || lp.w_out != vc.plans[0]->w_out)
+                return fail(INFV_ERR_INVALID, "%s: handle %d's plan for its tail length %d differs from the plan for T = %d in a table "
+                                              "that does not depend on the chunk length (read-out weights, sticky histogram, uniform "
+                                              "resampling): were they built for one (num_basis, tau, nb_samples)?", name, v, t, vc.T);
+            vc.ragged = true;
+        }
+    }
     if (vc.new_doc)
         for (int v = 0; v < V; ++v) infv_ltm_reset(hs[v]);
     vc.chunk_k = (size_t)vc.T * h0->P * h0->d * token_bytes(h0->tok); vc.chunk_kbar = (size_t)vc.T * h0->d;
@@ -755,27 +804,46 @@ struct MassTraceSlice {
     }
     ~MassTraceSlice() { h->mass_trace = was; h->mass_cap = was_cap; }
 };
+// the handle's draw trace (infv_ltm_set_trace) is indexed by the chunk of the per-handle call: a video's second per-handle call
+// (its short last chunk, infv_ltm_videos_tail) goes on at row `c0`, where the first one stopped
+struct DrawTraceShift {
+    infv_ltm_handle h; int32_t* bins; float* probs; long cap;
+    DrawTraceShift(infv_ltm_handle h_, long c0) : h(h_), bins(h_->trace_bins), probs(h_->trace_probs), cap(h_->trace_cap) {
+        if (c0 <= 0) return;
+        if (bins) h->trace_bins = bins + (size_t)c0 * h->L * h->S;
+        if (probs) h->trace_probs = probs + (size_t)c0 * h->L * h->n_bins;
+        h->trace_cap = cap > c0 ? cap - c0 : 0;
+    }
+    ~DrawTraceShift() { h->trace_bins = bins; h->trace_probs = probs; h->trace_cap = cap; }
+};
 
 int videos_per_video(const VideosCall& vc) {
     infv_ltm_handle h0 = vc.hs[0];
     float* const vmass = h0->vmass_trace;
     const long vcap = h0->vmass_cap;
+    // chunks [c0, c0 + n) of video v, all of T frames, the first of them `frame` frames into the packed k / kbar
+    auto run = [&](int v, int c0, int n, int T, size_t frame) {
+        infv_ltm_handle h = vc.hs[v];
+        const size_t chunk = (size_t)vc.cu[v] + c0;
+        MassTraceSlice tr_(h, vmass ? vmass + chunk * h0->L * h0->N : nullptr, vcap - (long)chunk);
+        DrawTraceShift dt_(h, c0);
+        const double* uv = vc.u ? vc.u + chunk * vc.chunk_u : nullptr;
+        float* cv = vc.ctx + chunk * vc.chunk_ctx;
+        if (vc.tokens)
+            return infv_ltm_consolidate(h, vc.k + frame * (vc.chunk_k / vc.T), n, T, vc.q, vc.Q, vc.proj, uv, 0, cv, vc.stream_);
+        if (vc.q_per_chunk)
+            return infv_ltm_steps(h, vc.kbar + frame * h0->d, n, T, vc.q + chunk * vc.chunk_ctx, vc.Q, vc.proj, uv, cv, vc.stream_);
+        return infv_ltm_consolidate_pooled(h, vc.kbar + frame * h0->d, n, T, vc.q, vc.Q, vc.proj, uv, 0, cv, vc.stream_);
+    };
     for (int v = 0; v < vc.V; ++v) {
         const int n = vc.len(v);
         if (n == 0) continue;
-        MassTraceSlice tr_(vc.hs[v], vmass ? vmass + (size_t)vc.cu[v] * h0->L * h0->N : nullptr, vcap - vc.cu[v]);
-        const double* uv = vc.u ? vc.u + (size_t)vc.cu[v] * vc.chunk_u : nullptr;
-        float* cv = vc.ctx + (size_t)vc.cu[v] * vc.chunk_ctx;
-        int rc;
-        if (vc.tokens)
-            rc = infv_ltm_consolidate(vc.hs[v], vc.k + (size_t)vc.cu[v] * vc.chunk_k, n, vc.T, vc.q, vc.Q, vc.proj, uv, 0, cv, vc.stream_);
-        else if (vc.q_per_chunk)
-            rc = infv_ltm_steps(vc.hs[v], vc.kbar + vc.kbar_base(v) * vc.chunk_kbar, n, vc.T, vc.q + (size_t)vc.cu[v] * vc.chunk_ctx, vc.Q,
-                                vc.proj, uv, cv, vc.stream_);
-        else
-            rc = infv_ltm_consolidate_pooled(vc.hs[v], vc.kbar + vc.kbar_base(v) * vc.chunk_kbar, n, vc.T, vc.q, vc.Q, vc.proj, uv, 0, cv,
-                                             vc.stream_);
-        if (rc) return rc;
+        const size_t frame = vc.ragged ? (size_t)vc.frame0[v] : vc.kbar_base(v) * (size_t)vc.T;
+        const int n_full = vc.short_tail(v) ? n - 1 : n;          // (infv_ltm_videos_tail: the full chunks, then one at the tail length)
+        if (n_full > 0)
+            if (int rc = run(v, 0, n_full, vc.T, frame)) return rc;
+        if (n_full < n)
+            if (int rc = run(v, n_full, 1, vc.tail(v), frame + (size_t)n_full * vc.T)) return rc;
     }
     return INFV_OK;
 }
@@ -808,7 +876,23 @@ int videos_group_table(VideosCall& vc, int g0, int gn, int* g_len) {
     }
     // the table travels in kernel arguments (launch_video_table): no host buffer outlives the call, nothing waits on the host,
     // and a captured graph holds its own copy; the group's launches and the next group's table write follow in stream order
-    HIP_TRY(launch_video_table(vc.hs[0]->vid_tab.as<VideoDesc>(), tab.data(), gn, vc.stream));
+    if (!vc.ragged) {
+        HIP_TRY(launch_video_table(vc.hs[0]->vid_tab.as<VideoDesc>(), tab.data(), gn, vc.stream));
+        return INFV_OK;
+    }
+    // ... and with it, in the same launches, the side table of the stages that depend on the chunk length (VideoTail)
+    std::vector<VideoTail> tails(gn, VideoTail{});
+    for (int j = 0; j < gn; ++j) {
+        const int v = vc.order[j];
+        VideoTail& t = tails[j];
+        t.frame0 = vc.frame0[v];
+        t.len = vc.len(v);
+        t.tail = vc.tail(v);
+        // a short chunk that starts a document (the video's only one, new_doc) takes its plan's first-chunk operator
+        t.op_last = vc.short_tail(v) ? vc.last_plans[v]->device_view(!(vc.new_doc && t.len == 1)) : nullptr;
+    }
+    HIP_TRY(launch_video_tables(vc.hs[0]->vid_tab.as<VideoDesc>(), tab.data(), vc.hs[0]->vid_tail.as<VideoTail>(), tails.data(), gn,
+                                vc.stream));
     return INFV_OK;
 }
 
@@ -822,19 +906,49 @@ int videos_steps(const VideosCall& vc, int g_len) {
     const int N = h0->N, d = h0->d, dm = h0->dm, L = h0->L, S = h0->S, T = vc.T;
     const long q_stride = vc.q_per_chunk ? (long)vc.chunk_ctx : 0;
     int n = (int)vc.order.size();
+    // ragged: the most new rows of any operator at work in step s -- the step's own, and those of the short chunks that end there.
+    // The projected rows of a step are packed with THAT many row slots per video (in whole tiles), not with the call's maximum:
+    // a tile without rows still costs a workgroup, and workgroups that do nothing at a regular stride of the grid leave the
+    // workgroups that do work on few of the XCDs (256 x (7 + tail) at the headline shape, 4 tiles per video of which 3 are empty
+    // in every step but the first: 31.7 ms of projection per call against 12.5 ms with the step's own count).
+    std::vector<int> step_rows;
+    if (vc.ragged) {
+        step_rows.resize(g_len);
+        for (int s = 0; s < g_len; ++s) step_rows[s] = (vc.new_doc && s == 0) ? plan.first.rows : plan.inf.rows;
+        for (int v : vc.order)
+            if (vc.short_tail(v)) {
+                const Plan& lp = *vc.last_plans[v];
+                const int rows = (vc.new_doc && vc.len(v) == 1) ? lp.first.rows : lp.inf.rows;
+                step_rows[vc.len(v) - 1] = std::max(step_rows[vc.len(v) - 1], rows);
+            }
+    }
     for (int s = 0; s < g_len; ++s) {
         while (n > 0 && vc.len(vc.order[n - 1]) <= s) --n;
         const bool inf = !(vc.new_doc && s == 0);
         const Operator& op = inf ? plan.inf : plan.first;
         const VideoStep vs{h0->vid_tab.as<VideoDesc>(), s, n, vc.mask_step()};
+        // ragged (infv_ltm_videos_tail with a short last chunk somewhere): the three stages that depend on the chunk length take it,
+        // and the operator, per video rank; `op` is then the operator of the step's full chunks.  Every video of a call starts at
+        // step 0, so "first chunk of a document" stays a property of the step.
+        const TailStep ts{h0->vid_tail.as<VideoTail>(), T};
+        const int row_slots = vc.ragged ? tail_row_slots(step_rows[s]) : 0;
+        const int32_t* idx_shared = (inf && !vc.sticky) ? plan.uniform_idx.as<int32_t>() : nullptr;
         {
             Timed t_(h0->prof, INFV_KERNEL_POOL, stream);
-            if (vc.tokens) HIP_TRY(launch_pool_videos(vc.k, h0->tok, vs, T, h0->P, d, h0->vid_kbar.as<float>(), stream));
+            if (vc.ragged) {
+                if (vc.tokens) HIP_TRY(launch_pool_videos_tail(vc.k, h0->tok, vs, ts, h0->P, d, h0->vid_kbar.as<float>(), stream));
+                else HIP_TRY(launch_gather_videos_tail(vc.kbar, vs, ts, d, h0->vid_kbar.as<float>(), stream));
+            }
+            else if (vc.tokens) HIP_TRY(launch_pool_videos(vc.k, h0->tok, vs, T, h0->P, d, h0->vid_kbar.as<float>(), stream));
             else HIP_TRY(launch_gather_videos(vc.kbar, vs, T, d, h0->vid_kbar.as<float>(), stream));
         }
         {
             Timed t_(h0->prof, INFV_KERNEL_PROJECT, stream);
-            HIP_TRY(launch_project_videos(h0->vid_kbar.as<float>(), n, T, d, dm, L, op.view(), vc.pp, h0->vid_P.as<float>(), stream));
+            if (vc.ragged)
+                HIP_TRY(launch_project_videos_tail(h0->vid_kbar.as<float>(), vs, ts, d, dm, L, op.view(), row_slots, vc.pp,
+                                                   h0->vid_P.as<float>(), stream));
+            else
+                HIP_TRY(launch_project_videos(h0->vid_kbar.as<float>(), n, T, d, dm, L, op.view(), vc.pp, h0->vid_P.as<float>(), stream));
         }
         if (inf && vc.sticky) {
             Timed t_(h0->prof, INFV_KERNEL_DRAW, stream);
@@ -842,8 +956,12 @@ int videos_steps(const VideosCall& vc, int g_len) {
         }
         {
             Timed t_(h0->prof, INFV_KERNEL_UPDATE, stream);
-            HIP_TRY(launch_update_videos(vs, op.view(), N, T, d, dm, L, S, (inf && !vc.sticky) ? plan.uniform_idx.as<int32_t>() : nullptr,
-                                         h0->vid_kbar.as<float>(), h0->vid_P.as<float>(), stream));
+            if (vc.ragged)
+                HIP_TRY(launch_update_videos_tail(vs, ts, op.view(), row_slots, N, d, dm, L, S, idx_shared, h0->vid_kbar.as<float>(),
+                                                  h0->vid_P.as<float>(), stream));
+            else
+                HIP_TRY(launch_update_videos(vs, op.view(), N, T, d, dm, L, S, idx_shared, h0->vid_kbar.as<float>(), h0->vid_P.as<float>(),
+                                             stream));
         }
         {
             Timed t_(h0->prof, INFV_KERNEL_ATTEND, stream);
@@ -863,7 +981,7 @@ void videos_bookkeeping(const VideosCall& vc) {
         const int len = vc.len(v);
         if (len == 0) continue;
         h->mem.memory_written(len);
-        h->mem.attended(vc.plans[v], vc.Q, vc.parts, len);
+        h->mem.attended(vc.last_plan(v), vc.Q, vc.parts, len);
         if (vc.sticky && len > vc.mask_step()) { h->override_mask = 0; h->forced_mask = 0; }
     }
 }
@@ -876,18 +994,28 @@ int videos_impl(VideosCall& vc) {
     infv_ltm_handle h0 = vc.hs[0];
     const Plan& plan = *vc.plans[0];
     const int V = vc.V;
-    if (!videos_supported(h0->N, h0->d, h0->dm, h0->L, h0->S) || plan.dense.on) return videos_per_video(vc);
+    bool dense = plan.dense.on;
+    vc.rows_max = plan.first.rows > plan.inf.rows ? plan.first.rows : plan.inf.rows;
+    if (vc.ragged)
+        for (int v = 0; v < V; ++v) {
+            const Plan& lp = *vc.last_plans[v];
+            dense = dense || lp.dense.on;                        // (whether the boxes overlap at a sample position depends on T too)
+            vc.rows_max = std::max(vc.rows_max, std::max(lp.first.rows, lp.inf.rows));
+        }
+    if (!videos_supported(h0->N, h0->d, h0->dm, h0->L, h0->S) || dense) return videos_per_video(vc);
     vc.stream = static_cast<hipStream_t>(vc.stream_);
     vc.pp = make_proj(vc.proj, h0->L);
     for (int v = 0; v < V; ++v)                    // the per-call step re-derives a stale K' half before stepping (infv_ltm_step)
         if (vc.len(v) > 0 && vc.hs[v]->mem.k_stale() && vc.hs[v]->mem.has_memory())
             if (int rc = infv_ltm_reproject(vc.hs[v], vc.proj, vc.stream_)) return rc;
-    const int rows_max = plan.first.rows > plan.inf.rows ? plan.first.rows : plan.inf.rows;
+    // row slots per video of the projected rows: the plan's most rows; ragged, the most of any plan involved, in whole 64-row tiles
+    const int row_slots = vc.ragged ? tail_row_slots(vc.rows_max) : (vc.rows_max > 0 ? vc.rows_max : 1);
     const int group = V < kVideoGroup ? V : kVideoGroup;
     // workspaces of one step (grown, never shrunk; released with the lead handle)
     HIP_TRY(reserve_all({{h0->vid_tab, (size_t)group * sizeof(VideoDesc)},
+                         {h0->vid_tail, vc.ragged ? (size_t)group * sizeof(VideoTail) : 0},
                          {h0->vid_kbar, (size_t)group * vc.T * h0->d * sizeof(float)},
-                         {h0->vid_P, (size_t)group * (rows_max > 0 ? rows_max : 1) * h0->L * 2 * h0->dm * sizeof(float)}}));
+                         {h0->vid_P, (size_t)group * row_slots * h0->L * 2 * h0->dm * sizeof(float)}}));
     vc.parts = attend_parts(vc.Q, h0->H, h0->N);
     for (int g0 = 0; g0 < V; g0 += group) {
         int g_len = 0;
@@ -926,6 +1054,19 @@ int infv_ltm_steps_videos_from(const infv_ltm_handle* hs, int32_t V, const int32
     VideosCall vc{};
     vc.name = "steps_videos_from"; vc.hs = hs; vc.V = V; vc.cu = cu; vc.kbar = kbar; vc.kbar_chunk0 = kbar_chunk0; vc.q_per_chunk = q_per_chunk != 0;
     vc.T = T; vc.q = q; vc.Q = Q; vc.proj = proj; vc.u = u; vc.new_doc = new_doc; vc.ctx = ctx; vc.stream_ = stream;
+    return videos_impl(vc);
+}
+
+int infv_ltm_videos_tail(const infv_ltm_videos_tail_desc* d) {
+    if (!d) return fail(INFV_ERR_INVALID, "videos_tail: null descriptor");
+    if (!d->tail_T) return fail(INFV_ERR_INVALID, "videos_tail: null tail_T");
+    if ((d->k != nullptr) == (d->kbar != nullptr)) return fail(INFV_ERR_INVALID, "videos_tail: exactly one of k (frame tokens) and kbar (frame means) must be given");
+    if (d->q_per_chunk != 0 && d->q_per_chunk != 1) return fail(INFV_ERR_INVALID, "videos_tail: q_per_chunk must be 0 or 1");
+    if (d->reserved != 0) return fail(INFV_ERR_INVALID, "videos_tail: reserved must be 0");
+    VideosCall vc{};
+    vc.name = "videos_tail"; vc.hs = d->hs; vc.V = d->V; vc.cu = d->cu; vc.tail_T = d->tail_T;
+    vc.tokens = d->k != nullptr; vc.k = static_cast<const char*>(d->k); vc.kbar = d->kbar; vc.q_per_chunk = d->q_per_chunk != 0;
+    vc.T = d->T; vc.q = d->q; vc.Q = d->Q; vc.proj = d->proj; vc.u = d->u; vc.new_doc = d->new_doc; vc.ctx = d->ctx; vc.stream_ = d->hip_stream;
     return videos_impl(vc);
 }
 

@@ -60,6 +60,12 @@ struct Plan {
     int n_bins = 0;
     bool points_ok = false;            // the histogram edges are the bins' left edges (what chain_batch3_kernel assumes)
     uint64_t digest = 0;               // FNV-1a of every table infv_ltm_set_plan received (infv_ltm_consolidate_videos: same plan on every handle)
+    // FNV-1a of the tables that do not depend on T for one (num_basis, tau, nb_samples) -- read-out weights, sticky histogram,
+    // uniform resampling table: infv_ltm_videos_tail draws and attends every video of a step with ONE copy of them, whatever
+    // the length of its chunk, and refuses handles whose plans disagree here
+    uint64_t shared_digest = 0;
+    DeviceBuf views;                   // OperatorView[2] on the device: {first.view(), inf.view()} (VideoTail.op_last points here)
+    const OperatorView* device_view(bool inf_op) const { return views.as<OperatorView>() + (inf_op ? 1 : 0); }
     StickyView sticky() const {
         StickyView s;
         s.points_ok = points_ok ? 1 : 0;
@@ -187,6 +193,7 @@ struct infv_ltm_s {
     bool ctx_sum_on = false;
     infv::DeviceBuf ctx_sum;           // [L][Q][dm]
     infv::DeviceBuf vid_tab, vid_kbar, vid_P;   // infv_ltm_consolidate_videos with this handle first: video table, pooled frames and projected rows of one step
+    infv::DeviceBuf vid_tail;          // infv_ltm_videos_tail with this handle first: the side table beside vid_tab (VideoTail per rank)
     int n_bins = 128;
     // device rng (infv_ltm_set_rng): with it on, a NULL u is generated by the kernels (philox.h), at position mem.pos()
     bool rng_on = false; uint64_t rng_seed = 0; uint32_t rng_stream = 0;

@@ -379,4 +379,35 @@ hipError_t launch_attend_videos(const VideoStep& vs, const float* q, long q_stri
 // [L][rows][N] the attend launch of this step left in vd[j].scores (ltm_density.hip: box_mass_kernel<true>'s arithmetic)
 hipError_t launch_box_mass_videos(const VideoStep& vs, int rows, int N, int n_layers, const float* w, float w_out, float* mass_all,
                                   long cap, hipStream_t stream);
+
+// ---- a short last chunk per video (infv_ltm_videos_tail; ltm_videos_tail.hip) ----
+// Beside VideoDesc, which does not grow: what rank j of the table needs where its last chunk holds fewer than T frames.  The
+// packed k / kbar of such a call are laid out by FRAME; u, q and ctx stay packed by chunk (VideoDesc.chunk0).
+struct VideoTail {
+    long long frame0;                 // first frame of the video in the packed k / kbar
+    const OperatorView* op_last;      // DEVICE: operator of its last chunk (Plan::views of the plan for `tail`), nullptr: a full chunk
+    int32_t len;                      // chunks of the video in this call
+    int32_t tail;                     // frames of the last one (T: full)
+};
+// the three stages of a lockstep step that depend on the chunk length read video rank j's frames and operator of step s here
+struct TailStep {
+    const VideoTail* vt;              // device table, rank-indexed like VideoStep.vd
+    int T;                            // frames of a full chunk (= frame stride of the kbar workspace slots)
+};
+// vd_dst[0, n) = descs, vt_dst[0, n) = tails: launch_video_table's launches (kVideoTableChunk ranks each), carrying both tables
+hipError_t launch_video_tables(VideoDesc* vd_dst, const VideoDesc* descs, VideoTail* vt_dst, const VideoTail* tails, int n,
+                               hipStream_t stream);
+// row slots per video of the projected-row workspace: rows_max rounded up to the projection's 64-row tile, so that no tile
+// holds rows of two videos (two operators)
+inline int tail_row_slots(int rows_max) { return ((rows_max > 0 ? rows_max : 1) + 63) / 64 * 64; }
+// launch_pool_videos / launch_gather_videos / launch_project_videos / launch_update_videos with the frames of video rank j's
+// chunk and its operator taken per rank: those of `ts` where step vs.s is the video's last, else T frames and `op_full`
+hipError_t launch_pool_videos_tail(const void* k, tok_code tok, const VideoStep& vs, const TailStep& ts, int P, int d, float* kbar,
+                                   hipStream_t stream);
+hipError_t launch_gather_videos_tail(const float* kbar, const VideoStep& vs, const TailStep& ts, int d, float* out, hipStream_t stream);
+hipError_t launch_project_videos_tail(const float* kbar, const VideoStep& vs, const TailStep& ts, int d, int dm, int n_layers,
+                                      const OperatorView& op_full, int row_slots, const ProjPtrs& proj, float* Pnew, hipStream_t stream);
+hipError_t launch_update_videos_tail(const VideoStep& vs, const TailStep& ts, const OperatorView& op_full, int row_slots, int N, int d,
+                                     int dm, int n_layers, int S, const int32_t* idx_shared, const float* kbar, const float* Pnew,
+                                     hipStream_t stream);
 }  // namespace infv

@@ -1848,3 +1848,7 @@ hipError_t launch_pack_memory(const PackMemoryArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 }  // namespace infv
+
+// the lockstep stages with a per-video chunk length (infv_ltm_videos_tail): kernels over this file's __device__ bodies
+#define INFV_LTM_KERNELS_UNIT
+#include "ltm_videos_tail.hip"

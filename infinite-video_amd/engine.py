@@ -850,6 +850,111 @@ def steps_videos(engines: Sequence[LTMEngine], kbar, chunk_counts, q: torch.Tens
     return out
 
 
+def split_frames(frame_counts, T: int):
+    """How ``torch.split(video, T, dim=1)`` cuts videos of ``frame_counts`` frames: ``(chunk_counts, tails, cu, frame0)`` -- video v
+    has ``ceil(F_v / T)`` chunks, the last of ``tails[v]`` frames (T: full; 0 for a video without frames); ``cu`` [V+1] int32 is the
+    running sum of the chunk counts (where u, ctx and per-chunk queries sit) and ``frame0`` [V+1] int64 that of the frame counts
+    (where k / kbar sit).  A last chunk of ONE frame has an empty operator in the reference (LTM.py:79-82): ``ValueError``."""
+    if isinstance(frame_counts, torch.Tensor):
+        frame_counts = frame_counts.tolist()
+    frames = [int(f) for f in frame_counts]
+    T = int(T)
+    if T < 2:
+        raise ValueError(f"T must be at least 2, got {T}")
+    counts, tails = [], []
+    for v, f in enumerate(frames):
+        if f < 0:
+            raise ValueError(f"frame_counts[{v}] = {f} is negative")
+        if f % T == 1:
+            raise ValueError(f"video {v} has {f} frames: its last chunk would hold one frame (T = {T}), which the reference cannot step")
+        counts.append(-(-f // T))
+        tails.append(0 if f == 0 else f - (counts[-1] - 1) * T)
+    cu = np.zeros(len(frames) + 1, np.int32)
+    cu[1:] = np.cumsum(counts)
+    frame0 = np.zeros(len(frames) + 1, np.int64)
+    frame0[1:] = np.cumsum(frames)
+    return counts, tails, cu, frame0
+
+
+def _videos_tail(what: str, engines, x, tokens: bool, frame_counts, T: int, q: torch.Tensor, projs, u, new_doc: bool):
+    """infv_ltm_videos_tail over frame tokens (``tokens``) or frame means, ``x`` packed by frame."""
+    if isinstance(x, (list, tuple)):
+        if frame_counts is None:
+            frame_counts = [int(t.shape[0]) for t in x]
+        x = torch.cat(list(x)) if len(x) else x
+    counts, tails, cu, frame0 = split_frames(frame_counts, T)
+    engines, cu = _video_engines(engines, counts, what)
+    if isinstance(u, (list, tuple)):
+        u = torch.cat(list(u))
+    V, e0 = len(engines), engines[0]
+    total, n_frames = int(cu[-1]), int(frame0[-1])
+    if tokens:
+        if token_code(x.dtype) is None:
+            raise TypeError(f"frame tokens must be float32, float16, bfloat16 or float8_e4m3fn, got {x.dtype}")
+        if x.dtype == torch.float16 and not all(e.fp16_tokens for e in engines):
+            raise TypeError("float16 frame tokens need engines created with fp16_tokens=True")
+        _check_dev(x, e0.device, "k", x.dtype)
+        if x.dim() != 3 or tuple(x.shape) != (n_frames, e0.P, e0.d):
+            raise ValueError(f"k must be [{n_frames}, {e0.P}, {e0.d}] (packed by frame), got {tuple(x.shape)}")
+    else:
+        _check_dev(x, e0.device, "kbar")
+        if x.dim() != 2 or tuple(x.shape) != (n_frames, e0.d):
+            raise ValueError(f"kbar must be fp32 [{n_frames}, {e0.d}] (packed by frame), got {tuple(x.shape)}")
+        if x.data_ptr() % 16:
+            raise ValueError("kbar must start at a 16-byte boundary (the frames are copied as float4)")
+    if q.dim() == 4 and not tokens:
+        _check_dev(q, e0.device, "q")
+        if q.shape[0] != total or q.shape[1] != e0.L or q.shape[3] != e0.dm or q.shape[2] > e0.max_q:
+            raise ValueError(f"q must be [{e0.L}, Q, {e0.dm}] or [{total}, {e0.L}, Q <= {e0.max_q}, {e0.dm}], got {tuple(q.shape)}")
+        Q, per_chunk = int(q.shape[2]), 1
+    else:
+        Q, per_chunk = e0._check_q(q), 0
+    e0._check_u(u, (total,))
+    for v, e in enumerate(engines):
+        if tokens:
+            x = e._tokens(x)
+        e.ensure_plan(T)
+        if counts[v] and tails[v] != T:
+            e.ensure_plan(tails[v])
+        if not per_chunk:
+            e._check_q(q)
+    proj_arr = e0._proj_array(projs)
+    out = torch.empty(total, e0.L, Q, e0.dm, device=e0.device, dtype=torch.float32)
+    hs = (C.c_void_p * V)(*[e._h.value for e in engines])
+    tail_T = _np_i32(tails)
+    desc = _lib.VideosTailDesc(hs=C.cast(hs, C.c_void_p), V=V, T=int(T), cu=cu.ctypes.data, tail_T=tail_T.ctypes.data,
+                               k=_ptr(x) if tokens else None, kbar=None if tokens else _ptr(x), q=_ptr(q), q_per_chunk=per_chunk, Q=Q,
+                               proj=C.cast(proj_arr, C.c_void_p), u=_ptr(u), new_doc=int(new_doc), reserved=0, ctx=_ptr(out),
+                               hip_stream=_stream(e0.device))
+    with torch.cuda.device(e0.device):
+        _lib.check(e0.lib.infv_ltm_videos_tail(C.byref(desc)))
+    return out, cu
+
+
+def consolidate_videos_frames(engines: Sequence[LTMEngine], k, frame_counts, T: int, q: torch.Tensor, projs: Sequence[ProjTensors],
+                              u=None, new_doc: bool = True):
+    """``consolidate_videos`` for videos cut the way the reference cuts them, ``torch.split(video, T, dim=1)``: video v has
+    ``frame_counts[v]`` frames, ``ceil(F_v / T)`` chunks, and a last chunk of ``F_v - (C_v - 1) * T`` frames that steps with the
+    plan for its own length (infv_ltm_videos_tail) -- in the same launches as everybody else's chunk of that step.
+
+    ``k`` is PACKED BY FRAME, [sum F_v, P, d] (any token dtype ``consolidate_videos`` takes), or a list of per-video [F_v, P, d]
+    tensors (packed with one copy; ``frame_counts`` may then be None).  ``u`` [sum C_v, L, S] and the result stay packed by CHUNK.
+    ``q`` [L, Q, dm] and ``projs`` are shared.  A video with ``F_v % T == 1`` raises ``ValueError``: a chunk of one frame has an
+    empty operator.  Returns ``(ctx [sum C_v, L, Q, dm], cu)`` with ``cu`` the int32 running sum of the chunk counts.  Per video
+    the bits are those of ``consolidate_videos`` on its full chunks followed by ``consolidate_videos(new_doc=False)`` on its last
+    chunk at that chunk's length; ``trace_videos`` over the chunk counts records the call like any lockstep call."""
+    return _videos_tail("consolidate_videos_frames", engines, k, True, frame_counts, T, q, projs, u, new_doc)
+
+
+def steps_videos_frames(engines: Sequence[LTMEngine], kbar, frame_counts, T: int, q: torch.Tensor, projs: Sequence[ProjTensors],
+                        u=None, new_doc: bool = True):
+    """``consolidate_videos_frames`` from frame means, with an optional query per chunk: ``kbar`` is PACKED BY FRAME
+    [sum F_v, d] fp32 (or a list of per-video [F_v, d] tensors), ``q`` [L, Q, dm] or [sum C_v, L, Q, dm] as ``steps_videos`` takes
+    it.  Returns ``(ctx, cu)``.  Per video the bits are those of ``steps_videos`` on its full chunks followed by
+    ``steps_videos(new_doc=False)`` on its last chunk; with a shared query and kbar = pool(k), those of the token form."""
+    return _videos_tail("steps_videos_frames", engines, kbar, False, frame_counts, T, q, projs, u, new_doc)
+
+
 class VideosTrace:
     """The packed traces of the lockstep calls, as ``trace_videos`` armed them: ``bins`` [total, L, S] int32 (-1 where nothing
     drew: a video's first chunk), ``probs`` [total, L, 128] and ``mass`` [total, L, N] fp32 (NaN where nothing wrote; ``None``
